@@ -14,7 +14,12 @@ resident in HBM is measured in short extra legs and reported under other keys, n
 Frames are independent, so ranks shard them with no data-path collective (weak scaling: per-GPU work is
 fixed); the only exchange is the final gather of the per-frame results over RCCL.
 
-Rank 0 prints ONE JSON line carrying, besides the contract's keys:
+A plain run does only what the headline needs: it makes the frames, warms up, times the `--steps` steps and prints
+ONE JSON line (rank 0) with `metric`, `value`, `unit`, `higher_is_better`, `dtype` and `ms_per_step` (wall ms of one
+timed step).  `--dump-outputs DIR` then also writes what the last timed step handed its caller, as .npy files (see
+dump_outputs); the frames are seeded, so two runs with the same arguments see the same inputs.
+
+`--full` adds every other measurement, each outside the timed region.  Its line carries, besides the headline keys:
   roofline     — the fused filter kernel (HBM-bound): algorithmic 18 B/px over the
                  kernel's mean duration, measured with HIP events on the library's own stream; and the
                  same with the bytes the kernel really moves (PMC pass under profiles/);
@@ -31,7 +36,10 @@ Rank 0 prints ONE JSON line carrying, besides the contract's keys:
   roofline_ransac — 15 flop per (hypothesis, line) x line evaluations per second against the fp32 vector peak;
   roofline_8k  — the filter kernel on 8192x8192 frames (1.2 GB of algorithmic traffic per launch: nothing of it
                  fits the 256 MiB Infinity Cache);
-  cht          — the diamond-space estimator (lr_estimate_line_pencils_cht): ms per grouping call and votes per second.
+  cht          — the diamond-space estimator (lr_estimate_line_pencils_cht): ms per grouping call and votes per second;
+  stage_ms_per_frame — device ms per stage, from two extra steps with the stage timers on;
+  other_rates_Mpix_per_s — the same workload from the other kinds of memory.
+`--no-extra-legs` and `--no-cpu-baseline` leave parts of that out again; `--roofline-only` runs the roofline leg alone.
 
 `--config batch1080` makes that last workload the timed one (512 frames over N ranks, "scaling": "strong").
 
@@ -522,6 +530,34 @@ def roofline_8k(L, ctx, torch, dev, base):
             "frac_moved_bytes": round(traffic / (k * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if traffic else None}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+SEGMENT_FIELDS = ("x1", "y1", "x2", "y2", "weight", "err", "group_id")
+
+
+def dump_outputs(path, out, n_lines, tforms, suffix=""):
+    """What the batch call of the last timed step handed its caller, as .npy files in `path`:
+      segments.npy           float32 [rows, 7]: x1, y1, x2, y2, weight, err, group_id, the frames' rows one after the other
+      segments_per_frame.npy float64 [frames]
+      transforms.npy         float32 [frames, 6, 3]: each frame's rectification transform (ImageTransform.as_array)
+    If the segments would take the files past 64 MB in all, a fixed sample of their rows (seed 0, in row order) is written
+    instead, with the sampled row numbers in segment_rows.npy.  `suffix` tells ranks apart."""
+    os.makedirs(path, exist_ok=True)
+    n = np.asarray(n_lines, np.int64)
+    rows = np.concatenate([out[b][: n[b]] for b in range(len(n))]) if len(n) else out[:0, 0]
+    seg = np.stack([rows[k].astype(np.float32) for k in SEGMENT_FIELDS], axis=1)
+    arrays = {"segments_per_frame": n.astype(np.float64), "transforms": np.asarray(tforms, np.float32)}
+    budget = DUMP_LIMIT_BYTES - sum(a.nbytes for a in arrays.values())
+    if seg.nbytes > budget:
+        keep = budget // (seg.shape[1] * 4 + 8)
+        idx = np.sort(np.random.default_rng(0).choice(len(seg), keep, replace=False))
+        arrays["segment_rows"] = idx.astype(np.float64)
+        seg = seg[idx]
+    arrays["segments"] = seg
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + suffix + ".npy"), a)
+    return sorted(arrays)
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     ap = argparse.ArgumentParser()
@@ -538,6 +574,11 @@ def main(argv=None):
     ap.add_argument("--host-memory", choices=["pageable", "pinned", "device"], default="pageable",
                     help="where the timed region's frames live (the other kind and the device-resident rate are extra legs); "
                          "'device' = already in HBM: a diagnostic, NOT the metric (the line's workload says so)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every other measurement: stage times, the other kinds of memory, the 1080p batch, "
+                         "the roofline legs, RANSAC / CHT rates, single-frame and worst-case latencies, the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (segments, counts, transforms) as .npy files into DIR")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-gather", action="store_true", help="with a process group: leave the gather of the results out of the steps (what a process "
                     "group costs by being there, apart from what the gather costs)")
@@ -565,6 +606,8 @@ def main(argv=None):
                     help="host cores of a rank (its lanes, uploader, staging threads; its frames are first touched there): the cores of "
                          "its GPU's NUMA node, of another node (experiment: copies and DMA on different memory controllers), or no binding")
     args = ap.parse_args(argv)
+    if args.dump_outputs and (args.steps < 1 or args.roofline_only):
+        ap.error("--dump-outputs needs at least one timed step")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and (args.gpus > 1 or args.rehearse_collective):
@@ -743,6 +786,7 @@ def main(argv=None):
     if args.roofline_only:
         args.steps = args.warmup = 0
         args.no_cpu_baseline = args.no_extra_legs = True
+        args.full = True  # (the roofline leg is one of --full's)
     for _ in range(args.warmup):
         wl.step(kind, n_total)
     filt_ms = []
@@ -788,9 +832,11 @@ def main(argv=None):
         pump["thread"].join()
         sys.stderr.write("dma pump %s: %.1f GB/s beside the timed steps\n" % (args.dma_pump, pump["bytes"] / pump["t"] / 1e9))
     segs = float(np.mean(wl.n_lines[: max(wl.B, 1)]))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, wl.out[: wl.B], wl.n_lines[: wl.B], wl.tforms[: wl.B], "_rank%d" % rank if world > 1 else "")
     # stage times of frames inside the pipeline: two extra steps with the stage timers on (they cost the frame seven event
     # records, some 40 us of idle GPU: not inside the timed region)
-    if args.steps > 0 and not args.roofline_only:
+    if args.full and args.steps > 0 and not args.roofline_only:
         ctx.set_stage_timing(True)
         for _ in range(2):
             wl.step(kind, n_total)
@@ -801,7 +847,7 @@ def main(argv=None):
 
     # ---- extra legs (outside the timed region; each bracketed like it) ------------------------------------------
     extra = {}
-    if not args.no_extra_legs:
+    if args.full and not args.no_extra_legs:
         legs = [k for k in ("pageable", "pinned", "device") if k != kind and (k != "device" or wl.want_device)]
         for k in legs:
             if k == "pinned":
@@ -843,7 +889,7 @@ def main(argv=None):
     # records around the launch
     iso = []
     rw, rh = (W4K, H4K) if args.config == "batch1080" else (wl.w, wl.h)
-    if rank == 0:
+    if rank == 0 and args.full:
         nroof = 32
         wl.d = None
         torch.cuda.empty_cache()
@@ -886,6 +932,7 @@ def main(argv=None):
             "vs_baseline": None,
             "dtype": "f32",
             "data": "synthetic",
+            "full": args.full,
             "config": {
                 "workload": ("%dx%d frames in %s HOST memory -> find_line_segment_groups + compute_rectification_transform per frame "
                              "(lr_find_line_segment_groups_batch_host): H2D of every frame and D2H of its results are inside the timed "
@@ -926,7 +973,7 @@ def main(argv=None):
                 "host_pageable_256_frames_per_call": extra.get("pageable_256_per_call"),
             },
             "config4_batch1080": extra.get("config4_batch1080"),
-            "roofline": {
+            "roofline": None if not iso else {
                 "bound": "hbm",
                 "kernel": "filter_lanes_kernel (row-streaming fused 5x5 derivative + magnitude + bin + dilated mask + NMS candidates)",
                 "achieved": round(achieved, 2),
@@ -946,14 +993,14 @@ def main(argv=None):
                 "algorithmic_bytes_per_launch": ALGO_BYTES_PER_PX * rw * rh,
                 "frame": "%dx%d" % (rw, rh),
             },
-            "stage_ms_per_frame": {
+            "stage_ms_per_frame": None if not filt_ms else {
                 k: round(float(stage_acc[i]) / nfr, 4)
                 for k, i in [("filter", L.T_FILTER), ("seeds", L.T_SEEDS), ("flood", L.T_FLOOD), ("fit", L.T_FIT), ("ransac", L.T_RANSAC), ("total_device", L.T_TOTAL)]
             },
         }
         res["ranks_seen"] = ranks_seen
         res["host_cores_per_rank"] = {"count": len(cpus), "how": cpus_how, "staging_threads": args.staging_threads}
-        if not args.no_extra_legs:
+        if args.full and not args.no_extra_legs:
             rr = ransac_rates(ctx)
             res["ransac_hypotheses_per_s"] = rr
             res["roofline_ransac"] = {
@@ -972,7 +1019,7 @@ def main(argv=None):
                 res["natural_frame"] = natural_frame_rates(L, ctx)
                 res["worst_case"] = worst_case_rates(L, ctx, with_cpu=not args.no_cpu_baseline)
             res["roofline_8k"] = roofline_8k(L, ctx, torch, dev, wl.pageable[0] if wl.B and (wl.w, wl.h) == (W4K, H4K) else None)
-        if not args.no_cpu_baseline and n_gpus == 1 and wl.B:
+        if args.full and not args.no_cpu_baseline and n_gpus == 1 and wl.B:
             res["cpu_baseline"] = cpu_baseline(wl.pageable[:2], w, h, wl.min_length)
         else:
             res["cpu_baseline"] = None

@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
 
@@ -100,3 +102,59 @@ def test_a_single_rank_may_be_bound_to_its_gpus_numa_node_or_to_another():
     assert cpus == node0 and how.startswith("numa node 0")
     assert bench.rank_cpus(0, 1, None, avail, nodes=[0], numa="none") == (avail, "all")
     assert bench.rank_cpus(0, 1, None, avail, nodes=[-1]) == (avail, "all")
+
+
+def _records(n_lines, cap, seed):
+    sys.path.insert(0, ROOT)
+    import bench
+
+    rng = np.random.default_rng(seed)
+    out = np.zeros((len(n_lines), cap), [(k, "<i4" if k == "group_id" else "<f4") for k in bench.SEGMENT_FIELDS])
+    for k in bench.SEGMENT_FIELDS:
+        out[k] = rng.integers(-1, 4, out.shape) if k == "group_id" else rng.random(out.shape, dtype="float32")
+    return bench, out
+
+
+def test_dump_outputs_writes_what_the_batch_call_returned(tmp_path):
+    """--dump-outputs: the frames' segment rows one after the other (float32, group_id exact), the counts (float64) and the
+    transforms (float32 [frames, 6, 3])."""
+    n = np.array([3, 0, 5], np.int32)
+    bench, out = _records(n, 8, 1)
+    tf = np.arange(3 * 18, dtype=np.float32).reshape(3, 6, 3)
+    names = bench.dump_outputs(str(tmp_path / "d"), out, n, tf)
+    assert names == ["segments", "segments_per_frame", "transforms"]
+    seg = np.load(str(tmp_path / "d" / "segments.npy"))
+    assert seg.dtype == np.float32 and seg.shape == (8, 7)
+    want = np.concatenate([out[0][:3], out[2][:5]])
+    for j, k in enumerate(bench.SEGMENT_FIELDS):
+        assert (seg[:, j] == want[k].astype(np.float32)).all()
+    cnt = np.load(str(tmp_path / "d" / "segments_per_frame.npy"))
+    assert cnt.dtype == np.float64 and cnt.tolist() == [3.0, 0.0, 5.0]
+    got_tf = np.load(str(tmp_path / "d" / "transforms.npy"))
+    assert got_tf.dtype == np.float32 and (got_tf == tf).all()
+
+
+def test_dump_outputs_samples_rows_beyond_the_size_limit(tmp_path, monkeypatch):
+    """Past the limit the segments become a fixed sample (seed 0, in row order) and their row numbers are written too:
+    two dumps of the same outputs are the same files."""
+    n = np.array([400, 400], np.int32)
+    bench, out = _records(n, 400, 2)
+    tf = np.zeros((2, 6, 3), np.float32)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 10000)
+    for d in ("a", "b"):
+        assert "segment_rows" in bench.dump_outputs(str(tmp_path / d), out, n, tf)
+    total = sum(os.path.getsize(str(p)) - 128 for p in (tmp_path / "a").iterdir())  # (less each file's .npy header)
+    assert total <= 10000
+    rows = np.load(str(tmp_path / "a" / "segment_rows.npy"))
+    seg = np.load(str(tmp_path / "a" / "segments.npy"))
+    assert len(rows) == len(seg) > 0 and (np.diff(rows) > 0).all()
+    flat = np.concatenate([out[0], out[1]])
+    assert (seg[:, 0] == flat["x1"][rows.astype(np.int64)]).all()
+    for name in ("segments", "segment_rows"):
+        assert (np.load(str(tmp_path / "a" / (name + ".npy"))) == np.load(str(tmp_path / "b" / (name + ".npy")))).all()
+
+
+def test_dump_outputs_needs_a_timed_step():
+    for extra in (["--steps", "0"], ["--roofline-only"]):
+        p = _run(["--gpus", "1", "--dump-outputs", "unused"] + extra)
+        assert p.returncode == 2 and "needs at least one timed step" in p.stderr

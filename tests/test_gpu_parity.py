@@ -508,7 +508,9 @@ def test_workspace_shrinks_after_a_large_frame(L):
 
     from librectify_amd import synth
 
-    hip = C.CDLL("libamdhip64.so")
+    # the HIP runtime the library is bound to, looked up through its own handle: once torch is imported the process may
+    # hold a second copy of the runtime, and the name "libamdhip64.so" can resolve to that one
+    hip = L.lib()
 
     def free_bytes():
         f, t = C.c_size_t(0), C.c_size_t(0)

@@ -4,7 +4,7 @@
 O=${1:-gpurun_out/bks}
 export TMPDIR=/tmp
 mkdir -p $O
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/p -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extra-legs > $O/bench.json 2> /dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/p -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-extra-legs > $O/bench.json 2> /dev/null
 find $O/p -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/kernel_stats.csv; rm -rf $O/p
 python3 - $O <<'PY'
 import csv, json, sys

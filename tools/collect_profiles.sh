@@ -7,8 +7,8 @@ O=gpurun_out/profiles_$R
 export TMPDIR=/tmp
 mkdir -p $O
 if [[ $PART == *a* ]]; then
-python3 bench.py --steps 20 --warmup 5 > $O/${R}_bench.json 2> $O/bench.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/p1 -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extra-legs > $O/${R}_bench_under_rocprof.json 2> /dev/null
+python3 bench.py --full --steps 20 --warmup 5 > $O/${R}_bench.json 2> $O/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/p1 -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-extra-legs > $O/${R}_bench_under_rocprof.json 2> /dev/null
 find $O/p1 -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/${R}_kernel_stats.csv; rm -rf $O/p1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/p2 -- python3 bench.py --roofline-only > $O/${R}_bench_roofline_leg.json 2> /dev/null
 find $O/p2 -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/${R}_kernel_stats_roofline_leg.csv; rm -rf $O/p2

@@ -6,9 +6,9 @@
 export TMPDIR=/tmp
 for mem in pinned device; do
   rm -rf /tmp/dkt_$mem /tmp/dkp_$mem
-  timeout -k 5 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/dkt_$mem -- python3 bench.py --no-extra-legs --no-cpu-baseline --steps 3 --warmup 1 --host-memory $mem > /tmp/dkt_$mem.log 2>&1
+  timeout -k 5 300 rocprofv3 --kernel-trace --output-format csv -d $TMPDIR/dkt_$mem -- python3 bench.py --full --no-extra-legs --no-cpu-baseline --steps 3 --warmup 1 --host-memory $mem > $TMPDIR/dkt_$mem.log 2>&1
   grep -o '"value": [0-9.]*' /tmp/dkt_$mem.log | head -1 | sed "s/^/$mem traced /"
-  timeout -k 5 300 rocprofv3 --pmc GRBM_GUI_ACTIVE --output-format csv -d /tmp/dkp_$mem -- python3 bench.py --no-extra-legs --no-cpu-baseline --steps 2 --warmup 1 --host-memory $mem > /dev/null 2>&1
+  timeout -k 5 300 rocprofv3 --pmc GRBM_GUI_ACTIVE --output-format csv -d $TMPDIR/dkp_$mem -- python3 bench.py --full --no-extra-legs --no-cpu-baseline --steps 2 --warmup 1 --host-memory $mem > /dev/null 2>&1
 done
 python3 - <<'PY'
 import csv,glob,collections,re

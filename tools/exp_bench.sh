@@ -6,7 +6,7 @@ mkdir -p gpurun_out; : > gpurun_out/$out
 for setting in "base" "$@" "base"; do
   if [ "$setting" = "base" ]; then envs=(); else IFS=';' read -ra envs <<< "$setting"; fi
   for rep in 1 2; do
-    v=$(env "${envs[@]}" python3 bench.py --no-cpu-baseline --no-extra-legs "${args[@]}" 2>/dev/null | tail -1 | python3 -c "import json,sys; r=json.loads(sys.stdin.read()); print(r['value'], r['stage_ms_per_frame'])")
+    v=$(env "${envs[@]}" python3 bench.py --full --no-cpu-baseline --no-extra-legs "${args[@]}" 2>/dev/null | tail -1 | python3 -c "import json,sys; r=json.loads(sys.stdin.read()); print(r['value'], r['stage_ms_per_frame'])")
     echo "$setting | $v" >> gpurun_out/$out
   done
 done

@@ -3,7 +3,7 @@
 out=$1; shift; mkdir -p gpurun_out; : > gpurun_out/$out
 for l in "$@"; do
   for rep in 1 2; do
-    v=$(python3 bench.py --no-cpu-baseline --no-extra-legs --steps 10 --warmup 3 --host-memory ${MEM:-device} --streams $l 2>/dev/null | tail -1 | python3 -c "import json,sys; r=json.loads(sys.stdin.read()); print(r['value'], r['stage_ms_per_frame'])")
+    v=$(python3 bench.py --full --no-cpu-baseline --no-extra-legs --steps 10 --warmup 3 --host-memory ${MEM:-device} --streams $l 2>/dev/null | tail -1 | python3 -c "import json,sys; r=json.loads(sys.stdin.read()); print(r['value'], r['stage_ms_per_frame'])")
     echo "lanes $l | $v" >> gpurun_out/$out
   done
 done

@@ -7,7 +7,7 @@ for mem in pinned device; do
   i=0
   for c in "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_LEVEL_sum" "TCC_EA0_RDREQ_DRAM_sum TCC_EA0_RDREQ_DRAM_CREDIT_STALL_sum" "TCC_HIT_sum TCC_MISS_sum"; do
     i=$((i+1)); rm -rf /tmp/pmcd_$i
-    timeout -k 5 300 rocprofv3 --pmc $c --output-format csv -d /tmp/pmcd_$i -- python3 bench.py --no-extra-legs --no-cpu-baseline --steps 2 --warmup 1 --host-memory $mem > /dev/null 2>&1
+    timeout -k 5 300 rocprofv3 --pmc $c --output-format csv -d $TMPDIR/pmcd_$i -- python3 bench.py --full --no-extra-legs --no-cpu-baseline --steps 2 --warmup 1 --host-memory $mem > /dev/null 2>&1
     python3 - $mem $i <<'PY'
 import csv,glob,collections,sys,re
 mem,i=sys.argv[1],sys.argv[2]
