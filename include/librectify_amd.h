@@ -143,13 +143,6 @@ void lr_set_flood_blind_rounds(lr_context* ctx, int rounds);
 /* Comparison hook: the flood's partial commits (a blocked seed commits at once the part of its footprint that no lower
  * seed can reach; on by default, LIBRECTIFY_FLOOD_PARTIAL=0 also switches them off).  Same labels either way. */
 void lr_set_flood_partial_commits(lr_context* ctx, int on);
-/* Opt-in (round 4): the flood's multi-source re-walks.  A seed whose walk covered a hundred tiles or more leaves way-points
- * on its footprint; if it has to walk again, a team of wavefronts starts from the seed and from every way-point at once,
- * beside the round's exploration on a second stream, and keeps what is connected to the seed.  Same labels either way
- * (exact by construction, tested against the oracle); on the bench frames the late rounds get 25 % shorter and the whole
- * flood 2-10 %, frames of regions and of very long bars lose as much, hence off by default.
- * LIBRECTIFY_FLOOD_MULTI=1 turns it on for every new context; lr_stage_counters [10] counts such walks. */
-void lr_set_flood_multi_source(lr_context* ctx, int on);
 /* The flood's later rounds from the logs (kernels_flood.hip: flood_rewalk_kernel): a walk of twelve tiles or more leaves
  * its footprint as (tile, pixels) records, and since a footprint only ever shrinks (filter.cpp:101-153 accepts a pixel on
  * static data and on "not claimed yet"), the seed's next footprint is the connected part around it of those records minus
@@ -226,8 +219,8 @@ int lr_filter_kernel_ms(lr_context* ctx, float* ms);
 /* Extra counters of the last call: [0] seeds, [1] components, [2] flood rounds, [3] labelled pixels, and how the
  * flood's walks were stored: [4] seeds that moved to the second LDS tier, [5] global slabs used, [6] seeds finished by
  * the ordered single-wave tail (storage exhausted); [7] laps of the frame through the pipeline (1 normally); [8] pixels
- * the flood's explorations walked in all rounds together (over [3]: the re-walk factor), [9] their 8x8-tile steps, [10] re-walks that
- * started from several way-points at once (lr_set_flood_multi_source), [11] footprints worked out from a log instead of
+ * the flood's explorations walked in all rounds together (over [3]: the re-walk factor), [9] their 8x8-tile steps, [10] retired (always 0:
+ * it counted the re-walks from way-points, a path the logs replaced), [11] footprints worked out from a log instead of
  * walked (lr_set_flood_logs), [12] those of them that took the fall-back path (sweeps), [13] walks that outgrew the second
  * tier's table and were held back until their seed was the lowest active one (instead of moving into a global slab),
  * [14] giant steps: floods of the lowest active seed labelled by the whole device (lr_set_flood_giant_step), [15] walks that

@@ -70,7 +70,7 @@ EXPORTS = [
     "lr_stage_counters", "lr_filter_kernel_ms", "lr_ransac_best", "lr_estimate_line_pencils",
     "lr_find_line_segment_groups_batch_host", "lr_find_line_segment_groups_batch_host_ptrs", "lr_host_alloc", "lr_host_free",
     "lr_set_seed_capacity", "lr_set_flood_blind_rounds", "lr_set_flood_staged", "lr_set_batch_streams", "lr_device_malloc", "lr_device_free", "lr_memcpy_h2d", "lr_cht_vanishing_point", "lr_refine_lines", "lr_set_estimator", "lr_ht_weights", "lr_prosac_solve", "lr_estimate_line_pencils_prosac", "lr_direct_solve", "lr_estimate_line_pencils_direct",
-    "lr_estimate_line_pencils_cht", "lr_set_stage_timing", "lr_release_thread_context", "lr_set_flood_partial_commits", "lr_set_flood_multi_source", "lr_set_flood_logs", "lr_set_flood_just_in_time", "lr_set_flood_giant_step", "lr_context_trim", "lr_trim_thread_context",
+    "lr_estimate_line_pencils_cht", "lr_set_stage_timing", "lr_release_thread_context", "lr_set_flood_partial_commits", "lr_set_flood_logs", "lr_set_flood_just_in_time", "lr_set_flood_giant_step", "lr_context_trim", "lr_trim_thread_context",
     "lr_find_line_segment_groups_batch_host_multi",
 ]
 
@@ -148,8 +148,6 @@ def lib():
         L.lr_refine_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
         L.lr_set_flood_partial_commits.argtypes = [C.c_void_p, C.c_int]
         L.lr_set_flood_partial_commits.restype = None
-        L.lr_set_flood_multi_source.argtypes = [C.c_void_p, C.c_int]
-        L.lr_set_flood_multi_source.restype = None
         L.lr_set_flood_logs.argtypes = [C.c_void_p, C.c_int]
         L.lr_set_flood_logs.restype = None
         L.lr_set_flood_giant_step.argtypes = [C.c_void_p, C.c_int]
@@ -282,7 +280,7 @@ class Context:
         _check(lib().lr_stage_counters(self._h, _ptr(c), 16))
         return dict(seeds=int(c[0]), components=int(c[1]), flood_rounds=int(c[2]), labelled_px=int(c[3]),
                     second_tier_seeds=int(c[4]), slabs=int(c[5]), ordered_tail_seeds=int(c[6]), frame_laps=int(c[7]),
-                    walked_px=int(c[8]), walk_steps=int(c[9]), multi_source_walks=int(c[10]), log_rewalks=int(c[11]), log_give_ups=int(c[12]), giants_held=int(c[13]), giant_steps=int(c[14]),
+                    walked_px=int(c[8]), walk_steps=int(c[9]), log_rewalks=int(c[11]), log_give_ups=int(c[12]), giants_held=int(c[13]), giant_steps=int(c[14]),
                     quiet_round_misses=int(c[15]))
 
     # ---- full path ----
@@ -411,9 +409,6 @@ class Context:
 
     def set_flood_partial_commits(self, on=True):
         lib().lr_set_flood_partial_commits(self._h, int(bool(on)))
-
-    def set_flood_multi_source(self, on=True):
-        lib().lr_set_flood_multi_source(self._h, int(bool(on)))
 
     def set_flood_just_in_time(self, on=True):
         lib().lr_set_flood_just_in_time(self._h, int(bool(on)))

@@ -336,7 +336,6 @@ void lr_set_seed_capacity(lr_context* ctx, uint32_t cap) { ctx->seed_cap_once = 
 void lr_set_flood_staged(lr_context* ctx, int on) { ctx->flood_staged = on != 0; }
 void lr_set_flood_blind_rounds(lr_context* ctx, int rounds) { ctx->flood_rounds_hint = rounds; }
 void lr_set_flood_partial_commits(lr_context* ctx, int on) { ctx->flood_partial = on != 0; }
-void lr_set_flood_multi_source(lr_context* ctx, int on) { ctx->flood_multi = on != 0; }
 void lr_set_flood_just_in_time(lr_context* ctx, int on) { ctx->flood_jit = on != 0; }
 void lr_set_flood_giant_step(lr_context* ctx, int on) { ctx->flood_giant_step = on != 0; }
 void lr_set_flood_logs(lr_context* ctx, int on) {
@@ -452,7 +451,7 @@ int lr_stage_counters(lr_context* ctx, int64_t* out, int count) {
                                (int64_t)ctx->flood_tiers[2], (int64_t)ctx->frame_laps,
                                (int64_t)(((uint64_t)ctx->flood_tiers[5] << 32) | ctx->flood_tiers[4]),
                                (int64_t)(((uint64_t)ctx->flood_tiers[7] << 32) | ctx->flood_tiers[6]),
-                               (int64_t)ctx->flood_tiers[9], (int64_t)ctx->flood_tiers[10], (int64_t)ctx->flood_tiers[11], (int64_t)ctx->flood_tiers[12],
+                               0 /* [10]: retired */, (int64_t)ctx->flood_tiers[10], (int64_t)ctx->flood_tiers[11], (int64_t)ctx->flood_tiers[12],
                                (int64_t)ctx->flood_tiers[13], (int64_t)ctx->flood_tiers[15]};
         for (int i = 0; i < count && i < 16; ++i) out[i] = v[i];
         return 0;

@@ -110,7 +110,6 @@ int launch_flood_ordered(const float* dx, const float* dy, const uint8_t* dmask,
                          BinTrig trig, uint32_t* label, int32_t* seed_size, int32_t* queue, hipStream_t s);
 
 // parallel-round flood (mode 1): per-seed round state, active lists and overflow slabs
-constexpr size_t kFloodWpWords = 8;      // per seed: header (way-points | tiles of the walk << 8) and seven pixel indices
 constexpr size_t kFloodHandWords = 1024;  // per hand-over: header, up to 192 table entries, up to 128 frontier records
 struct FloodBuffers {
     uint32_t* blocked = nullptr;
@@ -125,26 +124,14 @@ struct FloodBuffers {
     uint8_t* dirty = nullptr;       // one mark per 256 pixels of the label image: stamped in the current round
     uint32_t* big_list = nullptr;   // 8192 seeds: this round's hand-over to the second storage tier
     uint32_t* handover = nullptr;   // ... and the state each of their walks had reached (kFloodHandWords words per list entry)
-    // Way-points of long walks (round 4): a seed whose walk covered many tiles leaves kFloodWpWords - 1 pixels spread over its
-    // footprint; if it has to walk again, a team of wavefronts starts from the seed AND from those pixels at once
-    // (kernels_flood.hip: team_walk, kMulti).  One record per seed for the first wp_cap seeds.
-    uint32_t* waypoints = nullptr;
-    uint32_t wp_cap = 0;
-    bool multi_source = true;       // lr_set_flood_multi_source / LIBRECTIFY_FLOOD_MULTI=0: comparison hook, same labels
-    uint32_t* multi_list = nullptr; // way-point seeds of the coming round (8192): walked by a team launch beside the exploration ...
-    hipStream_t aux_stream = nullptr;          // ... on this second stream of the context (nullptr: they go through big_list, after it)
-    const hipEvent_t* fork_events = nullptr;   // one pair per round that forks (enqueue_round)
-    const hipEvent_t* join_events = nullptr;
-    int n_fork_events = 0;
-    int multi_round_last = 4;       // last round (index from 0) that walks its way-point seeds beside its exploration
     // Re-walks from the log (round 4; kernels_flood.hip: flood_rewalk_kernel).  A blocked seed walks its footprint again
     // every round, tile after tile, and rounds 2-5 of a frame last as long as their one longest such walk.  But a footprint
     // only ever SHRINKS (acceptance is static but for commits), so the next footprint is the connected part around the seed
     // of (last footprint minus committed pixels): a finished walk leaves its (tile, pixels) records here, and the later
     // rounds label the components of those records in LDS -- no dependent chain of memory round trips.
     bool rewalk_logs = false;
-    int log_min_tiles = 0, log_walk_tiles = 0;  // 0: the defaults (16 and 12, LIBRECTIFY_FLOOD_LOG_MIN / _WALK); the lanes of a batch bring their own
-    int log_from_round = 1;    // first round (from 0) whose seeds turn to their logs (walks leave logs from the first round on)
+    uint32_t* rewalk_list = nullptr;  // a round's seeds whose footprint is worked out from their log (8192)
+    int log_min_tiles = 0, log_walk_tiles = 0;  // 0: the defaults (16 and 12: kernels_flood.hip, kLogMinTiles); the lanes of a batch bring their own
     bool giant_hold = false;   // only the lowest active seed walks on into a global slab; other walks that outgrow the second tier are held back (kernels_flood.hip: kCtrlLowest)
     // The giant step (round 5; kernels_flood.hip: kCtrlGiantStep): when the lowest active seed's walk outgrows the LDS tiers, its
     // flood -- a plain connected component, nothing speculative about it -- is labelled by the whole device between two
@@ -154,7 +141,7 @@ struct FloodBuffers {
     uint32_t* giant_parent = nullptr;  // one word per pixel (the ordered kernels' queue: never in use at the same time)
     bool log_sweep = false;    // test hook: the fall-back (sweeps) for every log
     bool rewalk_big = false;   // the frame is expected to have walks beyond the first tier: their logs are kept too, and a second launch per round works on them
-    uint32_t log_seeds = 0, log_cap = 0;
+    uint32_t log_seeds = 0, log_cap = 0;  // seeds with a log word (the first log_seeds of the order), records the buffer holds
     uint32_t* log_off = nullptr;
     uint32_t* log_len = nullptr;
     uint32_t* log_buf = nullptr;
@@ -194,7 +181,6 @@ struct FloodBuffers {
     uint32_t* host_ctrl = nullptr;      // page-locked, device-visible: the round that ends the flood leaves the control block here (no copy of it is enqueued then)
     int jit_first = 0;                  // 0: off
     int jit_sleep_us = 0;               // the polling thread sleeps this long between looks (0: it spins -- single calls)
-    int jit_lead = 0;                   // rounds the host keeps enqueued ahead of the last one it has seen finished
     uint32_t big_cap_override = 0;  // test hook: seeds per round the second tier takes (0 = the default, 8192)
     uint32_t team_tile_cap = 0;     // test hook: tiles after which the second tier's team hands a walk to a slab (0 = its table)
 };
@@ -232,7 +218,8 @@ int flood_enqueue(const FloodBuffers& B, const FloodFrame& F, FloodProgress* P, 
 // synchronises).  *extra = the label image changed after flood_enqueue's rounds, so later stages must run again.
 int flood_finish(const FloodBuffers& B, const FloodFrame& F, FloodProgress* P, uint32_t* h_ctrl, int* rounds_out,
                  uint32_t* tiers_out /* [14]: seeds moved to the second tier, slabs used, seeds left to the ordered tail,
-                                        hold-back engaged, pixels walked (lo, hi), tile steps (lo, hi), ... giant steps */,
+                                        hold-back engaged, pixels walked (lo, hi), tile steps (lo, hi), ... giant steps;
+                                        [9] is retired and always 0 */,
                  bool* extra, hipStream_t s);
 
 // kernels_fit.hip (all counts stay on the device: launches cover seed_cap / comp_cap)

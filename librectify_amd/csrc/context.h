@@ -65,9 +65,6 @@ struct lr_context {
     uint32_t* label = nullptr;
     int32_t* queue = nullptr;
     lramd::FloodBuffers fb;
-    hipStream_t flood_aux = nullptr;       // second stream of the flood: way-point seeds' team walks beside a round's exploration
-    std::vector<hipEvent_t> flood_fork, flood_join;
-    bool flood_aux_on = true;              // off for the lanes of a batch call (their frames overlap each other instead)
     size_t fb_cap_seeds = 0;
     // stage 4
     uint32_t* comp_rank = nullptr;
@@ -168,13 +165,11 @@ struct lr_context {
     int flood_staged_streak = 0;     // frames in a row that started staged (every sixteenth starts without the hint)
     bool flood_staged_hint = false;  // was the last frame one of overlapping giants (kernels_flood.hip: kCtrlStaged)?  Then this one starts on its strongest quarter
     bool flood_calm_hint = false;      // the last frame's walks all stayed in the first storage tier (FloodBuffers::calm_hint)
-    uint32_t flood_tiers[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // last flood: seeds in the second tier, slabs used, seeds of the ordered tail, hold-back, walked px (lo, hi), steps (lo, hi), walks beyond the first tier's table, multi-source re-walks, re-walks from logs, logs given up, giants held back
+    uint32_t flood_tiers[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // last flood: seeds in the second tier, slabs used, seeds of the ordered tail, hold-back, walked px (lo, hi), steps (lo, hi), walks beyond the first tier's table, 0 (retired), re-walks from logs, logs given up, giants held back
     bool flood_partial = true;  // partial commits of blocked seeds (kernels_flood.hip); lr_set_flood_partial_commits
     int flood_log_min = 0, flood_log_walk = 0;  // thresholds of the logs (0: the defaults; the lanes of a batch call get 32 and 24)
-    int flood_log_from = 1;        // first round (from 0) whose seeds turn to their logs (lanes of a batch: experiment knob LIBRECTIFY_FLOOD_LOGS_LANES_FROM)
     bool flood_log_sweep = false;  // test hook (lr_set_flood_logs(ctx, 2)): every footprint worked out from a log goes the fall-back way (sweeps)
     bool flood_logs = true;     // blocked seeds work their next footprint out from the records of their last walk (kernels_flood.hip: flood_rewalk_kernel); lr_set_flood_logs, LIBRECTIFY_FLOOD_LOGS=0
-    bool flood_multi = false;   // re-walks of long footprints from several way-points at once (kernels_flood.hip): opt-in, lr_set_flood_multi_source / LIBRECTIFY_FLOOD_MULTI=1
     bool flood_staged = false;  // lr_set_flood_staged: the rounds start on the strongest eighth of the seeds (test / experiment hook)
     // Stage timers (HIP events between the stages of a frame): off in the frame calls unless lr_set_stage_timing or
     // LIBRECTIFY_STAGE_TIMES asks -- every event record is a barrier packet in the stream, some 6 us of idle GPU each,

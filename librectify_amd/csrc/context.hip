@@ -30,10 +30,9 @@
 // Less host-memory traffic beside the transfers, which read the same memory.
 static inline void stage_copy(void* dst, const void* src, size_t n) {
 #if defined(__SSE2__)
-    static const bool plain = std::getenv("LIBRECTIFY_STAGE_PLAIN") != nullptr;  // (comparison knob)
     char* d = static_cast<char*>(dst);
     const char* s_ = static_cast<const char*>(src);
-    if (plain || n < 4096) {
+    if (n < 4096) {
         std::memcpy(d, s_, n);
         return;
     }
@@ -128,7 +127,6 @@ int ctx_trim(lr_context* c, bool frames_too) {
     LR_HIP(hipSetDevice(c->device));
     LR_HIP(hipStreamSynchronize(c->stream));
     if (c->copy_stream) LR_HIP(hipStreamSynchronize(c->copy_stream));
-    if (c->flood_aux) LR_HIP(hipStreamSynchronize(c->flood_aux));
     auto drop = [](auto*& p) {
         if (p) (void)hipFree(p);
         p = nullptr;
@@ -142,7 +140,7 @@ int ctx_trim(lr_context* c, bool frames_too) {
     c->cap_tiles = 0;
     FloodBuffers& f = c->fb;
     drop(f.blocked), drop(f.count), drop(f.flags), drop(f.state), drop(f.tier), drop(f.blk), drop(f.act_a), drop(f.act_b), drop(f.ctrl), drop(f.big_list);
-    drop(f.handover), drop(f.dirty), drop(f.giant_mask), drop(f.waypoints), drop(f.multi_list), drop(f.log_off), drop(f.log_len), drop(f.log_buf);
+    drop(f.handover), drop(f.dirty), drop(f.giant_mask), drop(f.rewalk_list), drop(f.log_off), drop(f.log_len), drop(f.log_buf);
     drop(f.slab_ring), drop(f.slab_hash);
     c->fb_cap_seeds = 0;
     // (the frame slots hold the frame that is being processed when the workspace shrinks by itself: only on request)
@@ -266,29 +264,14 @@ static int ensure_flood_buffers(lr_context* c) {
         if (dev_alloc(gm, cs / 16 + 64)) return 1;
         f.giant_mask = gm;
     }
-    f.wp_cap = (uint32_t)std::min<size_t>(std::max<size_t>(cs / 16, 4096), cs);  // (one seed per 16 pixels: the 4K bench frame has one per 200)
-    if (dev_alloc(f.waypoints, (size_t)f.wp_cap * kFloodWpWords) || dev_alloc(f.multi_list, 8192)) return 1;
-    // footprint logs (FloodBuffers::rewalk_logs): per-seed words for one seed per 16 pixels, a record per 8 pixels
-    f.log_seeds = f.wp_cap;
-    static const int log_div = std::getenv("LIBRECTIFY_FLOOD_LOG_CAP_DIV") ? std::max(1, std::atoi(std::getenv("LIBRECTIFY_FLOOD_LOG_CAP_DIV"))) : 8;
-    f.log_cap = (uint32_t)std::min<size_t>(std::max<size_t>(cs / (size_t)log_div, 65536), 1u << 28);
-    if (dev_alloc(f.log_off, f.log_seeds) || dev_alloc(f.log_len, f.log_seeds) || dev_alloc(f.log_buf, (size_t)f.log_cap * 3)) return 1;
-    if (!c->flood_aux) {
-        // At a priority of its own: HIP maps streams onto a few hardware queues, and a second stream that lands on the queue
-        // of the first runs BEHIND it -- fork and join then cost two barriers a round and buy nothing (seen in bench.py, whose
-        // process has thirteen streams: flood 1.28 -> 1.80 ms).  Streams of different priorities never share a queue.
-        int lo = 0, hi = 0;
-        if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) lo = hi = 0;
-        if (hi == lo) LR_HIP(hipStreamCreateWithFlags(&c->flood_aux, hipStreamNonBlocking));
-        else LR_HIP(hipStreamCreateWithPriority(&c->flood_aux, hipStreamNonBlocking, hi));
-        for (int i = 0; i < 8; ++i) {
-            hipEvent_t a = nullptr, b = nullptr;
-            LR_HIP(hipEventCreateWithFlags(&a, hipEventDisableTiming));
-            c->flood_fork.push_back(a);
-            LR_HIP(hipEventCreateWithFlags(&b, hipEventDisableTiming));
-            c->flood_join.push_back(b);
-        }
-    }
+    // footprint logs (FloodBuffers::rewalk_logs): per-seed words for one seed per 16 pixels (the 4K bench frame has one per
+    // 200), a record per 8 pixels
+    constexpr size_t kLogCapDiv = 8;
+    f.log_seeds = (uint32_t)std::min<size_t>(std::max<size_t>(cs / 16, 4096), cs);
+    f.log_cap = (uint32_t)std::min<size_t>(std::max<size_t>(cs / kLogCapDiv, 65536), 1u << 28);
+    if (dev_alloc(f.rewalk_list, 8192) || dev_alloc(f.log_off, f.log_seeds) || dev_alloc(f.log_len, f.log_seeds) ||
+        dev_alloc(f.log_buf, (size_t)f.log_cap * 3))
+        return 1;
     LR_HIP(hipMemsetAsync(f.ctrl, 0, kFloodCtrlWords * sizeof(uint32_t), c->stream));
     c->fb_cap_seeds = cs;
     return ensure_flood_slabs(c);
@@ -334,7 +317,7 @@ int staging_threads(int num_threads, size_t frame_bytes = 0) {
 // The host cores next to a device: those of the NUMA node its PCI function sits on (sysfs), as far as this process may use
 // them; empty if unknown.  Staging helpers bind themselves there: copies by cores of the other socket reach 41 GB/s where
 // the same copies by cores of the device's own node keep the link at 54 (tools/ubench/h2d_placement.hip,
-// profiles/r04_h2d_paths.txt).  LIBRECTIFY_STAGING_BIND=0 leaves the helpers where the scheduler puts them.
+// profiles/r04_h2d_paths.txt).
 // (Returned by value, copied under the lock: a reference into the cache dangled when another thread asked for a device with
 // a higher index and the outer vector grew -- the start-up pattern of the multi-device batch call.)
 std::vector<int> device_node_cpus(int device) {
@@ -344,9 +327,8 @@ std::vector<int> device_node_cpus(int device) {
     const auto found = cache.find(device);
     if (found != cache.end()) return found->second;
     std::vector<int>& out = cache[device];
-    static const bool off = std::getenv("LIBRECTIFY_STAGING_BIND") && std::atoi(std::getenv("LIBRECTIFY_STAGING_BIND")) == 0;
     char bus[64] = {0};
-    if (off || hipDeviceGetPCIBusId(bus, (int)sizeof(bus), device) != hipSuccess) return out;
+    if (hipDeviceGetPCIBusId(bus, (int)sizeof(bus), device) != hipSuccess) return out;
     for (char* p = bus; *p; ++p) *p = (char)std::tolower((unsigned char)*p);
     int node = -1;
     if (FILE* f = std::fopen((std::string("/sys/bus/pci/devices/") + bus + "/numa_node").c_str(), "r")) {
@@ -397,8 +379,7 @@ static int ensure_copy_stream(lr_context* c) {
     // ... and at a higher priority than the lanes' streams: streams of different priorities do not share a queue
     int lo = 0, hi = 0;
     if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) lo = hi = 0;
-    static const bool plain = std::getenv("LIBRECTIFY_COPY_STREAM_PLAIN") != nullptr;  // (measurement)
-    if (plain || hi == lo) LR_HIP(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+    if (hi == lo) LR_HIP(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
     else LR_HIP(hipStreamCreateWithPriority(&c->copy_stream, hipStreamNonBlocking, hi));
     return 0;
 }
@@ -736,9 +717,6 @@ int ctx_create(int device, lr_context** out) {
     c->ransac_seed = env ? std::strtoull(env, nullptr, 0) : 0ull;
     c->timing_on = std::getenv("LIBRECTIFY_STAGE_TIMES") != nullptr;
     if (const char* e = std::getenv("LIBRECTIFY_FLOOD_LOGS")) c->flood_logs = std::atoi(e) != 0;
-    if (const char* e = std::getenv("LIBRECTIFY_FLOOD_MULTI")) c->flood_multi = std::atoi(e) != 0;  // (opt-in: DESIGN.md section 7, round 4)
-    const char* fm = std::getenv("LIBRECTIFY_FLOOD_MODE");
-    if (fm) c->flood_mode = std::atoi(fm);
     *out = c;
     return 0;
 }
@@ -756,19 +734,11 @@ void ctx_destroy(lr_context* c) {
                     c->label, c->queue, c->comp_rank, c->comp_seed, c->comp_off, c->cursor, c->px_a, c->px_b,
                     c->scratch_w, c->d_lines, c->temp, c->d_model, c->d_best_slots,
                     c->fb.blocked, c->fb.count, c->fb.flags, c->fb.state, c->fb.tier, c->fb.blk, c->fb.act_a, c->fb.act_b,
-                    c->fb.ctrl, c->fb.big_list, c->fb.handover, c->fb.waypoints, c->fb.multi_list, c->fb.log_off, c->fb.log_len, c->fb.log_buf, c->fb.dirty, c->fb.giant_mask, c->fb.slab_ring, c->fb.slab_hash, c->d_pairs, c->d_peak, c->d_weights,
+                    c->fb.ctrl, c->fb.big_list, c->fb.handover, c->fb.rewalk_list, c->fb.log_off, c->fb.log_len, c->fb.log_buf, c->fb.dirty, c->fb.giant_mask, c->fb.slab_ring, c->fb.slab_hash, c->d_pairs, c->d_peak, c->d_weights,
                     c->d_samples, c->d_hcounts, c->comp_large, c->huge.tab, c->huge.jobs, c->huge.list, c->d_tables, c->d_orig, c->d_inl, c->d_flines, c->d_gctl,
                     c->d_gnorm, c->d_models, c->d_refine_table, c->d_refine_edges, c->d_cht_acc, c->d_cht_idx, c->d_cht_peak, c->d_rec, c->d_recflags};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
-    if (c->flood_aux) {
-        (void)hipStreamSynchronize(c->flood_aux);
-        (void)hipStreamDestroy(c->flood_aux);
-    }
-    for (auto& e : c->flood_fork)
-        if (e) (void)hipEventDestroy(e);
-    for (auto& e : c->flood_join)
-        if (e) (void)hipEventDestroy(e);
     delete static_cast<StagingCrew*>(c->crew);
     c->crew = nullptr;
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
@@ -885,26 +855,15 @@ FloodBuffers flood_buffers_for(lr_context* c) {
     }
     static const bool partial_off = std::getenv("LIBRECTIFY_FLOOD_PARTIAL") && std::atoi(std::getenv("LIBRECTIFY_FLOOD_PARTIAL")) == 0;
     fbuf.partial_commits = !partial_off && c->flood_partial;
-    fbuf.multi_source = c->flood_multi;
-    fbuf.rewalk_logs = c->flood_logs && !c->flood_multi;  // (way-points, when asked for, instead)
+    fbuf.rewalk_logs = c->flood_logs;
     fbuf.log_sweep = c->flood_log_sweep;
-    fbuf.log_from_round = c->flood_log_from;
     fbuf.log_min_tiles = c->flood_log_min;
     fbuf.log_walk_tiles = c->flood_log_walk;
-    static const bool giants_off = std::getenv("LIBRECTIFY_FLOOD_GIANTS") && std::atoi(std::getenv("LIBRECTIFY_FLOOD_GIANTS")) == 0;
-    fbuf.giant_hold = c->flood_mode == 1 && !giants_off;  // (the storage test hooks -- modes 2-7 -- keep their slabs)
+    fbuf.giant_hold = c->flood_mode == 1;  // (the storage test hooks -- modes 2-7 -- keep their slabs)
     static const bool giant_step_off = std::getenv("LIBRECTIFY_FLOOD_GIANT_STEP") && std::atoi(std::getenv("LIBRECTIFY_FLOOD_GIANT_STEP")) == 0;
     fbuf.giant_step = !giant_step_off && c->flood_giant_step;
     fbuf.giant_parent = reinterpret_cast<uint32_t*>(c->queue);
     fbuf.rewalk_big = c->flood_logbig_hint && !c->flood_logbig_off;  // (the context's last frame had walks beyond the first tier)
-    static const int aux_env = std::getenv("LIBRECTIFY_FLOOD_MULTI_BESIDE") ? std::atoi(std::getenv("LIBRECTIFY_FLOOD_MULTI_BESIDE")) : -1;  // (experiment: 0 = after the exploration, N = beside it in rounds 2 .. N + 1)
-    if (c->flood_aux && c->flood_aux_on && aux_env != 0 && c->flood_fork.size() == c->flood_join.size()) {
-        fbuf.aux_stream = c->flood_aux;
-        fbuf.fork_events = c->flood_fork.data();
-        fbuf.join_events = c->flood_join.data();
-        fbuf.n_fork_events = (int)c->flood_fork.size();
-        if (aux_env > 0) fbuf.multi_round_last = aux_env;
-    }
     if (c->flood_staged) fbuf.win_first_shift = 3;
     fbuf.blind_rounds = c->flood_rounds_hint;
     // rounds just in time (FloodBuffers::host_progress): what the last frame needed less one at once (three on a new context)
@@ -919,18 +878,9 @@ FloodBuffers flood_buffers_for(lr_context* c) {
     // (at most four rounds blindly -- the rounds that always bring their `rest` launch, kernels_flood.hip kRestRounds: a later
     // blind round whose list is longer than its grid walks only a part of it, and lists stay long while a window is closed in
     // front of waiting seeds (a frame of soft blobs went to the ordered tail that way now and then: 42 -> 200 ms); a round
-    // enqueued just in time knows its list's length and brings the launch when it needs it.  LIBRECTIFY_FLOOD_JIT_FIRST_MAX)
-    static const int jit_first_max = std::getenv("LIBRECTIFY_FLOOD_JIT_FIRST_MAX") ? std::max(1, std::atoi(std::getenv("LIBRECTIFY_FLOOD_JIT_FIRST_MAX"))) : 4;
-    fbuf.jit_first = (c->flood_jit && !jit_off) ? std::min(c->flood_rounds_last > 0 ? std::max(c->flood_rounds_last - 1, 2) : 3, jit_first_max) : 0;
-    // (the lanes of a batch: LIBRECTIFY_FLOOD_JIT_FIRST_LANES / _LEAD_LANES = rounds enqueued blindly at most / rounds kept ahead)
-    static const int first_lanes = std::getenv("LIBRECTIFY_FLOOD_JIT_FIRST_LANES") ? std::atoi(std::getenv("LIBRECTIFY_FLOOD_JIT_FIRST_LANES")) : 0;
-    static const int lead_lanes = std::getenv("LIBRECTIFY_FLOOD_JIT_LEAD_LANES") ? std::atoi(std::getenv("LIBRECTIFY_FLOOD_JIT_LEAD_LANES")) : 0;
-    static const int lead_single = std::getenv("LIBRECTIFY_FLOOD_JIT_LEAD") ? std::max(0, std::atoi(std::getenv("LIBRECTIFY_FLOOD_JIT_LEAD"))) : 0;
-    fbuf.jit_lead = lead_single;
-    if (c->flood_jit_sleep_us > 0 && fbuf.jit_first > 0) {
-        if (first_lanes > 0) fbuf.jit_first = std::min(fbuf.jit_first, first_lanes);
-        fbuf.jit_lead = std::max(lead_lanes, 0);
-    }
+    // enqueued just in time knows its list's length and brings the launch when it needs it.
+    constexpr int kJitFirstMax = 4;
+    fbuf.jit_first = (c->flood_jit && !jit_off) ? std::min(c->flood_rounds_last > 0 ? std::max(c->flood_rounds_last - 1, 2) : 3, kJitFirstMax) : 0;
     return fbuf;
 }
 
@@ -1017,42 +967,34 @@ int finish_flood(lr_context* c, bool* extra) {
                      c->flood_rounds, c->flood_tiers[0], c->flood_tiers[8], c->flood_tiers[3], (int)c->flood_hold_hint);
     c->flood_logbig_hint = c->flood_tiers[0] > 0;
     c->flood_calm_hint = c->flood_tiers[0] == 0 && c->flood_tiers[1] == 0 && c->flood_tiers[15] == 0;
-    static const int hints_env = std::getenv("LIBRECTIFY_FLOOD_HINTS") ? std::atoi(std::getenv("LIBRECTIFY_FLOOD_HINTS")) : 1;  // (experiment knob)
-    if (hints_env == 0) {  // as in round 2
-        c->flood_big_hint = c->flood_tiers[0] > 0 || c->flood_tiers[1] > 0;
-        c->flood_hold_hint = c->flood_tiers[3] != 0;
-    } else {
-        // The second tier is always there: a frame of regions that follows a frame of lines on this context used to run its
-        // first batch of rounds without it, every long walk in a global slab (6.4 instead of 1.5 ms of flood on the natural
-        // 4K frame), and an empty launch of its kernel costs a round 5 us.  The hold-back starts with the frame only after a
-        // frame of REGIONS (many walks beyond the first tier's table): engaged from the start on a frame of lines it costs
-        // three rounds (1.55 instead of 1.10 ms), and the old rule -- "the last frame engaged it" -- kept itself alive from
-        // frame to frame once a single frame had.
-        c->flood_big_hint = true;
-        c->flood_hold_hint = c->flood_tiers[3] != 0 && c->flood_tiers[8] >= 16;
-        // A frame that went on staged (many walks held back in its first round) hands that on; a frame that STARTED staged
-        // keeps handing it on while its floods still look like regions (walks in the second tier: the staged start itself
-        // keeps the giants away, so their count says nothing any more).
-        static const int staged_keep = std::getenv("LIBRECTIFY_FLOOD_STAGED_KEEP") ? std::atoi(std::getenv("LIBRECTIFY_FLOOD_STAGED_KEEP")) : 64;
-        c->flood_staged_hint = c->flood_tiers[14] != 0 && (!c->flood_staged_hint || (int)c->flood_tiers[0] >= staged_keep);
-        // (a frame that started staged cannot tell whether it would have gone staged by itself: every sixteenth frame of such
-        // a run starts without the hint and finds out -- a ramp under noise pays 1.6 ms for that frame, soft blobs that
-        // inherited the hint from other content are rid of it)
-        c->flood_staged_streak = c->flood_staged_hint ? c->flood_staged_streak + 1 : 0;
-        if (c->flood_staged_streak >= 16) {
-            c->flood_staged_hint = false;
-            c->flood_staged_streak = 0;
-        }
-        if (c->flood_staged_hint) c->flood_hold_hint = false;
-        // (The verdict "many long walks" -- early hand-over to the second tier, flood_advance -- is NOT carried over: started
-        // with it, the natural 4K frame sends 735 walks to the second tier in round one and its flood takes 1.88 ms instead
-        // of 1.5, and a frame of lines that follows pays 0.7 ms for the wrong guess.)
+    // The second tier is always there: a frame of regions that follows a frame of lines on this context used to run its
+    // first batch of rounds without it, every long walk in a global slab (6.4 instead of 1.5 ms of flood on the natural
+    // 4K frame), and an empty launch of its kernel costs a round 5 us.  The hold-back starts with the frame only after a
+    // frame of REGIONS (many walks beyond the first tier's table): engaged from the start on a frame of lines it costs
+    // three rounds (1.55 instead of 1.10 ms), and the old rule -- "the last frame engaged it" -- kept itself alive from
+    // frame to frame once a single frame had.
+    c->flood_big_hint = true;
+    c->flood_hold_hint = c->flood_tiers[3] != 0 && c->flood_tiers[8] >= 16;
+    // A frame that went on staged (many walks held back in its first round) hands that on; a frame that STARTED staged
+    // keeps handing it on while its floods still look like regions (walks in the second tier: the staged start itself
+    // keeps the giants away, so their count says nothing any more).
+    constexpr uint32_t kStagedKeep = 64;  // second-tier walks of a staged frame that keep the hint
+    c->flood_staged_hint = c->flood_tiers[14] != 0 && (!c->flood_staged_hint || c->flood_tiers[0] >= kStagedKeep);
+    // (a frame that started staged cannot tell whether it would have gone staged by itself: every sixteenth frame of such
+    // a run starts without the hint and finds out -- a ramp under noise pays 1.6 ms for that frame, soft blobs that
+    // inherited the hint from other content are rid of it)
+    c->flood_staged_streak = c->flood_staged_hint ? c->flood_staged_streak + 1 : 0;
+    if (c->flood_staged_streak >= 16) {
+        c->flood_staged_hint = false;
+        c->flood_staged_streak = 0;
     }
+    if (c->flood_staged_hint) c->flood_hold_hint = false;
+    // (The verdict "many long walks" -- early hand-over to the second tier, flood_advance -- is NOT carried over: started
+    // with it, the natural 4K frame sends 735 walks to the second tier in round one and its flood takes 1.88 ms instead
+    // of 1.5, and a frame of lines that follows pays 0.7 ms for the wrong guess.)
 
     // blind rounds of the next frame: what this one needed plus two, decaying slowly
-    static const int blind_extra = std::getenv("LIBRECTIFY_BLIND_EXTRA") ? std::atoi(std::getenv("LIBRECTIFY_BLIND_EXTRA")) : 2;  // (experiment knob)
-    static const int blind_min = std::getenv("LIBRECTIFY_BLIND_MIN") ? std::atoi(std::getenv("LIBRECTIFY_BLIND_MIN")) : 6;
-    c->flood_rounds_hint = std::max(std::max(c->flood_rounds + blind_extra, blind_min), c->flood_rounds_hint - 1);
+    c->flood_rounds_hint = std::max(std::max(c->flood_rounds + 2, 6), c->flood_rounds_hint - 1);
     c->flood_rounds_last = c->flood_rounds;
     return 0;
 }
@@ -2214,7 +2156,6 @@ int ctx_find_groups_host(lr_context* c, const float* buffer, int w, int h, int s
     // own -- transfer submission, event, cross-stream wait -- on the stream that carries the frame: measured on 4K frames
     // 3.01 ms per call with 4 MB bands, 3.49 with 1 MB, 4.07 with 512 KB (profiles/r03_single_call_sweep.txt).
     static const size_t band_bytes = std::getenv("LIBRECTIFY_UPLOAD_BAND_KB") ? (size_t)std::max(64, std::atoi(std::getenv("LIBRECTIFY_UPLOAD_BAND_KB"))) << 10 : (size_t)4 << 20;
-    static const int filter_every = std::getenv("LIBRECTIFY_FILTER_EVERY") ? std::max(1, std::atoi(std::getenv("LIBRECTIFY_FILTER_EVERY"))) : 1;
     // (a page-locked source goes up in ONE transfer unless the knob says otherwise: eight bands of 4 MB with an event each cost
     // the call more than the filter gains by starting under the transfer -- 2.07 -> 1.94 ms per 4K frame, round 5)
     static const bool band_env = std::getenv("LIBRECTIFY_UPLOAD_BAND_KB") != nullptr;
@@ -2234,7 +2175,6 @@ int ctx_find_groups_host(lr_context* c, const float* buffer, int w, int h, int s
         // the compute stream waits for EVERY band's own event: the bands are enqueued by several threads in no particular
         // order, so a later band's event says nothing about an earlier band
         LR_HIP(hipStreamWaitEvent(c->stream, c->band_ev[(size_t)k], 0));
-        if ((k + 1) % filter_every != 0 && k != n_bands - 1) return 0;
         const int last_row = std::min(h, (k + 1) * rpb) - 1;  // last image row on the device once bands 0..k are
         int by_end = by_next;
         while (by_end < band_rows && std::min(h - 1, filter_band_last_row(by_end)) <= last_row) ++by_end;
@@ -2332,14 +2272,9 @@ static int ensure_upload_ring(lr_context* c, int R, size_t npix, bool staging) {
         c->ring_img.assign((size_t)std::max<int>(R, (int)c->ring_img.size()), nullptr);
         c->ring_cap_pix = 0;
         const size_t cap = std::max(npix, c->ring_cap_pix);
-        // (LIBRECTIFY_RING_UNCACHED=1, experiment of round 5: the frames' device buffers as uncached / fine-grained memory -- do the
-        // lanes' kernels lose less beside the transfers when the incoming frames bypass the caches?  profiles/r05_dma_interference.txt)
-        static const int ring_flags = std::getenv("LIBRECTIFY_RING_UNCACHED") ? std::atoi(std::getenv("LIBRECTIFY_RING_UNCACHED")) : 0;
-        for (float*& p : c->ring_img) {
-            if (ring_flags == 1) LR_HIP(hipExtMallocWithFlags((void**)&p, cap * sizeof(float), hipDeviceMallocUncached));
-            else if (ring_flags == 2) LR_HIP(hipExtMallocWithFlags((void**)&p, cap * sizeof(float), hipDeviceMallocFinegrained));
-            else LR_HIP(hipMalloc((void**)&p, cap * sizeof(float)));
-        }
+        // (uncached or fine-grained memory for these buffers -- so that the incoming frames bypass the caches -- was measured
+        // and not kept: profiles/r05_dma_interference.txt)
+        for (float*& p : c->ring_img) LR_HIP(hipMalloc((void**)&p, cap * sizeof(float)));
         c->ring_cap_pix = cap;
     }
     static const bool lane_debug = std::getenv("LIBRECTIFY_LANE_DEBUG") != nullptr || std::getenv("LIBRECTIFY_BATCH_STATS") != nullptr;  // (they time the uploads)
@@ -2374,8 +2309,7 @@ static int find_groups_batch(lr_context* c, const float* d_images, size_t image_
     std::vector<lr_context*> lanes;
     lanes.push_back(c);
     for (int i = 0; i < S - 1; ++i) lanes.push_back(c->workers[i]);
-    const bool caller_multi = c->flood_multi;  // (lane 0 is the caller's own context: its setting comes back after the call)
-    const bool caller_logs = c->flood_logs;
+    const bool caller_logs = c->flood_logs;  // (lane 0 is the caller's own context: its settings come back after the call)
     const bool caller_jit = c->flood_jit;
     for (lr_context* l : lanes) {
         l->ransac_seed = c->ransac_seed;
@@ -2384,37 +2318,24 @@ static int find_groups_batch(lr_context* c, const float* d_images, size_t image_
         l->flood_staged = c->flood_staged;  // (off unless lr_set_flood_staged: +6 % in round 1, -3 % now)
         l->flood_partial = c->flood_partial;
         l->flood_giant_step = c->flood_giant_step;
-        // Multi-source re-walks shorten a frame's rounds at the price of more work per long walk (eight wavefronts and a
-        // second table entry per tile): worth it when the frame has the GPU to itself, not when S frames share it -- their
-        // rounds overlap each other anyway (profiles/r04_flood_multi_sweep.txt).  LIBRECTIFY_FLOOD_MULTI_LANES=1 keeps them.
-        static const bool multi_lanes = std::getenv("LIBRECTIFY_FLOOD_MULTI_LANES") && std::atoi(std::getenv("LIBRECTIFY_FLOOD_MULTI_LANES")) != 0;
-        l->flood_multi = caller_multi && (S == 1 || multi_lanes);
         // Re-walks from the logs: in the lanes only for walks of 32 tiles and more, behind a walk of 24 tiles.  With the
         // thresholds of a single call (16 / 12) round two's work on thousands of small logs is work on top, and S frames in
         // flight gain nothing from shorter rounds: 10.34 -> 10.2 Gpix/s; with these the long re-walks go and little is added:
-        // 10.34 -> 10.55 (profiles/r04_flood_logs.txt section 14).  LIBRECTIFY_FLOOD_LOGS_LANES=0 keeps the lanes without.
-        static const bool logs_lanes = !(std::getenv("LIBRECTIFY_FLOOD_LOGS_LANES") && std::atoi(std::getenv("LIBRECTIFY_FLOOD_LOGS_LANES")) == 0);
-        l->flood_logs = caller_logs && (S == 1 || logs_lanes);
-        static const int lanes_min = std::getenv("LIBRECTIFY_FLOOD_LOG_MIN_LANES") ? std::atoi(std::getenv("LIBRECTIFY_FLOOD_LOG_MIN_LANES")) : 32;
-        static const int lanes_walk = std::getenv("LIBRECTIFY_FLOOD_LOG_WALK_LANES") ? std::atoi(std::getenv("LIBRECTIFY_FLOOD_LOG_WALK_LANES")) : 24;
-        l->flood_log_min = S == 1 ? 0 : lanes_min;
-        l->flood_log_walk = S == 1 ? 0 : lanes_walk;
-        static const int logs_lanes_from = std::getenv("LIBRECTIFY_FLOOD_LOGS_LANES_FROM") ? std::atoi(std::getenv("LIBRECTIFY_FLOOD_LOGS_LANES_FROM")) : 1;
-        l->flood_log_from = S == 1 ? 1 : std::max(logs_lanes_from, 1);
+        // 10.34 -> 10.55 (profiles/r04_flood_logs.txt section 14).
+        l->flood_logs = caller_logs;
+        l->flood_log_min = S == 1 ? 0 : 32;
+        l->flood_log_walk = S == 1 ? 0 : 24;
         // ... and without the logs of second-tier walks: their kernel is a launch of 1 024 threads and 142 KB of LDS a
         // workgroup that has to find whole CUs beside the other lanes' kernels (2.7 launches a frame x 52 us in
-        // profiles/r04_kernel_stats.csv): 10.67 -> 10.76 Gpix/s without (three repetitions each).  LIBRECTIFY_FLOOD_LOGBIG_LANES=1
-        static const bool logbig_lanes = std::getenv("LIBRECTIFY_FLOOD_LOGBIG_LANES") && std::atoi(std::getenv("LIBRECTIFY_FLOOD_LOGBIG_LANES")) != 0;
-        l->flood_logbig_off = S > 1 && !logbig_lanes;
+        // profiles/r04_kernel_stats.csv): 10.67 -> 10.76 Gpix/s without (three repetitions each).
+        l->flood_logbig_off = S > 1;
         l->flood_log_sweep = c->flood_log_sweep;
         // (a lane's thread has nothing else to do while its frame is in flight, but the call's staging threads need the cores:
-        // a lane looks at the words every few tens of microseconds instead of spinning -- the other lanes keep the GPU busy)
+        // a lane looks at the words every 20 microseconds instead of spinning -- the other lanes keep the GPU busy)
         // Measured (profiles/r04_flood_logs.txt, section 9): 9.93 -> 10.29 Gpix/s from pageable frames, 11.7 -> 12.1 from
         // resident ones -- a frame of a lane no longer drags 3-4 rounds of empty launches through its stream.
-        // LIBRECTIFY_FLOOD_JIT_LANES = microseconds between looks (20); 0 = blind rounds.
-        static const int jit_lanes = std::getenv("LIBRECTIFY_FLOOD_JIT_LANES") ? std::atoi(std::getenv("LIBRECTIFY_FLOOD_JIT_LANES")) : 20;
-        l->flood_jit = caller_jit && (S == 1 || jit_lanes > 0);
-        l->flood_jit_sleep_us = S == 1 ? 0 : jit_lanes;
+        l->flood_jit = caller_jit;
+        l->flood_jit_sleep_us = S == 1 ? 0 : 20;
         l->estimator = c->estimator;
         l->prosac_T_N = c->prosac_T_N;
         l->cht_d = c->cht_d;
@@ -2457,7 +2378,7 @@ static int find_groups_batch(lr_context* c, const float* d_images, size_t image_
     for (auto& a : enq) a.store(0, std::memory_order_relaxed);
     for (auto& a : slot_busy) a.store(0, std::memory_order_relaxed);
     static const bool lane_debug = std::getenv("LIBRECTIFY_LANE_DEBUG") != nullptr;
-    static const size_t batch_band = std::getenv("LIBRECTIFY_BATCH_BAND_KB") ? (size_t)std::max(64, std::atoi(std::getenv("LIBRECTIFY_BATCH_BAND_KB"))) << 10 : (size_t)4 << 20;
+    constexpr size_t kBatchBand = (size_t)4 << 20;  // staging bands of the batch's pageable frames
     std::atomic<int> abort_all{0};
     std::string up_err;
     auto nap = [](int& spins) {  // a wait that is usually short: yield first, then sleep
@@ -2487,9 +2408,8 @@ static int find_groups_batch(lr_context* c, const float* d_images, size_t image_
     // (page-locked already, registration refused, or the uploader got there first).  The helpers take the frames in order; a
     // frame the uploader reaches before any helper has is staged.  (Helpers that begin at the fourth frame, the uploader staging
     // the call's first three rather than waiting 1.3 ms for the first registration: 11.30 against 11.41 Gpix/s -- the staging
-    // copies cost the helpers more than the wait costs the call; LIBRECTIFY_REGISTER_LEAD=<n> for the comparison.)
-    static const int reg_lead = std::getenv("LIBRECTIFY_REGISTER_LEAD") ? std::max(0, std::atoi(std::getenv("LIBRECTIFY_REGISTER_LEAD"))) : 0;
-    std::atomic<int> reg_next{std::min(batch, reg_lead)};
+    // copies cost the helpers more than the wait costs the call.)
+    std::atomic<int> reg_next{0};
     std::vector<std::thread> reg_pool;
     if (reg_frames)
         for (int t = 0; t < register_threads; ++t)
@@ -2546,7 +2466,7 @@ static int find_groups_batch(lr_context* c, const float* d_images, size_t image_
             const double t_u0 = now_ms();
             hipEvent_t e_dbg = nullptr;
             if (lane_debug && hipEventCreate(&e_dbg) == hipSuccess) (void)hipEventRecord(e_dbg, c->copy_stream);
-            const int up_rc = stage ? crew.run(c->ring_img[(size_t)slot], stage, h_frames[i], w, h, stride, c->copy_stream, batch_band, batch_band > ((size_t)4 << 20) ? StagingCrew::kPieces : 1)
+            const int up_rc = stage ? crew.run(c->ring_img[(size_t)slot], stage, h_frames[i], w, h, stride, c->copy_stream, kBatchBand, 1)
                                     : upload_rows(c, c->ring_img[(size_t)slot], nullptr, h_frames[i], w, h, stride, 1, c->copy_stream);
             if (up_rc || hipEventRecord(c->ring_ev[(size_t)slot], c->copy_stream) != hipSuccess) {
                 up_err = get_error().empty() ? "upload failed" : get_error();
@@ -2647,9 +2567,7 @@ static int find_groups_batch(lr_context* c, const float* d_images, size_t image_
             if (reg_ready[(size_t)i].load(std::memory_order_acquire) == 1 && hipHostUnregister(const_cast<float*>(h_frames[i])) != hipSuccess)
                 (void)hipGetLastError();  // (nothing to be done about it, and the caller's thread must not find it in its next call)
     for (lr_context* l : lanes) l->sleep_in_wait = false;
-    c->flood_multi = caller_multi;
     c->flood_logs = caller_logs;
-    c->flood_log_from = 1;
     c->flood_logbig_off = false;
     c->flood_log_min = c->flood_log_walk = 0;
     c->flood_jit = caller_jit;
@@ -2720,12 +2638,10 @@ int ctx_find_groups_batch_host_multi(lr_context* c, const int* devices, int n_de
         p->flood_mode = c->flood_mode;
         p->flood_staged = c->flood_staged;
         p->flood_partial = c->flood_partial;
-        p->flood_multi = c->flood_multi;
         p->flood_logs = c->flood_logs;
         p->flood_log_sweep = c->flood_log_sweep;
         p->flood_giant_step = c->flood_giant_step;
         p->flood_jit = c->flood_jit;
-        p->flood_aux_on = c->flood_aux_on;
         p->seed_keep_ratio = c->seed_keep_ratio;
         p->estimator = c->estimator;
         p->prosac_T_N = c->prosac_T_N;

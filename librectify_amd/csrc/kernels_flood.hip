@@ -159,21 +159,10 @@ constexpr uint32_t kMarkBit = 0x80000000u;
 #define LR_HASH_T 256
 #endif
 constexpr int kRingT = LR_RING_T, kHashT = LR_HASH_T;
-constexpr int kRingBig = 1024, kHashBig = 2048;
+constexpr int kHashBig = 2048;  // (the second tier's table: flood_explore_team_kernel)
 constexpr uint32_t kHandTiles = kHashT * 3 / 4, kHandRecs = kRingT;  // what a first-tier walk can hold when it is handed over
 constexpr uint32_t kHandTable = 4, kHandRing = kHandTable + 3 * kHandTiles;
 static_assert(kHandRing + 3 * kHandRecs <= kFloodHandWords, "hand-over record");
-// Way-points (round 4).  A walk of many tiles is a long dependent chain -- a line's frontier is two records wide, so not even
-// a team of wavefronts gets through it faster than a tile at a time -- and a blocked seed walks its footprint again every
-// round: rounds 2 to 5 of the bench frame lasted 235, 181, 157 us for single walks of 183, 155, 142 tiles while the chip
-// idled.  So a finished walk of at least wp_min_tiles tiles leaves kWpK pixels spread over its footprint (every
-// ntiles / (kWpK + 1)-th tile in order of insertion, which for a line alternates between its two arms), and the seed's
-// next walk starts from the seed AND from those pixels at once, on the eight wavefronts of a team: team_walk<.., true>.
-constexpr uint32_t kWpK = (uint32_t)kFloodWpWords - 1u;
-constexpr uint32_t kWpNone = 0xFFFFFFFFu;
-constexpr uint32_t kWpThinPx = 40u;      // way-points only for footprints of at most this many pixels a tile (lines, not regions)
-constexpr uint32_t kWpMaxTiles = 600u;   // the team's table holds an entry per (tile, source) and one per tile: 1536 in all
-constexpr uint32_t kSrcShift = 28u, kSrcMask = 0xF0000000u, kSrcClaim = 0xF0000000u;  // table keys of a multi-source walk
 constexpr uint32_t kBigCap = 8192;  // seeds per round that can move to the second tier (FloodBuffers::big_list)
 constexpr uint32_t kFlagIncomplete = 1u, kFlagSelfFail = 2u;
 constexpr uint32_t kHugeFlood = 1u << 14;  // (kernels_fit.hip: kSortLdsBig)
@@ -181,6 +170,19 @@ constexpr uint32_t kFullTiles = 48u;     // a first-tier walk is held at this ma
 constexpr uint32_t kGiantProbes = 512u;  // marked seeds a round lets walk again (one team each: a launch's worth)
 constexpr uint32_t kLogShrunk = 0x80000000u;  // FloodArgs::log_len: the log has been cut down to a later footprint by flood_rewalk_kernel
 constexpr uint32_t kMaxSteps = 1u << 22;  // safety net of the walk loop: more records than an 8K frame has tile visits
+// Tunables of the rounds, each at the value its sweep chose (the measurements are in the comments where they are used)
+constexpr uint32_t kTeamTiles = 1024;      // a second-tier walk counts as a giant at this many tiles (flood_args)
+constexpr uint32_t kGiantMany = 64;        // walks held back after which a frame is one of overlapping giants (kCtrlStaged)
+constexpr uint32_t kDeferSteps = 512;      // a blocked, log-less walk of this many tile steps waits for its blocker (kCtrlDeferLow)
+constexpr uint32_t kRegionalTiles = 32;    // a "regional" frame hands its walks to the second tier at this many tiles ...
+constexpr uint32_t kRegionalMin = 16;      // ... once it has had this many walks beyond the first tier's table (explore_body)
+constexpr uint32_t kHoldMinBig = 4;        // walks in the second tier after which the hold-back engages (flood_advance)
+constexpr uint32_t kHoldRelease = 64;      // the hold-back ends when so few seeds below the line are still active
+constexpr uint32_t kPartialSteps = 16;     // partial-commit walks stop after this many tile steps
+constexpr int kPartialRounds = 3;          // rounds that bring the partial commits (enqueue_round)
+constexpr uint32_t kDenseDiv = 12;         // a frame with a seed in every kDenseDiv pixels starts staged (flood_init_seeds_kernel)
+constexpr uint32_t kLogMinTiles = 16;      // walks of this many tiles leave a log (single calls; the lanes of a batch bring their own) ...
+constexpr uint32_t kLogWalkTiles = 12;     // ... and a seed with a log walks this many before it turns to it
 
 struct FloodArgs {
     const float* dx;
@@ -201,31 +203,23 @@ struct FloodArgs {
     uint4* slab_hash;   // n_slabs x slab_hash_cap x 2 records {generation, tile+1, V.lo, V.hi} {A.lo, A.hi, -, -}
     uint32_t n_slabs, slab_ring_cap, slab_hash_cap;  // caps are powers of two
     uint32_t win_shift;                              // staged start (see kCtrlWindow): growth of the window per round
-    uint32_t from_end;                               // explore the active list from its end (see flood_explore_kernel)
     uint32_t no_rest;                                // this round has no `rest` launch: entries past the grid are not walked
     uint32_t next_reach;                             // list entries the NEXT round's exploration reaches (0xFFFFFFFF: all)
     uint32_t big_cap;                                // seeds per round the second tier takes (0: tier switched off)
-    uint32_t g_cap;                                  // partial-commit walks stop after this many tile steps
-    uint32_t t1_tiles;                               // first tier hands a walk to the second at this many tiles (when there is one)
     uint32_t* handover;                              // state of the walks handed to the second tier (FloodBuffers::handover)
-    uint32_t team_tiles;                             // test hook: the team's table counts as full at this many tiles
+    uint32_t team_tiles;                             // the team's table counts as full at this many tiles (kTeamTiles, or a test hook's)
     uint32_t* blk;                                   // per seed: the lower seed a long, log-less walk of it was blocked by (0xFFFFFFFF: none; see kCtrlDeferLow)
-    uint32_t defer_steps;                            // ... walks of at least this many tile steps
-    uint32_t giant_many;                             // walks held back after which a frame counts as one of overlapping giants (see kCtrlStaged)
-    uint32_t hold_min_big;                           // walks in the second tier after which the hold-back engages
-    uint32_t hold_release;                           // the hold-back ends when so few seeds below the line are still active
-    uint32_t t1_regional, t1_regional_min;           // ... at t1_regional tiles once the frame has had t1_regional_min walks beyond the first tier's table
-    uint32_t t1_wide_tiles, t1_wide_front;           // ... or at this many tiles when its frontier holds this many records
-    uint32_t* waypoints;                             // FloodBuffers::waypoints (kFloodWpWords per seed), wp_cap seeds
-    uint32_t wp_cap;
-    uint32_t wp_min_tiles;                           // walks of at least this many tiles leave way-points (0xFFFFFFFF: never)
-    uint32_t* multi_list;                            // way-point seeds of the coming round (written by the survivors pass), kBigCap entries
-    uint32_t multi_next;                             // the coming round walks that list in a launch of its own, beside its exploration
+    // A first-tier walk whose frontier holds wide_front records at wide_tiles tiles goes to the second tier.  Off (wide_tiles =
+    // 0xFFFFFFFF): measured and not kept.  The words stay because the exploration kernel compiles to 96 VGPRs with this
+    // test in its walk loop and to 97 without it -- four walks per SIMD instead of five.
+    uint32_t wide_tiles, wide_front;
+    uint32_t giant_many;                             // walks held back after which a frame counts as one of overlapping giants (see kCtrlStaged; 0: never)
+    uint32_t* rewalk_list;                           // this round's seeds whose footprint flood_rewalk_kernel works out from their log, kBigCap entries
     // ---- re-walks from the log (flood_rewalk_kernel): a finished walk of at least log_min_tiles tiles leaves its footprint
     // as (tile, walked pixels) records; the seed's later rounds work on those records instead of walking the image again
     uint32_t log_min_tiles;                          // 0xFFFFFFFF: no logs
     uint32_t log_walk_tiles;                         // a seed with a log walks this many tiles before it turns to the log
-    uint32_t log_use;                                // 0: this round's walks leave logs but none is used yet (FloodBuffers::log_from_round)
+    uint32_t log_use;                                // 0: this round's walks leave logs but none is used yet (the frame's first round)
     uint32_t log_max_len;                            // logs of at most this many records are written and used (what the launched kernels' tables hold)
     uint32_t log_sweep;                              // test hook: every footprint is worked out by sweeps (flood_rewalk_kernel)
     uint32_t* host_progress;                         // FloodBuffers::host_progress (nullptr: nobody is looking)
@@ -278,9 +272,8 @@ enum {
     kCtrlBigSeen = 22,  // 1: the frame had many long walks (kCtrlBigLong) when the current round began -- early hand-over
     kCtrlBarrierNext = 24,  // lowest seed of the next round's list that its exploration launch will not reach (no `rest` launch)
     kCtrlBigLong = 23,  // walks of the frame that really outgrew the first tier (more tiles than its table holds)
-    kCtrlMulti = 25,    // re-walks that started from several way-points at once (diagnostics: lr_stage_counters [10])
-    kCtrlNMulti = 26,   // length of the current round's list of way-point seeds (walked by a launch of their own on a second stream)
-    kCtrlNMultiNext = 27,  // ... of the next round's (being appended by the survivors pass)
+    // (25 and 27: unused)
+    kCtrlNRewalk = 26,   // length of this round's list of seeds that turn to their logs (FloodArgs::rewalk_list)
     kCtrlLogTotal = 28,  // footprint-log records handed out this frame
     kCtrlLogWalks = 29,  // re-walks from logs (diagnostics: lr_stage_counters [11])
     kCtrlLogGiveUp = 30, // ... that gave their log up (tables too small) [12]
@@ -428,7 +421,6 @@ struct LdsStoreT {
 };
 
 using LdsStore = LdsStoreT<kRingT, kHashT, uint8_t>;
-using LdsStoreBig = LdsStoreT<kRingBig, kHashBig, uint16_t>;
 
 struct SlabStore {
     static constexpr bool kDeferStamps = false;
@@ -925,11 +917,10 @@ __device__ int walk(const FloodArgs& A, uint32_t k, int b, float thr, float sn, 
 #endif
         if (st.head == st.tail) return 0;
         if ((st.tail - st.head) + 8u > S.ring_cap() || st.ntiles + 2u > tile_limit) return 1;
-        // a walk with a wide frontier (a region, not a line) is handed to the second tier early: its team of wavefronts
-        // takes a frontier eight records at a time
+        // a walk with a wide frontier (a region, not a line) is handed to the second tier early (FloodArgs::wide_tiles)
         if (st.ntiles >= wide_tiles && (st.tail - st.head) >= wide_front) return 1;
         if (st.steps > kMaxSteps) return 1;  // never reached by a terminating walk; treated like exhausted storage
-        if (kMode == 1 && st.steps >= A.g_cap) return 1;  // partial-commit walk: any connected part is as safe as the whole
+        if (kMode == 1 && st.steps >= kPartialSteps) return 1;  // partial-commit walk: any connected part is as safe as the whole
         cur = fetch_tile<kMode>(A, S, st.head, lr, lc, rx, ry, ring_lane, fw, G, own);
         LR_TICK(4)
     }
@@ -981,26 +972,6 @@ __device__ __forceinline__ void stamp_footprint(const FloodArgs& A, uint32_t k, 
     }
 }
 
-// Way-points of a finished walk (see kWpK): lanes 0 .. kWpK-1 take the (lane + 1) ntiles / (kWpK + 1)-th tile in order of
-// insertion and a walked pixel of it.  Written once per seed: footprints only shrink, the points stay representative.
-template <class Lds>
-__device__ __forceinline__ void save_waypoints(const FloodArgs& A, uint32_t k, const Lds& S, uint32_t ntiles, int lane) {
-    uint32_t* wp = A.waypoints + (size_t)k * kFloodWpWords;
-    if ((uint32_t)lane < kWpK) {
-        const uint32_t i = ((uint32_t)lane + 1u) * ntiles / (kWpK + 1u);
-        const uint32_t slot = S.ord[i];
-        const uint32_t tile = S.hk[slot] - 1u;
-        const uint64_t V = ((uint64_t)S.hv1[slot] << 32) | S.hv0[slot];
-        uint32_t q = kWpNone;  // (a tile whose entry pixels turned out unacceptable holds nothing)
-        if (V != 0ull) {
-            const uint32_t bit = (uint32_t)__builtin_ctzll(V);
-            q = ((tile >> 16) * 8u + (bit >> 3)) * (uint32_t)A.w + (tile & 0xFFFFu) * 8u + (bit & 7u);
-        }
-        wp[1 + lane] = q;
-    }
-    if (lane == 0) wp[0] = kWpK | (ntiles << 8);
-}
-
 // The records of a finished walk (see FloodArgs::log_buf): handed out of one buffer per frame by a counter.  A buffer that
 // is full leaves the seed without a log: it walks.
 template <class Lds>
@@ -1022,11 +993,10 @@ __device__ __forceinline__ void save_log(const FloodArgs& A, uint32_t k, const L
     }
 }
 
-// One seed's exploration by one wavefront (see walk).  kFirstTier: a walk that outgrows the store is handed to the
-// second tier (big_list) instead of going on in a slab.
-template <class Lds, bool kFirstTier>
-__device__ __forceinline__ void explore_seed(const FloodArgs& A, const BinTrig& trig, uint32_t k, Lds& L, Pending& P,
-                                             uint32_t* __restrict__ big_list, int lane, uint32_t t1_tiles = 0xFFFFFFFFu) {
+// One seed's exploration by one wavefront (see walk).  A walk that outgrows the store is handed to the second tier
+// (big_list) when there is one this round, and goes on in a slab otherwise.
+__device__ __forceinline__ void explore_seed(const FloodArgs& A, const BinTrig& trig, uint32_t k, LdsStore& L, Pending& P,
+                                             uint32_t* __restrict__ big_list, int lane, uint32_t t1_tiles) {
     const int s = (int)uni((uint32_t)A.seed_idx[k]);
     const int b = (int)uni((uint32_t)A.seed_bin[k]);
     const float thr = __uint_as_float(uni(__float_as_uint(A.seed_thr[k])));
@@ -1039,9 +1009,8 @@ __device__ __forceinline__ void explore_seed(const FloodArgs& A, const BinTrig& 
     // flood_partial_commit_kernel) and explores on from there: its walk passes through the pixels labelled with its index.
     const bool own = seed_label == k;
     if (seed_label < kMarkBit && !own) return;  // claimed by an earlier flood: dead (the survivors pass takes it off the list)
-    // on this round's list of way-point seeds: a team walks it right now, in a launch beside this one (enqueue_round)
-    // (bit 3: finished by a giant step between the rounds -- the survivors pass of this round takes it off the list)
-    if (kFirstTier && (uni((uint32_t)A.tier[k]) & 10u) != 0u) return;
+    // (tier bit 3: finished by a giant step between the rounds -- the survivors pass of this round takes it off the list)
+    if ((uni((uint32_t)A.tier[k]) & 8u) != 0u) return;
     if (!own && !(((seed_mask >> b) & 1) && directional(seed_dx, seed_dy, sn, cs) > thr)) {
         if (lane == 0) A.flags[k] = kFlagSelfFail;  // flood() accepts nothing, not even the seed
         return;
@@ -1050,28 +1019,24 @@ __device__ __forceinline__ void explore_seed(const FloodArgs& A, const BinTrig& 
     int rc = 1;
     // a walk that outgrew the first tier in an earlier round does not try it again (footprints only shrink, but
     // rarely below 190 tiles from above 1500 px)
-    // ... and a seed that left way-points on a long footprint in an earlier round goes straight to the second tier, whose
-    // team walks it from all of them at once
     // (not on a frame that went on staged after its first round -- kCtrlStaged: what a weak seed reached then says little
     // about what it reaches once the stronger seeds have committed)
-    const bool outgrown = kFirstTier && A.big_cap != 0u && (uni((uint32_t)A.tier[k]) & 1u) != 0u && uni(A.ctrl[kCtrlStaged]) == 0u;
-    const bool wp_seed = kFirstTier && A.big_cap != 0u && A.wp_min_tiles != 0xFFFFFFFFu && k < A.wp_cap &&
-                         uni(A.waypoints[(size_t)k * kFloodWpWords]) != 0u;
+    const bool outgrown = A.big_cap != 0u && (uni((uint32_t)A.tier[k]) & 1u) != 0u && uni(A.ctrl[kCtrlStaged]) == 0u;
     // A seed with a log (save_log) walks a few tiles only: most footprints have shrunk to a handful of tiles by their second
     // round, and a short walk is cheaper than the records of a long one.  If the walk is not over by then, the seed goes
     // on this round's list of flood_rewalk_kernel, which runs behind the exploration (nothing is stamped yet).
-    const uint32_t log_w = (kFirstTier && A.log_min_tiles != 0xFFFFFFFFu && k < A.log_seeds) ? uni(A.log_len[k]) : 0u;
+    const uint32_t log_w = (A.log_min_tiles != 0xFFFFFFFFu && k < A.log_seeds) ? uni(A.log_len[k]) : 0u;
     const uint32_t log_n = log_w & ~kLogShrunk;
     const bool has_log = log_n != 0u && log_n <= A.log_max_len && A.log_use != 0u;
-    const bool skip_first = (outgrown || wp_seed) && !has_log;
+    const bool skip_first = outgrown && !has_log;
     if (!skip_first) {
-        for (int i = lane; i < Lds::kHashN; i += 64) L.hk[i] = 0u;
+        for (int i = lane; i < LdsStore::kHashN; i += 64) L.hk[i] = 0u;
         P.pt[lane] = 0u;
         const int sr = s / A.w, sc = s - sr * A.w;
         L.put(0u, ((uint32_t)(sr >> 3) << 16) | (uint32_t)(sc >> 3), 1ull << ((sr & 7) * 8 + (sc & 7)));
-        // (with a second tier behind it, the first hands a walk over at A.t1_tiles tiles, before its table is full: the
+        // (with a second tier behind it, the first hands a walk over at t1_tiles tiles, before its table is full: the
         // second tier's team of wavefronts is the faster walker from there on)
-        const bool hand_over = kFirstTier && A.big_cap != 0u;
+        const bool hand_over = A.big_cap != 0u;
         if (has_log) {
             // (a log that the last round has already cut down to the footprint of then, and that is still twice the budget
             // long, goes on the list at once: the walk would only find out the same, 12 steps later)
@@ -1079,19 +1044,19 @@ __device__ __forceinline__ void explore_seed(const FloodArgs& A, const BinTrig& 
             if (!direct) rc = walk(A, k, b, thr, sn, cs, L, P, st, lane, own, nullptr, A.log_walk_tiles);
             if (rc != 0) {
                 uint32_t pos = 0;
-                if (lane == 0) pos = atomicAdd(&A.ctrl[kCtrlNMulti], 1u);
+                if (lane == 0) pos = atomicAdd(&A.ctrl[kCtrlNRewalk], 1u);
                 pos = (uint32_t)__shfl((int)pos, 0);
                 if (pos < kBigCap) {
-                    if (lane == 0) A.multi_list[pos] = k;
+                    if (lane == 0) A.rewalk_list[pos] = k;
                     return;
                 }
             }
         }
         if (rc != 0)  // (from the start, or from where the budgeted walk stands: the list was full)
             rc = walk(A, k, b, thr, sn, cs, L, P, st, lane, own, nullptr, hand_over ? t1_tiles : 0xFFFFFFFFu,
-                      hand_over ? A.t1_wide_tiles : 0xFFFFFFFFu, hand_over ? A.t1_wide_front : 0xFFFFFFFFu);
+                      hand_over ? A.wide_tiles : 0xFFFFFFFFu, hand_over ? A.wide_front : 0xFFFFFFFFu);
     }
-    if (kFirstTier && rc != 0 && A.big_cap == 0u && A.quiet != 0u) {
+    if (rc != 0 && A.big_cap == 0u && A.quiet != 0u) {
         // outgrew the first tier in a round that was enqueued without the second (the last frame never needed it): nothing is
         // stamped yet, the seed counts as unfinished -- nothing above it commits this round -- and the report says "not calm",
         // so the rounds that follow bring the second tier
@@ -1102,7 +1067,7 @@ __device__ __forceinline__ void explore_seed(const FloodArgs& A, const BinTrig& 
         }
         return;
     }
-    if (kFirstTier && rc != 0 && A.big_cap != 0u) {
+    if (rc != 0 && A.big_cap != 0u) {
         // outgrew the first tier: start again in the second (nothing is stamped yet, so nothing to undo)
         uint32_t pos = 0;
         if (lane == 0) pos = atomicAdd(&A.ctrl[kCtrlNBig], 1u);
@@ -1110,10 +1075,8 @@ __device__ __forceinline__ void explore_seed(const FloodArgs& A, const BinTrig& 
         if (pos < A.big_cap) {
             if (lane == 0) {
                 big_list[pos] = k;
-                if (!skip_first || outgrown) {  // (a way-point seed has not outgrown anything: it does not count towards the hold-back)
-                    A.tier[k] = 1;  // (bit 1 is clear here: listed seeds left above)
-                    atomicAdd(&A.ctrl[kCtrlBigTotal], 1u);
-                }
+                A.tier[k] = 1;
+                atomicAdd(&A.ctrl[kCtrlBigTotal], 1u);
             }
             // The second tier goes on from where this walk stands (nothing is stamped yet): the walked sets of its tiles
             // and the frontier records travel with the list entry.  A seed that skipped this tier has nothing to hand over.
@@ -1131,7 +1094,7 @@ __device__ __forceinline__ void explore_seed(const FloodArgs& A, const BinTrig& 
                 hb[kHandTable + 3u * i + 2u] = L.hv1[slot];
             }
             for (uint32_t i = (uint32_t)lane; i < nr; i += 64u) {
-                const uint32_t j = (st.head + i) & (uint32_t)(Lds::kRingN - 1);
+                const uint32_t j = (st.head + i) & (uint32_t)(LdsStore::kRingN - 1);
                 hb[kHandRing + 3u * i] = L.rt[j];
                 hb[kHandRing + 3u * i + 1u] = L.rlo[j];
                 hb[kHandRing + 3u * i + 2u] = L.rhi[j];
@@ -1139,7 +1102,7 @@ __device__ __forceinline__ void explore_seed(const FloodArgs& A, const BinTrig& 
             return;
         }
         if (skip_first) {  // no room in the second tier this round: walk in the first after all, then a slab
-            for (int i = lane; i < Lds::kHashN; i += 64) L.hk[i] = 0u;
+            for (int i = lane; i < LdsStore::kHashN; i += 64) L.hk[i] = 0u;
             P.pt[lane] = 0u;
             const int sr = s / A.w, sc = s - sr * A.w;
             L.put(0u, ((uint32_t)(sr >> 3) << 16) | (uint32_t)(sc >> 3), 1ull << ((sr & 7) * 8 + (sc & 7)));
@@ -1162,13 +1125,9 @@ __device__ __forceinline__ void explore_seed(const FloodArgs& A, const BinTrig& 
         }
     }
     stamp_footprint(A, k, L, st, lane);
-    // (only THIN footprints: a region's frontier is wide, the team's level-synchronous walk takes it eight tiles at a time as
-    // it is, and the second table entry per tile only costs -- natural 4K frame: flood 1.45 -> 1.61 ms without this test)
-    if (kFirstTier && rc == 0 && !wp_seed && st.ntiles >= A.wp_min_tiles && st.cnt <= kWpThinPx * st.ntiles && k < A.wp_cap)
-        save_waypoints(A, k, L, st.ntiles, lane);
     // the footprint's records for the seed's later rounds (flood_rewalk_kernel); one log per seed and frame: the records of
     // ANY finished walk of the seed hold its present footprint
-    if (kFirstTier && rc == 0 && st.ntiles >= A.log_min_tiles && st.ntiles <= A.log_max_len && k < A.log_seeds && uni(A.log_len[k]) == 0u)
+    if (rc == 0 && st.ntiles >= A.log_min_tiles && st.ntiles <= A.log_max_len && k < A.log_seeds && uni(A.log_len[k]) == 0u)
         save_log(A, k, L, st.ntiles, lane);
     if (rc != 0) {
         // LDS storage exhausted: move the walk to a global slab and carry on
@@ -1188,7 +1147,7 @@ __device__ __forceinline__ void explore_seed(const FloodArgs& A, const BinTrig& 
                 L.get(i, t, m);
                 G.put(i, t, m);
             }
-            for (int i = 0; i < Lds::kHashN; ++i) {
+            for (int i = 0; i < LdsStore::kHashN; ++i) {
                 const uint32_t key = L.hk[i];
                 if (key) {
                     uint32_t slot;
@@ -1264,12 +1223,12 @@ __device__ __forceinline__ void explore_body(const FloodArgs& A, const BinTrig& 
     const uint32_t* __restrict__ act = act_now(A);
     const uint32_t n_act = uni(A.ctrl[kCtrlNAct]), window = uni(A.ctrl[kCtrlWindow]);
     // A frame with many LONG walks (sixteen beyond what the first tier's table holds: natural images, frames of long bars)
-    // hands its walks over earlier from the next round on -- at 32 tiles instead of 190: the first tier's rounds last as
+    // hands its walks over earlier from the next round on -- at kRegionalTiles = 32 tiles instead of 190: the first tier's rounds last as
     // long as its longest walk, and the second tier has 512 teams to take the walks side by side (with 128 teams the long
     // bars' thousands of thin walks queued up behind each other and the same rule cost that frame 0.5 ms; with 512 it
     // gains 0.3).  The synthetic bench frames never get there (0-7 long walks), and handing THEIR walks over early costs
     // them 0.3-0.9 ms: the tiers' kernels run one after the other, and a thin walk gains nothing from a team.
-    const uint32_t t1_usual = uni(A.ctrl[kCtrlBigSeen]) != 0u ? min(A.t1_tiles, A.t1_regional) : A.t1_tiles;
+    const uint32_t t1_usual = uni(A.ctrl[kCtrlBigSeen]) != 0u ? kRegionalTiles : 0xFFFFFFFFu;
     // The second tier's list is full already when this workgroup starts -- eight thousand long walks in this round: a frame of
     // overlapping giants, a noiseless gradient whose every pixel is a seed -- so a walk that outgrows this tier will be held
     // back whatever its length (explore_seed): it is held at kFullTiles tiles instead of walking on to the table's 190 (radial
@@ -1288,16 +1247,16 @@ __device__ __forceinline__ void explore_body(const FloodArgs& A, const BinTrig& 
         // (a round without a `rest` launch whose list is longer than its grid walks the FIRST entries: the survivors pass
         // that wrote the list has put a barrier at the lowest seed behind them -- enqueue_round)
         const bool fwd = A.no_rest != 0u && n_act > gridDim.x;
-        const uint32_t k = uni(act[(A.from_end && !fwd) ? n_act - 1u - ai : ai]);
+        const uint32_t k = uni(act[!fwd ? n_act - 1u - ai : ai]);
         if (k >= window) return;  // not yet in the staged window (stays active)
         const uint32_t t1_tiles = (tier2_full && k != lowest) ? min(t1_usual, kFullTiles) : t1_usual;
-        explore_seed<LdsStore, true>(A, trig, k, L, P, big_list, lane, t1_tiles);
+        explore_seed(A, trig, k, L, P, big_list, lane, t1_tiles);
     } else {
         for (uint32_t ai = first + uni(blockIdx.x); ai < n_act; ai += gridDim.x) {
-            const uint32_t k = uni(act[A.from_end ? n_act - 1u - ai : ai]);
+            const uint32_t k = uni(act[n_act - 1u - ai]);
             if (k >= window) continue;
             const uint32_t t1_tiles = (tier2_full && k != lowest) ? min(t1_usual, kFullTiles) : t1_usual;
-            explore_seed<LdsStore, true>(A, trig, k, L, P, big_list, lane, t1_tiles);
+            explore_seed(A, trig, k, L, P, big_list, lane, t1_tiles);
         }
     }
 }
@@ -1312,27 +1271,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void flood_explore_rest_kernel(
     FloodArgs A, BinTrig trig, uint32_t* __restrict__ big_list, uint32_t first) {
     explore_body<true>(A, trig, big_list, first);
-}
-
-// Second storage tier: the same walk from the start with a 1024-record ring and a 2048-tile table (dynamic LDS,
-// kBigLdsBytes), for the seeds the first tier handed over this round.
-constexpr size_t kBigLdsBytes = (size_t)(3 * kRingBig + 3 * kHashBig + 2 * kPend) * 4 + (size_t)kHashBig * 2;
-__global__ __launch_bounds__(64) void flood_explore_big_kernel(FloodArgs A, BinTrig trig,
-                                                               uint32_t* __restrict__ big_list) {
-    extern __shared__ uint32_t s_big[];
-    const int lane = threadIdx.x & 63;
-    if (giant_pending(A)) return;
-    const uint32_t ai = uni(blockIdx.x);
-    const uint32_t n_big = uni(A.ctrl[kCtrlNBig]);
-    if (ai >= (n_big < A.big_cap ? n_big : A.big_cap)) return;
-    const uint32_t k = uni(big_list[ai]);
-    uint32_t* ring = s_big;
-    uint32_t* hash = ring + 3 * kRingBig;
-    uint32_t* pend = hash + 3 * kHashBig;
-    uint16_t* ord = reinterpret_cast<uint16_t*>(pend + 2 * kPend);
-    LdsStoreBig L{ring, ring + kRingBig, ring + 2 * kRingBig, hash, hash + kHashBig, hash + 2 * kHashBig, ord};
-    Pending P{pend, pend + kPend};
-    explore_seed<LdsStoreBig, false>(A, trig, k, L, P, big_list, lane);
 }
 
 // ---- Second tier, cooperative: a TEAM of wavefronts walks one footprint -------------------------------------------------
@@ -1365,8 +1303,6 @@ constexpr uint32_t kVoidTile = 0xFFFFFFFFu;
 
 struct TeamShared {
     uint32_t tail, end, ntiles, blocked, overflow, cnt, steps, pad;
-    uint32_t adj[8];          // multi-source walk: sources whose regions share a pixel with source i (bit per source)
-    uint32_t reach, ctiles;   // ... sources connected to the seed's own; tiles of the footprint kept
     uint32_t blocker, pad2;   // lowest seed whose stamp this walk's stamps met (WalkState::blocker)
 };
 __device__ __forceinline__ uint32_t lds_now(const uint32_t* p) {
@@ -1442,39 +1378,6 @@ struct TeamStore {
         rhi[j] = (uint32_t)(E >> 32);
     }
     __device__ void mark_processed(uint32_t i) const { rt[i & (uint32_t)(kRingTeam - 1)] = kVoidTile; }
-    // read-only look-up, per lane (the walk is over: nothing is inserted any more)
-    __device__ bool find_ro(uint32_t tile, uint32_t& slot) const {
-        const uint32_t key = tile + 1u;
-        uint32_t hs = (key * 2654435761u) >> kHashShift;
-        for (int probe = 0; probe < kHashBig; ++probe) {
-            const uint32_t cur = hk[hs];
-            if (cur == key) {
-                slot = hs;
-                return true;
-            }
-            if (cur == 0u) return false;
-            hs = (hs + 1) & (kHashBig - 1);
-        }
-        return false;
-    }
-};
-
-// A multi-source walk keeps, in the SAME table, one entry per (tile, source) -- what that source has seen of the tile as
-// connected to itself -- and one per tile for the pixels claimed so far by anybody; the source (0 = the seed itself,
-// 1.. = way-points) or kSrcClaim sits in the four high bits of the tile id (tile rows stay below 4096: frames of fewer
-// than 2^29 pixels).  Ring records carry the source the same way.  This view hands fetch_tile the plain tile id and
-// directs its look-up to the entry of the record's source.
-struct MultiView {
-    const TeamStore& S;
-    mutable uint32_t tag;
-    __device__ void get(uint32_t i, uint32_t& tile, uint64_t& m) const {
-        uint32_t t;
-        S.get(i, t, m);
-        tag = t & kSrcMask;
-        tile = t & ~kSrcMask;
-    }
-    __device__ bool lookup(uint32_t tile, uint32_t& slot, uint64_t& V) const { return S.lookup(tile | tag, slot, V); }
-    __device__ void value(uint32_t slot, uint64_t& V) const { S.value(slot, V); }
 };
 
 // The same store in GLOBAL memory (one overflow slab of FloodBuffers: 16 Ki ring records, a table of 64 Ki tiles), for a
@@ -1558,8 +1461,8 @@ struct TeamGlobalStore {
 // neighbour records of a step, one direction per lane 0..7 (as push8; no merging with pending records of the same tile:
 // duplicates of a level are taken by different wavefronts at the same time)
 template <class Store>
-__device__ __forceinline__ void team_push8(Store& S, uint32_t tile, uint64_t H, int lane, const PushLane& c, uint32_t tag = 0u) {
-    const uint32_t nt = (tile + c.off) | tag;  // (tag: the source of a multi-source walk; lanes whose neighbour lies outside the frame carry no entry)
+__device__ __forceinline__ void team_push8(Store& S, uint32_t tile, uint64_t H, int lane, const PushLane& c) {
+    const uint32_t nt = tile + c.off;  // (lanes whose neighbour lies outside the frame carry no entry)
     const uint32_t key = nt + 1u;
     const uint64_t src = (H >> c.shamt) & (uint64_t)c.msk;
     uint64_t E = (c.spread ? spread_col(src) : src) << c.sh;
@@ -1595,19 +1498,7 @@ __device__ __forceinline__ void team_push8(Store& S, uint32_t tile, uint64_t H, 
 
 // returns 0 when the footprint is complete; 1 when ring or table ran out: *begin_out is then the first ring index that
 // may hold an unprocessed record (processed ones read kVoidTile)
-// kMulti (TeamStore only): the records carry a source each -- the seed's own pixel and the way-points its last walk left
-// (kWpK) -- and every source grows its region at once.  A source keeps what it has SEEN as connected to itself in entries of
-// its own (V_s, whole in-tile components as ever) and goes on only from the pixels it was the first of all sources to CLAIM
-// (the tile's claim entry, atomic OR): the regions share the footprint out between them and stop where they meet.  Two
-// regions that touch have seen a common pixel: if p (claimed by s) and q (claimed by s') are neighbours, s pushed a record
-// for q when it claimed p -- the neighbour filter looks at s's OWN entry of q's tile -- and q, though claimed already,
-// entered V_s as well as V_s'.  After the walk (flood_explore_team_kernel) sources with a common pixel in some tile are
-// joined, and the footprint is the union of V_s over the sources joined with source 0 -- exactly the pixels connected to
-// the seed: each V_s is connected and contains its starting point; every pixel on a path from the seed is claimed by some
-// source (induction along the path: a claimed pixel's in-tile component and ring neighbours are all visited by its
-// claimer), and consecutive pixels of the path have claimers that saw a common pixel.  Way-points the footprint has lost
-// grow regions of their own that join nothing and are dropped.
-template <class Store, bool kMulti = false>
+template <class Store>
 __device__ int team_walk(const FloodArgs& A, uint32_t k, int b, float thr, float sn, float cs, Store& S, int lane,
                          int wave, bool own, uint32_t first_level, uint32_t tile_cap, uint32_t* begin_out, uint32_t* steps_out) {
     TeamShared* sh = S.sh;
@@ -1632,20 +1523,12 @@ __device__ int team_walk(const FloodArgs& A, uint32_t k, int b, float thr, float
         for (uint32_t i = gb + (uint32_t)wave; i < ge; i += kTeamWaves) {
             // room for what the steps in flight may add: eight records and one tile each
             if ((uni(lds_now(&sh->tail)) - gb) + 8u * kTeamWaves > S.ring_cap() ||
-                uni(lds_now(&sh->ntiles)) + (kMulti ? 2u : 1u) * kTeamWaves + 1u > min(S.hash_limit(), tile_cap)) {
+                uni(lds_now(&sh->ntiles)) + kTeamWaves + 1u > min(S.hash_limit(), tile_cap)) {
                 if (lane == 0) sh->overflow = 1u;
                 break;
             }
             if (uni(lds_now(&sh->overflow)) != 0u) break;
-            uint32_t tag = 0u;
-            TileFetch cur;
-            if constexpr (kMulti) {
-                const MultiView MV{S, 0u};
-                cur = fetch_tile<0>(A, MV, i, lr, lc, rx, ry, ring_lane, fw, G, own);
-                tag = MV.tag;
-            } else {
-                cur = fetch_tile<0>(A, S, i, lr, lc, rx, ry, ring_lane, fw, G, own);
-            }
+            const TileFetch cur = fetch_tile<0>(A, S, i, lr, lc, rx, ry, ring_lane, fw, G, own);
             ++steps;
             const uint32_t tile = cur.tile;
             uint64_t Am = cur.inside & m_ne(cur.dm & bin_bit, 0u) & m_gt_f(directional(cur.dx, cur.dy, sn, cs), thr);
@@ -1665,21 +1548,11 @@ __device__ int team_walk(const FloodArgs& A, uint32_t k, int b, float thr, float
                 const uint64_t New = R & ~cur.V;
                 if (New != 0ull) {
                     uint64_t was = 0ull;
-                    if constexpr (kMulti) {
-                        uint32_t slot_c;
-                        uint64_t claimed;
-                        (void)S.lookup(tile | kSrcClaim, slot_c, claimed);  // (find or insert)
-                        if (lane == 0) {
-                            was = S.add_walked(slot_c, New);     // claimed before by whichever source
-                            (void)S.add_walked(cur.slot, New);   // seen by this one, claimed or not
-                        }
-                    } else {
-                        if (lane == 0) was = S.add_walked(cur.slot, New);
-                    }
+                    if (lane == 0) was = S.add_walked(cur.slot, New);
                     const uint64_t first_here = New & ~uni64(was);  // the pixels this step was the first to walk
                     if (first_here != 0ull) {
                         const uint64_t H = Rg & m_ne64(first_here & adj, 0ull);
-                        if (H != 0ull) team_push8(S, tile, H, lane, pc, tag);
+                        if (H != 0ull) team_push8(S, tile, H, lane, pc);
                     }
                 }
             }
@@ -1711,16 +1584,13 @@ __device__ int team_walk(const FloodArgs& A, uint32_t k, int b, float thr, float
 // registers.  A first version counted the wavefronts "trying to claim" in a counter of its own: three and more idle
 // wavefronts then kept each other waiting for ever, each finding another in the middle of its attempt.  Not in the tree.)
 constexpr size_t kTeamLdsBytes = (size_t)(3 * kRingTeam + 3 * kHashBig + 2 * kPend) * 4 + (size_t)kHashBig * 2 + sizeof(TeamShared);
-// from_multi_list: the list is the round's way-point seeds (A.multi_list, written by the last survivors pass) instead of
-// what this round's first tier handed over; nothing comes with its entries.
 __global__ __launch_bounds__(64 * kTeamWaves) void flood_explore_team_kernel(FloodArgs A, BinTrig trig,
-                                                                             const uint32_t* __restrict__ big_list,
-                                                                             uint32_t from_multi_list) {
+                                                                             const uint32_t* __restrict__ big_list) {
     extern __shared__ uint32_t s_team[];
     const int lane = threadIdx.x & 63, wave = (int)uni(threadIdx.x >> 6);
     if (uni(A.ctrl[kCtrlNAct]) == 0u || giant_pending(A)) return;  // a round enqueued past the end (or past a stall: the listed seeds are the ordered tail's)
-    const uint32_t n_big_raw = uni(A.ctrl[from_multi_list ? kCtrlNMulti : kCtrlNBig]);
-    const uint32_t n_big = from_multi_list ? min(n_big_raw, kBigCap) : (n_big_raw < A.big_cap ? n_big_raw : A.big_cap);
+    const uint32_t n_big_raw = uni(A.ctrl[kCtrlNBig]);
+    const uint32_t n_big = n_big_raw < A.big_cap ? n_big_raw : A.big_cap;
     uint32_t* ring = s_team;
     uint32_t* hash = ring + 3 * kRingTeam;
     uint32_t* pend = hash + 3 * kHashBig;
@@ -1729,9 +1599,6 @@ __global__ __launch_bounds__(64 * kTeamWaves) void flood_explore_team_kernel(Flo
     TeamStore S{ring, ring + kRingTeam, ring + 2 * kRingTeam, hash, hash + kHashBig, hash + 2 * kHashBig, ord, sh};
     for (uint32_t ai = uni(blockIdx.x); ai < n_big; ai += gridDim.x) {
         const uint32_t k = uni(big_list[ai]);
-        // (a listed seed above the round's window is not walked at all, like every seed there: a commit is only valid if
-        // every lower active seed has walked)
-        if (from_multi_list && k >= uni(A.ctrl[kCtrlWindow])) continue;
         const int s = (int)uni((uint32_t)A.seed_idx[k]);
         const int b = (int)uni((uint32_t)A.seed_bin[k]);
         const float thr = __uint_as_float(uni(__float_as_uint(A.seed_thr[k])));
@@ -1752,7 +1619,7 @@ __global__ __launch_bounds__(64 * kTeamWaves) void flood_explore_team_kernel(Flo
         // of the round closes the window in front of them -- kCtrlStaged: the strongest quarter first, twice as many a round.
         // (only in a round whose end will close the window: flood_advance tests the same words)
         if (A.giant_hold != 0u && k != uni(A.ctrl[kCtrlLowest]) &&
-            ((k >= (uni(A.ctrl[kCtrlNSeeds]) >> 2) && giants_many(A.ctrl, A.giant_many)) || (!from_multi_list && giants_all(A.ctrl)))) {
+            ((k >= (uni(A.ctrl[kCtrlNSeeds]) >> 2) && giants_many(A.ctrl, A.giant_many)) || giants_all(A.ctrl))) {
             if (threadIdx.x == 0) {
                 A.flags[k] = kFlagIncomplete;
                 atomicMin(&A.ctrl[kCtrlBarrier], k);
@@ -1761,98 +1628,51 @@ __global__ __launch_bounds__(64 * kTeamWaves) void flood_explore_team_kernel(Flo
         }
         // what the first tier handed over with this entry (A.big_cap entries at most, so ai is its position in the list)
         const uint32_t* hb = A.handover + (size_t)ai * kFloodHandWords;
-        const uint32_t h_recs_in = from_multi_list ? 0u : min(uni(hb[1]), kHandRecs);
-        // A seed that left way-points on its footprint (save_waypoints) and comes without a walk in progress is walked from
-        // all of them at once (team_walk, kMulti).  Should the table run out -- two entries a tile -- it starts again, plainly.
-        const uint32_t wp_hdr = (A.wp_min_tiles != 0xFFFFFFFFu && k < A.wp_cap) ? uni(A.waypoints[(size_t)k * kFloodWpWords]) : 0u;
-        const bool multi = h_recs_in == 0u && wp_hdr != 0u && (wp_hdr >> 8) <= kWpMaxTiles;
+        const uint32_t h_recs = min(uni(hb[1]), kHandRecs);
         uint32_t begin = 0u, my_steps = 0u;
-        int rc = 0;
-        bool did_multi = false;
-        if (multi) {
-            __syncthreads();  // the previous seed's table is no longer read
-            for (int i = (int)threadIdx.x; i < kHashBig; i += 64 * kTeamWaves) {
-                S.hk[i] = 0u;
-                S.hv0[i] = 0u;
-                S.hv1[i] = 0u;
-            }
-            if (threadIdx.x <= kWpK) {  // source 0: the seed's own pixel; 1 .. kWpK: the way-points
-                const uint32_t t = threadIdx.x;
-                uint32_t q = t == 0u ? (uint32_t)s : A.waypoints[(size_t)k * kFloodWpWords + t];
-                uint64_t m = 0ull;
-                if (q == kWpNone || q >= (uint32_t)A.w * (uint32_t)A.h) q = (uint32_t)s;  // (no way-point here: an empty record)
-                else m = 1ull << (((q / (uint32_t)A.w) & 7u) * 8u + ((q % (uint32_t)A.w) & 7u));
-                const uint32_t qr = q / (uint32_t)A.w, qc = q % (uint32_t)A.w;
-                S.rt[t] = (((qr >> 3) << 16) | (qc >> 3)) | (t << kSrcShift);
-                S.rlo[t] = (uint32_t)m;
-                S.rhi[t] = (uint32_t)(m >> 32);
-                sh->adj[t] = 0u;
-            }
-            if (threadIdx.x == 0) {
-                sh->tail = kWpK + 1u;
-                sh->end = kWpK + 1u;
-                sh->ntiles = 0u;
-                sh->blocked = 0u;
-                sh->blocker = 0xFFFFFFFFu;
-                sh->overflow = 0u;
-                sh->cnt = 0u;
-                sh->steps = 0u;
-                sh->reach = 0u;
-                sh->ctiles = 0u;
-            }
-            __syncthreads();
-            uint32_t multi_steps = 0u;
-            rc = team_walk<TeamStore, true>(A, k, b, thr, sn, cs, S, lane, wave, own, kWpK + 1u, A.team_tiles, &begin, &multi_steps);
-            my_steps += multi_steps;
-            did_multi = rc == 0;
+        __syncthreads();  // the previous seed's table is no longer read
+        for (int i = (int)threadIdx.x; i < kHashBig; i += 64 * kTeamWaves) {
+            S.hk[i] = 0u;
+            S.hv0[i] = 0u;
+            S.hv1[i] = 0u;
         }
-        if (!did_multi) {
-            __syncthreads();  // the previous seed's table is no longer read
-            for (int i = (int)threadIdx.x; i < kHashBig; i += 64 * kTeamWaves) {
-                S.hk[i] = 0u;
-                S.hv0[i] = 0u;
-                S.hv1[i] = 0u;
+        const uint32_t h_tiles = min(uni(hb[0]), kHandTiles);
+        const uint32_t first_level = h_recs ? h_recs : 1u;
+        __syncthreads();  // (table cleared)
+        if (h_recs) {
+            for (uint32_t t = threadIdx.x; t < h_tiles; t += 64u * kTeamWaves) {
+                const uint32_t key = hb[kHandTable + 3u * t];
+                uint32_t hs = (key * 2654435761u) >> TeamStore::kHashShift;
+                while (atomicCAS(&S.hk[hs], 0u, key) != 0u) hs = (hs + 1u) & (uint32_t)(kHashBig - 1);  // (the tiles are distinct)
+                S.hv0[hs] = hb[kHandTable + 3u * t + 1u];
+                S.hv1[hs] = hb[kHandTable + 3u * t + 2u];
+                S.ord[t] = (uint16_t)hs;
             }
-            // what the first tier handed over with this entry (A.big_cap entries at most, so ai is its position in the list)
-            const uint32_t* hb = A.handover + (size_t)ai * kFloodHandWords;
-            const uint32_t h_tiles = min(uni(hb[0]), kHandTiles), h_recs = h_recs_in;
-            const uint32_t first_level = h_recs ? h_recs : 1u;
-            __syncthreads();  // (table cleared)
-            if (h_recs) {
-                for (uint32_t t = threadIdx.x; t < h_tiles; t += 64u * kTeamWaves) {
-                    const uint32_t key = hb[kHandTable + 3u * t];
-                    uint32_t hs = (key * 2654435761u) >> TeamStore::kHashShift;
-                    while (atomicCAS(&S.hk[hs], 0u, key) != 0u) hs = (hs + 1u) & (uint32_t)(kHashBig - 1);  // (the tiles are distinct)
-                    S.hv0[hs] = hb[kHandTable + 3u * t + 1u];
-                    S.hv1[hs] = hb[kHandTable + 3u * t + 2u];
-                    S.ord[t] = (uint16_t)hs;
-                }
-                for (uint32_t t = threadIdx.x; t < h_recs; t += 64u * kTeamWaves) {
-                    S.rt[t] = hb[kHandRing + 3u * t];
-                    S.rlo[t] = hb[kHandRing + 3u * t + 1u];
-                    S.rhi[t] = hb[kHandRing + 3u * t + 2u];
-                }
+            for (uint32_t t = threadIdx.x; t < h_recs; t += 64u * kTeamWaves) {
+                S.rt[t] = hb[kHandRing + 3u * t];
+                S.rlo[t] = hb[kHandRing + 3u * t + 1u];
+                S.rhi[t] = hb[kHandRing + 3u * t + 2u];
             }
-            if (threadIdx.x == 0) {
-                if (!h_recs) {
-                    const int sr = s / A.w, sc = s - sr * A.w;
-                    const uint64_t m = 1ull << ((sr & 7) * 8 + (sc & 7));
-                    S.rt[0] = ((uint32_t)(sr >> 3) << 16) | (uint32_t)(sc >> 3);
-                    S.rlo[0] = (uint32_t)m;
-                    S.rhi[0] = (uint32_t)(m >> 32);
-                }
-                sh->tail = first_level;
-                sh->end = first_level;
-                sh->ntiles = h_recs ? h_tiles : 0u;
-                sh->blocked = 0u;
-                sh->blocker = 0xFFFFFFFFu;
-                sh->overflow = 0u;
-                sh->cnt = 0u;
-                sh->steps = h_recs ? hb[2] : 0u;
-            }
-            __syncthreads();
-            rc = team_walk(A, k, b, thr, sn, cs, S, lane, wave, own, first_level, A.team_tiles, &begin, &my_steps);
         }
+        if (threadIdx.x == 0) {
+            if (!h_recs) {
+                const int sr = s / A.w, sc = s - sr * A.w;
+                const uint64_t m = 1ull << ((sr & 7) * 8 + (sc & 7));
+                S.rt[0] = ((uint32_t)(sr >> 3) << 16) | (uint32_t)(sc >> 3);
+                S.rlo[0] = (uint32_t)m;
+                S.rhi[0] = (uint32_t)(m >> 32);
+            }
+            sh->tail = first_level;
+            sh->end = first_level;
+            sh->ntiles = h_recs ? h_tiles : 0u;
+            sh->blocked = 0u;
+            sh->blocker = 0xFFFFFFFFu;
+            sh->overflow = 0u;
+            sh->cnt = 0u;
+            sh->steps = h_recs ? hb[2] : 0u;
+        }
+        __syncthreads();
+        int rc = team_walk(A, k, b, thr, sn, cs, S, lane, wave, own, first_level, A.team_tiles, &begin, &my_steps);
         // (team_walk ends behind a barrier: every wavefront sees the final table)
         WalkState st{0u, 0u, 0u, 0u, false, 0u, 0u};
         uint32_t px = 0u;
@@ -1866,10 +1686,8 @@ __global__ __launch_bounds__(64 * kTeamWaves) void flood_explore_team_kernel(Flo
                 A.flags[k] = kFlagIncomplete;
                 atomicMin(&A.ctrl[kCtrlBarrier], k);
                 atomicAdd(&A.ctrl[kCtrlGiants], 1u);
-                if (!from_multi_list) {
-                    atomicAdd(&A.ctrl[kCtrlTeamGiants], 1u);
-                    atomicAdd(&A.ctrl[kCtrlTeamDone], 1u);
-                }
+                atomicAdd(&A.ctrl[kCtrlTeamGiants], 1u);
+                atomicAdd(&A.ctrl[kCtrlTeamDone], 1u);
             }
             continue;
         }
@@ -1941,80 +1759,7 @@ __global__ __launch_bounds__(64 * kTeamWaves) void flood_explore_team_kernel(Flo
                 st.ntiles = nt;
             }
         }
-        if (did_multi) {
-            // Which sources belong to the seed?  Two sources that have seen a common pixel are joined (see team_walk); the
-            // footprint is what the sources joined with source 0 have seen.
-            for (int i = (int)threadIdx.x; i < kHashBig; i += 64 * kTeamWaves) {
-                const uint32_t key = S.hk[i];
-                if (key == 0u) continue;
-                const uint32_t tk = key - 1u, src = tk >> kSrcShift;
-                if (src == 0u || src > kWpK) continue;  // (source 0 is met from the other side; claim entries join nobody)
-                const uint64_t V = S.peek_walked((uint32_t)i);
-                if (V == 0ull) continue;
-                for (uint32_t s2 = 0u; s2 < src; ++s2) {
-                    uint32_t sl;
-                    if (S.find_ro((tk & ~kSrcMask) | (s2 << kSrcShift), sl) && (S.peek_walked(sl) & V) != 0ull) {
-                        atomicOr(&sh->adj[src], 1u << s2);
-                        atomicOr(&sh->adj[s2], 1u << src);
-                    }
-                }
-            }
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                uint32_t reach = 1u;
-                for (;;) {
-                    uint32_t nr = reach;
-                    for (uint32_t s2 = 0u; s2 <= kWpK; ++s2)
-                        if ((reach >> s2) & 1u) nr |= sh->adj[s2];
-                    if (nr == reach) break;
-                    reach = nr;
-                }
-                sh->reach = reach;
-                atomicAdd(&A.ctrl[kCtrlMulti], 1u);
-            }
-            __syncthreads();
-            // Stamps and pixel count, tile by tile over the claim entries (one per tile of whatever any source walked): the
-            // tile's share of the footprint is what the joined sources have seen of it, looked up by lanes 0 .. kWpK side by side.
-            const uint32_t reach = sh->reach, nt = sh->ntiles, mine = kMarkBit | k;
-            const int lr = lane >> 3, lc = lane & 7;
-            bool foreign = false;
-            uint32_t ctl = 0u;
-            for (uint32_t i = (uint32_t)wave; i < nt; i += kTeamWaves) {
-                const uint32_t slot = uni((uint32_t)S.ord[i]);
-                const uint32_t tk = uni(S.hk[slot]) - 1u;
-                if ((tk & kSrcMask) != kSrcClaim) continue;
-                const uint32_t T = tk & ~kSrcMask;
-                uint32_t u0 = 0u, u1 = 0u;
-                if ((uint32_t)lane <= kWpK && ((reach >> lane) & 1u)) {
-                    uint32_t sl;
-                    if (S.find_ro(T | ((uint32_t)lane << kSrcShift), sl)) {
-                        u0 = S.hv0[sl];
-                        u1 = S.hv1[sl];
-                    }
-                }
-#pragma unroll
-                for (int off = 4; off >= 1; off >>= 1) {
-                    u0 |= (uint32_t)__shfl_xor((int)u0, off);
-                    u1 |= (uint32_t)__shfl_xor((int)u1, off);
-                }
-                const uint64_t U = uni64(u0, u1);
-                if (U == 0ull) continue;
-                ctl += 1u;
-                if (lane == 0) px += (uint32_t)__popcll(U);
-                if ((U >> lane) & 1ull) {
-                    const size_t q = (size_t)((T >> 16) * 8 + lr) * A.w + ((T & 0xFFFFu) * 8 + lc);
-                    const uint32_t old = atomicMin(&A.label[q], mine);
-                    A.dirty[q >> 8] = 1;
-                    if (old > mine) {
-                        if (old != kLabelFree) A.blocked[old & ~kMarkBit] = 1u;
-                    } else if (old < mine && old >= kMarkBit) {
-                        foreign = true;
-                    }
-                }
-            }
-            if (__ballot(foreign)) st.blocked = true;
-            if (lane == 0 && ctl) atomicAdd(&sh->ctiles, ctl);
-        } else if (!in_slab) {
+        if (!in_slab) {
             st.ntiles = sh->ntiles;
             stamp_footprint(A, k, S, st, lane, (uint32_t)wave * 8u, 8u * kTeamWaves);
             for (int i = (int)threadIdx.x; i < kHashBig; i += 64 * kTeamWaves) px += (uint32_t)__popc(S.hv0[i]) + (uint32_t)__popc(S.hv1[i]);
@@ -2033,15 +1778,10 @@ __global__ __launch_bounds__(64 * kTeamWaves) void flood_explore_team_kernel(Flo
         st.steps = sh->steps;
         st.blocked = sh->blocked != 0u;
         st.blocker = sh->blocker;
-        if (did_multi) st.ntiles = sh->ctiles;
-        // a long walk that came here for the first time (handed over by the first tier) leaves its way-points now
-        if (!did_multi && !in_slab && rc == 0 && wp_hdr == 0u && k < A.wp_cap && st.ntiles >= A.wp_min_tiles && st.ntiles <= kWpMaxTiles &&
-            st.cnt <= kWpThinPx * st.ntiles)
-            save_waypoints(A, k, S, st.ntiles, lane);
         // a marked giant whose footprint fits by now is an ordinary seed again
         if (rc == 0 && lane == 0 && (A.tier[k] & 4u)) A.tier[k] = (uint8_t)(A.tier[k] & ~4u);
         // ... and its records (save_log), for flood_rewalk_kernel
-        if (!did_multi && !in_slab && rc == 0 && st.ntiles >= A.log_min_tiles && st.ntiles <= A.log_max_len && k < A.log_seeds &&
+        if (!in_slab && rc == 0 && st.ntiles >= A.log_min_tiles && st.ntiles <= A.log_max_len && k < A.log_seeds &&
             uni(A.log_len[k]) == 0u)
             save_log(A, k, S, st.ntiles, lane);
         if (rc != 0 && lane == 0) {  // no slab to go to, or the slab ran out as well: the ordered tail will finish this seed
@@ -2059,7 +1799,7 @@ __global__ __launch_bounds__(64 * kTeamWaves) void flood_explore_team_kernel(Flo
             // (the LOWEST of the lower seeds it met.  Waiting for the highest -- the chain below it resolves from its lowest seed
             // up, and the walk finds the next of them in its way every other round -- was measured and is no better: the window
             // stays closed longer and the seeds above pay with rounds of their own, 33 instead of 22 on the frame of soft blobs)
-            A.blk[k] = (rc == 0 && st.blocked && st.blocker < k && st.steps >= A.defer_steps && k >= (A.ctrl[kCtrlNSeeds] >> 1) && no_log) ? st.blocker : 0xFFFFFFFFu;
+            A.blk[k] = (rc == 0 && st.blocked && st.blocker < k && st.steps >= kDeferSteps && k >= (A.ctrl[kCtrlNSeeds] >> 1) && no_log) ? st.blocker : 0xFFFFFFFFu;
         }
         if (lane == 0) {
             A.count[k] = st.cnt;
@@ -2068,7 +1808,7 @@ __global__ __launch_bounds__(64 * kTeamWaves) void flood_explore_team_kernel(Flo
             // (what makes a frame "regional", explore_body: walks the first tier could not have held, however early they
             // were handed over)
             if (st.ntiles > kHandTiles) atomicAdd(&A.ctrl[kCtrlBigLong], 1u);
-            if (!from_multi_list) atomicAdd(&A.ctrl[kCtrlTeamDone], 1u);  // (giants_all)
+            atomicAdd(&A.ctrl[kCtrlTeamDone], 1u);  // (giants_all)
         }
     }
 }
@@ -2082,7 +1822,7 @@ __global__ __launch_bounds__(64 * kTeamWaves) void flood_explore_team_kernel(Flo
 // (tile, walked pixels) records (save_log), and in the seed's later rounds
 //  - the exploration walks log_walk_tiles tiles of it (most footprints have shrunk to a handful of tiles by their second
 //    round, and a short walk is cheaper than the records of a long one); if that is not the end of the walk the seed goes
-//    on the round's list (multi_list; a log that the last round has cut down already and is still long goes there at once),
+//    on the round's list (rewalk_list; a log that the last round has cut down already and is still long goes there at once),
 //  - this kernel, launched behind the exploration, works the footprint out from the records, a workgroup a seed: the
 //    records' pixels are looked at once (all tiles' loads in flight together -- no chain), the components of each tile's
 //    surviving pixels become nodes (a thread a tile, 64-bit masks), pairs of nodes of neighbouring tiles that touch are
@@ -2168,7 +1908,7 @@ __global__ __launch_bounds__(kThreads) void flood_rewalk_kernel(FloodArgs A, con
     const int lane = threadIdx.x & 63, wave = (int)uni(threadIdx.x >> 6);
     const int lr = lane >> 3, lc = lane & 7;
     if (uni(A.ctrl[kCtrlNAct]) == 0u || giant_pending(A)) return;  // a round enqueued past the end, or past a stall
-    const uint32_t n_list = min(uni(A.ctrl[kCtrlNMulti]), kBigCap);
+    const uint32_t n_list = min(uni(A.ctrl[kCtrlNRewalk]), kBigCap);
     const uint32_t window = uni(A.ctrl[kCtrlWindow]);
     for (uint32_t ai = uni(blockIdx.x); ai < n_list; ai += gridDim.x) {
         const uint32_t k = uni(list[ai]);
@@ -2589,8 +2329,8 @@ __device__ __forceinline__ void flood_report(uint32_t* host_progress, uint32_t r
 
 // End of a round (one thread: the last workgroup of the survivors pass): the next list becomes the current one.  A round without progress (possible only
 // when storage ran out on the lowest active seed) stops the rounds and leaves the rest to the ordered tail.
-__device__ void flood_advance(uint32_t* __restrict__ ctrl, uint32_t win_shift, uint32_t regional_min, uint32_t hold_min_big,
-                              uint32_t* host_progress, uint32_t hold_release, uint32_t giant_step, uint32_t giant_many) {
+__device__ void flood_advance(uint32_t* __restrict__ ctrl, uint32_t win_shift, uint32_t* host_progress, uint32_t giant_step,
+                              uint32_t giant_many) {
     const uint32_t n_act = ld_agent(&ctrl[kCtrlNAct]);
     if (n_act == 0u) {  // (a round enqueued past the end -- or a frame without seeds: the host must not wait for more)
         if (host_progress)
@@ -2621,7 +2361,7 @@ __device__ void flood_advance(uint32_t* __restrict__ ctrl, uint32_t win_shift, u
         ctrl[kCtrlStaged] = 1u;
         ctrl[kCtrlPhase] = 2u;
         grown = n_seeds >> 2;
-    } else if (phase == 0u && window >= n_seeds && win_hold < n_seeds && ld_agent(&ctrl[kCtrlBigTotal]) >= hold_min_big && n_next > 0u) {
+    } else if (phase == 0u && window >= n_seeds && win_hold < n_seeds && ld_agent(&ctrl[kCtrlBigTotal]) >= kHoldMinBig && n_next > 0u) {
         grown = win_hold;
         ctrl[kCtrlPhase] = 1u;
     } else if (phase == 1u) {
@@ -2633,7 +2373,7 @@ __device__ void flood_advance(uint32_t* __restrict__ ctrl, uint32_t win_shift, u
             // moved nothing (storage ran out on the lowest active seed): the full window lets the next round detect
             // the stall
             grown = window;
-            if (ld_agent(&ctrl[kCtrlBelow]) <= hold_release || !moved) {
+            if (ld_agent(&ctrl[kCtrlBelow]) <= kHoldRelease || !moved) {
                 grown = n_seeds;
                 ctrl[kCtrlPhase] = 2u;
             }
@@ -2686,9 +2426,8 @@ __device__ void flood_advance(uint32_t* __restrict__ ctrl, uint32_t win_shift, u
     ctrl[kCtrlBarrierNext] = 0xFFFFFFFFu;
     ctrl[kCtrlSlabs] = 0u;
     ctrl[kCtrlNBig] = 0u;
-    ctrl[kCtrlNMulti] = progress ? ld_agent(&ctrl[kCtrlNMultiNext]) : 0u;
-    ctrl[kCtrlNMultiNext] = 0u;
-    ctrl[kCtrlBigSeen] = ld_agent(&ctrl[kCtrlBigLong]) >= regional_min ? 1u : 0u;
+    ctrl[kCtrlNRewalk] = 0u;
+    ctrl[kCtrlBigSeen] = ld_agent(&ctrl[kCtrlBigLong]) >= kRegionalMin ? 1u : 0u;
     ctrl[kCtrlGiantStep] = (progress && want_giant) ? ld_agent(&ctrl[kCtrlLowest]) + 1u : 0u;  // (kCtrlLowest: the lowest survivor, set above)
     ctrl[kCtrlGiantReuse] = 0u;  // (a round has run: the masks of the last step are history)
     if (host_progress)  // the host enqueues the next round when it sees this one over and seeds left (flood_enqueue)
@@ -2743,21 +2482,7 @@ __global__ __launch_bounds__(256) void flood_survivors_kernel(FloodArgs A, uint8
                     A.blocked[k] = 0u;
                     A.count[k] = 0u;
                     A.flags[k] = 0u;
-                    // A survivor that left way-points on a long footprint: the coming round walks it from all of them at once
-                    // (team_walk, kMulti) in a launch of its own BESIDE the round's exploration, which passes it over (tier
-                    // bit 1).  (A few hundred such seeds a round at most: one atomic each.)
-                    uint8_t t = (uint8_t)(A.tier[k] & 5u);  // (bit 0: outgrew the first tier; bit 2: a giant, held back)
-                    if (A.multi_next != 0u && k < window && k < A.wp_cap) {
-                        const uint32_t hdr = A.waypoints[(size_t)k * kFloodWpWords];
-                        if (hdr != 0u && (hdr >> 8) <= kWpMaxTiles) {
-                            const uint32_t pos = atomicAdd(&A.ctrl[kCtrlNMultiNext], 1u);
-                            if (pos < kBigCap) {
-                                A.multi_list[pos] = k;
-                                t |= 2u;
-                            }
-                        }
-                    }
-                    A.tier[k] = t;
+                    A.tier[k] = (uint8_t)(A.tier[k] & 5u);  // (bit 0: outgrew the first tier; bit 2: a giant, held back)
                     // its last long walk was blocked by a lower seed that is still unresolved (see flood_explore_team_kernel):
                     // it waits.  (state[] of the blocker may be written in this very pass: read as unresolved, the seed waits a
                     // round longer.)
@@ -2838,7 +2563,7 @@ __global__ __launch_bounds__(256) void flood_survivors_kernel(FloodArgs A, uint8
         if (atomicAdd(&A.ctrl[kCtrlDone], 1u) == gridDim.x - 1u) {
             __threadfence();
             A.ctrl[kCtrlDone] = 0u;
-            flood_advance(A.ctrl, A.win_shift, A.t1_regional_min, A.hold_min_big, A.host_progress, A.hold_release, A.giant_step, A.giant_many);
+            flood_advance(A.ctrl, A.win_shift, A.host_progress, A.giant_step, A.giant_many);
             __threadfence();
             s_closed = 1u;
         }
@@ -2859,8 +2584,7 @@ __global__ __launch_bounds__(256) void flood_init_seeds_kernel(const uint32_t* _
                                                                uint8_t* __restrict__ dirty, uint32_t n_runs,
                                                                int win_first_shift, int hold_pct, uint32_t hold_from_start,
                                                                uint32_t* __restrict__ label, size_t npix,
-                                                               uint32_t* __restrict__ waypoints, uint32_t wp_cap,
-                                                               uint32_t* __restrict__ log_len, uint32_t log_seeds, uint32_t dense_div,
+                                                               uint32_t* __restrict__ log_len, uint32_t log_seeds,
                                                                uint32_t staged_from_start, uint32_t* __restrict__ blk) {
     // (the label image is set to "free" here as well: one launch less in front of the first round)
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < npix; i += (size_t)gridDim.x * 256) label[i] = kLabelFree;
@@ -2872,7 +2596,7 @@ __global__ __launch_bounds__(256) void flood_init_seeds_kernel(const uint32_t* _
         // A frame where every twelfth pixel or more is a seed is one of exact ties (a periodic pattern without noise: every
         // pixel of a flank a seed of the same magnitude, hundreds of seeds with ONE footprint): the strongest eighth walks
         // first, commits the flanks, and the others die unwalked (stripes of period 6 at 1080p: 687 564 seeds, 639 components).
-        if (dense_div != 0u && win_first_shift <= 0 && n_seeds > (uint32_t)(npix / dense_div)) win_first = max(1024u, n_seeds >> 3);
+        if (win_first_shift <= 0 && n_seeds > (uint32_t)(npix / kDenseDiv)) win_first = max(1024u, n_seeds >> 3);
         if (win_first > n_seeds) win_first = n_seeds;
         uint32_t win_hold = (hold_pct > 0 && hold_pct < 100) ? (uint32_t)((unsigned long long)n_seeds * (uint32_t)hold_pct / 100u) : n_seeds;
         if (win_hold < 1024u) win_hold = n_seeds;  // not worth another phase
@@ -2887,9 +2611,7 @@ __global__ __launch_bounds__(256) void flood_init_seeds_kernel(const uint32_t* _
         ctrl[kCtrlBigTotal] = 0u;
         ctrl[kCtrlBigLong] = 0u;
         ctrl[kCtrlBigSeen] = 0u;
-        ctrl[kCtrlMulti] = 0u;
-        ctrl[kCtrlNMulti] = 0u;
-        ctrl[kCtrlNMultiNext] = 0u;
+        ctrl[kCtrlNRewalk] = 0u;
         ctrl[kCtrlLowest] = 0u;
         ctrl[kCtrlLowestNext] = 0xFFFFFFFFu;
         ctrl[kCtrlGiantLow] = 0xFFFFFFFFu;
@@ -2928,7 +2650,6 @@ __global__ __launch_bounds__(256) void flood_init_seeds_kernel(const uint32_t* _
     }
     for (uint32_t r = k; r < n_runs; r += gridDim.x * 256) dirty[r] = 0;  // (all clear after a flood that ran to its end)
     if (k >= n_seeds) return;
-    if (k < wp_cap) waypoints[(size_t)k * kFloodWpWords] = 0u;
     if (k < log_seeds) log_len[k] = 0u;
     act[k] = k;
     state[k] = 0;
@@ -3500,53 +3221,26 @@ FloodArgs flood_args(const FloodBuffers& B, const FloodFrame& F, bool use_big) {
     A.n_slabs = B.n_slabs;
     A.slab_ring_cap = B.slab_ring_cap;
     A.slab_hash_cap = B.slab_hash_cap;
-    static const int order_env = std::getenv("LIBRECTIFY_FLOOD_ORDER") ? std::atoi(std::getenv("LIBRECTIFY_FLOOD_ORDER")) : -1;
-    A.from_end = order_env >= 0 ? (uint32_t)order_env : 1u;
     A.no_rest = 0u;
     A.next_reach = 0xFFFFFFFFu;
     A.win_shift = 2u;
     const uint32_t big_cap = B.big_cap_override ? B.big_cap_override : kBigCap;
     A.big_cap = use_big ? big_cap : 0u;
-    static const int t1_env = std::getenv("LIBRECTIFY_FLOOD_T1_TILES") ? std::atoi(std::getenv("LIBRECTIFY_FLOOD_T1_TILES")) : 0;
-    // With the giants' rule a second-tier walk counts as a giant at 1 024 tiles, two thirds of what the team's table holds
-    // (LIBRECTIFY_FLOOD_TEAM_TILES; 0 = the table's 1 536): ramp frame 11.0 -> 8.7 ms, regions 41.5 -> 39.6, frames without
-    // such walks unchanged; at 640 the edge-less 4K frame pays (5.7 -> 7.0 ms).
-    static const int team_tiles_env = std::getenv("LIBRECTIFY_FLOOD_TEAM_TILES") ? std::atoi(std::getenv("LIBRECTIFY_FLOOD_TEAM_TILES")) : 1024;
-    A.team_tiles = B.team_tile_cap ? B.team_tile_cap : ((B.giant_hold && team_tiles_env > 0) ? (uint32_t)team_tiles_env : 0xFFFFFFFFu);
-    static const int many_env = std::getenv("LIBRECTIFY_FLOOD_GIANT_MANY") ? std::atoi(std::getenv("LIBRECTIFY_FLOOD_GIANT_MANY")) : 64;
-    A.giant_many = B.giant_hold ? (uint32_t)std::max(many_env, 0) : 0u;
-    static const int defer_env = std::getenv("LIBRECTIFY_FLOOD_DEFER_STEPS") ? std::atoi(std::getenv("LIBRECTIFY_FLOOD_DEFER_STEPS")) : 512;
-    A.blk = (B.giant_hold && defer_env > 0) ? B.blk : nullptr;
-    A.defer_steps = (uint32_t)std::max(defer_env, 1);
+    // With the giants' rule a second-tier walk counts as a giant at kTeamTiles = 1 024 tiles, two thirds of what the team's
+    // table holds (1 536): ramp frame 11.0 -> 8.7 ms, regions 41.5 -> 39.6, frames without such walks unchanged; at 640 the
+    // edge-less 4K frame pays (5.7 -> 7.0 ms).
+    A.team_tiles = B.team_tile_cap ? B.team_tile_cap : (B.giant_hold ? kTeamTiles : 0xFFFFFFFFu);
+    A.giant_many = B.giant_hold ? kGiantMany : 0u;
+    A.wide_tiles = 0xFFFFFFFFu;
+    A.wide_front = 6u;
+    A.blk = B.giant_hold ? B.blk : nullptr;
     A.handover = B.handover;
-    A.t1_tiles = t1_env > 8 ? (uint32_t)t1_env : 0xFFFFFFFFu;
-    static const int t1r_env = std::getenv("LIBRECTIFY_FLOOD_T1_REGIONAL") ? std::atoi(std::getenv("LIBRECTIFY_FLOOD_T1_REGIONAL")) : 32;
-    static const int t1m_env = std::getenv("LIBRECTIFY_FLOOD_T1_REGIONAL_MIN") ? std::atoi(std::getenv("LIBRECTIFY_FLOOD_T1_REGIONAL_MIN")) : 16;
-    A.t1_regional = t1r_env > 8 ? (uint32_t)t1r_env : 0xFFFFFFFFu;
-    A.t1_regional_min = (uint32_t)std::max(t1m_env, 1);
-    static const int holdmin_env = std::getenv("LIBRECTIFY_FLOOD_HOLD_MIN") ? std::atoi(std::getenv("LIBRECTIFY_FLOOD_HOLD_MIN")) : 4;
-    A.hold_min_big = (uint32_t)std::max(holdmin_env, 1);
-    static const int holdrel_env = std::getenv("LIBRECTIFY_FLOOD_HOLD_RELEASE") ? std::atoi(std::getenv("LIBRECTIFY_FLOOD_HOLD_RELEASE")) : 64;
-    A.hold_release = (uint32_t)std::max(holdrel_env, 0);
-    static const int t1w_env = std::getenv("LIBRECTIFY_FLOOD_T1_WIDE_TILES") ? std::atoi(std::getenv("LIBRECTIFY_FLOOD_T1_WIDE_TILES")) : 0;
-    static const int t1f_env = std::getenv("LIBRECTIFY_FLOOD_T1_WIDE_FRONT") ? std::atoi(std::getenv("LIBRECTIFY_FLOOD_T1_WIDE_FRONT")) : 6;
-    A.t1_wide_tiles = t1w_env > 0 ? (uint32_t)t1w_env : 0xFFFFFFFFu;
-    A.t1_wide_front = (uint32_t)std::max(t1f_env, 1);
-    // way-points: walks of this many tiles leave them (LIBRECTIFY_FLOOD_MULTI_MIN; profiles/r04_flood_multi_sweep.txt)
-    static const int wp_min_env = std::getenv("LIBRECTIFY_FLOOD_MULTI_MIN") ? std::atoi(std::getenv("LIBRECTIFY_FLOOD_MULTI_MIN")) : 100;
-    A.waypoints = B.waypoints;
-    A.wp_cap = B.waypoints ? B.wp_cap : 0u;
-    A.multi_list = B.multi_list;
-    A.multi_next = 0u;
-    A.wp_min_tiles = (B.multi_source && B.waypoints && use_big) ? (uint32_t)std::max(wp_min_env, (int)kWpK + 1) : 0xFFFFFFFFu;
-    // logs: walks of this many tiles leave one (LIBRECTIFY_FLOOD_LOG_MIN); with logs there are no way-points
-    static const int log_min_env = std::getenv("LIBRECTIFY_FLOOD_LOG_MIN") ? std::atoi(std::getenv("LIBRECTIFY_FLOOD_LOG_MIN")) : 16;
-    const bool logs = B.rewalk_logs && B.log_buf && B.log_off && B.log_len && B.multi_list;
-    A.log_min_tiles = logs ? (uint32_t)std::max(B.log_min_tiles > 0 ? B.log_min_tiles : log_min_env, 1) : 0xFFFFFFFFu;
-    static const int log_walk_env = std::getenv("LIBRECTIFY_FLOOD_LOG_WALK") ? std::atoi(std::getenv("LIBRECTIFY_FLOOD_LOG_WALK")) : 12;
-    A.log_walk_tiles = (uint32_t)std::max(B.log_walk_tiles > 0 ? B.log_walk_tiles : log_walk_env, 3);
-    static const bool log_sweep_env = std::getenv("LIBRECTIFY_FLOOD_LOG_SWEEP") && std::atoi(std::getenv("LIBRECTIFY_FLOOD_LOG_SWEEP")) != 0;
-    A.log_sweep = (log_sweep_env || B.log_sweep) ? 1u : 0u;
+    A.rewalk_list = B.rewalk_list;
+    // logs: walks of kLogMinTiles tiles and more leave one (the lanes of a batch bring thresholds of their own)
+    const bool logs = B.rewalk_logs && B.log_buf && B.log_off && B.log_len && B.rewalk_list;
+    A.log_min_tiles = logs ? (B.log_min_tiles > 0 ? (uint32_t)B.log_min_tiles : kLogMinTiles) : 0xFFFFFFFFu;
+    A.log_walk_tiles = B.log_walk_tiles > 0 ? (uint32_t)B.log_walk_tiles : kLogWalkTiles;
+    A.log_sweep = B.log_sweep ? 1u : 0u;
     A.host_progress = (B.jit_first > 0 && !g_flood_debug) ? B.host_progress : nullptr;
     static const bool mirror_off = std::getenv("LIBRECTIFY_FLOOD_MIRROR") && std::atoi(std::getenv("LIBRECTIFY_FLOOD_MIRROR")) == 0;  // (comparison)
     A.host_ctrl = (A.host_progress && !mirror_off) ? B.host_ctrl : nullptr;
@@ -3558,9 +3252,6 @@ FloodArgs flood_args(const FloodBuffers& B, const FloodFrame& F, bool use_big) {
     A.log_len = B.log_len;
     A.log_buf = B.log_buf;
     A.log_cap = B.log_cap;
-    if (logs) A.wp_min_tiles = 0xFFFFFFFFu;
-    static const int g_cap_env = std::getenv("LIBRECTIFY_FLOOD_PARTIAL_STEPS") ? std::atoi(std::getenv("LIBRECTIFY_FLOOD_PARTIAL_STEPS")) : 16;
-    A.g_cap = g_cap_env > 0 ? (uint32_t)g_cap_env : kMaxSteps;
     A.act_a = B.act_a;
     A.act_b = B.act_b;
     A.giant_mask = reinterpret_cast<unsigned long long*>(B.giant_mask);
@@ -3620,41 +3311,21 @@ void enqueue_round(const FloodBuffers& B, const FloodFrame& F, const FloodArgs& 
     FloodArgs A = A0;
     A.no_rest = (grid < F.seed_cap && !rest_now && !exact) ? 1u : 0u;
     A.next_reach = (grid_of(index + 1) < F.seed_cap && !has_rest(index + 1) && !next_known) ? grid_of(index + 1) : 0xFFFFFFFFu;
-    // Way-point seeds listed by the last survivors pass are walked by teams in a launch of their own on the context's second
-    // stream, BESIDE this round's exploration (one stream runs its kernels one after the other, and hipExtAnyOrderLaunch is
-    // not honoured on gfx950: tools/ubench/anyorder.hip): fork behind the last round, join in front of the commit passes.
-    // Only in the rounds that have such walks to speak of (2 .. kMultiRoundLast + 1): a fork and a join are two event
-    // packets a round.
-    const bool multi_now = B.aux_stream != nullptr && A.wp_min_tiles != 0xFFFFFFFFu && use_big && index >= 1 && index <= B.multi_round_last &&
-                           index < B.n_fork_events && !g_flood_debug;
-    A.multi_next = (B.aux_stream != nullptr && A.wp_min_tiles != 0xFFFFFFFFu && use_big && index + 1 >= 1 && index + 1 <= B.multi_round_last &&
-                    index + 1 < B.n_fork_events && !g_flood_debug) ? 1u : 0u;
+    // (walks leave logs from the first round on, the rounds after it use them)
     const bool logs = A.log_min_tiles != 0xFFFFFFFFu;
-    A.log_use = (logs && index >= B.log_from_round) ? 1u : 0u;
-    if (multi_now) {
-        (void)hipEventRecord(B.fork_events[index], s);
-        (void)hipStreamWaitEvent(B.aux_stream, B.fork_events[index], 0);
-        hipLaunchKernelGGL(flood_explore_team_kernel, dim3(std::min<uint32_t>(F.seed_cap, kTeamGrid)), dim3(64 * kTeamWaves),
-                           kTeamLdsBytes, B.aux_stream, A, F.trig, B.multi_list, 1u);
-        (void)hipEventRecord(B.join_events[index], B.aux_stream);
-    }
+    A.log_use = (logs && index >= 1) ? 1u : 0u;
     hipLaunchKernelGGL(flood_explore_kernel, dim3(grid), dim3(64), 0, s, A, F.trig, B.big_list);
     if (rest_now)  // entries past the guess, if any
         hipLaunchKernelGGL(flood_explore_rest_kernel, dim3(1024), dim3(64), 0, s, A, F.trig, B.big_list, grid);
-    static const bool team = !(std::getenv("LIBRECTIFY_FLOOD_TEAM") && std::atoi(std::getenv("LIBRECTIFY_FLOOD_TEAM")) == 0);
-    if (use_big && team)
+    if (use_big)
         hipLaunchKernelGGL(flood_explore_team_kernel, dim3(std::min<uint32_t>(F.seed_cap, kTeamGrid)), dim3(64 * kTeamWaves),
-                           kTeamLdsBytes, s, A, F.trig, B.big_list, 0u);
-    else if (use_big)
-        hipLaunchKernelGGL(flood_explore_big_kernel, dim3(std::min<uint32_t>(F.seed_cap, kBigCap)), dim3(64), kBigLdsBytes, s,
-                           A, F.trig, B.big_list);
-    if (multi_now) (void)hipStreamWaitEvent(s, B.join_events[index], 0);
-    if (logs && index >= std::max(B.log_from_round, 1))
+                           kTeamLdsBytes, s, A, F.trig, B.big_list);
+    if (logs && index >= 1)
         hipLaunchKernelGGL((flood_rewalk_kernel<kRewalkThreads, kRewalkTiles>), dim3(std::min<uint32_t>(F.seed_cap, kRewalkGrid)), dim3(kRewalkThreads),
-                           rewalk_lds_bytes<kRewalkTiles>(), s, A, B.multi_list, 1u);
-    if (logs && index >= std::max(B.log_from_round, 1) && A.log_max_len > (uint32_t)kRewalkTiles)
+                           rewalk_lds_bytes<kRewalkTiles>(), s, A, B.rewalk_list, 1u);
+    if (logs && index >= 1 && A.log_max_len > (uint32_t)kRewalkTiles)
         hipLaunchKernelGGL((flood_rewalk_kernel<kRewalkThreadsBig, kRewalkTilesBig>), dim3(std::min<uint32_t>(F.seed_cap, 1024u)),
-                           dim3(kRewalkThreadsBig), rewalk_lds_bytes<kRewalkTilesBig>(), s, A, B.multi_list, (uint32_t)kRewalkTiles + 1u);
+                           dim3(kRewalkThreadsBig), rewalk_lds_bytes<kRewalkTilesBig>(), s, A, B.rewalk_list, (uint32_t)kRewalkTiles + 1u);
     if (g_flood_debug) (void)hipEventRecord(dbg1, s);
     if (g_flood_debug) {
         uint32_t n = 0;
@@ -3667,11 +3338,10 @@ void enqueue_round(const FloodBuffers& B, const FloodFrame& F, const FloodArgs& 
         (void)hipEventDestroy(dbg0);
         (void)hipEventDestroy(dbg1);
     }
-    static const int g_rounds_env = std::getenv("LIBRECTIFY_FLOOD_PARTIAL_ROUNDS") ? std::atoi(std::getenv("LIBRECTIFY_FLOOD_PARTIAL_ROUNDS")) : 3;
-    // (only in the first three rounds: with the logs the later rounds' re-walks are cheap, and what the partial commits save
+    // (only in the first kPartialRounds = 3 rounds: with the logs the later rounds' re-walks are cheap, and what the partial commits save
     // there no longer pays their launch -- 0.970 -> 0.935 ms over the four bench frames, same rounds; and the lanes of a batch
     // are better off with a launch less per late round: 9.81 -> 9.99 Gpix/s)
-    if (B.partial_commits && index < g_rounds_env)
+    if (B.partial_commits && index < kPartialRounds)
         hipLaunchKernelGGL(flood_partial_commit_kernel, dim3(grid), dim3(64), 0, s, A, const_cast<uint8_t*>(F.dmask));
     hipLaunchKernelGGL(flood_commit_pixels_kernel, dim3(pix_blocks), dim3(256), 0, s, A, F.label, npix,
                        const_cast<uint8_t*>(F.dmask));
@@ -3717,23 +3387,13 @@ int flood_enqueue(const FloodBuffers& B, const FloodFrame& F, FloodProgress* P, 
     P->max_flood = 0;
     P->use_big = B.second_tier && B.second_tier_from_start;
     if (F.seed_cap == 0) return launch_label_init(F.label, (size_t)F.w * F.h, s);
-    // staged start (FloodBuffers::win_*); LIBRECTIFY_FLOOD_WINDOW="<first shift>,<growth shift>" overrides
-    static const char* win_env = std::getenv("LIBRECTIFY_FLOOD_WINDOW");
+    // staged start (FloodBuffers::win_*)
     int win_first_shift = B.win_first_shift, win_growth = B.win_growth;
     if (B.staged_from_start && win_first_shift <= 0) {  // the strongest quarter first, twice as many a round (kCtrlStaged)
         win_first_shift = 2;
         win_growth = 1;
     }
-    if (win_env) {
-        win_first_shift = std::atoi(win_env);
-        const char* c = std::strchr(win_env, ',');
-        if (c) win_growth = std::max(1, std::atoi(c + 1));
-    }
     P->win_growth = win_growth;
-    static const int hold_env = std::getenv("LIBRECTIFY_FLOOD_HOLD") ? std::atoi(std::getenv("LIBRECTIFY_FLOOD_HOLD")) : -1;
-    const int hold_pct = hold_env >= 0 ? hold_env : B.win_hold_pct;
-    static const bool hold_start_env = std::getenv("LIBRECTIFY_FLOOD_HOLD_START") != nullptr;
-    const bool hold_start = B.hold_from_start || hold_start_env;
     // the opt-in for more than 32 KB of dynamic LDS is a per-device attribute of the kernel: once per device of this process
     {
         static std::atomic<uint64_t> done_mask{0};
@@ -3741,9 +3401,7 @@ int flood_enqueue(const FloodBuffers& B, const FloodFrame& F, FloodProgress* P, 
         LR_HIP(hipGetDevice(&dev));
         const uint64_t bit = 1ull << (dev & 63);
         if (!(done_mask.load(std::memory_order_acquire) & bit)) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(flood_explore_big_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBigLdsBytes) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(flood_explore_team_kernel),
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(flood_explore_team_kernel),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTeamLdsBytes) != hipSuccess ||
                 hipFuncSetAttribute(reinterpret_cast<const void*>(flood_rewalk_kernel<kRewalkThreadsBig, kRewalkTilesBig>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)rewalk_lds_bytes<kRewalkTilesBig>()) != hipSuccess) {
@@ -3754,16 +3412,14 @@ int flood_enqueue(const FloodBuffers& B, const FloodFrame& F, FloodProgress* P, 
         }
     }
     {
-        static const int dense_env = std::getenv("LIBRECTIFY_FLOOD_DENSE_DIV") ? std::atoi(std::getenv("LIBRECTIFY_FLOOD_DENSE_DIV")) : 12;
-        const uint32_t dense_div = (uint32_t)std::max(dense_env, 0);
         const size_t npix = (size_t)F.w * F.h;
         const uint32_t seed_blocks = (F.seed_cap + 255) / 256;
         const uint32_t blocks = std::max<uint32_t>(seed_blocks, (uint32_t)std::min<size_t>((npix + 255) / 256, 4096));
         hipLaunchKernelGGL(flood_init_seeds_kernel, dim3(blocks), dim3(256), 0, s, F.d_n_seeds, F.seed_cap, B.act_a, B.state,
                            B.tier, B.blocked, B.count, B.flags, F.seed_size, B.ctrl, B.dirty,
-                           (uint32_t)((npix + 255) >> 8), win_first_shift, hold_pct, hold_start ? 1u : 0u, F.label, npix,
-                           B.waypoints, B.wp_cap, B.log_len, B.log_len ? B.log_seeds : 0u, dense_div,
-                           (B.staged_from_start && !win_env && B.win_first_shift <= 0) ? 1u : 0u, B.blk);
+                           (uint32_t)((npix + 255) >> 8), win_first_shift, B.win_hold_pct, B.hold_from_start ? 1u : 0u, F.label,
+                           npix, B.log_len, B.log_len ? B.log_seeds : 0u, (B.staged_from_start && B.win_first_shift <= 0) ? 1u : 0u,
+                           B.blk);
     }
     FloodArgs A = flood_args(B, F, P->use_big);
     A.win_shift = (uint32_t)win_growth;
@@ -3788,16 +3444,14 @@ int flood_enqueue(const FloodBuffers& B, const FloodFrame& F, FloodProgress* P, 
                           ((w >> 29) & 1ull) != 0ull, ((w >> 30) & 1ull) != 0ull, ((w >> 31) & 1ull) != 0ull, ((w >> 60) & 1ull) != 0ull};
         };
         const int first = std::min(std::max(B.jit_first, 1), 16);
-        // (LIBRECTIFY_FLOOD_JIT_LEAD=1 keeps one round ahead -- the next round goes in when all but the last one enqueued are
-        // over and left seeds, the host's reaction hides behind that last round, at most one round is enqueued in vain:
-        // measured the same as none ahead, 0.921 against 0.923 ms over eight 4K frames, blind rounds 0.937)
-        const int lead = B.jit_lead;
+        // (Keeping one round ahead -- the next round goes in when all but the last one enqueued are over and left seeds, the
+        // host's reaction hides behind that last round, at most one round is enqueued in vain -- measured the same as none
+        // ahead: 0.921 against 0.923 ms over eight 4K frames, blind rounds 0.937.)
         // The context's last frame never needed the second tier (calm_hint): the rounds enqueued blindly behind the first go
         // without its launch -- empty on such frames, and in a batch each waits ~50 us for room beside the other lanes' walks.
         // A walk that outgrows the first tier there counts as unfinished (explore_seed: A.quiet), the report stops saying
         // "calm", and the rounds enqueued from then on bring the second tier.
-        const bool multi_on0 = B.aux_stream != nullptr && A.wp_min_tiles != 0xFFFFFFFFu;
-        const bool quiet = B.calm_hint && P->use_big && !multi_on0;
+        const bool quiet = B.calm_hint && P->use_big;
         FloodArgs A_quiet = A;
         if (quiet) {
             A_quiet = flood_args(B, F, false);
@@ -3854,7 +3508,7 @@ int flood_enqueue(const FloodBuffers& B, const FloodFrame& F, FloodProgress* P, 
             bool timed_out = false;
             for (;;) {
                 r = look();
-                if (r.any && ((int)r.rounds + lead >= counting || r.n_left == 0u || r.want_giant)) break;
+                if (r.any && ((int)r.rounds >= counting || r.n_left == 0u || r.want_giant)) break;
                 if (deadline_passed()) {
                     timed_out = true;
                     break;
@@ -3898,10 +3552,7 @@ int flood_enqueue(const FloodBuffers& B, const FloodFrame& F, FloodProgress* P, 
             // 512 workgroups of 512 threads and 41 KB of LDS each, which in a batch waits ~50 us for room beside the other
             // lanes' walks.  (A walk that outgrew the first tier after all would move into a slab or count as unfinished:
             // exact either way.)
-            static const bool calm_off = std::getenv("LIBRECTIFY_FLOOD_CALM") && std::atoi(std::getenv("LIBRECTIFY_FLOOD_CALM")) == 0;
-            // (not with multi-source re-walks on: their launch is the second tier's, and the round before has listed seeds for it)
-            const bool multi_on = B.aux_stream != nullptr && A.wp_min_tiles != 0xFFFFFFFFu;
-            if (r.calm && !calm_off && !calm && P->use_big && !multi_on) {
+            if (r.calm && !calm && P->use_big) {
                 calm = true;
                 A_calm = flood_args(B, F, false);
                 A_calm.win_shift = A.win_shift;
@@ -3988,7 +3639,7 @@ int flood_finish(const FloodBuffers& B, const FloodFrame& F, FloodProgress* P, u
         tiers_out[6] = h_ctrl[kCtrlSteps];
         tiers_out[7] = h_ctrl[kCtrlSteps + 1];
         tiers_out[8] = h_ctrl[kCtrlBigLong];
-        tiers_out[9] = h_ctrl[kCtrlMulti];
+        tiers_out[9] = 0u;  // (retired: re-walks from way-points)
         tiers_out[10] = h_ctrl[kCtrlLogWalks];
         tiers_out[11] = h_ctrl[kCtrlLogGiveUp];
         tiers_out[12] = h_ctrl[kCtrlGiants];

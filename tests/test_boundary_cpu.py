@@ -55,6 +55,28 @@ def test_library_exports_nothing_but_the_declared_symbols(L):
     assert len(exported) <= 60
 
 
+# The environment variables the library reads: switches a caller or a test may set, and diagnostic printers.  Every other
+# setting is a constant in the code.
+ENV_NAMES = {
+    "DEVICE", "SEED", "STAGE_TIMES", "REGISTER_FRAMES", "RING_EXTRA", "LANES_SLEEP", "FLOOD_LOGS", "FLOOD_JIT",
+    "FLOOD_GIANT_STEP", "FLOOD_PARTIAL", "FLOOD_CALM_HINT",
+    "TEST_CREATE_FAIL", "FLOOD_TEST_GRID", "FLOOD_MIRROR", "FLOOD_SLABS", "SEED_SELECT_FUSED", "UPLOAD_BAND_KB",
+    "FLOOD_DEBUG", "CALL_DEBUG", "LANE_DEBUG", "BATCH_STATS", "FIT_DEBUG", "PROSAC_DEBUG",
+}
+
+
+def test_library_reads_exactly_the_documented_environment_variables():
+    csrc = os.path.join(ROOT, "librectify_amd", "csrc")
+    read = set()
+    for name in os.listdir(csrc):
+        read |= set(re.findall(r'getenv\("LIBRECTIFY_([A-Z0-9_]+)"', open(os.path.join(csrc, name)).read()))
+    txt = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    section = txt[txt.index("## 4. Environment variables"):txt.index("## 5.")]
+    documented = set(re.findall(r"LIBRECTIFY_([A-Z0-9_]+)", section))
+    assert read == ENV_NAMES, (sorted(read - ENV_NAMES), sorted(ENV_NAMES - read))
+    assert documented == ENV_NAMES, (sorted(documented - ENV_NAMES), sorted(ENV_NAMES - documented))
+
+
 def test_frames_below_the_kernel_size_return_the_reference_silent_null(L, capfd):
     """interface.cpp:50-54: a frame smaller than the 5x5 kernel has no peaks, hence fewer than two lines: NULL, *n_lines = 0,
     and not a word on stderr (missing 4) -- decided before any GPU is asked for."""

@@ -1,6 +1,6 @@
 """One 4K frame at a time through the reference's own entry (find_line_segment_groups + compute_rectification_transform):
-wall time from pageable and page-locked buffers, four bench frames.  Env knobs of the upload path are read by the
-library (LIBRECTIFY_UPLOAD_BAND_KB, LIBRECTIFY_FILTER_EVERY)."""
+wall time from pageable and page-locked buffers, four bench frames.  The upload band size is read by the library
+(LIBRECTIFY_UPLOAD_BAND_KB)."""
 import os
 import sys
 import time
