@@ -25,6 +25,10 @@ struct lr_context {
     hipStream_t copy_stream = nullptr;
     float* d_img_slot[2] = {nullptr, nullptr};
     size_t cap_slot[2] = {0, 0};
+    // Device frames whose rows span 4 GiB or more (the filter kernel addresses a frame with 32-bit byte offsets) are
+    // first copied here, packed, on the context's stream (enqueue_filter).
+    float* d_img_packed = nullptr;
+    size_t cap_packed = 0;
     float* h_stage[2] = {nullptr, nullptr};
     size_t cap_stage[2] = {0, 0};
     hipEvent_t ev_up[2] = {};

@@ -144,6 +144,10 @@ int ctx_trim(lr_context* c, bool frames_too) {
     drop(f.slab_ring), drop(f.slab_hash);
     c->fb_cap_seeds = 0;
     // (the frame slots hold the frame that is being processed when the workspace shrinks by itself: only on request)
+    if (frames_too) {
+        drop(c->d_img_packed);
+        c->cap_packed = 0;
+    }
     for (int s = 0; s < 2 && frames_too; ++s) {
         drop(c->d_img_slot[s]);
         c->cap_slot[s] = 0;
@@ -199,9 +203,11 @@ int ctx_ensure_image_capacity(lr_context* c, int w, int h) {
     LR_HIP(hipStreamSynchronize(c->stream));
     const size_t cp = std::max(npix, c->cap_pix);
     const int ct = std::max(ntiles, c->cap_tiles);
+    // (seed_select_kernel keeps one 64-bit status word a workgroup in tile_off: 2 words for a one-tile frame)
+    const size_t tile_off_words = std::max(ct, 2);
     if (dev_alloc(c->dx, cp) || dev_alloc(c->dy, cp) || dev_alloc(c->dmask, cp + 16) ||
         dev_alloc(c->cand, (size_t)ct * fg.cand_cap) || dev_alloc(c->cand_count, ct) || dev_alloc(c->tile_max, ct) ||
-        dev_alloc(c->tile_pass, ct) || dev_alloc(c->tile_off, ct) || dev_alloc(c->keys_a, cp) ||
+        dev_alloc(c->tile_pass, ct) || dev_alloc(c->tile_off, tile_off_words) || dev_alloc(c->keys_a, cp) ||
         dev_alloc(c->keys_b, cp) || dev_alloc(c->seed_idx, cp) || dev_alloc(c->seed_bin, cp) ||
         dev_alloc(c->seed_thr, cp) || dev_alloc(c->seed_size, cp) || dev_alloc(c->label, cp) ||
         dev_alloc(c->queue, cp) || dev_alloc(c->comp_rank, cp) || dev_alloc(c->comp_seed, cp) ||
@@ -209,7 +215,7 @@ int ctx_ensure_image_capacity(lr_context* c, int w, int h) {
         dev_alloc(c->px_b, cp) || dev_alloc(c->scratch_w, cp) || dev_alloc(c->d_lines, cp / 6 + 16) ||
         dev_alloc(c->comp_large, cp / 64 + 16))
         return 1;
-    LR_HIP(hipMemsetAsync(c->tile_off, 0, (size_t)ct * sizeof(uint32_t), c->stream));  // (seed_select_kernel's status words)
+    LR_HIP(hipMemsetAsync(c->tile_off, 0, tile_off_words * sizeof(uint32_t), c->stream));  // (seed_select_kernel's status words)
     {   // huge components: a row of buckets (2^14 pixel indices each) for up to 256 of them; the table is zero between frames
         const size_t nb = (cp + 16383) >> 14;
         c->huge.max = 256;
@@ -729,7 +735,7 @@ void ctx_destroy(lr_context* c) {
     c->peers.clear();
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    void* ptrs[] = {c->d_img_slot[0], c->d_img_slot[1], c->dx, c->dy, c->dmask, c->cand, c->cand_count, c->tile_max, c->tile_pass, c->tile_off,
+    void* ptrs[] = {c->d_img_slot[0], c->d_img_slot[1], c->d_img_packed, c->dx, c->dy, c->dmask, c->cand, c->cand_count, c->tile_max, c->tile_pass, c->tile_off,
                     c->maxmag, c->keys_a, c->keys_b, c->d_counts, c->seed_idx, c->seed_bin, c->seed_thr, c->seed_size,
                     c->label, c->queue, c->comp_rank, c->comp_seed, c->comp_off, c->cursor, c->px_a, c->px_b,
                     c->scratch_w, c->d_lines, c->temp, c->d_model, c->d_best_slots,
@@ -912,6 +918,23 @@ int prepare_frame(lr_context* c, int w, int h) {
 
 int enqueue_filter(lr_context* c, const float* d_image, int w, int h, int stride) {
     if (prepare_frame(c, w, h)) return 1;
+    // The filter kernel addresses the frame with 32-bit byte offsets from its first row (buffer resource and row offsets,
+    // kernels_filter.hip).  A caller's frame whose rows span 4 GiB or more -- a narrow crop of a large device mosaic -- is
+    // packed into a buffer of the context first, so the kernel sees the same pixels at stride w.
+    // (a frame of 2^29 pixels or more is refused by launch_filter without the copy)
+    if (stride > w && (uint64_t)w * (uint64_t)h < (1ull << 29) &&
+        ((uint64_t)(h - 1) * (uint64_t)stride + (uint64_t)w) * 4u >= (1ull << 32)) {
+        const size_t npix = (size_t)w * h;
+        if (c->cap_packed < npix) {
+            LR_HIP(hipStreamSynchronize(c->stream));
+            if (dev_alloc(c->d_img_packed, npix)) return 1;
+            c->cap_packed = npix;
+        }
+        LR_HIP(hipMemcpy2DAsync(c->d_img_packed, (size_t)w * sizeof(float), d_image, (size_t)stride * sizeof(float),
+                                (size_t)w * sizeof(float), (size_t)h, hipMemcpyDeviceToDevice, c->stream));
+        d_image = c->d_img_packed;
+        stride = w;
+    }
     if (c->timing_on) LR_HIP(hipEventRecord(c->ev[0], c->stream));
     if (launch_filter(d_image, w, h, stride, c->fconsts, c->dx, c->dy, c->dmask, c->cand, c->cand_count, c->tile_max,
                       c->stream))

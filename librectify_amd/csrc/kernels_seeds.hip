@@ -438,7 +438,8 @@ int launch_seed_select(const uint64_t* cand, const uint32_t* cand_count, const u
                        int cand_cap, float seed_keep_ratio, float* maxmag, uint32_t* tile_pass, uint32_t* tile_off, uint64_t* keys,
                        uint32_t key_cap, uint32_t* n_seeds, uint32_t frame_tag, hipStream_t s) {
     static const bool fused = !(std::getenv("LIBRECTIFY_SEED_SELECT_FUSED") && std::atoi(std::getenv("LIBRECTIFY_SEED_SELECT_FUSED")) == 0);
-    // (the status words are tile_off's: n_tiles words, zero when allocated -- two words a workgroup, at most n_tiles / 4 workgroups)
+    // (the status words are tile_off's: one 64-bit word a workgroup, at most ceil(n_tiles / 4) workgroups; the context
+    // allocates and zeroes max(n_tiles, 2) 32-bit words, so a one-tile frame's single workgroup has its whole word)
     if (fused && frame_tag != 0u && n_tiles > 0) {
         int wgs = std::min(256, (n_tiles + 3) / 4);
         int per_wg = (n_tiles + wgs - 1) / wgs;
