@@ -5,10 +5,13 @@
 // (<prefix>_lines.csv: x1,y1,x2,y2,weight,err,group_id per row; <prefix>_tform.csv: TL, TR, BL, BR, hvp, vvp).
 //
 //   rectify_recipe in.pgm|in.ppm out_prefix [--max-size N|fraction] [--refine] [--threads N]
-//                  [--h-strategy rotate_h|rotate_v|rectify|keep] [--v-strategy ...]
+//                  [--h-strategy rotate_h|rotate_v|rectify|keep] [--v-strategy ...] [--warp]
 //
 // Input is a binary PGM (P5, 8 bit) or PPM (P6, 8 bit; converted with the usual integer luma weights
-// (4899 R + 9617 G + 1868 B + 8192) >> 14).  Image decoding and warping stay with the caller's imaging library.
+// (4899 R + 9617 G + 1868 B + 8192) >> 14).  Image decoding stays with the caller's imaging library.
+// --warp: the demo's last step too (autorectify.cpp:357-360) -- lr_rectification_homography with clip 3.0, the 8-bit
+// frame as read warped on the GPU (lr_warp_perspective_device), written as <out_prefix>_warp.pgm or .ppm
+// (INTEGRATION.md §6).
 // Links against librectify_amd.so exactly like a program written for the reference.
 #include <algorithm>
 #include <cctype>
@@ -22,7 +25,7 @@
 #include <string>
 #include <vector>
 
-#include "librectify.h"
+#include "librectify_amd.h"
 
 using namespace librectify;
 
@@ -31,6 +34,8 @@ namespace {
 struct Gray {
     int w = 0, h = 0;
     std::vector<float> px;  // row-major
+    int ch = 1;               // the 8-bit frame as read (gray or interleaved RGB), for --warp
+    std::vector<uint8_t> raw;
 };
 
 bool read_token(std::istream& f, std::string& tok) {
@@ -62,7 +67,9 @@ bool load_pnm(const std::string& path, Gray& g) {
     g.w = std::atoi(tw.c_str());
     g.h = std::atoi(th.c_str());
     if (g.w <= 0 || g.h <= 0) return false;
-    std::vector<uint8_t> raw((size_t)g.w * g.h * ch);
+    g.ch = ch;
+    std::vector<uint8_t>& raw = g.raw;
+    raw.resize((size_t)g.w * g.h * ch);
     f.read(reinterpret_cast<char*>(raw.data()), (std::streamsize)raw.size());
     if ((size_t)f.gcount() != raw.size()) return false;
     g.px.resize((size_t)g.w * g.h);
@@ -122,6 +129,45 @@ Gray prescale(const Gray& in, int max_size, float& scale) {
     return out;
 }
 
+// The demo's homography_from_corners(t, 3.0) + warpPerspective of the frame as read, on the GPU; writes
+// <prefix>_warp.pgm / .ppm.  Returns false with the reason on stderr.
+bool warp_frame(const Gray& g, const ImageTransform& t, const std::string& prefix) {
+    double M[9];
+    int ow = 0, oh = 0;
+    lr_context* ctx = nullptr;
+    void* d_src = nullptr;
+    void* d_dst = nullptr;
+    const size_t bpp = (size_t)g.ch;
+    std::vector<uint8_t> out;
+    bool ok = lr_rectification_homography(&t, 3.0f, nullptr, M, &ow, &oh) == 0 && lr_context_create(0, &ctx) == 0;
+    if (ok) {
+        out.resize((size_t)ow * oh * bpp);
+        ok = lr_device_malloc(ctx, g.raw.size(), &d_src) == 0 && lr_device_malloc(ctx, out.size(), &d_dst) == 0 &&
+             lr_memcpy_h2d(ctx, d_src, g.raw.data(), g.raw.size()) == 0 &&
+             lr_warp_perspective_device(ctx, d_src, g.raw.size(), 1, g.w, g.h, (size_t)g.w * bpp,
+                                        g.ch == 3 ? LR_PIX_U8X3 : LR_PIX_U8, M, d_dst, out.size(), ow, oh,
+                                        (size_t)ow * bpp) == 0 &&
+             lr_memcpy_d2h(ctx, out.data(), d_dst, out.size()) == 0;
+    }
+    if (!ok) std::fprintf(stderr, "warp failed: %s\n", lr_last_error());
+    if (ctx) {
+        if (d_src) lr_device_free(ctx, d_src);
+        if (d_dst) lr_device_free(ctx, d_dst);
+        lr_context_destroy(ctx);
+    }
+    if (!ok) return false;
+    const std::string path = prefix + (g.ch == 3 ? "_warp.ppm" : "_warp.pgm");
+    std::ofstream f(path, std::ios::binary);
+    f << (g.ch == 3 ? "P6" : "P5") << "\n" << ow << " " << oh << "\n255\n";
+    f.write(reinterpret_cast<const char*>(out.data()), (std::streamsize)out.size());
+    if (!f) {
+        std::fprintf(stderr, "warp failed: cannot write %s\n", path.c_str());
+        return false;
+    }
+    std::printf("wrote %s (%dx%d)\n", path.c_str(), ow, oh);
+    return true;
+}
+
 bool parse_strategy(const std::string& s, RectificationStrategy& out) {
     if (s == "rotate_h") out = ROTATE_H;
     else if (s == "rotate_v") out = ROTATE_V;
@@ -137,12 +183,12 @@ int main(int argc, char** argv) {
     if (argc < 3) {
         std::fprintf(stderr,
                      "usage: %s in.pgm|in.ppm out_prefix [--max-size N|fraction] [--refine] [--threads N]\n"
-                     "          [--h-strategy rotate_h|rotate_v|rectify|keep] [--v-strategy ...]\n",
+                     "          [--h-strategy rotate_h|rotate_v|rectify|keep] [--v-strategy ...] [--warp]\n",
                      argv[0]);
         return 2;
     }
     float max_size = 1200.f;  // the demo's default
-    bool refine = false;
+    bool refine = false, warp = false;
     int threads = -1;
     RectificationConfig cfg;
     cfg.horizontal_vp_min_distance = 2;  // autorectify.cpp:347
@@ -150,6 +196,7 @@ int main(int argc, char** argv) {
         const std::string a = argv[i];
         const bool has_val = i + 1 < argc;
         if (a == "--refine") refine = true;
+        else if (a == "--warp") warp = true;
         else if (a == "--max-size" && has_val) max_size = (float)std::atof(argv[++i]);
         else if (a == "--threads" && has_val) threads = std::atoi(argv[++i]);
         else if (a == "--h-strategy" && has_val && parse_strategy(argv[i + 1], cfg.h_strategy)) ++i;
@@ -197,5 +244,6 @@ int main(int argc, char** argv) {
     std::printf("%dx%d -> %dx%d (scale %g), %d segments, wrote %s_lines.csv and %s_tform.csv\n", full.w, full.h, img.w,
                 img.h, (double)scale, n, prefix.c_str(), prefix.c_str());
     release_line_segments(&lines);
+    if (warp && !warp_frame(full, t, prefix)) return 1;
     return lines == nullptr ? 0 : 1;
 }

@@ -128,6 +128,9 @@ int lr_host_free(lr_context* ctx, void* p);
 int lr_device_malloc(lr_context* ctx, size_t bytes, void** out);
 int lr_device_free(lr_context* ctx, void* p);
 int lr_memcpy_h2d(lr_context* ctx, void* dst, const void* src, size_t bytes);
+/* The twin of lr_memcpy_h2d: waits for the context's stream first (it is a non-blocking stream, which a plain hipMemcpy
+ * would not wait for), then copies `bytes` from device to host. */
+int lr_memcpy_d2h(lr_context* ctx, void* dst, const void* src, size_t bytes);
 /* Frames kept in flight by the batch call (one host thread + HIP stream + workspace each; default 5). */
 void lr_set_batch_streams(lr_context* ctx, int n);
 /* Test hooks for the two situations in which a frame takes a second lap (lr_stage_counters [7] tells): the capacity
@@ -166,6 +169,28 @@ void lr_set_flood_just_in_time(lr_context* ctx, int on);
  * instead of one team of wavefronts walking it tile after tile through a global slab.  Same labels.  On by default;
  * 0 = the slab walk (comparison), LIBRECTIFY_FLOOD_GIANT_STEP=0 likewise; lr_stage_counters [14] counts the steps. */
 void lr_set_flood_giant_step(lr_context* ctx, int on);
+
+/* ---- rectified images ------------------------------------------------------------------ */
+/* The reference demo's last step (autorectify.cpp: homography_from_corners with clip 3.0, then warpPerspective).
+ * In float, as the demo: bounding box of the four corners, centre (max + min) / 2, size min(max - min, t->width * clip)
+ * (likewise the height), output size = its truncation, origin = centre - 0.5f * size.  In double: H (row-major, H[8] = 1)
+ * maps the source corners (0,0), (w,0), (0,h), (w,h) to the corners minus the origin (exact 4-point solve, 8x8 system with
+ * partial pivoting); M = H^-1 (adjugate / determinant) is the destination-to-source map lr_warp_perspective_device takes.
+ * H or M may be NULL.  Fails (non-zero, lr_last_error) on a non-finite corner, clip <= 0, a size below 1 and a singular
+ * system (three collinear corners).  Host only: needs no context and no GPU. */
+int lr_rectification_homography(const ImageTransform* t, float clip, double* H, double* M, int* out_width,
+                                int* out_height);
+enum lr_pixel_format { LR_PIX_U8 = 0, LR_PIX_U8X3 = 1, LR_PIX_F32 = 2 };
+/* Bilinear perspective warp of `batch` device frames in ONE launch on the context's stream: frame b at
+ * d_src + b*src_image_bytes (rows src_row_bytes apart), its output at d_dst + b*dst_image_bytes (rows dst_row_bytes
+ * apart); M: 9 doubles per frame (HOST), the destination-to-source map of that frame; one output size for all.
+ * Arithmetic: OpenCV's 8-bit bilinear warp, 5 fractional bits per axis, pixel centres on integer
+ * coordinates, a constant zero border.  Formats: u8 gray, u8 interleaved 3-channel, f32 gray (4-byte aligned pointers
+ * and strides).  Byte offsets are 64-bit.  Fails cleanly on null pointers, batch < 1, sizes below 1, strides shorter
+ * than a row (or, for batch > 1, than a frame), misaligned f32 pointers or strides, an unknown format, a non-finite M. */
+int lr_warp_perspective_device(lr_context* ctx, const void* d_src, size_t src_image_bytes, int batch, int width,
+                               int height, size_t src_row_bytes, int format, const double* M, void* d_dst,
+                               size_t dst_image_bytes, int out_width, int out_height, size_t dst_row_bytes);
 
 /* ---- stage API (tests, bench) --------------------------------------------------------- */
 /* Stage 1: fused 5x5 derivative filter + magnitude + direction bin + dilated-bin mask +

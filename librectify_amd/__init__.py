@@ -59,6 +59,7 @@ class RectificationConfig(C.Structure):  # reference src/librectify.h:137-150
 
 BUF_DX, BUF_DY, BUF_DMASK, BUF_LABEL, BUF_SEED_IDX, BUF_SEED_BIN, BUF_SEED_THR, BUF_MAXMAG, BUF_SEED_SIZE = range(9)
 T_UPLOAD, T_FILTER, T_SEEDS, T_FLOOD, T_FIT, T_RANSAC, T_TOTAL, T_FILTER_KERNEL, T_COUNT = range(9)
+PIX_U8, PIX_U8X3, PIX_F32 = range(3)  # enum lr_pixel_format
 
 EXPORTS = [
     "find_line_segment_groups", "release_line_segments", "compute_rectification_transform",
@@ -71,7 +72,7 @@ EXPORTS = [
     "lr_find_line_segment_groups_batch_host", "lr_find_line_segment_groups_batch_host_ptrs", "lr_host_alloc", "lr_host_free",
     "lr_set_seed_capacity", "lr_set_flood_blind_rounds", "lr_set_flood_staged", "lr_set_batch_streams", "lr_device_malloc", "lr_device_free", "lr_memcpy_h2d", "lr_cht_vanishing_point", "lr_refine_lines", "lr_set_estimator", "lr_ht_weights", "lr_prosac_solve", "lr_estimate_line_pencils_prosac", "lr_direct_solve", "lr_estimate_line_pencils_direct",
     "lr_estimate_line_pencils_cht", "lr_set_stage_timing", "lr_release_thread_context", "lr_set_flood_partial_commits", "lr_set_flood_logs", "lr_set_flood_just_in_time", "lr_set_flood_giant_step", "lr_context_trim", "lr_trim_thread_context",
-    "lr_find_line_segment_groups_batch_host_multi",
+    "lr_find_line_segment_groups_batch_host_multi", "lr_memcpy_d2h", "lr_rectification_homography", "lr_warp_perspective_device",
 ]
 
 _lib = None
@@ -136,6 +137,9 @@ def lib():
         L.lr_device_malloc.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
         L.lr_device_free.argtypes = [C.c_void_p, C.c_void_p]
         L.lr_memcpy_h2d.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.lr_memcpy_d2h.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.lr_rectification_homography.argtypes = [C.POINTER(ImageTransform), C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.lr_warp_perspective_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_size_t]
         L.lr_set_batch_streams.argtypes = [C.c_void_p, C.c_int]
         L.lr_set_batch_streams.restype = None
         L.lr_set_seed_capacity.argtypes = [C.c_void_p, C.c_uint32]
@@ -316,6 +320,72 @@ class Context:
 
     def device_free(self, ptr):
         _check(lib().lr_device_free(self._h, C.c_void_p(ptr)))
+
+    def device_download(self, ptr, shape, dtype):
+        """Copies a device buffer into a new numpy array of that shape and dtype, once the context's stream is done."""
+        a = np.empty(shape, dtype)
+        if a.nbytes:
+            _check(lib().lr_memcpy_d2h(self._h, _ptr(a), C.c_void_p(ptr), a.nbytes))
+        return a
+
+    # ---- rectified images ----
+    def warp_perspective_device(self, d_src, src_image_bytes, batch, width, height, src_row_bytes, fmt, M, d_dst,
+                                dst_image_bytes, out_width, out_height, dst_row_bytes):
+        """lr_warp_perspective_device: one launch for `batch` device frames, enqueued on the context's stream.  M: 9
+        doubles per frame ((batch, 3, 3) or (3, 3)), the destination-to-source map.  fmt: PIX_U8, PIX_U8X3, PIX_F32."""
+        M = np.ascontiguousarray(M, np.float64).reshape(-1)
+        if M.size < 9 * max(int(batch), 1):
+            raise ValueError("warp_perspective_device: M needs 9 values per frame")
+        _check(lib().lr_warp_perspective_device(self._h, C.c_void_p(d_src), src_image_bytes, batch, width, height, src_row_bytes, fmt, _ptr(M), C.c_void_p(d_dst), dst_image_bytes, out_width, out_height, dst_row_bytes))
+
+    def warp_perspective(self, array, M, out_size):
+        """Warps one host frame (2-D uint8 or float32, or H x W x 3 uint8) by M (3x3, destination -> source) into an image
+        of out_size = (width, height) on the GPU: upload, one launch, download.  Returns the (height, width[, 3]) array."""
+        a = np.ascontiguousarray(array)
+        if a.dtype == np.uint8 and a.ndim == 2:
+            fmt, bpp = PIX_U8, 1
+        elif a.dtype == np.uint8 and a.ndim == 3 and a.shape[2] == 3:
+            fmt, bpp = PIX_U8X3, 3
+        elif a.dtype == np.float32 and a.ndim == 2:
+            fmt, bpp = PIX_F32, 4
+        else:
+            raise ValueError("warp_perspective: a 2-D uint8 or float32 frame, or an H x W x 3 uint8 frame")
+        h, w = a.shape[:2]
+        ow, oh = int(out_size[0]), int(out_size[1])
+        d_src = self.device_upload(a)
+        d_dst = C.c_void_p()
+        try:
+            _check(lib().lr_device_malloc(self._h, ow * oh * bpp, C.byref(d_dst)))
+            self.warp_perspective_device(d_src, a.nbytes, 1, w, h, w * bpp, fmt, M, d_dst.value, ow * oh * bpp, ow, oh, ow * bpp)
+            return self.device_download(d_dst.value, (oh, ow) + a.shape[2:], a.dtype)
+        finally:
+            self.device_free(d_src)
+            if d_dst.value:
+                self.device_free(d_dst.value)
+
+    def rectify(self, image_u8, min_length=None, refine=False, cfg=None, clip=3.0):
+        """The reference demo's pipeline (autorectify.cpp) without its prescale, on an 8-bit frame (H x W gray or
+        H x W x 3 RGB): luma (4899 R + 9617 G + 1868 B + 8192) >> 14, / 256, find_line_segment_groups with min_length
+        max(w, h) / 100 by default, compute_rectification_transform (cfg: the demo's, horizontal_vp_min_distance = 2),
+        rectification_homography(clip) and the warp of the original frame.  Returns (lines, transform, warped)."""
+        img = np.ascontiguousarray(image_u8)
+        if img.dtype != np.uint8 or not (img.ndim == 2 or (img.ndim == 3 and img.shape[2] == 3)):
+            raise ValueError("rectify: an H x W or H x W x 3 uint8 frame")
+        if img.ndim == 3:
+            c = img.astype(np.int32)
+            gray = (4899 * c[..., 0] + 9617 * c[..., 1] + 1868 * c[..., 2] + 8192) >> 14
+        else:
+            gray = img
+        h, w = gray.shape
+        luma = gray.astype(np.float32) / np.float32(256.0)
+        if min_length is None:
+            min_length = max(w, h) / 100.0
+        lines = self.find_line_segment_groups(luma, min_length, refine=refine)
+        if cfg is None:
+            cfg = RectificationConfig(hmin=2.0)
+        t = compute_rectification_transform(lines, w, h, cfg)
+        _, M, size = rectification_homography(t, clip)
+        return lines, t, self.warp_perspective(img, M, size)
 
     def set_seed_capacity(self, cap):
         lib().lr_set_seed_capacity(self._h, int(cap))
@@ -518,6 +588,17 @@ def compute_rectification_transform_from_vp(width, height, vp_h, vp_v):
     a = Point(*[float(v) for v in vp_h])
     b = Point(*[float(v) for v in vp_v])
     return lib().compute_rectification_transform_from_vp(width, height, C.byref(a), C.byref(b))
+
+
+def rectification_homography(t, clip=3.0):
+    """lr_rectification_homography (the reference demo's homography_from_corners; host only) on an ImageTransform.
+    Returns (H, M, (width, height)): H (3x3) maps the source frame into the rectified image of that size, M = H^-1 the
+    rectified image back into the source (what the warp takes)."""
+    H = np.zeros(9, np.float64)
+    M = np.zeros(9, np.float64)
+    w, h = C.c_int(0), C.c_int(0)
+    _check(lib().lr_rectification_homography(C.byref(t), clip, _ptr(H), _ptr(M), C.byref(w), C.byref(h)))
+    return H.reshape(3, 3), M.reshape(3, 3), (w.value, h.value)
 
 
 def fit_vanishing_point(lines, group):

@@ -17,6 +17,7 @@ SOURCES = [
     "kernels_fit.hip",
     "kernels_ransac.hip",
     "kernels_groups.hip",
+    "kernels_warp.hip",
     "context.hip",
     "vp_host.cpp",
     "api.cpp",

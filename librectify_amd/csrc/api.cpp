@@ -330,6 +330,44 @@ int lr_memcpy_h2d(lr_context* ctx, void* dst, const void* src, size_t bytes) {
         return guard_fail("lr_memcpy_h2d");
     }
 }
+int lr_memcpy_d2h(lr_context* ctx, void* dst, const void* src, size_t bytes) {
+    try {
+        LR_HIP(hipSetDevice(ctx->device));
+        LR_HIP(hipStreamSynchronize(ctx->stream));  // (a non-blocking stream: hipMemcpy alone would not wait for it)
+        LR_HIP(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+        return 0;
+    } catch (...) {
+        return guard_fail("lr_memcpy_d2h");
+    }
+}
+
+int lr_rectification_homography(const ImageTransform* t, float clip, double* H, double* M, int* out_width,
+                                 int* out_height) {
+    try {
+        if (!t) {
+            set_error("lr_rectification_homography: no transform");
+            return 1;
+        }
+        if (const char* why = rectification_homography(*t, clip, H, M, out_width, out_height)) {
+            set_error(std::string("lr_rectification_homography: ") + why);
+            return 1;
+        }
+        return 0;
+    } catch (...) {
+        return guard_fail("lr_rectification_homography");
+    }
+}
+
+int lr_warp_perspective_device(lr_context* ctx, const void* d_src, size_t src_image_bytes, int batch, int width,
+                               int height, size_t src_row_bytes, int format, const double* M, void* d_dst,
+                               size_t dst_image_bytes, int out_width, int out_height, size_t dst_row_bytes) {
+    try {
+        return ctx_warp_perspective(ctx, d_src, src_image_bytes, batch, width, height, src_row_bytes, format, M, d_dst,
+                                    dst_image_bytes, out_width, out_height, dst_row_bytes);
+    } catch (...) {
+        return guard_fail("lr_warp_perspective_device");
+    }
+}
 
 void lr_set_batch_streams(lr_context* ctx, int n) { ctx->batch_streams = n < 1 ? 1 : n; }
 void lr_set_seed_capacity(lr_context* ctx, uint32_t cap) { ctx->seed_cap_once = cap; }

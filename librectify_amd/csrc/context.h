@@ -112,6 +112,11 @@ struct lr_context {
     uint32_t* d_cht_peak = nullptr;  // {cell, value lo, value hi, -, votes lo, votes hi}
     uint32_t* h_cht_peak = nullptr;  // pinned mirror
     int cht_d = 128;                 // accumulator size of estimator 3
+    // lr_warp_perspective_device: the frames' maps (9 doubles each) go up from page-locked memory on the context's stream
+    double* d_warp_m = nullptr;
+    double* h_warp_m = nullptr;
+    size_t cap_warp_m = 0;             // frames the two hold
+    hipEvent_t ev_warp_m = nullptr;    // the last upload from h_warp_m (rewritten only once that has been read)
     // RANSAC
     size_t cap_lines = 0;
     float* d_model = nullptr;  // 8 arrays of cap_lines
@@ -246,4 +251,8 @@ int ctx_find_groups_batch_host_multi(lr_context* c, const int* devices, int n_de
 // the caller makes its compute stream wait on that event.  num_threads: the reference's knob (threading.h:24-27),
 // here the number of host threads that stage a pageable frame (< 0: serial, as there).
 int ctx_upload_frame(lr_context* c, int slot, const float* buffer, int w, int h, int stride, int num_threads);
+// kernels_warp.hip: lr_warp_perspective_device (validates its arguments, uploads the maps, enqueues one launch)
+int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_bytes, int batch, int width, int height,
+                         size_t src_row_bytes, int format, const double* M, void* d_dst, size_t dst_image_bytes,
+                         int out_width, int out_height, size_t dst_row_bytes);
 }  // namespace lramd

@@ -742,7 +742,7 @@ void ctx_destroy(lr_context* c) {
                     c->fb.blocked, c->fb.count, c->fb.flags, c->fb.state, c->fb.tier, c->fb.blk, c->fb.act_a, c->fb.act_b,
                     c->fb.ctrl, c->fb.big_list, c->fb.handover, c->fb.rewalk_list, c->fb.log_off, c->fb.log_len, c->fb.log_buf, c->fb.dirty, c->fb.giant_mask, c->fb.slab_ring, c->fb.slab_hash, c->d_pairs, c->d_peak, c->d_weights,
                     c->d_samples, c->d_hcounts, c->comp_large, c->huge.tab, c->huge.jobs, c->huge.list, c->d_tables, c->d_orig, c->d_inl, c->d_flines, c->d_gctl,
-                    c->d_gnorm, c->d_models, c->d_refine_table, c->d_refine_edges, c->d_cht_acc, c->d_cht_idx, c->d_cht_peak, c->d_rec, c->d_recflags};
+                    c->d_gnorm, c->d_models, c->d_refine_table, c->d_refine_edges, c->d_cht_acc, c->d_cht_idx, c->d_cht_peak, c->d_rec, c->d_recflags, c->d_warp_m};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     delete static_cast<StagingCrew*>(c->crew);
@@ -776,6 +776,8 @@ void ctx_destroy(lr_context* c) {
         if (e) (void)hipEventDestroy(e);
     if (c->h_cht_idx) (void)hipHostFree(c->h_cht_idx);
     if (c->h_cht_peak) (void)hipHostFree(c->h_cht_peak);
+    if (c->h_warp_m) (void)hipHostFree(c->h_warp_m);
+    if (c->ev_warp_m) (void)hipEventDestroy(c->ev_warp_m);
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
     (void)hipStreamDestroy(c->stream);

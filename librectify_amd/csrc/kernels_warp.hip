@@ -1,0 +1,289 @@
+// Rectified images: the bilinear perspective warp of lr_warp_perspective_device for gfx950.
+//
+// A gather: every destination pixel maps back into its source frame through the frame's 3x3 matrix M and reads four
+// source pixels.  The source is read through L2, so what matters is that the pixels a workgroup reads lie close
+// together, and that workgroups reading neighbouring source rows share an L2:
+//
+//   * a workgroup takes one 64 x 16 tile of the destination (a wavefront 64 x 4: 16 lanes across, 4 pixels a lane,
+//     4 rows), so its source footprint is a compact patch rather than a long row;
+//   * the tiles of all frames, in row-major order frame by frame, are cut into eight contiguous runs, one per XCD
+//     (workgroups are dealt to the XCDs round-robin: the XCD band order of kernels_filter.hip), so each XCD's L2 holds
+//     one band of destination rows and the source rows they read;
+//   * a lane's four pixels are consecutive, so its u8 results go out as one dword (u8x3: three, f32: one dwordx4)
+//     wherever the destination address allows; the two horizontal taps of a source row are one u16 (u8) or dwordx2 (f32)
+//     load where they are both inside and aligned.
+//
+// The arithmetic is the canonical one of DESIGN.md section 3 (mirrored by tests/numpy_warp_ref.py): coordinates in
+// double without contraction (-ffp-contract=off), 5 fractional bits per axis, integer taps and weights.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "context.h"
+
+namespace lramd {
+namespace {
+
+constexpr int kTileW = 64;  // destination pixels per tile row (16 lanes x 4 pixels)
+constexpr int kTileH = 16;  // destination rows per tile (4 wavefronts x 4 rows)
+constexpr int kBlock = 256;
+constexpr int kMaxGrid = 8 * 8192;  // beyond that the workgroups of an XCD loop over its run of tiles
+
+struct WarpArgs {
+    const uint8_t* src;
+    size_t src_image_bytes, src_row_bytes;
+    int w, h;
+    uint8_t* dst;
+    size_t dst_image_bytes, dst_row_bytes;
+    int ow, oh;
+    const double* M;  // 9 doubles per frame
+    int tiles_x, tiles_per_frame, n_tiles;
+};
+
+// ((M0 x + M1 y) + M2) * Wq clamped to [INT_MIN, INT_MAX] and rounded half to even; a NaN fails both comparisons and
+// becomes INT_MIN, whose taps lie outside every source
+__device__ __forceinline__ int fixed_coord(double v) {
+    const double c = v >= 2147483647.0 ? 2147483647.0 : (v >= -2147483648.0 ? v : -2147483648.0);
+    return (int)rint(c);
+}
+
+struct Taps {
+    int ix, iy;        // the top-left tap
+    int w00, w01, w10, w11;  // weights of (ix, iy), (ix+1, iy), (ix, iy+1), (ix+1, iy+1); they sum to 1024
+};
+
+__device__ __forceinline__ Taps taps_of(const double* __restrict__ m, unsigned x, unsigned y) {
+    const double xd = (double)x, yd = (double)y;
+    const double W0 = (m[6] * xd + m[7] * yd) + m[8];
+    const double Wq = W0 != 0.0 ? 32.0 / W0 : 0.0;
+    const int X = fixed_coord(((m[0] * xd + m[1] * yd) + m[2]) * Wq);
+    const int Y = fixed_coord(((m[3] * xd + m[4] * yd) + m[5]) * Wq);
+    Taps t;
+    t.ix = X >> 5;
+    t.iy = Y >> 5;
+    const int ax = X & 31, ay = Y & 31;
+    t.w00 = (32 - ax) * (32 - ay);
+    t.w01 = ax * (32 - ay);
+    t.w10 = (32 - ax) * ay;
+    t.w11 = ax * ay;
+    return t;
+}
+
+__device__ __forceinline__ bool inside(int i, int n) { return (unsigned)i < (unsigned)n; }
+
+// the two horizontal taps (ix, ix+1) of one source row; 0 outside
+__device__ __forceinline__ void pair_u8(const uint8_t* row, bool row_in, int ix, int w, uint32_t& a, uint32_t& b) {
+    const bool in_a = row_in && inside(ix, w), in_b = row_in && inside(ix + 1, w);
+    a = 0;
+    b = 0;
+    if (in_a && in_b && ((reinterpret_cast<uintptr_t>(row) + (unsigned)ix) & 1u) == 0) {
+        const uint32_t v = *reinterpret_cast<const uint16_t*>(row + ix);
+        a = v & 0xFFu;
+        b = v >> 8;
+    } else {
+        if (in_a) a = row[ix];
+        if (in_b) b = row[ix + 1];
+    }
+}
+
+__device__ __forceinline__ void pair_f32(const uint8_t* row, bool row_in, int ix, int w, float& a, float& b) {
+    const bool in_a = row_in && inside(ix, w), in_b = row_in && inside(ix + 1, w);
+    a = 0.f;
+    b = 0.f;
+    const float* r = reinterpret_cast<const float*>(row);
+    if (in_a && in_b && ((reinterpret_cast<uintptr_t>(r + ix)) & 7u) == 0) {
+        const float2 v = *reinterpret_cast<const float2*>(r + ix);
+        a = v.x;
+        b = v.y;
+    } else {
+        if (in_a) a = r[ix];
+        if (in_b) b = r[ix + 1];
+    }
+}
+
+// one interleaved 3-byte tap at p: an aligned u16 and the byte beside it (two loads, no branch)
+__device__ __forceinline__ uint32_t tap_u8x3(const uint8_t* p, bool in) {
+    if (!in) return 0;
+    const uint32_t odd = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 1u);
+    const uint32_t v = *reinterpret_cast<const uint16_t*>(p + odd);
+    const uint32_t s = p[odd ? 0 : 2];
+    return odd ? (s | (v << 8)) : (v | (s << 16));  // bytes r | g << 8 | b << 16
+}
+
+__device__ __forceinline__ uint32_t blend_u8(uint32_t a, uint32_t b, uint32_t c, uint32_t d, const Taps& t) {
+    return (a * (uint32_t)t.w00 + b * (uint32_t)t.w01 + c * (uint32_t)t.w10 + d * (uint32_t)t.w11 + 512u) >> 10;
+}
+
+template <int kFormat>
+__global__ __launch_bounds__(kBlock) void warp_perspective_kernel(WarpArgs g) {
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    const unsigned lx = (unsigned)lane & 15u, row_in_tile = (unsigned)(wave * 4 + (lane >> 4));
+    // XCD band order: the tiles [xcd * per_xcd, (xcd + 1) * per_xcd) go to the workgroups of one XCD (the launcher makes
+    // the grid a multiple of eight)
+    const int per_xcd = (g.n_tiles + 7) / 8;
+    const int xcd = (int)(blockIdx.x & 7u), slots = (int)(gridDim.x >> 3);
+    for (int j = (int)(blockIdx.x >> 3); j < per_xcd; j += slots) {
+        const int tile = xcd * per_xcd + j;
+        if (tile >= g.n_tiles) return;
+        const int b = tile / g.tiles_per_frame;
+        const int r = tile - b * g.tiles_per_frame;
+        const int ty = r / g.tiles_x, tx = r - ty * g.tiles_x;
+        const unsigned y = (unsigned)ty * kTileH + row_in_tile;
+        const unsigned x0 = (unsigned)tx * kTileW + lx * 4u;
+        if (y >= (unsigned)g.oh || x0 >= (unsigned)g.ow) continue;
+        const double* m = g.M + (size_t)b * 9;
+        const uint8_t* src = g.src + (size_t)b * g.src_image_bytes;
+        uint8_t* out = g.dst + (size_t)b * g.dst_image_bytes + (size_t)y * g.dst_row_bytes;
+        const int n = min(4, g.ow - (int)x0);  // pixels of this lane inside the row
+
+        uint32_t res_u8 = 0;          // LR_PIX_U8: four bytes
+        uint32_t res_rgb[3] = {0, 0, 0};  // LR_PIX_U8X3: twelve bytes
+        float res_f[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const Taps t = taps_of(m, x0 + (unsigned)k, y);
+            const bool in0 = inside(t.iy, g.h), in1 = inside(t.iy + 1, g.h);
+            const uint8_t* row0 = src + (size_t)(in0 ? t.iy : 0) * g.src_row_bytes;
+            const uint8_t* row1 = src + (size_t)(in1 ? t.iy + 1 : 0) * g.src_row_bytes;
+            if (kFormat == LR_PIX_U8) {
+                uint32_t a, bb, c, d;
+                pair_u8(row0, in0, t.ix, g.w, a, bb);
+                pair_u8(row1, in1, t.ix, g.w, c, d);
+                res_u8 |= blend_u8(a, bb, c, d, t) << (8 * k);
+            } else if (kFormat == LR_PIX_U8X3) {
+                const bool ia = inside(t.ix, g.w), ib = inside(t.ix + 1, g.w);
+                const size_t oa = (size_t)(ia ? t.ix : 0) * 3, ob = (size_t)(ib ? t.ix + 1 : 0) * 3;
+                const uint32_t p00 = tap_u8x3(row0 + oa, in0 && ia), p01 = tap_u8x3(row0 + ob, in0 && ib);
+                const uint32_t p10 = tap_u8x3(row1 + oa, in1 && ia), p11 = tap_u8x3(row1 + ob, in1 && ib);
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) {
+                    const int s = 8 * ch;
+                    const uint32_t v = blend_u8((p00 >> s) & 0xFFu, (p01 >> s) & 0xFFu, (p10 >> s) & 0xFFu, (p11 >> s) & 0xFFu, t);
+                    const int byte = 3 * k + ch;  // byte of the lane's twelve
+                    res_rgb[byte >> 2] |= v << (8 * (byte & 3));
+                }
+            } else {
+                float a, bb, c, d;
+                pair_f32(row0, in0, t.ix, g.w, a, bb);
+                pair_f32(row1, in1, t.ix, g.w, c, d);
+                const float f00 = (float)t.w00 / 1024.0f, f01 = (float)t.w01 / 1024.0f;
+                const float f10 = (float)t.w10 / 1024.0f, f11 = (float)t.w11 / 1024.0f;
+                res_f[k] = ((a * f00 + bb * f01) + c * f10) + d * f11;
+            }
+        }
+
+        if (kFormat == LR_PIX_U8) {
+            uint8_t* p = out + x0;
+            if (n == 4 && (reinterpret_cast<uintptr_t>(p) & 3u) == 0) {
+                *reinterpret_cast<uint32_t*>(p) = res_u8;
+            } else {
+                for (int k = 0; k < n; ++k) p[k] = (uint8_t)(res_u8 >> (8 * k));
+            }
+        } else if (kFormat == LR_PIX_U8X3) {
+            uint8_t* p = out + (size_t)x0 * 3;
+            if (n == 4 && (reinterpret_cast<uintptr_t>(p) & 3u) == 0) {
+                uint32_t* q = reinterpret_cast<uint32_t*>(p);
+                q[0] = res_rgb[0];
+                q[1] = res_rgb[1];
+                q[2] = res_rgb[2];
+            } else {
+                for (int k = 0; k < 3 * n; ++k) p[k] = (uint8_t)(res_rgb[k >> 2] >> (8 * (k & 3)));
+            }
+        } else {
+            float* p = reinterpret_cast<float*>(out) + x0;
+            if (n == 4 && (reinterpret_cast<uintptr_t>(p) & 15u) == 0) {
+                *reinterpret_cast<float4*>(p) = make_float4(res_f[0], res_f[1], res_f[2], res_f[3]);
+            } else {
+                for (int k = 0; k < n; ++k) p[k] = res_f[k];
+            }
+        }
+    }
+}
+
+// bytes one frame spans: (rows - 1) * row_bytes + last_row_bytes; false if that does not fit in 64 bits
+bool frame_span(int rows, size_t row_bytes, size_t last_row_bytes, size_t* out) {
+    size_t s;
+    if (__builtin_mul_overflow((size_t)(rows - 1), row_bytes, &s) || __builtin_add_overflow(s, last_row_bytes, &s)) return false;
+    *out = s;
+    return true;
+}
+
+}  // namespace
+
+int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_bytes, int batch, int width, int height,
+                         size_t src_row_bytes, int format, const double* M, void* d_dst, size_t dst_image_bytes,
+                         int out_width, int out_height, size_t dst_row_bytes) {
+    auto fail = [](const char* what) {
+        set_error(std::string("lr_warp_perspective_device: ") + what);
+        return 1;
+    };
+    if (!c) return fail("no context");
+    if (!d_src || !d_dst || !M) return fail("null pointer (source, destination or M)");
+    if (batch < 1) return fail("batch < 1");
+    if (width < 1 || height < 1 || out_width < 1 || out_height < 1) return fail("source or output size below 1");
+    if (format != LR_PIX_U8 && format != LR_PIX_U8X3 && format != LR_PIX_F32) return fail("unknown pixel format");
+    const size_t bpp = format == LR_PIX_U8 ? 1 : (format == LR_PIX_U8X3 ? 3 : 4);
+    if (src_row_bytes < (size_t)width * bpp) return fail("source row stride shorter than a row");
+    if (dst_row_bytes < (size_t)out_width * bpp) return fail("destination row stride shorter than a row");
+    size_t src_span, dst_span;
+    if (!frame_span(height, src_row_bytes, (size_t)width * bpp, &src_span) ||
+        !frame_span(out_height, dst_row_bytes, (size_t)out_width * bpp, &dst_span))
+        return fail("frame larger than the address space");
+    if (batch > 1 && (src_image_bytes < src_span || dst_image_bytes < dst_span))
+        return fail("image stride shorter than a frame");
+    if (format == LR_PIX_F32) {
+        const uintptr_t bits = reinterpret_cast<uintptr_t>(d_src) | reinterpret_cast<uintptr_t>(d_dst) | src_row_bytes |
+                               dst_row_bytes | (batch > 1 ? (src_image_bytes | dst_image_bytes) : 0);
+        if (bits & 3u) return fail("f32 pointer or stride not 4-byte aligned");
+    }
+    for (size_t i = 0; i < (size_t)batch * 9; ++i)
+        if (!std::isfinite(M[i])) return fail("M is not finite");
+    const int64_t tiles_x = ((int64_t)out_width + kTileW - 1) / kTileW, tiles_y = ((int64_t)out_height + kTileH - 1) / kTileH;
+    const int64_t n_tiles = tiles_x * tiles_y * (int64_t)batch;
+    if (n_tiles > 0x7FFFFFF0ll) return fail("output larger than 2^31 tiles of 64 x 16 pixels");
+
+    LR_HIP(hipSetDevice(c->device));
+    if ((size_t)batch > c->cap_warp_m) {  // (grows: the buffers of a previous call may still be read by its launch)
+        LR_HIP(hipStreamSynchronize(c->stream));
+        if (c->d_warp_m) LR_HIP(hipFree(c->d_warp_m));
+        if (c->h_warp_m) LR_HIP(hipHostFree(c->h_warp_m));
+        c->d_warp_m = nullptr;
+        c->h_warp_m = nullptr;
+        c->cap_warp_m = 0;
+        LR_HIP(hipMalloc((void**)&c->d_warp_m, (size_t)batch * 9 * sizeof(double)));
+        LR_HIP(hipHostMalloc((void**)&c->h_warp_m, (size_t)batch * 9 * sizeof(double)));
+        c->cap_warp_m = (size_t)batch;
+    }
+    if (!c->ev_warp_m) LR_HIP(hipEventCreateWithFlags(&c->ev_warp_m, hipEventDisableTiming));
+    LR_HIP(hipEventSynchronize(c->ev_warp_m));  // the previous call's upload has read h_warp_m
+    std::memcpy(c->h_warp_m, M, (size_t)batch * 9 * sizeof(double));
+    LR_HIP(hipMemcpyAsync(c->d_warp_m, c->h_warp_m, (size_t)batch * 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    LR_HIP(hipEventRecord(c->ev_warp_m, c->stream));
+
+    WarpArgs g;
+    g.src = static_cast<const uint8_t*>(d_src);
+    g.src_image_bytes = src_image_bytes;
+    g.src_row_bytes = src_row_bytes;
+    g.w = width;
+    g.h = height;
+    g.dst = static_cast<uint8_t*>(d_dst);
+    g.dst_image_bytes = dst_image_bytes;
+    g.dst_row_bytes = dst_row_bytes;
+    g.ow = out_width;
+    g.oh = out_height;
+    g.M = c->d_warp_m;
+    g.tiles_x = (int)tiles_x;
+    g.tiles_per_frame = (int)(tiles_x * tiles_y);
+    g.n_tiles = (int)n_tiles;
+    const int grid = (int)std::min<int64_t>((n_tiles + 7) / 8 * 8, kMaxGrid);
+    if (format == LR_PIX_U8)
+        hipLaunchKernelGGL(warp_perspective_kernel<LR_PIX_U8>, dim3(grid), dim3(kBlock), 0, c->stream, g);
+    else if (format == LR_PIX_U8X3)
+        hipLaunchKernelGGL(warp_perspective_kernel<LR_PIX_U8X3>, dim3(grid), dim3(kBlock), 0, c->stream, g);
+    else
+        hipLaunchKernelGGL(warp_perspective_kernel<LR_PIX_F32>, dim3(grid), dim3(kBlock), 0, c->stream, g);
+    LR_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // namespace lramd

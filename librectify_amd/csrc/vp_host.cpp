@@ -617,4 +617,78 @@ void assign_groups(const LineSegment* lines, int n, LineSegment* new_lines, int 
         if (best[i] > thr) new_lines[i].group_id = best_id[i];
 }
 
+const char* rectification_homography(const ImageTransform& t, float clip, double* H, double* M, int* out_width,
+                                     int* out_height) {
+    const Point c[4] = {t.top_left, t.top_right, t.bottom_left, t.bottom_right};
+    for (const Point& p : c)
+        if (!std::isfinite(p.x) || !std::isfinite(p.y)) return "a corner of the transform is not finite";
+    if (!(clip > 0.f)) return "clip must be positive";
+    // the bounding box, its centre and the clipped size in float, as the demo computes them
+    float xmin = c[0].x, xmax = c[0].x, ymin = c[0].y, ymax = c[0].y;
+    for (int k = 1; k < 4; ++k) {
+        xmin = std::min(xmin, c[k].x);
+        xmax = std::max(xmax, c[k].x);
+        ymin = std::min(ymin, c[k].y);
+        ymax = std::max(ymax, c[k].y);
+    }
+    const float xc = (xmax + xmin) / 2, yc = (ymax + ymin) / 2;
+    const float width = std::min(xmax - xmin, (float)t.width * clip);
+    const float height = std::min(ymax - ymin, (float)t.height * clip);
+    if (!(width >= 1.f) || !(height >= 1.f)) return "the rectified image would be smaller than one pixel";
+    if (!(width < 2147483648.f) || !(height < 2147483648.f)) return "the rectified image would be wider or taller than 2^31 - 1 pixels";
+    const float x0 = xc - 0.5f * width, y0 = yc - 0.5f * height;
+
+    // exact 4-point solve in double: h0 x + h1 y + h2 - u (h6 x + h7 y) = u, h3 x + h4 y + h5 - v (h6 x + h7 y) = v
+    const double src[4][2] = {{0.0, 0.0}, {(double)t.width, 0.0}, {0.0, (double)t.height}, {(double)t.width, (double)t.height}};
+    double A[8][9];
+    for (int k = 0; k < 4; ++k) {
+        const double x = src[k][0], y = src[k][1];
+        const double u = (double)(c[k].x - x0), v = (double)(c[k].y - y0);
+        const double r0[9] = {x, y, 1.0, 0.0, 0.0, 0.0, -x * u, -y * u, u};
+        const double r1[9] = {0.0, 0.0, 0.0, x, y, 1.0, -x * v, -y * v, v};
+        for (int j = 0; j < 9; ++j) {
+            A[2 * k][j] = r0[j];
+            A[2 * k + 1][j] = r1[j];
+        }
+    }
+    double scale = 0.0;
+    for (auto& row : A)
+        for (int j = 0; j < 8; ++j) scale = std::max(scale, std::fabs(row[j]));
+    for (int col = 0; col < 8; ++col) {
+        int piv = col;
+        for (int r = col + 1; r < 8; ++r)
+            if (std::fabs(A[r][col]) > std::fabs(A[piv][col])) piv = r;
+        if (!(std::fabs(A[piv][col]) > 1e-12 * scale)) return "singular homography (three corners are collinear)";
+        if (piv != col)
+            for (int j = 0; j < 9; ++j) std::swap(A[piv][j], A[col][j]);
+        for (int r = col + 1; r < 8; ++r) {
+            const double f = A[r][col] / A[col][col];
+            for (int j = col; j < 9; ++j) A[r][j] -= f * A[col][j];
+        }
+    }
+    double h[9];
+    h[8] = 1.0;
+    for (int r = 7; r >= 0; --r) {
+        double s = A[r][8];
+        for (int j = r + 1; j < 8; ++j) s -= A[r][j] * h[j];
+        h[r] = s / A[r][r];
+    }
+    // M = adj(H) / det(H)
+    const double a[9] = {h[4] * h[8] - h[5] * h[7], h[2] * h[7] - h[1] * h[8], h[1] * h[5] - h[2] * h[4],
+                         h[5] * h[6] - h[3] * h[8], h[0] * h[8] - h[2] * h[6], h[2] * h[3] - h[0] * h[5],
+                         h[3] * h[7] - h[4] * h[6], h[1] * h[6] - h[0] * h[7], h[0] * h[4] - h[1] * h[3]};
+    const double det = h[0] * a[0] + h[1] * a[3] + h[2] * a[6];
+    double m[9];
+    for (int j = 0; j < 9; ++j) m[j] = a[j] / det;
+    for (int j = 0; j < 9; ++j)
+        if (!std::isfinite(h[j]) || !std::isfinite(m[j]) || det == 0.0) return "singular homography (three corners are collinear)";
+    if (H)
+        for (int j = 0; j < 9; ++j) H[j] = h[j];
+    if (M)
+        for (int j = 0; j < 9; ++j) M[j] = m[j];
+    if (out_width) *out_width = (int)width;
+    if (out_height) *out_height = (int)height;
+    return nullptr;
+}
+
 }  // namespace lramd

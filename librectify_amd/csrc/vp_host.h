@@ -65,4 +65,10 @@ ImageTransform rectification_transform(const LineSegment* lines, int n, int widt
 ImageTransform rectification_transform_from_vp(int width, int height, const Point& vp_h, const Point& vp_v);  // :93-119
 void assign_groups(const LineSegment* lines, int n, LineSegment* new_lines, int n_new, float tol_deg);        // :218-265
 
+// The demo's homography_from_corners (autorectify.cpp:152-192) restated: H maps the source frame's corners to the
+// transform's corners shifted into a clipped bounding box, M = H^-1 (either may be null).  Returns nullptr on success,
+// else what is wrong (include/librectify_amd.h: lr_rectification_homography).
+const char* rectification_homography(const ImageTransform& t, float clip, double* H, double* M, int* out_width,
+                                     int* out_height);
+
 }  // namespace lramd

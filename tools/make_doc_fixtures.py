@@ -10,6 +10,8 @@ Outputs (data only, no reference source text):
                                        which autorectify.cpp:329-330 uses)
   tests/golden/doc_warp_lines.csv      copy of doc/image.jpg_warp_lines.csv (848 rows)
   tests/golden/doc_warp_tform.csv      copy of doc/image.jpg_warp_tform.csv (6 rows)
+  tests/golden/doc_warp_gray.npz       uint8 594x1132 luma (key "gray") of doc/image.jpg_warp.jpg, the demo's
+                                       warp of doc/image.jpg under that transform (decoded like doc_image_gray.npy)
 """
 import os, shutil, sys
 import numpy as np
@@ -25,6 +27,9 @@ def main():
     np.save(os.path.join(OUT, "doc_image_gray.npy"), a)
     shutil.copyfile(os.path.join(REF, "image.jpg_warp_lines.csv"), os.path.join(OUT, "doc_warp_lines.csv"))
     shutil.copyfile(os.path.join(REF, "image.jpg_warp_tform.csv"), os.path.join(OUT, "doc_warp_tform.csv"))
+    warped = np.asarray(Image.open(os.path.join(REF, "image.jpg_warp.jpg")).convert("L"), dtype=np.uint8)
+    assert warped.shape == (594, 1132), warped.shape
+    np.savez_compressed(os.path.join(OUT, "doc_warp_gray.npz"), gray=warped)
     print("wrote fixtures to", os.path.normpath(OUT))
 
 if __name__ == "__main__":
