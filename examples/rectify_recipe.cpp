@@ -5,13 +5,16 @@
 // (<prefix>_lines.csv: x1,y1,x2,y2,weight,err,group_id per row; <prefix>_tform.csv: TL, TR, BL, BR, hvp, vvp).
 //
 //   rectify_recipe in.pgm|in.ppm out_prefix [--max-size N|fraction] [--refine] [--threads N]
-//                  [--h-strategy rotate_h|rotate_v|rectify|keep] [--v-strategy ...] [--warp]
+//                  [--h-strategy rotate_h|rotate_v|rectify|keep] [--v-strategy ...] [--warp] [--device-prepare]
 //
 // Input is a binary PGM (P5, 8 bit) or PPM (P6, 8 bit; converted with the usual integer luma weights
 // (4899 R + 9617 G + 1868 B + 8192) >> 14).  Image decoding stays with the caller's imaging library.
 // --warp: the demo's last step too (autorectify.cpp:357-360) -- lr_rectification_homography with clip 3.0, the 8-bit
 // frame as read warped on the GPU (lr_warp_perspective_device), written as <out_prefix>_warp.pgm or .ppm
 // (INTEGRATION.md §6).
+// --device-prepare: the first step on the GPU as well -- the file's 8-bit pixels go up as they are, luma, / 256 and the
+// prescale are one lr_warp_perspective_device call with LR_WARP_PREPARE, and lr_find_line_segment_groups_device runs
+// on the prepared frame where it lies.  Same CSV files, byte for byte.
 // Links against librectify_amd.so exactly like a program written for the reference.
 #include <algorithm>
 #include <cctype>
@@ -129,6 +132,38 @@ Gray prescale(const Gray& in, int max_size, float& scale) {
     return out;
 }
 
+// --device-prepare: the prescaled size by the rule of prescale() above, the raw frame uploaded, prepared on the device
+// and searched there.  Fills `found`, `out_w`, `out_h` and `scale`; returns false with the reason on stderr.
+bool find_groups_device_prepared(const Gray& g, int max_size, bool refine, int threads,
+                                 std::vector<LineSegment>& found, int& out_w, int& out_h, float& scale) {
+    scale = std::min((float)max_size / (float)std::max(g.w, g.h), 1.0f);
+    out_w = scale == 1.0f ? g.w : std::max(1, (int)std::lround(g.w * (double)scale));
+    out_h = scale == 1.0f ? g.h : std::max(1, (int)std::lround(g.h * (double)scale));
+    lr_context* ctx = nullptr;
+    void* d_src = nullptr;
+    void* d_img = nullptr;
+    const size_t img_bytes = (size_t)out_w * out_h * sizeof(float);
+    found.resize((size_t)out_w * out_h / 6 + 16);
+    int n = 0;
+    const bool ok =
+        lr_context_create(0, &ctx) == 0 && lr_device_malloc(ctx, g.raw.size(), &d_src) == 0 &&
+        lr_device_malloc(ctx, img_bytes, &d_img) == 0 && lr_memcpy_h2d(ctx, d_src, g.raw.data(), g.raw.size()) == 0 &&
+        lr_warp_perspective_device(ctx, d_src, g.raw.size(), 1, g.w, g.h, (size_t)g.w * g.ch,
+                                   (g.ch == 3 ? LR_PIX_U8X3 : LR_PIX_U8) | LR_WARP_PREPARE, nullptr, d_img, img_bytes, out_w,
+                                   out_h, (size_t)out_w * sizeof(float)) == 0 &&
+        lr_find_line_segment_groups_device(ctx, static_cast<const float*>(d_img), out_w, out_h, out_w,
+                                           (float)std::max(out_w, out_h) / 100.0f, refine, threads, found.data(),
+                                           (int)found.size(), &n) == 0;
+    if (!ok) std::fprintf(stderr, "device prepare failed: %s\n", lr_last_error());
+    if (ctx) {
+        if (d_src) lr_device_free(ctx, d_src);
+        if (d_img) lr_device_free(ctx, d_img);
+        lr_context_destroy(ctx);
+    }
+    found.resize(ok ? (size_t)std::min(n, (int)found.size()) : 0);
+    return ok;
+}
+
 // The demo's homography_from_corners(t, 3.0) + warpPerspective of the frame as read, on the GPU; writes
 // <prefix>_warp.pgm / .ppm.  Returns false with the reason on stderr.
 bool warp_frame(const Gray& g, const ImageTransform& t, const std::string& prefix) {
@@ -183,12 +218,12 @@ int main(int argc, char** argv) {
     if (argc < 3) {
         std::fprintf(stderr,
                      "usage: %s in.pgm|in.ppm out_prefix [--max-size N|fraction] [--refine] [--threads N]\n"
-                     "          [--h-strategy rotate_h|rotate_v|rectify|keep] [--v-strategy ...] [--warp]\n",
+                     "          [--h-strategy rotate_h|rotate_v|rectify|keep] [--v-strategy ...] [--warp] [--device-prepare]\n",
                      argv[0]);
         return 2;
     }
     float max_size = 1200.f;  // the demo's default
-    bool refine = false, warp = false;
+    bool refine = false, warp = false, device_prepare = false;
     int threads = -1;
     RectificationConfig cfg;
     cfg.horizontal_vp_min_distance = 2;  // autorectify.cpp:347
@@ -197,6 +232,7 @@ int main(int argc, char** argv) {
         const bool has_val = i + 1 < argc;
         if (a == "--refine") refine = true;
         else if (a == "--warp") warp = true;
+        else if (a == "--device-prepare") device_prepare = true;
         else if (a == "--max-size" && has_val) max_size = (float)std::atof(argv[++i]);
         else if (a == "--threads" && has_val) threads = std::atoi(argv[++i]);
         else if (a == "--h-strategy" && has_val && parse_strategy(argv[i + 1], cfg.h_strategy)) ++i;
@@ -214,11 +250,21 @@ int main(int argc, char** argv) {
     // a value below 1 is a fraction of the long side (autorectify.cpp:121-125)
     const int max_px = max_size < 1.f ? (int)(std::max(full.w, full.h) * max_size) : (int)max_size;
     float scale = 1.f;
-    Gray img = prescale(full, std::max(1, max_px), scale);
-
-    int n = 0;
-    LineSegment* lines = find_line_segment_groups(img.px.data(), img.w, img.h, img.w,
-                                                  (float)std::max(img.w, img.h) / 100.0f, refine, threads, &n);
+    int n = 0, small_w = 0, small_h = 0;
+    LineSegment* lines = nullptr;
+    std::vector<LineSegment> found;  // --device-prepare: the caller's array
+    if (device_prepare) {
+        if (!find_groups_device_prepared(full, std::max(1, max_px), refine, threads, found, small_w, small_h, scale))
+            return 1;
+        n = (int)found.size();
+        lines = found.data();
+    } else {
+        Gray img = prescale(full, std::max(1, max_px), scale);
+        small_w = img.w;
+        small_h = img.h;
+        lines = find_line_segment_groups(img.px.data(), img.w, img.h, img.w, (float)std::max(img.w, img.h) / 100.0f,
+                                         refine, threads, &n);
+    }
     for (int i = 0; i < n; ++i) {  // back to the coordinates of the full image
         lines[i].x1 /= scale;
         lines[i].y1 /= scale;
@@ -241,9 +287,9 @@ int main(int argc, char** argv) {
     tf << t.bottom_right.x << "," << t.bottom_right.y << "\n";
     tf << t.horizontal_vp.x << "," << t.horizontal_vp.y << "," << t.horizontal_vp.z << "\n";
     tf << t.vertical_vp.x << "," << t.vertical_vp.y << "," << t.vertical_vp.z << "\n";
-    std::printf("%dx%d -> %dx%d (scale %g), %d segments, wrote %s_lines.csv and %s_tform.csv\n", full.w, full.h, img.w,
-                img.h, (double)scale, n, prefix.c_str(), prefix.c_str());
-    release_line_segments(&lines);
+    std::printf("%dx%d -> %dx%d (scale %g), %d segments, wrote %s_lines.csv and %s_tform.csv\n", full.w, full.h, small_w,
+                small_h, (double)scale, n, prefix.c_str(), prefix.c_str());
+    if (!device_prepare) release_line_segments(&lines);
     if (warp && !warp_frame(full, t, prefix)) return 1;
-    return lines == nullptr ? 0 : 1;
+    return device_prepare || lines == nullptr ? 0 : 1;
 }

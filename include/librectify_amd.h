@@ -41,7 +41,7 @@ typedef struct lr_context lr_context;
 int lr_context_create(int device, lr_context** out);
 void lr_context_destroy(lr_context* ctx);
 /* The drop-in functions keep one context per calling host thread (device workspace of about 130 bytes per pixel of the
- * largest frame seen, 288 MB of flood overflow slabs, 32 MB of hand-over records, page-locked staging, staging threads) until the thread exits;
+ * largest frame seen, 36 MB of flood overflow slabs, 32 MB of hand-over records, page-locked staging, staging threads) until the thread exits;
  * a thread that is done with the library for a while can give it back at once.  The next call makes a new one. */
 void lr_release_thread_context(void);
 /* The reference is stateless; a context is not: its device workspace is sized by the LARGEST frame it has seen (an 8192 x 8192
@@ -191,6 +191,19 @@ enum lr_pixel_format { LR_PIX_U8 = 0, LR_PIX_U8X3 = 1, LR_PIX_F32 = 2 };
 int lr_warp_perspective_device(lr_context* ctx, const void* d_src, size_t src_image_bytes, int batch, int width,
                                int height, size_t src_row_bytes, int format, const double* M, void* d_dst,
                                size_t dst_image_bytes, int out_width, int out_height, size_t dst_row_bytes);
+/* `format` is a word: its low byte is the source's lr_pixel_format, the bits above it are options (0: the warp above).
+ * LR_WARP_PREPARE makes the call the detector's front end, the reference demo's first step (gray, / 256, INTER_AREA
+ * prescale) on frames that stay in HBM: the destination is F32 GRAY whatever the source format, its value luma / 256
+ * area-averaged from width x height down to out_width x out_height (scale n_src / n_dst per axis, as cv::resize with a
+ * dsize; out == src is a pure conversion, exactly v / 256).  Luma: u8 the value; u8x3 (4899 c0 + 9617 c1 + 1868 c2 +
+ * 8192) >> 14; f32 the value itself and no / 256 (the caller has scaled it).  M is ignored and may be NULL.  Batched
+ * like the warp: one launch on the context's stream, 64-bit byte offsets, the caller's strides (dst_row_bytes >=
+ * 4 * out_width).  Arithmetic: per axis destination sample i covers [i s, min(n_src,
+ * (i + 1) s)), a tap's weight is its overlap / s computed in double and rounded once to float; h = h + w_x * p over a
+ * source row's taps in order, then v = v + w_y * h over the rows in order, every product and sum rounded on its own.
+ * Fails cleanly on what the warp rejects and on any other option bit, out_width > width or out_height > height (no
+ * upscaling), a destination pointer or stride that is not 4-byte aligned. */
+enum lr_warp_option { LR_WARP_PREPARE = 0x100 }; /* or-ed into `format` */
 
 /* ---- stage API (tests, bench) --------------------------------------------------------- */
 /* Stage 1: fused 5x5 derivative filter + magnitude + direction bin + dilated-bin mask +

@@ -60,6 +60,7 @@ class RectificationConfig(C.Structure):  # reference src/librectify.h:137-150
 BUF_DX, BUF_DY, BUF_DMASK, BUF_LABEL, BUF_SEED_IDX, BUF_SEED_BIN, BUF_SEED_THR, BUF_MAXMAG, BUF_SEED_SIZE = range(9)
 T_UPLOAD, T_FILTER, T_SEEDS, T_FLOOD, T_FIT, T_RANSAC, T_TOTAL, T_FILTER_KERNEL, T_COUNT = range(9)
 PIX_U8, PIX_U8X3, PIX_F32 = range(3)  # enum lr_pixel_format
+WARP_PREPARE = 0x100  # enum lr_warp_option, or-ed into the format of lr_warp_perspective_device
 
 EXPORTS = [
     "find_line_segment_groups", "release_line_segments", "compute_rectification_transform",
@@ -185,6 +186,31 @@ def _ptr(a):
 
 def device_count():
     return lib().lr_device_count()
+
+
+def prepared_size(width, height, max_size):
+    """The reference demo's prescale rule (autorectify.cpp:56-68,121-125; examples/rectify_recipe.cpp) in float32:
+    scale = min(f32(max_size) / f32(max(width, height)), 1), sizes max(1, w * scale rounded half away from zero);
+    max_size < 1 is a fraction of the longer side.  Returns (out_width, out_height, scale as numpy.float32)."""
+    f = np.float32
+    longer = max(int(width), int(height))
+    px = int(f(longer) * f(max_size)) if max_size < 1 else int(f(max_size))
+    scale = min(f(max(1, px)) / f(longer), f(1.0))
+    if scale == f(1.0):
+        return int(width), int(height), scale
+    size = lambda n: max(1, int(np.floor(n * float(scale) + 0.5)))  # noqa: E731
+    return size(int(width)), size(int(height)), scale
+
+
+def _frame_format(a, what):
+    """(format, bytes per pixel) of one 8-bit or f32 frame as the warp and the prepare step take it"""
+    if a.dtype == np.uint8 and a.ndim == 2:
+        return PIX_U8, 1
+    if a.dtype == np.uint8 and a.ndim == 3 and a.shape[2] == 3:
+        return PIX_U8X3, 3
+    if a.dtype == np.float32 and a.ndim == 2:
+        return PIX_F32, 4
+    raise ValueError(what + ": a 2-D uint8 or float32 frame, or an H x W x 3 uint8 frame")
 
 
 class Context:
@@ -342,14 +368,7 @@ class Context:
         """Warps one host frame (2-D uint8 or float32, or H x W x 3 uint8) by M (3x3, destination -> source) into an image
         of out_size = (width, height) on the GPU: upload, one launch, download.  Returns the (height, width[, 3]) array."""
         a = np.ascontiguousarray(array)
-        if a.dtype == np.uint8 and a.ndim == 2:
-            fmt, bpp = PIX_U8, 1
-        elif a.dtype == np.uint8 and a.ndim == 3 and a.shape[2] == 3:
-            fmt, bpp = PIX_U8X3, 3
-        elif a.dtype == np.float32 and a.ndim == 2:
-            fmt, bpp = PIX_F32, 4
-        else:
-            raise ValueError("warp_perspective: a 2-D uint8 or float32 frame, or an H x W x 3 uint8 frame")
+        fmt, bpp = _frame_format(a, "warp_perspective")
         h, w = a.shape[:2]
         ow, oh = int(out_size[0]), int(out_size[1])
         d_src = self.device_upload(a)
@@ -363,14 +382,78 @@ class Context:
             if d_dst.value:
                 self.device_free(d_dst.value)
 
-    def rectify(self, image_u8, min_length=None, refine=False, cfg=None, clip=3.0):
-        """The reference demo's pipeline (autorectify.cpp) without its prescale, on an 8-bit frame (H x W gray or
-        H x W x 3 RGB): luma (4899 R + 9617 G + 1868 B + 8192) >> 14, / 256, find_line_segment_groups with min_length
-        max(w, h) / 100 by default, compute_rectification_transform (cfg: the demo's, horizontal_vp_min_distance = 2),
-        rectification_homography(clip) and the warp of the original frame.  Returns (lines, transform, warped)."""
+    def prepare_device(self, d_src, src_image_bytes, batch, width, height, src_row_bytes, fmt, d_dst, dst_image_bytes,
+                       out_width, out_height, dst_row_bytes):
+        """lr_warp_perspective_device with LR_WARP_PREPARE: `batch` device frames of format fmt (PIX_U8, PIX_U8X3,
+        PIX_F32) become f32 gray frames of out_width x out_height, luma / 256 area-averaged; one launch on the context's
+        stream."""
+        _check(lib().lr_warp_perspective_device(self._h, C.c_void_p(d_src), src_image_bytes, batch, width, height, src_row_bytes, fmt | WARP_PREPARE, None, C.c_void_p(d_dst), dst_image_bytes, out_width, out_height, dst_row_bytes))
+
+    def prepare(self, frames_u8, max_size):
+        """The demo's first step on the GPU: uploads 8-bit frames (H x W, H x W x 3, or either with a leading batch
+        axis), prepares them to prepared_size(W, H, max_size) and downloads the float32 result ((B,) H' x W')."""
+        a = np.ascontiguousarray(frames_u8)
+        if a.dtype != np.uint8 or a.ndim not in (2, 3, 4) or (a.ndim == 4 and a.shape[3] != 3):
+            raise ValueError("prepare: uint8 frames, H x W or H x W x 3, or a batch of either")
+        batched = a.ndim == 4 or (a.ndim == 3 and a.shape[2] != 3)
+        frames = a if batched else a[None]
+        fmt, bpp = _frame_format(frames[0], "prepare")
+        batch, h, w = frames.shape[:3]
+        ow, oh, _ = prepared_size(w, h, max_size)
+        d_src = self.device_upload(frames)
+        d_dst = C.c_void_p()
+        try:
+            _check(lib().lr_device_malloc(self._h, batch * ow * oh * 4, C.byref(d_dst)))
+            self.prepare_device(d_src, h * w * bpp, batch, w, h, w * bpp, fmt, d_dst.value, ow * oh * 4, ow, oh, ow * 4)
+            out = self.device_download(d_dst.value, (batch, oh, ow), np.float32)
+        finally:
+            self.device_free(d_src)
+            if d_dst.value:
+                self.device_free(d_dst.value)
+        return out if batched else out[0]
+
+    def _rectify_prepared(self, img, max_size, min_length, refine, cfg, clip):
+        """rectify with the demo's prescale: the 8-bit frame goes up once; the prepare step, the detector and the warp all
+        read it in HBM"""
+        fmt, bpp = _frame_format(img, "rectify")
+        h, w = img.shape[:2]
+        ow, oh, scale = prepared_size(w, h, max_size)
+        d_src = self.device_upload(img)
+        d_small, d_dst = C.c_void_p(), C.c_void_p()
+        try:
+            _check(lib().lr_device_malloc(self._h, ow * oh * 4, C.byref(d_small)))
+            self.prepare_device(d_src, img.nbytes, 1, w, h, w * bpp, fmt, d_small.value, ow * oh * 4, ow, oh, ow * 4)
+            if min_length is None:
+                min_length = max(ow, oh) / 100.0
+            lines = self.find_line_segment_groups_device(d_small.value, ow, oh, min_length, refine=refine).copy()
+            for k in ("x1", "y1", "x2", "y2"):  # back to the coordinates of the full frame, in float32 as the demo
+                lines[k] = lines[k] / scale
+            t = compute_rectification_transform(lines, w, h, cfg)
+            _, M, (rw, rh) = rectification_homography(t, clip)
+            _check(lib().lr_device_malloc(self._h, rw * rh * bpp, C.byref(d_dst)))
+            self.warp_perspective_device(d_src, img.nbytes, 1, w, h, w * bpp, fmt, M, d_dst.value, rw * rh * bpp, rw, rh, rw * bpp)
+            return lines, t, self.device_download(d_dst.value, (rh, rw) + img.shape[2:], np.uint8)
+        finally:
+            self.device_free(d_src)
+            for p in (d_small, d_dst):
+                if p.value:
+                    self.device_free(p.value)
+
+    def rectify(self, image_u8, min_length=None, refine=False, cfg=None, clip=3.0, max_size=None):
+        """The reference demo's pipeline (autorectify.cpp) on an 8-bit frame (H x W gray or H x W x 3 RGB): luma
+        (4899 R + 9617 G + 1868 B + 8192) >> 14, / 256, find_line_segment_groups with min_length max(w, h) / 100 by
+        default, compute_rectification_transform (cfg: the demo's, horizontal_vp_min_distance = 2),
+        rectification_homography(clip) and the warp of the original frame.  Returns (lines, transform, warped).
+        max_size=None: without the demo's prescale, luma on the host and the float frame uploaded.  max_size=N (the
+        demo's default is 1200; below 1 a fraction of the longer side): with it -- the 8-bit frame is uploaded once,
+        prepared on the device (prepare_device) to prepared_size(w, h, max_size), the detector runs on that with
+        min_length max(w', h') / 100, the endpoints are divided by the scale, the transform is the full frame's and the
+        warp reads the same resident frame."""
         img = np.ascontiguousarray(image_u8)
         if img.dtype != np.uint8 or not (img.ndim == 2 or (img.ndim == 3 and img.shape[2] == 3)):
             raise ValueError("rectify: an H x W or H x W x 3 uint8 frame")
+        if max_size is not None:
+            return self._rectify_prepared(img, max_size, min_length, refine, cfg or RectificationConfig(hmin=2.0), clip)
         if img.ndim == 3:
             c = img.astype(np.int32)
             gray = (4899 * c[..., 0] + 9617 * c[..., 1] + 1868 * c[..., 2] + 8192) >> 14

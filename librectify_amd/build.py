@@ -18,6 +18,7 @@ SOURCES = [
     "kernels_ransac.hip",
     "kernels_groups.hip",
     "kernels_warp.hip",
+    "kernels_prepare.hip",
     "context.hip",
     "vp_host.cpp",
     "api.cpp",

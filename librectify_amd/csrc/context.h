@@ -117,6 +117,14 @@ struct lr_context {
     double* h_warp_m = nullptr;
     size_t cap_warp_m = 0;             // frames the two hold
     hipEvent_t ev_warp_m = nullptr;    // the last upload from h_warp_m (rewritten only once that has been read)
+    // ... with LR_WARP_PREPARE (kernels_prepare.hip): the span table of the last (source size, output size), made on the
+    // host in page-locked memory and kept on the device while the sizes repeat
+    void* d_prep_spans = nullptr;
+    void* h_prep_spans = nullptr;
+    size_t cap_prep_spans = 0;         // entries (output width + output height) the two hold
+    int prep_key[4] = {0, 0, 0, 0};    // width, output width, height, output height of the table ([0] = 0: none)
+    float prep_w_in[2] = {0.f, 0.f};   // (float)(1 / scale) of the table's two axes
+    hipEvent_t ev_prep_spans = nullptr;  // the last upload from h_prep_spans
     // RANSAC
     size_t cap_lines = 0;
     float* d_model = nullptr;  // 8 arrays of cap_lines
@@ -255,4 +263,16 @@ int ctx_upload_frame(lr_context* c, int slot, const float* buffer, int w, int h,
 int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_bytes, int batch, int width, int height,
                          size_t src_row_bytes, int format, const double* M, void* d_dst, size_t dst_image_bytes,
                          int out_width, int out_height, size_t dst_row_bytes);
+// kernels_prepare.hip: the same entry with LR_WARP_PREPARE in `format` (the low byte arrives here): luma / 256, area-averaged
+// to the output size as f32 gray
+int ctx_prepare_frames(lr_context* c, const void* d_src, size_t src_image_bytes, int batch, int width, int height,
+                       size_t src_row_bytes, int format, void* d_dst, size_t dst_image_bytes, int out_width,
+                       int out_height, size_t dst_row_bytes);
+// bytes one frame spans: (rows - 1) * row_bytes + last_row_bytes; false if that does not fit in 64 bits
+inline bool frame_span(int rows, size_t row_bytes, size_t last_row_bytes, size_t* out) {
+    size_t s;
+    if (__builtin_mul_overflow((size_t)(rows - 1), row_bytes, &s) || __builtin_add_overflow(s, last_row_bytes, &s)) return false;
+    *out = s;
+    return true;
+}
 }  // namespace lramd

@@ -164,6 +164,13 @@ int ctx_trim(lr_context* c, bool frames_too) {
         }
         c->ring_stage_cap_pix = 0;
     }
+    if (frames_too) {  // the prepare step's span table (sized by a frame's width + height)
+        drop(c->d_prep_spans);
+        if (c->h_prep_spans) (void)hipHostFree(c->h_prep_spans);
+        c->h_prep_spans = nullptr;
+        c->cap_prep_spans = 0;
+        c->prep_key[0] = 0;
+    }
     c->small_frames = 0;
     c->w = c->h = 0;
     c->seed_cap = 0;
@@ -742,7 +749,7 @@ void ctx_destroy(lr_context* c) {
                     c->fb.blocked, c->fb.count, c->fb.flags, c->fb.state, c->fb.tier, c->fb.blk, c->fb.act_a, c->fb.act_b,
                     c->fb.ctrl, c->fb.big_list, c->fb.handover, c->fb.rewalk_list, c->fb.log_off, c->fb.log_len, c->fb.log_buf, c->fb.dirty, c->fb.giant_mask, c->fb.slab_ring, c->fb.slab_hash, c->d_pairs, c->d_peak, c->d_weights,
                     c->d_samples, c->d_hcounts, c->comp_large, c->huge.tab, c->huge.jobs, c->huge.list, c->d_tables, c->d_orig, c->d_inl, c->d_flines, c->d_gctl,
-                    c->d_gnorm, c->d_models, c->d_refine_table, c->d_refine_edges, c->d_cht_acc, c->d_cht_idx, c->d_cht_peak, c->d_rec, c->d_recflags, c->d_warp_m};
+                    c->d_gnorm, c->d_models, c->d_refine_table, c->d_refine_edges, c->d_cht_acc, c->d_cht_idx, c->d_cht_peak, c->d_rec, c->d_recflags, c->d_warp_m, c->d_prep_spans};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     delete static_cast<StagingCrew*>(c->crew);
@@ -778,6 +785,8 @@ void ctx_destroy(lr_context* c) {
     if (c->h_cht_peak) (void)hipHostFree(c->h_cht_peak);
     if (c->h_warp_m) (void)hipHostFree(c->h_warp_m);
     if (c->ev_warp_m) (void)hipEventDestroy(c->ev_warp_m);
+    if (c->h_prep_spans) (void)hipHostFree(c->h_prep_spans);
+    if (c->ev_prep_spans) (void)hipEventDestroy(c->ev_prep_spans);
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
     (void)hipStreamDestroy(c->stream);

@@ -200,14 +200,6 @@ __global__ __launch_bounds__(kBlock) void warp_perspective_kernel(WarpArgs g) {
     }
 }
 
-// bytes one frame spans: (rows - 1) * row_bytes + last_row_bytes; false if that does not fit in 64 bits
-bool frame_span(int rows, size_t row_bytes, size_t last_row_bytes, size_t* out) {
-    size_t s;
-    if (__builtin_mul_overflow((size_t)(rows - 1), row_bytes, &s) || __builtin_add_overflow(s, last_row_bytes, &s)) return false;
-    *out = s;
-    return true;
-}
-
 }  // namespace
 
 int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_bytes, int batch, int width, int height,
@@ -218,6 +210,11 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
         return 1;
     };
     if (!c) return fail("no context");
+    if (format & ~0xFF) {  // option bits above the pixel format
+        if ((format & ~0xFF) != LR_WARP_PREPARE) return fail("unknown option bits in format");
+        return ctx_prepare_frames(c, d_src, src_image_bytes, batch, width, height, src_row_bytes, format & 0xFF, d_dst,
+                                  dst_image_bytes, out_width, out_height, dst_row_bytes);
+    }
     if (!d_src || !d_dst || !M) return fail("null pointer (source, destination or M)");
     if (batch < 1) return fail("batch < 1");
     if (width < 1 || height < 1 || out_width < 1 || out_height < 1) return fail("source or output size below 1");
