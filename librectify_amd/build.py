@@ -20,6 +20,10 @@ SOURCES = [
     "kernels_warp.hip",
     "kernels_prepare.hip",
     "context.hip",
+    "upload.hip",
+    "frame.hip",
+    "estimators.hip",
+    "batch.hip",
     "vp_host.cpp",
     "api.cpp",
 ]

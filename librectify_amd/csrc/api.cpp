@@ -187,11 +187,11 @@ int lr_synchronize(lr_context* ctx) {
         return guard_fail("lr_synchronize");
     }
 }
-void lr_set_ransac_seed(lr_context* ctx, uint64_t seed) { ctx->ransac_seed = seed; }
-void lr_set_stage_timing(lr_context* ctx, int on) { ctx->timing_on = on != 0; }
-void lr_set_ransac_iterations(lr_context* ctx, int n_iter) { ctx->ransac_iters = n_iter; }
+void lr_set_ransac_seed(lr_context* ctx, uint64_t seed) { ctx->opt.ransac_seed = seed; }
+void lr_set_stage_timing(lr_context* ctx, int on) { ctx->opt.timing_on = on != 0; }
+void lr_set_ransac_iterations(lr_context* ctx, int n_iter) { ctx->opt.ransac_iters = n_iter; }
 void lr_set_flood_mode(lr_context* ctx, int mode) {
-    ctx->flood_mode = mode;
+    ctx->opt.flood_mode = mode;
     ctx->flood_big_hint = true;  // forget what the previous frame needed
     ctx->flood_hold_hint = false;
     ctx->flood_staged_hint = false;
@@ -369,16 +369,16 @@ int lr_warp_perspective_device(lr_context* ctx, const void* d_src, size_t src_im
     }
 }
 
-void lr_set_batch_streams(lr_context* ctx, int n) { ctx->batch_streams = n < 1 ? 1 : n; }
+void lr_set_batch_streams(lr_context* ctx, int n) { ctx->opt.batch_streams = n < 1 ? 1 : n; }
 void lr_set_seed_capacity(lr_context* ctx, uint32_t cap) { ctx->seed_cap_once = cap; }
-void lr_set_flood_staged(lr_context* ctx, int on) { ctx->flood_staged = on != 0; }
+void lr_set_flood_staged(lr_context* ctx, int on) { ctx->opt.flood_staged = on != 0; }
 void lr_set_flood_blind_rounds(lr_context* ctx, int rounds) { ctx->flood_rounds_hint = rounds; }
-void lr_set_flood_partial_commits(lr_context* ctx, int on) { ctx->flood_partial = on != 0; }
-void lr_set_flood_just_in_time(lr_context* ctx, int on) { ctx->flood_jit = on != 0; }
-void lr_set_flood_giant_step(lr_context* ctx, int on) { ctx->flood_giant_step = on != 0; }
+void lr_set_flood_partial_commits(lr_context* ctx, int on) { ctx->opt.flood_partial = on != 0; }
+void lr_set_flood_just_in_time(lr_context* ctx, int on) { ctx->opt.flood_jit = on != 0; }
+void lr_set_flood_giant_step(lr_context* ctx, int on) { ctx->opt.flood_giant_step = on != 0; }
 void lr_set_flood_logs(lr_context* ctx, int on) {
-    ctx->flood_logs = on != 0;
-    ctx->flood_log_sweep = on == 2;
+    ctx->opt.flood_logs = on != 0;
+    ctx->opt.flood_log_sweep = on == 2;
 }
 
 int lr_stage_filter(lr_context* ctx, const float* d_image, int width, int height, int stride) {
@@ -395,7 +395,7 @@ int lr_stage_filter_host(lr_context* ctx, const float* buffer, int width, int he
             return 1;
         }
         if (upload_host_image(ctx, buffer, width, height, stride, -1)) return 1;
-        return ctx_stage_filter(ctx, ctx->d_img_slot[0], width, height, width);
+        return ctx_stage_filter(ctx, ctx->frames.slot[0], width, height, width);
     } catch (...) {
         return guard_fail("lr_stage_filter_host");
     }
@@ -435,15 +435,15 @@ int lr_download(lr_context* ctx, int buffer_id, void* dst, size_t bytes) {
         const void* src = nullptr;
         size_t have = 0;
         switch (buffer_id) {
-            case LR_BUF_DX: src = ctx->dx; have = npix * 4; break;
-            case LR_BUF_DY: src = ctx->dy; have = npix * 4; break;
-            case LR_BUF_DMASK: src = ctx->dmask; have = npix; break;
-            case LR_BUF_LABEL: src = ctx->label; have = npix * 4; break;
-            case LR_BUF_SEED_IDX: src = ctx->seed_idx; have = (size_t)ctx->n_seeds * 4; break;
-            case LR_BUF_SEED_BIN: src = ctx->seed_bin; have = (size_t)ctx->n_seeds * 4; break;
-            case LR_BUF_SEED_THR: src = ctx->seed_thr; have = (size_t)ctx->n_seeds * 4; break;
+            case LR_BUF_DX: src = ctx->ws.dx; have = npix * 4; break;
+            case LR_BUF_DY: src = ctx->ws.dy; have = npix * 4; break;
+            case LR_BUF_DMASK: src = ctx->ws.dmask; have = npix; break;
+            case LR_BUF_LABEL: src = ctx->ws.label; have = npix * 4; break;
+            case LR_BUF_SEED_IDX: src = ctx->ws.seed_idx; have = (size_t)ctx->n_seeds * 4; break;
+            case LR_BUF_SEED_BIN: src = ctx->ws.seed_bin; have = (size_t)ctx->n_seeds * 4; break;
+            case LR_BUF_SEED_THR: src = ctx->ws.seed_thr; have = (size_t)ctx->n_seeds * 4; break;
             case LR_BUF_MAXMAG: src = ctx->maxmag; have = 4; break;
-            case LR_BUF_SEED_SIZE: src = ctx->seed_size; have = (size_t)ctx->n_seeds * 4; break;
+            case LR_BUF_SEED_SIZE: src = ctx->ws.seed_size; have = (size_t)ctx->n_seeds * 4; break;
             default: set_error("lr_download: unknown buffer id"); return 1;
         }
         if (buffer_id == LR_BUF_DMASK && ctx->dmask_consumed) {
@@ -556,9 +556,9 @@ int lr_refine_lines(lr_context* ctx, const LineSegment* in, int n, LineSegment* 
 }
 
 void lr_set_estimator(lr_context* ctx, int kind, int param) {
-    ctx->estimator = kind;
-    if (kind == 3) ctx->cht_d = param > 0 ? param : 128;
-    else ctx->prosac_T_N = param;
+    ctx->opt.estimator = kind;
+    if (kind == 3) ctx->opt.cht_d = param > 0 ? param : 128;
+    else ctx->opt.prosac_T_N = param;
 }
 
 int lr_estimate_line_pencils_cht(lr_context* ctx, LineSegment* lines, int n, int max_models, float inlier_deg,

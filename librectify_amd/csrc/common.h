@@ -162,7 +162,7 @@ struct FloodBuffers {
     bool partial_commits = true;
     bool second_tier = true;  // test hook: without it every walk that outgrows the first tier goes to a slab
     // Whether a flood starts with the second tier or only turns it on once a walk has had to go to a slab.  Since round 3
-    // the context always asks for it from the start (context.hip, finish_flood: a frame of regions after a frame of lines
+    // the context always asks for it from the start (frame.hip, finish_flood: a frame of regions after a frame of lines
     // otherwise runs its long walks in slabs, 6.4 instead of 1.7 ms of flood at 4K; an empty launch costs a round 5 us).
     bool second_tier_from_start = true;
     // Likewise the hold-back: if the context's previous frame engaged it, this frame starts with it (a round of very

@@ -2,162 +2,186 @@
 #pragma once
 #include <atomic>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <vector>
 
+#include "buffers.h"
 #include "common.h"
 #include "vp_host.h"
 
-struct lr_context {
-    int device = 0;
-    hipStream_t stream = nullptr;
+namespace lramd {
+struct StagingCrew;  // host.h
 
-    // geometry of the workspace / last frame
+// What a caller sets through lr_set_* (and the environment at creation): copied as a whole to the lanes of a batch call
+// and to the peers of a multi-device call.
+struct Settings {
+    uint64_t ransac_seed = 0;
+    int ransac_iters = kRansacMaxIter;
+    int estimator = 0;            // 0 = RANSAC (reference default), 1 = PROSAC, 2 = DirectEstimator, 3 = diamond space (CHT)
+    int prosac_T_N = -1;
+    int cht_d = 128;              // accumulator size of estimator 3
+    int batch_streams = 5;
+    int flood_mode = 1;
+    bool flood_giant_step = true;  // the lowest active seed's flood by the whole device when it outgrows the LDS tiers (kernels_flood.hip: kCtrlGiantStep); lr_set_flood_giant_step, LIBRECTIFY_FLOOD_GIANT_STEP=0
+    bool flood_jit = true;       // single calls enqueue the flood's later rounds just in time (kernels_flood.hip: flood_enqueue); LIBRECTIFY_FLOOD_JIT=0
+    bool flood_partial = true;  // partial commits of blocked seeds (kernels_flood.hip); lr_set_flood_partial_commits
+    bool flood_log_sweep = false;  // test hook (lr_set_flood_logs(ctx, 2)): every footprint worked out from a log goes the fall-back way (sweeps)
+    bool flood_logs = true;     // blocked seeds work their next footprint out from the records of their last walk (kernels_flood.hip: flood_rewalk_kernel); lr_set_flood_logs, LIBRECTIFY_FLOOD_LOGS=0
+    bool flood_staged = false;  // lr_set_flood_staged: the rounds start on the strongest eighth of the seeds (test / experiment hook)
+    // Stage timers (HIP events between the stages of a frame): off in the frame calls unless lr_set_stage_timing or
+    // LIBRECTIFY_STAGE_TIMES asks -- every event record is a barrier packet in the stream, some 6 us of idle GPU each,
+    // seven of them per frame.  The staged API (lr_stage_*) always times its stages.
+    bool timing_on = false;
+};
+
+// The groups below are what lr_context_trim gives back: each is reset as a whole (ctx_trim).
+
+// per-pixel workspace, sized by the largest frame seen (ctx_ensure_image_capacity)
+struct Workspace {
     size_t cap_pix = 0;
     int cap_tiles = 0;
-    int w = 0, h = 0;
+    // stage 1
+    DeviceBuffer<float> dx, dy;
+    DeviceBuffer<uint8_t> dmask;
+    DeviceBuffer<uint64_t> cand;
+    DeviceBuffer<uint32_t> cand_count, tile_max;
+    // stage 2
+    DeviceBuffer<uint32_t> tile_pass;
+    DeviceBuffer<uint32_t> tile_off;  // (the fused seed selection keeps its workgroups' status words here: zeroed when allocated)
+    DeviceBuffer<uint64_t> keys_a, keys_b;
+    DeviceBuffer<int32_t> seed_idx, seed_bin;
+    DeviceBuffer<float> seed_thr;
+    DeviceBuffer<int32_t> seed_size;
+    // stage 3
+    DeviceBuffer<uint32_t> label;
+    DeviceBuffer<int32_t> queue;
+    // stage 4
+    DeviceBuffer<uint32_t> comp_rank, comp_seed, comp_off, cursor, px_a, px_b;
+    DeviceBuffer<float> scratch_w;
+    DeviceBuffer<LineSegment> d_lines;
+    DeviceBuffer<unsigned char> temp;     // (cap() = its bytes)
+    DeviceBuffer<uint32_t> comp_large;    // components of more than 64 pixels (sorted by a workgroup each)
+    DeviceBuffer<uint32_t> huge_tab, huge_list, huge_jobs;
+    HugeSort huge;                        // ... of more than 2^14: buckets (kernels_fit.hip: huge_count_kernel), pointing into the three above
+};
 
-    // Host-buffer entry points (the reference's only kind, image.cpp:11-19): frames go through one of two device
-    // slots on a copy stream of their own, so the upload of a lane's next frame overlaps the kernels of its current
-    // one.  Pageable sources are first copied (in row bands, by `upload_threads` host threads) into a pinned staging
-    // buffer per slot; sources that are already page-locked (lr_host_alloc, hipHostMalloc, hipHostRegister) are
-    // DMA-copied where they lie.
-    hipStream_t copy_stream = nullptr;
-    float* d_img_slot[2] = {nullptr, nullptr};
-    size_t cap_slot[2] = {0, 0};
+// the parallel flood's per-seed buffers, logs and slabs; `fb` is what the kernels get (by value), pointing into the owners
+struct FloodStore {
+    DeviceBuffer<uint32_t> blocked, count, flags, blk, act_a, act_b, ctrl, big_list, handover, rewalk_list, log_off, log_len, log_buf;
+    DeviceBuffer<uint8_t> state, tier, dirty;
+    DeviceBuffer<uint64_t> giant_mask;
+    DeviceBuffer<uint4> slab_ring, slab_hash;
+    FloodBuffers fb;
+    size_t cap_seeds = 0;
+};
+
+// Host-buffer entry points (the reference's only kind, image.cpp:11-19): frames go through one of two device
+// slots on a copy stream of their own, so the upload of a lane's next frame overlaps the kernels of its current
+// one.  Pageable sources are first copied (in row bands, by `upload_threads` host threads) into a pinned staging
+// buffer per slot; sources that are already page-locked (lr_host_alloc, hipHostMalloc, hipHostRegister) are
+// DMA-copied where they lie.
+struct FrameSlots {
+    DeviceBuffer<float> slot[2];
+    PinnedBuffer<float> stage[2];
     // Device frames whose rows span 4 GiB or more (the filter kernel addresses a frame with 32-bit byte offsets) are
     // first copied here, packed, on the context's stream (enqueue_filter).
-    float* d_img_packed = nullptr;
-    size_t cap_packed = 0;
-    float* h_stage[2] = {nullptr, nullptr};
-    size_t cap_stage[2] = {0, 0};
-    hipEvent_t ev_up[2] = {};
-    hipEvent_t ev_wait = nullptr;  // (blocking-sync flag) what a batch lane sleeps on
-    std::vector<hipEvent_t> band_ev;  // single host frames: one event per 4 MB upload band (the filter follows the bands)
-    void* crew = nullptr;             // StagingCrew of single host frames: threads kept from call to call
+    DeviceBuffer<float> packed;
+};
+
+// Batch calls on host frames: a ring of device frames (and, for pageable frames, of page-locked staging buffers)
+// that ONE uploader fills in frame order on the copy stream, as far ahead of the lanes as the ring allows
+// (find_groups_batch).
+struct UploadRing {
+    std::vector<DeviceBuffer<float>> img;
+    std::vector<PinnedBuffer<float>> stage;
+    size_t cap_pix = 0, stage_cap_pix = 0;
+    void drop() {  // the memory goes, the ring keeps its length
+        for (auto& b : img) b.reset();
+        for (auto& b : stage) b.reset();
+        cap_pix = stage_cap_pix = 0;
+    }
+};
+
+// LR_WARP_PREPARE (kernels_prepare.hip): the span table of the last (source size, output size), made on the
+// host in page-locked memory and kept on the device while the sizes repeat
+struct PrepareSpans {
+    MirroredBuffer<unsigned char> spans;  // (cap() = bytes: output width + output height entries)
+    int key[4] = {0, 0, 0, 0};            // width, output width, height, output height of the table ([0] = 0: none)
+    float w_in[2] = {0.f, 0.f};           // (float)(1 / scale) of the table's two axes
+};
+}  // namespace lramd
+
+struct lr_context {
+    lr_context();
+    ~lr_context();
+    int device = 0;
+    lramd::Stream stream, copy_stream;  // (first: everything below is gone before they are)
+    lramd::Settings opt;
+
+    int w = 0, h = 0;  // the last frame
+    lramd::Workspace ws;
+    lramd::FloodStore flood;
+    lramd::FrameSlots frames;
+    lramd::UploadRing ring;
+    lramd::PrepareSpans prep;
+    lramd::Event ev_prep_spans;  // the last upload from prep.spans.h
+
+    lramd::Event ev_up[2];
+    lramd::Event ev_wait;  // (blocking-sync flag) what a batch lane sleeps on
+    std::vector<lramd::Event> band_ev;  // single host frames: one event per 4 MB upload band (the filter follows the bands)
+    std::vector<lramd::Event> ring_ev;
+    std::unique_ptr<lramd::StagingCrew> crew;  // single host frames: threads kept from call to call
     int crew_helpers = 0;
     bool sleep_in_wait = false;
-    // Batch calls on host frames: a ring of device frames (and, for pageable frames, of page-locked staging buffers)
-    // that ONE uploader fills in frame order on the copy stream, as far ahead of the lanes as the ring allows
-    // (find_groups_batch).
-    std::vector<float*> ring_img;
-    std::vector<float*> ring_stage;
-    std::vector<hipEvent_t> ring_ev;
-    size_t ring_cap_pix = 0, ring_stage_cap_pix = 0;
-    // stage 1
-    float* dx = nullptr;
-    float* dy = nullptr;
-    uint8_t* dmask = nullptr;
-    uint64_t* cand = nullptr;
-    uint32_t* cand_count = nullptr;
-    uint32_t* tile_max = nullptr;
-    // stage 2
-    uint32_t* tile_pass = nullptr;
-    uint32_t* tile_off = nullptr;      // (the fused seed selection keeps its workgroups' status words here: zeroed when allocated)
-    uint32_t fit_tag = 0;              // ... and of the last component scan (kernels_fit.hip: component_offsets_kernel)
-    int register_slow_calls = 0;       // batch calls still to go with the staging copy after pinning frames in place turned out slow (context.hip: find_groups_batch)
+    uint32_t fit_tag = 0;              // tag of the last component scan (kernels_fit.hip: component_offsets_kernel)
+    int register_slow_calls = 0;       // batch calls still to go with the staging copy after pinning frames in place turned out slow (batch.hip: find_groups_batch)
     uint32_t select_tag = 0;           // tag of the last seed selection on this context (kernels_seeds.hip: seed_select_kernel)
-    float* maxmag = nullptr;
-    uint64_t* keys_a = nullptr;
-    uint64_t* keys_b = nullptr;
-    uint32_t* d_counts = nullptr;  // [0] n_seeds, [1] n_comp, [2] n_px, [3..] flood scratch
-    int32_t* seed_idx = nullptr;
-    int32_t* seed_bin = nullptr;
-    float* seed_thr = nullptr;
-    int32_t* seed_size = nullptr;
-    // stage 3
-    uint32_t* label = nullptr;
-    int32_t* queue = nullptr;
-    lramd::FloodBuffers fb;
-    size_t fb_cap_seeds = 0;
-    // stage 4
-    uint32_t* comp_rank = nullptr;
-    uint32_t* comp_seed = nullptr;
-    uint32_t* comp_off = nullptr;
-    uint32_t* cursor = nullptr;
-    uint32_t* px_a = nullptr;
-    uint32_t* px_b = nullptr;
-    float* scratch_w = nullptr;
-    LineSegment* d_lines = nullptr;
-    void* temp = nullptr;
-    size_t temp_bytes = 0;
-    uint32_t* comp_large = nullptr;  // components of more than 64 pixels (sorted by a workgroup each)
-    lramd::HugeSort huge;                   // ... of more than 2^14: buckets (kernels_fit.hip: huge_count_kernel)
+    lramd::DeviceBuffer<float> maxmag;
+    lramd::DeviceBuffer<uint32_t> d_counts;  // [0] n_seeds, [1] n_comp, [2] n_px, [3..] flood scratch
     uint32_t seed_cap = 0;           // capacity the seed sort runs with (the seed count is not known when it is enqueued)
     uint32_t seed_cap_once = 0;      // test hook: capacity of the next frame's seed sort
     int frame_laps = 0;              // laps the last frame took (1; 2 if the seed sort overflowed or the flood needed more rounds)
     lramd::FloodProgress flood_prog;
     int small_frames = 0;  // frames in a row of at most a quarter of the workspace's capacity (ctx_ensure_image_capacity gives it back after eight)
     // filter_lines + peeling on the device (kernels_groups.hip)
-    size_t cap_glines = 0, cap_flines = 0;
-    float* d_tables = nullptr;      // 3 pencil tables (all lines, two ping-pong round tables) x 8 arrays x cap_glines
-    uint32_t* d_orig = nullptr;     // 3 x cap_glines
-    float* d_inl = nullptr;         // 4 x cap_glines: (h, length) of a round's inliers beyond those staged in LDS
-    LineSegment* d_flines = nullptr;  // filtered (then grouped) lines
-    uint32_t* d_gctl = nullptr;     // peeling control block (kGc*)
-    float* d_gnorm = nullptr;       // bounding-box centre and scale
-    float* d_models = nullptr;      // refit model of each round
-    uint8_t* h_res = nullptr;       // pinned: header (counts, control block, models) + the first res_lines_cap lines
+    size_t cap_glines = 0;
+    lramd::DeviceBuffer<float> d_tables;      // 3 pencil tables (all lines, two ping-pong round tables) x 8 arrays x cap_glines
+    lramd::DeviceBuffer<uint32_t> d_orig;     // 3 x cap_glines
+    lramd::DeviceBuffer<float> d_inl;         // 4 x cap_glines: (h, length) of a round's inliers beyond those staged in LDS
+    lramd::DeviceBuffer<LineSegment> d_flines;  // filtered (then grouped) lines
+    lramd::DeviceBuffer<uint32_t> d_gctl;     // peeling control block (kGc*)
+    lramd::DeviceBuffer<float> d_gnorm;       // bounding-box centre and scale
+    lramd::DeviceBuffer<float> d_models;      // refit model of each round
+    lramd::PinnedBuffer<uint8_t> h_res;       // header (counts, control block, models) + the first res_lines_cap lines
     size_t res_lines_cap = 0;
     // grow-on-demand workspaces of the opt-in paths
-    float* d_refine_table = nullptr;
-    size_t cap_refine_table = 0;
-    void* d_refine_edges = nullptr;
-    size_t cap_refine_edges = 0;
-    unsigned long long* d_cht_acc = nullptr;
-    size_t cap_cht = 0;
-    uint32_t* d_cht_idx = nullptr;   // lines a peeling round of the diamond-space estimator takes out of the accumulator
-    uint32_t* h_cht_idx = nullptr;   // pinned mirror
-    size_t cap_cht_idx = 0;
-    uint32_t* d_cht_peak = nullptr;  // {cell, value lo, value hi, -, votes lo, votes hi}
-    uint32_t* h_cht_peak = nullptr;  // pinned mirror
-    int cht_d = 128;                 // accumulator size of estimator 3
+    lramd::DeviceBuffer<float> d_refine_table;
+    lramd::DeviceBuffer<uint2> d_refine_edges;
+    lramd::DeviceBuffer<unsigned long long> d_cht_acc;
+    lramd::MirroredBuffer<uint32_t> cht_idx;   // lines a peeling round of the diamond-space estimator takes out of the accumulator
+    lramd::MirroredBuffer<uint32_t> cht_peak;  // {cell, value lo, value hi, -, votes lo, votes hi}
     // lr_warp_perspective_device: the frames' maps (9 doubles each) go up from page-locked memory on the context's stream
-    double* d_warp_m = nullptr;
-    double* h_warp_m = nullptr;
-    size_t cap_warp_m = 0;             // frames the two hold
-    hipEvent_t ev_warp_m = nullptr;    // the last upload from h_warp_m (rewritten only once that has been read)
-    // ... with LR_WARP_PREPARE (kernels_prepare.hip): the span table of the last (source size, output size), made on the
-    // host in page-locked memory and kept on the device while the sizes repeat
-    void* d_prep_spans = nullptr;
-    void* h_prep_spans = nullptr;
-    size_t cap_prep_spans = 0;         // entries (output width + output height) the two hold
-    int prep_key[4] = {0, 0, 0, 0};    // width, output width, height, output height of the table ([0] = 0: none)
-    float prep_w_in[2] = {0.f, 0.f};   // (float)(1 / scale) of the table's two axes
-    hipEvent_t ev_prep_spans = nullptr;  // the last upload from h_prep_spans
+    lramd::MirroredBuffer<double> warp_m;
+    lramd::Event ev_warp_m;    // the last upload from warp_m.h (rewritten only once that has been read)
     // RANSAC
-    size_t cap_lines = 0;
-    float* d_model = nullptr;  // 8 arrays of cap_lines
-    float* h_model = nullptr;  // pinned mirror
-    size_t cap_iter = 0;
-    unsigned long long* d_best_slots = nullptr;  // kRansacBestSlots words: a scoring launch's best (score, iteration), cleared by its reader
+    lramd::MirroredBuffer<float> model;  // 8 arrays of lines
+    lramd::DeviceBuffer<unsigned long long> d_best_slots;  // kRansacBestSlots words: a scoring launch's best (score, iteration), cleared by its reader
     // PROSAC / Hough weights (opt-in estimator)
-    int32_t* d_pairs = nullptr;   // 2 x ht_pairs
-    int32_t* h_pairs = nullptr;
-    size_t cap_pairs = 0;
-    float* d_peak = nullptr;      // 3 floats
-    float* d_weights = nullptr;   // cap_lines
-    float* h_weights = nullptr;
-    uint32_t* d_samples = nullptr;  // 2 buffers x 2 x cap_chunk
-    uint32_t* h_samples = nullptr;
-    uint32_t* d_hcounts = nullptr;  // 2 x cap_chunk
-    uint32_t* h_hcounts = nullptr;
-    size_t cap_chunk = 0, cap_wlines = 0;
-    uint32_t* d_rec = nullptr;       // PROSAC: new-best iterations of a chunk ([0] = how many) ...
-    uint32_t* h_rec = nullptr;
-    uint8_t* d_recflags = nullptr;   // ... and a row of inlier flags for each
-    uint8_t* h_recflags = nullptr;
-    size_t cap_recflags = 0;         // (per chunk buffer; there are two of each)
-    hipEvent_t prosac_ev[2] = {nullptr, nullptr};  // end of a chunk's work on the stream
+    lramd::MirroredBuffer<int32_t> pairs;   // 2 x ht_pairs
+    lramd::DeviceBuffer<float> d_peak;      // 3 floats
+    lramd::MirroredBuffer<float> weights;   // one per line
+    lramd::MirroredBuffer<uint32_t> samples;  // 2 buffers x 2 x chunk
+    lramd::MirroredBuffer<uint32_t> hcounts;  // 2 x chunk
+    lramd::MirroredBuffer<uint32_t> rec;      // PROSAC: new-best iterations of a chunk ([0] = how many) ...
+    lramd::MirroredBuffer<uint8_t> recflags;  // ... and a row of inlier flags for each (two chunk buffers of each)
+    lramd::Event prosac_ev[2];  // end of a chunk's work on the stream
     std::vector<int> prosac_imin;    // prosac.h's Imin(2, n) by n (constants of prosac.h:62-66 only)
     std::vector<lr_context*> workers;  // extra contexts (own stream + workspace) for frames in flight in batch calls
     std::vector<lr_context*> peers;    // one context per entry of the device list of the last multi-device batch call (each with its own lanes)
-    int batch_streams = 5;
-    int estimator = 0;            // 0 = RANSAC (reference default), 1 = PROSAC, 2 = DirectEstimator, 3 = diamond space (CHT)
-    int prosac_T_N = -1;
     // pinned host scalars
-    uint32_t* h_counts = nullptr;  // 8 words of counts; + 16: the flood's control block; + 72: the words the flood's rounds report in
-    float* h_best = nullptr;       // [0] score, [1] iter (as int bits)
+    lramd::PinnedBuffer<uint32_t> h_counts;  // 8 words of counts; + 16: the flood's control block; + 72: the words the flood's rounds report in
+    lramd::PinnedBuffer<float> h_best;       // [0] score, [1] iter (as int bits)
 
     // constants
     lramd::FilterConsts fconsts;
@@ -169,13 +193,10 @@ struct lr_context {
     int flood_rounds = 0;
     int flood_rounds_hint = 10;  // rounds the next flood enqueues blindly
     int flood_rounds_last = 0;   // rounds the last flood needed (0: none yet)
-    int flood_jit_sleep_us = 0;  // (lanes of a batch call, when they enqueue just in time at all: pause between looks)
-    bool flood_giant_step = true;  // the lowest active seed's flood by the whole device when it outgrows the LDS tiers (kernels_flood.hip: kCtrlGiantStep); lr_set_flood_giant_step, LIBRECTIFY_FLOOD_GIANT_STEP=0
-    bool flood_jit = true;       // single calls enqueue the flood's later rounds just in time (kernels_flood.hip: flood_enqueue); LIBRECTIFY_FLOOD_JIT=0
-    uint64_t ransac_seed = 0;
-    int ransac_iters = lramd::kRansacMaxIter;
-    int flood_mode = 1;
-    bool flood_logbig_off = false;  // lanes of a batch call keep no logs of second-tier walks (context.hip: find_groups_batch)
+    // what find_groups_batch gives its lanes for the length of a call (0 / false otherwise)
+    int flood_jit_sleep_us = 0;  // (when they enqueue just in time at all: pause between looks)
+    bool flood_logbig_off = false;  // no logs of second-tier walks
+    int flood_log_min = 0, flood_log_walk = 0;  // thresholds of the logs (0: the defaults; the lanes get 32 and 24)
     bool flood_logbig_hint = true;  // did the last frame have walks in the second tier? (their logs need a launch of their own per round: kernels_flood.hip, flood_rewalk_kernel)
     bool flood_big_hint = true;  // did the last frame's walks outgrow the first storage tier? (none yet: assume so)
     bool flood_hold_hint = false;  // did the last frame hold its weakest seeds back?
@@ -183,16 +204,7 @@ struct lr_context {
     bool flood_staged_hint = false;  // was the last frame one of overlapping giants (kernels_flood.hip: kCtrlStaged)?  Then this one starts on its strongest quarter
     bool flood_calm_hint = false;      // the last frame's walks all stayed in the first storage tier (FloodBuffers::calm_hint)
     uint32_t flood_tiers[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // last flood: seeds in the second tier, slabs used, seeds of the ordered tail, hold-back, walked px (lo, hi), steps (lo, hi), walks beyond the first tier's table, 0 (retired), re-walks from logs, logs given up, giants held back
-    bool flood_partial = true;  // partial commits of blocked seeds (kernels_flood.hip); lr_set_flood_partial_commits
-    int flood_log_min = 0, flood_log_walk = 0;  // thresholds of the logs (0: the defaults; the lanes of a batch call get 32 and 24)
-    bool flood_log_sweep = false;  // test hook (lr_set_flood_logs(ctx, 2)): every footprint worked out from a log goes the fall-back way (sweeps)
-    bool flood_logs = true;     // blocked seeds work their next footprint out from the records of their last walk (kernels_flood.hip: flood_rewalk_kernel); lr_set_flood_logs, LIBRECTIFY_FLOOD_LOGS=0
-    bool flood_staged = false;  // lr_set_flood_staged: the rounds start on the strongest eighth of the seeds (test / experiment hook)
-    // Stage timers (HIP events between the stages of a frame): off in the frame calls unless lr_set_stage_timing or
-    // LIBRECTIFY_STAGE_TIMES asks -- every event record is a barrier packet in the stream, some 6 us of idle GPU each,
-    // seven of them per frame.  The staged API (lr_stage_*) always times its stages.
-    bool timing_on = false;
-    hipEvent_t ev[16] = {};
+    lramd::Event ev[16];  // stage timers (Settings::timing_on)
     float stage_ms[LR_T_COUNT] = {};
     double host_ms[3] = {0, 0, 0};  // last frame: enqueue, next-frame staging + upload, wait (LIBRECTIFY_LANE_DEBUG)
     bool stage_valid[4] = {false, false, false, false};
@@ -206,7 +218,7 @@ void ctx_destroy(lr_context* c);
 const std::string& get_error();
 int ctx_ensure_image_capacity(lr_context* c, int w, int h);
 int ctx_trim(lr_context* c, bool frames_too);
-int ctx_ensure_ransac_capacity(lr_context* c, size_t n_lines, size_t n_iter);
+int ctx_ensure_ransac_capacity(lr_context* c, size_t n_lines);
 int ctx_stage_filter(lr_context* c, const float* d_image, int w, int h, int stride);
 int ctx_stage_seeds(lr_context* c);
 int ctx_stage_flood(lr_context* c);

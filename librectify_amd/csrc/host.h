@@ -1,0 +1,104 @@
+// Internals shared by the host units: context.hip (workspace), upload.hip (host frames -> device), frame.hip (one frame),
+// estimators.hip (vanishing points), batch.hip (many frames, many devices).
+#pragma once
+#include <atomic>
+#include <chrono>
+#include <condition_variable>
+#include <mutex>
+#include <thread>
+#include <vector>
+
+#include "context.h"
+
+namespace lramd {
+
+inline double now_ms() {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// d_counts words
+enum { kCntSeeds = 0, kCntComp = 1, kCntPx = 2, kCntLarge = 4 };
+
+// context.hip
+int ensure_flood_buffers(lr_context* c);
+int ensure_group_capacity(lr_context* c, size_t n_lines);
+
+// frame.hip
+int enqueue_groups(lr_context* c, uint32_t line_cap, int max_models, float inlier_deg, float garbage_deg, int n_iter,
+                   uint64_t seed, bool model_done = false, bool gather = false);
+int run_frame(lr_context* c, const float* d_image, int w, int h, int stride, float min_length, bool refine,
+              std::vector<LineSegment>& out, bool filter_enqueued = false);
+
+// upload.hip
+int ensure_copy_stream(lr_context* c);
+bool is_page_locked(const void* p);
+int staging_threads(int num_threads, size_t frame_bytes = 0);
+void bind_this_thread_near(int device);
+int upload_rows(lr_context* c, float* dst, float* stage, const float* buffer, int w, int h, int stride, int num_threads,
+                hipStream_t up);
+int ensure_frame_slot(lr_context* c, int slot, size_t npix, bool pageable, float** stage);
+int ensure_upload_ring(lr_context* c, int R, size_t npix, bool staging);
+
+// The threads that stage pageable frames for a batch call: started once per call, not once per frame (seven thread
+// starts a frame were a tenth of a millisecond of the uploader's time and the larger part of its jitter).  A job is one
+// frame; its 4 MB bands are claimed through a counter that carries the job's number, so that a thread that is late for
+// one job cannot take a band of the next with the old job's pointers.
+struct StagingCrew {
+    lr_context* c = nullptr;
+    std::vector<std::thread> th;
+    std::atomic<uint32_t> job{0};
+    std::atomic<uint64_t> next{0};   // job number << 32 | next piece
+    std::atomic<uint64_t> total{0};  // job number << 32 | pieces of that job
+    std::atomic<int> bands_left{0}, failed{0};
+    std::atomic<bool> quit{false};
+    // Two job descriptors, used alternately (job number & 1): the one a late helper may still be reading is not the one
+    // the uploader fills for the next frame, and the one after that is only filled when every band of this one is done.
+    struct Job {
+        float* dst = nullptr;
+        float* stage = nullptr;
+        const float* src = nullptr;
+        int w = 0, h = 0, stride = 0, rows_per_band = 1, n_bands = 0;
+        hipStream_t up = nullptr;
+        int pieces = 1;                       // row runs a band is copied in (by different threads)
+        const Event* band_ev = nullptr;       // optional: recorded after each band's transfer is enqueued ...
+        std::atomic<int>* ready = nullptr;    // ... and then ready[k] = 1 (-1 if the band failed)
+    } jobs[2];
+
+    // A single frame's bands are staged by ALL the threads together, piece by piece (`pieces` row runs per band, claimed in
+    // order through `next`), and sent by whichever thread finishes a band's last piece: the first transfer starts after one
+    // band's worth of copying spread over the crew instead of after every thread has copied a whole band of its own (which
+    // is when all of them are ready at once).  A batch's uploader keeps whole bands per thread (pieces = 1): there the
+    // link is busy with the previous frame anyway, and fewer hand-overs are worth more than an early start.
+    static constexpr int kPieces = 8;
+    static constexpr int kMaxBands = 256;
+    std::atomic<int> pieces_left[2][kMaxBands];
+
+    // Helpers between jobs: a short spin (frames of a batch follow each other within microseconds), then they BLOCK on a
+    // condition variable -- a library behind librectify.h must not keep eight threads polling in a process that is doing
+    // nothing (round 3 did: 20 us naps for ever).  begin() wakes them only if somebody sleeps.
+    std::mutex mu;
+    std::condition_variable cv;
+    std::atomic<int> sleepers{0};
+    std::atomic<int> live{0};  // helpers that have a device and are taking jobs (the caller stages alone if none is)
+
+    bool work_one(uint32_t gen);  // one piece of job `gen`, if there is one left: true if a piece was claimed (and copied)
+    void work(uint32_t gen) {
+        while (work_one(gen)) {
+        }
+    }
+    void start(lr_context* ctx, int helpers);
+    // stages one frame (rows as in upload_rows) and enqueues its transfers; returns when every band is enqueued
+    int run(float* dst_, float* stage_, const float* buffer, int w_, int h_, int stride_, hipStream_t up_,
+            size_t band_bytes = (size_t)4 << 20, int pieces_ = 1) {
+        const uint32_t g = begin(dst_, stage_, buffer, w_, h_, stride_, up_, nullptr, nullptr, band_bytes, pieces_);
+        work(g);
+        return finish();
+    }
+    // the two halves of run(): publish the job (the helpers start on it), and wait for its last band
+    uint32_t begin(float* dst_, float* stage_, const float* buffer, int w_, int h_, int stride_, hipStream_t up_,
+                   const Event* band_ev_, std::atomic<int>* ready_, size_t band_bytes = (size_t)4 << 20, int pieces_ = 0);
+    int finish();
+    ~StagingCrew();
+};
+
+}  // namespace lramd

@@ -271,7 +271,7 @@ int filter_band_last_row(int by) { return kBandRows * by - 4 + kBandSteps - 1; }
 
 // The bands whose image rows lie in [row_begin, row_end) -- band row `by` reads the image rows 30 by - 4 .. 30 by + 33 --
 // i.e. the band rows [by_begin, by_end).  A frame that is still arriving over the link is filtered in a few such
-// launches, each as soon as its rows are on the device (context.hip: find_groups_host).
+// launches, each as soon as its rows are on the device (frame.hip: ctx_find_groups_host).
 int launch_filter_rows(const float* img, int w, int h, int stride, const FilterConsts& fc, float* dx, float* dy,
                        uint8_t* dmask, uint64_t* cand, uint32_t* cand_count, uint32_t* tile_max, int by_begin, int by_end,
                        hipStream_t s) {

@@ -3269,7 +3269,7 @@ FloodArgs flood_args(const FloodBuffers& B, const FloodFrame& F, bool use_big) {
 // front of waiting seeds -- the hold-back, the giants' line: a late round that walked only its first grid's worth of an
 // unordered list could leave the lowest active seed unwalked, move nothing, and send the frame to the ordered tail.)
 constexpr uint32_t kFullGridCap = 1u << 18;
-constexpr int kRestRounds = 4;  // rounds 0 .. kRestRounds - 1 always bring their `rest` launch: the rounds a frame may enqueue blindly (context.hip: jit_first_max)
+constexpr int kRestRounds = 4;  // rounds 0 .. kRestRounds - 1 always bring their `rest` launch: the rounds a frame may enqueue blindly (frame.hip: flood_buffers_for, kJitFirstMax)
 void enqueue_round(const FloodBuffers& B, const FloodFrame& F, const FloodArgs& A0, bool use_big, int index, hipStream_t s,
                    uint32_t known_len = 0xFFFFFFFFu, bool next_known = false) {
     // (which of the two active lists a round reads is the device's business -- kCtrlRounds, act_now: rounds enqueued behind a

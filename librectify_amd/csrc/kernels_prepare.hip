@@ -257,32 +257,25 @@ int ctx_prepare_frames(lr_context* c, const void* d_src, size_t src_image_bytes,
     // The span table is made once per (source size, output size) and kept.  The launches that read the device copy and
     // the upload that overwrites it are all on the context's stream; the page-locked copy waits for its last upload.
     const size_t n_spans = (size_t)out_width + (size_t)out_height;
-    const bool same = c->d_prep_spans && c->prep_key[0] == width && c->prep_key[1] == out_width &&
-                      c->prep_key[2] == height && c->prep_key[3] == out_height;
+    const bool same = c->prep.spans.d && c->prep.key[0] == width && c->prep.key[1] == out_width &&
+                      c->prep.key[2] == height && c->prep.key[3] == out_height;
     if (!same) {
-        c->prep_key[0] = 0;  // (no table while this is under way)
-        if (n_spans > c->cap_prep_spans) {
+        c->prep.key[0] = 0;  // (no table while this is under way)
+        if (n_spans * sizeof(Span) > c->prep.spans.cap()) {
             LR_HIP(hipStreamSynchronize(c->stream));
-            if (c->d_prep_spans) LR_HIP(hipFree(c->d_prep_spans));
-            if (c->h_prep_spans) LR_HIP(hipHostFree(c->h_prep_spans));
-            c->d_prep_spans = nullptr;
-            c->h_prep_spans = nullptr;
-            c->cap_prep_spans = 0;
-            LR_HIP(hipMalloc(&c->d_prep_spans, n_spans * sizeof(Span)));
-            LR_HIP(hipHostMalloc(&c->h_prep_spans, n_spans * sizeof(Span)));
-            c->cap_prep_spans = n_spans;
+            if (c->prep.spans.grow(n_spans * sizeof(Span))) return 1;
         }
-        if (!c->ev_prep_spans) LR_HIP(hipEventCreateWithFlags(&c->ev_prep_spans, hipEventDisableTiming));
+        if (c->ev_prep_spans.ensure(hipEventDisableTiming)) return 1;
         LR_HIP(hipEventSynchronize(c->ev_prep_spans));  // the previous table's upload has read h_prep_spans
-        Span* hs = static_cast<Span*>(c->h_prep_spans);
-        c->prep_w_in[0] = make_spans(width, out_width, hs);
-        c->prep_w_in[1] = make_spans(height, out_height, hs + out_width);
-        LR_HIP(hipMemcpyAsync(c->d_prep_spans, c->h_prep_spans, n_spans * sizeof(Span), hipMemcpyHostToDevice, c->stream));
+        Span* hs = reinterpret_cast<Span*>(c->prep.spans.h.get());
+        c->prep.w_in[0] = make_spans(width, out_width, hs);
+        c->prep.w_in[1] = make_spans(height, out_height, hs + out_width);
+        LR_HIP(hipMemcpyAsync(c->prep.spans.d, c->prep.spans.h, n_spans * sizeof(Span), hipMemcpyHostToDevice, c->stream));
         LR_HIP(hipEventRecord(c->ev_prep_spans, c->stream));
-        c->prep_key[0] = width;
-        c->prep_key[1] = out_width;
-        c->prep_key[2] = height;
-        c->prep_key[3] = out_height;
+        c->prep.key[0] = width;
+        c->prep.key[1] = out_width;
+        c->prep.key[2] = height;
+        c->prep.key[3] = out_height;
     }
 
     PrepareArgs g;
@@ -294,10 +287,10 @@ int ctx_prepare_frames(lr_context* c, const void* d_src, size_t src_image_bytes,
     g.dst_row_bytes = dst_row_bytes;
     g.ow = out_width;
     g.oh = out_height;
-    g.sx = static_cast<const Span*>(c->d_prep_spans);
+    g.sx = reinterpret_cast<const Span*>(c->prep.spans.d.get());
     g.sy = g.sx + out_width;
-    g.wx_in = c->prep_w_in[0];
-    g.wy_in = c->prep_w_in[1];
+    g.wx_in = c->prep.w_in[0];
+    g.wy_in = c->prep.w_in[1];
     g.tiles_x = (int)tiles_x;
     g.tiles_per_frame = (int)(tiles_x * tiles_y);
     g.n_tiles = (int)n_tiles;

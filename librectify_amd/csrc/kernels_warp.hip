@@ -240,21 +240,14 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
     if (n_tiles > 0x7FFFFFF0ll) return fail("output larger than 2^31 tiles of 64 x 16 pixels");
 
     LR_HIP(hipSetDevice(c->device));
-    if ((size_t)batch > c->cap_warp_m) {  // (grows: the buffers of a previous call may still be read by its launch)
+    if ((size_t)batch * 9 > c->warp_m.cap()) {  // (grows: the buffers of a previous call may still be read by its launch)
         LR_HIP(hipStreamSynchronize(c->stream));
-        if (c->d_warp_m) LR_HIP(hipFree(c->d_warp_m));
-        if (c->h_warp_m) LR_HIP(hipHostFree(c->h_warp_m));
-        c->d_warp_m = nullptr;
-        c->h_warp_m = nullptr;
-        c->cap_warp_m = 0;
-        LR_HIP(hipMalloc((void**)&c->d_warp_m, (size_t)batch * 9 * sizeof(double)));
-        LR_HIP(hipHostMalloc((void**)&c->h_warp_m, (size_t)batch * 9 * sizeof(double)));
-        c->cap_warp_m = (size_t)batch;
+        if (c->warp_m.grow((size_t)batch * 9)) return 1;
     }
-    if (!c->ev_warp_m) LR_HIP(hipEventCreateWithFlags(&c->ev_warp_m, hipEventDisableTiming));
+    if (c->ev_warp_m.ensure(hipEventDisableTiming)) return 1;
     LR_HIP(hipEventSynchronize(c->ev_warp_m));  // the previous call's upload has read h_warp_m
-    std::memcpy(c->h_warp_m, M, (size_t)batch * 9 * sizeof(double));
-    LR_HIP(hipMemcpyAsync(c->d_warp_m, c->h_warp_m, (size_t)batch * 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    std::memcpy(c->warp_m.h, M, (size_t)batch * 9 * sizeof(double));
+    LR_HIP(hipMemcpyAsync(c->warp_m.d, c->warp_m.h, (size_t)batch * 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
     LR_HIP(hipEventRecord(c->ev_warp_m, c->stream));
 
     WarpArgs g;
@@ -268,7 +261,7 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
     g.dst_row_bytes = dst_row_bytes;
     g.ow = out_width;
     g.oh = out_height;
-    g.M = c->d_warp_m;
+    g.M = c->warp_m.d;
     g.tiles_x = (int)tiles_x;
     g.tiles_per_frame = (int)(tiles_x * tiles_y);
     g.n_tiles = (int)n_tiles;

@@ -418,7 +418,7 @@ static std::vector<LineSegment> merge_graph(const std::vector<LineSegment>& line
 }
 
 
-// line_detector.cpp:254-444 with the O(n^2) pair test on the host (used for small n; context.hip switches to
+// line_detector.cpp:254-444 with the O(n^2) pair test on the host (used for small n; estimators.hip: ctx_refine switches to
 // refine_pairs_kernel for large n); the merge graph walk reproduces the reference's forward-only BFS (:293).
 std::vector<LineSegment> refine_lines(const std::vector<LineSegment>& lines) {
     const int n = (int)lines.size();
