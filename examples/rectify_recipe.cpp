@@ -145,15 +145,22 @@ bool find_groups_device_prepared(const Gray& g, int max_size, bool refine, int t
     const size_t img_bytes = (size_t)out_w * out_h * sizeof(float);
     found.resize((size_t)out_w * out_h / 6 + 16);
     int n = 0;
-    const bool ok =
-        lr_context_create(0, &ctx) == 0 && lr_device_malloc(ctx, g.raw.size(), &d_src) == 0 &&
-        lr_device_malloc(ctx, img_bytes, &d_img) == 0 && lr_memcpy_h2d(ctx, d_src, g.raw.data(), g.raw.size()) == 0 &&
-        lr_warp_perspective_device(ctx, d_src, g.raw.size(), 1, g.w, g.h, (size_t)g.w * g.ch,
-                                   (g.ch == 3 ? LR_PIX_U8X3 : LR_PIX_U8) | LR_WARP_PREPARE, nullptr, d_img, img_bytes, out_w,
-                                   out_h, (size_t)out_w * sizeof(float)) == 0 &&
-        lr_find_line_segment_groups_device(ctx, static_cast<const float*>(d_img), out_w, out_h, out_w,
-                                           (float)std::max(out_w, out_h) / 100.0f, refine, threads, found.data(),
-                                           (int)found.size(), &n) == 0;
+    // (a frame that needs no prescale is searched where it lies: the detector reads 8-bit frames itself -- LR_FRAMES_*)
+    const bool in_place = scale == 1.0f;
+    const float min_length = (float)std::max(out_w, out_h) / 100.0f;
+    bool ok = lr_context_create(0, &ctx) == 0 && lr_device_malloc(ctx, g.raw.size(), &d_src) == 0 &&
+              lr_memcpy_h2d(ctx, d_src, g.raw.data(), g.raw.size()) == 0;
+    if (ok && in_place)
+        ok = lr_find_line_segment_groups_device(ctx, static_cast<const float*>(d_src), g.w, g.h, g.w, min_length,
+                                                (g.ch == 3 ? LR_FRAMES_U8X3 : LR_FRAMES_U8) | (refine ? 1 : 0), threads,
+                                                found.data(), (int)found.size(), &n) == 0;
+    else if (ok)
+        ok = lr_device_malloc(ctx, img_bytes, &d_img) == 0 &&
+             lr_warp_perspective_device(ctx, d_src, g.raw.size(), 1, g.w, g.h, (size_t)g.w * g.ch,
+                                        (g.ch == 3 ? LR_PIX_U8X3 : LR_PIX_U8) | LR_WARP_PREPARE, nullptr, d_img, img_bytes, out_w,
+                                        out_h, (size_t)out_w * sizeof(float)) == 0 &&
+             lr_find_line_segment_groups_device(ctx, static_cast<const float*>(d_img), out_w, out_h, out_w, min_length, refine,
+                                                threads, found.data(), (int)found.size(), &n) == 0;
     if (!ok) std::fprintf(stderr, "device prepare failed: %s\n", lr_last_error());
     if (ctx) {
         if (d_src) lr_device_free(ctx, d_src);

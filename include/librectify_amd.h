@@ -34,6 +34,7 @@ extern "C" {
 #endif
 
 typedef struct lr_context lr_context;
+enum lr_pixel_format { LR_PIX_U8 = 0, LR_PIX_U8X3 = 1, LR_PIX_F32 = 2 };
 
 /* ---- context ------------------------------------------------------------------------- */
 /* One context = one device, one HIP stream, one reusable workspace.  Not thread-safe; use
@@ -69,6 +70,24 @@ void lr_set_flood_mode(lr_context* ctx, int mode);
 int lr_device_count(void);
 
 /* ---- full path ------------------------------------------------------------------------ */
+/* 8-bit frames.  The six lr_find_line_segment_groups_* entries below take the frames' pixel format in their `refine`
+ * argument, which is a word: if it is non-negative, its bits 16 and up are zero and its bits 8-15 are 1, 2 or 3, the
+ * frames are of lr_pixel_format (bits 8-15) - 1 and the reference's flag is (refine & 0xFF) != 0.  EVERY OTHER VALUE MEANS
+ * WHAT IT ALWAYS MEANT: refine != 0 on fp32 frames -- 0, 1, -1, `true` are untouched; only the values 256 .. 1023 changed
+ * their meaning (they were "refine on").  With a format word
+ *  - the `const float*` frame parameters take the frames' address whatever the format: cast it
+ *    ((const float*)bytes; nothing is read through it as float).  8-bit frames need no alignment, of pointer or of stride;
+ *  - `stride` and `image_stride` stay in PIXELS of the frames' format: rows are stride * bpp bytes apart, bpp = 1 (u8),
+ *    3 (u8x3, interleaved) or 4 (f32); any sign for host frames, as image.cpp:11-19;
+ *  - the detector runs on p = float(luma) * (1/256.f), which is exact: luma is the byte (u8) or
+ *    (4899 c0 + 9617 c1 + 1868 c2 + 8192) >> 14 (u8x3, the prepare step's); the result is, bit for bit, that of the fp32
+ *    frame p.  A u8 frame is read by the filter kernel itself, byte by byte: no fp32 copy of it exists anywhere and a
+ *    quarter of the bytes crosses the link and the host's memory.  A u8x3 frame (3 B/px on the link) becomes p in a
+ *    buffer of the context by one launch on the frame's stream, and the fp32 filter reads that;
+ *  - a frame smaller than 5 x 5 is answered as the drop-in symbol answers it: success, *n_lines = 0 (the plain flag keeps
+ *    its error return).
+ * The drop-in find_line_segment_groups (bool refine, float buffer) and the stage API (lr_stage_filter*) stay fp32. */
+enum lr_frames_option { LR_FRAMES_U8 = 0x100, LR_FRAMES_U8X3 = 0x200, LR_FRAMES_F32 = 0x300 }; /* or-ed into `refine`: (lr_pixel_format + 1) << 8 */
 /* find_line_segment_groups on an image already resident in HBM (row-major float, `stride`
  * elements between rows, stride >= width).  Writes at most `capacity` segments to the HOST
  * array `out`; *n_lines is the number found (0 on the reference's NULL paths,
@@ -76,7 +95,8 @@ int lr_device_count(void);
 int lr_find_line_segment_groups_device(lr_context* ctx, const float* d_image, int width, int height, int stride,
                                        float min_length, int refine, int num_threads, LineSegment* out, int capacity,
                                        int* n_lines);
-/* Same, host buffer (any stride sign, as the reference: image.cpp:11-19). */
+/* Same, host buffer (any stride sign, as the reference: image.cpp:11-19).  An 8-bit frame travels as it is: staged and
+ * sent in bands of 4 MB (four times as many rows as of an fp32 frame), the filter following the bands (u8). */
 int lr_find_line_segment_groups_host(lr_context* ctx, const float* buffer, int width, int height, int stride,
                                      float min_length, int refine, int num_threads, LineSegment* out, int capacity,
                                      int* n_lines);
@@ -97,8 +117,11 @@ int lr_find_line_segment_groups_batch_device(lr_context* ctx, const float* d_ima
  * where it lies.  Pageable memory goes through page-locked staging buffers -- as many as there are pool slots, i.e.
  * the same amount again in pinned host memory, allocated when a call first meets a pageable frame -- filled in 4 MB
  * row bands by `num_threads` host threads shared by the whole call (the reference's knob, threading.h:24-27: < 0 or
- * 1 = the uploader alone; capped at 8 and at the host's cores), started once per call.  Outputs as for the device
- * batch. */
+ * 1 = the uploader alone; capped at 8 and at the host's cores), started once per call.  By default pageable frames are
+ * instead page-locked where they lie for the length of the call (LIBRECTIFY_REGISTER_FRAMES): only the whole pages INSIDE a
+ * frame -- frames of one array share the page at each end, and no page is registered twice; the few rows that reach into
+ * those pages take the staging buffer (and the frame's lane fetches them), and so does every frame that overlaps an earlier one of the call.  Outputs as for
+ * the device batch. */
 int lr_find_line_segment_groups_batch_host(lr_context* ctx, const float* frames, size_t image_stride, int batch,
                                            int width, int height, int stride, float min_length, int refine,
                                            int num_threads, LineSegment* out, int capacity, int* n_lines,
@@ -180,7 +203,6 @@ void lr_set_flood_giant_step(lr_context* ctx, int on);
  * system (three collinear corners).  Host only: needs no context and no GPU. */
 int lr_rectification_homography(const ImageTransform* t, float clip, double* H, double* M, int* out_width,
                                 int* out_height);
-enum lr_pixel_format { LR_PIX_U8 = 0, LR_PIX_U8X3 = 1, LR_PIX_F32 = 2 };
 /* Bilinear perspective warp of `batch` device frames in ONE launch on the context's stream: frame b at
  * d_src + b*src_image_bytes (rows src_row_bytes apart), its output at d_dst + b*dst_image_bytes (rows dst_row_bytes
  * apart); M: 9 doubles per frame (HOST), the destination-to-source map of that frame; one output size for all.

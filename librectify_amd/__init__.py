@@ -61,6 +61,24 @@ BUF_DX, BUF_DY, BUF_DMASK, BUF_LABEL, BUF_SEED_IDX, BUF_SEED_BIN, BUF_SEED_THR, 
 T_UPLOAD, T_FILTER, T_SEEDS, T_FLOOD, T_FIT, T_RANSAC, T_TOTAL, T_FILTER_KERNEL, T_COUNT = range(9)
 PIX_U8, PIX_U8X3, PIX_F32 = range(3)  # enum lr_pixel_format
 WARP_PREPARE = 0x100  # enum lr_warp_option, or-ed into the format of lr_warp_perspective_device
+FRAMES_U8, FRAMES_U8X3, FRAMES_F32 = 0x100, 0x200, 0x300  # enum lr_frames_option, or-ed into `refine` of the frame entries
+
+
+def frames_word(fmt, refine=False):
+    """The `refine` word of the lr_find_line_segment_groups_* entries for frames of format fmt (PIX_U8, PIX_U8X3,
+    PIX_F32): (fmt + 1) << 8 | flag.  PIX_F32 gives the plain flag, 0 or 1, as these calls always passed it."""
+    if fmt not in (PIX_U8, PIX_U8X3, PIX_F32):
+        raise ValueError("frames_word: fmt is PIX_U8, PIX_U8X3 or PIX_F32")
+    flag = 1 if refine else 0
+    return flag if fmt == PIX_F32 else ((fmt + 1) << 8) | flag
+
+
+def split_frames_word(word):
+    """(fmt, flag) of a `refine` word, as the library reads it (api.cpp): a format only in the values 256 .. 1023"""
+    word = int(word)
+    if word >= 0 and 1 <= (word >> 8) <= 3:
+        return (word >> 8) - 1, (word & 0xFF) != 0
+    return PIX_F32, word != 0
 
 EXPORTS = [
     "find_line_segment_groups", "release_line_segments", "compute_rectification_transform",
@@ -213,6 +231,20 @@ def _frame_format(a, what):
     raise ValueError(what + ": a 2-D uint8 or float32 frame, or an H x W x 3 uint8 frame")
 
 
+def _host_frame(a, what):
+    """a host frame as the detector's entries take it: (array, format, bytes per pixel, stride in pixels); float32 for
+    everything that is not uint8, as ever"""
+    a = np.asarray(a)
+    if a.dtype != np.uint8:
+        a = np.asarray(a, np.float32)
+    fmt, bpp = _frame_format(a, what)
+    if fmt == PIX_U8X3:
+        assert a.strides[2] == 1 and a.strides[1] == 3 and a.strides[0] % 3 == 0
+    else:
+        assert a.strides[1] == bpp and a.strides[0] % bpp == 0
+    return a, fmt, bpp, a.strides[0] // bpp
+
+
 class Context:
     """One device, one stream, one workspace (include/librectify_amd.h)."""
 
@@ -315,25 +347,25 @@ class Context:
 
     # ---- full path ----
     def find_line_segment_groups(self, img, min_length, refine=False, num_threads=-1, capacity=None):
-        """img: 2-D float32 numpy array (host)."""
-        img = np.asarray(img, np.float32)
-        h, w = img.shape
-        stride = img.strides[0] // 4
-        assert img.strides[1] == 4
+        """img: 2-D float32 numpy array (host), or an 8-bit frame: 2-D uint8, or H x W x 3 uint8 (interleaved; the
+        detector runs on luma / 256, exactly what it gives on that float32 frame)."""
+        img, fmt, _, stride = _host_frame(img, "find_line_segment_groups")
+        h, w = img.shape[:2]
         cap = capacity or (h * w // 6 + 16)
         out = np.zeros(cap, LINE_DTYPE)
         n = C.c_int(0)
         self.shape = (h, w)
-        _check(lib().lr_find_line_segment_groups_host(self._h, _ptr(img), w, h, stride, min_length, int(refine), num_threads, _ptr(out), cap, C.byref(n)))
+        _check(lib().lr_find_line_segment_groups_host(self._h, _ptr(img), w, h, stride, min_length, frames_word(fmt, refine), num_threads, _ptr(out), cap, C.byref(n)))
         return out[: min(n.value, cap)].copy()
 
-    def find_line_segment_groups_device(self, dptr, w, h, min_length, refine=False, stride=None, capacity=None, out=None):
+    def find_line_segment_groups_device(self, dptr, w, h, min_length, refine=False, stride=None, capacity=None, out=None, fmt=PIX_F32):
+        """fmt: the resident frame's format (PIX_F32, PIX_U8, PIX_U8X3); stride in pixels of it"""
         cap = capacity or (h * w // 6 + 16)
         if out is None:
             out = np.zeros(cap, LINE_DTYPE)
         n = C.c_int(0)
         self.shape = (h, w)
-        _check(lib().lr_find_line_segment_groups_device(self._h, C.c_void_p(dptr), w, h, stride or w, min_length, int(refine), -1, _ptr(out), cap, C.byref(n)))
+        _check(lib().lr_find_line_segment_groups_device(self._h, C.c_void_p(dptr), w, h, stride or w, min_length, frames_word(fmt, refine), -1, _ptr(out), cap, C.byref(n)))
         return out[: min(n.value, cap)]
 
     def device_upload(self, array):
@@ -444,7 +476,8 @@ class Context:
         (4899 R + 9617 G + 1868 B + 8192) >> 14, / 256, find_line_segment_groups with min_length max(w, h) / 100 by
         default, compute_rectification_transform (cfg: the demo's, horizontal_vp_min_distance = 2),
         rectification_homography(clip) and the warp of the original frame.  Returns (lines, transform, warped).
-        max_size=None: without the demo's prescale, luma on the host and the float frame uploaded.  max_size=N (the
+        max_size=None: without the demo's prescale -- the 8-bit frame is uploaded once, the detector reads it where it lies
+        (frames_word: luma and / 256 happen on the device, exactly) and the warp reads the same resident frame.  max_size=N (the
         demo's default is 1200; below 1 a fraction of the longer side): with it -- the 8-bit frame is uploaded once,
         prepared on the device (prepare_device) to prepared_size(w, h, max_size), the detector runs on that with
         min_length max(w', h') / 100, the endpoints are divided by the scale, the transform is the full frame's and the
@@ -454,21 +487,25 @@ class Context:
             raise ValueError("rectify: an H x W or H x W x 3 uint8 frame")
         if max_size is not None:
             return self._rectify_prepared(img, max_size, min_length, refine, cfg or RectificationConfig(hmin=2.0), clip)
-        if img.ndim == 3:
-            c = img.astype(np.int32)
-            gray = (4899 * c[..., 0] + 9617 * c[..., 1] + 1868 * c[..., 2] + 8192) >> 14
-        else:
-            gray = img
-        h, w = gray.shape
-        luma = gray.astype(np.float32) / np.float32(256.0)
+        fmt, bpp = _frame_format(img, "rectify")
+        h, w = img.shape[:2]
         if min_length is None:
             min_length = max(w, h) / 100.0
-        lines = self.find_line_segment_groups(luma, min_length, refine=refine)
         if cfg is None:
             cfg = RectificationConfig(hmin=2.0)
-        t = compute_rectification_transform(lines, w, h, cfg)
-        _, M, size = rectification_homography(t, clip)
-        return lines, t, self.warp_perspective(img, M, size)
+        d_src = self.device_upload(img)
+        d_dst = C.c_void_p()
+        try:
+            lines = self.find_line_segment_groups_device(d_src, w, h, min_length, refine=refine, fmt=fmt).copy()
+            t = compute_rectification_transform(lines, w, h, cfg)
+            _, M, (rw, rh) = rectification_homography(t, clip)
+            _check(lib().lr_device_malloc(self._h, rw * rh * bpp, C.byref(d_dst)))
+            self.warp_perspective_device(d_src, img.nbytes, 1, w, h, w * bpp, fmt, M, d_dst.value, rw * rh * bpp, rw, rh, rw * bpp)
+            return lines, t, self.device_download(d_dst.value, (rh, rw) + img.shape[2:], np.uint8)
+        finally:
+            self.device_free(d_src)
+            if d_dst.value:
+                self.device_free(d_dst.value)
 
     def set_seed_capacity(self, cap):
         lib().lr_set_seed_capacity(self._h, int(cap))
@@ -482,25 +519,42 @@ class Context:
     def set_batch_streams(self, n):
         lib().lr_set_batch_streams(self._h, int(n))
 
-    def find_line_segment_groups_batch_device(self, dptr, image_stride, batch, w, h, min_length, refine=False, capacity=4096, cfg=None, out=None):
+    def find_line_segment_groups_batch_device(self, dptr, image_stride, batch, w, h, min_length, refine=False, capacity=4096, cfg=None, out=None, fmt=PIX_F32, stride=None):
+        """fmt: the resident frames' format; image_stride (and stride, default w) in pixels of it"""
         if out is None:
             out = np.zeros((batch, capacity), LINE_DTYPE)
         n = np.zeros(batch, np.int32)
         tf = (ImageTransform * batch)()
         cfg = cfg or RectificationConfig()
         self.shape = (h, w)
-        _check(lib().lr_find_line_segment_groups_batch_device(self._h, C.c_void_p(dptr), image_stride, batch, w, h, w, min_length, int(refine), -1, _ptr(out), capacity, _ptr(n), C.byref(cfg), C.byref(tf)))
+        _check(lib().lr_find_line_segment_groups_batch_device(self._h, C.c_void_p(dptr), image_stride, batch, w, h, stride or w, min_length, frames_word(fmt, refine), -1, _ptr(out), capacity, _ptr(n), C.byref(cfg), C.byref(tf)))
         return out, n, tf
 
     def find_line_segment_groups_batch_host(self, frames, min_length, refine=False, num_threads=-1, capacity=4096, cfg=None, out=None, devices=None):
         """frames: float32 array [B, H, W] (rows contiguous; any row/frame strides) or a list of 2-D float32 arrays
-        of one shape, in HOST memory (pageable, or page-locked as host_alloc returns it).  devices: a list of device
-        indices to deal the frames over in contiguous blocks (lr_find_line_segment_groups_batch_host_multi)."""
-        if isinstance(frames, np.ndarray) and frames.ndim == 3:
+        of one shape, in HOST memory (pageable, or page-locked as host_alloc returns it); or 8-bit frames: a uint8 array
+        [B, H, W] or [B, H, W, 3], or a list of such frames.  devices: a list of device indices to deal the frames over in
+        contiguous blocks (lr_find_line_segment_groups_batch_host_multi)."""
+        fmt, array_stride = PIX_F32, None
+        if isinstance(frames, np.ndarray) and frames.dtype == np.uint8 and frames.ndim in (3, 4):
+            _, fmt, bpp, stride = _host_frame(frames[0], "find_line_segment_groups_batch_host")
+            batch, h, w = frames.shape[:3]
+            ptrs = (C.c_void_p * batch)(*[frames.ctypes.data + b * frames.strides[0] for b in range(batch)])
+            if frames.strides[0] > 0 and frames.strides[0] % bpp == 0:  # (one array: the entry that takes a frame stride)
+                array_stride = frames.strides[0] // bpp
+        elif isinstance(frames, np.ndarray) and frames.ndim == 3:
             assert frames.dtype == np.float32 and frames.strides[2] == 4
             batch, h, w = frames.shape
             stride = frames.strides[1] // 4
             ptrs = (C.c_void_p * batch)(*[frames.ctypes.data + b * frames.strides[0] for b in range(batch)])
+        elif len(frames) and np.asarray(frames[0]).dtype == np.uint8:
+            frames = [_host_frame(f, "find_line_segment_groups_batch_host") for f in frames]
+            fmt, stride = frames[0][1], frames[0][3]
+            frames = [f[0] for f in frames]
+            batch = len(frames)
+            h, w = frames[0].shape[:2]
+            assert all(f.dtype == np.uint8 and f.shape == frames[0].shape and f.strides == frames[0].strides for f in frames)
+            ptrs = (C.c_void_p * batch)(*[f.ctypes.data for f in frames])
         else:
             frames = [np.asarray(f, np.float32) for f in frames]
             batch = len(frames)
@@ -508,6 +562,7 @@ class Context:
             stride = frames[0].strides[0] // 4
             assert all(f.shape == (h, w) and f.strides == frames[0].strides and f.strides[1] == 4 for f in frames)
             ptrs = (C.c_void_p * batch)(*[f.ctypes.data for f in frames])
+        word = frames_word(fmt, refine)
         if out is None:
             out = np.zeros((batch, capacity), LINE_DTYPE)
         n = np.zeros(batch, np.int32)
@@ -516,9 +571,12 @@ class Context:
         self.shape = (h, w)
         if devices is not None:
             devs = (C.c_int * len(devices))(*[int(d) for d in devices])
-            _check(lib().lr_find_line_segment_groups_batch_host_multi(self._h, devs, len(devices), ptrs, batch, w, h, stride, min_length, int(refine), num_threads, _ptr(out), capacity, _ptr(n), C.byref(cfg), C.byref(tf)))
+            _check(lib().lr_find_line_segment_groups_batch_host_multi(self._h, devs, len(devices), ptrs, batch, w, h, stride, min_length, word, num_threads, _ptr(out), capacity, _ptr(n), C.byref(cfg), C.byref(tf)))
             return out, n, tf
-        _check(lib().lr_find_line_segment_groups_batch_host_ptrs(self._h, ptrs, batch, w, h, stride, min_length, int(refine), num_threads, _ptr(out), capacity, _ptr(n), C.byref(cfg), C.byref(tf)))
+        if array_stride is not None:
+            _check(lib().lr_find_line_segment_groups_batch_host(self._h, C.c_void_p(frames.ctypes.data), array_stride, batch, w, h, stride, min_length, word, num_threads, _ptr(out), capacity, _ptr(n), C.byref(cfg), C.byref(tf)))
+            return out, n, tf
+        _check(lib().lr_find_line_segment_groups_batch_host_ptrs(self._h, ptrs, batch, w, h, stride, min_length, word, num_threads, _ptr(out), capacity, _ptr(n), C.byref(cfg), C.byref(tf)))
         return out, n, tf
 
     def host_alloc(self, shape, dtype=np.float32):

@@ -59,6 +59,39 @@ int guard_fail(const char* where) {
     return 1;
 }
 
+// The `refine` word of the six lr_find_line_segment_groups_* entries (include/librectify_amd.h: lr_frames_option): a
+// non-negative word whose bits 16 and up are zero and whose bits 8-15 are 1, 2 or 3 names the frames' lr_pixel_format and
+// carries the reference's flag in its low byte; every other value is the plain flag on fp32 frames, as it always was.
+struct FramesWord {
+    int format = LR_PIX_F32;
+    bool refine = false;
+    bool tagged = false;  // the word named a format
+    explicit FramesWord(int word) {
+        const int f = word >> 8;
+        if (word >= 0 && f >= 1 && f <= 3) {
+            format = f - 1;
+            refine = (word & 0xFF) != 0;
+            tagged = true;
+        } else {
+            refine = word != 0;
+        }
+    }
+};
+
+// A frame smaller than the 5x5 kernel given with a format word: no lines, silently, as the drop-in symbol answers it
+// (interface.cpp:50-54).  The plain flag keeps the error it always got.
+bool below_filter(const FramesWord& fw, const void* frames, int width, int height) {
+    return fw.tagged && frames != nullptr && width > 0 && height > 0 && (width < 5 || height < 5);
+}
+int nothing_found(int batch, int width, int height, int* n_lines, const RectificationConfig* cfg, ImageTransform* transforms) {
+    const RectificationConfig def;
+    for (int b = 0; b < batch; ++b) {
+        if (n_lines) n_lines[b] = 0;
+        if (transforms) transforms[b] = rectification_transform(nullptr, 0, width, height, cfg ? *cfg : def);
+    }
+    return 0;
+}
+
 int copy_out(const std::vector<LineSegment>& v, LineSegment* out, int capacity, int* n_lines) {
     const int n = (int)v.size();
     if (n_lines) *n_lines = n;
@@ -96,7 +129,7 @@ LineSegment* find_line_segment_groups(float* buffer, int width, int height, int 
         lr_context* c = thread_context();
         if (!c) return fail();
         std::vector<LineSegment> res;
-        if (ctx_find_groups_host(c, buffer, width, height, stride, min_length, refine, num_threads, res)) return fail();
+        if (ctx_find_groups_host(c, buffer, LR_PIX_F32, width, height, stride, min_length, refine, num_threads, res)) return fail();
         if (res.empty()) return nullptr;
         LineSegment* out = new (std::nothrow) LineSegment[res.size()];
         if (!out) {
@@ -207,8 +240,10 @@ int lr_find_line_segment_groups_device(lr_context* ctx, const float* d_image, in
                                        int* n_lines) {
     try {
         (void)num_threads;
+        const FramesWord fw(refine);
+        if (below_filter(fw, d_image, width, height)) return nothing_found(1, width, height, n_lines, nullptr, nullptr);
         std::vector<LineSegment> res;
-        if (ctx_find_groups_device(ctx, d_image, width, height, stride, min_length, refine != 0, res)) return 1;
+        if (ctx_find_groups_device(ctx, d_image, fw.format, width, height, stride, min_length, fw.refine, res)) return 1;
         return copy_out(res, out, capacity, n_lines);
     } catch (...) {
         return guard_fail("lr_find_line_segment_groups_device");
@@ -219,12 +254,14 @@ int lr_find_line_segment_groups_host(lr_context* ctx, const float* buffer, int w
                                      float min_length, int refine, int num_threads, LineSegment* out, int capacity,
                                      int* n_lines) {
     try {
+        const FramesWord fw(refine);
+        if (below_filter(fw, buffer, width, height)) return nothing_found(1, width, height, n_lines, nullptr, nullptr);
         if (width < 5 || height < 5 || buffer == nullptr) {
             set_error("image smaller than the 5x5 filter");
             return 1;
         }
         std::vector<LineSegment> res;
-        if (ctx_find_groups_host(ctx, buffer, width, height, stride, min_length, refine != 0, num_threads, res)) return 1;
+        if (ctx_find_groups_host(ctx, buffer, fw.format, width, height, stride, min_length, fw.refine, num_threads, res)) return 1;
         return copy_out(res, out, capacity, n_lines);
     } catch (...) {
         return guard_fail("lr_find_line_segment_groups_host");
@@ -237,8 +274,10 @@ int lr_find_line_segment_groups_batch_device(lr_context* ctx, const float* d_ima
                                              const RectificationConfig* cfg, ImageTransform* transforms) {
     try {
         (void)num_threads;
-        return ctx_find_groups_batch_device(ctx, d_images, image_stride, batch, width, height, stride, min_length,
-                                            refine != 0, out, capacity, n_lines, cfg, transforms);
+        const FramesWord fw(refine);
+        if (below_filter(fw, d_images, width, height)) return nothing_found(batch, width, height, n_lines, cfg, transforms);
+        return ctx_find_groups_batch_device(ctx, d_images, fw.format, image_stride, batch, width, height, stride, min_length,
+                                            fw.refine, out, capacity, n_lines, cfg, transforms);
     } catch (...) {
         return guard_fail("lr_find_line_segment_groups_batch_device");
     }
@@ -249,9 +288,12 @@ int lr_find_line_segment_groups_batch_host(lr_context* ctx, const float* frames,
                                            int num_threads, LineSegment* out, int capacity, int* n_lines,
                                            const RectificationConfig* cfg, ImageTransform* transforms) {
     try {
-        std::vector<const float*> ptrs((size_t)std::max(batch, 0));
-        for (int b = 0; b < batch; ++b) ptrs[b] = frames + (size_t)b * image_stride;
-        return ctx_find_groups_batch_host(ctx, ptrs.data(), batch, width, height, stride, min_length, refine != 0,
+        const FramesWord fw(refine);
+        if (below_filter(fw, frames, width, height)) return nothing_found(batch, width, height, n_lines, cfg, transforms);
+        std::vector<const void*> ptrs((size_t)std::max(batch, 0));
+        for (int b = 0; b < batch; ++b)
+            ptrs[b] = reinterpret_cast<const unsigned char*>(frames) + (size_t)b * image_stride * (size_t)pix_bytes(fw.format);
+        return ctx_find_groups_batch_host(ctx, ptrs.data(), fw.format, batch, width, height, stride, min_length, fw.refine,
                                           num_threads, out, capacity, n_lines, cfg, transforms);
     } catch (...) {
         return guard_fail("lr_find_line_segment_groups_batch_host");
@@ -263,8 +305,10 @@ int lr_find_line_segment_groups_batch_host_ptrs(lr_context* ctx, const float* co
                                                 LineSegment* out, int capacity, int* n_lines,
                                                 const RectificationConfig* cfg, ImageTransform* transforms) {
     try {
-        return ctx_find_groups_batch_host(ctx, frames, batch, width, height, stride, min_length, refine != 0, num_threads,
-                                          out, capacity, n_lines, cfg, transforms);
+        const FramesWord fw(refine);
+        if (below_filter(fw, frames, width, height)) return nothing_found(batch, width, height, n_lines, cfg, transforms);
+        return ctx_find_groups_batch_host(ctx, reinterpret_cast<const void* const*>(frames), fw.format, batch, width, height, stride,
+                                          min_length, fw.refine, num_threads, out, capacity, n_lines, cfg, transforms);
     } catch (...) {
         return guard_fail("lr_find_line_segment_groups_batch_host_ptrs");
     }
@@ -276,8 +320,11 @@ int lr_find_line_segment_groups_batch_host_multi(lr_context* ctx, const int* dev
                                                  int capacity, int* n_lines, const RectificationConfig* cfg,
                                                  ImageTransform* transforms) {
     try {
-        return ctx_find_groups_batch_host_multi(ctx, devices, n_devices, frames, batch, width, height, stride, min_length,
-                                                refine != 0, num_threads, out, capacity, n_lines, cfg, transforms);
+        const FramesWord fw(refine);
+        if (below_filter(fw, frames, width, height)) return nothing_found(batch, width, height, n_lines, cfg, transforms);
+        return ctx_find_groups_batch_host_multi(ctx, devices, n_devices, reinterpret_cast<const void* const*>(frames), fw.format, batch,
+                                                width, height, stride, min_length, fw.refine, num_threads, out, capacity, n_lines, cfg,
+                                                transforms);
     } catch (...) {
         return guard_fail("lr_find_line_segment_groups_batch_host_multi");
     }

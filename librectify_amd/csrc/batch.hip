@@ -20,11 +20,19 @@ namespace lramd {
 // batch still waited for their own upload, although the link was busy only two thirds of the time: 7.5 Gpix/s where
 // the same batch without the transfers ran at 9.0; LIBRECTIFY_LANE_DEBUG prints each frame's lead.)  A lane makes its
 // stream wait for the frame's transfer and never touches host memory itself.
-static int find_groups_batch(lr_context* c, const float* d_images, size_t image_stride, const float* const* h_frames,
+// Frames are of one lr_pixel_format (`format`; strides and image_stride in pixels of it) and travel as bytes.
+static int find_groups_batch(lr_context* c, const void* d_images_, int format, size_t image_stride, const void* const* h_frames_,
                              int batch, int w, int h, int stride, float min_length, bool refine, int num_threads,
                              LineSegment* out, int capacity, int* n_lines, const RectificationConfig* cfg,
                              ImageTransform* transforms) {
     if (batch <= 0) return 0;
+    const uint8_t* d_images = static_cast<const uint8_t*>(d_images_);
+    const uint8_t* const* h_frames = reinterpret_cast<const uint8_t* const*>(h_frames_);
+    const size_t bpp = (size_t)pix_bytes(format);
+    if (bpp == 0) {
+        set_error("unknown pixel format of the frames");
+        return 1;
+    }
     const int S = std::max(1, std::min(c->opt.batch_streams, batch));
     while ((int)c->workers.size() < S - 1) {
         lr_context* wc = nullptr;
@@ -61,6 +69,7 @@ static int find_groups_batch(lr_context* c, const float* d_images, size_t image_
     const size_t npix = (size_t)w * h;
     int R = 0;
     bool any_pageable = false;
+    std::vector<char> locked(h_frames ? (size_t)batch : 0, 0);  // frames in memory the CALLER has page-locked
     if (h_frames) {
         if (w < 1 || h < 1) {
             set_error("upload: bad frame");
@@ -76,17 +85,26 @@ static int find_groups_batch(lr_context* c, const float* d_images, size_t image_
                 return 1;
             }
         }
-        for (int i = 0; i < batch && !any_pageable; ++i) any_pageable = !is_page_locked(h_frames[i]);
+        // (asked once, before this call page-locks anything: a frame that overlaps one the call has registered is still
+        // the caller's pageable memory)
+        for (int i = 0; i < batch; ++i) {
+            locked[(size_t)i] = is_page_locked(h_frames[i]);
+            any_pageable = any_pageable || !locked[(size_t)i];
+        }
         // slots beyond one per lane: what the link may be ahead.  Six absorb the moments when several lanes finish
         // together (pageable 4K frames: 7.8 Gpix/s with three, 8.0 with six or ten); at most 2 GiB of frames, though.
         static const int extra_env = std::getenv("LIBRECTIFY_RING_EXTRA") ? std::max(1, std::atoi(std::getenv("LIBRECTIFY_RING_EXTRA"))) : 0;
-        const int by_bytes = (int)std::min<size_t>(64, ((size_t)2 << 30) / (npix * sizeof(float)));
+        const int by_bytes = (int)std::min<size_t>(64, ((size_t)2 << 30) / (npix * bpp));
         R = extra_env ? S + extra_env : std::max(S + 1, std::min(S + 6, by_bytes));
         R = std::min(batch, R);
         if (ensure_upload_ring(c, R, npix, any_pageable)) return 1;
     }
     std::vector<std::atomic<int>> enq(h_frames ? (size_t)batch : 0);  // frame's slot + 1 once its transfer is enqueued
     std::vector<std::atomic<int>> slot_busy((size_t)R);
+    struct SlotEdges {
+        int r_lo = 0, r_hi = 0;  // rows [0, r_lo) and [r_hi, h) of the slot's frame wait in its staging buffer (r_hi = 0: none)
+    };
+    std::vector<SlotEdges> slot_edges((size_t)R);  // (written by the uploader before enq[], read by the frame's lane after it)
     for (auto& a : enq) a.store(0, std::memory_order_relaxed);
     for (auto& a : slot_busy) a.store(0, std::memory_order_relaxed);
     static const bool lane_debug = std::getenv("LIBRECTIFY_LANE_DEBUG") != nullptr;
@@ -103,7 +121,17 @@ static int find_groups_batch(lr_context* c, const float* d_images, size_t image_
     std::atomic<int> late_frames{0};
     // Pageable caller frames are page-locked WHERE THEY LIE (hipHostRegister) by a few helper threads running ahead of the
     // uploader, sent by DMA from there, and released when the call is over -- no staging copy, i.e. one pass through host DRAM
-    // instead of three.  What it costs instead is the pinning itself (page-table work, ~1.3 ms a 4K frame on one thread).
+    // instead of three.
+    // No page is ever registered twice.  Frames of one array share the page at each end with their neighbours (an 8-bit
+    // 1080p frame is 506.25 pages; an fp32 frame too, where the array does not start on a page), and the helpers register
+    // and release frame by frame, concurrently.  So a frame's range is rounded INWARDS to whole pages: the pages two
+    // frames share belong to neither, and the rows that reach into them -- at most 4 KB and a row at each end -- go through
+    // the slot's staging buffer instead (RegPlan below): the uploader copies them there and sends the rows in between in ONE
+    // transfer, as ever; the frame's LANE fetches the few staged rows on its own stream before its filter, so the link's
+    // queue carries one command a frame (three -- head, middle, tail on the copy stream -- cost the fp32 headline 3 %).  A frame
+    // whose pages overlap an earlier frame's (a frame listed twice, sliding windows over one array) is not registered at
+    // all: it takes the staging copy, which only reads the caller's memory.
+    // What registration costs instead of the copy is the pinning itself (page-table work, ~1.3 ms a 4K frame on one thread).
     // Round 5: 10.93 -> 11.38 Gpix/s on the headline leg with four helpers, the 1080p batch unchanged;
     // the default since.  A frame whose registration is refused (memory somebody else has registered, a mapping that cannot be
     // pinned) goes through the staging copy as before; LIBRECTIFY_REGISTER_FRAMES=0 sends every frame that way,
@@ -113,6 +141,34 @@ static int find_groups_batch(lr_context* c, const float* d_images, size_t image_
     // 6 GB/s -- gets the staging copy back: for the rest of the call, and for the context's next 32 batch calls before it tries again)
     if (c->register_slow_calls > 0) --c->register_slow_calls;
     const bool reg_frames = register_threads > 0 && h_frames != nullptr && any_pageable && stride >= w && c->register_slow_calls == 0;
+    const size_t row_bytes = (size_t)w * bpp, pitch = (size_t)(stride < 0 ? -stride : stride) * bpp;
+    struct RegPlan {
+        uintptr_t lo = 0, hi = 0;  // the whole pages inside the frame (hi <= lo: none worth registering)
+        int r_lo = 0, r_hi = 0;    // rows [r_lo, r_hi) lie in them; the rows before and after are staged
+    };
+    std::vector<RegPlan> plan(reg_frames ? (size_t)batch : 0);
+    if (reg_frames) {
+        constexpr uintptr_t kPage = 4096;
+        for (int i = 0; i < batch; ++i) {
+            RegPlan& p = plan[(size_t)i];
+            const uintptr_t a = reinterpret_cast<uintptr_t>(h_frames[i]), e = a + (size_t)(h - 1) * pitch + row_bytes;
+            const uintptr_t lo = (a + kPage - 1) / kPage * kPage, hi = e / kPage * kPage;
+            if (hi <= lo) continue;
+            const int r_lo = (int)((lo - a + pitch - 1) / pitch);                                // first row that starts at or behind lo
+            const int r_hi = hi - a >= row_bytes ? (int)std::min<size_t>((size_t)h, (hi - a - row_bytes) / pitch + 1) : 0;  // rows that end at or before hi
+            if (r_hi - r_lo < h / 2) continue;  // (a frame of a few pages: the staging copy)
+            bool apart = !locked[(size_t)i] && !c->batch_no_register;  // ... from every earlier frame's pages
+            for (int j = 0; j < i && apart; ++j) {
+                const RegPlan& q = plan[(size_t)j];
+                apart = q.hi <= q.lo || q.hi <= lo || hi <= q.lo;
+            }
+            if (!apart) continue;
+            p.lo = lo;
+            p.hi = hi;
+            p.r_lo = r_lo;
+            p.r_hi = r_hi;
+        }
+    }
     std::atomic<int> reg_slow{0};
     std::vector<std::atomic<int>> reg_ready(reg_frames ? (size_t)batch : 0);
     for (auto& a : reg_ready) a.store(0, std::memory_order_relaxed);
@@ -135,14 +191,12 @@ static int find_groups_batch(lr_context* c, const float* d_images, size_t image_
                     if (!reg_ready[(size_t)i].compare_exchange_strong(expect, 3, std::memory_order_acq_rel)) continue;  // (the uploader has it)
                     int ok = 2;
                     const double t_r0 = now_ms();
-                    // (a frame that is in the batch more than once is registered by its first entry only: two helpers
-                    // registering one range at the same time can both be told "done", and the second release then fails)
-                    bool first = true;
-                    for (int j = 0; j < i && first; ++j) first = h_frames[j] != h_frames[i];
-                    if (first && !is_page_locked(h_frames[i]))
-                        ok = hipHostRegister(const_cast<float*>(h_frames[i]), ((size_t)(h - 1) * (size_t)stride + (size_t)w) * sizeof(float), hipHostRegisterDefault) == hipSuccess ? 1 : 2;
+                    // (only the frames with a plan: whole pages of their own, apart from every earlier frame's)
+                    const RegPlan& p = plan[(size_t)i];
+                    if (p.hi > p.lo)
+                        ok = hipHostRegister(reinterpret_cast<void*>(p.lo), p.hi - p.lo, hipHostRegisterDefault) == hipSuccess ? 1 : 2;
                     if (ok == 2) (void)hipGetLastError();
-                    if (ok == 1 && (now_ms() - t_r0) * 6.0e6 > (double)((size_t)h * (size_t)stride * sizeof(float))) reg_slow.fetch_add(1, std::memory_order_relaxed);
+                    if (ok == 1 && (now_ms() - t_r0) * 6.0e6 > (double)(p.hi - p.lo)) reg_slow.fetch_add(1, std::memory_order_relaxed);
                     reg_ready[(size_t)i].store(ok, std::memory_order_release);
                 }
             });
@@ -155,7 +209,7 @@ static int find_groups_batch(lr_context* c, const float* d_images, size_t image_
         }
         if (any_pageable) bind_this_thread_near(c->device);  // (this thread stages too; it is the library's own)
         StagingCrew crew;
-        if (any_pageable) crew.start(c, staging_threads(num_threads, npix * sizeof(float)) - 1);
+        if (any_pageable) crew.start(c, staging_threads(num_threads, npix * bpp) - 1);
         for (int i = 0; i < batch; ++i) {
             int slot = -1, spins = 0;
             const double t_w0 = batch_stats ? now_ms() : 0.0;
@@ -174,12 +228,36 @@ static int find_groups_batch(lr_context* c, const float* d_images, size_t image_
                 if (!reg_ready[(size_t)i].compare_exchange_strong(expect, 2, std::memory_order_acq_rel))  // (else: nobody has it -- staged)
                     while (reg_ready[(size_t)i].load(std::memory_order_acquire) == 3 && !abort_all.load(std::memory_order_relaxed)) nap(sp2);
             }
-            float* stage = is_page_locked(h_frames[i]) ? nullptr : c->ring.stage[(size_t)slot];
+            const bool registered = reg_frames && reg_ready[(size_t)i].load(std::memory_order_acquire) == 1;
+            uint8_t* stage = locked[(size_t)i] ? nullptr : reinterpret_cast<uint8_t*>(c->ring.stage[(size_t)slot].get());
+            uint8_t* dimg = reinterpret_cast<uint8_t*>(c->ring.img[(size_t)slot].get());
             const double t_u0 = now_ms();
             Event e_dbg;
             if (lane_debug && e_dbg.create() == hipSuccess) (void)hipEventRecord(e_dbg, c->copy_stream);
-            const int up_rc = stage ? crew.run(c->ring.img[(size_t)slot], stage, h_frames[i], w, h, stride, c->copy_stream, kBatchBand, 1)
-                                    : upload_rows(c, c->ring.img[(size_t)slot], nullptr, h_frames[i], w, h, stride, 1, c->copy_stream);
+            int up_rc = 0;
+            if (registered) {
+                const RegPlan& p = plan[(size_t)i];
+                const uint8_t* f = h_frames[i];
+                // the rows that reach into a page shared with a neighbour: staged here, fetched by the lane
+                for (int r = 0; r < p.r_lo; ++r) std::memcpy(stage + (size_t)r * row_bytes, f + (size_t)r * pitch, row_bytes);
+                for (int r = p.r_hi; r < h; ++r) std::memcpy(stage + (size_t)r * row_bytes, f + (size_t)r * pitch, row_bytes);
+                slot_edges[(size_t)slot].r_lo = p.r_lo;
+                slot_edges[(size_t)slot].r_hi = p.r_hi;
+                {
+                    const hipError_t e = pitch == row_bytes
+                        ? hipMemcpyAsync(dimg + (size_t)p.r_lo * row_bytes, f + (size_t)p.r_lo * pitch, (size_t)(p.r_hi - p.r_lo) * row_bytes, hipMemcpyHostToDevice, c->copy_stream)
+                        : hipMemcpy2DAsync(dimg + (size_t)p.r_lo * row_bytes, row_bytes, f + (size_t)p.r_lo * pitch, pitch, row_bytes, (size_t)(p.r_hi - p.r_lo), hipMemcpyHostToDevice, c->copy_stream);
+                    if (e != hipSuccess) up_rc = 1;
+                }
+                if (up_rc) {
+                    (void)hipGetLastError();
+                    set_error("upload: transfer of a registered frame failed");
+                }
+            } else {
+                slot_edges[(size_t)slot].r_hi = 0;
+                up_rc = stage ? crew.run(dimg, stage, h_frames[i], w, h, stride, (int)bpp, c->copy_stream, kBatchBand, 1)
+                              : upload_rows(c, dimg, nullptr, h_frames[i], w, h, stride, (int)bpp, 1, c->copy_stream);
+            }
             if (up_rc || hipEventRecord(c->ring_ev[(size_t)slot], c->copy_stream) != hipSuccess) {
                 up_err = get_error().empty() ? "upload failed" : get_error();
                 abort_all.store(1);
@@ -212,7 +290,7 @@ static int find_groups_batch(lr_context* c, const float* d_images, size_t image_
             return fail();
         }
         for (int b = next_frame.fetch_add(1, std::memory_order_relaxed); b < batch; b = next_frame.fetch_add(1, std::memory_order_relaxed)) {
-            const float* img = nullptr;
+            const void* img = nullptr;
             int img_stride = stride, slot = -1;
             if (h_frames) {
                 int spins = 0;
@@ -224,14 +302,28 @@ static int find_groups_batch(lr_context* c, const float* d_images, size_t image_
                     set_error("hipStreamWaitEvent failed");
                     return fail();
                 }
-                img = c->ring.img[(size_t)slot];
+                img = c->ring.img[(size_t)slot].get();
                 img_stride = w;
+                const SlotEdges ed = slot_edges[(size_t)slot];
+                if (ed.r_hi > 0) {  // (page-locked staging memory: two small transfers on the lane's own stream)
+                    uint8_t* dimg = reinterpret_cast<uint8_t*>(c->ring.img[(size_t)slot].get());
+                    const uint8_t* st = reinterpret_cast<const uint8_t*>(c->ring.stage[(size_t)slot].get());
+                    hipError_t e = hipSuccess;
+                    if (ed.r_lo > 0) e = hipMemcpyAsync(dimg, st, (size_t)ed.r_lo * row_bytes, hipMemcpyHostToDevice, l->stream);
+                    if (e == hipSuccess && ed.r_hi < h)
+                        e = hipMemcpyAsync(dimg + (size_t)ed.r_hi * row_bytes, st + (size_t)ed.r_hi * row_bytes, (size_t)(h - ed.r_hi) * row_bytes, hipMemcpyHostToDevice, l->stream);
+                    if (e != hipSuccess) {
+                        (void)hipGetLastError();
+                        set_error("upload: transfer of a registered frame's first or last rows failed");
+                        return fail();
+                    }
+                }
             } else {
-                img = d_images + (size_t)b * image_stride;
+                img = d_images + (size_t)b * image_stride * bpp;
             }
             std::vector<LineSegment> res;
             const double t_f0 = now_ms();
-            if (ctx_find_groups_device(l, img, w, h, img_stride, min_length, refine, res)) return fail();
+            if (ctx_find_groups_device(l, img, format, w, h, img_stride, min_length, refine, res)) return fail();
             if (batch_stats && h_frames && l->opt.timing_on) {  // (with the stage timers on: ev[0] is the frame's first kernel)
                 float lead = 0.f;
                 if (hipEventElapsedTime(&lead, c->ring_ev[(size_t)slot], l->ev[0]) == hipSuccess) {
@@ -275,7 +367,7 @@ static int find_groups_batch(lr_context* c, const float* d_images, size_t image_
     if (reg_slow.load() >= 2) c->register_slow_calls = 32;
     if (reg_frames)  // the caller's frames go back to being pageable
         for (int i = 0; i < batch; ++i)
-            if (reg_ready[(size_t)i].load(std::memory_order_acquire) == 1 && hipHostUnregister(const_cast<float*>(h_frames[i])) != hipSuccess)
+            if (reg_ready[(size_t)i].load(std::memory_order_acquire) == 1 && hipHostUnregister(reinterpret_cast<void*>(plan[(size_t)i].lo)) != hipSuccess)
                 (void)hipGetLastError();  // (nothing to be done about it, and the caller's thread must not find it in its next call)
     for (lr_context* l : lanes) l->sleep_in_wait = false;
     c->flood_logbig_off = false;
@@ -293,24 +385,24 @@ static int find_groups_batch(lr_context* c, const float* d_images, size_t image_
     return 0;
 }
 
-int ctx_find_groups_batch_device(lr_context* c, const float* d_images, size_t image_stride, int batch, int w, int h,
+int ctx_find_groups_batch_device(lr_context* c, const void* d_images, int format, size_t image_stride, int batch, int w, int h,
                                  int stride, float min_length, bool refine, LineSegment* out, int capacity, int* n_lines,
                                  const RectificationConfig* cfg, ImageTransform* transforms) {
-    return find_groups_batch(c, d_images, image_stride, nullptr, batch, w, h, stride, min_length, refine, -1, out,
+    return find_groups_batch(c, d_images, format, image_stride, nullptr, batch, w, h, stride, min_length, refine, -1, out,
                              capacity, n_lines, cfg, transforms);
 }
 
-int ctx_find_groups_batch_host(lr_context* c, const float* const* frames, int batch, int w, int h, int stride,
+int ctx_find_groups_batch_host(lr_context* c, const void* const* frames, int format, int batch, int w, int h, int stride,
                                float min_length, bool refine, int num_threads, LineSegment* out, int capacity,
                                int* n_lines, const RectificationConfig* cfg, ImageTransform* transforms) {
-    return find_groups_batch(c, nullptr, 0, frames, batch, w, h, stride, min_length, refine, num_threads, out, capacity,
+    return find_groups_batch(c, nullptr, format, 0, frames, batch, w, h, stride, min_length, refine, num_threads, out, capacity,
                              n_lines, cfg, transforms);
 }
 
 // One batch call over several devices of this process.  Every entry of the device list has a context of its own (kept
 // with `c` from call to call), configured like `c`, with its own uploader, copy stream, lanes and pool; a host thread per
 // entry runs the single-device batch call on its contiguous block of the frames.
-int ctx_find_groups_batch_host_multi(lr_context* c, const int* devices, int n_devices, const float* const* frames, int batch,
+int ctx_find_groups_batch_host_multi(lr_context* c, const int* devices, int n_devices, const void* const* frames, int format, int batch,
                                      int w, int h, int stride, float min_length, bool refine, int num_threads,
                                      LineSegment* out, int capacity, int* n_lines, const RectificationConfig* cfg,
                                      ImageTransform* transforms) {
@@ -344,6 +436,21 @@ int ctx_find_groups_batch_host_multi(lr_context* c, const int* devices, int n_de
         c->peers[(size_t)i]->opt = c->opt;
     }
     const int per = (batch + n_devices - 1) / n_devices;  // contiguous blocks of ceil(B / G) frames
+    // The blocks register and release their frames independently of each other (find_groups_batch).  Frames of different
+    // blocks that overlap (a frame listed in two blocks, sliding windows across a block's end) would have their pages
+    // registered by two entries at once: such a call stages all its frames instead.
+    bool blocks_apart = true;
+    if (const size_t fbpp = (size_t)pix_bytes(format)) {
+        const size_t span = (size_t)(h - 1) * (size_t)(stride < 0 ? -stride : stride) * fbpp + (size_t)w * fbpp;
+        for (int i = 0; i < batch && blocks_apart && w > 0 && h > 0; ++i)
+            for (int j = (i / per + 1) * per; j < batch && blocks_apart; ++j) {
+                if (!frames[i] || !frames[j]) continue;
+                const uintptr_t a = reinterpret_cast<uintptr_t>(frames[i]) - (stride < 0 ? (size_t)(h - 1) * (size_t)(-stride) * fbpp : 0);
+                const uintptr_t b = reinterpret_cast<uintptr_t>(frames[j]) - (stride < 0 ? (size_t)(h - 1) * (size_t)(-stride) * fbpp : 0);
+                blocks_apart = a + span <= b || b + span <= a;
+            }
+    }
+    for (lr_context* p : c->peers) p->batch_no_register = !blocks_apart;
     std::vector<int> rc((size_t)n_devices, 0);
     std::vector<std::string> err((size_t)n_devices);
     auto run = [&](int i) {
@@ -357,7 +464,7 @@ int ctx_find_groups_batch_host_multi(lr_context* c, const int* devices, int n_de
         }
         // (a share of the staging threads each: they all copy out of the same host memory)
         const int nt = num_threads > 1 ? std::max(2, num_threads / std::min(n_devices, (batch + per - 1) / per)) : num_threads;
-        if (ctx_find_groups_batch_host(p, frames + b0, b1 - b0, w, h, stride, min_length, refine, nt,
+        if (ctx_find_groups_batch_host(p, frames + b0, format, b1 - b0, w, h, stride, min_length, refine, nt,
                                        out ? out + (size_t)b0 * capacity : nullptr, capacity, n_lines ? n_lines + b0 : nullptr, cfg,
                                        transforms ? transforms + b0 : nullptr)) {
             rc[(size_t)i] = 1;

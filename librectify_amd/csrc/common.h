@@ -80,11 +80,14 @@ void set_error(const std::string& msg);
 
 // ---- launchers (each enqueues on `s`, never synchronises unless stated) -----------------
 // kernels_filter.hip
-int launch_filter(const float* img, int w, int h, int stride, const FilterConsts& fc, float* dx, float* dy,
+// bytes of a pixel of an lr_pixel_format (0: not a format)
+inline int pix_bytes(int format) { return format == LR_PIX_U8 ? 1 : format == LR_PIX_U8X3 ? 3 : format == LR_PIX_F32 ? 4 : 0; }
+// (format: LR_PIX_F32 or LR_PIX_U8, stride in pixels of it)
+int launch_filter(const void* img, int format, int w, int h, int stride, const FilterConsts& fc, float* dx, float* dy,
                   uint8_t* dmask, uint64_t* cand, uint32_t* cand_count, uint32_t* tile_max, hipStream_t s);
 int filter_band_rows();  // image rows per band of the filter kernel
 int filter_band_last_row(int by);  // last image row band row `by` reads (its first is filter_band_rows() * by - 4)
-int launch_filter_rows(const float* img, int w, int h, int stride, const FilterConsts& fc, float* dx, float* dy,
+int launch_filter_rows(const void* img, int format, int w, int h, int stride, const FilterConsts& fc, float* dx, float* dy,
                        uint8_t* dmask, uint64_t* cand, uint32_t* cand_count, uint32_t* tile_max, int by_begin, int by_end,
                        hipStream_t s);
 struct FilterGeom {

@@ -86,7 +86,11 @@ struct FrameSlots {
     PinnedBuffer<float> stage[2];
     // Device frames whose rows span 4 GiB or more (the filter kernel addresses a frame with 32-bit byte offsets) are
     // first copied here, packed, on the context's stream (enqueue_filter).
+    // (of the frame's own format: an 8-bit frame is packed as bytes)
     DeviceBuffer<float> packed;
+    // An interleaved 8-bit frame (LR_PIX_U8X3) becomes luma / 256 here, by one launch of the prepare kernel at the
+    // frame's own size on the context's stream, and the fp32 filter reads this (enqueue_filter).
+    DeviceBuffer<float> luma;
 };
 
 // Batch calls on host frames: a ring of device frames (and, for pageable frames, of page-locked staging buffers)
@@ -135,6 +139,7 @@ struct lr_context {
     int crew_helpers = 0;
     bool sleep_in_wait = false;
     uint32_t fit_tag = 0;              // tag of the last component scan (kernels_fit.hip: component_offsets_kernel)
+    bool batch_no_register = false;    // a multi-device call whose blocks overlap: its frames are staged, none is page-locked in place
     int register_slow_calls = 0;       // batch calls still to go with the staging copy after pinning frames in place turned out slow (batch.hip: find_groups_batch)
     uint32_t select_tag = 0;           // tag of the last seed selection on this context (kernels_seeds.hip: seed_select_kernel)
     lramd::DeviceBuffer<float> maxmag;
@@ -249,21 +254,22 @@ struct ChtTrace {
 int ctx_estimate_line_pencils_cht(lr_context* c, std::vector<LineSegment>& lines, int max_models, float inlier_deg,
                                   float garbage_deg, int d, ChtTrace* trace);
 int ctx_refine(lr_context* c, std::vector<LineSegment>& lines);
-int ctx_find_groups_device(lr_context* c, const float* d_image, int w, int h, int stride, float min_length, bool refine,
+// (the frame entries below: `format` is the frames' lr_pixel_format, strides are in pixels of it)
+int ctx_find_groups_device(lr_context* c, const void* d_image, int format, int w, int h, int stride, float min_length, bool refine,
                            std::vector<LineSegment>& out);
-int ctx_find_groups_host(lr_context* c, const float* buffer, int w, int h, int stride, float min_length, bool refine,
+int ctx_find_groups_host(lr_context* c, const void* buffer, int format, int w, int h, int stride, float min_length, bool refine,
                          int num_threads, std::vector<LineSegment>& out);
-int ctx_find_groups_batch_device(lr_context* c, const float* d_images, size_t image_stride, int batch, int w, int h,
+int ctx_find_groups_batch_device(lr_context* c, const void* d_images, int format, size_t image_stride, int batch, int w, int h,
                                  int stride, float min_length, bool refine, LineSegment* out, int capacity, int* n_lines,
                                  const RectificationConfig* cfg, ImageTransform* transforms);
 // host-resident frames (any stride sign, pageable or page-locked): staged uploads overlap the kernels
-int ctx_find_groups_batch_host(lr_context* c, const float* const* frames, int batch, int w, int h, int stride,
+int ctx_find_groups_batch_host(lr_context* c, const void* const* frames, int format, int batch, int w, int h, int stride,
                                float min_length, bool refine, int num_threads, LineSegment* out, int capacity,
                                int* n_lines, const RectificationConfig* cfg, ImageTransform* transforms);
 // The same over several devices of this process ("one host thread + stream set per device"): frames are
 // dealt in contiguous blocks of ceil(batch / n_devices), block i to devices[i] (a device may be listed more than once:
 // every entry gets a lane set of its own), results land in the caller's arrays; no collective, it is one process.
-int ctx_find_groups_batch_host_multi(lr_context* c, const int* devices, int n_devices, const float* const* frames, int batch,
+int ctx_find_groups_batch_host_multi(lr_context* c, const int* devices, int n_devices, const void* const* frames, int format, int batch,
                                      int w, int h, int stride, float min_length, bool refine, int num_threads,
                                      LineSegment* out, int capacity, int* n_lines, const RectificationConfig* cfg,
                                      ImageTransform* transforms);

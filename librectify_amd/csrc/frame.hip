@@ -122,26 +122,52 @@ int prepare_frame(lr_context* c, int w, int h) {
     return 0;
 }
 
-int enqueue_filter(lr_context* c, const float* d_image, int w, int h, int stride) {
+// `format`: the frame's lr_pixel_format, `stride` in pixels of it.  fp32 and 8-bit gray frames are read by the filter kernel
+// itself (an instantiation each); an interleaved 8-bit frame first becomes luma / 256 in a buffer of the context.
+int enqueue_filter(lr_context* c, const void* d_image, int format, int w, int h, int stride) {
     if (prepare_frame(c, w, h)) return 1;
+    const size_t bpp = (size_t)pix_bytes(format);
+    if (bpp == 0 || d_image == nullptr || stride < w) {
+        set_error(bpp == 0 ? "unknown pixel format of the frames" : "launch_filter: bad geometry");
+        return 1;
+    }
+    const size_t npix = (size_t)w * h;
+    if (format == LR_PIX_U8X3) {
+        // three byte loads a row would keep thirty registers of the filter's prefetch queue busy; one
+        // launch of the prepare kernel at the frame's own size (weights exactly 1: the value is exactly luma / 256) instead
+        if (npix >= ((size_t)1 << 29)) {
+            set_error("launch_filter: image larger than 2^29 pixels is not supported (seed key packs index in 29 bits)");
+            return 1;
+        }
+        if (c->frames.luma.cap() < npix) {
+            LR_HIP(hipStreamSynchronize(c->stream));
+            if (c->frames.luma.grow(npix)) return 1;
+        }
+        if (ctx_prepare_frames(c, d_image, 0, 1, w, h, (size_t)stride * bpp, LR_PIX_U8X3, c->frames.luma.get(), 0, w, h, (size_t)w * sizeof(float)))
+            return 1;
+        d_image = c->frames.luma.get();
+        format = LR_PIX_F32;
+        stride = w;
+    }
     // The filter kernel addresses the frame with 32-bit byte offsets from its first row (buffer resource and row offsets,
     // kernels_filter.hip).  A caller's frame whose rows span 4 GiB or more -- a narrow crop of a large device mosaic -- is
-    // packed into a buffer of the context first, so the kernel sees the same pixels at stride w.
+    // packed into a buffer of the context first, so the kernel sees the same pixels at stride w.  The limit is one of BYTES:
+    // an 8-bit frame reaches it at four times the pixel span of an fp32 one, and is packed as bytes.
     // (a frame of 2^29 pixels or more is refused by launch_filter without the copy)
+    const size_t fbpp = (size_t)pix_bytes(format);
     if (stride > w && (uint64_t)w * (uint64_t)h < (1ull << 29) &&
-        ((uint64_t)(h - 1) * (uint64_t)stride + (uint64_t)w) * 4u >= (1ull << 32)) {
-        const size_t npix = (size_t)w * h;
-        if (c->frames.packed.cap() < npix) {
+        ((uint64_t)(h - 1) * (uint64_t)stride + (uint64_t)w) * fbpp >= (1ull << 32)) {
+        if (c->frames.packed.cap() < npix) {  // (sized in floats: a frame of bytes fits)
             LR_HIP(hipStreamSynchronize(c->stream));
             if (c->frames.packed.grow(npix)) return 1;
         }
-        LR_HIP(hipMemcpy2DAsync(c->frames.packed, (size_t)w * sizeof(float), d_image, (size_t)stride * sizeof(float),
-                                (size_t)w * sizeof(float), (size_t)h, hipMemcpyDeviceToDevice, c->stream));
+        LR_HIP(hipMemcpy2DAsync(c->frames.packed, (size_t)w * fbpp, d_image, (size_t)stride * fbpp,
+                                (size_t)w * fbpp, (size_t)h, hipMemcpyDeviceToDevice, c->stream));
         d_image = c->frames.packed;
         stride = w;
     }
     if (c->opt.timing_on) LR_HIP(hipEventRecord(c->ev[0], c->stream));
-    if (launch_filter(d_image, w, h, stride, c->fconsts, c->ws.dx, c->ws.dy, c->ws.dmask, c->ws.cand, c->ws.cand_count, c->ws.tile_max,
+    if (launch_filter(d_image, format, w, h, stride, c->fconsts, c->ws.dx, c->ws.dy, c->ws.dmask, c->ws.cand, c->ws.cand_count, c->ws.tile_max,
                       c->stream))
         return 1;
     if (c->opt.timing_on) LR_HIP(hipEventRecord(c->ev[1], c->stream));
@@ -341,7 +367,7 @@ struct TimingOn {
 
 int ctx_stage_filter(lr_context* c, const float* d_image, int w, int h, int stride) {
     TimingOn t(c);
-    if (enqueue_filter(c, d_image, w, h, stride)) return 1;
+    if (enqueue_filter(c, d_image, LR_PIX_F32, w, h, stride)) return 1;
     c->stage_valid[0] = true;
     return 0;
 }
@@ -421,7 +447,7 @@ int ctx_detect(lr_context* c, const float* d_image, int w, int h, int stride, st
 // detected from that copy: more seeds than the seed sort was sized for (the frame is repeated with room), and a flood
 // that needs more rounds than were enqueued blindly (the rounds are completed, the stages after the flood repeated).
 // With refine or PROSAC the raw segments go to the host after the fit, as before.
-int run_frame(lr_context* c, const float* d_image, int w, int h, int stride, float min_length, bool refine,
+int run_frame(lr_context* c, const void* d_image, int format, int w, int h, int stride, float min_length, bool refine,
               std::vector<LineSegment>& out, bool filter_enqueued) {
     out.clear();
     const double t_begin = now_ms();
@@ -452,7 +478,7 @@ int run_frame(lr_context* c, const float* d_image, int w, int h, int stride, flo
         c->frame_laps += 1;
         // (a frame that came from a host buffer has had its filter launched band by band as its rows arrived:
         // ctx_find_groups_host; a second lap takes the whole frame from the device slot)
-        if (!(filter_enqueued && attempt == 0) && enqueue_filter(c, d_image, w, h, stride)) return 1;
+        if (!(filter_enqueued && attempt == 0) && enqueue_filter(c, d_image, format, w, h, stride)) return 1;
         if (enqueue_seeds(c)) return 1;
         if (enqueue_flood(c)) return 1;
         if (enqueue_fit(c)) return 1;
@@ -545,9 +571,9 @@ int run_frame(lr_context* c, const float* d_image, int w, int h, int stride, flo
     return 0;
 }
 
-int ctx_find_groups_device(lr_context* c, const float* d_image, int w, int h, int stride, float min_length, bool refine,
+int ctx_find_groups_device(lr_context* c, const void* d_image, int format, int w, int h, int stride, float min_length, bool refine,
                            std::vector<LineSegment>& out) {
-    return run_frame(c, d_image, w, h, stride, min_length, refine, out);
+    return run_frame(c, d_image, format, w, h, stride, min_length, refine, out);
 }
 
 // find_line_segment_groups on a HOST buffer (the reference's only kind of input: interface.cpp:43-48, image.cpp:11-19),
@@ -560,8 +586,16 @@ int ctx_find_groups_device(lr_context* c, const float* d_image, int w, int h, in
 //  - the calling thread only drives (waits for "band k enqueued", launches its filter rows) and then enqueues the rest
 //    of the frame while the last transfers are still on the link.
 // What cannot overlap: everything after the filter needs the frame's largest magnitude, i.e. the whole frame.
-int ctx_find_groups_host(lr_context* c, const float* buffer, int w, int h, int stride, float min_length, bool refine,
+// Frames of any lr_pixel_format travel as bytes (bpp a pixel; upload bands of 4 MB are four times as many rows of an 8-bit
+// frame).  An interleaved frame goes up whole before its luma launch: the filter does not follow its bands.
+int ctx_find_groups_host(lr_context* c, const void* buffer_, int format, int w, int h, int stride, float min_length, bool refine,
                          int num_threads, std::vector<LineSegment>& out) {
+    const uint8_t* buffer = static_cast<const uint8_t*>(buffer_);
+    const int bpp = pix_bytes(format);
+    if (bpp == 0) {
+        set_error("unknown pixel format of the frames");
+        return 1;
+    }
     const double t_call = now_ms();
     LR_HIP(hipSetDevice(c->device));
     if (w < 5 || h < 5 || buffer == nullptr) {
@@ -576,8 +610,12 @@ int ctx_find_groups_host(lr_context* c, const float* buffer, int w, int h, int s
     hipStream_t up = c->copy_stream;
     const size_t npix = (size_t)w * h;
     const int slot = 0;
-    float* stage = nullptr;
-    if (ensure_frame_slot(c, slot, npix, !is_page_locked(buffer), &stage)) return 1;
+    uint8_t* stage = nullptr;
+    {
+        float* stage_f = nullptr;  // (slots and staging buffers are sized in floats: a frame of bytes fits)
+        if (ensure_frame_slot(c, slot, npix, !is_page_locked(buffer), &stage_f)) return 1;
+        stage = reinterpret_cast<uint8_t*>(stage_f);
+    }
     if (prepare_frame(c, w, h)) return 1;
     // Whatever way this call ends, nothing of it may still be on the link or the GPU when it returns with an error: the
     // next call would fill the staging buffer under a transfer that still reads it (ev_up is only recorded on success).
@@ -592,13 +630,14 @@ int ctx_find_groups_host(lr_context* c, const float* buffer, int w, int h, int s
             (void)hipGetLastError();
         }
     } drain{c, up};
-    const float* src = buffer;
+    const uint8_t* src = buffer;
     int sstride = stride;
     if (sstride < 0) {  // image.cpp:14-18: the same rows, addressed from the other end (no flip)
-        src = buffer + (std::ptrdiff_t)(h - 1) * sstride;
+        src = buffer + (std::ptrdiff_t)(h - 1) * sstride * bpp;
         sstride = -sstride;
     }
-    const size_t row_bytes = (size_t)w * sizeof(float);
+    const size_t row_bytes = (size_t)w * bpp, pitch = (size_t)sstride * bpp;
+    const bool follow = format != LR_PIX_U8X3;  // the filter reads the slot itself, band by band
     // Upload bands of 4 MB, the filter behind every band.  Smaller bands would start the link earlier (with eight staging
     // threads the first 4 MB bands are all ready at the same moment, 0.4 ms in), but every band costs about 18 us of its
     // own -- transfer submission, event, cross-stream wait -- on the stream that carries the frame: measured on 4K frames
@@ -615,7 +654,7 @@ int ctx_find_groups_host(lr_context* c, const float* buffer, int w, int h, int s
         if (e.ensure(hipEventDisableTiming)) return 1;
         c->band_ev.push_back(std::move(e));
     }
-    float* dst = c->frames.slot[slot];
+    uint8_t* dst = reinterpret_cast<uint8_t*>(c->frames.slot[slot].get());
     const int fb = filter_band_rows(), band_rows = (h + fb - 1) / fb;
     int by_next = 0;
     // filter rows that upload band k completes, behind that band's event
@@ -623,33 +662,34 @@ int ctx_find_groups_host(lr_context* c, const float* buffer, int w, int h, int s
         // the compute stream waits for EVERY band's own event: the bands are enqueued by several threads in no particular
         // order, so a later band's event says nothing about an earlier band
         LR_HIP(hipStreamWaitEvent(c->stream, c->band_ev[(size_t)k], 0));
+        if (!follow) return 0;
         const int last_row = std::min(h, (k + 1) * rpb) - 1;  // last image row on the device once bands 0..k are
         int by_end = by_next;
         while (by_end < band_rows && std::min(h - 1, filter_band_last_row(by_end)) <= last_row) ++by_end;
         if (k == n_bands - 1) by_end = band_rows;
-        if (launch_filter_rows(dst, w, h, w, c->fconsts, c->ws.dx, c->ws.dy, c->ws.dmask, c->ws.cand, c->ws.cand_count, c->ws.tile_max, by_next,
+        if (launch_filter_rows(dst, format, w, h, w, c->fconsts, c->ws.dx, c->ws.dy, c->ws.dmask, c->ws.cand, c->ws.cand_count, c->ws.tile_max, by_next,
                                by_end, c->stream))
             return 1;
         by_next = by_end;
         return 0;
     };
-    if (c->opt.timing_on) LR_HIP(hipEventRecord(c->ev[0], c->stream));
-    const int T = stage ? staging_threads(num_threads, npix * sizeof(float)) : 1;  // (the threads share every band: StagingCrew::work)
+    if (follow && c->opt.timing_on) LR_HIP(hipEventRecord(c->ev[0], c->stream));
+    const int T = stage ? staging_threads(num_threads, npix * bpp) : 1;  // (the threads share every band: StagingCrew::work)
     if (T <= 1) {
         // the calling thread alone (the reference's serial mode, or a page-locked source that needs no staging)
         for (int k = 0; k < n_bands; ++k) {
             const int r0 = k * rpb, r1 = std::min(h, r0 + rpb);
             if (stage) {
-                if (sstride == w) std::memcpy(stage + (size_t)r0 * w, src + (size_t)r0 * sstride, (size_t)(r1 - r0) * row_bytes);
+                if (sstride == w) std::memcpy(stage + (size_t)r0 * row_bytes, src + (size_t)r0 * pitch, (size_t)(r1 - r0) * row_bytes);
                 else
-                    for (int r = r0; r < r1; ++r) std::memcpy(stage + (size_t)r * w, src + (size_t)r * sstride, row_bytes);
-                LR_HIP(hipMemcpyAsync(dst + (size_t)r0 * w, stage + (size_t)r0 * w, (size_t)(r1 - r0) * row_bytes,
+                    for (int r = r0; r < r1; ++r) std::memcpy(stage + (size_t)r * row_bytes, src + (size_t)r * pitch, row_bytes);
+                LR_HIP(hipMemcpyAsync(dst + (size_t)r0 * row_bytes, stage + (size_t)r0 * row_bytes, (size_t)(r1 - r0) * row_bytes,
                                       hipMemcpyHostToDevice, up));
             } else if (sstride == w) {
-                LR_HIP(hipMemcpyAsync(dst + (size_t)r0 * w, src + (size_t)r0 * w, (size_t)(r1 - r0) * row_bytes,
+                LR_HIP(hipMemcpyAsync(dst + (size_t)r0 * row_bytes, src + (size_t)r0 * row_bytes, (size_t)(r1 - r0) * row_bytes,
                                       hipMemcpyHostToDevice, up));
             } else {
-                LR_HIP(hipMemcpy2DAsync(dst + (size_t)r0 * w, row_bytes, src + (size_t)r0 * sstride, (size_t)sstride * sizeof(float),
+                LR_HIP(hipMemcpy2DAsync(dst + (size_t)r0 * row_bytes, row_bytes, src + (size_t)r0 * pitch, pitch,
                                         row_bytes, (size_t)(r1 - r0), hipMemcpyHostToDevice, up));
             }
             LR_HIP(hipEventRecord(c->band_ev[(size_t)k], up));
@@ -666,7 +706,7 @@ int ctx_find_groups_host(lr_context* c, const float* buffer, int w, int h, int s
         StagingCrew* cr = c->crew.get();
         std::vector<std::atomic<int>> ready((size_t)n_bands);
         for (auto& a : ready) a.store(0, std::memory_order_relaxed);
-        const uint32_t g = cr->begin(dst, stage, src, w, h, sstride, up, c->band_ev.data(), ready.data(), band_bytes);
+        const uint32_t g = cr->begin(dst, stage, src, w, h, sstride, bpp, up, c->band_ev.data(), ready.data(), band_bytes);
         int rc = 0;
         for (int k = 0; k < n_bands && rc == 0; ++k) {
             int spins = 0, r;
@@ -685,11 +725,11 @@ int ctx_find_groups_host(lr_context* c, const float* buffer, int w, int h, int s
             return 1;
         }
     }
-    if (c->opt.timing_on) LR_HIP(hipEventRecord(c->ev[1], c->stream));
+    if (follow && c->opt.timing_on) LR_HIP(hipEventRecord(c->ev[1], c->stream));
     LR_HIP(hipEventRecord(c->ev_up[slot], up));
     static const bool call_debug = std::getenv("LIBRECTIFY_CALL_DEBUG") != nullptr;
     const double t_up = now_ms();
-    const int rc = run_frame(c, dst, w, h, w, min_length, refine, out, true);
+    const int rc = run_frame(c, dst, format, w, h, w, min_length, refine, out, follow);
     drain.ok = rc == 0;
     if (call_debug)
         std::fprintf(stderr, "host frame: bands staged, sent and filter launched in %.3f ms; rest of the frame enqueued in %.3f ms; waited %.3f ms; "

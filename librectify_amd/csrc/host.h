@@ -26,7 +26,7 @@ int ensure_group_capacity(lr_context* c, size_t n_lines);
 // frame.hip
 int enqueue_groups(lr_context* c, uint32_t line_cap, int max_models, float inlier_deg, float garbage_deg, int n_iter,
                    uint64_t seed, bool model_done = false, bool gather = false);
-int run_frame(lr_context* c, const float* d_image, int w, int h, int stride, float min_length, bool refine,
+int run_frame(lr_context* c, const void* d_image, int format, int w, int h, int stride, float min_length, bool refine,
               std::vector<LineSegment>& out, bool filter_enqueued = false);
 
 // upload.hip
@@ -34,7 +34,8 @@ int ensure_copy_stream(lr_context* c);
 bool is_page_locked(const void* p);
 int staging_threads(int num_threads, size_t frame_bytes = 0);
 void bind_this_thread_near(int device);
-int upload_rows(lr_context* c, float* dst, float* stage, const float* buffer, int w, int h, int stride, int num_threads,
+// (host frames travel as bytes: `bpp` bytes a pixel, strides in pixels, device and staging buffers packed at w * bpp a row)
+int upload_rows(lr_context* c, void* dst, void* stage, const void* buffer, int w, int h, int stride, int bpp, int num_threads,
                 hipStream_t up);
 int ensure_frame_slot(lr_context* c, int slot, size_t npix, bool pageable, float** stage);
 int ensure_upload_ring(lr_context* c, int R, size_t npix, bool staging);
@@ -54,10 +55,11 @@ struct StagingCrew {
     // Two job descriptors, used alternately (job number & 1): the one a late helper may still be reading is not the one
     // the uploader fills for the next frame, and the one after that is only filled when every band of this one is done.
     struct Job {
-        float* dst = nullptr;
-        float* stage = nullptr;
-        const float* src = nullptr;
-        int w = 0, h = 0, stride = 0, rows_per_band = 1, n_bands = 0;
+        uint8_t* dst = nullptr;
+        uint8_t* stage = nullptr;
+        const uint8_t* src = nullptr;
+        size_t row_bytes = 0, src_pitch = 0;  // bytes of a row, and from one source row to the next
+        int h = 0, rows_per_band = 1, n_bands = 0;
         hipStream_t up = nullptr;
         int pieces = 1;                       // row runs a band is copied in (by different threads)
         const Event* band_ev = nullptr;       // optional: recorded after each band's transfer is enqueued ...
@@ -88,14 +90,14 @@ struct StagingCrew {
     }
     void start(lr_context* ctx, int helpers);
     // stages one frame (rows as in upload_rows) and enqueues its transfers; returns when every band is enqueued
-    int run(float* dst_, float* stage_, const float* buffer, int w_, int h_, int stride_, hipStream_t up_,
+    int run(void* dst_, void* stage_, const void* buffer, int w_, int h_, int stride_, int bpp_, hipStream_t up_,
             size_t band_bytes = (size_t)4 << 20, int pieces_ = 1) {
-        const uint32_t g = begin(dst_, stage_, buffer, w_, h_, stride_, up_, nullptr, nullptr, band_bytes, pieces_);
+        const uint32_t g = begin(dst_, stage_, buffer, w_, h_, stride_, bpp_, up_, nullptr, nullptr, band_bytes, pieces_);
         work(g);
         return finish();
     }
     // the two halves of run(): publish the job (the helpers start on it), and wait for its last band
-    uint32_t begin(float* dst_, float* stage_, const float* buffer, int w_, int h_, int stride_, hipStream_t up_,
+    uint32_t begin(void* dst_, void* stage_, const void* buffer, int w_, int h_, int stride_, int bpp_, hipStream_t up_,
                    const Event* band_ev_, std::atomic<int>* ready_, size_t band_bytes = (size_t)4 << 20, int pieces_ = 0);
     int finish();
     ~StagingCrew();

@@ -5,7 +5,7 @@
 // masks of the reference (line_detector.cpp:41-49,126-182; filter.cpp:29-98,161-168) are
 // never materialised in HBM:
 //
-//   read  img                       4 B/px
+//   read  img                       4 B/px   (fp32 frames; 1 B/px for 8-bit frames, converted where they are consumed)
 //   write dx, dy                    8 B/px   (fp32, reused by flood + line fit)
 //   write dmask                     1 B/px   (bit b: pixel lies in dilate3x3(grad_bin == b))
 //   write peak candidates           sparse   (mag == max5x5 && mag > 0, with value, index, bin)
@@ -59,12 +59,14 @@ __device__ __forceinline__ uint32_t from_upper(uint32_t v) {
 
 constexpr int kLaneCols = 56;
 
+// Q: what a slot of the prefetch queue holds -- the pixel itself (fp32 frames) or the raw byte, zero-extended (8-bit frames)
+template <typename Q>
 struct Roll1 {
     float hx[5];       // row pass of image rows t-4..t (slot = row mod 5): derivative along x ...
     float hs[5];       // ... and smoothing along x
     float mag[5];
     uint32_t bits[5];  // 1 << bin
-    float q[10];       // prefetched image rows (nine steps ahead: loads share the in-order vmcnt with the stores)
+    Q q[10];           // prefetched image rows (nine steps ahead: loads share the in-order vmcnt with the stores)
 };
 
 // Unconditional load from a clamped position: pixels outside the image are never used by a valid output
@@ -89,8 +91,40 @@ __device__ __forceinline__ float load_px_in(const float* __restrict__ img, int s
     return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(row) + (unsigned)xcl * 4u);
 }
 
-template <int K10>
-__device__ __forceinline__ void lane_step(Roll1& R, const int t, const float* __restrict__ img, const int w, const int h,
+// The pixel formats of a frame.  The format only decides how a pixel gets into the prefetch
+// queue and how it leaves it: an fp32 pixel is loaded as a dword and used as it is; a byte is loaded as a byte (no
+// alignment of base or stride needed), kept raw for the nine rows it waits, and becomes float(byte) * (1/256) -- exact --
+// where the row pass consumes it (v_cvt_f32_ubyte0 and one multiply at the head of the step).
+template <int kFormat>
+struct Px;
+template <>
+struct Px<LR_PIX_F32> {
+    using Q = float;
+    static constexpr unsigned kBytes = 4u;
+    static __device__ __forceinline__ Q first(const void* __restrict__ img, int stride, int h, int yr, int xcl) {
+        return load_px(static_cast<const float*>(img), stride, h, yr, xcl);
+    }
+    static __device__ __forceinline__ Q fetch(const BufRsrc r_img, unsigned xcl, unsigned row) {
+        return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r_img, xcl * 4u, row * 4u, 0));
+    }
+    static __device__ __forceinline__ float value(Q q) { return q; }
+};
+template <>
+struct Px<LR_PIX_U8> {
+    using Q = uint32_t;
+    static constexpr unsigned kBytes = 1u;
+    static __device__ __forceinline__ Q first(const void* __restrict__ img, int stride, int h, int yr, int xcl) {
+        const int yy = min(max(yr, 0), h - 1);  // clamped: see load_px
+        return static_cast<const uint8_t*>(img)[(size_t)yy * stride + (unsigned)xcl];
+    }
+    static __device__ __forceinline__ Q fetch(const BufRsrc r_img, unsigned xcl, unsigned row) {
+        return (Q)__builtin_amdgcn_raw_buffer_load_b8(r_img, xcl, row, 0);
+    }
+    static __device__ __forceinline__ float value(Q q) { return (float)(q & 0xFFu) * (1.0f / 256.0f); }
+};
+
+template <int kFormat, int K10>
+__device__ __forceinline__ void lane_step(Roll1<typename Px<kFormat>::Q>& R, const int t, const void* __restrict__ img, const int w, const int h,
                                           const int stride, const FilterTaps& fc, float* __restrict__ dx_out,
                                           float* __restrict__ dy_out, uint8_t* __restrict__ dmask_out,
                                           uint64_t* __restrict__ cand_band, uint32_t& ncand, float& lmax, const int y0,
@@ -99,11 +133,10 @@ __device__ __forceinline__ void lane_step(Roll1& R, const int t, const float* __
                                           const BufRsrc r_dm) {
     constexpr int K = K10 % 5;
     if (t >= kBandSteps) return;  // wave-uniform (the unrolled loop runs in chunks of ten steps)
-    const float cur = R.q[K10];
+    const float cur = Px<kFormat>::value(R.q[K10]);
     {
         const int yy = min(max(y0 - 4 + t + 9, 0), h - 1);  // clamped: see load_px
-        R.q[(K10 + 9) % 10] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                  r_img, (unsigned)xcl * 4u, (unsigned)yy * (unsigned)stride * 4u, 0));
+        R.q[(K10 + 9) % 10] = Px<kFormat>::fetch(r_img, (unsigned)xcl, (unsigned)yy * (unsigned)stride);
     }
     // row pass of the new image row (oracle: conv_gradients)
     const float l1 = from_lower(cur), r1 = from_upper(cur);
@@ -175,7 +208,8 @@ __device__ __forceinline__ void lane_step(Roll1& R, const int t, const float* __
     }
 }
 
-__global__ __launch_bounds__(256) void filter_lanes_kernel(const float* __restrict__ img, int w, int h, int stride,
+template <int kFormat>
+__global__ __launch_bounds__(256) void filter_lanes_kernel(const void* __restrict__ img, int w, int h, int stride,
                                                            FilterTaps fc, float* __restrict__ dx_out,
                                                            float* __restrict__ dy_out, uint8_t* __restrict__ dmask_out,
                                                            uint64_t* __restrict__ cand, uint32_t* __restrict__ cand_count,
@@ -202,7 +236,8 @@ __global__ __launch_bounds__(256) void filter_lanes_kernel(const float* __restri
     const int x = bx * kLaneCols - 4 + lane;
     const int xcl = min(max(x, 0), w - 1);
     const bool useful = lane >= 4 && lane <= 59;
-    Roll1 R;
+    using P = Px<kFormat>;
+    Roll1<typename P::Q> R;
 #pragma unroll
     for (int i = 0; i < 5; ++i) {
         R.hx[i] = 0.f;
@@ -211,14 +246,14 @@ __global__ __launch_bounds__(256) void filter_lanes_kernel(const float* __restri
         R.bits[i] = 1u;
     }
 #pragma unroll
-    for (int i = 0; i < 10; ++i) R.q[i] = (i < 9) ? load_px(img, stride, h, y0 - 4 + i, xcl) : 0.f;
+    for (int i = 0; i < 10; ++i) R.q[i] = (i < 9) ? P::first(img, stride, h, y0 - 4 + i, xcl) : typename P::Q(0);
     uint64_t* cand_band = cand + (size_t)band * (kLaneCols * kBandRows);
     uint32_t ncand = 0;
     float lmax = 0.f;
     const uint32_t npx = (uint32_t)w * (uint32_t)h;
-    const BufRsrc r_img = make_rsrc(img, ((uint32_t)(h - 1) * (uint32_t)stride + (uint32_t)w) * 4u);
+    const BufRsrc r_img = make_rsrc(img, ((uint32_t)(h - 1) * (uint32_t)stride + (uint32_t)w) * P::kBytes);
     const BufRsrc r_dx = make_rsrc(dx_out, npx * 4u), r_dy = make_rsrc(dy_out, npx * 4u), r_dm = make_rsrc(dmask_out, npx);
-#define LR_STEP(k) lane_step<k>(R, t0 + k, img, w, h, stride, fc, dx_out, dy_out, dmask_out, cand_band, ncand, lmax, y0, x, xcl, lane, useful, r_img, r_dx, r_dy, r_dm)
+#define LR_STEP(k) lane_step<kFormat, k>(R, t0 + k, img, w, h, stride, fc, dx_out, dy_out, dmask_out, cand_band, ncand, lmax, y0, x, xcl, lane, useful, r_img, r_dx, r_dy, r_dm)
     // fully unrolled: across a loop back-edge the compiler can only wait for vmcnt(0), which would expose the
     // latency of every store in flight once per iteration.
     // (An instantiation without border tests, clamps and predicates for the bands away from the image border -- some 55
@@ -272,11 +307,17 @@ int filter_band_last_row(int by) { return kBandRows * by - 4 + kBandSteps - 1; }
 // The bands whose image rows lie in [row_begin, row_end) -- band row `by` reads the image rows 30 by - 4 .. 30 by + 33 --
 // i.e. the band rows [by_begin, by_end).  A frame that is still arriving over the link is filtered in a few such
 // launches, each as soon as its rows are on the device (frame.hip: ctx_find_groups_host).
-int launch_filter_rows(const float* img, int w, int h, int stride, const FilterConsts& fc, float* dx, float* dy,
+// `format`: LR_PIX_F32 or LR_PIX_U8 (an interleaved frame is turned into luma before it gets here: frame.hip, enqueue_filter);
+// `stride` in pixels of that format.
+int launch_filter_rows(const void* img, int format, int w, int h, int stride, const FilterConsts& fc, float* dx, float* dy,
                        uint8_t* dmask, uint64_t* cand, uint32_t* cand_count, uint32_t* tile_max, int by_begin, int by_end,
                        hipStream_t s) {
     if (w < 1 || h < 1 || stride < w) {
         set_error("launch_filter: bad geometry");
+        return 1;
+    }
+    if (format != LR_PIX_F32 && format != LR_PIX_U8) {
+        set_error("launch_filter: no filter kernel for this pixel format");
         return 1;
     }
     if ((uint64_t)w * (uint64_t)h >= (1ull << 29)) {
@@ -292,15 +333,19 @@ int launch_filter_rows(const float* img, int w, int h, int stride, const FilterC
     if (by_end <= by_begin) return 0;
     const int band_begin = by_begin * bands_x, band_end = by_end * bands_x;
     const int n_wg = ((band_end - band_begin + 3) / 4 + 7) / 8 * 8;  // a multiple of eight: see the XCD mapping in the kernel
-    hipLaunchKernelGGL(filter_lanes_kernel, dim3(n_wg), dim3(256), 0, s, img, w, h, stride, ft, dx, dy, dmask,
-                       cand, cand_count, tile_max, bands_x, band_begin, band_end);
+    if (format == LR_PIX_U8)
+        hipLaunchKernelGGL(filter_lanes_kernel<LR_PIX_U8>, dim3(n_wg), dim3(256), 0, s, img, w, h, stride, ft, dx, dy, dmask,
+                           cand, cand_count, tile_max, bands_x, band_begin, band_end);
+    else
+        hipLaunchKernelGGL(filter_lanes_kernel<LR_PIX_F32>, dim3(n_wg), dim3(256), 0, s, img, w, h, stride, ft, dx, dy, dmask,
+                           cand, cand_count, tile_max, bands_x, band_begin, band_end);
     LR_HIP(hipGetLastError());
     return 0;
 }
 
-int launch_filter(const float* img, int w, int h, int stride, const FilterConsts& fc, float* dx, float* dy,
+int launch_filter(const void* img, int format, int w, int h, int stride, const FilterConsts& fc, float* dx, float* dy,
                   uint8_t* dmask, uint64_t* cand, uint32_t* cand_count, uint32_t* tile_max, hipStream_t s) {
-    return launch_filter_rows(img, w, h, stride, fc, dx, dy, dmask, cand, cand_count, tile_max, 0, (h + kBandRows - 1) / kBandRows, s);
+    return launch_filter_rows(img, format, w, h, stride, fc, dx, dy, dmask, cand, cand_count, tile_max, 0, (h + kBandRows - 1) / kBandRows, s);
 }
 
 }  // namespace lramd

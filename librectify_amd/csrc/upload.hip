@@ -140,23 +140,24 @@ int ensure_copy_stream(lr_context* c) {
 }
 
 // Rows of a host frame (|stride| >= w; a negative stride addresses the same rows from the other end, reference
-// image.cpp:11-19) into a device buffer of w x h floats, on stream `up`.  Page-locked memory goes as it lies; pageable
+// image.cpp:11-19) into a device buffer of w x h pixels of `bpp` bytes, packed, on stream `up`.  Page-locked memory goes as it lies; pageable
 // memory goes through the page-locked buffer `stage` in 4 MB bands, copied by up to `num_threads` threads, each band's
 // transfer enqueued as soon as it is staged.  Nothing here waits for the transfers.
-int upload_rows(lr_context* c, float* dst, float* stage, const float* buffer, int w, int h, int stride, int num_threads,
+int upload_rows(lr_context* c, void* dst_, void* stage_, const void* buffer_, int w, int h, int stride, int bpp, int num_threads,
                        hipStream_t up) {
+    uint8_t* dst = static_cast<uint8_t*>(dst_);
+    uint8_t* stage = static_cast<uint8_t*>(stage_);
+    const uint8_t* buffer = static_cast<const uint8_t*>(buffer_);
     if (stride < 0) {
-        buffer = buffer + (std::ptrdiff_t)(h - 1) * stride;
+        buffer = buffer + (std::ptrdiff_t)(h - 1) * stride * bpp;
         stride = -stride;
     }
-    const size_t npix = (size_t)w * h;
-    const size_t row_bytes = (size_t)w * sizeof(float);
+    const size_t row_bytes = (size_t)w * bpp, pitch = (size_t)stride * bpp;
     if (stage == nullptr) {
         if (stride == w)  // one linear transfer: a pitched copy of the same bytes goes row by row
-            LR_HIP(hipMemcpyAsync(dst, buffer, npix * sizeof(float), hipMemcpyHostToDevice, up));
+            LR_HIP(hipMemcpyAsync(dst, buffer, row_bytes * h, hipMemcpyHostToDevice, up));
         else
-            LR_HIP(hipMemcpy2DAsync(dst, row_bytes, buffer, (size_t)stride * sizeof(float), row_bytes, (size_t)h,
-                                    hipMemcpyHostToDevice, up));
+            LR_HIP(hipMemcpy2DAsync(dst, row_bytes, buffer, pitch, row_bytes, (size_t)h, hipMemcpyHostToDevice, up));
         return 0;
     }
     const int rows_per_band = (int)std::max<size_t>(1, ((size_t)4 << 20) / row_bytes);
@@ -171,11 +172,11 @@ int upload_rows(lr_context* c, float* dst, float* stage, const float* buffer, in
         for (int k = t; k < n_bands; k += T) {
             const int r0 = k * rows_per_band, r1 = std::min(h, r0 + rows_per_band);
             if (stride == w) {
-                std::memcpy(stage + (size_t)r0 * w, buffer + (size_t)r0 * stride, (size_t)(r1 - r0) * row_bytes);
+                std::memcpy(stage + (size_t)r0 * row_bytes, buffer + (size_t)r0 * pitch, (size_t)(r1 - r0) * row_bytes);
             } else {
-                for (int r = r0; r < r1; ++r) std::memcpy(stage + (size_t)r * w, buffer + (size_t)r * stride, row_bytes);
+                for (int r = r0; r < r1; ++r) std::memcpy(stage + (size_t)r * row_bytes, buffer + (size_t)r * pitch, row_bytes);
             }
-            if (hipMemcpyAsync(dst + (size_t)r0 * w, stage + (size_t)r0 * w, (size_t)(r1 - r0) * row_bytes,
+            if (hipMemcpyAsync(dst + (size_t)r0 * row_bytes, stage + (size_t)r0 * row_bytes, (size_t)(r1 - r0) * row_bytes,
                                hipMemcpyHostToDevice, up) != hipSuccess)
                 rc[t] = 1;
         }
@@ -205,21 +206,21 @@ bool StagingCrew::work_one(uint32_t gen) {
         if ((uint32_t)(x >> 32) != gen || (uint32_t)(t >> 32) != gen || (uint32_t)x >= (uint32_t)t) return false;
         if (!next.compare_exchange_weak(x, x + 1, std::memory_order_acq_rel)) continue;
         const Job& j = jobs[gen & 1u];
-        const size_t row_bytes = (size_t)j.w * sizeof(float);
+        const size_t row_bytes = j.row_bytes;
         const int kP = j.pieces;
         const int rows_per_piece = (j.rows_per_band + kP - 1) / kP;
         const int k = (int)(uint32_t)x / kP, piece = (int)(uint32_t)x % kP;
         const int b0 = k * j.rows_per_band, b1 = std::min(j.h, b0 + j.rows_per_band);
         const int r0 = std::min(b1, b0 + piece * rows_per_piece), r1 = std::min(b1, r0 + rows_per_piece);
         if (r1 > r0) {
-            if (j.stride == j.w) {
-                stage_copy(j.stage + (size_t)r0 * j.w, j.src + (size_t)r0 * j.stride, (size_t)(r1 - r0) * row_bytes);
+            if (j.src_pitch == row_bytes) {
+                stage_copy(j.stage + (size_t)r0 * row_bytes, j.src + (size_t)r0 * j.src_pitch, (size_t)(r1 - r0) * row_bytes);
             } else {
-                for (int r = r0; r < r1; ++r) stage_copy(j.stage + (size_t)r * j.w, j.src + (size_t)r * j.stride, row_bytes);
+                for (int r = r0; r < r1; ++r) stage_copy(j.stage + (size_t)r * row_bytes, j.src + (size_t)r * j.src_pitch, row_bytes);
             }
         }
         if (pieces_left[gen & 1u][k].fetch_sub(1, std::memory_order_acq_rel) != 1) return true;  // not the band's last piece
-        bool ok = hipMemcpyAsync(j.dst + (size_t)b0 * j.w, j.stage + (size_t)b0 * j.w, (size_t)(b1 - b0) * row_bytes,
+        bool ok = hipMemcpyAsync(j.dst + (size_t)b0 * row_bytes, j.stage + (size_t)b0 * row_bytes, (size_t)(b1 - b0) * row_bytes,
                                  hipMemcpyHostToDevice, j.up) == hipSuccess;
         if (ok && j.band_ev) ok = hipEventRecord(j.band_ev[k], j.up) == hipSuccess;
         if (!ok) {
@@ -267,24 +268,25 @@ void StagingCrew::start(lr_context* ctx, int helpers) {
 }
 
 // the two halves of run(): publish the job (the helpers start on it), and wait for its last band
-uint32_t StagingCrew::begin(float* dst_, float* stage_, const float* buffer, int w_, int h_, int stride_, hipStream_t up_,
+uint32_t StagingCrew::begin(void* dst_, void* stage_, const void* buffer_, int w_, int h_, int stride_, int bpp_, hipStream_t up_,
                             const Event* band_ev_, std::atomic<int>* ready_, size_t band_bytes, int pieces_) {
+    const uint8_t* buffer = static_cast<const uint8_t*>(buffer_);
     if (stride_ < 0) {
-        buffer = buffer + (std::ptrdiff_t)(h_ - 1) * stride_;
+        buffer = buffer + (std::ptrdiff_t)(h_ - 1) * stride_ * bpp_;
         stride_ = -stride_;
     }
     const uint32_t g = job.load(std::memory_order_relaxed) + 1u;
     Job& j = jobs[g & 1u];
-    j.dst = dst_;
-    j.stage = stage_;
+    j.dst = static_cast<uint8_t*>(dst_);
+    j.stage = static_cast<uint8_t*>(stage_);
     j.src = buffer;
-    j.w = w_;
+    j.row_bytes = (size_t)w_ * bpp_;
+    j.src_pitch = (size_t)stride_ * bpp_;
     j.h = h_;
-    j.stride = stride_;
     j.up = up_;
     j.band_ev = band_ev_;
     j.ready = ready_;
-    j.rows_per_band = (int)std::max<size_t>(1, band_bytes / ((size_t)w_ * sizeof(float)));
+    j.rows_per_band = (int)std::max<size_t>(1, band_bytes / j.row_bytes);
     j.n_bands = (h_ + j.rows_per_band - 1) / j.rows_per_band;
     if (j.n_bands > kMaxBands) {  // (a frame of more than 1 GiB: fewer, larger bands)
         j.rows_per_band = (h_ + kMaxBands - 1) / kMaxBands;
@@ -321,8 +323,8 @@ StagingCrew::~StagingCrew() {
     for (auto& t : th) t.join();
 }
 
-// Device slot `slot` of at least npix floats and, for a pageable source, its page-locked staging buffer (*stage; nullptr for
-// a source that is page-locked already).  Growing either waits for whatever still uses the old one.
+// Device slot `slot` of at least npix floats (a frame of any format fits) and, for a pageable source, its page-locked
+// staging buffer (*stage; nullptr for a source that is page-locked already).  Growing either waits for whatever still uses the old one.
 int ensure_frame_slot(lr_context* c, int slot, size_t npix, bool pageable, float** stage) {
     hipStream_t up = c->copy_stream;
     if (c->frames.slot[slot].cap() < npix) {
@@ -355,7 +357,7 @@ int ctx_upload_frame(lr_context* c, int slot, const float* buffer, int w, int h,
     if (ensure_copy_stream(c)) return 1;
     float* stage = nullptr;
     if (ensure_frame_slot(c, slot, (size_t)w * h, !is_page_locked(buffer), &stage)) return 1;
-    if (upload_rows(c, c->frames.slot[slot], stage, buffer, w, h, stride, num_threads, c->copy_stream)) return 1;
+    if (upload_rows(c, c->frames.slot[slot], stage, buffer, w, h, stride, (int)sizeof(float), num_threads, c->copy_stream)) return 1;
     LR_HIP(hipEventRecord(c->ev_up[slot], c->copy_stream));
     return 0;
 }
