@@ -226,6 +226,20 @@ int lr_warp_perspective_device(lr_context* ctx, const void* d_src, size_t src_im
  * Fails cleanly on what the warp rejects and on any other option bit, out_width > width or out_height > height (no
  * upscaling), a destination pointer or stride that is not 4-byte aligned. */
 enum lr_warp_option { LR_WARP_PREPARE = 0x100 }; /* or-ed into `format` */
+/* LR_WARP_PACKED is the warp for a batch whose frames have their OWN output sizes (lr_rectification_homography gives every
+ * frame its own), still in one launch and into one destination region without padding to the largest.  The source is
+ * as ever: `batch` frames of width x height, frame b at d_src + b*src_image_bytes.  M is a HOST table of 13 doubles per
+ * frame: [0..8] the destination-to-source map, [9] and [10] that frame's out_width_b and out_height_b, [11] the byte
+ * offset of its output from d_dst, [12] its row stride in bytes.  Entries 9..12 are integers (at most 2^53): sizes >= 1,
+ * offset >= 0, stride >= out_width_b * bytes per pixel; for f32 offset and stride are multiples of 4 and d_dst is 4-byte
+ * aligned.  out_width and out_height are upper bounds of the frames' sizes, dst_image_bytes is the size of the whole
+ * region (every frame's offset + (out_height_b - 1) * stride + out_width_b * bpp lies within it) and dst_row_bytes is 0.
+ * Frame b's pixels are exactly those of the single-frame warp with its map and size; no other byte of the region is
+ * written, row padding and the gaps between frames included.  Fails cleanly (nothing launched, nothing written) on what
+ * the warp rejects, a table entry that is not an integer in its range, a frame outside the region, two frames whose
+ * extents [offset, end) overlap, more than 2^31 tiles of 64 x 16 pixels in total, LR_WARP_PACKED | LR_WARP_PREPARE and
+ * any other option bit.  (An enum of its own: enumerators are ints, and lr_warp_option's one line stays as it was.) */
+enum lr_warp_layout { LR_WARP_PACKED = 0x200 }; /* or-ed into `format` like lr_warp_option */
 
 /* ---- stage API (tests, bench) --------------------------------------------------------- */
 /* Stage 1: fused 5x5 derivative filter + magnitude + direction bin + dilated-bin mask +

@@ -61,6 +61,7 @@ BUF_DX, BUF_DY, BUF_DMASK, BUF_LABEL, BUF_SEED_IDX, BUF_SEED_BIN, BUF_SEED_THR, 
 T_UPLOAD, T_FILTER, T_SEEDS, T_FLOOD, T_FIT, T_RANSAC, T_TOTAL, T_FILTER_KERNEL, T_COUNT = range(9)
 PIX_U8, PIX_U8X3, PIX_F32 = range(3)  # enum lr_pixel_format
 WARP_PREPARE = 0x100  # enum lr_warp_option, or-ed into the format of lr_warp_perspective_device
+WARP_PACKED = 0x200  # enum lr_warp_layout, likewise: per-frame output sizes and places (warp_table)
 FRAMES_U8, FRAMES_U8X3, FRAMES_F32 = 0x100, 0x200, 0x300  # enum lr_frames_option, or-ed into `refine` of the frame entries
 
 
@@ -218,6 +219,42 @@ def prepared_size(width, height, max_size):
         return int(width), int(height), scale
     size = lambda n: max(1, int(np.floor(n * float(scale) + 0.5)))  # noqa: E731
     return size(int(width)), size(int(height)), scale
+
+
+def warp_table(Ms, sizes, bpp, align=4):
+    """The table of a packed warp (lr_warp_perspective_device with LR_WARP_PACKED) for frames laid out one after the
+    other in frame order.  Ms: (B, 3, 3) destination-to-source maps; sizes: B pairs (out_width, out_height); bpp: bytes
+    per pixel (1 u8, 3 u8x3, 4 f32); every row stride and every frame's start is rounded up to `align` bytes (for f32 a
+    multiple of 4).  Returns (table, total_bytes): table float64 (B, 13) -- the map, width, height, byte offset, row
+    stride -- and the bytes of the destination, which end with the last frame's last pixel.  Needs no GPU."""
+    Ms = np.asarray(Ms, np.float64)
+    if Ms.ndim == 2 and Ms.shape == (3, 3):
+        Ms = Ms[None]
+    if Ms.ndim != 3 or Ms.shape[1:] != (3, 3):
+        raise ValueError("warp_table: Ms is (B, 3, 3)")
+    if not np.isfinite(Ms).all():
+        raise ValueError("warp_table: M is not finite")
+    sz = np.asarray(sizes)
+    if sz.shape != (len(Ms), 2) or not np.issubdtype(sz.dtype, np.integer):
+        raise ValueError("warp_table: sizes is B pairs of integers (out_width, out_height)")
+    if len(sz) and int(sz.min()) < 1:
+        raise ValueError("warp_table: an output size below 1")
+    if bpp not in (1, 3, 4):
+        raise ValueError("warp_table: bpp is 1, 3 or 4")
+    if isinstance(align, bool) or not isinstance(align, (int, np.integer)) or align < 1 or (bpp == 4 and align % 4):
+        raise ValueError("warp_table: align is an integer >= 1, for f32 a multiple of 4")
+    align = int(align)
+    up = lambda v: (v + align - 1) // align * align  # noqa: E731
+    table = np.zeros((len(Ms), 13), np.float64)
+    table[:, :9] = Ms.reshape(-1, 9)
+    end = 0
+    for b, (ow, oh) in enumerate(sz.tolist()):
+        start, row = up(end), up(ow * bpp)
+        end = start + (oh - 1) * row + ow * bpp
+        table[b, 9:] = (ow, oh, start, row)
+    if end > 2 ** 53:
+        raise ValueError("warp_table: the destination is larger than 2^53 bytes")
+    return table, end
 
 
 def _frame_format(a, what):
@@ -396,6 +433,16 @@ class Context:
             raise ValueError("warp_perspective_device: M needs 9 values per frame")
         _check(lib().lr_warp_perspective_device(self._h, C.c_void_p(d_src), src_image_bytes, batch, width, height, src_row_bytes, fmt, _ptr(M), C.c_void_p(d_dst), dst_image_bytes, out_width, out_height, dst_row_bytes))
 
+    def warp_perspective_packed_device(self, d_src, src_image_bytes, batch, width, height, src_row_bytes, fmt, table, d_dst,
+                                       dst_bytes):
+        """lr_warp_perspective_device with LR_WARP_PACKED: one launch for `batch` device frames of one size whose outputs
+        have their own sizes and places in the dst_bytes at d_dst.  table: 13 doubles per frame (warp_table)."""
+        table = np.ascontiguousarray(table, np.float64).reshape(-1)
+        if table.size != 13 * int(batch) or batch < 1:
+            raise ValueError("warp_perspective_packed_device: the table has 13 values per frame")
+        out_w, out_h = (int(min(max(v, 1), 2 ** 31 - 1)) for v in np.nan_to_num(table.reshape(-1, 13)[:, 9:11]).max(axis=0))
+        _check(lib().lr_warp_perspective_device(self._h, C.c_void_p(d_src), src_image_bytes, batch, width, height, src_row_bytes, fmt | WARP_PACKED, _ptr(table), C.c_void_p(d_dst), dst_bytes, out_w, out_h, 0))
+
     def warp_perspective(self, array, M, out_size):
         """Warps one host frame (2-D uint8 or float32, or H x W x 3 uint8) by M (3x3, destination -> source) into an image
         of out_size = (width, height) on the GPU: upload, one launch, download.  Returns the (height, width[, 3]) array."""
@@ -506,6 +553,118 @@ class Context:
             self.device_free(d_src)
             if d_dst.value:
                 self.device_free(d_dst.value)
+
+    def rectify_batch_device(self, d_frames, batch, width, height, fmt, src_row_bytes=None, src_image_bytes=None,
+                             min_length=None, refine=False, cfg=None, clip=3.0, max_size=None, capacity=4096):
+        """rectify for `batch` 8-bit frames (fmt PIX_U8 or PIX_U8X3) of one width x height that are resident in HBM, frame
+        b at d_frames + b * src_image_bytes: with max_size one batched prepare_device, then the batch detector
+        (lr_find_line_segment_groups_batch_device on the 8-bit frames, or on the prepared ones; its own transforms are not
+        asked for), on the host what rectify does per frame (endpoints / scale, compute_rectification_transform for the
+        full size, rectification_homography), and the packed warp into one allocation: one launch when every frame has an
+        image, else one per run of consecutive frames that have one (a launch's source frames are consecutive), all into
+        the same region.  Returns (lines_list, transforms, table, d_out, total_bytes): row b of table (warp_table's layout,
+        rows and frames aligned to 4 bytes) says where frame b's image lies in the total_bytes at d_out, which stay on the
+        device and are the caller's to free (None when no frame has an image).  A frame whose homography cannot be formed
+        has an all-zero row and no bytes in d_out; its lines and transform are returned all the same.
+        capacity: lines per frame of the first detector pass.  A frame that has more makes the WHOLE batch's detector pass
+        run once more with room for the longest list, so no frame's lines are ever cut, at twice the detector's cost for
+        such a batch; a caller who expects more than 4096 lines in a frame passes a larger capacity."""
+        if fmt not in (PIX_U8, PIX_U8X3):
+            raise ValueError("rectify_batch_device: 8-bit frames, PIX_U8 or PIX_U8X3")
+        batch, w, h = int(batch), int(width), int(height)
+        if batch < 1:
+            raise ValueError("rectify_batch_device: batch < 1")
+        bpp = 3 if fmt == PIX_U8X3 else 1
+        srow = w * bpp if src_row_bytes is None else int(src_row_bytes)
+        simg = h * srow if src_image_bytes is None else int(src_image_bytes)
+        if cfg is None:
+            cfg = RectificationConfig(hmin=2.0)
+        d_small, d_out = C.c_void_p(), C.c_void_p()
+        try:
+            if max_size is not None:
+                pw, ph, scale = prepared_size(w, h, max_size)
+                _check(lib().lr_device_malloc(self._h, batch * pw * ph * 4, C.byref(d_small)))
+                self.prepare_device(d_frames, simg, batch, w, h, srow, fmt, d_small.value, pw * ph * 4, pw, ph, pw * 4)
+                self.synchronize()  # (the batch detector reads the frames on its lanes' streams, not after this one's work)
+                det = dict(dptr=d_small.value, image_stride=pw * ph, w=pw, h=ph, fmt=PIX_F32, stride=pw)
+            else:
+                if srow % bpp or simg % bpp:
+                    raise ValueError("rectify_batch_device: the detector takes strides in whole pixels")
+                pw, ph, scale = w, h, None
+                det = dict(dptr=d_frames, image_stride=simg // bpp, w=w, h=h, fmt=fmt, stride=srow // bpp)
+            if min_length is None:
+                min_length = max(pw, ph) / 100.0
+            capacity = max(int(capacity), 1)
+            n = np.zeros(batch, np.int32)
+            self.shape = (det["h"], det["w"])
+            while True:
+                out = np.zeros((batch, capacity), LINE_DTYPE)
+                # (no transforms: the library's would be the prepared size's; the full size's are computed below)
+                _check(lib().lr_find_line_segment_groups_batch_device(self._h, C.c_void_p(det["dptr"]), det["image_stride"], batch, det["w"], det["h"], det["stride"], min_length, frames_word(det["fmt"], refine), -1, _ptr(out), capacity, _ptr(n), C.byref(cfg), None))
+                if int(n.max()) <= capacity:
+                    break
+                capacity = int(n.max())  # (a frame's lines were cut: once more, with room for the longest list)
+            lines_list, transforms, good, Ms, sizes = [], [], [], [], []
+            for b in range(batch):
+                lines = out[b][: n[b]].copy()
+                if scale is not None:
+                    for k in ("x1", "y1", "x2", "y2"):  # back to the coordinates of the full frame, in float32 as the demo
+                        lines[k] = lines[k] / scale
+                t = compute_rectification_transform(lines, w, h, cfg)
+                lines_list.append(lines)
+                transforms.append(t)
+                try:
+                    _, M, size = rectification_homography(t, clip)
+                except LibrectifyError:
+                    continue  # (collinear corners, a size below 1, ...: this frame has no image)
+                good.append(b)
+                Ms.append(M)
+                sizes.append(size)
+            table = np.zeros((batch, 13), np.float64)
+            if not good:
+                return lines_list, transforms, table, None, 0
+            table[good], total = warp_table(np.stack(Ms), np.array(sizes, np.int64), bpp, 4)
+            _check(lib().lr_device_malloc(self._h, total, C.byref(d_out)))
+            # one launch; a frame without an image splits it, as a launch's frames are consecutive in the source
+            runs = np.split(np.array(good), np.flatnonzero(np.diff(good) != 1) + 1)
+            for run in runs:
+                b0 = int(run[0])
+                self.warp_perspective_packed_device(d_frames + b0 * simg, simg, len(run), w, h, srow, fmt, table[run], d_out.value, total)
+            res, d_out = d_out.value, C.c_void_p()
+            return lines_list, transforms, table, res, total
+        finally:
+            for p in (d_small, d_out):
+                if p.value:
+                    self.device_free(p.value)
+
+    def rectify_batch(self, frames_u8, min_length=None, refine=False, cfg=None, clip=3.0, max_size=None, capacity=4096):
+        """Context.rectify for a batch: frames_u8 is a uint8 array [B, H, W] or [B, H, W, 3], or a list of such frames of one
+        shape.  One upload, rectify_batch_device (one detector batch, the packed warp), one download.  Returns a
+        list of (lines, transform, warped), frame by frame what rectify returns for it; warped is None for a frame whose
+        homography cannot be formed."""
+        a = np.ascontiguousarray(frames_u8 if isinstance(frames_u8, np.ndarray) else np.stack([np.asarray(f) for f in frames_u8]))
+        if a.dtype != np.uint8 or a.ndim not in (3, 4) or (a.ndim == 4 and a.shape[3] != 3) or a.shape[0] < 1:
+            raise ValueError("rectify_batch: uint8 frames [B, H, W] or [B, H, W, 3]")
+        fmt, bpp = _frame_format(a[0], "rectify_batch")
+        batch, h, w = a.shape[:3]
+        d_src = self.device_upload(a)
+        d_out = None
+        try:
+            lines, tfs, table, d_out, total = self.rectify_batch_device(d_src, batch, w, h, fmt, min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, capacity=capacity)
+            packed = self.device_download(d_out, (total,), np.uint8) if d_out else None
+        finally:
+            self.device_free(d_src)
+            if d_out:
+                self.device_free(d_out)
+        res = []
+        for b in range(batch):
+            ow, oh, off, row = (int(v) for v in table[b, 9:])
+            img = None
+            if ow:
+                rows = np.lib.stride_tricks.as_strided(packed[off:], (oh, ow * bpp), (row, 1))
+                img = np.ascontiguousarray(rows).reshape((oh, ow) + a.shape[3:])
+            res.append((lines[b], tfs[b], img))
+        return res
 
     def set_seed_capacity(self, cap):
         lib().lr_set_seed_capacity(self._h, int(cap))

@@ -15,9 +15,17 @@
 //
 // The arithmetic is the canonical one of DESIGN.md section 3 (mirrored by tests/numpy_warp_ref.py): coordinates in
 // double without contraction (-ffp-contract=off), 5 fractional bits per axis, integer taps and weights.
+//
+// LR_WARP_PACKED (warp_packed_kernel): every frame has its own output size and its own place in one destination region.
+// The tile list is ragged -- frame b adds ceil(ow_b / 64) * ceil(oh_b / 16) tiles -- and is cut into the same eight runs.  A
+// workgroup finds its frame by a binary search of the tiles' prefix table; the tile index is the same for all its lanes, so
+// the search and the read of the frame's record (map, size, tiles per row, offset, stride) are scalar loads and compares.
+// The lanes' work inside a tile (warp_lane) is the single-size kernel's, statement for statement.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <utility>
+#include <vector>
 
 #include "context.h"
 
@@ -38,6 +46,21 @@ struct WarpArgs {
     int ow, oh;
     const double* M;  // 9 doubles per frame
     int tiles_x, tiles_per_frame, n_tiles;
+};
+
+// LR_WARP_PACKED: a frame's record, 13 doubles long like the caller's row it is made from
+struct PackedFrame {
+    double m[9];
+    unsigned long long offset, row_bytes;  // of its output, from the destination pointer
+    int ow, oh, tiles_x, pad;
+};
+static_assert(sizeof(PackedFrame) == 13 * sizeof(double), "a record per 13 doubles of the mirror");
+
+struct PackedArgs {
+    const uint8_t* src;
+    size_t src_image_bytes, src_row_bytes;
+    int w, h;
+    int batch, n_tiles;
 };
 
 // ((M0 x + M1 y) + M2) * Wq clamped to [INT_MIN, INT_MAX] and rounded half to even; a NaN fails both comparisons and
@@ -112,6 +135,76 @@ __device__ __forceinline__ uint32_t tap_u8x3(const uint8_t* p, bool in) {
 
 __device__ __forceinline__ uint32_t blend_u8(uint32_t a, uint32_t b, uint32_t c, uint32_t d, const Taps& t) {
     return (a * (uint32_t)t.w00 + b * (uint32_t)t.w01 + c * (uint32_t)t.w10 + d * (uint32_t)t.w11 + 512u) >> 10;
+}
+
+// LR_WARP_PACKED: one lane's four consecutive pixels (x0 .. x0 + 3, those below ow) of destination row y, whose first byte
+// is `out`.  The text of warp_perspective_kernel's loop body, which keeps its own copy so that its code is what it was.
+template <int kFormat>
+__device__ __forceinline__ void warp_lane(const double* m, const uint8_t* src, size_t src_row_bytes, int w, int h,
+                                          uint8_t* out, int ow, unsigned x0, unsigned y) {
+    const int n = min(4, ow - (int)x0);  // pixels of this lane inside the row
+
+    uint32_t res_u8 = 0;          // LR_PIX_U8: four bytes
+    uint32_t res_rgb[3] = {0, 0, 0};  // LR_PIX_U8X3: twelve bytes
+    float res_f[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const Taps t = taps_of(m, x0 + (unsigned)k, y);
+        const bool in0 = inside(t.iy, h), in1 = inside(t.iy + 1, h);
+        const uint8_t* row0 = src + (size_t)(in0 ? t.iy : 0) * src_row_bytes;
+        const uint8_t* row1 = src + (size_t)(in1 ? t.iy + 1 : 0) * src_row_bytes;
+        if (kFormat == LR_PIX_U8) {
+            uint32_t a, bb, c, d;
+            pair_u8(row0, in0, t.ix, w, a, bb);
+            pair_u8(row1, in1, t.ix, w, c, d);
+            res_u8 |= blend_u8(a, bb, c, d, t) << (8 * k);
+        } else if (kFormat == LR_PIX_U8X3) {
+            const bool ia = inside(t.ix, w), ib = inside(t.ix + 1, w);
+            const size_t oa = (size_t)(ia ? t.ix : 0) * 3, ob = (size_t)(ib ? t.ix + 1 : 0) * 3;
+            const uint32_t p00 = tap_u8x3(row0 + oa, in0 && ia), p01 = tap_u8x3(row0 + ob, in0 && ib);
+            const uint32_t p10 = tap_u8x3(row1 + oa, in1 && ia), p11 = tap_u8x3(row1 + ob, in1 && ib);
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                const int s = 8 * ch;
+                const uint32_t v = blend_u8((p00 >> s) & 0xFFu, (p01 >> s) & 0xFFu, (p10 >> s) & 0xFFu, (p11 >> s) & 0xFFu, t);
+                const int byte = 3 * k + ch;  // byte of the lane's twelve
+                res_rgb[byte >> 2] |= v << (8 * (byte & 3));
+            }
+        } else {
+            float a, bb, c, d;
+            pair_f32(row0, in0, t.ix, w, a, bb);
+            pair_f32(row1, in1, t.ix, w, c, d);
+            const float f00 = (float)t.w00 / 1024.0f, f01 = (float)t.w01 / 1024.0f;
+            const float f10 = (float)t.w10 / 1024.0f, f11 = (float)t.w11 / 1024.0f;
+            res_f[k] = ((a * f00 + bb * f01) + c * f10) + d * f11;
+        }
+    }
+
+    if (kFormat == LR_PIX_U8) {
+        uint8_t* p = out + x0;
+        if (n == 4 && (reinterpret_cast<uintptr_t>(p) & 3u) == 0) {
+            *reinterpret_cast<uint32_t*>(p) = res_u8;
+        } else {
+            for (int k = 0; k < n; ++k) p[k] = (uint8_t)(res_u8 >> (8 * k));
+        }
+    } else if (kFormat == LR_PIX_U8X3) {
+        uint8_t* p = out + (size_t)x0 * 3;
+        if (n == 4 && (reinterpret_cast<uintptr_t>(p) & 3u) == 0) {
+            uint32_t* q = reinterpret_cast<uint32_t*>(p);
+            q[0] = res_rgb[0];
+            q[1] = res_rgb[1];
+            q[2] = res_rgb[2];
+        } else {
+            for (int k = 0; k < 3 * n; ++k) p[k] = (uint8_t)(res_rgb[k >> 2] >> (8 * (k & 3)));
+        }
+    } else {
+        float* p = reinterpret_cast<float*>(out) + x0;
+        if (n == 4 && (reinterpret_cast<uintptr_t>(p) & 15u) == 0) {
+            *reinterpret_cast<float4*>(p) = make_float4(res_f[0], res_f[1], res_f[2], res_f[3]);
+        } else {
+            for (int k = 0; k < n; ++k) p[k] = res_f[k];
+        }
+    }
 }
 
 template <int kFormat>
@@ -200,6 +293,144 @@ __global__ __launch_bounds__(kBlock) void warp_perspective_kernel(WarpArgs g) {
     }
 }
 
+// The same tiles over a ragged list: everything up to x0 and y depends on the tile index alone, which is uniform across
+// the workgroup.  frames and start (batch + 1 entries: frame b owns the tiles [start[b], start[b + 1])) are arguments of
+// their own, restrict-qualified: the stores to dst cannot change them, so their uniform reads stay scalar loads.
+template <int kFormat>
+__global__ __launch_bounds__(kBlock) void warp_packed_kernel(PackedArgs g, const PackedFrame* __restrict__ frames,
+                                                             const int* __restrict__ start, uint8_t* __restrict__ dst) {
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    const unsigned lx = (unsigned)lane & 15u, row_in_tile = (unsigned)(wave * 4 + (lane >> 4));
+    const int per_xcd = (g.n_tiles + 7) / 8;
+    const int xcd = (int)(blockIdx.x & 7u), slots = (int)(gridDim.x >> 3);
+    for (int j = (int)(blockIdx.x >> 3); j < per_xcd; j += slots) {
+        const int tile = xcd * per_xcd + j;
+        if (tile >= g.n_tiles) return;
+        int b = 0, hi = g.batch;  // start[b] <= tile < start[hi]
+        while (hi - b > 1) {
+            const int mid = (b + hi) >> 1;
+            if (start[mid] <= tile) b = mid;
+            else hi = mid;
+        }
+        const PackedFrame* f = frames + b;
+        const int ow = f->ow, oh = f->oh, tiles_x = f->tiles_x;
+        const int r = tile - start[b];
+        const int ty = r / tiles_x, tx = r - ty * tiles_x;
+        const unsigned y = (unsigned)ty * kTileH + row_in_tile;
+        const unsigned x0 = (unsigned)tx * kTileW + lx * 4u;
+        if (y >= (unsigned)oh || x0 >= (unsigned)ow) continue;
+        const uint8_t* src = g.src + (size_t)b * g.src_image_bytes;
+        uint8_t* out = dst + (size_t)f->offset + (size_t)y * (size_t)f->row_bytes;
+        warp_lane<kFormat>(f->m, src, g.src_row_bytes, g.w, g.h, out, ow, x0, y);
+    }
+}
+
+// v as an integer in [lo, hi], if it is one
+bool table_integer(double v, double lo, double hi, uint64_t* out) {
+    if (!(v >= lo && v <= hi) || v != std::floor(v)) return false;
+    *out = (uint64_t)v;
+    return true;
+}
+
+// lr_warp_perspective_device with LR_WARP_PACKED: M is the table of 13 doubles per frame, out_width x out_height bound the
+// frames' sizes and dst_image_bytes is the size of the whole destination region
+int warp_packed(lr_context* c, const void* d_src, size_t src_image_bytes, int batch, int width, int height, size_t src_row_bytes,
+                int format, const double* T, void* d_dst, size_t dst_bytes, int out_width, int out_height, size_t dst_row_bytes) {
+    auto fail = [](const char* what) {
+        set_error(std::string("lr_warp_perspective_device: LR_WARP_PACKED: ") + what);
+        return 1;
+    };
+    if (!d_src || !d_dst || !T) return fail("null pointer (source, destination or table)");
+    if (batch < 1) return fail("batch < 1");
+    if (width < 1 || height < 1 || out_width < 1 || out_height < 1) return fail("source size or output bound below 1");
+    if (format != LR_PIX_U8 && format != LR_PIX_U8X3 && format != LR_PIX_F32) return fail("unknown pixel format");
+    if (dst_row_bytes != 0) return fail("dst_row_bytes must be 0 (every frame's stride is in the table)");
+    const size_t bpp = format == LR_PIX_U8 ? 1 : (format == LR_PIX_U8X3 ? 3 : 4);
+    if (src_row_bytes < (size_t)width * bpp) return fail("source row stride shorter than a row");
+    size_t src_span;
+    if (!frame_span(height, src_row_bytes, (size_t)width * bpp, &src_span)) return fail("frame larger than the address space");
+    if (batch > 1 && src_image_bytes < src_span) return fail("image stride shorter than a frame");
+    if (format == LR_PIX_F32) {
+        const uintptr_t bits = reinterpret_cast<uintptr_t>(d_src) | reinterpret_cast<uintptr_t>(d_dst) | src_row_bytes |
+                               (batch > 1 ? src_image_bytes : 0);
+        if (bits & 3u) return fail("f32 pointer or stride not 4-byte aligned");
+    }
+    // the table: every frame's map, size and place, and the tiles before it
+    constexpr double kExact = 9007199254740992.0;  // 2^53: integers up to it are doubles
+    std::vector<PackedFrame> rec((size_t)batch);
+    std::vector<int> start((size_t)batch + 1);
+    std::vector<std::pair<uint64_t, uint64_t>> extent((size_t)batch);  // [first byte, end)
+    int64_t n_tiles = 0;
+    for (int b = 0; b < batch; ++b) {
+        const double* t = T + (size_t)b * 13;
+        for (int i = 0; i < 9; ++i)
+            if (!std::isfinite(t[i])) return fail("M is not finite");
+        uint64_t ow, oh, off, row;
+        if (!table_integer(t[9], 1, out_width, &ow) || !table_integer(t[10], 1, out_height, &oh))
+            return fail("a frame's size is not an integer from 1 to out_width x out_height");
+        if (!table_integer(t[11], 0, kExact, &off)) return fail("a frame's offset is not an integer from 0 to 2^53");
+        if (!table_integer(t[12], (double)(ow * bpp), kExact, &row))
+            return fail("a frame's row stride is not an integer from a row's bytes to 2^53");
+        if (format == LR_PIX_F32 && ((off | row) & 3u)) return fail("f32 offset or stride not a multiple of 4");
+        uint64_t end;
+        if (__builtin_mul_overflow(oh - 1, row, &end) || __builtin_add_overflow(end, off, &end) ||
+            __builtin_add_overflow(end, ow * bpp, &end) || end > dst_bytes)
+            return fail("a frame reaches beyond dst_image_bytes");
+        extent[(size_t)b] = {off, end};
+        PackedFrame& f = rec[(size_t)b];
+        std::memcpy(f.m, t, sizeof f.m);
+        f.offset = off;
+        f.row_bytes = row;
+        f.ow = (int)ow;
+        f.oh = (int)oh;
+        f.tiles_x = (int)((ow + kTileW - 1) / kTileW);
+        f.pad = 0;
+        start[(size_t)b] = (int)n_tiles;
+        n_tiles += (int64_t)f.tiles_x * (int64_t)((oh + kTileH - 1) / kTileH);
+        if (n_tiles > 0x7FFFFFF0ll) return fail("output larger than 2^31 tiles of 64 x 16 pixels");
+    }
+    start[(size_t)batch] = (int)n_tiles;
+    std::sort(extent.begin(), extent.end());
+    for (int b = 1; b < batch; ++b)
+        if (extent[(size_t)b].first < extent[(size_t)b - 1].second) return fail("two frames' extents overlap");
+
+    // records, then the prefix table, in the mirror of the maps (in doubles: 13 a frame + the table's ints)
+    const size_t rec_doubles = (size_t)batch * 13, need = rec_doubles + ((size_t)batch + 2) / 2;
+    LR_HIP(hipSetDevice(c->device));
+    if (need > c->warp_m.cap()) {  // (grows: the buffers of a previous call may still be read by its launch)
+        LR_HIP(hipStreamSynchronize(c->stream));
+        if (c->warp_m.grow(need)) return 1;
+    }
+    if (c->ev_warp_m.ensure(hipEventDisableTiming)) return 1;
+    LR_HIP(hipEventSynchronize(c->ev_warp_m));  // the previous call's upload has read h_warp_m
+    std::memcpy(c->warp_m.h, rec.data(), rec_doubles * sizeof(double));
+    std::memcpy(c->warp_m.h + rec_doubles, start.data(), start.size() * sizeof(int));
+    const size_t up_bytes = rec_doubles * sizeof(double) + start.size() * sizeof(int);
+    LR_HIP(hipMemcpyAsync(c->warp_m.d, c->warp_m.h, up_bytes, hipMemcpyHostToDevice, c->stream));
+    LR_HIP(hipEventRecord(c->ev_warp_m, c->stream));
+
+    PackedArgs g;
+    g.src = static_cast<const uint8_t*>(d_src);
+    g.src_image_bytes = src_image_bytes;
+    g.src_row_bytes = src_row_bytes;
+    g.w = width;
+    g.h = height;
+    uint8_t* dst = static_cast<uint8_t*>(d_dst);
+    const PackedFrame* frames = reinterpret_cast<const PackedFrame*>(c->warp_m.d.get());
+    const int* tile_start = reinterpret_cast<const int*>(c->warp_m.d.get() + rec_doubles);
+    g.batch = batch;
+    g.n_tiles = (int)n_tiles;
+    const int grid = (int)std::min<int64_t>((n_tiles + 7) / 8 * 8, kMaxGrid);
+    if (format == LR_PIX_U8)
+        hipLaunchKernelGGL(warp_packed_kernel<LR_PIX_U8>, dim3(grid), dim3(kBlock), 0, c->stream, g, frames, tile_start, dst);
+    else if (format == LR_PIX_U8X3)
+        hipLaunchKernelGGL(warp_packed_kernel<LR_PIX_U8X3>, dim3(grid), dim3(kBlock), 0, c->stream, g, frames, tile_start, dst);
+    else
+        hipLaunchKernelGGL(warp_packed_kernel<LR_PIX_F32>, dim3(grid), dim3(kBlock), 0, c->stream, g, frames, tile_start, dst);
+    LR_HIP(hipGetLastError());
+    return 0;
+}
+
 }  // namespace
 
 int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_bytes, int batch, int width, int height,
@@ -211,6 +442,10 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
     };
     if (!c) return fail("no context");
     if (format & ~0xFF) {  // option bits above the pixel format
+        if ((format & ~0xFF) == LR_WARP_PACKED)
+            return warp_packed(c, d_src, src_image_bytes, batch, width, height, src_row_bytes, format & 0xFF, M, d_dst,
+                               dst_image_bytes, out_width, out_height, dst_row_bytes);
+        if ((format & ~0xFF) == (LR_WARP_PACKED | LR_WARP_PREPARE)) return fail("LR_WARP_PACKED together with LR_WARP_PREPARE");
         if ((format & ~0xFF) != LR_WARP_PREPARE) return fail("unknown option bits in format");
         return ctx_prepare_frames(c, d_src, src_image_bytes, batch, width, height, src_row_bytes, format & 0xFF, d_dst,
                                   dst_image_bytes, out_width, out_height, dst_row_bytes);
