@@ -107,6 +107,18 @@ int lr_find_line_segment_groups_batch_device(lr_context* ctx, const float* d_ima
                                              int width, int height, int stride, float min_length, int refine,
                                              int num_threads, LineSegment* out, int capacity, int* n_lines,
                                              const RectificationConfig* cfg, ImageTransform* transforms);
+/* The same entry with width == 0 && height == 0 (and batch >= 1): every frame has its OWN size.  d_images is then a HOST
+ * array of `batch` lr_frame records (cast to const float*), image_stride must be sizeof(lr_frame) (the layout check) and
+ * stride must be 0.  data: the frame's DEVICE address; stride: in pixels of the frames' format (the `refine` word's, fp32
+ * for a plain flag), >= width; min_length < 0: the call's min_length.  Output b goes to out + b*capacity, n_lines[b] is the
+ * number found (even above capacity), transforms[b] is compute_rectification_transform for width_b x height_b.  The whole
+ * table is checked before anything is launched (a null data, a size below 1, a stride below the width, a misaligned f32
+ * address fail the call); a frame below 5 x 5 is answered as elsewhere (format word: n_lines[b] = 0 and the no-lines
+ * transform; plain flag: the call fails).  Every frame's result is, bit for bit, lr_find_line_segment_groups_device's on
+ * that frame alone, whatever its position, the number of lanes and the lane that took it.  The lanes' workspaces are
+ * sized once, before the first frame, for the call's largest frame, and none is given back while the call runs.  The
+ * other five lr_find_line_segment_groups_* entries keep refusing 0 x 0. */
+typedef struct lr_frame { const void* data; int32_t width, height, stride; float min_length; } lr_frame; /* 24 bytes */
 
 /* Batch of `batch` HOST-resident frames of one size, frame b at frames + b*image_stride (elements), rows `stride`
  * elements apart (any sign, as image.cpp:11-19).  This is the reference's own kind of input, many frames at once.
@@ -240,6 +252,26 @@ enum lr_warp_option { LR_WARP_PREPARE = 0x100 }; /* or-ed into `format` */
  * extents [offset, end) overlap, more than 2^31 tiles of 64 x 16 pixels in total, LR_WARP_PACKED | LR_WARP_PREPARE and
  * any other option bit.  (An enum of its own: enumerators are ints, and lr_warp_option's one line stays as it was.) */
 enum lr_warp_layout { LR_WARP_PACKED = 0x200 }; /* or-ed into `format` like lr_warp_option */
+/* LR_WARP_RAGGED gives every frame its own SOURCE size and place as well: a folder of photographs (portrait and landscape,
+ * several cameras) in one source region, one launch.  M is a HOST table of 18 doubles per frame: [0..8] the
+ * destination-to-source map, [9] [10] out_width_b and out_height_b, [11] [12] byte offset of the output from d_dst and its
+ * row stride in bytes (all as LR_WARP_PACKED), [13] [14] the source's width_b and height_b, [15] [16] byte offset of the
+ * source from d_src and its row stride in bytes, [17] reserved, 0.  width x height and out_width x out_height are upper
+ * bounds of the frames' sizes, src_image_bytes and dst_image_bytes the sizes of the two regions, src_row_bytes and
+ * dst_row_bytes are 0.  Entries 9..16 are integers (at most 2^53) under LR_WARP_PACKED's rules for 9..12.  Outputs are laid
+ * out as with LR_WARP_PACKED (no two extents overlap; any order, gaps and padded rows); sources are only read, may share or
+ * overlap, and lie within [0, src_image_bytes).  Two spellings:
+ *   fmt | LR_WARP_RAGGED                     the bilinear warp: frame b is exactly the single-frame call with its source,
+ *                                            map and size; no other byte of the destination region is written;
+ *   fmt | LR_WARP_RAGGED | LR_WARP_PREPARE   the prepare step: entries 0..8 are ignored (they may be NaN), the destination
+ *                                            is f32 gray, frame b exactly the single-frame LR_WARP_PREPARE call for
+ *                                            width_b x height_b -> out_width_b x out_height_b (equal sizes: the pure
+ *                                            conversion); out sizes <= source sizes, destination offsets and strides
+ *                                            multiples of 4, d_dst 4-byte aligned; f32 sources likewise.
+ * Fails cleanly (nothing launched, nothing written) on LR_WARP_RAGGED | LR_WARP_PACKED, any other option bit, a non-zero
+ * [17], an entry that is not an integer in its range, a source or output outside its region, overlapping outputs, a
+ * non-finite map (the warp only), a non-zero src_row_bytes or dst_row_bytes, more than 2^31 tiles, the alignment rules. */
+enum lr_warp_sources { LR_WARP_RAGGED = 0x800 }; /* or-ed into `format` like lr_warp_option */
 
 /* ---- stage API (tests, bench) --------------------------------------------------------- */
 /* Stage 1: fused 5x5 derivative filter + magnitude + direction bin + dilated-bin mask +

@@ -57,11 +57,17 @@ class RectificationConfig(C.Structure):  # reference src/librectify.h:137-150
         super().__init__(tol, vmin, v_strategy, hmin, h_strategy)
 
 
+class Frame(C.Structure):  # lr_frame: a row of the batch detector's frame table (width == 0 && height == 0)
+    _fields_ = [("data", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("stride", C.c_int32),
+                ("min_length", C.c_float)]
+
+
 BUF_DX, BUF_DY, BUF_DMASK, BUF_LABEL, BUF_SEED_IDX, BUF_SEED_BIN, BUF_SEED_THR, BUF_MAXMAG, BUF_SEED_SIZE = range(9)
 T_UPLOAD, T_FILTER, T_SEEDS, T_FLOOD, T_FIT, T_RANSAC, T_TOTAL, T_FILTER_KERNEL, T_COUNT = range(9)
 PIX_U8, PIX_U8X3, PIX_F32 = range(3)  # enum lr_pixel_format
 WARP_PREPARE = 0x100  # enum lr_warp_option, or-ed into the format of lr_warp_perspective_device
 WARP_PACKED = 0x200  # enum lr_warp_layout, likewise: per-frame output sizes and places (warp_table)
+WARP_RAGGED = 0x800  # enum lr_warp_sources, likewise: per-frame source sizes and places as well (ragged_table)
 FRAMES_U8, FRAMES_U8X3, FRAMES_F32 = 0x100, 0x200, 0x300  # enum lr_frames_option, or-ed into `refine` of the frame entries
 
 
@@ -255,6 +261,51 @@ def warp_table(Ms, sizes, bpp, align=4):
     if end > 2 ** 53:
         raise ValueError("warp_table: the destination is larger than 2^53 bytes")
     return table, end
+
+
+def ragged_table(Ms, out_sizes, sources, bpp, out_bpp=None, align=4):
+    """The table of a ragged call (lr_warp_perspective_device with LR_WARP_RAGGED): warp_table's layout for the outputs plus
+    the four source columns.  Ms: (B, 3, 3) destination-to-source maps, or None (identity: the prepare step ignores them);
+    out_sizes: B pairs (out_width, out_height); sources: B rows (width, height, byte_offset, row_bytes) of the frames in
+    the source region; bpp: bytes per source pixel (1 u8, 3 u8x3, 4 f32); out_bpp: bytes per output pixel (default bpp;
+    4 for the prepare step, whose output is f32 gray).  Outputs lie one after the other in frame order, every row stride
+    and start rounded up to `align` bytes (a multiple of 4 for 4-byte outputs).  Returns (table, dst_bytes): table
+    float64 (B, 18).  Needs no GPU."""
+    if bpp not in (1, 3, 4):
+        raise ValueError("ragged_table: bpp is 1, 3 or 4")
+    out_bpp = bpp if out_bpp is None else out_bpp
+    if out_bpp not in (1, 3, 4):
+        raise ValueError("ragged_table: out_bpp is 1, 3 or 4")
+    src = np.asarray(sources)
+    if src.ndim != 2 or src.shape[1] != 4 or not np.issubdtype(src.dtype, np.integer):
+        raise ValueError("ragged_table: sources is B rows of integers (width, height, byte_offset, row_bytes)")
+    B = len(src)
+    if Ms is None:
+        Ms = np.broadcast_to(np.eye(3), (B, 3, 3))
+    try:
+        packed, total = warp_table(Ms, out_sizes, out_bpp, align)
+    except ValueError as e:
+        raise ValueError(str(e).replace("warp_table", "ragged_table")) from None
+    if len(packed) != B:
+        raise ValueError("ragged_table: as many sources as maps")
+    for w, h, off, row in src.tolist():
+        if w < 1 or h < 1:
+            raise ValueError("ragged_table: a source size below 1")
+        if off < 0 or row < w * bpp:
+            raise ValueError("ragged_table: a source offset below 0 or a row stride shorter than a row")
+        if bpp == 4 and (off % 4 or row % 4):
+            raise ValueError("ragged_table: f32 source offsets and strides are multiples of 4")
+        if off + (h - 1) * row + w * bpp > 2 ** 53:
+            raise ValueError("ragged_table: the source region is larger than 2^53 bytes")
+    table = np.zeros((B, 18), np.float64)
+    table[:, :13] = packed
+    table[:, 13:17] = src
+    return table, total
+
+
+def _source_extent(sources, bpp):
+    """bytes of the region that holds the sources (width, height, byte_offset, row_bytes)"""
+    return max(off + (h - 1) * row + w * bpp for w, h, off, row in sources)
 
 
 def _frame_format(a, what):
@@ -637,11 +688,173 @@ class Context:
                 if p.value:
                     self.device_free(p.value)
 
+    def _ragged_call(self, d_src, src_bytes, fmt_word, table, d_dst, dst_bytes, what):
+        table = np.ascontiguousarray(table, np.float64)
+        if table.ndim != 2 or table.shape[1] != 18 or len(table) < 1:
+            raise ValueError(what + ": the table has 18 values per frame")
+        bound = lambda col: int(min(max(np.nan_to_num(table[:, col]).max(), 1), 2 ** 31 - 1))  # noqa: E731
+        _check(lib().lr_warp_perspective_device(self._h, C.c_void_p(d_src), src_bytes, len(table), bound(13), bound(14), 0, fmt_word, _ptr(table), C.c_void_p(d_dst), dst_bytes, bound(9), bound(10), 0))
+
+    def warp_perspective_ragged_device(self, d_src, src_bytes, fmt, table, d_dst, dst_bytes):
+        """lr_warp_perspective_device with LR_WARP_RAGGED: one launch for frames that have their own source size and place
+        in the src_bytes at d_src and their own output size and place in the dst_bytes at d_dst.  table: 18 doubles per
+        frame (ragged_table)."""
+        self._ragged_call(d_src, src_bytes, fmt | WARP_RAGGED, table, d_dst, dst_bytes, "warp_perspective_ragged_device")
+
+    def prepare_ragged_device(self, d_src, src_bytes, fmt, table, d_dst, dst_bytes):
+        """lr_warp_perspective_device with LR_WARP_RAGGED | LR_WARP_PREPARE: one launch that prepares every frame of the
+        table from its own source size to its own output size (f32 gray; ragged_table with out_bpp=4; the maps are
+        ignored)."""
+        self._ragged_call(d_src, src_bytes, fmt | WARP_RAGGED | WARP_PREPARE, table, d_dst, dst_bytes, "prepare_ragged_device")
+
+    def _find_frames(self, table, fmt, min_length, refine, capacity, cfg):
+        """the batch detector on a frame table ((Frame * B) array): (out [B, capacity], n [B], transforms)"""
+        batch = len(table)
+        out = np.zeros((batch, capacity), LINE_DTYPE)
+        n = np.zeros(batch, np.int32)
+        tf = (ImageTransform * batch)()
+        cfg = cfg or RectificationConfig()
+        _check(lib().lr_find_line_segment_groups_batch_device(self._h, C.cast(table, C.c_void_p), C.sizeof(Frame), batch, 0, 0, 0, min_length, frames_word(fmt, refine), -1, _ptr(out), capacity, _ptr(n), C.byref(cfg), C.byref(tf)))
+        return out, n, tf
+
+    def find_line_segment_groups_frames_device(self, frames, fmt, min_length, refine=False, capacity=4096, cfg=None):
+        """The batch detector on resident frames that each have their own size (lr_find_line_segment_groups_batch_device
+        with a frame table).  frames: a (Frame * B) array, or B tuples (device address, width, height, stride in pixels of
+        fmt[, min_length]); a frame's min_length below 0 (the default) is the call's.  Returns (lines_list, transforms):
+        frame b's lines (at most `capacity` of them) and its ImageTransform for its own size."""
+        if not isinstance(frames, C.Array):
+            rows = [tuple(f) for f in frames]
+            frames = (Frame * len(rows))(*[Frame(int(f[0]), int(f[1]), int(f[2]), int(f[3]), float(f[4]) if len(f) > 4 else -1.0) for f in rows])
+        if len(frames) < 1:
+            raise ValueError("find_line_segment_groups_frames_device: no frames")
+        out, n, tf = self._find_frames(frames, fmt, min_length, refine, capacity, cfg)
+        return [out[b][: min(int(n[b]), capacity)].copy() for b in range(len(frames))], tf
+
+    def rectify_frames_device(self, d_base, sources, fmt, min_length=None, refine=False, cfg=None, clip=3.0, max_size=None,
+                              capacity=4096):
+        """rectify for 8-bit frames (fmt PIX_U8 or PIX_U8X3) that are resident in HBM and have their OWN sizes: frame b is
+        sources[b] = (width, height, byte_offset from d_base, row_bytes).  With max_size one ragged prepare
+        (prepare_ragged_device) to prepared_size(w_b, h_b, max_size) per frame, one detector call with a frame table (on
+        the 8-bit frames, or on the prepared ones; min_length float32(max(pw_b, ph_b) / 100) per frame unless given), on
+        the host what rectify does per frame, and the ragged warp into one allocation: one launch per run of consecutive
+        frames that have an image.  Returns (lines_list, transforms, table, d_out, total_bytes) like rectify_batch_device;
+        table is ragged_table's (18 columns; an all-zero row for a frame without an image).  capacity: as there."""
+        if fmt not in (PIX_U8, PIX_U8X3):
+            raise ValueError("rectify_frames_device: 8-bit frames, PIX_U8 or PIX_U8X3")
+        sources = [tuple(int(v) for v in s) for s in sources]
+        batch = len(sources)
+        if batch < 1 or any(len(s) != 4 for s in sources):
+            raise ValueError("rectify_frames_device: sources is B rows (width, height, byte_offset, row_bytes)")
+        bpp = 3 if fmt == PIX_U8X3 else 1
+        src_bytes = _source_extent(sources, bpp)
+        if cfg is None:
+            cfg = RectificationConfig(hmin=2.0)
+        d_small, d_out = C.c_void_p(), C.c_void_p()
+        try:
+            frames = (Frame * batch)()
+            if max_size is not None:
+                prepared = [prepared_size(w, h, max_size) for w, h, _, _ in sources]
+                ptable, small_bytes = ragged_table(None, np.array([p[:2] for p in prepared], np.int64), np.array(sources, np.int64), bpp, out_bpp=4)
+                _check(lib().lr_device_malloc(self._h, small_bytes, C.byref(d_small)))
+                self.prepare_ragged_device(d_base, src_bytes, fmt, ptable, d_small.value, small_bytes)
+                self.synchronize()  # (the batch detector reads the frames on its lanes' streams, not after this one's work)
+                det_fmt = PIX_F32
+                for b, (pw, ph, _) in enumerate(prepared):
+                    frames[b] = Frame(d_small.value + int(ptable[b, 11]), pw, ph, int(ptable[b, 12]) // 4, -1.0)
+                scales = [p[2] for p in prepared]
+            else:
+                if any(row % bpp for _, _, _, row in sources):
+                    raise ValueError("rectify_frames_device: the detector takes strides in whole pixels")
+                det_fmt = fmt
+                for b, (w, h, off, row) in enumerate(sources):
+                    frames[b] = Frame(d_base + off, w, h, row // bpp, -1.0)
+                scales = [None] * batch
+            for f in frames:
+                f.min_length = float(np.float32(max(f.width, f.height) / 100.0)) if min_length is None else float(min_length)
+            capacity = max(int(capacity), 1)
+            while True:
+                # (the library's transforms would be the prepared sizes'; the full sizes' are computed below)
+                out, n, _ = self._find_frames(frames, det_fmt, 0.0, refine, capacity, cfg)
+                if int(n.max()) <= capacity:
+                    break
+                capacity = int(n.max())  # (a frame's lines were cut: once more, with room for the longest list)
+            lines_list, transforms, good, Ms, sizes = [], [], [], [], []
+            for b, (w, h, _, _) in enumerate(sources):
+                lines = out[b][: n[b]].copy()
+                if scales[b] is not None:
+                    for k in ("x1", "y1", "x2", "y2"):  # back to the coordinates of the full frame, in float32 as the demo
+                        lines[k] = lines[k] / scales[b]
+                t = compute_rectification_transform(lines, w, h, cfg)
+                lines_list.append(lines)
+                transforms.append(t)
+                try:
+                    _, M, size = rectification_homography(t, clip)
+                except LibrectifyError:
+                    continue  # (collinear corners, a size below 1, ...: this frame has no image)
+                good.append(b)
+                Ms.append(M)
+                sizes.append(size)
+            table = np.zeros((batch, 18), np.float64)
+            if not good:
+                return lines_list, transforms, table, None, 0
+            table[good], total = ragged_table(np.stack(Ms), np.array(sizes, np.int64), np.array([sources[b] for b in good], np.int64), bpp, align=4)
+            _check(lib().lr_device_malloc(self._h, total, C.byref(d_out)))
+            for run in np.split(np.array(good), np.flatnonzero(np.diff(good) != 1) + 1):
+                self.warp_perspective_ragged_device(d_base, src_bytes, fmt, table[run], d_out.value, total)
+            res, d_out = d_out.value, C.c_void_p()
+            return lines_list, transforms, table, res, total
+        finally:
+            for p in (d_small, d_out):
+                if p.value:
+                    self.device_free(p.value)
+
+    def _rectify_mixed(self, frames, min_length, refine, cfg, clip, max_size, capacity):
+        """rectify_batch for a list of 8-bit frames of different shapes: all frames in one host buffer, one upload,
+        rectify_frames_device, one download"""
+        frames = [np.ascontiguousarray(f) for f in frames]
+        if any(f.dtype != np.uint8 or not (f.ndim == 2 or (f.ndim == 3 and f.shape[2] == 3)) for f in frames):
+            raise ValueError("rectify_batch: uint8 frames, H x W or H x W x 3")
+        if len({f.ndim for f in frames}) != 1:
+            raise ValueError("rectify_batch: the frames are all H x W or all H x W x 3")
+        fmt, bpp = _frame_format(frames[0], "rectify_batch")
+        sources, end = [], 0
+        for f in frames:
+            start = (end + 3) // 4 * 4
+            sources.append((f.shape[1], f.shape[0], start, f.shape[1] * bpp))
+            end = start + f.nbytes
+        host = np.zeros(end, np.uint8)
+        for f, (_, _, start, _) in zip(frames, sources):
+            host[start: start + f.nbytes] = f.reshape(-1)
+        d_src = self.device_upload(host)
+        d_out = None
+        try:
+            lines, tfs, table, d_out, total = self.rectify_frames_device(d_src, sources, fmt, min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, capacity=capacity)
+            packed = self.device_download(d_out, (total,), np.uint8) if d_out else None
+        finally:
+            self.device_free(d_src)
+            if d_out:
+                self.device_free(d_out)
+        res = []
+        for b, f in enumerate(frames):
+            ow, oh, off, row = (int(v) for v in table[b, 9:13])
+            img = None
+            if ow:
+                rows = np.lib.stride_tricks.as_strided(packed[off:], (oh, ow * bpp), (row, 1))
+                img = np.ascontiguousarray(rows).reshape((oh, ow) + f.shape[2:])
+            res.append((lines[b], tfs[b], img))
+        return res
+
     def rectify_batch(self, frames_u8, min_length=None, refine=False, cfg=None, clip=3.0, max_size=None, capacity=4096):
         """Context.rectify for a batch: frames_u8 is a uint8 array [B, H, W] or [B, H, W, 3], or a list of such frames of one
         shape.  One upload, rectify_batch_device (one detector batch, the packed warp), one download.  Returns a
         list of (lines, transform, warped), frame by frame what rectify returns for it; warped is None for a frame whose
-        homography cannot be formed."""
+        homography cannot be formed.  A list of frames of DIFFERENT shapes (all H x W or all H x W x 3) takes the
+        mixed-size pipeline: all frames in one host buffer, one upload, rectify_frames_device (one ragged prepare, one
+        detector call with a frame table, one ragged warp launch), one download -- frame by frame what rectify returns."""
+        if not isinstance(frames_u8, np.ndarray):
+            frames_u8 = [np.asarray(f) for f in frames_u8]
+            if len({f.shape for f in frames_u8}) > 1:
+                return self._rectify_mixed(frames_u8, min_length, refine, cfg, clip, max_size, capacity)
         a = np.ascontiguousarray(frames_u8 if isinstance(frames_u8, np.ndarray) else np.stack([np.asarray(f) for f in frames_u8]))
         if a.dtype != np.uint8 or a.ndim not in (3, 4) or (a.ndim == 4 and a.shape[3] != 3) or a.shape[0] < 1:
             raise ValueError("rectify_batch: uint8 frames [B, H, W] or [B, H, W, 3]")

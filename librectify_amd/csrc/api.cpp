@@ -101,6 +101,8 @@ int copy_out(const std::vector<LineSegment>& v, LineSegment* out, int capacity, 
 
 }  // namespace
 
+static_assert(sizeof(lr_frame) == 24, "lr_frame is 24 bytes: the layout check of the frame table");
+
 extern "C" {
 
 // ---- the reference's six entry points ----------------------------------------------------
@@ -275,6 +277,16 @@ int lr_find_line_segment_groups_batch_device(lr_context* ctx, const float* d_ima
     try {
         (void)num_threads;
         const FramesWord fw(refine);
+        if (width == 0 && height == 0 && batch >= 1) {  // every frame its own size: d_images is a HOST table of lr_frame
+            if (image_stride != sizeof(lr_frame) || stride != 0) {
+                set_error(image_stride != sizeof(lr_frame)
+                              ? "lr_find_line_segment_groups_batch_device: frame table: image_stride must be sizeof(lr_frame)"
+                              : "lr_find_line_segment_groups_batch_device: frame table: stride must be 0");
+                return 1;
+            }
+            return ctx_find_groups_frames_device(ctx, reinterpret_cast<const lr_frame*>(d_images), fw.format, fw.tagged, batch,
+                                                 min_length, fw.refine, out, capacity, n_lines, cfg, transforms);
+        }
         if (below_filter(fw, d_images, width, height)) return nothing_found(batch, width, height, n_lines, cfg, transforms);
         return ctx_find_groups_batch_device(ctx, d_images, fw.format, image_stride, batch, width, height, stride, min_length,
                                             fw.refine, out, capacity, n_lines, cfg, transforms);

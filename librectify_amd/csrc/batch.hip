@@ -8,6 +8,49 @@
 
 namespace lramd {
 
+// The lanes of a batch call: the caller's context and S - 1 workers of its own (kept from call to call), set up for the
+// length of the call; lanes_done gives the caller's context its own settings back.
+static int lanes_begin(lr_context* c, int S, bool host_frames, std::vector<lr_context*>& lanes) {
+    while ((int)c->workers.size() < S - 1) {
+        lr_context* wc = nullptr;
+        if (ctx_create(c->device, &wc)) return 1;
+        c->workers.push_back(wc);
+    }
+    lanes.push_back(c);
+    for (int i = 0; i < S - 1; ++i) lanes.push_back(c->workers[i]);
+    for (lr_context* l : lanes) {
+        l->opt = c->opt;  // (flood_staged: off unless lr_set_flood_staged: +6 % in round 1, -3 % now, DESIGN.md §7)
+        // What only the lanes of a call run with (lane 0 is the caller's own context: it gets its own back below).
+        // Re-walks from the logs: in the lanes only for walks of 32 tiles and more, behind a walk of 24 tiles.  With the
+        // thresholds of a single call (16 / 12) round two's work on thousands of small logs is work on top, and S frames in
+        // flight gain nothing from shorter rounds: 10.34 -> 10.2 Gpix/s; with these the long re-walks go and little is added:
+        // 10.34 -> 10.55 (profiles/r04_flood_logs.txt section 14).
+        l->flood_log_min = S == 1 ? 0 : 32;
+        l->flood_log_walk = S == 1 ? 0 : 24;
+        // ... and without the logs of second-tier walks: their kernel is a launch of 1 024 threads and 142 KB of LDS a
+        // workgroup that has to find whole CUs beside the other lanes' kernels (2.7 launches a frame x 52 us in
+        // profiles/r04_kernel_stats.csv): 10.67 -> 10.76 Gpix/s without (three repetitions each).
+        l->flood_logbig_off = S > 1;
+        // (a lane's thread has nothing else to do while its frame is in flight, but the call's staging threads need the cores:
+        // a lane looks at the words every 20 microseconds instead of spinning -- the other lanes keep the GPU busy)
+        // Measured (profiles/r04_flood_logs.txt, section 9): 9.93 -> 10.29 Gpix/s from pageable frames, 11.7 -> 12.1 from
+        // resident ones -- a frame of a lane no longer drags 3-4 rounds of empty launches through its stream.
+        l->flood_jit_sleep_us = S == 1 ? 0 : 20;
+        // LIBRECTIFY_LANES_SLEEP: the lanes sleep on an event instead of spinning in hipStreamSynchronize, for hosts
+        // short of cores (on the 16-core share of a one-GPU box: pageable frames equal, page-locked ones 5 % slower)
+        static const bool sleep_env = std::getenv("LIBRECTIFY_LANES_SLEEP") != nullptr;
+        l->sleep_in_wait = sleep_env && host_frames;
+    }
+    return 0;
+}
+
+static void lanes_done(lr_context* c, const std::vector<lr_context*>& lanes) {
+    for (lr_context* l : lanes) l->sleep_in_wait = false;
+    c->flood_logbig_off = false;
+    c->flood_log_min = c->flood_log_walk = 0;
+    c->flood_jit_sleep_us = 0;
+}
+
 // Batch of independent frames: the stages of one frame are latency-bound (flood rounds,
 // host round trips), so several frames are kept in flight, one host thread + context + HIP stream each ("lanes");
 // frames are handed out dynamically (they differ in cost, and with a fixed assignment the batch ends on one lane).
@@ -34,37 +77,8 @@ static int find_groups_batch(lr_context* c, const void* d_images_, int format, s
         return 1;
     }
     const int S = std::max(1, std::min(c->opt.batch_streams, batch));
-    while ((int)c->workers.size() < S - 1) {
-        lr_context* wc = nullptr;
-        if (ctx_create(c->device, &wc)) return 1;
-        c->workers.push_back(wc);
-    }
     std::vector<lr_context*> lanes;
-    lanes.push_back(c);
-    for (int i = 0; i < S - 1; ++i) lanes.push_back(c->workers[i]);
-    for (lr_context* l : lanes) {
-        l->opt = c->opt;  // (flood_staged: off unless lr_set_flood_staged: +6 % in round 1, -3 % now, DESIGN.md §7)
-        // What only the lanes of a call run with (lane 0 is the caller's own context: it gets its own back below).
-        // Re-walks from the logs: in the lanes only for walks of 32 tiles and more, behind a walk of 24 tiles.  With the
-        // thresholds of a single call (16 / 12) round two's work on thousands of small logs is work on top, and S frames in
-        // flight gain nothing from shorter rounds: 10.34 -> 10.2 Gpix/s; with these the long re-walks go and little is added:
-        // 10.34 -> 10.55 (profiles/r04_flood_logs.txt section 14).
-        l->flood_log_min = S == 1 ? 0 : 32;
-        l->flood_log_walk = S == 1 ? 0 : 24;
-        // ... and without the logs of second-tier walks: their kernel is a launch of 1 024 threads and 142 KB of LDS a
-        // workgroup that has to find whole CUs beside the other lanes' kernels (2.7 launches a frame x 52 us in
-        // profiles/r04_kernel_stats.csv): 10.67 -> 10.76 Gpix/s without (three repetitions each).
-        l->flood_logbig_off = S > 1;
-        // (a lane's thread has nothing else to do while its frame is in flight, but the call's staging threads need the cores:
-        // a lane looks at the words every 20 microseconds instead of spinning -- the other lanes keep the GPU busy)
-        // Measured (profiles/r04_flood_logs.txt, section 9): 9.93 -> 10.29 Gpix/s from pageable frames, 11.7 -> 12.1 from
-        // resident ones -- a frame of a lane no longer drags 3-4 rounds of empty launches through its stream.
-        l->flood_jit_sleep_us = S == 1 ? 0 : 20;
-        // LIBRECTIFY_LANES_SLEEP: the lanes sleep on an event instead of spinning in hipStreamSynchronize, for hosts
-        // short of cores (on the 16-core share of a one-GPU box: pageable frames equal, page-locked ones 5 % slower)
-        static const bool sleep_env = std::getenv("LIBRECTIFY_LANES_SLEEP") != nullptr;
-        l->sleep_in_wait = sleep_env && h_frames != nullptr;
-    }
+    if (lanes_begin(c, S, h_frames != nullptr, lanes)) return 1;
     // ---- the upload ring
     const size_t npix = (size_t)w * h;
     int R = 0;
@@ -369,10 +383,7 @@ static int find_groups_batch(lr_context* c, const void* d_images_, int format, s
         for (int i = 0; i < batch; ++i)
             if (reg_ready[(size_t)i].load(std::memory_order_acquire) == 1 && hipHostUnregister(reinterpret_cast<void*>(plan[(size_t)i].lo)) != hipSuccess)
                 (void)hipGetLastError();  // (nothing to be done about it, and the caller's thread must not find it in its next call)
-    for (lr_context* l : lanes) l->sleep_in_wait = false;
-    c->flood_logbig_off = false;
-    c->flood_log_min = c->flood_log_walk = 0;
-    c->flood_jit_sleep_us = 0;
+    lanes_done(c, lanes);
     for (int si = 0; si < S; ++si)
         if (rc[si]) {
             set_error(err[si]);
@@ -390,6 +401,102 @@ int ctx_find_groups_batch_device(lr_context* c, const void* d_images, int format
                                  const RectificationConfig* cfg, ImageTransform* transforms) {
     return find_groups_batch(c, d_images, format, image_stride, nullptr, batch, w, h, stride, min_length, refine, -1, out,
                              capacity, n_lines, cfg, transforms);
+}
+
+// The device batch with a frame table (lr_find_line_segment_groups_batch_device with width == 0 && height == 0): every frame
+// has its own address, size, stride and min_length.  The lanes take the frames dynamically, as above, and run the
+// single-frame path on each; what is the call's own is the workspace: every lane grows ONCE, before the first frame, to the
+// largest pixel count and the largest tile count among the frames (not necessarily one frame's), and for the length of the
+// call no lane counts small frames towards giving its workspace back (ctx_ensure_image_capacity) -- nothing is freed or
+// reallocated while another lane's kernels run.
+int ctx_find_groups_frames_device(lr_context* c, const lr_frame* frames, int format, bool tagged, int batch, float min_length,
+                                  bool refine, LineSegment* out, int capacity, int* n_lines, const RectificationConfig* cfg,
+                                  ImageTransform* transforms) {
+    auto bad = [](int b, const char* what) {
+        set_error("lr_find_line_segment_groups_batch_device: frame " + std::to_string(b) + " of the table: " + what);
+        return 1;
+    };
+    const size_t bpp = (size_t)pix_bytes(format);
+    if (bpp == 0) {
+        set_error("unknown pixel format of the frames");
+        return 1;
+    }
+    if (frames == nullptr) {
+        set_error("lr_find_line_segment_groups_batch_device: no frame table");
+        return 1;
+    }
+    // the whole table, before anything is launched
+    size_t max_pix = 0;
+    int max_tiles = 0;
+    for (int b = 0; b < batch; ++b) {
+        const lr_frame& f = frames[b];
+        if (f.data == nullptr) return bad(b, "null data");
+        if (f.width < 1 || f.height < 1) return bad(b, "size below 1");
+        if (f.stride < f.width) return bad(b, "stride smaller than the width");
+        if (format == LR_PIX_F32 && (reinterpret_cast<uintptr_t>(f.data) & 3u)) return bad(b, "f32 address not 4-byte aligned");
+        if (f.width < 5 || f.height < 5) {
+            if (!tagged) return bad(b, "image smaller than the 5x5 filter");
+            continue;  // (answered below without a launch)
+        }
+        max_pix = std::max(max_pix, (size_t)f.width * (size_t)f.height);
+        max_tiles = std::max(max_tiles, filter_geometry(f.width, f.height).n_tiles);
+    }
+    const RectificationConfig def;
+    const int S = std::max(1, std::min(c->opt.batch_streams, batch));
+    std::vector<lr_context*> lanes;
+    if (lanes_begin(c, S, false, lanes)) return 1;
+    LR_HIP(hipSetDevice(c->device));
+    int grow_rc = 0;
+    for (lr_context* l : lanes) {
+        l->keep_workspace = true;
+        if (!grow_rc && max_pix) grow_rc = ctx_reserve_workspace(l, max_pix, max_tiles);
+    }
+    std::atomic<int> next_frame{0}, abort_all{0};
+    std::vector<int> rc(S, 0);
+    std::vector<std::string> err(S);
+    auto work = [&](int si) {
+        lr_context* l = lanes[si];
+        auto fail = [&]() {
+            rc[si] = 1;
+            err[si] = get_error();
+            abort_all.store(1);
+        };
+        if (si > 0 && hipSetDevice(c->device) != hipSuccess) {
+            set_error("hipSetDevice failed");
+            return fail();
+        }
+        for (int b = next_frame.fetch_add(1, std::memory_order_relaxed); b < batch && !abort_all.load(std::memory_order_relaxed);
+             b = next_frame.fetch_add(1, std::memory_order_relaxed)) {
+            const lr_frame& f = frames[b];
+            std::vector<LineSegment> res;
+            if (f.width >= 5 && f.height >= 5 &&
+                ctx_find_groups_device(l, f.data, format, f.width, f.height, f.stride, f.min_length < 0.f ? min_length : f.min_length,
+                                       refine, res))
+                return fail();
+            const int n = (int)res.size();
+            if (n_lines) n_lines[b] = n;
+            if (out && capacity > 0)
+                std::memcpy(out + (size_t)b * capacity, res.data(), sizeof(LineSegment) * (size_t)std::min(n, capacity));
+            if (transforms)
+                transforms[b] = rectification_transform(res.data(), std::min(n, capacity > 0 ? capacity : n), f.width, f.height,
+                                                        cfg ? *cfg : def);
+        }
+    };
+    if (!grow_rc) {
+        std::vector<std::thread> th;
+        for (int si = 1; si < S; ++si) th.emplace_back(work, si);
+        work(0);
+        for (auto& t : th) t.join();
+    }
+    for (lr_context* l : lanes) l->keep_workspace = false;
+    lanes_done(c, lanes);
+    if (grow_rc) return 1;
+    for (int si = 0; si < S; ++si)
+        if (rc[si]) {
+            set_error(err[si]);
+            return 1;
+        }
+    return 0;
 }
 
 int ctx_find_groups_batch_host(lr_context* c, const void* const* frames, int format, int batch, int w, int h, int stride,

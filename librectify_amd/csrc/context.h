@@ -113,6 +113,9 @@ struct PrepareSpans {
     MirroredBuffer<unsigned char> spans;  // (cap() = bytes: output width + output height entries)
     int key[4] = {0, 0, 0, 0};            // width, output width, height, output height of the table ([0] = 0: none)
     float w_in[2] = {0.f, 0.f};           // (float)(1 / scale) of the table's two axes
+    // LR_WARP_RAGGED | LR_WARP_PREPARE: a call's frame records, tile prefix table and span tables (made per call, sized by
+    // the call: cap() = bytes)
+    MirroredBuffer<unsigned char> ragged;
 };
 }  // namespace lramd
 
@@ -130,6 +133,7 @@ struct lr_context {
     lramd::UploadRing ring;
     lramd::PrepareSpans prep;
     lramd::Event ev_prep_spans;  // the last upload from prep.spans.h
+    lramd::Event ev_prep_ragged;  // the last upload from prep.ragged.h
 
     lramd::Event ev_up[2];
     lramd::Event ev_wait;  // (blocking-sync flag) what a batch lane sleeps on
@@ -148,6 +152,7 @@ struct lr_context {
     uint32_t seed_cap_once = 0;      // test hook: capacity of the next frame's seed sort
     int frame_laps = 0;              // laps the last frame took (1; 2 if the seed sort overflowed or the flood needed more rounds)
     lramd::FloodProgress flood_prog;
+    bool keep_workspace = false;  // a batch call with a frame table: its lanes are sized once for the call's largest frame and the count below rests
     int small_frames = 0;  // frames in a row of at most a quarter of the workspace's capacity (ctx_ensure_image_capacity gives it back after eight)
     // filter_lines + peeling on the device (kernels_groups.hip)
     size_t cap_glines = 0;
@@ -223,6 +228,7 @@ int ctx_create(int device, lr_context** out);
 void ctx_destroy(lr_context* c);
 const std::string& get_error();
 int ctx_ensure_image_capacity(lr_context* c, int w, int h);
+int ctx_reserve_workspace(lr_context* c, size_t npix, int ntiles);
 int ctx_trim(lr_context* c, bool frames_too);
 int ctx_ensure_ransac_capacity(lr_context* c, size_t n_lines);
 int ctx_stage_filter(lr_context* c, const float* d_image, int w, int h, int stride);
@@ -263,6 +269,10 @@ int ctx_find_groups_host(lr_context* c, const void* buffer, int format, int w, i
 int ctx_find_groups_batch_device(lr_context* c, const void* d_images, int format, size_t image_stride, int batch, int w, int h,
                                  int stride, float min_length, bool refine, LineSegment* out, int capacity, int* n_lines,
                                  const RectificationConfig* cfg, ImageTransform* transforms);
+// the same call with width == 0 && height == 0: `frames` is a HOST table of lr_frame records, every frame its own size
+int ctx_find_groups_frames_device(lr_context* c, const lr_frame* frames, int format, bool tagged, int batch, float min_length,
+                                  bool refine, LineSegment* out, int capacity, int* n_lines, const RectificationConfig* cfg,
+                                  ImageTransform* transforms);
 // host-resident frames (any stride sign, pageable or page-locked): staged uploads overlap the kernels
 int ctx_find_groups_batch_host(lr_context* c, const void* const* frames, int format, int batch, int w, int h, int stride,
                                float min_length, bool refine, int num_threads, LineSegment* out, int capacity,
@@ -287,6 +297,18 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
 int ctx_prepare_frames(lr_context* c, const void* d_src, size_t src_image_bytes, int batch, int width, int height,
                        size_t src_row_bytes, int format, void* d_dst, size_t dst_image_bytes, int out_width,
                        int out_height, size_t dst_row_bytes);
+// LR_WARP_RAGGED (kernels_warp.hip): a row of the caller's table as integers, and the check of the whole table that the warp
+// and the prepare step share (sets the error and returns 1 on the first fault; tile_w x tile_h: the caller's destination tiles)
+struct RaggedEntry {
+    uint64_t ow, oh, dst_off, dst_row, w, h, src_off, src_row;
+};
+int ragged_parse(const void* d_src, size_t src_bytes, int batch, int width, int height, size_t src_row_bytes, int format,
+                 bool prepare, const double* T, const void* d_dst, size_t dst_bytes, int out_width, int out_height,
+                 size_t dst_row_bytes, int tile_w, int tile_h, std::vector<RaggedEntry>& out, int64_t* n_tiles);
+// kernels_prepare.hip: LR_WARP_RAGGED | LR_WARP_PREPARE (the low byte of `format` arrives here; T: 18 doubles per frame)
+int ctx_prepare_ragged(lr_context* c, const void* d_src, size_t src_bytes, int batch, int width, int height, size_t src_row_bytes,
+                       int format, const double* T, void* d_dst, size_t dst_bytes, int out_width, int out_height,
+                       size_t dst_row_bytes);
 // bytes one frame spans: (rows - 1) * row_bytes + last_row_bytes; false if that does not fit in 64 bits
 inline bool frame_span(int rows, size_t row_bytes, size_t last_row_bytes, size_t* out) {
     size_t s;

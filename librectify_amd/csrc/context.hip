@@ -94,11 +94,20 @@ int ctx_ensure_image_capacity(lr_context* c, int w, int h) {
     // A context that has seen one large frame keeps serving small ones out of the large workspace (an 8192 x 8192 call leaves
     // 8.9 GB behind): after eight frames in a row of at most a quarter of the capacity it is given back, and this frame
     // allocates its own size (lr_context_trim does the same at once).
-    if (c->ws.cap_pix != 0 && npix * 4 <= c->ws.cap_pix) {
-        if (++c->small_frames >= 8 && ctx_trim(c, false)) return 1;
-    } else {
-        c->small_frames = 0;
+    // (keep_workspace: a batch call with a frame table has sized its lanes for the call and the count rests until it is over)
+    if (!c->keep_workspace) {
+        if (c->ws.cap_pix != 0 && npix * 4 <= c->ws.cap_pix) {
+            if (++c->small_frames >= 8 && ctx_trim(c, false)) return 1;
+        } else {
+            c->small_frames = 0;
+        }
     }
+    return ctx_reserve_workspace(c, npix, ntiles);
+}
+
+// Grows the per-pixel workspace to npix pixels and ntiles candidate lists (which need not be one frame's); never shrinks it.
+int ctx_reserve_workspace(lr_context* c, size_t npix, int ntiles) {
+    const FilterGeom fg = filter_geometry(5, 5);  // (cand_cap: the same for every size)
     if (npix <= c->ws.cap_pix && ntiles <= c->ws.cap_tiles) return 0;
     LR_HIP(hipStreamSynchronize(c->stream));
     const size_t cp = std::max(npix, c->ws.cap_pix);

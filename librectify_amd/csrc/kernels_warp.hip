@@ -21,6 +21,10 @@
 // workgroup finds its frame by a binary search of the tiles' prefix table; the tile index is the same for all its lanes, so
 // the search and the read of the frame's record (map, size, tiles per row, offset, stride) are scalar loads and compares.
 // The lanes' work inside a tile (warp_lane) is the single-size kernel's, statement for statement.
+//
+// LR_WARP_RAGGED (warp_ragged_kernel): every frame has its own SOURCE size and place as well.  The same ragged tile list,
+// search and bands; the frame's record (18 doubles long, like the caller's row) also carries the source's offset from the
+// source pointer, its size and its row stride, all uniform across the workgroup.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -60,6 +64,20 @@ struct PackedArgs {
     const uint8_t* src;
     size_t src_image_bytes, src_row_bytes;
     int w, h;
+    int batch, n_tiles;
+};
+
+// LR_WARP_RAGGED: a frame's record, 18 doubles long like the caller's row it is made from
+struct RaggedFrame {
+    double m[9];
+    unsigned long long offset, row_bytes;          // of its output, from the destination pointer
+    unsigned long long src_offset, src_row_bytes;  // of its source, from the source pointer
+    int ow, oh, tiles_x, w, h, pad[5];
+};
+static_assert(sizeof(RaggedFrame) == 18 * sizeof(double), "a record per 18 doubles of the mirror");
+
+struct RaggedArgs {
+    const uint8_t* src;
     int batch, n_tiles;
 };
 
@@ -325,6 +343,36 @@ __global__ __launch_bounds__(kBlock) void warp_packed_kernel(PackedArgs g, const
     }
 }
 
+// LR_WARP_RAGGED: warp_packed_kernel with the source's place, size and stride read from the frame's record too
+template <int kFormat>
+__global__ __launch_bounds__(kBlock) void warp_ragged_kernel(RaggedArgs g, const RaggedFrame* __restrict__ frames,
+                                                             const int* __restrict__ start, uint8_t* __restrict__ dst) {
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    const unsigned lx = (unsigned)lane & 15u, row_in_tile = (unsigned)(wave * 4 + (lane >> 4));
+    const int per_xcd = (g.n_tiles + 7) / 8;
+    const int xcd = (int)(blockIdx.x & 7u), slots = (int)(gridDim.x >> 3);
+    for (int j = (int)(blockIdx.x >> 3); j < per_xcd; j += slots) {
+        const int tile = xcd * per_xcd + j;
+        if (tile >= g.n_tiles) return;
+        int b = 0, hi = g.batch;  // start[b] <= tile < start[hi]
+        while (hi - b > 1) {
+            const int mid = (b + hi) >> 1;
+            if (start[mid] <= tile) b = mid;
+            else hi = mid;
+        }
+        const RaggedFrame* f = frames + b;
+        const int ow = f->ow, oh = f->oh, tiles_x = f->tiles_x;
+        const int r = tile - start[b];
+        const int ty = r / tiles_x, tx = r - ty * tiles_x;
+        const unsigned y = (unsigned)ty * kTileH + row_in_tile;
+        const unsigned x0 = (unsigned)tx * kTileW + lx * 4u;
+        if (y >= (unsigned)oh || x0 >= (unsigned)ow) continue;
+        const uint8_t* src = g.src + (size_t)f->src_offset;
+        uint8_t* out = dst + (size_t)f->offset + (size_t)y * (size_t)f->row_bytes;
+        warp_lane<kFormat>(f->m, src, (size_t)f->src_row_bytes, f->w, f->h, out, ow, x0, y);
+    }
+}
+
 // v as an integer in [lo, hi], if it is one
 bool table_integer(double v, double lo, double hi, uint64_t* out) {
     if (!(v >= lo && v <= hi) || v != std::floor(v)) return false;
@@ -431,7 +479,132 @@ int warp_packed(lr_context* c, const void* d_src, size_t src_image_bytes, int ba
     return 0;
 }
 
+// lr_warp_perspective_device with LR_WARP_RAGGED: M is the table of 18 doubles per frame, width x height and out_width x
+// out_height bound the frames' sizes, src_image_bytes and dst_image_bytes are the sizes of the two regions
+int warp_ragged(lr_context* c, const void* d_src, size_t src_bytes, int batch, int width, int height, size_t src_row_bytes,
+                int format, const double* T, void* d_dst, size_t dst_bytes, int out_width, int out_height, size_t dst_row_bytes) {
+    std::vector<RaggedEntry> e;
+    int64_t n_tiles = 0;
+    if (ragged_parse(d_src, src_bytes, batch, width, height, src_row_bytes, format, false, T, d_dst, dst_bytes, out_width,
+                     out_height, dst_row_bytes, kTileW, kTileH, e, &n_tiles))
+        return 1;
+    std::vector<RaggedFrame> rec((size_t)batch);
+    std::vector<int> start((size_t)batch + 1);
+    int tiles = 0;
+    for (int b = 0; b < batch; ++b) {
+        const RaggedEntry& s = e[(size_t)b];
+        RaggedFrame& f = rec[(size_t)b];
+        std::memset(&f, 0, sizeof f);
+        std::memcpy(f.m, T + (size_t)b * 18, sizeof f.m);
+        f.offset = s.dst_off;
+        f.row_bytes = s.dst_row;
+        f.src_offset = s.src_off;
+        f.src_row_bytes = s.src_row;
+        f.ow = (int)s.ow;
+        f.oh = (int)s.oh;
+        f.tiles_x = (int)((s.ow + kTileW - 1) / kTileW);
+        f.w = (int)s.w;
+        f.h = (int)s.h;
+        start[(size_t)b] = tiles;
+        tiles += f.tiles_x * (int)((s.oh + kTileH - 1) / kTileH);
+    }
+    start[(size_t)batch] = tiles;
+
+    // records, then the prefix table, in the mirror of the maps (in doubles: 18 a frame + the table's ints)
+    const size_t rec_doubles = (size_t)batch * 18, need = rec_doubles + ((size_t)batch + 2) / 2;
+    LR_HIP(hipSetDevice(c->device));
+    if (need > c->warp_m.cap()) {  // (grows: the buffers of a previous call may still be read by its launch)
+        LR_HIP(hipStreamSynchronize(c->stream));
+        if (c->warp_m.grow(need)) return 1;
+    }
+    if (c->ev_warp_m.ensure(hipEventDisableTiming)) return 1;
+    LR_HIP(hipEventSynchronize(c->ev_warp_m));  // the previous call's upload has read h_warp_m
+    std::memcpy(c->warp_m.h, rec.data(), rec_doubles * sizeof(double));
+    std::memcpy(c->warp_m.h + rec_doubles, start.data(), start.size() * sizeof(int));
+    const size_t up_bytes = rec_doubles * sizeof(double) + start.size() * sizeof(int);
+    LR_HIP(hipMemcpyAsync(c->warp_m.d, c->warp_m.h, up_bytes, hipMemcpyHostToDevice, c->stream));
+    LR_HIP(hipEventRecord(c->ev_warp_m, c->stream));
+
+    RaggedArgs g;
+    g.src = static_cast<const uint8_t*>(d_src);
+    g.batch = batch;
+    g.n_tiles = (int)n_tiles;
+    uint8_t* dst = static_cast<uint8_t*>(d_dst);
+    const RaggedFrame* frames = reinterpret_cast<const RaggedFrame*>(c->warp_m.d.get());
+    const int* tile_start = reinterpret_cast<const int*>(c->warp_m.d.get() + rec_doubles);
+    const int grid = (int)std::min<int64_t>((n_tiles + 7) / 8 * 8, kMaxGrid);
+    if (format == LR_PIX_U8)
+        hipLaunchKernelGGL(warp_ragged_kernel<LR_PIX_U8>, dim3(grid), dim3(kBlock), 0, c->stream, g, frames, tile_start, dst);
+    else if (format == LR_PIX_U8X3)
+        hipLaunchKernelGGL(warp_ragged_kernel<LR_PIX_U8X3>, dim3(grid), dim3(kBlock), 0, c->stream, g, frames, tile_start, dst);
+    else
+        hipLaunchKernelGGL(warp_ragged_kernel<LR_PIX_F32>, dim3(grid), dim3(kBlock), 0, c->stream, g, frames, tile_start, dst);
+    LR_HIP(hipGetLastError());
+    return 0;
+}
+
 }  // namespace
+
+// The table of LR_WARP_RAGGED, checked as a whole before anything is launched (the warp and the prepare step share it):
+// fills `out` and the number of tile_w x tile_h destination tiles; sets the error and returns 1 on the first fault.
+int ragged_parse(const void* d_src, size_t src_bytes, int batch, int width, int height, size_t src_row_bytes, int format,
+                 bool prepare, const double* T, const void* d_dst, size_t dst_bytes, int out_width, int out_height,
+                 size_t dst_row_bytes, int tile_w, int tile_h, std::vector<RaggedEntry>& out, int64_t* n_tiles_out) {
+    auto fail = [](const char* what) {
+        set_error(std::string("lr_warp_perspective_device: LR_WARP_RAGGED: ") + what);
+        return 1;
+    };
+    if (!d_src || !d_dst || !T) return fail("null pointer (source, destination or table)");
+    if (batch < 1) return fail("batch < 1");
+    if (width < 1 || height < 1 || out_width < 1 || out_height < 1) return fail("source bound or output bound below 1");
+    if (format != LR_PIX_U8 && format != LR_PIX_U8X3 && format != LR_PIX_F32) return fail("unknown pixel format");
+    if (src_row_bytes != 0 || dst_row_bytes != 0) return fail("src_row_bytes and dst_row_bytes must be 0 (every frame's strides are in the table)");
+    const uint64_t bpp = format == LR_PIX_U8 ? 1 : (format == LR_PIX_U8X3 ? 3 : 4);
+    const uint64_t obpp = prepare ? 4 : bpp;  // (the prepare step writes f32 gray)
+    const bool src_f32 = format == LR_PIX_F32, dst_f32 = prepare || format == LR_PIX_F32;
+    if (src_f32 && (reinterpret_cast<uintptr_t>(d_src) & 3u)) return fail("f32 source pointer not 4-byte aligned");
+    if (dst_f32 && (reinterpret_cast<uintptr_t>(d_dst) & 3u)) return fail("f32 destination pointer not 4-byte aligned");
+    constexpr double kExact = 9007199254740992.0;  // 2^53: integers up to it are doubles
+    out.assign((size_t)batch, RaggedEntry{});
+    std::vector<std::pair<uint64_t, uint64_t>> extent((size_t)batch);  // of the outputs: [first byte, end)
+    int64_t n_tiles = 0;
+    for (int b = 0; b < batch; ++b) {
+        const double* t = T + (size_t)b * 18;
+        RaggedEntry& s = out[(size_t)b];
+        if (!(t[17] == 0.0)) return fail("a frame's entry [17] is reserved and must be 0");
+        if (!prepare)
+            for (int i = 0; i < 9; ++i)
+                if (!std::isfinite(t[i])) return fail("M is not finite");
+        if (!table_integer(t[9], 1, out_width, &s.ow) || !table_integer(t[10], 1, out_height, &s.oh))
+            return fail("a frame's output size is not an integer from 1 to out_width x out_height");
+        if (!table_integer(t[11], 0, kExact, &s.dst_off)) return fail("a frame's output offset is not an integer from 0 to 2^53");
+        if (!table_integer(t[12], (double)(s.ow * obpp), kExact, &s.dst_row))
+            return fail("a frame's output row stride is not an integer from a row's bytes to 2^53");
+        if (!table_integer(t[13], 1, width, &s.w) || !table_integer(t[14], 1, height, &s.h))
+            return fail("a frame's source size is not an integer from 1 to width x height");
+        if (!table_integer(t[15], 0, kExact, &s.src_off)) return fail("a frame's source offset is not an integer from 0 to 2^53");
+        if (!table_integer(t[16], (double)(s.w * bpp), kExact, &s.src_row))
+            return fail("a frame's source row stride is not an integer from a row's bytes to 2^53");
+        if (dst_f32 && ((s.dst_off | s.dst_row) & 3u)) return fail("f32 output offset or stride not a multiple of 4");
+        if (src_f32 && ((s.src_off | s.src_row) & 3u)) return fail("f32 source offset or stride not a multiple of 4");
+        if (prepare && (s.ow > s.w || s.oh > s.h)) return fail("LR_WARP_PREPARE: a frame's output larger than its source (no upscaling)");
+        uint64_t end;
+        if (__builtin_mul_overflow(s.oh - 1, s.dst_row, &end) || __builtin_add_overflow(end, s.dst_off, &end) ||
+            __builtin_add_overflow(end, s.ow * obpp, &end) || end > dst_bytes)
+            return fail("a frame's output reaches beyond dst_image_bytes");
+        extent[(size_t)b] = {s.dst_off, end};
+        if (__builtin_mul_overflow(s.h - 1, s.src_row, &end) || __builtin_add_overflow(end, s.src_off, &end) ||
+            __builtin_add_overflow(end, s.w * bpp, &end) || end > src_bytes)
+            return fail("a frame's source reaches beyond src_image_bytes");
+        n_tiles += (int64_t)((s.ow + (uint64_t)tile_w - 1) / (uint64_t)tile_w) * (int64_t)((s.oh + (uint64_t)tile_h - 1) / (uint64_t)tile_h);
+        if (n_tiles > 0x7FFFFFF0ll) return fail("output larger than 2^31 tiles");
+    }
+    std::sort(extent.begin(), extent.end());
+    for (int b = 1; b < batch; ++b)
+        if (extent[(size_t)b].first < extent[(size_t)b - 1].second) return fail("two frames' output extents overlap");
+    *n_tiles_out = n_tiles;
+    return 0;
+}
 
 int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_bytes, int batch, int width, int height,
                          size_t src_row_bytes, int format, const double* M, void* d_dst, size_t dst_image_bytes,
@@ -441,6 +614,17 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
         return 1;
     };
     if (!c) return fail("no context");
+    if (format & LR_WARP_RAGGED) {  // every frame its own source and output: one table for the warp and the prepare step
+        const int opts = format & ~0xFF;
+        if (opts & LR_WARP_PACKED) return fail("LR_WARP_RAGGED together with LR_WARP_PACKED (ragged outputs are always packed)");
+        if (opts == LR_WARP_RAGGED)
+            return warp_ragged(c, d_src, src_image_bytes, batch, width, height, src_row_bytes, format & 0xFF, M, d_dst,
+                               dst_image_bytes, out_width, out_height, dst_row_bytes);
+        if (opts == (LR_WARP_RAGGED | LR_WARP_PREPARE))
+            return ctx_prepare_ragged(c, d_src, src_image_bytes, batch, width, height, src_row_bytes, format & 0xFF, M, d_dst,
+                                      dst_image_bytes, out_width, out_height, dst_row_bytes);
+        return fail("unknown option bits in format");
+    }
     if (format & ~0xFF) {  // option bits above the pixel format
         if ((format & ~0xFF) == LR_WARP_PACKED)
             return warp_packed(c, d_src, src_image_bytes, batch, width, height, src_row_bytes, format & 0xFF, M, d_dst,
