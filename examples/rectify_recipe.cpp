@@ -5,7 +5,7 @@
 // (<prefix>_lines.csv: x1,y1,x2,y2,weight,err,group_id per row; <prefix>_tform.csv: TL, TR, BL, BR, hvp, vvp).
 //
 //   rectify_recipe in.pgm|in.ppm out_prefix [--max-size N|fraction] [--refine] [--threads N]
-//                  [--h-strategy rotate_h|rotate_v|rectify|keep] [--v-strategy ...] [--warp] [--device-prepare]
+//                  [--h-strategy rotate_h|rotate_v|rectify|keep] [--v-strategy ...] [--warp] [--device-prepare] [--lines]
 //
 // Input is a binary PGM (P5, 8 bit) or PPM (P6, 8 bit; converted with the usual integer luma weights
 // (4899 R + 9617 G + 1868 B + 8192) >> 14).  Image decoding stays with the caller's imaging library.
@@ -15,6 +15,9 @@
 // --device-prepare: the first step on the GPU as well -- the file's 8-bit pixels go up as they are, luma, / 256 and the
 // prescale are one lr_warp_perspective_device call with LR_WARP_PREPARE, and lr_find_line_segment_groups_device runs
 // on the prepared frame where it lies.  Same CSV files, byte for byte.
+// --lines: the demo's lines picture (autorectify.cpp:72-110,364-366) -- the segments, in the full frame's coordinates as
+// written to the CSV, drawn on the gray frame on the GPU (lr_draw_lines_device), written as <out_prefix>_lines.ppm; with
+// --warp also <out_prefix>_warp_lines.ppm: the rectified picture with the segments drawn through H.
 // Links against librectify_amd.so exactly like a program written for the reference.
 #include <algorithm>
 #include <cctype>
@@ -173,15 +176,15 @@ bool find_groups_device_prepared(const Gray& g, int max_size, bool refine, int t
 
 // The demo's homography_from_corners(t, 3.0) + warpPerspective of the frame as read, on the GPU; writes
 // <prefix>_warp.pgm / .ppm.  Returns false with the reason on stderr.
-bool warp_frame(const Gray& g, const ImageTransform& t, const std::string& prefix) {
+// `out`, `ow`, `oh` and `H` (source to rectified picture) are kept for --lines.
+bool warp_frame(const Gray& g, const ImageTransform& t, const std::string& prefix, std::vector<uint8_t>& out, int& ow, int& oh,
+                double* H) {
     double M[9];
-    int ow = 0, oh = 0;
     lr_context* ctx = nullptr;
     void* d_src = nullptr;
     void* d_dst = nullptr;
     const size_t bpp = (size_t)g.ch;
-    std::vector<uint8_t> out;
-    bool ok = lr_rectification_homography(&t, 3.0f, nullptr, M, &ow, &oh) == 0 && lr_context_create(0, &ctx) == 0;
+    bool ok = lr_rectification_homography(&t, 3.0f, H, M, &ow, &oh) == 0 && lr_context_create(0, &ctx) == 0;
     if (ok) {
         out.resize((size_t)ow * oh * bpp);
         ok = lr_device_malloc(ctx, g.raw.size(), &d_src) == 0 && lr_device_malloc(ctx, out.size(), &d_dst) == 0 &&
@@ -210,6 +213,44 @@ bool warp_frame(const Gray& g, const ImageTransform& t, const std::string& prefi
     return true;
 }
 
+// The demo's draw_lines on an 8-bit picture (ch 1: gray, every pixel v as (v, v, v); ch 3: drawn upon in place), the
+// segments through H if it is not null; writes `path` as a PPM.  Returns false with the reason on stderr.
+bool lines_picture(const uint8_t* img, int w, int h, int ch, const LineSegment* lines, int n, const double* H,
+                   const std::string& path) {
+    lr_context* ctx = nullptr;
+    void* d_img = nullptr;
+    void* d_rgb = nullptr;
+    const size_t img_bytes = (size_t)w * h * ch, rgb_bytes = (size_t)w * h * 3;
+    const double in_place[8] = {(double)w, (double)h, 0, 0, 0, (double)w * 3, 0, (double)n};
+    const double from_gray[8] = {(double)w, (double)h, 0, (double)w, 0, (double)w * 3, 0, (double)n};
+    std::vector<uint8_t> out(rgb_bytes);
+    bool ok = lr_context_create(0, &ctx) == 0 && lr_device_malloc(ctx, img_bytes, &d_img) == 0 &&
+              lr_memcpy_h2d(ctx, d_img, img, img_bytes) == 0;
+    if (ok && ch == 3)
+        ok = lr_draw_lines_device(ctx, nullptr, 0, LR_PIX_U8X3, lines, (size_t)n, in_place, 1, H, d_img, rgb_bytes) == 0 &&
+             lr_memcpy_d2h(ctx, out.data(), d_img, rgb_bytes) == 0;
+    else if (ok)
+        ok = lr_device_malloc(ctx, rgb_bytes, &d_rgb) == 0 &&
+             lr_draw_lines_device(ctx, d_img, img_bytes, LR_PIX_U8, lines, (size_t)n, from_gray, 1, H, d_rgb, rgb_bytes) == 0 &&
+             lr_memcpy_d2h(ctx, out.data(), d_rgb, rgb_bytes) == 0;
+    if (!ok) std::fprintf(stderr, "lines picture failed: %s\n", lr_last_error());
+    if (ctx) {
+        if (d_img) lr_device_free(ctx, d_img);
+        if (d_rgb) lr_device_free(ctx, d_rgb);
+        lr_context_destroy(ctx);
+    }
+    if (!ok) return false;
+    std::ofstream f(path, std::ios::binary);
+    f << "P6\n" << w << " " << h << "\n255\n";
+    f.write(reinterpret_cast<const char*>(out.data()), (std::streamsize)out.size());
+    if (!f) {
+        std::fprintf(stderr, "lines picture failed: cannot write %s\n", path.c_str());
+        return false;
+    }
+    std::printf("wrote %s (%dx%d, %d segments)\n", path.c_str(), w, h, n);
+    return true;
+}
+
 bool parse_strategy(const std::string& s, RectificationStrategy& out) {
     if (s == "rotate_h") out = ROTATE_H;
     else if (s == "rotate_v") out = ROTATE_V;
@@ -225,12 +266,13 @@ int main(int argc, char** argv) {
     if (argc < 3) {
         std::fprintf(stderr,
                      "usage: %s in.pgm|in.ppm out_prefix [--max-size N|fraction] [--refine] [--threads N]\n"
-                     "          [--h-strategy rotate_h|rotate_v|rectify|keep] [--v-strategy ...] [--warp] [--device-prepare]\n",
+                     "          [--h-strategy rotate_h|rotate_v|rectify|keep] [--v-strategy ...] [--warp] [--device-prepare]\n"
+                     "          [--lines]\n",
                      argv[0]);
         return 2;
     }
     float max_size = 1200.f;  // the demo's default
-    bool refine = false, warp = false, device_prepare = false;
+    bool refine = false, warp = false, device_prepare = false, lines_pictures = false;
     int threads = -1;
     RectificationConfig cfg;
     cfg.horizontal_vp_min_distance = 2;  // autorectify.cpp:347
@@ -240,6 +282,7 @@ int main(int argc, char** argv) {
         if (a == "--refine") refine = true;
         else if (a == "--warp") warp = true;
         else if (a == "--device-prepare") device_prepare = true;
+        else if (a == "--lines") lines_pictures = true;
         else if (a == "--max-size" && has_val) max_size = (float)std::atof(argv[++i]);
         else if (a == "--threads" && has_val) threads = std::atoi(argv[++i]);
         else if (a == "--h-strategy" && has_val && parse_strategy(argv[i + 1], cfg.h_strategy)) ++i;
@@ -296,7 +339,17 @@ int main(int argc, char** argv) {
     tf << t.vertical_vp.x << "," << t.vertical_vp.y << "," << t.vertical_vp.z << "\n";
     std::printf("%dx%d -> %dx%d (scale %g), %d segments, wrote %s_lines.csv and %s_tform.csv\n", full.w, full.h, small_w,
                 small_h, (double)scale, n, prefix.c_str(), prefix.c_str());
+    std::vector<uint8_t> warped;
+    int ow = 0, oh = 0;
+    double H[9];
+    bool ok = !warp || warp_frame(full, t, prefix, warped, ow, oh, H);
+    if (ok && lines_pictures) {  // on the gray frame, as the demo draws (autorectify.cpp:364)
+        std::vector<uint8_t> gray(full.px.size());
+        for (size_t i = 0; i < gray.size(); ++i) gray[i] = (uint8_t)(full.px[i] * 256.0f);
+        ok = lines_picture(gray.data(), full.w, full.h, 1, lines, n, nullptr, prefix + "_lines.ppm") &&
+             (!warp || lines_picture(warped.data(), ow, oh, full.ch, lines, n, H, prefix + "_warp_lines.ppm"));
+    }
     if (!device_prepare) release_line_segments(&lines);
-    if (warp && !warp_frame(full, t, prefix)) return 1;
+    if (!ok) return 1;
     return device_prepare || lines == nullptr ? 0 : 1;
 }

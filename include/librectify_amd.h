@@ -273,6 +273,51 @@ enum lr_warp_layout { LR_WARP_PACKED = 0x200 }; /* or-ed into `format` like lr_w
  * non-finite map (the warp only), a non-zero src_row_bytes or dst_row_bytes, more than 2^31 tiles, the alignment rules. */
 enum lr_warp_sources { LR_WARP_RAGGED = 0x800 }; /* or-ed into `format` like lr_warp_option */
 
+/* The demo's lines picture (autorectify.cpp:72-110, draw_lines; <name>_warp_lines.jpg) on frames that stay in HBM: every
+ * segment of a frame as a 3-pixel stroke with a disc of radius 5 at each end, in its group's colour, later segments over
+ * earlier ones, on the frame as u8x3.  One launch on the context's stream for a batch of frames of different sizes.
+ * `frames` is a HOST table of
+ * 8 doubles per frame: [0] [1] width_b, height_b, [2] [3] byte offset of the source from d_src and its row stride in bytes,
+ * [4] [5] byte offset of the output from d_dst and its row stride, [6] [7] first segment of the frame in `lines` and count
+ * `lines` is a HOST array of n_lines segments; [6] and [7] let the batch detector's output (out + b*capacity, n_lines[b])
+ * be passed as it is.  H is on the host: 9 doubles per frame (what lr_rectification_homography returns as H: the lines are
+ * then drawn on the rectified picture), or NULL for identity.  format is LR_PIX_U8 (pixel v becomes (v, v, v)) or
+ * LR_PIX_U8X3 (copied); the destination is always u8x3.  d_src == NULL draws in place on what d_dst holds: src_bytes and
+ * [2] [3] are 0, format is LR_PIX_U8X3, and only covered pixels are written.
+ * The shapes are exact and in integers (a restatement of the demo's line(..., 3) and circle(..., 5,
+ * -1), not OpenCV's bit pattern): endpoints are truncated toward zero, after H in double if there is one; a pixel takes
+ * the colour of the highest-index segment of its frame whose shape contains it; colours are white for group_id < 0 and
+ * otherwise entry group_id % 12 of the demo's palette with c0 red.  A segment with a non-finite coordinate, one beyond
+ * 2^24, or (with H) denominators that are zero or differ in sign is not drawn.
+ * The table follows LR_WARP_RAGGED's rules: integers (at most 2^53), sizes from 1 (to 2^30), strides at least a row, every
+ * extent within its region of src_bytes or dst_bytes, output extents that do not overlap each other, [6] + [7] <= n_lines
+ * (a count of 0 gives the background only); except in place the destination region does not overlap the source region.
+ * The whole table is checked before anything is enqueued: on failure (also a null `lines` with n_lines != 0, a format
+ * other than the two, batch < 1, a non-finite H) nothing is launched or written and lr_last_error names the frame and the
+ * entry.  No byte of the destination region outside the frames' pixels is written, row padding and gaps included.
+ * The library's table of exported symbols is full (tests/test_boundary_cpu.py holds it at 60), so the call travels through
+ * lr_warp_perspective_device: LR_WARP_LINES or-ed into `format`, `M` pointing to an lr_draw_lines_args, src_image_bytes
+ * and dst_image_bytes the two regions' sizes, and width, height, out_width, out_height and both row strides 0 (any other
+ * option bit or a non-zero one of these fails cleanly).  lr_draw_lines_device below is that call, spelled out. */
+typedef struct lr_draw_lines_args {
+    const LineSegment* lines; /* HOST, n_lines records */
+    size_t n_lines;
+    const double* frames; /* HOST, 8 doubles per frame */
+    const double* H;      /* HOST, 9 doubles per frame, or NULL */
+} lr_draw_lines_args;
+enum lr_warp_lines { LR_WARP_LINES = 0x1000 }; /* or-ed into `format` like lr_warp_option */
+static inline int lr_draw_lines_device(lr_context* ctx, const void* d_src, size_t src_bytes, int format, const LineSegment* lines,
+                                       size_t n_lines, const double* frames, int batch, const double* H, void* d_dst,
+                                       size_t dst_bytes) {
+    lr_draw_lines_args a;
+    a.lines = lines;
+    a.n_lines = n_lines;
+    a.frames = frames;
+    a.H = H;
+    return lr_warp_perspective_device(ctx, d_src, src_bytes, batch, 0, 0, 0, format | LR_WARP_LINES, (const double*)(const void*)&a,
+                                      d_dst, dst_bytes, 0, 0, 0);
+}
+
 /* ---- stage API (tests, bench) --------------------------------------------------------- */
 /* Stage 1: fused 5x5 derivative filter + magnitude + direction bin + dilated-bin mask +
  * 5x5 non-max candidates (reference line_detector.cpp:41-49,126-182, filter.cpp:29-98,161-168). */

@@ -62,12 +62,17 @@ class Frame(C.Structure):  # lr_frame: a row of the batch detector's frame table
                 ("min_length", C.c_float)]
 
 
+class DrawLinesArgs(C.Structure):  # lr_draw_lines_args
+    _fields_ = [("lines", C.c_void_p), ("n_lines", C.c_size_t), ("frames", C.c_void_p), ("H", C.c_void_p)]
+
+
 BUF_DX, BUF_DY, BUF_DMASK, BUF_LABEL, BUF_SEED_IDX, BUF_SEED_BIN, BUF_SEED_THR, BUF_MAXMAG, BUF_SEED_SIZE = range(9)
 T_UPLOAD, T_FILTER, T_SEEDS, T_FLOOD, T_FIT, T_RANSAC, T_TOTAL, T_FILTER_KERNEL, T_COUNT = range(9)
 PIX_U8, PIX_U8X3, PIX_F32 = range(3)  # enum lr_pixel_format
 WARP_PREPARE = 0x100  # enum lr_warp_option, or-ed into the format of lr_warp_perspective_device
 WARP_PACKED = 0x200  # enum lr_warp_layout, likewise: per-frame output sizes and places (warp_table)
 WARP_RAGGED = 0x800  # enum lr_warp_sources, likewise: per-frame source sizes and places as well (ragged_table)
+WARP_LINES = 0x1000  # enum lr_warp_lines, likewise: lr_draw_lines_device, whose own arguments travel behind M (DrawLinesArgs)
 FRAMES_U8, FRAMES_U8X3, FRAMES_F32 = 0x100, 0x200, 0x300  # enum lr_frames_option, or-ed into `refine` of the frame entries
 
 
@@ -303,6 +308,29 @@ def ragged_table(Ms, out_sizes, sources, bpp, out_bpp=None, align=4):
     return table, total
 
 
+def draw_table(sizes, sources, outputs, segments):
+    """The table of lr_draw_lines_device: sizes: B pairs (width, height); sources: B pairs (byte_offset, row_bytes) of the
+    frames in the source region, or None (in place: zeros); outputs: B pairs (byte_offset, row_bytes) of the u8x3 outputs
+    in the destination region; segments: B pairs (first, count) into the lines array.  Returns float64 (B, 8): width,
+    height, source offset and stride, output offset and stride, first segment and count.  Needs no GPU."""
+    sz = np.asarray(sizes)
+    if sz.ndim != 2 or sz.shape[1] != 2 or not np.issubdtype(sz.dtype, np.integer):
+        raise ValueError("draw_table: sizes is B pairs of integers (width, height)")
+    B = len(sz)
+    cols = [sz]
+    for name, a in (("sources", sources), ("outputs", outputs), ("segments", segments)):
+        a = np.zeros((B, 2), np.int64) if a is None and name == "sources" else np.asarray(a)
+        if a.shape != (B, 2) or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("draw_table: %s is B pairs of integers" % name)
+        cols.append(a)
+    table = np.concatenate([c.astype(np.int64) for c in cols], axis=1)
+    if B and (table.min() < 0 or table.max() > 2 ** 53):
+        raise ValueError("draw_table: an entry below 0 or above 2^53")
+    if B and int(sz.min()) < 1:
+        raise ValueError("draw_table: a size below 1")
+    return table.astype(np.float64)
+
+
 def _source_extent(sources, bpp):
     """bytes of the region that holds the sources (width, height, byte_offset, row_bytes)"""
     return max(off + (h - 1) * row + w * bpp for w, h, off, row in sources)
@@ -511,6 +539,69 @@ class Context:
             self.device_free(d_src)
             if d_dst.value:
                 self.device_free(d_dst.value)
+
+    # ---- the lines picture ----
+    def draw_lines_device(self, d_src, src_bytes, fmt, lines, table, d_dst, dst_bytes, H=None):
+        """lr_draw_lines_device (lr_warp_perspective_device with LR_WARP_LINES): one launch, enqueued on the context's stream, that draws every frame's segments (the demo's
+        draw_lines) on its u8 or u8x3 source into its u8x3 output.  lines: a LINE_DTYPE array on the host (or None);
+        table: 8 doubles per frame (draw_table); H: (B, 3, 3) or None; d_src None (or 0): in place on d_dst."""
+        table = np.ascontiguousarray(table, np.float64)
+        if table.ndim != 2 or table.shape[1] != 8:
+            raise ValueError("draw_lines_device: the table has 8 values per frame")
+        if lines is not None:
+            lines = np.ascontiguousarray(lines, LINE_DTYPE).reshape(-1)
+        if H is not None:
+            H = np.ascontiguousarray(H, np.float64).reshape(-1)
+            if H.size != 9 * len(table):
+                raise ValueError("draw_lines_device: H needs 9 values per frame")
+        args = DrawLinesArgs(_ptr(lines), 0 if lines is None else len(lines), _ptr(table), _ptr(H))
+        _check(lib().lr_warp_perspective_device(self._h, C.c_void_p(d_src) if d_src else None, src_bytes, len(table), 0, 0, 0,
+                                                fmt | WARP_LINES, C.cast(C.byref(args), C.c_void_p), C.c_void_p(d_dst),
+                                                dst_bytes, 0, 0, 0))
+
+    def draw_lines_batch(self, frames, lines_list, Hs=None):
+        """The demo's lines picture for a list of 8-bit frames of different shapes (all gray H x W, or all H x W x 3) and
+        their segments (one LINE_DTYPE array per frame; Hs: one 3x3 per frame, or None): one upload, one
+        lr_draw_lines_device call, one download.  Returns the list of H x W x 3 uint8 pictures: a loop of draw_lines."""
+        frames = [np.ascontiguousarray(f) for f in frames]
+        if not frames or len(lines_list) != len(frames) or (Hs is not None and len(Hs) != len(frames)):
+            raise ValueError("draw_lines_batch: as many line arrays (and Hs) as frames, at least one")
+        formats = [_frame_format(f, "draw_lines") for f in frames]
+        fmt, bpp = formats[0]
+        if fmt == PIX_F32 or any(f != formats[0] for f in formats):
+            raise ValueError("draw_lines_batch: uint8 frames, all H x W or all H x W x 3")
+        lines_list = [np.ascontiguousarray(l, LINE_DTYPE).reshape(-1) for l in lines_list]
+        sizes, sources, outputs, segments = [], [], [], []
+        src_end = dst_end = first = 0
+        for f, l in zip(frames, lines_list):
+            h, w = f.shape[:2]
+            sizes.append((w, h))
+            sources.append((src_end, w * bpp))
+            outputs.append((dst_end, w * 3))
+            segments.append((first, len(l)))
+            src_end = (src_end + h * w * bpp + 3) // 4 * 4  # (every frame starts at a multiple of 4)
+            dst_end = (dst_end + h * w * 3 + 3) // 4 * 4
+            first += len(l)
+        table = draw_table(sizes, sources, outputs, segments)
+        region = np.zeros(src_end, np.uint8)
+        for f, (off, _) in zip(frames, sources):
+            region[off:off + f.size] = f.reshape(-1)
+        d_src = self.device_upload(region)
+        d_dst = C.c_void_p()
+        try:
+            _check(lib().lr_device_malloc(self._h, dst_end, C.byref(d_dst)))
+            self.draw_lines_device(d_src, src_end, fmt, np.concatenate(lines_list), table, d_dst.value, dst_end, H=Hs)
+            out = self.device_download(d_dst.value, (dst_end,), np.uint8)
+        finally:
+            self.device_free(d_src)
+            if d_dst.value:
+                self.device_free(d_dst.value)
+        return [out[off:off + w * h * 3].reshape(h, w, 3).copy() for (w, h), (off, _) in zip(sizes, outputs)]
+
+    def draw_lines(self, image_u8, lines, H=None):
+        """The demo's lines picture of one 8-bit frame (H x W gray or H x W x 3) and the detector's segments, drawn through
+        H (3x3) if given: upload, one launch, download.  Returns H x W x 3 uint8."""
+        return self.draw_lines_batch([image_u8], [lines], None if H is None else [H])[0]
 
     def prepare_device(self, d_src, src_image_bytes, batch, width, height, src_row_bytes, fmt, d_dst, dst_image_bytes,
                        out_width, out_height, dst_row_bytes):

@@ -19,6 +19,7 @@ SOURCES = [
     "kernels_groups.hip",
     "kernels_warp.hip",
     "kernels_prepare.hip",
+    "kernels_overlay.hip",
     "context.hip",
     "upload.hip",
     "frame.hip",

@@ -25,6 +25,15 @@ constexpr float kLineMaxErr = 2.0f;
 constexpr float kLineMinLength = 5.f;
 constexpr int kComponentMinSize = 5;
 constexpr int kBins = 8;
+// the demo's lines picture (draw_lines), restated in integers: DESIGN.md section 3
+constexpr int kOverlayStrokeNum = 9, kOverlayStrokeDen = 4;  // (3 / 2)^2: line(..., w = 3), autorectify.cpp:98,103,105
+constexpr int kOverlayDiscR2 = 25;                           // circle(..., 5, ..., -1), autorectify.cpp:106-107
+constexpr int kOverlayColours = 12;                          // colors[g % 12], autorectify.cpp:102
+// c0 | c1 << 8 | c2 << 16, c0 red: autorectify.cpp:75-80 (r g b c m y), 82-87 (the same at 128)
+constexpr uint32_t kOverlayPalette[kOverlayColours] = {0x0000FFu, 0x00FF00u, 0xFF0000u, 0xFFFF00u, 0xFF00FFu, 0x00FFFFu,
+                                                       0x000080u, 0x008000u, 0x800000u, 0x808000u, 0x800080u, 0x008080u};
+constexpr uint32_t kOverlayUngrouped = 0xFFFFFFu;  // g == -1, autorectify.cpp:97
+constexpr int kOverlayMaxCoord = 1 << 24;          // endpoints beyond it are not drawn (every product then fits in int64)
 
 struct FilterConsts {
     float d[5];  // 1-D factors of the 5x5 taps (reference filter.cpp:65-78): Hx(i,j) = d[j] g[i], Hy(i,j) = d[i] g[j]

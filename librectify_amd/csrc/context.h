@@ -117,6 +117,12 @@ struct PrepareSpans {
     // the call: cap() = bytes)
     MirroredBuffer<unsigned char> ragged;
 };
+
+// lr_draw_lines_device (kernels_overlay.hip): a call's frame records, tile prefix table, bins, index lists and segment
+// records (made per call, sized by the call: cap() = bytes)
+struct OverlayStore {
+    MirroredBuffer<unsigned char> block;
+};
 }  // namespace lramd
 
 struct lr_context {
@@ -134,6 +140,8 @@ struct lr_context {
     lramd::PrepareSpans prep;
     lramd::Event ev_prep_spans;  // the last upload from prep.spans.h
     lramd::Event ev_prep_ragged;  // the last upload from prep.ragged.h
+    lramd::OverlayStore overlay;
+    lramd::Event ev_overlay;  // the last upload from overlay.block.h (rewritten only once that has been read)
 
     lramd::Event ev_up[2];
     lramd::Event ev_wait;  // (blocking-sync flag) what a batch lane sleeps on
@@ -309,6 +317,10 @@ int ragged_parse(const void* d_src, size_t src_bytes, int batch, int width, int 
 int ctx_prepare_ragged(lr_context* c, const void* d_src, size_t src_bytes, int batch, int width, int height, size_t src_row_bytes,
                        int format, const double* T, void* d_dst, size_t dst_bytes, int out_width, int out_height,
                        size_t dst_row_bytes);
+// kernels_overlay.hip: lr_draw_lines_device (validates the whole table, turns the segments into integer records and bins them
+// on the host, uploads them and enqueues one launch)
+int ctx_draw_lines(lr_context* c, const void* d_src, size_t src_bytes, int format, const LineSegment* lines, size_t n_lines,
+                   const double* frames, int batch, const double* H, void* d_dst, size_t dst_bytes);
 // bytes one frame spans: (rows - 1) * row_bytes + last_row_bytes; false if that does not fit in 64 bits
 inline bool frame_span(int rows, size_t row_bytes, size_t last_row_bytes, size_t* out) {
     size_t s;

@@ -63,6 +63,7 @@ int ctx_trim(lr_context* c, bool frames_too) {
         c->ring.drop();
         c->prep = PrepareSpans{};  // (sized by a frame's width + height)
         c->warp_m = MirroredBuffer<double>{};  // (sized by the largest batch warped)
+        c->overlay = OverlayStore{};           // (sized by the most segments drawn in a call)
     }
     c->small_frames = 0;
     c->w = c->h = 0;

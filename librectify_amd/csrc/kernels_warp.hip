@@ -25,6 +25,8 @@
 // LR_WARP_RAGGED (warp_ragged_kernel): every frame has its own SOURCE size and place as well.  The same ragged tile list,
 // search and bands; the frame's record (18 doubles long, like the caller's row) also carries the source's offset from the
 // source pointer, its size and its row stride, all uniform across the workgroup.
+//
+// LR_WARP_LINES is no warp: the entry hands lr_draw_lines_device's call on to kernels_overlay.hip (the export table is full).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -614,6 +616,15 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
         return 1;
     };
     if (!c) return fail("no context");
+    if (format & LR_WARP_LINES) {  // lr_draw_lines_device (kernels_overlay.hip): its own arguments arrive behind M
+        if ((format & ~0xFF) != LR_WARP_LINES) return fail("LR_WARP_LINES together with another option bit");
+        if (width != 0 || height != 0 || src_row_bytes != 0 || out_width != 0 || out_height != 0 || dst_row_bytes != 0)
+            return fail("LR_WARP_LINES: width, height, out_width, out_height and the row strides must be 0 (they are in the frame table)");
+        if (!M) return fail("LR_WARP_LINES: null pointer (lr_draw_lines_args)");
+        const lr_draw_lines_args* a = reinterpret_cast<const lr_draw_lines_args*>(M);
+        return ctx_draw_lines(c, d_src, src_image_bytes, format & 0xFF, a->lines, a->n_lines, a->frames, batch, a->H, d_dst,
+                              dst_image_bytes);
+    }
     if (format & LR_WARP_RAGGED) {  // every frame its own source and output: one table for the warp and the prepare step
         const int opts = format & ~0xFF;
         if (opts & LR_WARP_PACKED) return fail("LR_WARP_RAGGED together with LR_WARP_PACKED (ragged outputs are always packed)");
