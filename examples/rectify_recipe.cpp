@@ -6,6 +6,7 @@
 //
 //   rectify_recipe in.pgm|in.ppm out_prefix [--max-size N|fraction] [--refine] [--threads N]
 //                  [--h-strategy rotate_h|rotate_v|rectify|keep] [--v-strategy ...] [--warp] [--device-prepare] [--lines]
+//                  [--jpeg Q]
 //
 // Input is a binary PGM (P5, 8 bit) or PPM (P6, 8 bit; converted with the usual integer luma weights
 // (4899 R + 9617 G + 1868 B + 8192) >> 14).  Image decoding stays with the caller's imaging library.
@@ -18,6 +19,9 @@
 // --lines: the demo's lines picture (autorectify.cpp:72-110,364-366) -- the segments, in the full frame's coordinates as
 // written to the CSV, drawn on the gray frame on the GPU (lr_draw_lines_device), written as <out_prefix>_lines.ppm; with
 // --warp also <out_prefix>_warp_lines.ppm: the rectified picture with the segments drawn through H.
+// --jpeg Q: the demo's products as it writes them (autorectify.cpp:368-369, imwrite) -- implies --warp; the rectified picture
+// is compressed where the warp left it in HBM (lr_encode_jpeg_device, quality Q, 4:2:0 for colour) and only the stream comes
+// back: <out_prefix>_warp.jpg, and with --lines also <out_prefix>_warp_lines.jpg.
 // Links against librectify_amd.so exactly like a program written for the reference.
 #include <algorithm>
 #include <cctype>
@@ -174,11 +178,39 @@ bool find_groups_device_prepared(const Gray& g, int max_size, bool refine, int t
     return ok;
 }
 
+// A picture that lies in HBM (ch 1: gray, ch 3: RGB, rows packed) as a baseline JPEG file: an extent of lr_jpeg_bound bytes,
+// one lr_encode_jpeg_device call, and the stream alone comes back.  Returns false with the reason on stderr.
+bool write_jpeg(lr_context* ctx, const void* d_img, int w, int h, int ch, int quality, const std::string& path) {
+    const int format = ch == 3 ? LR_PIX_U8X3 : LR_PIX_U8;
+    const size_t cap = lr_jpeg_bound(w, h, format, 0);
+    const double frame[8] = {(double)w, (double)h, 0, (double)w * ch, 0, (double)cap, (double)quality, 0};
+    void* d_jpg = nullptr;
+    uint64_t size = 0;
+    std::vector<uint8_t> stream;
+    bool ok = cap != 0 && lr_device_malloc(ctx, cap, &d_jpg) == 0 &&
+              lr_encode_jpeg_device(ctx, d_img, (size_t)w * h * ch, format, frame, 1, d_jpg, cap, &size) == 0 && size <= cap;
+    if (ok) {
+        stream.resize((size_t)size);
+        ok = lr_memcpy_d2h(ctx, stream.data(), d_jpg, stream.size()) == 0;
+    }
+    if (!ok) std::fprintf(stderr, "jpeg failed: %s\n", cap == 0 ? "a picture beyond 65535 pixels a side" : lr_last_error());
+    if (d_jpg) lr_device_free(ctx, d_jpg);
+    if (!ok) return false;
+    std::ofstream f(path, std::ios::binary);
+    f.write(reinterpret_cast<const char*>(stream.data()), (std::streamsize)stream.size());
+    if (!f) {
+        std::fprintf(stderr, "jpeg failed: cannot write %s\n", path.c_str());
+        return false;
+    }
+    std::printf("wrote %s (%dx%d, quality %d, %zu bytes)\n", path.c_str(), w, h, quality, stream.size());
+    return true;
+}
+
 // The demo's homography_from_corners(t, 3.0) + warpPerspective of the frame as read, on the GPU; writes
 // <prefix>_warp.pgm / .ppm.  Returns false with the reason on stderr.
-// `out`, `ow`, `oh` and `H` (source to rectified picture) are kept for --lines.
+// `out`, `ow`, `oh` and `H` (source to rectified picture) are kept for --lines.  jpeg > 0: <prefix>_warp.jpg as well.
 bool warp_frame(const Gray& g, const ImageTransform& t, const std::string& prefix, std::vector<uint8_t>& out, int& ow, int& oh,
-                double* H) {
+                double* H, int jpeg) {
     double M[9];
     lr_context* ctx = nullptr;
     void* d_src = nullptr;
@@ -195,12 +227,13 @@ bool warp_frame(const Gray& g, const ImageTransform& t, const std::string& prefi
              lr_memcpy_d2h(ctx, out.data(), d_dst, out.size()) == 0;
     }
     if (!ok) std::fprintf(stderr, "warp failed: %s\n", lr_last_error());
+    const bool jpeg_ok = !ok || jpeg <= 0 || write_jpeg(ctx, d_dst, ow, oh, g.ch, jpeg, prefix + "_warp.jpg");
     if (ctx) {
         if (d_src) lr_device_free(ctx, d_src);
         if (d_dst) lr_device_free(ctx, d_dst);
         lr_context_destroy(ctx);
     }
-    if (!ok) return false;
+    if (!ok || !jpeg_ok) return false;
     const std::string path = prefix + (g.ch == 3 ? "_warp.ppm" : "_warp.pgm");
     std::ofstream f(path, std::ios::binary);
     f << (g.ch == 3 ? "P6" : "P5") << "\n" << ow << " " << oh << "\n255\n";
@@ -214,9 +247,10 @@ bool warp_frame(const Gray& g, const ImageTransform& t, const std::string& prefi
 }
 
 // The demo's draw_lines on an 8-bit picture (ch 1: gray, every pixel v as (v, v, v); ch 3: drawn upon in place), the
-// segments through H if it is not null; writes `path` as a PPM.  Returns false with the reason on stderr.
+// segments through H if it is not null; writes `path` as a PPM, and with jpeg > 0 `jpg_path` as a JPEG file compressed
+// where the picture was drawn.  Returns false with the reason on stderr.
 bool lines_picture(const uint8_t* img, int w, int h, int ch, const LineSegment* lines, int n, const double* H,
-                   const std::string& path) {
+                   const std::string& path, int jpeg = 0, const std::string& jpg_path = std::string()) {
     lr_context* ctx = nullptr;
     void* d_img = nullptr;
     void* d_rgb = nullptr;
@@ -234,6 +268,7 @@ bool lines_picture(const uint8_t* img, int w, int h, int ch, const LineSegment* 
              lr_draw_lines_device(ctx, d_img, img_bytes, LR_PIX_U8, lines, (size_t)n, from_gray, 1, H, d_rgb, rgb_bytes) == 0 &&
              lr_memcpy_d2h(ctx, out.data(), d_rgb, rgb_bytes) == 0;
     if (!ok) std::fprintf(stderr, "lines picture failed: %s\n", lr_last_error());
+    if (ok && jpeg > 0) ok = write_jpeg(ctx, ch == 3 ? d_img : d_rgb, w, h, 3, jpeg, jpg_path);
     if (ctx) {
         if (d_img) lr_device_free(ctx, d_img);
         if (d_rgb) lr_device_free(ctx, d_rgb);
@@ -267,13 +302,13 @@ int main(int argc, char** argv) {
         std::fprintf(stderr,
                      "usage: %s in.pgm|in.ppm out_prefix [--max-size N|fraction] [--refine] [--threads N]\n"
                      "          [--h-strategy rotate_h|rotate_v|rectify|keep] [--v-strategy ...] [--warp] [--device-prepare]\n"
-                     "          [--lines]\n",
+                     "          [--lines] [--jpeg Q]\n",
                      argv[0]);
         return 2;
     }
     float max_size = 1200.f;  // the demo's default
     bool refine = false, warp = false, device_prepare = false, lines_pictures = false;
-    int threads = -1;
+    int threads = -1, jpeg = 0;
     RectificationConfig cfg;
     cfg.horizontal_vp_min_distance = 2;  // autorectify.cpp:347
     for (int i = 3; i < argc; ++i) {
@@ -285,6 +320,10 @@ int main(int argc, char** argv) {
         else if (a == "--lines") lines_pictures = true;
         else if (a == "--max-size" && has_val) max_size = (float)std::atof(argv[++i]);
         else if (a == "--threads" && has_val) threads = std::atoi(argv[++i]);
+        else if (a == "--jpeg" && has_val && std::atoi(argv[i + 1]) >= 1 && std::atoi(argv[i + 1]) <= 100) {
+            jpeg = std::atoi(argv[++i]);
+            warp = true;
+        }
         else if (a == "--h-strategy" && has_val && parse_strategy(argv[i + 1], cfg.h_strategy)) ++i;
         else if (a == "--v-strategy" && has_val && parse_strategy(argv[i + 1], cfg.v_strategy)) ++i;
         else {
@@ -342,12 +381,12 @@ int main(int argc, char** argv) {
     std::vector<uint8_t> warped;
     int ow = 0, oh = 0;
     double H[9];
-    bool ok = !warp || warp_frame(full, t, prefix, warped, ow, oh, H);
+    bool ok = !warp || warp_frame(full, t, prefix, warped, ow, oh, H, jpeg);
     if (ok && lines_pictures) {  // on the gray frame, as the demo draws (autorectify.cpp:364)
         std::vector<uint8_t> gray(full.px.size());
         for (size_t i = 0; i < gray.size(); ++i) gray[i] = (uint8_t)(full.px[i] * 256.0f);
         ok = lines_picture(gray.data(), full.w, full.h, 1, lines, n, nullptr, prefix + "_lines.ppm") &&
-             (!warp || lines_picture(warped.data(), ow, oh, full.ch, lines, n, H, prefix + "_warp_lines.ppm"));
+             (!warp || lines_picture(warped.data(), ow, oh, full.ch, lines, n, H, prefix + "_warp_lines.ppm", jpeg, prefix + "_warp_lines.jpg"));
     }
     if (!device_prepare) release_line_segments(&lines);
     if (!ok) return 1;

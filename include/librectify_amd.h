@@ -318,6 +318,69 @@ static inline int lr_draw_lines_device(lr_context* ctx, const void* d_src, size_
                                       d_dst, dst_bytes, 0, 0, 0);
 }
 
+/* The demo's products are JPEG files (autorectify.cpp:368-369, imwrite): lr_encode_jpeg_device compresses 8-bit frames that
+ * lie in HBM into baseline JPEG streams in HBM, so that only the streams (about a tenth of the pixels' bytes at quality 95)
+ * cross the link.  One chain of launches for a batch of frames of different sizes; the call is SYNCHRONOUS like the
+ * detector's entries: it waits for the context's stream, and on return sizes[b] (HOST) is the length of frame b's stream.
+ * `frames` is a HOST table of 8 doubles per frame: [0] [1] width_b, height_b (1 .. 65535), [2] [3] byte offset of the
+ * source from d_src and its row stride in bytes, [4] [5] byte offset of the stream from d_dst and its CAPACITY in bytes,
+ * [6] the quality, 1 .. 100, [7] the chroma layout: 0 = 4:2:0, 1 = 4:4:4 (0 for LR_PIX_U8).  format is LR_PIX_U8 (a
+ * one-component stream) or LR_PIX_U8X3 (c0 red: a YCbCr stream).  The table follows LR_WARP_RAGGED's rules: integers (at most
+ * 2^53), strides at least a row, every source inside src_bytes, every extent [offset, offset + capacity) inside dst_bytes,
+ * no two extents overlapping, the destination region apart from the source region.  The whole table is checked before
+ * anything is enqueued: on failure (also a null pointer, batch < 1, another format) nothing is launched or written, `sizes`
+ * is untouched and lr_last_error names the frame and the entry.
+ * sizes[b] is the stream's length EVEN WHEN IT EXCEEDS THE CAPACITY (the n_lines convention): a stream that fits is complete
+ * at its offset; of one that does not fit the extent's content is unspecified, and the call still returns 0.  No byte
+ * outside the frames' extents is ever written.  lr_jpeg_bound gives a capacity that always suffices.
+ * The stream (tests/numpy_jpeg_ref.py produces the same bytes): SOI, JFIF 1.01 APP0, DQT (the
+ * Annex K tables scaled by the IJG quality rule), SOF0 (8 bits), DHT (the Annex K tables), DRI, one interleaved scan with
+ * RSTm after every restart interval but the last, EOI.  A restart interval is 96 blocks whatever the width: 16 MCUs of
+ * 4:2:0, 32 of 4:4:4, 96 of one component.  A one-component stream carries table 0 only.  Colour conversion, the 2 x 2 mean,
+ * the forward DCT and the quantisation are exact, in integers.  Frames are padded to whole MCUs by replicating the last
+ * column and row; a 4:2:0 luminance block that holds no pixel of the frame is coded as libjpeg codes its dummy blocks (a DC
+ * difference of 0 and an end of block).
+ * The coefficients (2 bytes per sample of the padded components), the intervals' lengths and places belong to the context's
+ * workspace: lr_context_trim frees them.
+ * The library's table of exported symbols is full, so the call travels through lr_warp_perspective_device like
+ * lr_draw_lines_device: LR_WARP_JPEG or-ed into `format`, `M` pointing to an lr_jpeg_args, src_image_bytes and
+ * dst_image_bytes the two regions' sizes, and width, height, out_width, out_height and both row strides 0 (any other option
+ * bit or a non-zero one of these fails cleanly).  lr_encode_jpeg_device below is that call, spelled out. */
+typedef struct lr_jpeg_args {
+    const double* frames; /* HOST, 8 doubles per frame */
+    uint64_t* sizes;      /* HOST, one per frame: the streams' lengths */
+} lr_jpeg_args;
+enum lr_warp_jpeg { LR_WARP_JPEG = 0x2000 }; /* or-ed into `format` like lr_warp_option */
+static inline int lr_encode_jpeg_device(lr_context* ctx, const void* d_src, size_t src_bytes, int format, const double* frames,
+                                        int batch, void* d_dst, size_t dst_bytes, uint64_t* sizes) {
+    lr_jpeg_args a;
+    a.frames = frames;
+    a.sizes = sizes;
+    return lr_warp_perspective_device(ctx, d_src, src_bytes, batch, 0, 0, 0, format | LR_WARP_JPEG, (const double*)(const void*)&a,
+                                      d_dst, dst_bytes, 0, 0, 0);
+}
+/* The longest stream lr_encode_jpeg_device can produce for a frame (0 for a size outside 1 .. 65535 or another format).
+ * A block's longest code: its DC difference, at most 11 bits of code (chrominance category 11) and 11 of magnitude, and 63
+ * AC coefficients of at most 16 bits of code and 10 of magnitude each, 22 + 63 * 26 = 1660 bits = 207.5 bytes: 208, which
+ * also covers an interval's padding to a whole byte (96 blocks leave 48 bytes over).  Every byte can be 0xFF and is then
+ * followed by a stuffed zero: 416 per block.  Every interval but the last is followed by a 2-byte RSTm.  The markers and
+ * headers in front of the scan are 629 bytes (334 for one component), the EOI 2: 640 covers both. */
+static inline size_t lr_jpeg_bound(int width, int height, int format, int layout) {
+    size_t mcu, bpm, ri, mcus;
+    if (width < 1 || height < 1 || width > 65535 || height > 65535) return 0;
+    if (format == LR_PIX_U8 && layout == 0) {
+        mcu = 8; bpm = 1; ri = 96;
+    } else if (format == LR_PIX_U8X3 && layout == 0) {
+        mcu = 16; bpm = 6; ri = 16;
+    } else if (format == LR_PIX_U8X3 && layout == 1) {
+        mcu = 8; bpm = 3; ri = 32;
+    } else {
+        return 0;
+    }
+    mcus = (((size_t)width + mcu - 1) / mcu) * (((size_t)height + mcu - 1) / mcu);
+    return 640 + 2 * ((mcus + ri - 1) / ri) + 416 * mcus * bpm;
+}
+
 /* ---- stage API (tests, bench) --------------------------------------------------------- */
 /* Stage 1: fused 5x5 derivative filter + magnitude + direction bin + dilated-bin mask +
  * 5x5 non-max candidates (reference line_detector.cpp:41-49,126-182, filter.cpp:29-98,161-168). */

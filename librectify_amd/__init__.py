@@ -66,6 +66,10 @@ class DrawLinesArgs(C.Structure):  # lr_draw_lines_args
     _fields_ = [("lines", C.c_void_p), ("n_lines", C.c_size_t), ("frames", C.c_void_p), ("H", C.c_void_p)]
 
 
+class JpegArgs(C.Structure):  # lr_jpeg_args
+    _fields_ = [("frames", C.c_void_p), ("sizes", C.c_void_p)]
+
+
 BUF_DX, BUF_DY, BUF_DMASK, BUF_LABEL, BUF_SEED_IDX, BUF_SEED_BIN, BUF_SEED_THR, BUF_MAXMAG, BUF_SEED_SIZE = range(9)
 T_UPLOAD, T_FILTER, T_SEEDS, T_FLOOD, T_FIT, T_RANSAC, T_TOTAL, T_FILTER_KERNEL, T_COUNT = range(9)
 PIX_U8, PIX_U8X3, PIX_F32 = range(3)  # enum lr_pixel_format
@@ -73,6 +77,7 @@ WARP_PREPARE = 0x100  # enum lr_warp_option, or-ed into the format of lr_warp_pe
 WARP_PACKED = 0x200  # enum lr_warp_layout, likewise: per-frame output sizes and places (warp_table)
 WARP_RAGGED = 0x800  # enum lr_warp_sources, likewise: per-frame source sizes and places as well (ragged_table)
 WARP_LINES = 0x1000  # enum lr_warp_lines, likewise: lr_draw_lines_device, whose own arguments travel behind M (DrawLinesArgs)
+WARP_JPEG = 0x2000  # enum lr_warp_jpeg, likewise: lr_encode_jpeg_device, whose own arguments travel behind M (JpegArgs)
 FRAMES_U8, FRAMES_U8X3, FRAMES_F32 = 0x100, 0x200, 0x300  # enum lr_frames_option, or-ed into `refine` of the frame entries
 
 
@@ -331,6 +336,61 @@ def draw_table(sizes, sources, outputs, segments):
     return table.astype(np.float64)
 
 
+def jpeg_bound(width, height, fmt, layout=0):
+    """lr_jpeg_bound: the longest stream lr_encode_jpeg_device can produce for a width x height frame of format fmt (PIX_U8,
+    PIX_U8X3) and chroma layout (0 = 4:2:0, 1 = 4:4:4; 0 for PIX_U8): 416 bytes a block (1660 bits of code, every byte
+    stuffed), 2 per restart interval, 640 for the headers and the EOI.  0 for a size outside 1 .. 65535 or another format."""
+    width, height = int(width), int(height)
+    if not (1 <= width <= 65535 and 1 <= height <= 65535):
+        return 0
+    if fmt == PIX_U8 and layout == 0:
+        mcu, bpm, ri = 8, 1, 96
+    elif fmt == PIX_U8X3 and layout == 0:
+        mcu, bpm, ri = 16, 6, 16
+    elif fmt == PIX_U8X3 and layout == 1:
+        mcu, bpm, ri = 8, 3, 32
+    else:
+        return 0
+    mcus = ((width + mcu - 1) // mcu) * ((height + mcu - 1) // mcu)
+    return 640 + 2 * ((mcus + ri - 1) // ri) + 416 * mcus * bpm
+
+
+def jpeg_table(sizes, sources, outputs, quality, layout=0):
+    """The table of lr_encode_jpeg_device: sizes: B pairs (width, height); sources: B pairs (byte_offset, row_bytes) of the
+    frames in the source region; outputs: B pairs (byte_offset, capacity) of the streams' extents in the destination
+    region; quality (1 .. 100) and layout (0 = 4:2:0, 1 = 4:4:4): one value for all frames, or B values.  Returns float64
+    (B, 8).  Rejects what can be seen without the regions: sizes outside 1 .. 65535, entries below 0 or above 2^53, a
+    quality outside 1 .. 100, a layout other than 0 or 1, extents that overlap.  Needs no GPU."""
+    sz = np.asarray(sizes)
+    if sz.ndim != 2 or sz.shape[1] != 2 or not np.issubdtype(sz.dtype, np.integer) or len(sz) < 1:
+        raise ValueError("jpeg_table: sizes is B pairs of integers (width, height), B >= 1")
+    B = len(sz)
+    cols = [sz]
+    for name, a in (("sources", sources), ("outputs", outputs)):
+        a = np.asarray(a)
+        if a.shape != (B, 2) or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("jpeg_table: %s is B pairs of integers" % name)
+        cols.append(a)
+    for name, a in (("quality", quality), ("layout", layout)):
+        a = np.asarray(a)
+        if not np.issubdtype(a.dtype, np.integer) or a.shape not in ((), (B,)):
+            raise ValueError("jpeg_table: %s is an integer, or B integers" % name)
+        cols.append(np.broadcast_to(a, (B,)).reshape(B, 1))
+    table = np.concatenate([c.astype(np.int64) for c in cols], axis=1)
+    if table.min() < 0 or table.max() > 2 ** 53:
+        raise ValueError("jpeg_table: an entry below 0 or above 2^53")
+    if int(sz.min()) < 1 or int(sz.max()) > 65535:
+        raise ValueError("jpeg_table: a size outside 1 .. 65535")
+    if int(table[:, 6].min()) < 1 or int(table[:, 6].max()) > 100:
+        raise ValueError("jpeg_table: a quality outside 1 .. 100")
+    if int(table[:, 7].max()) > 1:
+        raise ValueError("jpeg_table: a layout other than 0 (4:2:0) or 1 (4:4:4)")
+    ext = sorted((int(o), int(o) + int(c)) for o, c in table[:, 4:6].tolist())
+    if any(b[0] < a[1] for a, b in zip(ext, ext[1:])):
+        raise ValueError("jpeg_table: two frames' extents overlap")
+    return table.astype(np.float64)
+
+
 def _source_extent(sources, bpp):
     """bytes of the region that holds the sources (width, height, byte_offset, row_bytes)"""
     return max(off + (h - 1) * row + w * bpp for w, h, off, row in sources)
@@ -559,10 +619,12 @@ class Context:
                                                 fmt | WARP_LINES, C.cast(C.byref(args), C.c_void_p), C.c_void_p(d_dst),
                                                 dst_bytes, 0, 0, 0))
 
-    def draw_lines_batch(self, frames, lines_list, Hs=None):
+    def draw_lines_batch(self, frames, lines_list, Hs=None, jpeg=None):
         """The demo's lines picture for a list of 8-bit frames of different shapes (all gray H x W, or all H x W x 3) and
         their segments (one LINE_DTYPE array per frame; Hs: one 3x3 per frame, or None): one upload, one
-        lr_draw_lines_device call, one download.  Returns the list of H x W x 3 uint8 pictures: a loop of draw_lines."""
+        lr_draw_lines_device call, one download.  Returns the list of H x W x 3 uint8 pictures: a loop of draw_lines.
+        jpeg=Q: the pictures stay in HBM, are encoded there (lr_encode_jpeg_device, quality Q, 4:2:0) and come back as JPEG files
+        (bytes): exactly the encoder's stream of the picture that jpeg=None returns."""
         frames = [np.ascontiguousarray(f) for f in frames]
         if not frames or len(lines_list) != len(frames) or (Hs is not None and len(Hs) != len(frames)):
             raise ValueError("draw_lines_batch: as many line arrays (and Hs) as frames, at least one")
@@ -591,6 +653,9 @@ class Context:
         try:
             _check(lib().lr_device_malloc(self._h, dst_end, C.byref(d_dst)))
             self.draw_lines_device(d_src, src_end, fmt, np.concatenate(lines_list), table, d_dst.value, dst_end, H=Hs)
+            if jpeg is not None:
+                info = [(w, h, off, row) for (w, h), (off, row) in zip(sizes, outputs)]
+                return self._encode_resident(d_dst.value, dst_end, PIX_U8X3, info, jpeg, 0)
             out = self.device_download(d_dst.value, (dst_end,), np.uint8)
         finally:
             self.device_free(d_src)
@@ -602,6 +667,86 @@ class Context:
         """The demo's lines picture of one 8-bit frame (H x W gray or H x W x 3) and the detector's segments, drawn through
         H (3x3) if given: upload, one launch, download.  Returns H x W x 3 uint8."""
         return self.draw_lines_batch([image_u8], [lines], None if H is None else [H])[0]
+
+    # ---- JPEG streams ----
+    jpeg_first_capacity = None  # test hook: bytes of every frame's extent in the first pass of _encode_resident
+
+    def encode_jpeg_device(self, d_src, src_bytes, fmt, table, d_dst, dst_bytes):
+        """lr_encode_jpeg_device (lr_warp_perspective_device with LR_WARP_JPEG): baseline JPEG streams of the table's 8-bit
+        frames (fmt PIX_U8 or PIX_U8X3) in the src_bytes at d_src, each into its extent of the dst_bytes at d_dst.
+        table: 8 doubles per frame (jpeg_table).  Synchronous.  Returns the streams' lengths (uint64, one per frame), a
+        length above its frame's capacity meaning that the stream did not fit and the extent's content is unspecified."""
+        table = np.ascontiguousarray(table, np.float64)
+        if table.ndim != 2 or table.shape[1] != 8 or len(table) < 1:
+            raise ValueError("encode_jpeg_device: the table has 8 values per frame")
+        sizes = np.zeros(len(table), np.uint64)
+        args = JpegArgs(_ptr(table), _ptr(sizes))
+        _check(lib().lr_warp_perspective_device(self._h, C.c_void_p(d_src), src_bytes, len(table), 0, 0, 0, fmt | WARP_JPEG,
+                                                C.cast(C.byref(args), C.c_void_p), C.c_void_p(d_dst), dst_bytes, 0, 0, 0))
+        return sizes
+
+    def _encode_resident(self, d_src, src_bytes, fmt, frames, quality, layout):
+        """JPEG streams (bytes) of resident frames (width, height, byte_offset, row_bytes): one call with a modest extent per
+        frame (half the frame's bytes, or its bound if that is less), a second one with jpeg_bound for the frames whose
+        streams did not fit, and a download of the streams alone."""
+        bpp = 3 if fmt == PIX_U8X3 else 1
+        out = [None] * len(frames)
+        todo = list(range(len(frames)))
+        for attempt in (0, 1):
+            caps = []
+            for b in todo:
+                w, h = frames[b][:2]
+                bound = jpeg_bound(w, h, fmt, layout)
+                first = w * h * bpp // 2 + 1024 if self.jpeg_first_capacity is None else int(self.jpeg_first_capacity)
+                caps.append(bound if attempt else min(bound, first))
+            offs = np.concatenate([[0], np.cumsum(caps)]).astype(np.int64)
+            table = jpeg_table(np.array([frames[b][:2] for b in todo], np.int64), np.array([frames[b][2:] for b in todo], np.int64),
+                               np.stack([offs[:-1], np.array(caps, np.int64)], axis=1), int(quality), int(layout))
+            d_dst = C.c_void_p()
+            _check(lib().lr_device_malloc(self._h, int(offs[-1]), C.byref(d_dst)))
+            try:
+                sizes = self.encode_jpeg_device(d_src, src_bytes, fmt, table, d_dst.value, int(offs[-1]))
+                left = []
+                for b, off, cap, n in zip(todo, offs[:-1].tolist(), caps, sizes.tolist()):
+                    if n <= cap:
+                        out[b] = self.device_download(d_dst.value + off, (n,), np.uint8).tobytes()
+                    else:
+                        left.append(b)
+            finally:
+                self.device_free(d_dst.value)
+            todo = left
+            if not todo:
+                break
+        if todo:
+            raise LibrectifyError("encode_jpeg: a stream longer than jpeg_bound")
+        return out
+
+    def encode_jpeg_batch(self, frames, quality=95, layout=0):
+        """Baseline JPEG files of a list of 8-bit frames of any sizes (all H x W, or all H x W x 3 with c0 red): one upload,
+        one lr_encode_jpeg_device call (a second for frames whose streams outgrow half their pixels' bytes), and a download
+        of the streams only.  layout: 0 = 4:2:0, 1 = 4:4:4 (colour frames).  Returns a list of bytes."""
+        frames = [np.ascontiguousarray(f) for f in frames]
+        if not frames:
+            raise ValueError("encode_jpeg_batch: no frames")
+        formats = [_frame_format(f, "encode_jpeg") for f in frames]
+        fmt, bpp = formats[0]
+        if fmt == PIX_F32 or any(f != formats[0] for f in formats):
+            raise ValueError("encode_jpeg_batch: uint8 frames, all H x W or all H x W x 3")
+        info, end = [], 0
+        for f in frames:
+            h, w = f.shape[:2]
+            info.append((w, h, end, w * bpp))
+            end += f.nbytes
+        region = np.concatenate([f.reshape(-1) for f in frames])
+        d_src = self.device_upload(region)
+        try:
+            return self._encode_resident(d_src, end, fmt, info, quality, layout)
+        finally:
+            self.device_free(d_src)
+
+    def encode_jpeg(self, image_u8, quality=95, layout=0):
+        """The baseline JPEG file (bytes) of one 8-bit frame, H x W or H x W x 3 (c0 red), encoded on the GPU."""
+        return self.encode_jpeg_batch([image_u8], quality, layout)[0]
 
     def prepare_device(self, d_src, src_image_bytes, batch, width, height, src_row_bytes, fmt, d_dst, dst_image_bytes,
                        out_width, out_height, dst_row_bytes):
@@ -660,7 +805,7 @@ class Context:
                 if p.value:
                     self.device_free(p.value)
 
-    def rectify(self, image_u8, min_length=None, refine=False, cfg=None, clip=3.0, max_size=None):
+    def rectify(self, image_u8, min_length=None, refine=False, cfg=None, clip=3.0, max_size=None, jpeg=None):
         """The reference demo's pipeline (autorectify.cpp) on an 8-bit frame (H x W gray or H x W x 3 RGB): luma
         (4899 R + 9617 G + 1868 B + 8192) >> 14, / 256, find_line_segment_groups with min_length max(w, h) / 100 by
         default, compute_rectification_transform (cfg: the demo's, horizontal_vp_min_distance = 2),
@@ -670,10 +815,17 @@ class Context:
         demo's default is 1200; below 1 a fraction of the longer side): with it -- the 8-bit frame is uploaded once,
         prepared on the device (prepare_device) to prepared_size(w, h, max_size), the detector runs on that with
         min_length max(w', h') / 100, the endpoints are divided by the scale, the transform is the full frame's and the
-        warp reads the same resident frame."""
+        warp reads the same resident frame.
+        jpeg=Q: `warped` is the rectified picture's JPEG file (bytes, quality Q, 4:2:0), encoded in HBM: rectify_batch's
+        path for one frame."""
         img = np.ascontiguousarray(image_u8)
         if img.dtype != np.uint8 or not (img.ndim == 2 or (img.ndim == 3 and img.shape[2] == 3)):
             raise ValueError("rectify: an H x W or H x W x 3 uint8 frame")
+        if jpeg is not None:
+            lines, t, stream = self.rectify_batch(img[None], min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, jpeg=jpeg)[0]
+            if stream is None:
+                rectification_homography(t, clip)  # (raises what rectify raises for such a frame)
+            return lines, t, stream
         if max_size is not None:
             return self._rectify_prepared(img, max_size, min_length, refine, cfg or RectificationConfig(hmin=2.0), clip)
         fmt, bpp = _frame_format(img, "rectify")
@@ -899,7 +1051,16 @@ class Context:
                 if p.value:
                     self.device_free(p.value)
 
-    def _rectify_mixed(self, frames, min_length, refine, cfg, clip, max_size, capacity):
+    def _jpeg_results(self, d_out, total, fmt, table, quality):
+        """the warped pictures at d_out (rows of `table`: columns 9..12 width, height, offset, stride) as JPEG files"""
+        good = [b for b in range(len(table)) if table[b, 9]]
+        streams = self._encode_resident(d_out, total, fmt, [tuple(int(v) for v in table[b, 9:13]) for b in good], quality, 0) if good else []
+        out = [None] * len(table)
+        for b, s in zip(good, streams):
+            out[b] = s
+        return out
+
+    def _rectify_mixed(self, frames, min_length, refine, cfg, clip, max_size, capacity, jpeg=None):
         """rectify_batch for a list of 8-bit frames of different shapes: all frames in one host buffer, one upload,
         rectify_frames_device, one download"""
         frames = [np.ascontiguousarray(f) for f in frames]
@@ -920,6 +1081,9 @@ class Context:
         d_out = None
         try:
             lines, tfs, table, d_out, total = self.rectify_frames_device(d_src, sources, fmt, min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, capacity=capacity)
+            if jpeg is not None:
+                streams = self._jpeg_results(d_out, total, fmt, table, jpeg) if d_out else [None] * len(frames)
+                return [(lines[b], tfs[b], streams[b]) for b in range(len(frames))]
             packed = self.device_download(d_out, (total,), np.uint8) if d_out else None
         finally:
             self.device_free(d_src)
@@ -935,17 +1099,21 @@ class Context:
             res.append((lines[b], tfs[b], img))
         return res
 
-    def rectify_batch(self, frames_u8, min_length=None, refine=False, cfg=None, clip=3.0, max_size=None, capacity=4096):
+    def rectify_batch(self, frames_u8, min_length=None, refine=False, cfg=None, clip=3.0, max_size=None, capacity=4096, jpeg=None):
         """Context.rectify for a batch: frames_u8 is a uint8 array [B, H, W] or [B, H, W, 3], or a list of such frames of one
         shape.  One upload, rectify_batch_device (one detector batch, the packed warp), one download.  Returns a
         list of (lines, transform, warped), frame by frame what rectify returns for it; warped is None for a frame whose
         homography cannot be formed.  A list of frames of DIFFERENT shapes (all H x W or all H x W x 3) takes the
         mixed-size pipeline: all frames in one host buffer, one upload, rectify_frames_device (one ragged prepare, one
-        detector call with a frame table, one ragged warp launch), one download -- frame by frame what rectify returns."""
+        detector call with a frame table, one ragged warp launch), one download -- frame by frame what rectify returns.
+        jpeg=Q (1 .. 100): the warped pictures stay in HBM and are encoded there (lr_encode_jpeg_device, quality Q, 4:2:0 for
+        colour frames); `warped` is then the JPEG file as bytes -- exactly the encoder's stream of the picture that jpeg=None
+        returns -- and only the streams' lengths and the streams cross the link.  A frame whose stream outgrows a first
+        extent of half its pixels' bytes is encoded again with room for jpeg_bound, so nothing is ever cut."""
         if not isinstance(frames_u8, np.ndarray):
             frames_u8 = [np.asarray(f) for f in frames_u8]
             if len({f.shape for f in frames_u8}) > 1:
-                return self._rectify_mixed(frames_u8, min_length, refine, cfg, clip, max_size, capacity)
+                return self._rectify_mixed(frames_u8, min_length, refine, cfg, clip, max_size, capacity, jpeg)
         a = np.ascontiguousarray(frames_u8 if isinstance(frames_u8, np.ndarray) else np.stack([np.asarray(f) for f in frames_u8]))
         if a.dtype != np.uint8 or a.ndim not in (3, 4) or (a.ndim == 4 and a.shape[3] != 3) or a.shape[0] < 1:
             raise ValueError("rectify_batch: uint8 frames [B, H, W] or [B, H, W, 3]")
@@ -955,6 +1123,9 @@ class Context:
         d_out = None
         try:
             lines, tfs, table, d_out, total = self.rectify_batch_device(d_src, batch, w, h, fmt, min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, capacity=capacity)
+            if jpeg is not None:
+                streams = self._jpeg_results(d_out, total, fmt, table, jpeg) if d_out else [None] * batch
+                return [(lines[b], tfs[b], streams[b]) for b in range(batch)]
             packed = self.device_download(d_out, (total,), np.uint8) if d_out else None
         finally:
             self.device_free(d_src)

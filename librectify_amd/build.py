@@ -20,6 +20,7 @@ SOURCES = [
     "kernels_warp.hip",
     "kernels_prepare.hip",
     "kernels_overlay.hip",
+    "kernels_jpeg.hip",
     "context.hip",
     "upload.hip",
     "frame.hip",

@@ -123,6 +123,16 @@ struct PrepareSpans {
 struct OverlayStore {
     MirroredBuffer<unsigned char> block;
 };
+
+// lr_encode_jpeg_device (kernels_jpeg.hip): a call's frame records, prefix tables and code tables going up and the streams'
+// lengths coming back (block), the quantised coefficients (2 bytes per sample of the padded components), the restart
+// intervals' lengths and places in their streams; all sized by the call
+struct JpegStore {
+    MirroredBuffer<unsigned char> block;
+    DeviceBuffer<int16_t> coef;
+    DeviceBuffer<uint32_t> len;
+    DeviceBuffer<unsigned long long> place;
+};
 }  // namespace lramd
 
 struct lr_context {
@@ -142,6 +152,7 @@ struct lr_context {
     lramd::Event ev_prep_ragged;  // the last upload from prep.ragged.h
     lramd::OverlayStore overlay;
     lramd::Event ev_overlay;  // the last upload from overlay.block.h (rewritten only once that has been read)
+    lramd::JpegStore jpeg;
 
     lramd::Event ev_up[2];
     lramd::Event ev_wait;  // (blocking-sync flag) what a batch lane sleeps on
@@ -321,6 +332,10 @@ int ctx_prepare_ragged(lr_context* c, const void* d_src, size_t src_bytes, int b
 // on the host, uploads them and enqueues one launch)
 int ctx_draw_lines(lr_context* c, const void* d_src, size_t src_bytes, int format, const LineSegment* lines, size_t n_lines,
                    const double* frames, int batch, const double* H, void* d_dst, size_t dst_bytes);
+// kernels_jpeg.hip: lr_encode_jpeg_device (validates the whole table, builds the headers and tables on the host, enqueues the
+// transform, the two entropy passes and the scan between them, and waits for the streams' lengths)
+int ctx_encode_jpeg(lr_context* c, const void* d_src, size_t src_bytes, int format, const double* frames, int batch, void* d_dst,
+                    size_t dst_bytes, uint64_t* sizes);
 // bytes one frame spans: (rows - 1) * row_bytes + last_row_bytes; false if that does not fit in 64 bits
 inline bool frame_span(int rows, size_t row_bytes, size_t last_row_bytes, size_t* out) {
     size_t s;

@@ -64,6 +64,7 @@ int ctx_trim(lr_context* c, bool frames_too) {
         c->prep = PrepareSpans{};  // (sized by a frame's width + height)
         c->warp_m = MirroredBuffer<double>{};  // (sized by the largest batch warped)
         c->overlay = OverlayStore{};           // (sized by the most segments drawn in a call)
+        c->jpeg = JpegStore{};                 // (coefficients and interval tables of the largest batch encoded)
     }
     c->small_frames = 0;
     c->w = c->h = 0;

@@ -26,6 +26,7 @@
 // search and bands; the frame's record (18 doubles long, like the caller's row) also carries the source's offset from the
 // source pointer, its size and its row stride, all uniform across the workgroup.
 //
+// LR_WARP_JPEG is none either: lr_encode_jpeg_device's call goes on to kernels_jpeg.hip.
 // LR_WARP_LINES is no warp: the entry hands lr_draw_lines_device's call on to kernels_overlay.hip (the export table is full).
 #include <algorithm>
 #include <cmath>
@@ -616,6 +617,14 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
         return 1;
     };
     if (!c) return fail("no context");
+    if (format & LR_WARP_JPEG) {  // lr_encode_jpeg_device (kernels_jpeg.hip): its own arguments arrive behind M
+        if ((format & ~0xFF) != LR_WARP_JPEG) return fail("LR_WARP_JPEG together with another option bit");
+        if (width != 0 || height != 0 || src_row_bytes != 0 || out_width != 0 || out_height != 0 || dst_row_bytes != 0)
+            return fail("LR_WARP_JPEG: width, height, out_width, out_height and the row strides must be 0 (they are in the frame table)");
+        if (!M) return fail("LR_WARP_JPEG: null pointer (lr_jpeg_args)");
+        const lr_jpeg_args* a = reinterpret_cast<const lr_jpeg_args*>(M);
+        return ctx_encode_jpeg(c, d_src, src_image_bytes, format & 0xFF, a->frames, batch, d_dst, dst_image_bytes, a->sizes);
+    }
     if (format & LR_WARP_LINES) {  // lr_draw_lines_device (kernels_overlay.hip): its own arguments arrive behind M
         if ((format & ~0xFF) != LR_WARP_LINES) return fail("LR_WARP_LINES together with another option bit");
         if (width != 0 || height != 0 || src_row_bytes != 0 || out_width != 0 || out_height != 0 || dst_row_bytes != 0)
