@@ -191,7 +191,8 @@ struct lr_context {
     lramd::MirroredBuffer<uint32_t> cht_idx;   // lines a peeling round of the diamond-space estimator takes out of the accumulator
     lramd::MirroredBuffer<uint32_t> cht_peak;  // {cell, value lo, value hi, -, votes lo, votes hi}
     // lr_warp_perspective_device: the frames' maps (9 doubles each) go up from page-locked memory on the context's stream;
-    // with LR_WARP_PACKED a record of 13 doubles per frame and the tiles' prefix table (sized by the batch: ctx_trim)
+    // with LR_WARP_PACKED or LR_WARP_RAGGED a record of 18 doubles per frame and the tiles' prefix table (sized by the
+    // batch: ctx_trim)
     lramd::MirroredBuffer<double> warp_m;
     lramd::Event ev_warp_m;    // the last upload from warp_m.h (rewritten only once that has been read)
     // RANSAC

@@ -25,7 +25,8 @@
 #include <utility>
 #include <vector>
 
-#include "context.h"
+#include "tables.h"
+#include "tiles.h"
 
 namespace lramd {
 namespace {
@@ -58,17 +59,6 @@ __device__ constexpr int kDctHalf[8][4] = {{2896, 2896, 2896, 2896},  {4017, 340
 __device__ const uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
                                         41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
                                         30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-// start[b] <= i < start[b + 1]
-__device__ __forceinline__ int find_frame(const int* __restrict__ start, int batch, int i) {
-    int b = 0, hi = batch;
-    while (hi - b > 1) {
-        const int mid = (b + hi) >> 1;
-        if (start[mid] <= i) b = mid;
-        else hi = mid;
-    }
-    return b;
-}
 
 // one pass of the DCT over eight values: out[u] = sum_x T[u][x] s[x] (every |s| < 2^23 and every product < 2^31)
 __device__ __forceinline__ void dct8(const int (&s)[8], int (&out)[8]) {
@@ -107,7 +97,7 @@ __global__ __launch_bounds__(kWave) void jpeg_transform_kernel(const uint8_t* __
     __shared__ int s_t[8][65];
     const int lane = (int)threadIdx.x, k = lane >> 3, r = lane & 7;
     for (int grp = (int)blockIdx.x; grp < n_groups; grp += (int)gridDim.x) {
-        const int b = find_frame(grp_start, batch, grp);
+        const int b = frame_of_tile(grp_start, batch, grp);
         const JpegFrame* f = frames + b;
         const int w = f->w, h = f->h, bpm = f->bpm, layout = f->layout;
         const int blk = (grp - grp_start[b]) * 8 + k;
@@ -302,7 +292,7 @@ __global__ __launch_bounds__(kWave) void jpeg_entropy_kernel(const int16_t* __re
     const int lane = (int)threadIdx.x;
     for (int i = lane; i < kHuffWords; i += kWave) s_huff[i] = huff[i];
     for (int it = (int)blockIdx.x; it < n_intervals; it += (int)gridDim.x) {
-        const int b = find_frame(ivl_start, batch, it);
+        const int b = frame_of_tile(ivl_start, batch, it);
         const JpegFrame* f = frames + b;
         const int ii = it - ivl_start[b], layout = f->layout;
         const int first_mcu = ii * f->ri;
@@ -516,12 +506,6 @@ int write_header(JpegFrame& f, int components) {
     return h.n;
 }
 
-bool table_integer(double v, double lo, double hi, uint64_t* out) {
-    if (!(v >= lo && v <= hi) || v != std::floor(v)) return false;
-    *out = (uint64_t)v;
-    return true;
-}
-
 }  // namespace
 
 int ctx_encode_jpeg(lr_context* c, const void* d_src, size_t src_bytes, int format, const double* T, int batch, void* d_dst,
@@ -543,7 +527,6 @@ int ctx_encode_jpeg(lr_context* c, const void* d_src, size_t src_bytes, int form
     }
 
     // the table, as a whole
-    constexpr double kExact = 9007199254740992.0;  // 2^53: integers up to it are doubles
     const uint64_t bpp = format == LR_PIX_U8 ? 1 : 3;
     const int components = format == LR_PIX_U8 ? 1 : 3;
     std::vector<JpegFrame> fr((size_t)batch);
@@ -600,13 +583,11 @@ int ctx_encode_jpeg(lr_context* c, const void* d_src, size_t src_bytes, int form
     ivl_start[(size_t)batch] = (int)n_intervals;
     {
         std::vector<std::pair<uint64_t, uint64_t>> sorted = extent;
-        std::sort(sorted.begin(), sorted.end());
-        for (int b = 1; b < batch; ++b)
-            if (sorted[(size_t)b].first < sorted[(size_t)b - 1].second) {
-                int which = 0;
-                while (extent[(size_t)which] != sorted[(size_t)b]) ++which;
-                return fail_at(which, 4, "(stream offset): two frames' extents overlap");
-            }
+        if (const size_t at = extents_overlap(sorted)) {
+            int which = 0;
+            while (extent[(size_t)which] != sorted[at]) ++which;
+            return fail_at(which, 4, "(stream offset): two frames' extents overlap");
+        }
     }
 
     // one block of the mirror: frames | group prefix | interval prefix | code tables | the streams' lengths (coming back)
@@ -616,7 +597,9 @@ int ctx_encode_jpeg(lr_context* c, const void* d_src, size_t src_bytes, int form
     const size_t o_sizes = up8(o_huff + kHuffWords * sizeof(uint32_t)), need = o_sizes + (size_t)batch * sizeof(unsigned long long);
     LR_HIP(hipSetDevice(c->device));
     JpegStore& js = c->jpeg;
-    // (the call is synchronous: nothing of an earlier one is in flight when these are replaced)
+    // (the call is synchronous: nothing of an earlier one is in flight when these are replaced, so the block needs neither
+    // the stream synchronise before a grow nor an event behind the copy, and upload_reserve / upload_send of tables.h,
+    // which are that pair, are not used here)
     if (need > js.block.cap() && js.block.grow(need + need / 2)) return 1;
     const size_t n_coef = (size_t)n_groups * 8 * 64;
     if (n_coef > js.coef.cap() && js.coef.grow(n_coef)) return 1;

@@ -28,7 +28,8 @@
 #include <utility>
 #include <vector>
 
-#include "context.h"
+#include "tables.h"
+#include "tiles.h"
 
 namespace lramd {
 namespace {
@@ -72,18 +73,9 @@ __global__ __launch_bounds__(kBlock) void overlay_kernel(const uint8_t* __restri
     __shared__ int s_cnt[kBlock / 64];
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lx = lane & 15, row_in_tile = wave * 4 + (lane >> 4);
-    // XCD band order, as the warp's tiles
-    const int per_xcd = (n_tiles + 7) / 8;
-    const int xcd = (int)(blockIdx.x & 7u), slots = (int)(gridDim.x >> 3);
-    for (int j = (int)(blockIdx.x >> 3); j < per_xcd; j += slots) {
-        const int tile = xcd * per_xcd + j;
-        if (tile >= n_tiles) return;
-        int b = 0, hi = batch;  // start[b] <= tile < start[hi]
-        while (hi - b > 1) {
-            const int mid = (b + hi) >> 1;
-            if (start[mid] <= tile) b = mid;
-            else hi = mid;
-        }
+    XcdBand band(n_tiles);
+    for (int tile; band.next(&tile);) {
+        const int b = frame_of_tile(start, batch, tile);
         const OverlayFrame* f = frames + b;
         const int w = f->w, h = f->h, tiles_x = f->tiles_x;
         const int r = tile - start[b];
@@ -231,13 +223,6 @@ __global__ __launch_bounds__(kBlock) void overlay_kernel(const uint8_t* __restri
     }
 }
 
-// v as an integer in [lo, hi], if it is one
-bool table_integer(double v, double lo, double hi, uint64_t* out) {
-    if (!(v >= lo && v <= hi) || v != std::floor(v)) return false;
-    *out = (uint64_t)v;
-    return true;
-}
-
 // a coordinate truncated toward zero, as the demo's int(l.x1); false if it is not drawn (not finite, or beyond 2^24)
 bool truncated(double v, int* out) {
     if (!std::isfinite(v)) return false;
@@ -303,7 +288,6 @@ int ctx_draw_lines(lr_context* c, const void* d_src, size_t src_bytes, int forma
             if (!std::isfinite(H[i])) return fail("frame " + std::to_string(i / 9) + ": H is not finite");
 
     // the table, as a whole
-    constexpr double kExact = 9007199254740992.0;  // 2^53: integers up to it are doubles
     const uint64_t bpp = format == LR_PIX_U8 ? 1 : 3;
     std::vector<FrameEntry> e((size_t)batch);
     std::vector<std::pair<uint64_t, uint64_t>> extent((size_t)batch);  // of the outputs: [first byte, end)
@@ -345,13 +329,11 @@ int ctx_draw_lines(lr_context* c, const void* d_src, size_t src_bytes, int forma
     }
     {
         std::vector<std::pair<uint64_t, uint64_t>> sorted = extent;
-        std::sort(sorted.begin(), sorted.end());
-        for (int b = 1; b < batch; ++b)
-            if (sorted[(size_t)b].first < sorted[(size_t)b - 1].second) {
-                int which = 0;
-                while (extent[(size_t)which] != sorted[(size_t)b]) ++which;
-                return fail_at(which, 4, "(output offset): two frames' output extents overlap");
-            }
+        if (const size_t at = extents_overlap(sorted)) {
+            int which = 0;
+            while (extent[(size_t)which] != sorted[at]) ++which;
+            return fail_at(which, 4, "(output offset): two frames' output extents overlap");
+        }
     }
     if (n_recs > ((uint64_t)1 << 28)) return fail("more than 2^28 segments in the frames' ranges together");
 
@@ -437,19 +419,13 @@ int ctx_draw_lines(lr_context* c, const void* d_src, size_t src_bytes, int forma
     const size_t o_recs = up8(o_list + list.size() * sizeof(uint32_t)), need = o_recs + recs.size() * sizeof(OverlayRec);
     LR_HIP(hipSetDevice(c->device));
     MirroredBuffer<unsigned char>& m = c->overlay.block;
-    if (need > m.cap()) {  // (grows: the buffers of a previous call may still be read by its launch)
-        LR_HIP(hipStreamSynchronize(c->stream));
-        if (m.grow(need + need / 2)) return 1;
-    }
-    if (c->ev_overlay.ensure(hipEventDisableTiming)) return 1;
-    LR_HIP(hipEventSynchronize(c->ev_overlay));  // the previous call's upload has read the mirror
+    if (upload_reserve(c, m, c->ev_overlay, need, need + need / 2)) return 1;
     std::memcpy(m.h + o_frames, fr.data(), fr.size() * sizeof(OverlayFrame));
     std::memcpy(m.h + o_start, start.data(), start.size() * sizeof(int));
     if (!bins.empty()) std::memcpy(m.h + o_bins, bins.data(), bins.size() * sizeof(uint2));
     if (!list.empty()) std::memcpy(m.h + o_list, list.data(), list.size() * sizeof(uint32_t));
     if (!recs.empty()) std::memcpy(m.h + o_recs, recs.data(), recs.size() * sizeof(OverlayRec));
-    LR_HIP(hipMemcpyAsync(m.d, m.h, need, hipMemcpyHostToDevice, c->stream));
-    LR_HIP(hipEventRecord(c->ev_overlay, c->stream));
+    if (upload_send(c, m, c->ev_overlay, need)) return 1;
 
     const unsigned char* d = m.d.get();
     const OverlayFrame* d_frames = reinterpret_cast<const OverlayFrame*>(d + o_frames);

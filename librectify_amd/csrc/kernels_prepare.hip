@@ -24,8 +24,10 @@
 // order, each multiply and add rounded on its own (-ffp-contract=off).  The tap count has no bound (8192 to 1 is
 // legal): both loops run over chunks of the band.
 //
-// LR_WARP_RAGGED | LR_WARP_PREPARE (prepare_ragged_kernel): the same tiles, staging and accumulation order over frames
-// that each have their own source size, output size, span tables and places.
+// One tile body, two kernels: prepare_tile is a workgroup's work on a tile; prepare_kernel (one size for all frames: the
+// frame is tile / tiles per frame, everything else a kernel argument) and prepare_ragged_kernel (LR_WARP_RAGGED |
+// LR_WARP_PREPARE: frames that each have their own source size, output size, span tables and places, found through the
+// tiles' prefix table and a record per frame) only find the values it takes.
 //
 // Measured (profiles/prepare_*.txt): 24-40 us for a 4K frame, three to six times a device copy of
 // the same bytes -- bound by the bytes the workgroups keep in flight (a chunk each, nothing fetched ahead), not yet cured.
@@ -36,7 +38,8 @@
 #include <map>
 #include <vector>
 
-#include "context.h"
+#include "tables.h"
+#include "tiles.h"
 
 namespace lramd {
 namespace {
@@ -92,8 +95,12 @@ struct Staged<LR_PIX_F32> {
     using type = float;
 };
 
+// One tile: the 64 x 4 destination pixels from (x0, y0) of a frame whose source begins at `src`, whose span tables are sx
+// (ow entries) and sy (oh entries) and whose output begins at `out`.  Everything but the lane's own spans is uniform across
+// the workgroup.  The two kernels below differ only in where they find these values.
 template <int kFormat>
-__global__ __launch_bounds__(kBlock) void prepare_kernel(PrepareArgs g) {
+__device__ __forceinline__ void prepare_tile(const uint8_t* src, size_t src_row_bytes, const Span* sx, const Span* sy, float wx_in,
+                                             float wy_in, int ow, int oh, int x0, int y0, uint8_t* out, size_t dst_row_bytes) {
     using Lum = typename Staged<kFormat>::type;
     constexpr int kBpp = kFormat == LR_PIX_U8 ? 1 : (kFormat == LR_PIX_U8X3 ? 3 : 4);
     // raw: a chunk's bytes as fetched, every row from the aligned dword that holds its first byte (u8, f32: the taps
@@ -104,273 +111,140 @@ __global__ __launch_bounds__(kBlock) void prepare_kernel(PrepareArgs g) {
     __shared__ uint8_t lum[kFormat == LR_PIX_U8X3 ? kRows * kLumPitch : 4];
 
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // XCD band order: the tiles [xcd * per_xcd, (xcd + 1) * per_xcd) go to the workgroups of one XCD (the launcher makes
-    // the grid a multiple of eight)
-    const int per_xcd = (g.n_tiles + 7) / 8;
-    const int xcd = (int)(blockIdx.x & 7u), slots = (int)(gridDim.x >> 3);
-    for (int t = (int)(blockIdx.x >> 3); t < per_xcd; t += slots) {
-        const int tile = xcd * per_xcd + t;
-        if (tile >= g.n_tiles) return;
-        const int b = tile / g.tiles_per_frame;
-        const int r = tile - b * g.tiles_per_frame;
-        const int ty = r / g.tiles_x, tx = r - ty * g.tiles_x;
-        const int x0 = tx * kTileW, y0 = ty * kTileH;
-        const int x1 = min(x0 + kTileW, g.ow) - 1, y1 = min(y0 + kTileH, g.oh) - 1;  // last column and row of the tile
-        const uint8_t* src = g.src + (size_t)b * g.src_image_bytes;
+    const int x1 = min(x0 + kTileW, ow) - 1, y1 = min(y0 + kTileH, oh) - 1;  // last column and row of the tile
 
-        // the band of the source this tile reads (the same for the whole workgroup) ...
-        const Span sxa = g.sx[x0], sxb = g.sx[x1], sya = g.sy[y0], syb = g.sy[y1];
-        const int col_a = sxa.first, col_b = sxb.first + sxb.count - 1;
-        const int row_a = sya.first, row_b = syb.first + syb.count - 1;
-        // ... and this lane's pixel in it (lanes and wavefronts past the edge carry an empty span and store nothing)
-        const int x = x0 + lane, y = y0 + wave;
-        const bool live = x <= x1 && y <= y1;
-        Span mx = {0, 0, 0.f, 0.f}, my = {0, 0, 0.f, 0.f};
-        if (live) {
-            mx = g.sx[x];
-            my = g.sy[y];
-        }
-        const int mx_last = mx.first + mx.count - 1, my_last = my.first + my.count - 1;
+    // the band of the source this tile reads (the same for the whole workgroup) ...
+    const Span sxa = sx[x0], sxb = sx[x1], sya = sy[y0], syb = sy[y1];
+    const int col_a = sxa.first, col_b = sxb.first + sxb.count - 1;
+    const int row_a = sya.first, row_b = syb.first + syb.count - 1;
+    // ... and this lane's pixel in it (lanes and wavefronts past the edge carry an empty span and store nothing)
+    const int x = x0 + lane, y = y0 + wave;
+    const bool live = x <= x1 && y <= y1;
+    Span mx = {0, 0, 0.f, 0.f}, my = {0, 0, 0.f, 0.f};
+    if (live) {
+        mx = sx[x];
+        my = sy[y];
+    }
+    const int mx_last = mx.first + mx.count - 1, my_last = my.first + my.count - 1;
 
-        float v = 0.f;
-        for (int r0 = row_a; r0 <= row_b; r0 += kRows) {
-            const int nr = min(kRows, row_b - r0 + 1);
-            float h[kRows];
+    float v = 0.f;
+    for (int r0 = row_a; r0 <= row_b; r0 += kRows) {
+        const int nr = min(kRows, row_b - r0 + 1);
+        float h[kRows];
 #pragma unroll
-            for (int k = 0; k < kRows; ++k) h[k] = 0.f;
-            for (int c0 = col_a; c0 <= col_b; c0 += kCols) {
-                const int nc = min(kCols, col_b - c0 + 1);
-                // first byte of the chunk in its first row; row k's first byte is k row strides further
-                const uint8_t* chunk = src + (size_t)r0 * g.src_row_bytes + (size_t)c0 * kBpp;
-                __syncthreads();  // the previous chunk has been read
-                // fetch rows r0 .. r0 + nr - 1, bytes [c0 * kBpp, (c0 + nc) * kBpp) of each: words_row dwords cover a
-                // row wherever its first byte lies in its dword (<= kRawPitch / 4)
-                const int words_row = ((nc * kBpp + 3) >> 2) + 1, words = nr * words_row;
-                for (int i0 = tid; i0 < words; i0 += kFetch * kBlock) {
-                    uint32_t word[kFetch];
+        for (int k = 0; k < kRows; ++k) h[k] = 0.f;
+        for (int c0 = col_a; c0 <= col_b; c0 += kCols) {
+            const int nc = min(kCols, col_b - c0 + 1);
+            // first byte of the chunk in its first row; row k's first byte is k row strides further
+            const uint8_t* chunk = src + (size_t)r0 * src_row_bytes + (size_t)c0 * kBpp;
+            __syncthreads();  // the previous chunk has been read
+            // fetch rows r0 .. r0 + nr - 1, bytes [c0 * kBpp, (c0 + nc) * kBpp) of each: words_row dwords cover a
+            // row wherever its first byte lies in its dword (<= kRawPitch / 4)
+            const int words_row = ((nc * kBpp + 3) >> 2) + 1, words = nr * words_row;
+            for (int i0 = tid; i0 < words; i0 += kFetch * kBlock) {
+                uint32_t word[kFetch];
 #pragma unroll
-                    for (int u = 0; u < kFetch; ++u) {
-                        const int idx = i0 + u * kBlock;
-                        word[u] = 0;
-                        if (idx < words) {
-                            const int k = idx / words_row, d = idx - k * words_row;
-                            const uint8_t* beg = chunk + (size_t)k * g.src_row_bytes;
-                            const uint8_t* end = beg + (size_t)nc * kBpp;
-                            const uint8_t* p = beg - (reinterpret_cast<uintptr_t>(beg) & 3u) + 4 * (size_t)d;
-                            if (p >= beg && p + 4 <= end) {
-                                word[u] = *reinterpret_cast<const uint32_t*>(p);
-                            } else {
-                                for (int i = 0; i < 4; ++i)
-                                    if (p + i >= beg && p + i < end) word[u] |= (uint32_t)p[i] << (8 * i);
-                            }
-                        }
-                    }
-#pragma unroll
-                    for (int u = 0; u < kFetch; ++u) {
-                        const int idx = i0 + u * kBlock;
-                        if (idx < words) {
-                            const int k = idx / words_row, d = idx - k * words_row;
-                            reinterpret_cast<uint32_t*>(raw + k * kRawPitch)[d] = word[u];
-                        }
-                    }
-                }
-                if (kFormat == LR_PIX_U8X3) {
-                    __syncthreads();
-                    for (int idx = tid; idx < nr * nc; idx += kBlock) {
-                        const int k = idx / nc, i = idx - k * nc;
-                        const uint8_t* beg = chunk + (size_t)k * g.src_row_bytes;
-                        const uint8_t* px = raw + k * kRawPitch + (reinterpret_cast<uintptr_t>(beg) & 3u) + 3 * i;
-                        const uint32_t c0v = px[0], c1v = px[1], c2v = px[2];
-                        lum[k * kLumPitch + i] = (uint8_t)((4899u * c0v + 9617u * c1v + 1868u * c2v + 8192u) >> 14);
-                    }
-                }
-                __syncthreads();
-                // this lane's taps inside the chunk
-                const int ja = max(mx.first, c0), jb = min(mx_last, c0 + nc - 1);
-#pragma unroll
-                for (int k = 0; k < kRows; ++k) {
-                    const int row = r0 + k;
-                    if (k < nr && row >= my.first && row <= my_last && ja <= jb) {
-                        const Lum* line;
-                        if (kFormat == LR_PIX_U8X3) {
-                            line = reinterpret_cast<const Lum*>(lum + k * kLumPitch);
+                for (int u = 0; u < kFetch; ++u) {
+                    const int idx = i0 + u * kBlock;
+                    word[u] = 0;
+                    if (idx < words) {
+                        const int k = idx / words_row, d = idx - k * words_row;
+                        const uint8_t* beg = chunk + (size_t)k * src_row_bytes;
+                        const uint8_t* end = beg + (size_t)nc * kBpp;
+                        const uint8_t* p = beg - (reinterpret_cast<uintptr_t>(beg) & 3u) + 4 * (size_t)d;
+                        if (p >= beg && p + 4 <= end) {
+                            word[u] = *reinterpret_cast<const uint32_t*>(p);
                         } else {
-                            const uint8_t* beg = chunk + (size_t)k * g.src_row_bytes;
-                            line = reinterpret_cast<const Lum*>(raw + k * kRawPitch + (reinterpret_cast<uintptr_t>(beg) & 3u));
+                            for (int i = 0; i < 4; ++i)
+                                if (p + i >= beg && p + i < end) word[u] |= (uint32_t)p[i] << (8 * i);
                         }
-                        float acc = h[k];
-                        for (int j = ja; j <= jb; ++j) {
-                            const float w = j == mx.first ? mx.w_first : (j == mx_last ? mx.w_last : g.wx_in);
-                            const float p = kFormat == LR_PIX_F32 ? (float)line[j - c0] : (float)line[j - c0] * (1.0f / 256.0f);
-                            acc = acc + w * p;
-                        }
-                        h[k] = acc;
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < kFetch; ++u) {
+                    const int idx = i0 + u * kBlock;
+                    if (idx < words) {
+                        const int k = idx / words_row, d = idx - k * words_row;
+                        reinterpret_cast<uint32_t*>(raw + k * kRawPitch)[d] = word[u];
                     }
                 }
             }
+            if (kFormat == LR_PIX_U8X3) {
+                __syncthreads();
+                for (int idx = tid; idx < nr * nc; idx += kBlock) {
+                    const int k = idx / nc, i = idx - k * nc;
+                    const uint8_t* beg = chunk + (size_t)k * src_row_bytes;
+                    const uint8_t* px = raw + k * kRawPitch + (reinterpret_cast<uintptr_t>(beg) & 3u) + 3 * i;
+                    const uint32_t c0v = px[0], c1v = px[1], c2v = px[2];
+                    lum[k * kLumPitch + i] = (uint8_t)((4899u * c0v + 9617u * c1v + 1868u * c2v + 8192u) >> 14);
+                }
+            }
+            __syncthreads();
+            // this lane's taps inside the chunk
+            const int ja = max(mx.first, c0), jb = min(mx_last, c0 + nc - 1);
 #pragma unroll
             for (int k = 0; k < kRows; ++k) {
                 const int row = r0 + k;
-                if (k < nr && row >= my.first && row <= my_last) {
-                    const float w = row == my.first ? my.w_first : (row == my_last ? my.w_last : g.wy_in);
-                    v = v + w * h[k];
+                if (k < nr && row >= my.first && row <= my_last && ja <= jb) {
+                    const Lum* line;
+                    if (kFormat == LR_PIX_U8X3) {
+                        line = reinterpret_cast<const Lum*>(lum + k * kLumPitch);
+                    } else {
+                        const uint8_t* beg = chunk + (size_t)k * src_row_bytes;
+                        line = reinterpret_cast<const Lum*>(raw + k * kRawPitch + (reinterpret_cast<uintptr_t>(beg) & 3u));
+                    }
+                    float acc = h[k];
+                    for (int j = ja; j <= jb; ++j) {
+                        const float w = j == mx.first ? mx.w_first : (j == mx_last ? mx.w_last : wx_in);
+                        const float p = kFormat == LR_PIX_F32 ? (float)line[j - c0] : (float)line[j - c0] * (1.0f / 256.0f);
+                        acc = acc + w * p;
+                    }
+                    h[k] = acc;
                 }
             }
         }
-        if (live) {
-            float* out = reinterpret_cast<float*>(g.dst + (size_t)b * g.dst_image_bytes + (size_t)y * g.dst_row_bytes);
-            out[x] = v;
+#pragma unroll
+        for (int k = 0; k < kRows; ++k) {
+            const int row = r0 + k;
+            if (k < nr && row >= my.first && row <= my_last) {
+                const float w = row == my.first ? my.w_first : (row == my_last ? my.w_last : wy_in);
+                v = v + w * h[k];
+            }
         }
+    }
+    if (live) reinterpret_cast<float*>(out + (size_t)y * dst_row_bytes)[x] = v;
+}
+
+template <int kFormat>
+__global__ __launch_bounds__(kBlock) void prepare_kernel(PrepareArgs g) {
+    XcdBand band(g.n_tiles);
+    for (int tile; band.next(&tile);) {
+        const int b = tile / g.tiles_per_frame;
+        const int r = tile - b * g.tiles_per_frame;
+        const int ty = r / g.tiles_x, tx = r - ty * g.tiles_x;
+        prepare_tile<kFormat>(g.src + (size_t)b * g.src_image_bytes, g.src_row_bytes, g.sx, g.sy, g.wx_in, g.wy_in, g.ow, g.oh,
+                              tx * kTileW, ty * kTileH, g.dst + (size_t)b * g.dst_image_bytes, g.dst_row_bytes);
     }
 }
 
-// LR_WARP_RAGGED | LR_WARP_PREPARE: prepare_kernel over a ragged tile list.  Every frame has its own source (place, size,
-// stride), output (place, size, stride), span tables and (float)(1 / s) pair, all found through its record; tile to frame
-// goes by the scalar binary search of warp_packed_kernel.  Records, prefix table and spans are restrict-qualified arguments
-// of their own: the stores to dst cannot change them, so their uniform reads stay scalar loads.  Everything below the
-// record's reads is prepare_kernel's text, which keeps its own copy so that its code is what it was.
+// LR_WARP_RAGGED | LR_WARP_PREPARE: the same tiles over a ragged list.  Every frame has its own source (place, size, stride),
+// output (place, size, stride), span tables and (float)(1 / s) pair, all found through its record; tile to frame goes by
+// the scalar binary search of tiles.h.  Records, prefix table and spans are restrict-qualified arguments of their own: the
+// stores to dst cannot change them, so their uniform reads stay scalar loads.
 template <int kFormat>
 __global__ __launch_bounds__(kBlock) void prepare_ragged_kernel(RaggedPrepareArgs g, const PrepareFrame* __restrict__ frames,
                                                                 const int* __restrict__ start, const Span* __restrict__ spans,
                                                                 uint8_t* __restrict__ dst) {
-    using Lum = typename Staged<kFormat>::type;
-    constexpr int kBpp = kFormat == LR_PIX_U8 ? 1 : (kFormat == LR_PIX_U8X3 ? 3 : 4);
-    // raw: a chunk's bytes as fetched, every row from the aligned dword that holds its first byte (u8, f32: the taps
-    // read it where it lies).  lum (u8x3 only): the chunk's luma.
-    constexpr int kRawPitch = kCols * kBpp + 8;  // bytes; a multiple of 4
-    constexpr int kLumPitch = kFormat == LR_PIX_U8X3 ? kCols : 1;
-    __shared__ __attribute__((aligned(16))) uint8_t raw[kRows * kRawPitch];
-    __shared__ uint8_t lum[kFormat == LR_PIX_U8X3 ? kRows * kLumPitch : 4];
-
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // XCD band order: the tiles [xcd * per_xcd, (xcd + 1) * per_xcd) go to the workgroups of one XCD (the launcher makes
-    // the grid a multiple of eight)
-    const int per_xcd = (g.n_tiles + 7) / 8;
-    const int xcd = (int)(blockIdx.x & 7u), slots = (int)(gridDim.x >> 3);
-    for (int t = (int)(blockIdx.x >> 3); t < per_xcd; t += slots) {
-        const int tile = xcd * per_xcd + t;
-        if (tile >= g.n_tiles) return;
-        int b = 0, hi = g.batch;  // start[b] <= tile < start[hi] (uniform: scalar loads and compares, as warp_packed_kernel's)
-        while (hi - b > 1) {
-            const int mid = (b + hi) >> 1;
-            if (start[mid] <= tile) b = mid;
-            else hi = mid;
-        }
+    XcdBand band(g.n_tiles);
+    for (int tile; band.next(&tile);) {
+        const int b = frame_of_tile(start, g.batch, tile);
         const PrepareFrame* f = frames + b;
-        const int ow = f->ow, oh = f->oh, tiles_x = f->tiles_x;
-        const size_t src_row_bytes = (size_t)f->src_row_bytes;
+        const int ow = f->ow, tiles_x = f->tiles_x;
         const Span* sx = spans + f->span0;  // ow entries, then the rows' oh
-        const Span* sy = sx + ow;
-        const float wx_in = f->wx_in, wy_in = f->wy_in;
         const int r = tile - start[b];
         const int ty = r / tiles_x, tx = r - ty * tiles_x;
-        const int x0 = tx * kTileW, y0 = ty * kTileH;
-        const int x1 = min(x0 + kTileW, ow) - 1, y1 = min(y0 + kTileH, oh) - 1;  // last column and row of the tile
-        const uint8_t* src = g.src + (size_t)f->src_offset;
-
-        // the band of the source this tile reads (the same for the whole workgroup) ...
-        const Span sxa = sx[x0], sxb = sx[x1], sya = sy[y0], syb = sy[y1];
-        const int col_a = sxa.first, col_b = sxb.first + sxb.count - 1;
-        const int row_a = sya.first, row_b = syb.first + syb.count - 1;
-        // ... and this lane's pixel in it (lanes and wavefronts past the edge carry an empty span and store nothing)
-        const int x = x0 + lane, y = y0 + wave;
-        const bool live = x <= x1 && y <= y1;
-        Span mx = {0, 0, 0.f, 0.f}, my = {0, 0, 0.f, 0.f};
-        if (live) {
-            mx = sx[x];
-            my = sy[y];
-        }
-        const int mx_last = mx.first + mx.count - 1, my_last = my.first + my.count - 1;
-
-        float v = 0.f;
-        for (int r0 = row_a; r0 <= row_b; r0 += kRows) {
-            const int nr = min(kRows, row_b - r0 + 1);
-            float h[kRows];
-#pragma unroll
-            for (int k = 0; k < kRows; ++k) h[k] = 0.f;
-            for (int c0 = col_a; c0 <= col_b; c0 += kCols) {
-                const int nc = min(kCols, col_b - c0 + 1);
-                // first byte of the chunk in its first row; row k's first byte is k row strides further
-                const uint8_t* chunk = src + (size_t)r0 * src_row_bytes + (size_t)c0 * kBpp;
-                __syncthreads();  // the previous chunk has been read
-                // fetch rows r0 .. r0 + nr - 1, bytes [c0 * kBpp, (c0 + nc) * kBpp) of each: words_row dwords cover a
-                // row wherever its first byte lies in its dword (<= kRawPitch / 4)
-                const int words_row = ((nc * kBpp + 3) >> 2) + 1, words = nr * words_row;
-                for (int i0 = tid; i0 < words; i0 += kFetch * kBlock) {
-                    uint32_t word[kFetch];
-#pragma unroll
-                    for (int u = 0; u < kFetch; ++u) {
-                        const int idx = i0 + u * kBlock;
-                        word[u] = 0;
-                        if (idx < words) {
-                            const int k = idx / words_row, d = idx - k * words_row;
-                            const uint8_t* beg = chunk + (size_t)k * src_row_bytes;
-                            const uint8_t* end = beg + (size_t)nc * kBpp;
-                            const uint8_t* p = beg - (reinterpret_cast<uintptr_t>(beg) & 3u) + 4 * (size_t)d;
-                            if (p >= beg && p + 4 <= end) {
-                                word[u] = *reinterpret_cast<const uint32_t*>(p);
-                            } else {
-                                for (int i = 0; i < 4; ++i)
-                                    if (p + i >= beg && p + i < end) word[u] |= (uint32_t)p[i] << (8 * i);
-                            }
-                        }
-                    }
-#pragma unroll
-                    for (int u = 0; u < kFetch; ++u) {
-                        const int idx = i0 + u * kBlock;
-                        if (idx < words) {
-                            const int k = idx / words_row, d = idx - k * words_row;
-                            reinterpret_cast<uint32_t*>(raw + k * kRawPitch)[d] = word[u];
-                        }
-                    }
-                }
-                if (kFormat == LR_PIX_U8X3) {
-                    __syncthreads();
-                    for (int idx = tid; idx < nr * nc; idx += kBlock) {
-                        const int k = idx / nc, i = idx - k * nc;
-                        const uint8_t* beg = chunk + (size_t)k * src_row_bytes;
-                        const uint8_t* px = raw + k * kRawPitch + (reinterpret_cast<uintptr_t>(beg) & 3u) + 3 * i;
-                        const uint32_t c0v = px[0], c1v = px[1], c2v = px[2];
-                        lum[k * kLumPitch + i] = (uint8_t)((4899u * c0v + 9617u * c1v + 1868u * c2v + 8192u) >> 14);
-                    }
-                }
-                __syncthreads();
-                // this lane's taps inside the chunk
-                const int ja = max(mx.first, c0), jb = min(mx_last, c0 + nc - 1);
-#pragma unroll
-                for (int k = 0; k < kRows; ++k) {
-                    const int row = r0 + k;
-                    if (k < nr && row >= my.first && row <= my_last && ja <= jb) {
-                        const Lum* line;
-                        if (kFormat == LR_PIX_U8X3) {
-                            line = reinterpret_cast<const Lum*>(lum + k * kLumPitch);
-                        } else {
-                            const uint8_t* beg = chunk + (size_t)k * src_row_bytes;
-                            line = reinterpret_cast<const Lum*>(raw + k * kRawPitch + (reinterpret_cast<uintptr_t>(beg) & 3u));
-                        }
-                        float acc = h[k];
-                        for (int j = ja; j <= jb; ++j) {
-                            const float w = j == mx.first ? mx.w_first : (j == mx_last ? mx.w_last : wx_in);
-                            const float p = kFormat == LR_PIX_F32 ? (float)line[j - c0] : (float)line[j - c0] * (1.0f / 256.0f);
-                            acc = acc + w * p;
-                        }
-                        h[k] = acc;
-                    }
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < kRows; ++k) {
-                const int row = r0 + k;
-                if (k < nr && row >= my.first && row <= my_last) {
-                    const float w = row == my.first ? my.w_first : (row == my_last ? my.w_last : wy_in);
-                    v = v + w * h[k];
-                }
-            }
-        }
-        if (live) {
-            float* out = reinterpret_cast<float*>(dst + (size_t)f->dst_offset + (size_t)y * (size_t)f->dst_row_bytes);
-            out[x] = v;
-        }
+        prepare_tile<kFormat>(g.src + (size_t)f->src_offset, (size_t)f->src_row_bytes, sx, sx + ow, f->wx_in, f->wy_in, ow, f->oh,
+                              tx * kTileW, ty * kTileH, dst + (size_t)f->dst_offset, (size_t)f->dst_row_bytes);
     }
 }
 
@@ -433,17 +307,11 @@ int ctx_prepare_frames(lr_context* c, const void* d_src, size_t src_image_bytes,
                       c->prep.key[2] == height && c->prep.key[3] == out_height;
     if (!same) {
         c->prep.key[0] = 0;  // (no table while this is under way)
-        if (n_spans * sizeof(Span) > c->prep.spans.cap()) {
-            LR_HIP(hipStreamSynchronize(c->stream));
-            if (c->prep.spans.grow(n_spans * sizeof(Span))) return 1;
-        }
-        if (c->ev_prep_spans.ensure(hipEventDisableTiming)) return 1;
-        LR_HIP(hipEventSynchronize(c->ev_prep_spans));  // the previous table's upload has read h_prep_spans
+        if (upload_reserve(c, c->prep.spans, c->ev_prep_spans, n_spans * sizeof(Span))) return 1;
         Span* hs = reinterpret_cast<Span*>(c->prep.spans.h.get());
         c->prep.w_in[0] = make_spans(width, out_width, hs);
         c->prep.w_in[1] = make_spans(height, out_height, hs + out_width);
-        LR_HIP(hipMemcpyAsync(c->prep.spans.d, c->prep.spans.h, n_spans * sizeof(Span), hipMemcpyHostToDevice, c->stream));
-        LR_HIP(hipEventRecord(c->ev_prep_spans, c->stream));
+        if (upload_send(c, c->prep.spans, c->ev_prep_spans, n_spans * sizeof(Span))) return 1;
         c->prep.key[0] = width;
         c->prep.key[1] = out_width;
         c->prep.key[2] = height;
@@ -467,12 +335,9 @@ int ctx_prepare_frames(lr_context* c, const void* d_src, size_t src_image_bytes,
     g.tiles_per_frame = (int)(tiles_x * tiles_y);
     g.n_tiles = (int)n_tiles;
     const int grid = (int)std::min<int64_t>((n_tiles + 7) / 8 * 8, kMaxGrid);
-    if (format == LR_PIX_U8)
-        hipLaunchKernelGGL(prepare_kernel<LR_PIX_U8>, dim3(grid), dim3(kBlock), 0, c->stream, g);
-    else if (format == LR_PIX_U8X3)
-        hipLaunchKernelGGL(prepare_kernel<LR_PIX_U8X3>, dim3(grid), dim3(kBlock), 0, c->stream, g);
-    else
-        hipLaunchKernelGGL(prepare_kernel<LR_PIX_F32>, dim3(grid), dim3(kBlock), 0, c->stream, g);
+    launch_by_format(format, [&](auto fmt) {
+        hipLaunchKernelGGL(prepare_kernel<decltype(fmt)::value>, dim3(grid), dim3(kBlock), 0, c->stream, g);
+    });
     LR_HIP(hipGetLastError());
     return 0;
 }
@@ -513,12 +378,7 @@ int ctx_prepare_ragged(lr_context* c, const void* d_src, size_t src_bytes, int b
     const size_t start_bytes = (((size_t)batch + 1) * sizeof(int) + 15) / 16 * 16;
     const size_t bytes = rec_bytes + start_bytes + n_spans * sizeof(Span);
     LR_HIP(hipSetDevice(c->device));
-    if (bytes > c->prep.ragged.cap()) {  // (grows: the buffers of a previous call may still be read by its launch)
-        LR_HIP(hipStreamSynchronize(c->stream));
-        if (c->prep.ragged.grow(bytes)) return 1;
-    }
-    if (c->ev_prep_ragged.ensure(hipEventDisableTiming)) return 1;
-    LR_HIP(hipEventSynchronize(c->ev_prep_ragged));  // the previous call's upload has read the page-locked copy
+    if (upload_reserve(c, c->prep.ragged, c->ev_prep_ragged, bytes)) return 1;
     unsigned char* hb = c->prep.ragged.h.get();
     PrepareFrame* rec = reinterpret_cast<PrepareFrame*>(hb);
     int* start = reinterpret_cast<int*>(hb + rec_bytes);
@@ -547,8 +407,7 @@ int ctx_prepare_ragged(lr_context* c, const void* d_src, size_t src_bytes, int b
         tiles += f.tiles_x * (int)((s.oh + kTileH - 1) / kTileH);
     }
     start[batch] = tiles;
-    LR_HIP(hipMemcpyAsync(c->prep.ragged.d, c->prep.ragged.h, bytes, hipMemcpyHostToDevice, c->stream));
-    LR_HIP(hipEventRecord(c->ev_prep_ragged, c->stream));
+    if (upload_send(c, c->prep.ragged, c->ev_prep_ragged, bytes)) return 1;
 
     RaggedPrepareArgs g;
     g.src = static_cast<const uint8_t*>(d_src);
@@ -560,12 +419,10 @@ int ctx_prepare_ragged(lr_context* c, const void* d_src, size_t src_bytes, int b
     const Span* d_spans = reinterpret_cast<const Span*>(db + rec_bytes + start_bytes);
     uint8_t* dst = static_cast<uint8_t*>(d_dst);
     const int grid = (int)std::min<int64_t>((n_tiles + 7) / 8 * 8, kMaxGrid);
-    if (format == LR_PIX_U8)
-        hipLaunchKernelGGL(prepare_ragged_kernel<LR_PIX_U8>, dim3(grid), dim3(kBlock), 0, c->stream, g, d_rec, d_start, d_spans, dst);
-    else if (format == LR_PIX_U8X3)
-        hipLaunchKernelGGL(prepare_ragged_kernel<LR_PIX_U8X3>, dim3(grid), dim3(kBlock), 0, c->stream, g, d_rec, d_start, d_spans, dst);
-    else
-        hipLaunchKernelGGL(prepare_ragged_kernel<LR_PIX_F32>, dim3(grid), dim3(kBlock), 0, c->stream, g, d_rec, d_start, d_spans, dst);
+    launch_by_format(format, [&](auto fmt) {
+        hipLaunchKernelGGL(prepare_ragged_kernel<decltype(fmt)::value>, dim3(grid), dim3(kBlock), 0, c->stream, g, d_rec, d_start,
+                           d_spans, dst);
+    });
     LR_HIP(hipGetLastError());
     return 0;
 }

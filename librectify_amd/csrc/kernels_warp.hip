@@ -16,25 +16,28 @@
 // The arithmetic is the canonical one of DESIGN.md section 3 (mirrored by tests/numpy_warp_ref.py): coordinates in
 // double without contraction (-ffp-contract=off), 5 fractional bits per axis, integer taps and weights.
 //
-// LR_WARP_PACKED (warp_packed_kernel): every frame has its own output size and its own place in one destination region.
-// The tile list is ragged -- frame b adds ceil(ow_b / 64) * ceil(oh_b / 16) tiles -- and is cut into the same eight runs.  A
-// workgroup finds its frame by a binary search of the tiles' prefix table; the tile index is the same for all its lanes, so
-// the search and the read of the frame's record (map, size, tiles per row, offset, stride) are scalar loads and compares.
-// The lanes' work inside a tile (warp_lane) is the single-size kernel's, statement for statement.
+// One lane body, two kernels.  warp_lane is a lane's work inside a tile: its four pixels' taps, blends and stores.  The two
+// kernels differ only in how a workgroup finds its frame and the frame's values, all of which depend on the tile index
+// alone and are uniform across the workgroup:
 //
-// LR_WARP_RAGGED (warp_ragged_kernel): every frame has its own SOURCE size and place as well.  The same ragged tile list,
-// search and bands; the frame's record (18 doubles long, like the caller's row) also carries the source's offset from the
-// source pointer, its size and its row stride, all uniform across the workgroup.
+//   * warp_perspective_kernel (one size for all frames): the frame is tile / tiles per frame, and sizes, strides and
+//     pointers are kernel arguments.
+//   * warp_ragged_kernel (LR_WARP_PACKED and LR_WARP_RAGGED): the tile list is ragged -- frame b adds ceil(ow_b / 64) *
+//     ceil(oh_b / 16) tiles -- and is cut into the same eight runs.  A workgroup finds its frame by a binary search of the
+//     tiles' prefix table (tiles.h) and reads the frame's record: its map, its output's size, place and stride, and its
+//     source's size, place and stride.  LR_WARP_PACKED, whose frames share one source size and stride, is the same launch
+//     with records that say so.
 //
-// LR_WARP_JPEG is none either: lr_encode_jpeg_device's call goes on to kernels_jpeg.hip.
-// LR_WARP_LINES is no warp: the entry hands lr_draw_lines_device's call on to kernels_overlay.hip (the export table is full).
+// LR_WARP_JPEG is no warp: lr_encode_jpeg_device's call goes on to kernels_jpeg.hip.
+// LR_WARP_LINES is none either: the entry hands lr_draw_lines_device's call on to kernels_overlay.hip (the export table is full).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <utility>
 #include <vector>
 
-#include "context.h"
+#include "tables.h"
+#include "tiles.h"
 
 namespace lramd {
 namespace {
@@ -55,22 +58,7 @@ struct WarpArgs {
     int tiles_x, tiles_per_frame, n_tiles;
 };
 
-// LR_WARP_PACKED: a frame's record, 13 doubles long like the caller's row it is made from
-struct PackedFrame {
-    double m[9];
-    unsigned long long offset, row_bytes;  // of its output, from the destination pointer
-    int ow, oh, tiles_x, pad;
-};
-static_assert(sizeof(PackedFrame) == 13 * sizeof(double), "a record per 13 doubles of the mirror");
-
-struct PackedArgs {
-    const uint8_t* src;
-    size_t src_image_bytes, src_row_bytes;
-    int w, h;
-    int batch, n_tiles;
-};
-
-// LR_WARP_RAGGED: a frame's record, 18 doubles long like the caller's row it is made from
+// a frame's record of the table kernel, 18 doubles long like the row of LR_WARP_RAGGED's table it is made from
 struct RaggedFrame {
     double m[9];
     unsigned long long offset, row_bytes;          // of its output, from the destination pointer
@@ -158,8 +146,7 @@ __device__ __forceinline__ uint32_t blend_u8(uint32_t a, uint32_t b, uint32_t c,
     return (a * (uint32_t)t.w00 + b * (uint32_t)t.w01 + c * (uint32_t)t.w10 + d * (uint32_t)t.w11 + 512u) >> 10;
 }
 
-// LR_WARP_PACKED: one lane's four consecutive pixels (x0 .. x0 + 3, those below ow) of destination row y, whose first byte
-// is `out`.  The text of warp_perspective_kernel's loop body, which keeps its own copy so that its code is what it was.
+// One lane's four consecutive pixels (x0 .. x0 + 3, those below ow) of destination row y, whose first byte is `out`
 template <int kFormat>
 __device__ __forceinline__ void warp_lane(const double* m, const uint8_t* src, size_t src_row_bytes, int w, int h,
                                           uint8_t* out, int ow, unsigned x0, unsigned y) {
@@ -232,137 +219,31 @@ template <int kFormat>
 __global__ __launch_bounds__(kBlock) void warp_perspective_kernel(WarpArgs g) {
     const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
     const unsigned lx = (unsigned)lane & 15u, row_in_tile = (unsigned)(wave * 4 + (lane >> 4));
-    // XCD band order: the tiles [xcd * per_xcd, (xcd + 1) * per_xcd) go to the workgroups of one XCD (the launcher makes
-    // the grid a multiple of eight)
-    const int per_xcd = (g.n_tiles + 7) / 8;
-    const int xcd = (int)(blockIdx.x & 7u), slots = (int)(gridDim.x >> 3);
-    for (int j = (int)(blockIdx.x >> 3); j < per_xcd; j += slots) {
-        const int tile = xcd * per_xcd + j;
-        if (tile >= g.n_tiles) return;
+    XcdBand band(g.n_tiles);
+    for (int tile; band.next(&tile);) {
         const int b = tile / g.tiles_per_frame;
         const int r = tile - b * g.tiles_per_frame;
         const int ty = r / g.tiles_x, tx = r - ty * g.tiles_x;
         const unsigned y = (unsigned)ty * kTileH + row_in_tile;
         const unsigned x0 = (unsigned)tx * kTileW + lx * 4u;
         if (y >= (unsigned)g.oh || x0 >= (unsigned)g.ow) continue;
-        const double* m = g.M + (size_t)b * 9;
         const uint8_t* src = g.src + (size_t)b * g.src_image_bytes;
         uint8_t* out = g.dst + (size_t)b * g.dst_image_bytes + (size_t)y * g.dst_row_bytes;
-        const int n = min(4, g.ow - (int)x0);  // pixels of this lane inside the row
-
-        uint32_t res_u8 = 0;          // LR_PIX_U8: four bytes
-        uint32_t res_rgb[3] = {0, 0, 0};  // LR_PIX_U8X3: twelve bytes
-        float res_f[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const Taps t = taps_of(m, x0 + (unsigned)k, y);
-            const bool in0 = inside(t.iy, g.h), in1 = inside(t.iy + 1, g.h);
-            const uint8_t* row0 = src + (size_t)(in0 ? t.iy : 0) * g.src_row_bytes;
-            const uint8_t* row1 = src + (size_t)(in1 ? t.iy + 1 : 0) * g.src_row_bytes;
-            if (kFormat == LR_PIX_U8) {
-                uint32_t a, bb, c, d;
-                pair_u8(row0, in0, t.ix, g.w, a, bb);
-                pair_u8(row1, in1, t.ix, g.w, c, d);
-                res_u8 |= blend_u8(a, bb, c, d, t) << (8 * k);
-            } else if (kFormat == LR_PIX_U8X3) {
-                const bool ia = inside(t.ix, g.w), ib = inside(t.ix + 1, g.w);
-                const size_t oa = (size_t)(ia ? t.ix : 0) * 3, ob = (size_t)(ib ? t.ix + 1 : 0) * 3;
-                const uint32_t p00 = tap_u8x3(row0 + oa, in0 && ia), p01 = tap_u8x3(row0 + ob, in0 && ib);
-                const uint32_t p10 = tap_u8x3(row1 + oa, in1 && ia), p11 = tap_u8x3(row1 + ob, in1 && ib);
-#pragma unroll
-                for (int ch = 0; ch < 3; ++ch) {
-                    const int s = 8 * ch;
-                    const uint32_t v = blend_u8((p00 >> s) & 0xFFu, (p01 >> s) & 0xFFu, (p10 >> s) & 0xFFu, (p11 >> s) & 0xFFu, t);
-                    const int byte = 3 * k + ch;  // byte of the lane's twelve
-                    res_rgb[byte >> 2] |= v << (8 * (byte & 3));
-                }
-            } else {
-                float a, bb, c, d;
-                pair_f32(row0, in0, t.ix, g.w, a, bb);
-                pair_f32(row1, in1, t.ix, g.w, c, d);
-                const float f00 = (float)t.w00 / 1024.0f, f01 = (float)t.w01 / 1024.0f;
-                const float f10 = (float)t.w10 / 1024.0f, f11 = (float)t.w11 / 1024.0f;
-                res_f[k] = ((a * f00 + bb * f01) + c * f10) + d * f11;
-            }
-        }
-
-        if (kFormat == LR_PIX_U8) {
-            uint8_t* p = out + x0;
-            if (n == 4 && (reinterpret_cast<uintptr_t>(p) & 3u) == 0) {
-                *reinterpret_cast<uint32_t*>(p) = res_u8;
-            } else {
-                for (int k = 0; k < n; ++k) p[k] = (uint8_t)(res_u8 >> (8 * k));
-            }
-        } else if (kFormat == LR_PIX_U8X3) {
-            uint8_t* p = out + (size_t)x0 * 3;
-            if (n == 4 && (reinterpret_cast<uintptr_t>(p) & 3u) == 0) {
-                uint32_t* q = reinterpret_cast<uint32_t*>(p);
-                q[0] = res_rgb[0];
-                q[1] = res_rgb[1];
-                q[2] = res_rgb[2];
-            } else {
-                for (int k = 0; k < 3 * n; ++k) p[k] = (uint8_t)(res_rgb[k >> 2] >> (8 * (k & 3)));
-            }
-        } else {
-            float* p = reinterpret_cast<float*>(out) + x0;
-            if (n == 4 && (reinterpret_cast<uintptr_t>(p) & 15u) == 0) {
-                *reinterpret_cast<float4*>(p) = make_float4(res_f[0], res_f[1], res_f[2], res_f[3]);
-            } else {
-                for (int k = 0; k < n; ++k) p[k] = res_f[k];
-            }
-        }
+        warp_lane<kFormat>(g.M + (size_t)b * 9, src, g.src_row_bytes, g.w, g.h, out, g.ow, x0, y);
     }
 }
 
-// The same tiles over a ragged list: everything up to x0 and y depends on the tile index alone, which is uniform across
-// the workgroup.  frames and start (batch + 1 entries: frame b owns the tiles [start[b], start[b + 1])) are arguments of
-// their own, restrict-qualified: the stores to dst cannot change them, so their uniform reads stay scalar loads.
-template <int kFormat>
-__global__ __launch_bounds__(kBlock) void warp_packed_kernel(PackedArgs g, const PackedFrame* __restrict__ frames,
-                                                             const int* __restrict__ start, uint8_t* __restrict__ dst) {
-    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-    const unsigned lx = (unsigned)lane & 15u, row_in_tile = (unsigned)(wave * 4 + (lane >> 4));
-    const int per_xcd = (g.n_tiles + 7) / 8;
-    const int xcd = (int)(blockIdx.x & 7u), slots = (int)(gridDim.x >> 3);
-    for (int j = (int)(blockIdx.x >> 3); j < per_xcd; j += slots) {
-        const int tile = xcd * per_xcd + j;
-        if (tile >= g.n_tiles) return;
-        int b = 0, hi = g.batch;  // start[b] <= tile < start[hi]
-        while (hi - b > 1) {
-            const int mid = (b + hi) >> 1;
-            if (start[mid] <= tile) b = mid;
-            else hi = mid;
-        }
-        const PackedFrame* f = frames + b;
-        const int ow = f->ow, oh = f->oh, tiles_x = f->tiles_x;
-        const int r = tile - start[b];
-        const int ty = r / tiles_x, tx = r - ty * tiles_x;
-        const unsigned y = (unsigned)ty * kTileH + row_in_tile;
-        const unsigned x0 = (unsigned)tx * kTileW + lx * 4u;
-        if (y >= (unsigned)oh || x0 >= (unsigned)ow) continue;
-        const uint8_t* src = g.src + (size_t)b * g.src_image_bytes;
-        uint8_t* out = dst + (size_t)f->offset + (size_t)y * (size_t)f->row_bytes;
-        warp_lane<kFormat>(f->m, src, g.src_row_bytes, g.w, g.h, out, ow, x0, y);
-    }
-}
-
-// LR_WARP_RAGGED: warp_packed_kernel with the source's place, size and stride read from the frame's record too
+// The same tiles over a ragged list.  frames and start (batch + 1 entries: frame b owns the tiles [start[b], start[b + 1]))
+// are arguments of their own, restrict-qualified: the stores to dst cannot change them, so their uniform reads stay scalar
+// loads.
 template <int kFormat>
 __global__ __launch_bounds__(kBlock) void warp_ragged_kernel(RaggedArgs g, const RaggedFrame* __restrict__ frames,
                                                              const int* __restrict__ start, uint8_t* __restrict__ dst) {
     const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
     const unsigned lx = (unsigned)lane & 15u, row_in_tile = (unsigned)(wave * 4 + (lane >> 4));
-    const int per_xcd = (g.n_tiles + 7) / 8;
-    const int xcd = (int)(blockIdx.x & 7u), slots = (int)(gridDim.x >> 3);
-    for (int j = (int)(blockIdx.x >> 3); j < per_xcd; j += slots) {
-        const int tile = xcd * per_xcd + j;
-        if (tile >= g.n_tiles) return;
-        int b = 0, hi = g.batch;  // start[b] <= tile < start[hi]
-        while (hi - b > 1) {
-            const int mid = (b + hi) >> 1;
-            if (start[mid] <= tile) b = mid;
-            else hi = mid;
-        }
+    XcdBand band(g.n_tiles);
+    for (int tile; band.next(&tile);) {
+        const int b = frame_of_tile(start, g.batch, tile);
         const RaggedFrame* f = frames + b;
         const int ow = f->ow, oh = f->oh, tiles_x = f->tiles_x;
         const int r = tile - start[b];
@@ -376,11 +257,31 @@ __global__ __launch_bounds__(kBlock) void warp_ragged_kernel(RaggedArgs g, const
     }
 }
 
-// v as an integer in [lo, hi], if it is one
-bool table_integer(double v, double lo, double hi, uint64_t* out) {
-    if (!(v >= lo && v <= hi) || v != std::floor(v)) return false;
-    *out = (uint64_t)v;
-    return true;
+// The table kernel's launch: records, then the tiles' prefix table, go up in the mirror of the maps (in doubles: 18 a
+// frame + the table's ints)
+int launch_ragged(lr_context* c, const void* d_src, int format, const std::vector<RaggedFrame>& rec, const std::vector<int>& start,
+                  void* d_dst) {
+    const size_t batch = rec.size(), rec_doubles = batch * 18;
+    const int64_t n_tiles = start[batch];
+    LR_HIP(hipSetDevice(c->device));
+    if (upload_reserve(c, c->warp_m, c->ev_warp_m, rec_doubles + (batch + 2) / 2)) return 1;
+    std::memcpy(c->warp_m.h, rec.data(), rec_doubles * sizeof(double));
+    std::memcpy(c->warp_m.h + rec_doubles, start.data(), start.size() * sizeof(int));
+    if (upload_send(c, c->warp_m, c->ev_warp_m, rec_doubles * sizeof(double) + start.size() * sizeof(int))) return 1;
+
+    RaggedArgs g;
+    g.src = static_cast<const uint8_t*>(d_src);
+    g.batch = (int)batch;
+    g.n_tiles = (int)n_tiles;
+    uint8_t* dst = static_cast<uint8_t*>(d_dst);
+    const RaggedFrame* frames = reinterpret_cast<const RaggedFrame*>(c->warp_m.d.get());
+    const int* tile_start = reinterpret_cast<const int*>(c->warp_m.d.get() + rec_doubles);
+    const int grid = (int)std::min<int64_t>((n_tiles + 7) / 8 * 8, kMaxGrid);
+    launch_by_format(format, [&](auto fmt) {
+        hipLaunchKernelGGL(warp_ragged_kernel<decltype(fmt)::value>, dim3(grid), dim3(kBlock), 0, c->stream, g, frames, tile_start, dst);
+    });
+    LR_HIP(hipGetLastError());
+    return 0;
 }
 
 // lr_warp_perspective_device with LR_WARP_PACKED: M is the table of 13 doubles per frame, out_width x out_height bound the
@@ -407,8 +308,7 @@ int warp_packed(lr_context* c, const void* d_src, size_t src_image_bytes, int ba
         if (bits & 3u) return fail("f32 pointer or stride not 4-byte aligned");
     }
     // the table: every frame's map, size and place, and the tiles before it
-    constexpr double kExact = 9007199254740992.0;  // 2^53: integers up to it are doubles
-    std::vector<PackedFrame> rec((size_t)batch);
+    std::vector<RaggedFrame> rec((size_t)batch);
     std::vector<int> start((size_t)batch + 1);
     std::vector<std::pair<uint64_t, uint64_t>> extent((size_t)batch);  // [first byte, end)
     int64_t n_tiles = 0;
@@ -428,58 +328,25 @@ int warp_packed(lr_context* c, const void* d_src, size_t src_image_bytes, int ba
             __builtin_add_overflow(end, ow * bpp, &end) || end > dst_bytes)
             return fail("a frame reaches beyond dst_image_bytes");
         extent[(size_t)b] = {off, end};
-        PackedFrame& f = rec[(size_t)b];
+        RaggedFrame& f = rec[(size_t)b];
+        std::memset(&f, 0, sizeof f);
         std::memcpy(f.m, t, sizeof f.m);
         f.offset = off;
         f.row_bytes = row;
+        f.src_offset = (uint64_t)b * src_image_bytes;  // (the frames share one source size and stride)
+        f.src_row_bytes = src_row_bytes;
         f.ow = (int)ow;
         f.oh = (int)oh;
         f.tiles_x = (int)((ow + kTileW - 1) / kTileW);
-        f.pad = 0;
+        f.w = width;
+        f.h = height;
         start[(size_t)b] = (int)n_tiles;
         n_tiles += (int64_t)f.tiles_x * (int64_t)((oh + kTileH - 1) / kTileH);
         if (n_tiles > 0x7FFFFFF0ll) return fail("output larger than 2^31 tiles of 64 x 16 pixels");
     }
     start[(size_t)batch] = (int)n_tiles;
-    std::sort(extent.begin(), extent.end());
-    for (int b = 1; b < batch; ++b)
-        if (extent[(size_t)b].first < extent[(size_t)b - 1].second) return fail("two frames' extents overlap");
-
-    // records, then the prefix table, in the mirror of the maps (in doubles: 13 a frame + the table's ints)
-    const size_t rec_doubles = (size_t)batch * 13, need = rec_doubles + ((size_t)batch + 2) / 2;
-    LR_HIP(hipSetDevice(c->device));
-    if (need > c->warp_m.cap()) {  // (grows: the buffers of a previous call may still be read by its launch)
-        LR_HIP(hipStreamSynchronize(c->stream));
-        if (c->warp_m.grow(need)) return 1;
-    }
-    if (c->ev_warp_m.ensure(hipEventDisableTiming)) return 1;
-    LR_HIP(hipEventSynchronize(c->ev_warp_m));  // the previous call's upload has read h_warp_m
-    std::memcpy(c->warp_m.h, rec.data(), rec_doubles * sizeof(double));
-    std::memcpy(c->warp_m.h + rec_doubles, start.data(), start.size() * sizeof(int));
-    const size_t up_bytes = rec_doubles * sizeof(double) + start.size() * sizeof(int);
-    LR_HIP(hipMemcpyAsync(c->warp_m.d, c->warp_m.h, up_bytes, hipMemcpyHostToDevice, c->stream));
-    LR_HIP(hipEventRecord(c->ev_warp_m, c->stream));
-
-    PackedArgs g;
-    g.src = static_cast<const uint8_t*>(d_src);
-    g.src_image_bytes = src_image_bytes;
-    g.src_row_bytes = src_row_bytes;
-    g.w = width;
-    g.h = height;
-    uint8_t* dst = static_cast<uint8_t*>(d_dst);
-    const PackedFrame* frames = reinterpret_cast<const PackedFrame*>(c->warp_m.d.get());
-    const int* tile_start = reinterpret_cast<const int*>(c->warp_m.d.get() + rec_doubles);
-    g.batch = batch;
-    g.n_tiles = (int)n_tiles;
-    const int grid = (int)std::min<int64_t>((n_tiles + 7) / 8 * 8, kMaxGrid);
-    if (format == LR_PIX_U8)
-        hipLaunchKernelGGL(warp_packed_kernel<LR_PIX_U8>, dim3(grid), dim3(kBlock), 0, c->stream, g, frames, tile_start, dst);
-    else if (format == LR_PIX_U8X3)
-        hipLaunchKernelGGL(warp_packed_kernel<LR_PIX_U8X3>, dim3(grid), dim3(kBlock), 0, c->stream, g, frames, tile_start, dst);
-    else
-        hipLaunchKernelGGL(warp_packed_kernel<LR_PIX_F32>, dim3(grid), dim3(kBlock), 0, c->stream, g, frames, tile_start, dst);
-    LR_HIP(hipGetLastError());
-    return 0;
+    if (extents_overlap(extent)) return fail("two frames' extents overlap");
+    return launch_ragged(c, d_src, format, rec, start, d_dst);
 }
 
 // lr_warp_perspective_device with LR_WARP_RAGGED: M is the table of 18 doubles per frame, width x height and out_width x
@@ -512,38 +379,7 @@ int warp_ragged(lr_context* c, const void* d_src, size_t src_bytes, int batch, i
         tiles += f.tiles_x * (int)((s.oh + kTileH - 1) / kTileH);
     }
     start[(size_t)batch] = tiles;
-
-    // records, then the prefix table, in the mirror of the maps (in doubles: 18 a frame + the table's ints)
-    const size_t rec_doubles = (size_t)batch * 18, need = rec_doubles + ((size_t)batch + 2) / 2;
-    LR_HIP(hipSetDevice(c->device));
-    if (need > c->warp_m.cap()) {  // (grows: the buffers of a previous call may still be read by its launch)
-        LR_HIP(hipStreamSynchronize(c->stream));
-        if (c->warp_m.grow(need)) return 1;
-    }
-    if (c->ev_warp_m.ensure(hipEventDisableTiming)) return 1;
-    LR_HIP(hipEventSynchronize(c->ev_warp_m));  // the previous call's upload has read h_warp_m
-    std::memcpy(c->warp_m.h, rec.data(), rec_doubles * sizeof(double));
-    std::memcpy(c->warp_m.h + rec_doubles, start.data(), start.size() * sizeof(int));
-    const size_t up_bytes = rec_doubles * sizeof(double) + start.size() * sizeof(int);
-    LR_HIP(hipMemcpyAsync(c->warp_m.d, c->warp_m.h, up_bytes, hipMemcpyHostToDevice, c->stream));
-    LR_HIP(hipEventRecord(c->ev_warp_m, c->stream));
-
-    RaggedArgs g;
-    g.src = static_cast<const uint8_t*>(d_src);
-    g.batch = batch;
-    g.n_tiles = (int)n_tiles;
-    uint8_t* dst = static_cast<uint8_t*>(d_dst);
-    const RaggedFrame* frames = reinterpret_cast<const RaggedFrame*>(c->warp_m.d.get());
-    const int* tile_start = reinterpret_cast<const int*>(c->warp_m.d.get() + rec_doubles);
-    const int grid = (int)std::min<int64_t>((n_tiles + 7) / 8 * 8, kMaxGrid);
-    if (format == LR_PIX_U8)
-        hipLaunchKernelGGL(warp_ragged_kernel<LR_PIX_U8>, dim3(grid), dim3(kBlock), 0, c->stream, g, frames, tile_start, dst);
-    else if (format == LR_PIX_U8X3)
-        hipLaunchKernelGGL(warp_ragged_kernel<LR_PIX_U8X3>, dim3(grid), dim3(kBlock), 0, c->stream, g, frames, tile_start, dst);
-    else
-        hipLaunchKernelGGL(warp_ragged_kernel<LR_PIX_F32>, dim3(grid), dim3(kBlock), 0, c->stream, g, frames, tile_start, dst);
-    LR_HIP(hipGetLastError());
-    return 0;
+    return launch_ragged(c, d_src, format, rec, start, d_dst);
 }
 
 }  // namespace
@@ -567,7 +403,6 @@ int ragged_parse(const void* d_src, size_t src_bytes, int batch, int width, int 
     const bool src_f32 = format == LR_PIX_F32, dst_f32 = prepare || format == LR_PIX_F32;
     if (src_f32 && (reinterpret_cast<uintptr_t>(d_src) & 3u)) return fail("f32 source pointer not 4-byte aligned");
     if (dst_f32 && (reinterpret_cast<uintptr_t>(d_dst) & 3u)) return fail("f32 destination pointer not 4-byte aligned");
-    constexpr double kExact = 9007199254740992.0;  // 2^53: integers up to it are doubles
     out.assign((size_t)batch, RaggedEntry{});
     std::vector<std::pair<uint64_t, uint64_t>> extent((size_t)batch);  // of the outputs: [first byte, end)
     int64_t n_tiles = 0;
@@ -602,9 +437,7 @@ int ragged_parse(const void* d_src, size_t src_bytes, int batch, int width, int 
         n_tiles += (int64_t)((s.ow + (uint64_t)tile_w - 1) / (uint64_t)tile_w) * (int64_t)((s.oh + (uint64_t)tile_h - 1) / (uint64_t)tile_h);
         if (n_tiles > 0x7FFFFFF0ll) return fail("output larger than 2^31 tiles");
     }
-    std::sort(extent.begin(), extent.end());
-    for (int b = 1; b < batch; ++b)
-        if (extent[(size_t)b].first < extent[(size_t)b - 1].second) return fail("two frames' output extents overlap");
+    if (extents_overlap(extent)) return fail("two frames' output extents overlap");
     *n_tiles_out = n_tiles;
     return 0;
 }
@@ -679,15 +512,9 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
     if (n_tiles > 0x7FFFFFF0ll) return fail("output larger than 2^31 tiles of 64 x 16 pixels");
 
     LR_HIP(hipSetDevice(c->device));
-    if ((size_t)batch * 9 > c->warp_m.cap()) {  // (grows: the buffers of a previous call may still be read by its launch)
-        LR_HIP(hipStreamSynchronize(c->stream));
-        if (c->warp_m.grow((size_t)batch * 9)) return 1;
-    }
-    if (c->ev_warp_m.ensure(hipEventDisableTiming)) return 1;
-    LR_HIP(hipEventSynchronize(c->ev_warp_m));  // the previous call's upload has read h_warp_m
+    if (upload_reserve(c, c->warp_m, c->ev_warp_m, (size_t)batch * 9)) return 1;
     std::memcpy(c->warp_m.h, M, (size_t)batch * 9 * sizeof(double));
-    LR_HIP(hipMemcpyAsync(c->warp_m.d, c->warp_m.h, (size_t)batch * 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    LR_HIP(hipEventRecord(c->ev_warp_m, c->stream));
+    if (upload_send(c, c->warp_m, c->ev_warp_m, (size_t)batch * 9 * sizeof(double))) return 1;
 
     WarpArgs g;
     g.src = static_cast<const uint8_t*>(d_src);
@@ -705,12 +532,9 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
     g.tiles_per_frame = (int)(tiles_x * tiles_y);
     g.n_tiles = (int)n_tiles;
     const int grid = (int)std::min<int64_t>((n_tiles + 7) / 8 * 8, kMaxGrid);
-    if (format == LR_PIX_U8)
-        hipLaunchKernelGGL(warp_perspective_kernel<LR_PIX_U8>, dim3(grid), dim3(kBlock), 0, c->stream, g);
-    else if (format == LR_PIX_U8X3)
-        hipLaunchKernelGGL(warp_perspective_kernel<LR_PIX_U8X3>, dim3(grid), dim3(kBlock), 0, c->stream, g);
-    else
-        hipLaunchKernelGGL(warp_perspective_kernel<LR_PIX_F32>, dim3(grid), dim3(kBlock), 0, c->stream, g);
+    launch_by_format(format, [&](auto fmt) {
+        hipLaunchKernelGGL(warp_perspective_kernel<decltype(fmt)::value>, dim3(grid), dim3(kBlock), 0, c->stream, g);
+    });
     LR_HIP(hipGetLastError());
     return 0;
 }

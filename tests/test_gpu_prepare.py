@@ -87,6 +87,8 @@ SIZES = [  # source width, height -> output width, height
     (1, 1, 1, 1), (2, 1, 1, 1), (3, 2, 2, 1), (4, 2, 3, 2), (5, 1, 5, 1), (5, 2, 2, 2), (9, 2, 4, 1),  # widths 1-5, heights 1, 2
     (1000, 563, 333, 187),  # neither a multiple of the tile
     (257, 131, 129, 67),
+    (130, 10, 65, 5),       # a partial tile in both directions
+    (1100, 20, 2, 2),       # a pixel's 550 column taps cross the 512-pixel chunk, its 10 row taps the 8-row chunk
 ]
 
 
@@ -115,6 +117,14 @@ def test_identity_is_the_conversion_alone(ctx, fmt):
         luma = src if fmt == 0 else (4899 * c[..., 0] + 9617 * c[..., 1] + 1868 * c[..., 2] + 8192) >> 14
         exp = luma.astype(np.float32) / np.float32(256.0)
     assert_same_bits(got, exp)
+
+
+def test_u8x3_source_whose_first_byte_is_at_an_odd_offset(ctx):
+    """the unaligned row start of the staging fetch, on the shapes that walk a partial tile and both chunk loops"""
+    for w, h, ow, oh in ((130, 10, 65, 5), (1100, 20, 2, 2), (1, 1, 1, 1)):
+        src = frame(1, w, h, 50 + w)
+        for src_off, src_pad in ((1, 0), (3, 2)):
+            assert_same_bits(run_prepare(ctx, src, 1, ow, oh, src_pad=src_pad, src_off=src_off), P.prepare(src, ow, oh))
 
 
 def test_trim_frees_the_span_table_and_the_next_call_makes_it_again(ctx):

@@ -9,7 +9,7 @@ import pytest
 
 import numpy_prepare_ref as PR
 import numpy_warp_ref as R
-from test_gpu_rectify_batch import KINDS, SENTINEL, SETTINGS, SIZES, _kw, cut, gray_frame, same_results, seven_frames_table, written_mask
+from test_gpu_rectify_batch import EDGE_BATCHES, EDGE_KINDS, EDGE_SIZES, KINDS, SENTINEL, SETTINGS, SIZES, _kw, cut, gray_frame, edge_table, same_results, seven_frames_table, written_mask
 from test_gpu_rectify_warp import BPP, DTYPE, assert_same, frame, maps, synthetic_rgb
 
 pytestmark = pytest.mark.gpu
@@ -39,10 +39,10 @@ def P(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
-def source_region(frames, fmt, whole_pixels=False):
+def source_region(frames, fmt, whole_pixels=False, odd_stride=True):
     """The frames in one region, one after the other, with padded rows, gaps and (8-bit) odd offsets and strides
-    (whole_pixels: strides that the detector takes, too).  Returns (the region's bytes, [(width, height, byte_offset,
-    row_bytes)])."""
+    (whole_pixels: strides that the detector takes, too; odd_stride=False: a list too short to hold an odd stride for
+    sure).  Returns (the region's bytes, [(width, height, byte_offset, row_bytes)])."""
     bpp = BPP[fmt]
     cursor = 8 if fmt == 2 else 5
     sources = []
@@ -58,7 +58,7 @@ def source_region(frames, fmt, whole_pixels=False):
         rows = np.lib.stride_tricks.as_strided(buf[off:], (h, w * bpp), (row, 1))
         rows[:] = np.ascontiguousarray(f).reshape(h, -1).view(np.uint8)
     if fmt != 2:
-        assert any(s[2] % 2 for s in sources) and (whole_pixels or any(s[3] % 2 for s in sources))
+        assert any(s[2] % 2 for s in sources) and (whole_pixels or not odd_stride or any(s[3] % 2 for s in sources))
     return buf, sources
 
 
@@ -115,6 +115,31 @@ def test_ragged_warp_bit_exact_and_writes_nothing_else(L, ctx, fmt):
         assert_same(out, R.warp(srcs[b], table[b, :9], ow, oh)), KINDS[b]
         assert_same(out, np.ascontiguousarray(singles[b]).view(DTYPE[fmt]).reshape(out.shape))
     assert_same(cut(got, table[0, :13], fmt), srcs[0][:1, :1])  # (identity)
+
+
+@pytest.mark.parametrize("which", EDGE_BATCHES)
+@pytest.mark.parametrize("fmt", [0, 1, 2])
+def test_ragged_warp_of_a_few_tiles(L, ctx, fmt, which):
+    """EDGE_SIZES (six tiles in all: some XCDs' runs are empty), every frame from a source of its own size"""
+    srcs = [frame(fmt, *[(70, 20), (5, 7), (64, 16)][s], 200 + s) for s in which]
+    buf, sources = source_region(srcs, fmt, odd_stride=len(which) > 1)
+    packed, region = edge_table(fmt, which)
+    table = np.zeros((len(which), 18))
+    table[:, 9:13] = packed[:, 9:]
+    for k, s in enumerate(which):
+        table[k, :9] = maps(*sources[k][:2], *EDGE_SIZES[s])[EDGE_KINDS[s]].reshape(-1)
+        table[k, 13:17] = sources[k]
+    d_src = ctx.device_upload(buf)
+    d_dst = ctx.device_upload(np.full(region, SENTINEL, np.uint8))
+    try:
+        ctx.warp_perspective_ragged_device(d_src, len(buf), fmt, table, d_dst, region)
+        got = ctx.device_download(d_dst, (region,), np.uint8)
+    finally:
+        ctx.device_free(d_src)
+        ctx.device_free(d_dst)
+    assert (got[~written_mask(region, table[:, :13], BPP[fmt])] == SENTINEL).all(), "bytes outside the frames' pixel rows were written"
+    for k, s in enumerate(which):
+        assert_same(cut(got, table[k, :13], fmt), R.warp(srcs[k], table[k, :9], *EDGE_SIZES[s])), EDGE_KINDS[s]
 
 
 # ---- the ragged prepare step -------------------------------------------------------------------------------------
@@ -175,6 +200,42 @@ def test_ragged_prepare_bit_exact_and_writes_nothing_else(L, ctx, fmt):
         c = srcs[0].astype(np.int64)
         lum = c if fmt == 0 else (4899 * c[..., 0] + 9617 * c[..., 1] + 1868 * c[..., 2] + 8192) >> 14
         assert_same(cut(got, table[0, :13], 2), lum.astype(np.float32) / np.float32(256))
+
+
+EDGE_PREPARE = [  # source width, height -> output width, height
+    (130, 10, 65, 5),   # a partial tile in both directions
+    (1100, 20, 2, 2),   # a pixel's 550 column taps cross the 512-pixel chunk, its 10 row taps the 8-row chunk
+    (1, 1, 1, 1),
+]
+
+
+@pytest.mark.parametrize("fmt", [0, 1, 2])
+def test_ragged_prepare_edge_shapes(L, ctx, fmt):
+    srcs = [frame(fmt, w, h, 400 + k) for k, (w, h, _, _) in enumerate(EDGE_PREPARE)]
+    buf, sources = source_region(srcs, fmt)
+    if fmt == 1:
+        assert all(s[2] % 2 for s in sources[:2]), "u8x3 sources whose first byte is at an odd offset"
+    table = np.full((3, 18), np.nan)
+    cursor = 8
+    for b in (2, 0, 1):  # placed out of frame order, with gaps and padded rows
+        ow, oh = EDGE_PREPARE[b][2:]
+        row = ow * 4 + 4 * b
+        table[b, 9:13] = (ow, oh, cursor, row)
+        cursor += (oh - 1) * row + ow * 4 + 12
+    table[:, 13:17] = sources
+    table[:, 17] = 0
+    region = cursor + 12
+    d_src = ctx.device_upload(buf)
+    d_dst = ctx.device_upload(np.full(region, SENTINEL, np.uint8))
+    try:
+        ctx.prepare_ragged_device(d_src, len(buf), fmt, table, d_dst, region)
+        got = ctx.device_download(d_dst, (region,), np.uint8)
+    finally:
+        ctx.device_free(d_src)
+        ctx.device_free(d_dst)
+    assert (got[~written_mask(region, table[:, :13], 4)] == SENTINEL).all(), "bytes outside the frames' pixel rows were written"
+    for b, (w, h, ow, oh) in enumerate(EDGE_PREPARE):
+        assert_same(cut(got, table[b, :13], 2), PR.prepare(srcs[b], ow, oh))
 
 
 # ---- failures are clean ------------------------------------------------------------------------------------------

@@ -124,6 +124,46 @@ def test_packed_warp_bit_exact_and_writes_nothing_else(L, ctx, fmt):
     assert_same(cut(got, table[0], fmt), frames[0][:1, :1])  # (identity)
 
 
+# one tile, exactly one tile, one pixel over in each direction (four tiles, a partial lane at the right edge): six tiles in
+# all, so some XCDs' runs are empty; together and each as a batch of one
+EDGE_SIZES = [(1, 1), (64, 16), (65, 17)]
+EDGE_KINDS = ["identity", "perspective", "rotation"]
+EDGE_BATCHES = [(0, 1, 2), (0,), (1,), (2,)]
+
+
+def edge_table(fmt, which, w=W, h=H):
+    """the frames `which` of EDGE_SIZES one after the other, with gaps, padded strides and (8-bit) an odd offset"""
+    bpp = BPP[fmt]
+    table = np.zeros((len(which), 13))
+    cursor = 8 if fmt == 2 else 5
+    for k, s in enumerate(which):
+        ow, oh = EDGE_SIZES[s]
+        stride = ow * bpp + ((4, 12, 0)[k] if fmt == 2 else (1, 4, 0)[k])
+        table[k, :9] = maps(w, h, ow, oh)[EDGE_KINDS[s]].reshape(-1)
+        table[k, 9:] = (ow, oh, cursor, stride)
+        cursor += (oh - 1) * stride + ow * bpp + (4 if fmt == 2 else 3)
+    return table, cursor + 9
+
+
+@pytest.mark.parametrize("which", EDGE_BATCHES)
+@pytest.mark.parametrize("fmt", [0, 1, 2])
+def test_packed_warp_of_a_few_tiles(L, ctx, fmt, which):
+    w, h = 70, 20
+    frames = [frame(fmt, w, h, 100 + b) for b in which]
+    table, region = edge_table(fmt, which, w, h)
+    d_src, simg, srow = upload_frames(ctx, frames, fmt, 4 if fmt == 2 else 1, 4 if fmt == 2 else 7)
+    d_dst = ctx.device_upload(np.full(region, SENTINEL, np.uint8))
+    try:
+        ctx.warp_perspective_packed_device(d_src, simg, len(which), w, h, srow, fmt, table, d_dst, region)
+        got = ctx.device_download(d_dst, (region,), np.uint8)
+    finally:
+        ctx.device_free(d_src)
+        ctx.device_free(d_dst)
+    assert (got[~written_mask(region, table, BPP[fmt])] == SENTINEL).all(), "bytes outside the frames' pixel rows were written"
+    for k, s in enumerate(which):
+        assert_same(cut(got, table[k], fmt), R.warp(frames[k], table[k, :9], *EDGE_SIZES[s])), EDGE_KINDS[s]
+
+
 def test_packed_warp_large_frames(L, ctx):
     """Three 3840 x 2160 u8x3 frames, one of them at the full 3w x 3h: the whole images against the single-frame launch,
     bands of rows against the second source."""

@@ -130,6 +130,36 @@ def test_bit_exact_large_frames(L, ctx, fmt, w, h):
             assert_same(got, src)
 
 
+# outputs of one tile (1 x 1), exactly one tile (64 x 16) and one pixel over in each direction (65 x 17: four tiles, a partial
+# lane at the right edge); at most twelve tiles in a launch, so some XCDs' runs are short or empty
+@pytest.mark.parametrize("fmt", [0, 1, 2])
+@pytest.mark.parametrize("ow,oh,batch", [(1, 1, 1), (64, 16, 1), (65, 17, 1), (65, 17, 3)])
+def test_outputs_of_a_few_tiles(L, ctx, fmt, ow, oh, batch):
+    w, h = 70, 20
+    bpp = BPP[fmt]
+    frames = [frame(fmt, w, h, 40 + b) for b in range(batch)]
+    m = maps(w, h, ow, oh)
+    Ms = np.stack([m[name] for name in ("rotation", "identity", "perspective")[:batch]])
+    srow, drow = w * bpp + (4 if fmt == 2 else 1), ow * bpp + (4 if fmt == 2 else 3)
+    simg, dimg = h * srow + (4 if fmt == 2 else 7), oh * drow + (12 if fmt == 2 else 5)
+    sbuf = np.zeros(batch * simg, np.uint8)
+    for b, f in enumerate(frames):
+        sbuf[b * simg: b * simg + h * srow].reshape(h, srow)[:, : w * bpp] = f.reshape(h, -1).view(np.uint8)
+    d_src = ctx.device_upload(sbuf)
+    d_dst = ctx.device_upload(np.full(batch * dimg, 0xAB, np.uint8))
+    try:
+        ctx.warp_perspective_device(d_src, simg, batch, w, h, srow, fmt, Ms, d_dst, dimg, ow, oh, drow)
+        got = ctx.device_download(d_dst, (batch * dimg,), np.uint8)
+    finally:
+        ctx.device_free(d_src)
+        ctx.device_free(d_dst)
+    for b in range(batch):
+        rows = got[b * dimg: b * dimg + oh * drow].reshape(oh, drow)
+        assert (rows[:, ow * bpp:] == 0xAB).all() and (got[b * dimg + oh * drow: (b + 1) * dimg] == 0xAB).all()
+        out = np.ascontiguousarray(rows[:, : ow * bpp]).view(DTYPE[fmt]).reshape((oh, ow, 3) if fmt == 1 else (oh, ow))
+        assert_same(out, R.warp(frames[b], Ms[b], ow, oh))
+
+
 @pytest.mark.parametrize("fmt", [0, 1, 2])
 def test_batch_of_seven_frames_with_their_own_maps(L, ctx, fmt):
     w, h, ow, oh = 257, 131, 200, 150

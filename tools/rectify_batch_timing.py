@@ -232,8 +232,9 @@ def parent(out_path, batch, reps, repeats, shapes):
             for way in ("packed", "uniform", "single"):
                 with tempfile.TemporaryDirectory() as tmp:
                     out = step(["rocprofv3", "--kernel-trace", "--stats", "-d", tmp, "-o", "rb", "--output-format", "csv", "--"] + me + ["--child", "warp", "--way", way] + here, log)
-                    name = "warp_packed_kernel" if way == "packed" else "warp_perspective_kernel"
-                    other = "warp_perspective_kernel" if way == "packed" else "warp_packed_kernel"
+                    # (the packed warp is a launch of the table kernel, warp_ragged_kernel)
+                    name = "warp_ragged_kernel" if way == "packed" else "warp_perspective_kernel"
+                    other = "warp_perspective_kernel" if way == "packed" else "warp_ragged_kernel"
                     ns, stray = dispatch_times(tmp, name), dispatch_times(tmp, other)
                 per = batch if way == "single" else 1
                 if len(ns) != (WARM + reps) * per or stray:
