@@ -6,7 +6,7 @@
 //
 //   rectify_recipe in.pgm|in.ppm out_prefix [--max-size N|fraction] [--refine] [--threads N]
 //                  [--h-strategy rotate_h|rotate_v|rectify|keep] [--v-strategy ...] [--warp] [--device-prepare] [--lines]
-//                  [--jpeg Q]
+//                  [--jpeg Q] [--jpeg-in]
 //
 // Input is a binary PGM (P5, 8 bit) or PPM (P6, 8 bit; converted with the usual integer luma weights
 // (4899 R + 9617 G + 1868 B + 8192) >> 14).  Image decoding stays with the caller's imaging library.
@@ -22,6 +22,11 @@
 // --jpeg Q: the demo's products as it writes them (autorectify.cpp:368-369, imwrite) -- implies --warp; the rectified picture
 // is compressed where the warp left it in HBM (lr_encode_jpeg_device, quality Q, 4:2:0 for colour) and only the stream comes
 // back: <out_prefix>_warp.jpg, and with --lines also <out_prefix>_warp_lines.jpg.
+// --jpeg-in: the input file is a baseline JPEG file (the demo's imread) -- lr_jpeg_info tells its size from the headers, the
+// file goes up as it is and lr_decode_jpeg_device decodes it in HBM (RGB, or gray for a one-component file).  The example
+// then downloads the picture and goes on exactly as --device-prepare does with a PPM it has read, so here the pixels do
+// cross the link (once down, once up): a caller who wants them to stay in HBM passes the decoder's output on, as
+// Context.rectify_batch does with a list of files.  EXIF orientation is not applied.
 // Links against librectify_amd.so exactly like a program written for the reference.
 #include <algorithm>
 #include <cctype>
@@ -32,6 +37,7 @@
 #include <cstring>
 #include <fstream>
 #include <iostream>
+#include <iterator>
 #include <string>
 #include <vector>
 
@@ -86,6 +92,51 @@ bool load_pnm(const std::string& path, Gray& g) {
     for (size_t i = 0; i < g.px.size(); ++i) {
         int v = raw[i * ch];
         if (ch == 3) v = (4899 * raw[i * 3] + 9617 * raw[i * 3 + 1] + 1868 * raw[i * 3 + 2] + 8192) >> 14;
+        g.px[i] = (float)v * (1.0f / 256.0f);
+    }
+    return true;
+}
+
+// --jpeg-in: the file decoded on the GPU into g.raw (and g.px, for --lines).  Returns false with the reason on stderr.
+bool load_jpeg(const std::string& path, Gray& g) {
+    std::ifstream f(path, std::ios::binary);
+    std::vector<uint8_t> file((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+    if (!f || file.empty()) {
+        std::fprintf(stderr, "cannot read %s\n", path.c_str());
+        return false;
+    }
+    double frame[8] = {0, (double)file.size(), 0, 0, 0, 0, 0, 0};
+    int32_t info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (lr_jpeg_info(file.data(), file.size(), frame, 1, info) != 0 || info[5] != 0) {
+        std::fprintf(stderr, "jpeg input failed: %s\n", lr_last_error());
+        return false;
+    }
+    g.w = info[0];
+    g.h = info[1];
+    g.ch = info[2] == 1 ? 1 : 3;
+    g.raw.resize((size_t)g.w * g.h * g.ch);
+    frame[3] = (double)g.w * g.ch;
+    frame[4] = g.w;
+    frame[5] = g.h;
+    lr_context* ctx = nullptr;
+    void* d_file = nullptr;
+    void* d_img = nullptr;
+    const bool ok = lr_context_create(0, &ctx) == 0 && lr_device_malloc(ctx, file.size(), &d_file) == 0 &&
+                    lr_device_malloc(ctx, g.raw.size(), &d_img) == 0 && lr_memcpy_h2d(ctx, d_file, file.data(), file.size()) == 0 &&
+                    lr_decode_jpeg_device(ctx, d_file, file.data(), file.size(), g.ch == 3 ? LR_PIX_U8X3 : LR_PIX_U8, frame, 1, d_img,
+                                          g.raw.size(), info) == 0 &&
+                    info[5] == 0 && lr_memcpy_d2h(ctx, g.raw.data(), d_img, g.raw.size()) == 0;
+    if (!ok) std::fprintf(stderr, "jpeg input failed: %s\n", lr_last_error());
+    if (ctx) {
+        if (d_file) lr_device_free(ctx, d_file);
+        if (d_img) lr_device_free(ctx, d_img);
+        lr_context_destroy(ctx);
+    }
+    if (!ok) return false;
+    g.px.resize((size_t)g.w * g.h);
+    for (size_t i = 0; i < g.px.size(); ++i) {
+        int v = g.raw[i * g.ch];
+        if (g.ch == 3) v = (4899 * g.raw[i * 3] + 9617 * g.raw[i * 3 + 1] + 1868 * g.raw[i * 3 + 2] + 8192) >> 14;
         g.px[i] = (float)v * (1.0f / 256.0f);
     }
     return true;
@@ -302,12 +353,12 @@ int main(int argc, char** argv) {
         std::fprintf(stderr,
                      "usage: %s in.pgm|in.ppm out_prefix [--max-size N|fraction] [--refine] [--threads N]\n"
                      "          [--h-strategy rotate_h|rotate_v|rectify|keep] [--v-strategy ...] [--warp] [--device-prepare]\n"
-                     "          [--lines] [--jpeg Q]\n",
+                     "          [--lines] [--jpeg Q] [--jpeg-in]\n",
                      argv[0]);
         return 2;
     }
     float max_size = 1200.f;  // the demo's default
-    bool refine = false, warp = false, device_prepare = false, lines_pictures = false;
+    bool refine = false, warp = false, device_prepare = false, lines_pictures = false, jpeg_in = false;
     int threads = -1, jpeg = 0;
     RectificationConfig cfg;
     cfg.horizontal_vp_min_distance = 2;  // autorectify.cpp:347
@@ -318,6 +369,7 @@ int main(int argc, char** argv) {
         else if (a == "--warp") warp = true;
         else if (a == "--device-prepare") device_prepare = true;
         else if (a == "--lines") lines_pictures = true;
+        else if (a == "--jpeg-in") jpeg_in = device_prepare = true;
         else if (a == "--max-size" && has_val) max_size = (float)std::atof(argv[++i]);
         else if (a == "--threads" && has_val) threads = std::atoi(argv[++i]);
         else if (a == "--jpeg" && has_val && std::atoi(argv[i + 1]) >= 1 && std::atoi(argv[i + 1]) <= 100) {
@@ -332,7 +384,9 @@ int main(int argc, char** argv) {
         }
     }
     Gray full;
-    if (!load_pnm(argv[1], full)) {
+    if (jpeg_in) {
+        if (!load_jpeg(argv[1], full)) return 1;
+    } else if (!load_pnm(argv[1], full)) {
         std::fprintf(stderr, "cannot read %s (binary PGM/PPM, 8 bit, expected)\n", argv[1]);
         return 1;
     }

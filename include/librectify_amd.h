@@ -381,6 +381,65 @@ static inline size_t lr_jpeg_bound(int width, int height, int format, int layout
     return 640 + 2 * ((mcus + ri - 1) / ri) + 416 * mcus * bpm;
 }
 
+/* The demo's inputs are JPEG files as well (autorectify.cpp: imread): lr_decode_jpeg_device decodes baseline JPEG streams
+ * that lie in HBM into 8-bit frames in HBM, so that a folder of photographs goes up as files (about a tenth of the pixels'
+ * bytes).  One chain of launches for a batch of streams of different sizes and samplings; the call is SYNCHRONOUS like the
+ * encoder's, because the host needs the statuses.
+ * `frames` is a HOST table of 8 doubles per frame: [0] [1] byte offset and length of the stream in the source region (a
+ * length below 2^31), [2] [3] byte offset of the picture from d_dst and its row stride in bytes, [4] [5] the width and
+ * height the caller allocated for, [6] [7] reserved, 0.  `h_src` is a HOST copy of the source region (same layout as d_src):
+ * the host reads the headers up to SOS from it and nothing behind them.  `format` is the OUTPUT's format: LR_PIX_U8 gives the
+ * luminance plane (of a colour stream Y alone: its chrominance is entropy-decoded but never transformed), LR_PIX_U8X3 gives
+ * RGB with c0 red (a one-component stream replicated).  The table follows LR_WARP_RAGGED's rules: integers (at most 2^53),
+ * every extent inside its region, strides at least a row, output extents that overlap neither each other nor the source
+ * region; stream extents are only read and may overlap.  The whole table is checked before anything is enqueued: on a
+ * table error (also a null pointer, batch < 1, another format) nothing is launched or written, `info` is untouched and
+ * lr_last_error names the frame and the entry.
+ * `info` (HOST, 8 int32 per frame, written by the call): [0] width, [1] height, [2] components (1 or 3), [3] layout (0 =
+ * 4:2:0 or one component, 1 = 4:4:4, 2 = 4:2:2), [4] restart interval in MCUs (0: none), [5] status, [6] the most often
+ * any part of the scan had to be entropy-decoded until the chain of parts was consistent (see below; 0 in probe mode), [7] 0.
+ * Status: 0 decoded; 1 not a JPEG stream, or truncated before SOS; 2 unsupported (progressive, arithmetic, lossless or
+ * hierarchical coding, 12-bit precision, 16-bit quantisation tables, component counts other than 1 or 3, another sampling,
+ * a non-interleaved or multi-scan file, a missing table: lr_last_error tells which, for the last such frame); 3 the
+ * table's [4] [5] differ from the stream's size; 4 the scan is damaged (an invalid code, a coefficient index beyond 63,
+ * fewer or more MCUs than the frame has, a missing or misnumbered RSTm).  Per-frame failures are statuses, not failures of
+ * the call: a frame of status 1 to 3 is skipped on the host and no byte of its extent is written; of one of status 4 the
+ * extent's content is unspecified; nothing outside the frames' extents is ever written, and the call returns 0.
+ * Accepted: SOF0 or SOF1 with 8-bit samples, Huffman-coded, one interleaved scan, any DHT (table ids 0..3), any DRI or none,
+ * APPn and COM of any size, fill bytes in front of markers; the stream ends at EOI or at its length.  EXIF orientation is
+ * not applied.
+ * Probe mode: d_dst == NULL fills `info` from the headers alone and launches nothing; it needs no context (ctx may be NULL)
+ * and no GPU; [2] .. [5] of the table may then be 0 (no picture, no expected size).  lr_jpeg_info below spells it out.
+ * The arithmetic (tests/numpy_jpeg_decode_ref.py restates it) is exact, in integers.
+ * The entropy-coded bytes are cut into parts of 128 bytes, one lane each; every lane but a chain's first starts
+ * speculatively, and the chain is accepted at a verified fixed point (every part's entry state is its predecessor's exit
+ * state), which makes the result that of a sequential decoder on any content.
+ * The coefficients (2 bytes per sample of the padded components), the parts' records and the per-frame tables belong to
+ * the context's workspace: lr_context_trim frees them.
+ * The call travels through lr_warp_perspective_device like lr_encode_jpeg_device: LR_WARP_JPEG_DECODE or-ed into `format`,
+ * `M` pointing to an lr_jpeg_decode_args, src_image_bytes and dst_image_bytes the two regions' sizes, and width, height,
+ * out_width, out_height and both row strides 0 (any other option bit or a non-zero one of these fails cleanly). */
+typedef struct lr_jpeg_decode_args {
+    const void* h_src;    /* HOST copy of the stream region (same layout as d_src); only the headers are read from it */
+    const double* frames; /* HOST, 8 doubles per frame */
+    int32_t* info;        /* HOST, 8 int32 per frame, written by the call */
+} lr_jpeg_decode_args;
+enum lr_warp_jpeg_decode { LR_WARP_JPEG_DECODE = 0x4000 }; /* or-ed into `format` like lr_warp_option */
+static inline int lr_decode_jpeg_device(lr_context* ctx, const void* d_src, const void* h_src, size_t src_bytes, int format,
+                                        const double* frames, int batch, void* d_dst, size_t dst_bytes, int32_t* info) {
+    lr_jpeg_decode_args a;
+    a.h_src = h_src;
+    a.frames = frames;
+    a.info = info;
+    return lr_warp_perspective_device(ctx, d_src, src_bytes, batch, 0, 0, 0, format | LR_WARP_JPEG_DECODE,
+                                      (const double*)(const void*)&a, d_dst, dst_bytes, 0, 0, 0);
+}
+/* Probe mode of lr_decode_jpeg_device: width, height, components, layout, restart interval and status of every stream, from
+ * the headers in host memory.  No context, no GPU. */
+static inline int lr_jpeg_info(const void* h_src, size_t src_bytes, const double* frames, int batch, int32_t* info) {
+    return lr_decode_jpeg_device((lr_context*)0, (const void*)0, h_src, src_bytes, LR_PIX_U8X3, frames, batch, (void*)0, 0, info);
+}
+
 /* ---- stage API (tests, bench) --------------------------------------------------------- */
 /* Stage 1: fused 5x5 derivative filter + magnitude + direction bin + dilated-bin mask +
  * 5x5 non-max candidates (reference line_detector.cpp:41-49,126-182, filter.cpp:29-98,161-168). */

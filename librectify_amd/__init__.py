@@ -70,6 +70,10 @@ class JpegArgs(C.Structure):  # lr_jpeg_args
     _fields_ = [("frames", C.c_void_p), ("sizes", C.c_void_p)]
 
 
+class JpegDecodeArgs(C.Structure):  # lr_jpeg_decode_args
+    _fields_ = [("h_src", C.c_void_p), ("frames", C.c_void_p), ("info", C.c_void_p)]
+
+
 BUF_DX, BUF_DY, BUF_DMASK, BUF_LABEL, BUF_SEED_IDX, BUF_SEED_BIN, BUF_SEED_THR, BUF_MAXMAG, BUF_SEED_SIZE = range(9)
 T_UPLOAD, T_FILTER, T_SEEDS, T_FLOOD, T_FIT, T_RANSAC, T_TOTAL, T_FILTER_KERNEL, T_COUNT = range(9)
 PIX_U8, PIX_U8X3, PIX_F32 = range(3)  # enum lr_pixel_format
@@ -78,6 +82,8 @@ WARP_PACKED = 0x200  # enum lr_warp_layout, likewise: per-frame output sizes and
 WARP_RAGGED = 0x800  # enum lr_warp_sources, likewise: per-frame source sizes and places as well (ragged_table)
 WARP_LINES = 0x1000  # enum lr_warp_lines, likewise: lr_draw_lines_device, whose own arguments travel behind M (DrawLinesArgs)
 WARP_JPEG = 0x2000  # enum lr_warp_jpeg, likewise: lr_encode_jpeg_device, whose own arguments travel behind M (JpegArgs)
+WARP_JPEG_DECODE = 0x4000  # enum lr_warp_jpeg_decode, likewise: lr_decode_jpeg_device, whose own arguments travel behind M (JpegDecodeArgs)
+JPEG_OK, JPEG_NOT_JPEG, JPEG_UNSUPPORTED, JPEG_SIZE_MISMATCH, JPEG_DAMAGED = range(5)  # info[5] of lr_decode_jpeg_device
 FRAMES_U8, FRAMES_U8X3, FRAMES_F32 = 0x100, 0x200, 0x300  # enum lr_frames_option, or-ed into `refine` of the frame entries
 
 
@@ -391,6 +397,76 @@ def jpeg_table(sizes, sources, outputs, quality, layout=0):
     return table.astype(np.float64)
 
 
+def jpeg_decode_table(streams, outputs=None, sizes=None):
+    """The table of lr_decode_jpeg_device: streams: B pairs (byte_offset, length) of the streams in the source region;
+    outputs: B pairs (byte_offset, row_bytes) of the pictures in the destination region; sizes: B pairs (width, height)
+    the caller allocated for.  outputs and sizes None: probe mode's table (zeros).  Returns float64 (B, 8).  Rejects what
+    can be seen without the regions: entries below 0 or above 2^53, a length of 2^31 - 16 or more, sizes outside 1 .. 65535.
+    Needs no GPU."""
+    st = np.asarray(streams)
+    if st.ndim != 2 or st.shape[1] != 2 or not np.issubdtype(st.dtype, np.integer) or len(st) < 1:
+        raise ValueError("jpeg_decode_table: streams is B pairs of integers (byte_offset, length), B >= 1")
+    B = len(st)
+    if (outputs is None) != (sizes is None):
+        raise ValueError("jpeg_decode_table: outputs and sizes go together")
+    cols = [st]
+    for name, a in (("outputs", outputs), ("sizes", sizes)):
+        a = np.zeros((B, 2), np.int64) if a is None else np.asarray(a)
+        if a.shape != (B, 2) or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("jpeg_decode_table: %s is B pairs of integers" % name)
+        cols.append(a)
+    table = np.concatenate([c.astype(np.int64) for c in cols] + [np.zeros((B, 2), np.int64)], axis=1)
+    if table.min() < 0 or table.max() > 2 ** 53:
+        raise ValueError("jpeg_decode_table: an entry below 0 or above 2^53")
+    if int(table[:, 1].max()) > 2 ** 31 - 16:
+        raise ValueError("jpeg_decode_table: a stream longer than 2^31 - 16 bytes")
+    if sizes is not None and (int(table[:, 4:6].min()) < 1 or int(table[:, 4:6].max()) > 65535):
+        raise ValueError("jpeg_decode_table: a size outside 1 .. 65535")
+    return table.astype(np.float64)
+
+
+def _stream_region(streams):
+    """(the streams one behind the other as uint8, their (byte_offset, length) pairs)"""
+    streams = [bytes(s) for s in streams]
+    if not streams:
+        raise ValueError("no streams")
+    lens = np.array([len(s) for s in streams], np.int64)
+    offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+    region = np.frombuffer(b"".join(streams) or b"\0", np.uint8)
+    return np.ascontiguousarray(region), np.stack([offs, lens], axis=1)
+
+
+def _decode_call(handle, d_src, region, fmt, table, d_dst, dst_bytes):
+    table = np.ascontiguousarray(table, np.float64)
+    if table.ndim != 2 or table.shape[1] != 8 or len(table) < 1:
+        raise ValueError("decode_jpeg_device: the table has 8 values per frame")
+    region = np.ascontiguousarray(region, np.uint8)
+    info = np.zeros((len(table), 8), np.int32)
+    args = JpegDecodeArgs(_ptr(region), _ptr(table), _ptr(info))
+    _check(lib().lr_warp_perspective_device(handle, C.c_void_p(d_src) if d_src else None, region.nbytes, len(table), 0, 0, 0,
+                                            fmt | WARP_JPEG_DECODE, C.cast(C.byref(args), C.c_void_p),
+                                            C.c_void_p(d_dst) if d_dst else None, dst_bytes, 0, 0, 0))
+    return info
+
+
+def jpeg_info(streams):
+    """lr_jpeg_info (lr_decode_jpeg_device's probe mode): of every JPEG file in the list (bytes) width, height, components,
+    layout (0 = 4:2:0 or one component, 1 = 4:4:4, 2 = 4:2:2), restart interval and status (JPEG_OK, ...), from the headers
+    alone.  Returns int32 (B, 8).  No context, no GPU."""
+    region, extents = _stream_region(streams)
+    return _decode_call(None, None, region, PIX_U8X3, jpeg_decode_table(extents), None, 0)
+
+
+def _all_streams(frames, what):
+    """True if `frames` is a list of JPEG files (bytes), False if it holds none; a mixture is refused"""
+    if not isinstance(frames, (list, tuple)):
+        return False
+    n = sum(isinstance(f, (bytes, bytearray, memoryview)) for f in frames)
+    if n not in (0, len(frames)):
+        raise ValueError(what + ": the list is all JPEG files (bytes) or all arrays")
+    return n > 0
+
+
 def _source_extent(sources, bpp):
     """bytes of the region that holds the sources (width, height, byte_offset, row_bytes)"""
     return max(off + (h - 1) * row + w * bpp for w, h, off, row in sources)
@@ -625,6 +701,8 @@ class Context:
         lr_draw_lines_device call, one download.  Returns the list of H x W x 3 uint8 pictures: a loop of draw_lines.
         jpeg=Q: the pictures stay in HBM, are encoded there (lr_encode_jpeg_device, quality Q, 4:2:0) and come back as JPEG files
         (bytes): exactly the encoder's stream of the picture that jpeg=None returns."""
+        if _all_streams(frames, "draw_lines_batch"):
+            return self._draw_lines_streams([bytes(f) for f in frames], lines_list, Hs, jpeg)
         frames = [np.ascontiguousarray(f) for f in frames]
         if not frames or len(lines_list) != len(frames) or (Hs is not None and len(Hs) != len(frames)):
             raise ValueError("draw_lines_batch: as many line arrays (and Hs) as frames, at least one")
@@ -632,36 +710,48 @@ class Context:
         fmt, bpp = formats[0]
         if fmt == PIX_F32 or any(f != formats[0] for f in formats):
             raise ValueError("draw_lines_batch: uint8 frames, all H x W or all H x W x 3")
-        lines_list = [np.ascontiguousarray(l, LINE_DTYPE).reshape(-1) for l in lines_list]
-        sizes, sources, outputs, segments = [], [], [], []
-        src_end = dst_end = first = 0
-        for f, l in zip(frames, lines_list):
+        info, src_end = [], 0
+        for f in frames:
             h, w = f.shape[:2]
-            sizes.append((w, h))
-            sources.append((src_end, w * bpp))
-            outputs.append((dst_end, w * 3))
-            segments.append((first, len(l)))
+            info.append((w, h, src_end, w * bpp))
             src_end = (src_end + h * w * bpp + 3) // 4 * 4  # (every frame starts at a multiple of 4)
-            dst_end = (dst_end + h * w * 3 + 3) // 4 * 4
-            first += len(l)
-        table = draw_table(sizes, sources, outputs, segments)
         region = np.zeros(src_end, np.uint8)
-        for f, (off, _) in zip(frames, sources):
+        for f, (_, _, off, _) in zip(frames, info):
             region[off:off + f.size] = f.reshape(-1)
-        d_src = self.device_upload(region)
+        return self._draw_resident(self.device_upload(region), src_end, fmt, info, lines_list, Hs, jpeg)
+
+    def _draw_resident(self, d_src, src_bytes, fmt, frames, lines_list, Hs, jpeg):
+        """draw_lines_batch for frames (width, height, byte_offset, row_bytes) that lie in the src_bytes at d_src, which is
+        freed here: one lr_draw_lines_device call into a fresh buffer, then the download, or with jpeg the encoder"""
         d_dst = C.c_void_p()
         try:
+            lines_list = [np.ascontiguousarray(l, LINE_DTYPE).reshape(-1) for l in lines_list]
+            sizes, outputs, segments = [], [], []
+            dst_end = first = 0
+            for (w, h, _, _), l in zip(frames, lines_list):
+                sizes.append((w, h))
+                outputs.append((dst_end, w * 3))
+                segments.append((first, len(l)))
+                dst_end = (dst_end + h * w * 3 + 3) // 4 * 4
+                first += len(l)
+            table = draw_table(sizes, [f[2:] for f in frames], outputs, segments)
             _check(lib().lr_device_malloc(self._h, dst_end, C.byref(d_dst)))
-            self.draw_lines_device(d_src, src_end, fmt, np.concatenate(lines_list), table, d_dst.value, dst_end, H=Hs)
+            self.draw_lines_device(d_src, src_bytes, fmt, np.concatenate(lines_list), table, d_dst.value, dst_end, H=Hs)
             if jpeg is not None:
-                info = [(w, h, off, row) for (w, h), (off, row) in zip(sizes, outputs)]
-                return self._encode_resident(d_dst.value, dst_end, PIX_U8X3, info, jpeg, 0)
+                return self._encode_resident(d_dst.value, dst_end, PIX_U8X3, [(w, h, off, row) for (w, h), (off, row) in zip(sizes, outputs)], jpeg, 0)
             out = self.device_download(d_dst.value, (dst_end,), np.uint8)
         finally:
             self.device_free(d_src)
             if d_dst.value:
                 self.device_free(d_dst.value)
         return [out[off:off + w * h * 3].reshape(h, w, 3).copy() for (w, h), (off, _) in zip(sizes, outputs)]
+
+    def _draw_lines_streams(self, streams, lines_list, Hs, jpeg):
+        """draw_lines_batch for JPEG files (bytes): decoded in HBM, drawn on where they lie"""
+        if len(lines_list) != len(streams) or (Hs is not None and len(Hs) != len(streams)):
+            raise ValueError("draw_lines_batch: as many line arrays (and Hs) as frames, at least one")
+        d_src, src_bytes, fmt, frames = self._decode_resident(streams, None, "draw_lines_batch")
+        return self._draw_resident(d_src, src_bytes, fmt, frames, lines_list, Hs, jpeg)
 
     def draw_lines(self, image_u8, lines, H=None):
         """The demo's lines picture of one 8-bit frame (H x W gray or H x W x 3) and the detector's segments, drawn through
@@ -748,6 +838,74 @@ class Context:
         """The baseline JPEG file (bytes) of one 8-bit frame, H x W or H x W x 3 (c0 red), encoded on the GPU."""
         return self.encode_jpeg_batch([image_u8], quality, layout)[0]
 
+    def decode_jpeg_device(self, d_src, h_src, fmt, table, d_dst, dst_bytes):
+        """lr_decode_jpeg_device (lr_warp_perspective_device with LR_WARP_JPEG_DECODE): the table's baseline JPEG streams in
+        the region at d_src (h_src: the same bytes on the host, a uint8 array; only the headers are read from it) become
+        8-bit pictures (fmt PIX_U8: luminance, PIX_U8X3: RGB) in the dst_bytes at d_dst.  table: 8 doubles per frame
+        (jpeg_decode_table).  Synchronous.  Returns info, int32 (B, 8): width, height, components, layout, restart
+        interval, status, decodes of the most often decoded part, 0.  d_dst None: probe mode."""
+        return _decode_call(self._h, d_src, h_src, fmt, table, d_dst, dst_bytes)
+
+    def _decode_resident(self, streams, fmt, what):
+        """The JPEG files decoded into one fresh device buffer: one upload of the files, one lr_decode_jpeg_device call.
+        fmt None: PIX_U8 if every file has one component, else PIX_U8X3.  Returns (d_dst, total_bytes, fmt, frames) with
+        frames[b] = (width, height, byte_offset, row_bytes), every picture at a multiple of 4; the caller frees d_dst.
+        Raises LibrectifyError naming the first frame whose status is not 0."""
+        region, extents = _stream_region(streams)
+        info = _decode_call(None, None, region, PIX_U8X3, jpeg_decode_table(extents), None, 0)
+        bad = np.flatnonzero(info[:, 5])
+        if len(bad):
+            jpeg_info([streams[bad[0]]])  # (once more alone: lr_last_error then tells why)
+            raise LibrectifyError("%s: frame %d: status %d: %s" % (what, bad[0], info[bad[0], 5], lib().lr_last_error().decode().split(": ", 2)[-1]))
+        if fmt is None:
+            fmt = PIX_U8 if int(info[:, 2].max()) == 1 else PIX_U8X3
+        bpp = 3 if fmt == PIX_U8X3 else 1
+        frames, end = [], 0
+        for w, h in info[:, :2].tolist():
+            start = (end + 3) // 4 * 4
+            frames.append((w, h, start, w * bpp))
+            end = start + w * h * bpp
+        table = jpeg_decode_table(extents, np.array([f[2:] for f in frames], np.int64), np.array([f[:2] for f in frames], np.int64))
+        d_src = self.device_upload(region)
+        d_dst = C.c_void_p()
+        try:
+            _check(lib().lr_device_malloc(self._h, end, C.byref(d_dst)))
+            info = self.decode_jpeg_device(d_src, region, fmt, table, d_dst.value, end)
+            bad = np.flatnonzero(info[:, 5])
+            if len(bad):
+                raise LibrectifyError("%s: frame %d: status %d: %s" % (what, bad[0], info[bad[0], 5], lib().lr_last_error().decode()))
+            res, d_dst = d_dst.value, C.c_void_p()
+            return res, end, fmt, frames
+        finally:
+            self.device_free(d_src)
+            if d_dst.value:
+                self.device_free(d_dst.value)
+
+    def decode_jpeg_batch(self, streams, fmt=PIX_U8X3):
+        """A list of baseline JPEG files (bytes) of any sizes and samplings decoded on the GPU: one upload of the files, one
+        lr_decode_jpeg_device call, one download.  fmt PIX_U8X3: H x W x 3 RGB pictures (a one-component file replicated);
+        PIX_U8: H x W luminance.  Returns a list of uint8 arrays.  Raises LibrectifyError naming the frame on a status
+        other than 0 (jpeg_info tells the statuses beforehand)."""
+        if fmt not in (PIX_U8, PIX_U8X3):
+            raise ValueError("decode_jpeg_batch: fmt is PIX_U8 or PIX_U8X3")
+        d_dst, total, fmt, frames = self._decode_resident(streams, fmt, "decode_jpeg_batch")
+        try:
+            out = self.device_download(d_dst, (total,), np.uint8)
+        finally:
+            self.device_free(d_dst)
+        tail = (3,) if fmt == PIX_U8X3 else ()
+        return [out[off:off + h * row].reshape((h, w) + tail).copy() for w, h, off, row in frames]
+
+    def decode_jpeg(self, data, fmt=PIX_U8X3):
+        """One baseline JPEG file (bytes) decoded on the GPU: H x W x 3 RGB (PIX_U8X3) or H x W luminance (PIX_U8)."""
+        return self.decode_jpeg_batch([data], fmt)[0]
+
+    def _rectify_streams(self, streams, min_length, refine, cfg, clip, max_size, capacity, jpeg):
+        """rectify_batch for JPEG files: the files go up and are decoded in HBM, the pictures are handed to
+        rectify_frames_device where they lie; with jpeg=Q no pixel crosses the link in either direction"""
+        d_src, _, fmt, sources = self._decode_resident(streams, None, "rectify_batch")
+        return self._rectify_resident(d_src, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg)
+
     def prepare_device(self, d_src, src_image_bytes, batch, width, height, src_row_bytes, fmt, d_dst, dst_image_bytes,
                        out_width, out_height, dst_row_bytes):
         """lr_warp_perspective_device with LR_WARP_PREPARE: `batch` device frames of format fmt (PIX_U8, PIX_U8X3,
@@ -818,6 +976,11 @@ class Context:
         warp reads the same resident frame.
         jpeg=Q: `warped` is the rectified picture's JPEG file (bytes, quality Q, 4:2:0), encoded in HBM: rectify_batch's
         path for one frame."""
+        if isinstance(image_u8, (bytes, bytearray, memoryview)):  # a JPEG file: decoded in HBM, rectify_batch's path for one frame
+            lines, t, out = self.rectify_batch([bytes(image_u8)], min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, jpeg=jpeg)[0]
+            if out is None:
+                rectification_homography(t, clip)  # (raises what rectify raises for such a frame)
+            return lines, t, out
         img = np.ascontiguousarray(image_u8)
         if img.dtype != np.uint8 or not (img.ndim == 2 or (img.ndim == 3 and img.shape[2] == 3)):
             raise ValueError("rectify: an H x W or H x W x 3 uint8 frame")
@@ -1077,25 +1240,30 @@ class Context:
         host = np.zeros(end, np.uint8)
         for f, (_, _, start, _) in zip(frames, sources):
             host[start: start + f.nbytes] = f.reshape(-1)
-        d_src = self.device_upload(host)
+        return self._rectify_resident(self.device_upload(host), sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg)
+
+    def _rectify_resident(self, d_src, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg):
+        """rectify_batch for 8-bit frames (width, height, byte_offset, row_bytes) that lie at d_src, which is freed here:
+        rectify_frames_device, then one download of the pictures, or with jpeg the encoder and the streams alone"""
+        bpp = 3 if fmt == PIX_U8X3 else 1
         d_out = None
         try:
             lines, tfs, table, d_out, total = self.rectify_frames_device(d_src, sources, fmt, min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, capacity=capacity)
             if jpeg is not None:
-                streams = self._jpeg_results(d_out, total, fmt, table, jpeg) if d_out else [None] * len(frames)
-                return [(lines[b], tfs[b], streams[b]) for b in range(len(frames))]
+                streams = self._jpeg_results(d_out, total, fmt, table, jpeg) if d_out else [None] * len(sources)
+                return [(lines[b], tfs[b], streams[b]) for b in range(len(sources))]
             packed = self.device_download(d_out, (total,), np.uint8) if d_out else None
         finally:
             self.device_free(d_src)
             if d_out:
                 self.device_free(d_out)
         res = []
-        for b, f in enumerate(frames):
+        for b in range(len(sources)):
             ow, oh, off, row = (int(v) for v in table[b, 9:13])
             img = None
             if ow:
                 rows = np.lib.stride_tricks.as_strided(packed[off:], (oh, ow * bpp), (row, 1))
-                img = np.ascontiguousarray(rows).reshape((oh, ow) + f.shape[2:])
+                img = np.ascontiguousarray(rows).reshape((oh, ow) + ((3,) if bpp == 3 else ()))
             res.append((lines[b], tfs[b], img))
         return res
 
@@ -1109,7 +1277,13 @@ class Context:
         jpeg=Q (1 .. 100): the warped pictures stay in HBM and are encoded there (lr_encode_jpeg_device, quality Q, 4:2:0 for
         colour frames); `warped` is then the JPEG file as bytes -- exactly the encoder's stream of the picture that jpeg=None
         returns -- and only the streams' lengths and the streams cross the link.  A frame whose stream outgrows a first
-        extent of half its pixels' bytes is encoded again with room for jpeg_bound, so nothing is ever cut."""
+        extent of half its pixels' bytes is encoded again with room for jpeg_bound, so nothing is ever cut.
+        A list of JPEG files (bytes; all of them, else ValueError) in place of the frames: the files are uploaded and
+        decoded in HBM (lr_decode_jpeg_device; u8x3, or u8 if every file has one component) and handed to
+        rectify_frames_device where they lie -- bit for bit the call on decode_jpeg_batch's arrays (decode_jpeg_batch(files,
+        PIX_U8)'s for a list of one-component files); with jpeg=Q no pixel crosses the link in either direction."""
+        if _all_streams(frames_u8, "rectify_batch"):
+            return self._rectify_streams([bytes(f) for f in frames_u8], min_length, refine, cfg, clip, max_size, capacity, jpeg)
         if not isinstance(frames_u8, np.ndarray):
             frames_u8 = [np.asarray(f) for f in frames_u8]
             if len({f.shape for f in frames_u8}) > 1:

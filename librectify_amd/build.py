@@ -21,6 +21,7 @@ SOURCES = [
     "kernels_prepare.hip",
     "kernels_overlay.hip",
     "kernels_jpeg.hip",
+    "kernels_jpeg_decode.hip",
     "context.hip",
     "upload.hip",
     "frame.hip",

@@ -133,6 +133,17 @@ struct JpegStore {
     DeviceBuffer<uint32_t> len;
     DeviceBuffer<unsigned long long> place;
 };
+
+// lr_decode_jpeg_device (kernels_jpeg_decode.hip): a call's frame records (code tables and divisors in them), prefix tables
+// and flags going up and the frames' results coming back (block), the coefficients (2 bytes per sample of the padded
+// components; the transform leaves the samples in their place), and per 128-byte part of a scan its entry and exit states,
+// counts, number of decodes and first block; all sized by the call
+struct JpegDecodeStore {
+    MirroredBuffer<unsigned char> block;
+    DeviceBuffer<int16_t> coef;
+    DeviceBuffer<unsigned long long> state;  // entry | exit | carry (two of them)
+    DeviceBuffer<uint32_t> part;             // counts | tries | first block
+};
 }  // namespace lramd
 
 struct lr_context {
@@ -240,6 +251,8 @@ struct lr_context {
     double host_ms[3] = {0, 0, 0};  // last frame: enqueue, next-frame staging + upload, wait (LIBRECTIFY_LANE_DEBUG)
     bool stage_valid[4] = {false, false, false, false};
     bool dmask_consumed = false;  // the parallel flood clears the mask of labelled pixels: LR_BUF_DMASK is then stale
+    // (last: the members above keep the places they had before it came)
+    lramd::JpegDecodeStore jpeg_decode;
 };
 
 namespace lramd {
@@ -337,6 +350,11 @@ int ctx_draw_lines(lr_context* c, const void* d_src, size_t src_bytes, int forma
 // transform, the two entropy passes and the scan between them, and waits for the streams' lengths)
 int ctx_encode_jpeg(lr_context* c, const void* d_src, size_t src_bytes, int format, const double* frames, int batch, void* d_dst,
                     size_t dst_bytes, uint64_t* sizes);
+// kernels_jpeg_decode.hip: lr_decode_jpeg_device (validates the whole table, reads the headers on the host, enqueues the
+// entropy decoder's rounds, the placement, the coefficient pass, the DC scan, the inverse transform and the output pass, and
+// waits for the statuses); d_dst == NULL: the headers only, and then c may be NULL
+int ctx_decode_jpeg(lr_context* c, const void* d_src, const void* h_src, size_t src_bytes, int format, const double* frames,
+                    int batch, void* d_dst, size_t dst_bytes, int32_t* info);
 // bytes one frame spans: (rows - 1) * row_bytes + last_row_bytes; false if that does not fit in 64 bits
 inline bool frame_span(int rows, size_t row_bytes, size_t last_row_bytes, size_t* out) {
     size_t s;

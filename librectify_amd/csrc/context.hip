@@ -65,6 +65,7 @@ int ctx_trim(lr_context* c, bool frames_too) {
         c->warp_m = MirroredBuffer<double>{};  // (sized by the largest batch warped)
         c->overlay = OverlayStore{};           // (sized by the most segments drawn in a call)
         c->jpeg = JpegStore{};                 // (coefficients and interval tables of the largest batch encoded)
+        c->jpeg_decode = JpegDecodeStore{};    // (coefficients and part records of the largest batch decoded)
     }
     c->small_frames = 0;
     c->w = c->h = 0;

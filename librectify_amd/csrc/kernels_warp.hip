@@ -29,6 +29,7 @@
 //     with records that say so.
 //
 // LR_WARP_JPEG is no warp: lr_encode_jpeg_device's call goes on to kernels_jpeg.hip.
+// LR_WARP_JPEG_DECODE neither: lr_decode_jpeg_device's call goes on to kernels_jpeg_decode.hip.
 // LR_WARP_LINES is none either: the entry hands lr_draw_lines_device's call on to kernels_overlay.hip (the export table is full).
 #include <algorithm>
 #include <cmath>
@@ -449,6 +450,15 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
         set_error(std::string("lr_warp_perspective_device: ") + what);
         return 1;
     };
+    if (format & LR_WARP_JPEG_DECODE) {  // lr_decode_jpeg_device (kernels_jpeg_decode.hip): its own arguments arrive behind M
+        if ((format & ~0xFF) != LR_WARP_JPEG_DECODE) return fail("LR_WARP_JPEG_DECODE together with another option bit");
+        if (width != 0 || height != 0 || src_row_bytes != 0 || out_width != 0 || out_height != 0 || dst_row_bytes != 0)
+            return fail("LR_WARP_JPEG_DECODE: width, height, out_width, out_height and the row strides must be 0 (they are in the frame table)");
+        if (!M) return fail("LR_WARP_JPEG_DECODE: null pointer (lr_jpeg_decode_args)");
+        const lr_jpeg_decode_args* a = reinterpret_cast<const lr_jpeg_decode_args*>(M);
+        // (probe mode, d_dst == NULL, needs no context)
+        return ctx_decode_jpeg(c, d_src, a->h_src, src_image_bytes, format & 0xFF, a->frames, batch, d_dst, dst_image_bytes, a->info);
+    }
     if (!c) return fail("no context");
     if (format & LR_WARP_JPEG) {  // lr_encode_jpeg_device (kernels_jpeg.hip): its own arguments arrive behind M
         if ((format & ~0xFF) != LR_WARP_JPEG) return fail("LR_WARP_JPEG together with another option bit");
