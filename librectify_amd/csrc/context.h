@@ -95,7 +95,7 @@ struct FrameSlots {
 
 // Batch calls on host frames: a ring of device frames (and, for pageable frames, of page-locked staging buffers)
 // that ONE uploader fills in frame order on the copy stream, as far ahead of the lanes as the ring allows
-// (find_groups_batch).
+// (upload.hip: BatchUploader).
 struct UploadRing {
     std::vector<DeviceBuffer<float>> img;
     std::vector<PinnedBuffer<float>> stage;
@@ -174,7 +174,7 @@ struct lr_context {
     bool sleep_in_wait = false;
     uint32_t fit_tag = 0;              // tag of the last component scan (kernels_fit.hip: component_offsets_kernel)
     bool batch_no_register = false;    // a multi-device call whose blocks overlap: its frames are staged, none is page-locked in place
-    int register_slow_calls = 0;       // batch calls still to go with the staging copy after pinning frames in place turned out slow (batch.hip: find_groups_batch)
+    int register_slow_calls = 0;       // batch calls still to go with the staging copy after pinning frames in place turned out slow (upload.hip: BatchUploader)
     uint32_t select_tag = 0;           // tag of the last seed selection on this context (kernels_seeds.hip: seed_select_kernel)
     lramd::DeviceBuffer<float> maxmag;
     lramd::DeviceBuffer<uint32_t> d_counts;  // [0] n_seeds, [1] n_comp, [2] n_px, [3..] flood scratch
@@ -235,7 +235,7 @@ struct lr_context {
     int flood_rounds = 0;
     int flood_rounds_hint = 10;  // rounds the next flood enqueues blindly
     int flood_rounds_last = 0;   // rounds the last flood needed (0: none yet)
-    // what find_groups_batch gives its lanes for the length of a call (0 / false otherwise)
+    // what a batch call gives its lanes for the length of the call (batch.hip: LaneSet; 0 / false otherwise)
     int flood_jit_sleep_us = 0;  // (when they enqueue just in time at all: pause between looks)
     bool flood_logbig_off = false;  // no logs of second-tier walks
     int flood_log_min = 0, flood_log_walk = 0;  // thresholds of the logs (0: the defaults; the lanes get 32 and 24)

@@ -1,20 +1,34 @@
-// Internals shared by the host units: context.hip (workspace), upload.hip (host frames -> device), frame.hip (one frame),
-// estimators.hip (vanishing points), batch.hip (many frames, many devices).
+// Internals shared by the host units: context.hip (workspace), upload.hip (host frames -> device: single frames and the
+// uploader of batch calls, its page-registration plan from reg_plan.h), frame.hip (one frame), estimators.hip (vanishing
+// points), batch.hip (the lanes of a call: many frames, many devices).
 #pragma once
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
 #include <mutex>
+#include <string>
 #include <thread>
 #include <vector>
 
 #include "context.h"
+#include "reg_plan.h"
 
 namespace lramd {
 
 inline double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
+
+// Threads that are joined on every way out of their scope (an exception included: a std::thread destroyed while joinable
+// ends the process).
+struct JoinedThreads {
+    std::vector<std::thread> th;
+    void join() {
+        for (auto& t : th)
+            if (t.joinable()) t.join();
+    }
+    ~JoinedThreads() { join(); }
+};
 
 // d_counts words
 enum { kCntSeeds = 0, kCntComp = 1, kCntPx = 2, kCntLarge = 4 };
@@ -101,6 +115,73 @@ struct StagingCrew {
                    const Event* band_ev_, std::atomic<int>* ready_, size_t band_bytes = (size_t)4 << 20, int pieces_ = 0);
     int finish();
     ~StagingCrew();
+};
+
+// Host frames of a batch call on their way to device frames (the lanes of the call never touch host memory).  The frames
+// are uploaded by ONE uploader thread, in frame order, on the caller's copy stream, into a pool of lanes + 6 device frames:
+// frame i goes to whichever slot is free (frames finish out of order: a heavy frame runs as long as three light ones, and
+// slot i mod R would make the link wait for it), so the link works up to six frames ahead of the lanes instead of
+// starting a lane's next transfer only when the lane starts a frame.  (With one slot ahead per lane -- the first design --
+// a quarter to a third of the frames of a 4K batch still waited for their own upload, although the link was busy only two
+// thirds of the time: 7.5 Gpix/s where the same batch without the transfers ran at 9.0; LIBRECTIFY_LANE_DEBUG prints each
+// frame's lead.)  A lane makes its stream wait for the frame's transfer and never touches host memory itself.
+// Frames are of one pixel format (`bpp` bytes a pixel; the stride in pixels of it) and travel as bytes.
+// check() refuses what is wrong with the arguments (it needs no lane and touches nothing); start() sizes the ring and
+// starts the threads; a lane asks for frame b with ready() and gives its slot back with release();
+// end() -- or the destructor, where end() was not reached -- joins the threads, waits for the link and gives the caller's
+// pages back.
+class BatchUploader {
+public:
+    BatchUploader(lr_context* ctx, const void* const* frames, int batch, int w, int h, int stride, int bpp, int lanes, int num_threads);
+    ~BatchUploader();
+    BatchUploader(const BatchUploader&) = delete;
+    BatchUploader& operator=(const BatchUploader&) = delete;
+    int check() const;
+    int start();
+    // Frame b on the lane's stream: waits until its transfer is enqueued, makes `lane_stream` wait for it and fetch the rows
+    // that were staged.  0 with *img the device frame (packed rows) and *slot its slot; 0 with *img == nullptr if the call
+    // has been stopped (whoever stopped it has the message); 1 if this failed (the message is set).
+    int ready(int b, hipStream_t lane_stream, const void** img, int* slot);
+    // The frame of `slot` is done (its device frame and its staging buffer are free): frame b, by `lane` (number
+    // lane_index), whose call began at t_frame0 -- for LIBRECTIFY_BATCH_STATS and LIBRECTIFY_LANE_DEBUG.
+    void release(int slot, int b, const lr_context* lane, int lane_index, double t_frame0);
+    const std::string& end();  // the uploader's message; empty if it did not fail
+    std::atomic<int> stop{0};  // set by whoever fails, a lane or the uploader: everybody ends
+
+private:
+    void close();
+    void register_frames();
+    void upload_frames();
+    int send_frame(StagingCrew& crew, int i, int slot);
+
+    lr_context* c;
+    const uint8_t* const* frames;
+    const int batch, w, h, stride;
+    const size_t bpp, row_bytes, pitch;
+    const int lanes, num_threads;
+    int R = 0;
+    bool any_pageable = false, reg_frames = false, started = false, closed = false;
+    std::vector<char> locked;  // frames in memory the CALLER has page-locked
+    std::vector<RegPlan> plan;
+    std::vector<std::atomic<int>> enq;  // frame's slot + 1 once its transfer is enqueued
+    std::vector<std::atomic<int>> slot_busy;
+    struct SlotEdges {
+        int r_lo = 0, r_hi = 0;  // rows [0, r_lo) and [r_hi, h) of the slot's frame wait in its staging buffer (r_hi = 0: none)
+    };
+    std::vector<SlotEdges> slot_edges;  // (written by the uploader before enq[], read by the frame's lane after it)
+    // reg_ready[i]: 0 nobody has touched the frame, 3 a helper is registering it, 1 registered, 2 the staging copy takes it
+    // (page-locked already, registration refused, or the uploader got there first).  The helpers take the frames in order; a
+    // frame the uploader reaches before any helper has is staged.  (Helpers that begin at the fourth frame, the uploader staging
+    // the call's first three rather than waiting 1.3 ms for the first registration: 11.30 against 11.41 Gpix/s -- the staging
+    // copies cost the helpers more than the wait costs the call.)
+    std::vector<std::atomic<int>> reg_ready;
+    std::atomic<int> reg_next{0}, reg_slow{0};
+    std::string up_err;
+    // LIBRECTIFY_BATCH_STATS: who waited for whom in this call (host clocks only, nothing is synchronised for it)
+    std::atomic<long long> up_wait_us{0}, lane_wait_us{0}, lead_sum_us{0};
+    std::atomic<int> late_frames{0};
+    double t_call0 = 0.0;
+    JoinedThreads helpers, uploader;
 };
 
 }  // namespace lramd

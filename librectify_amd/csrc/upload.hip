@@ -394,4 +394,271 @@ int ensure_upload_ring(lr_context* c, int R, size_t npix, bool staging) {
     return 0;
 }
 
+static bool batch_stats_on() {
+    static const bool on = std::getenv("LIBRECTIFY_BATCH_STATS") != nullptr;
+    return on;
+}
+static bool lane_debug_on() {
+    static const bool on = std::getenv("LIBRECTIFY_LANE_DEBUG") != nullptr;
+    return on;
+}
+static void nap(int& spins) {  // a wait that is usually short: yield first, then sleep
+    if (++spins < 64) std::this_thread::yield();
+    else std::this_thread::sleep_for(std::chrono::microseconds(30));
+}
+
+BatchUploader::BatchUploader(lr_context* ctx, const void* const* frames_, int batch_, int w_, int h_, int stride_, int bpp_, int lanes_,
+                             int num_threads_)
+    : c(ctx), frames(reinterpret_cast<const uint8_t* const*>(frames_)), batch(batch_), w(w_), h(h_), stride(stride_), bpp((size_t)bpp_),
+      row_bytes((size_t)w_ * (size_t)bpp_), pitch((size_t)(stride_ < 0 ? -stride_ : stride_) * (size_t)bpp_), lanes(lanes_),
+      num_threads(num_threads_) {}
+
+int BatchUploader::check() const {
+    if (w < 1 || h < 1) {
+        set_error("upload: bad frame");
+        return 1;
+    }
+    if ((stride < 0 ? -stride : stride) < w) {
+        set_error("upload: |stride| smaller than the width");
+        return 1;
+    }
+    for (int i = 0; i < batch; ++i) {
+        if (frames[i] == nullptr) {
+            set_error("upload: bad frame");
+            return 1;
+        }
+    }
+    return 0;
+}
+
+int BatchUploader::start() {
+    // (asked once, before this call page-locks anything: a frame that overlaps one the call has registered is still
+    // the caller's pageable memory)
+    locked.assign((size_t)batch, 0);
+    for (int i = 0; i < batch; ++i) {
+        locked[(size_t)i] = is_page_locked(frames[i]);
+        any_pageable = any_pageable || !locked[(size_t)i];
+    }
+    // slots beyond one per lane: what the link may be ahead.  Six absorb the moments when several lanes finish
+    // together (pageable 4K frames: 7.8 Gpix/s with three, 8.0 with six or ten); at most 2 GiB of frames, though.
+    static const int extra_env = std::getenv("LIBRECTIFY_RING_EXTRA") ? std::max(1, std::atoi(std::getenv("LIBRECTIFY_RING_EXTRA"))) : 0;
+    const size_t npix = (size_t)w * h;
+    const int by_bytes = (int)std::min<size_t>(64, ((size_t)2 << 30) / (npix * bpp));
+    R = extra_env ? lanes + extra_env : std::max(lanes + 1, std::min(lanes + 6, by_bytes));
+    R = std::min(batch, R);
+    if (ensure_upload_ring(c, R, npix, any_pageable)) return 1;
+    enq = std::vector<std::atomic<int>>((size_t)batch);
+    slot_busy = std::vector<std::atomic<int>>((size_t)R);
+    slot_edges.assign((size_t)R, SlotEdges());
+    for (auto& a : enq) a.store(0, std::memory_order_relaxed);
+    for (auto& a : slot_busy) a.store(0, std::memory_order_relaxed);
+    // Pageable caller frames are page-locked WHERE THEY LIE (hipHostRegister) by a few helper threads running ahead of the
+    // uploader, sent by DMA from there, and released when the call is over -- no staging copy, i.e. one pass through host DRAM
+    // instead of three.
+    // No page is ever registered twice: a frame's range is rounded INWARDS to whole pages, and the rows that reach into the
+    // pages it shares with its neighbours -- at most 4 KB and a row at each end -- go through the slot's staging buffer
+    // instead (reg_plan.h: RegPlan, with the reasons): the uploader copies them there and sends the rows in between in ONE
+    // transfer, as ever; the frame's LANE fetches the few staged rows on its own stream before its filter, so the link's
+    // queue carries one command a frame (three -- head, middle, tail on the copy stream -- cost the fp32 headline 3 %).
+    // What registration costs instead of the copy is the pinning itself (page-table work, ~1.3 ms a 4K frame on one thread).
+    // Round 5: 10.93 -> 11.38 Gpix/s on the headline leg with four helpers, the 1080p batch unchanged;
+    // the default since.  A frame whose registration is refused (memory somebody else has registered, a mapping that cannot be
+    // pinned) goes through the staging copy as before; LIBRECTIFY_REGISTER_FRAMES=0 sends every frame that way,
+    // =<n> sets the helpers (profiles/r05_h2d_register.txt).
+    static const int register_threads = std::getenv("LIBRECTIFY_REGISTER_FRAMES") ? std::max(0, std::atoi(std::getenv("LIBRECTIFY_REGISTER_FRAMES"))) : 4;
+    // (a host on which pinning is slow -- measured on this box: 1.3 ms a 4K frame on one thread, 25 GB/s; the guard trips below
+    // 6 GB/s -- gets the staging copy back: for the rest of the call, and for the context's next 32 batch calls before it tries again)
+    if (c->register_slow_calls > 0) --c->register_slow_calls;
+    reg_frames = register_threads > 0 && any_pageable && stride >= w && c->register_slow_calls == 0;
+    if (reg_frames) {
+        std::vector<char> may((size_t)batch);
+        for (int i = 0; i < batch; ++i) may[(size_t)i] = !locked[(size_t)i] && !c->batch_no_register;
+        plan = plan_registrations(reinterpret_cast<const void* const*>(frames), batch, h, pitch, row_bytes, 4096, may.data());
+        reg_ready = std::vector<std::atomic<int>>((size_t)batch);
+        for (auto& a : reg_ready) a.store(0, std::memory_order_relaxed);
+    }
+    started = true;
+    if (reg_frames)
+        for (int t = 0; t < register_threads; ++t) helpers.th.emplace_back([this]() { register_frames(); });
+    t_call0 = now_ms();
+    uploader.th.emplace_back([this]() { upload_frames(); });
+    return 0;
+}
+
+// a registration helper: the frames in order, each by whoever gets there first
+void BatchUploader::register_frames() {
+    (void)hipSetDevice(c->device);
+    bind_this_thread_near(c->device);
+    for (int i = reg_next.fetch_add(1, std::memory_order_relaxed); i < batch && !stop.load(std::memory_order_relaxed);
+         i = reg_next.fetch_add(1, std::memory_order_relaxed)) {
+        if (reg_slow.load(std::memory_order_relaxed) >= 2) break;  // (pinning is slow here: the uploader stages the rest)
+        int expect = 0;
+        if (!reg_ready[(size_t)i].compare_exchange_strong(expect, 3, std::memory_order_acq_rel)) continue;  // (the uploader has it)
+        int ok = 2;
+        const double t_r0 = now_ms();
+        // (only the frames with a plan: whole pages of their own, apart from every earlier frame's)
+        const RegPlan& p = plan[(size_t)i];
+        if (p.hi > p.lo)
+            ok = hipHostRegister(reinterpret_cast<void*>(p.lo), p.hi - p.lo, hipHostRegisterDefault) == hipSuccess ? 1 : 2;
+        if (ok == 2) (void)hipGetLastError();
+        if (ok == 1 && (now_ms() - t_r0) * 6.0e6 > (double)(p.hi - p.lo)) reg_slow.fetch_add(1, std::memory_order_relaxed);
+        reg_ready[(size_t)i].store(ok, std::memory_order_release);
+    }
+}
+
+// the uploader thread: every frame, in order, into a free slot
+void BatchUploader::upload_frames() {
+    if (hipSetDevice(c->device) != hipSuccess) {
+        up_err = "hipSetDevice failed";
+        stop.store(1);
+        return;
+    }
+    if (any_pageable) bind_this_thread_near(c->device);  // (this thread stages too; it is the library's own)
+    StagingCrew crew;
+    if (any_pageable) crew.start(c, staging_threads(num_threads, (size_t)w * h * bpp) - 1);
+    for (int i = 0; i < batch; ++i) {
+        int slot = -1, spins = 0;
+        const double t_w0 = batch_stats_on() ? now_ms() : 0.0;
+        // a slot whose frame is done (its transfer and its staging buffer are then free as well)
+        while (slot < 0 && !stop.load(std::memory_order_relaxed)) {
+            for (int k = 0; k < R && slot < 0; ++k)
+                if (!slot_busy[(size_t)k].load(std::memory_order_acquire)) slot = k;
+            if (slot < 0) nap(spins);
+        }
+        if (batch_stats_on()) up_wait_us.fetch_add((long long)((now_ms() - t_w0) * 1e3));
+        if (stop.load(std::memory_order_relaxed)) return;
+        slot_busy[(size_t)slot].store(1, std::memory_order_relaxed);
+        if (reg_frames) {  // (the frame is being pinned by a helper: wait for it)
+            int sp2 = 0;
+            int expect = 0;
+            if (!reg_ready[(size_t)i].compare_exchange_strong(expect, 2, std::memory_order_acq_rel))  // (else: nobody has it -- staged)
+                while (reg_ready[(size_t)i].load(std::memory_order_acquire) == 3 && !stop.load(std::memory_order_relaxed)) nap(sp2);
+        }
+        const double t_u0 = now_ms();
+        Event e_dbg;
+        if (lane_debug_on() && e_dbg.create() == hipSuccess) (void)hipEventRecord(e_dbg, c->copy_stream);
+        if (send_frame(crew, i, slot) || hipEventRecord(c->ring_ev[(size_t)slot], c->copy_stream) != hipSuccess) {
+            up_err = get_error().empty() ? "upload failed" : get_error();
+            stop.store(1);
+            return;
+        }
+        enq[(size_t)i].store(slot + 1, std::memory_order_release);
+        if (lane_debug_on()) {
+            const double t_u1 = now_ms();
+            float dma = 0.f;  // from the moment the link was free for this frame to the end of its last transfer
+            if (e_dbg) {
+                (void)hipEventSynchronize(c->ring_ev[(size_t)slot]);
+                if (hipEventElapsedTime(&dma, e_dbg, c->ring_ev[(size_t)slot]) != hipSuccess) (void)hipGetLastError();
+            }
+            std::fprintf(stderr, "uploader frame %d: slot %d, waited %d naps for it, staged and enqueued in %.2f ms, on the link %.2f ms\n", i, slot, spins, t_u1 - t_u0, dma);
+        }
+    }
+}
+
+// frame i's transfer into `slot` on the copy stream: from where it lies if it is registered (its first and last rows into the
+// slot's staging buffer, for the lane), else as it is (page-locked by the caller) or through the staging buffer
+int BatchUploader::send_frame(StagingCrew& crew, int i, int slot) {
+    constexpr size_t kBatchBand = (size_t)4 << 20;  // staging bands of the batch's pageable frames
+    const bool registered = reg_frames && reg_ready[(size_t)i].load(std::memory_order_acquire) == 1;
+    uint8_t* stage = locked[(size_t)i] ? nullptr : reinterpret_cast<uint8_t*>(c->ring.stage[(size_t)slot].get());
+    uint8_t* dimg = reinterpret_cast<uint8_t*>(c->ring.img[(size_t)slot].get());
+    if (!registered) {
+        slot_edges[(size_t)slot].r_hi = 0;
+        return stage ? crew.run(dimg, stage, frames[i], w, h, stride, (int)bpp, c->copy_stream, kBatchBand, 1)
+                     : upload_rows(c, dimg, nullptr, frames[i], w, h, stride, (int)bpp, 1, c->copy_stream);
+    }
+    const RegPlan& p = plan[(size_t)i];
+    const uint8_t* f = frames[i];
+    // the rows that reach into a page shared with a neighbour: staged here, fetched by the lane
+    for (int r = 0; r < p.r_lo; ++r) std::memcpy(stage + (size_t)r * row_bytes, f + (size_t)r * pitch, row_bytes);
+    for (int r = p.r_hi; r < h; ++r) std::memcpy(stage + (size_t)r * row_bytes, f + (size_t)r * pitch, row_bytes);
+    slot_edges[(size_t)slot].r_lo = p.r_lo;
+    slot_edges[(size_t)slot].r_hi = p.r_hi;
+    const hipError_t e = pitch == row_bytes
+        ? hipMemcpyAsync(dimg + (size_t)p.r_lo * row_bytes, f + (size_t)p.r_lo * pitch, (size_t)(p.r_hi - p.r_lo) * row_bytes, hipMemcpyHostToDevice, c->copy_stream)
+        : hipMemcpy2DAsync(dimg + (size_t)p.r_lo * row_bytes, row_bytes, f + (size_t)p.r_lo * pitch, pitch, row_bytes, (size_t)(p.r_hi - p.r_lo), hipMemcpyHostToDevice, c->copy_stream);
+    if (e == hipSuccess) return 0;
+    (void)hipGetLastError();
+    set_error("upload: transfer of a registered frame failed");
+    return 1;
+}
+
+int BatchUploader::ready(int b, hipStream_t lane_stream, const void** img, int* slot_out) {
+    *img = nullptr;
+    int slot = -1, spins = 0;
+    const double t_w0 = batch_stats_on() ? now_ms() : 0.0;
+    while ((slot = enq[(size_t)b].load(std::memory_order_acquire) - 1) < 0 && !stop.load(std::memory_order_relaxed)) nap(spins);
+    if (batch_stats_on()) lane_wait_us.fetch_add((long long)((now_ms() - t_w0) * 1e3));
+    if (slot < 0) return 0;  // (whoever stopped the batch has the message)
+    if (hipStreamWaitEvent(lane_stream, c->ring_ev[(size_t)slot], 0) != hipSuccess) {
+        set_error("hipStreamWaitEvent failed");
+        return 1;
+    }
+    uint8_t* dimg = reinterpret_cast<uint8_t*>(c->ring.img[(size_t)slot].get());
+    const SlotEdges ed = slot_edges[(size_t)slot];
+    if (ed.r_hi > 0) {  // (page-locked staging memory: two small transfers on the lane's own stream)
+        const uint8_t* st = reinterpret_cast<const uint8_t*>(c->ring.stage[(size_t)slot].get());
+        hipError_t e = hipSuccess;
+        if (ed.r_lo > 0) e = hipMemcpyAsync(dimg, st, (size_t)ed.r_lo * row_bytes, hipMemcpyHostToDevice, lane_stream);
+        if (e == hipSuccess && ed.r_hi < h)
+            e = hipMemcpyAsync(dimg + (size_t)ed.r_hi * row_bytes, st + (size_t)ed.r_hi * row_bytes, (size_t)(h - ed.r_hi) * row_bytes, hipMemcpyHostToDevice, lane_stream);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("upload: transfer of a registered frame's first or last rows failed");
+            return 1;
+        }
+    }
+    *img = dimg;
+    *slot_out = slot;
+    return 0;
+}
+
+void BatchUploader::release(int slot, int b, const lr_context* l, int lane_index, double t_frame0) {
+    if (batch_stats_on() && l->opt.timing_on) {  // (with the stage timers on: ev[0] is the frame's first kernel)
+        float lead = 0.f;
+        if (hipEventElapsedTime(&lead, c->ring_ev[(size_t)slot], l->ev[0]) == hipSuccess) {
+            lead_sum_us.fetch_add((long long)(lead * 1e3));
+            if (lead < 0.05f) late_frames.fetch_add(1);
+        } else {
+            (void)hipGetLastError();
+        }
+    }
+    if (lane_debug_on()) {
+        float lead = 0.f;  // how long the frame's upload had been finished when its first kernel started
+        if (hipEventElapsedTime(&lead, c->ring_ev[(size_t)slot], l->ev[0]) != hipSuccess) (void)hipGetLastError();
+        std::fprintf(stderr, "lane %d frame %d: enqueue %.2f ms, wait %.2f, whole call %.2f; device total %.2f; upload done %.2f ms before the first kernel\n",
+                     lane_index, b, l->host_ms[0], l->host_ms[2], now_ms() - t_frame0, l->stage_ms[LR_T_TOTAL], lead);
+    }
+    slot_busy[(size_t)slot].store(0, std::memory_order_release);
+}
+
+void BatchUploader::close() {
+    if (closed || !started) return;
+    closed = true;
+    uploader.join();
+    if (batch_stats_on())
+        std::fprintf(stderr, "batch of %d frames: %.2f ms; the uploader waited %.2f ms for free device frames; the %d lanes waited %.2f ms in all for their frame's transfer to be enqueued\n",
+                     batch, now_ms() - t_call0, up_wait_us.load() * 1e-3, lanes, lane_wait_us.load() * 1e-3);
+    if (batch_stats_on() && c->opt.timing_on)
+        std::fprintf(stderr, "   a frame's transfer was finished %.3f ms (mean) before its first kernel started; %d of %d frames started within 0.05 ms of it (they waited for the link)\n",
+                     lead_sum_us.load() * 1e-3 / batch, late_frames.load(), batch);
+    (void)hipStreamSynchronize(c->copy_stream);  // (after an error: nothing may still read the caller's frames)
+    helpers.join();
+    if (reg_slow.load() >= 2) c->register_slow_calls = 32;
+    if (reg_frames)  // the caller's frames go back to being pageable
+        for (int i = 0; i < batch; ++i)
+            if (reg_ready[(size_t)i].load(std::memory_order_acquire) == 1 && hipHostUnregister(reinterpret_cast<void*>(plan[(size_t)i].lo)) != hipSuccess)
+                (void)hipGetLastError();  // (nothing to be done about it, and the caller's thread must not find it in its next call)
+}
+
+const std::string& BatchUploader::end() {
+    close();
+    return up_err;
+}
+
+BatchUploader::~BatchUploader() {
+    stop.store(1);  // (no-one is left to take the frames if end() was not reached)
+    close();
+}
+
 }  // namespace lramd

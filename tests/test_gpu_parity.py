@@ -905,6 +905,53 @@ def test_host_batch_entry_point_pageable_pinned_and_strided(L, ctx):
     check(*ctx.find_line_segment_groups_batch_host(frames, 3.3, capacity=1024))
 
 
+def test_refused_host_batch_calls_leave_the_context_with_its_own_flood_settings(L):
+    """A batch call gives its lanes -- the caller's context is lane 0 -- thresholds of their own for the re-walks from logs
+    (32 / 24 tiles, a single call's are 16 / 12).  A call that is refused gives them back like any other: after a NULL frame
+    pointer and after a stride below the width, a single call on the same context returns a fresh context's records AND
+    works out as many footprints from logs (stage_counters: log_rewalks, log_give_ups).  640x360 with 30 bars is the smallest
+    synth.frame tried (after 333x190 with 18 bars: none with either pair) whose count differs between the two pairs of
+    thresholds: seed 72 has 30 re-walks with a single call's thresholds and none with a lane's."""
+    import ctypes as C
+
+    from librectify_amd import synth
+
+    w, h, bars = 640, 360, 30
+    frames = np.stack([synth.frame(w, h, 70 + i, bars=bars) for i in range(3)])
+    ml = w / 100.0
+    fresh = L.Context(0)
+    fresh.set_seed(0)
+    ref = fresh.find_line_segment_groups(frames[2], ml)
+    want = fresh.stage_counters()
+    fresh.close()
+    assert len(ref) > 10
+    out = np.zeros((3, 1024), L.LINE_DTYPE)
+    n = np.zeros(3, np.int32)
+    outs = (out.ctypes.data_as(C.c_void_p), 1024, n.ctypes.data_as(C.c_void_p), None, None)
+
+    def null_frame(c):
+        ptrs = (C.c_void_p * 3)(frames[0].ctypes.data, None, frames[2].ctypes.data)
+        return L.lib().lr_find_line_segment_groups_batch_host_ptrs(c._h, ptrs, 3, w, h, w, ml, 0, -1, *outs)
+
+    def short_stride(c):
+        return L.lib().lr_find_line_segment_groups_batch_host(c._h, C.c_void_p(frames.ctypes.data), h * w, 3, w, h, w - 1, ml, 0, -1, *outs)
+
+    for refused, message in ((null_frame, "upload: bad frame"), (short_stride, "upload: |stride| smaller than the width")):
+        c = L.Context(0)
+        try:
+            c.set_seed(0)
+            c.set_batch_streams(3)
+            assert refused(c) == 1
+            assert L.lib().lr_last_error().decode() == message
+            got = c.find_line_segment_groups(frames[2], ml)
+            used = c.stage_counters()
+        finally:
+            c.close()
+        print(message, "-> log_rewalks %d (fresh %d), log_give_ups %d (fresh %d)" % (used["log_rewalks"], want["log_rewalks"], used["log_give_ups"], want["log_give_ups"]))
+        _assert_lines_equal(got, ref)
+        assert (used["log_rewalks"], used["log_give_ups"]) == (want["log_rewalks"], want["log_give_ups"]), message
+
+
 def test_batch_lanes_with_refine_and_with_prosac_and_concurrent_callers(L, ctx):
     """The paths that leave the one-wait pipeline after the line fit (refine = true; the opt-in PROSAC estimator) inside
     batch lanes with prefetching uploads, and the reference's re-entrancy: four host threads calling the drop-in
