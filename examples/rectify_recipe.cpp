@@ -6,7 +6,7 @@
 //
 //   rectify_recipe in.pgm|in.ppm out_prefix [--max-size N|fraction] [--refine] [--threads N]
 //                  [--h-strategy rotate_h|rotate_v|rectify|keep] [--v-strategy ...] [--warp] [--device-prepare] [--lines]
-//                  [--jpeg Q] [--jpeg-in]
+//                  [--jpeg Q] [--jpeg-in] [--orient]
 //
 // Input is a binary PGM (P5, 8 bit) or PPM (P6, 8 bit; converted with the usual integer luma weights
 // (4899 R + 9617 G + 1868 B + 8192) >> 14).  Image decoding stays with the caller's imaging library.
@@ -26,7 +26,10 @@
 // file goes up as it is and lr_decode_jpeg_device decodes it in HBM (RGB, or gray for a one-component file).  The example
 // then downloads the picture and goes on exactly as --device-prepare does with a PPM it has read, so here the pixels do
 // cross the link (once down, once up): a caller who wants them to stay in HBM passes the decoder's output on, as
-// Context.rectify_batch does with a list of files.  EXIF orientation is not applied.
+// Context.rectify_batch does with a list of files.
+// --orient (with --jpeg-in alone): the file's EXIF orientation is applied as the demo's imread applies it -- entry [7] of the
+// frame's row is 1 for lr_jpeg_info, which then tells the upright size, and for lr_decode_jpeg_device, whose output pass
+// writes the upright picture; that one goes on to prepare, detect and warp.  Without it the picture is the stored one.
 // Links against librectify_amd.so exactly like a program written for the reference.
 #include <algorithm>
 #include <cctype>
@@ -98,14 +101,14 @@ bool load_pnm(const std::string& path, Gray& g) {
 }
 
 // --jpeg-in: the file decoded on the GPU into g.raw (and g.px, for --lines).  Returns false with the reason on stderr.
-bool load_jpeg(const std::string& path, Gray& g) {
+bool load_jpeg(const std::string& path, bool orient, Gray& g) {
     std::ifstream f(path, std::ios::binary);
     std::vector<uint8_t> file((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
     if (!f || file.empty()) {
         std::fprintf(stderr, "cannot read %s\n", path.c_str());
         return false;
     }
-    double frame[8] = {0, (double)file.size(), 0, 0, 0, 0, 0, 0};
+    double frame[8] = {0, (double)file.size(), 0, 0, 0, 0, 0, orient ? 1.0 : 0.0};
     int32_t info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (lr_jpeg_info(file.data(), file.size(), frame, 1, info) != 0 || info[5] != 0) {
         std::fprintf(stderr, "jpeg input failed: %s\n", lr_last_error());
@@ -353,12 +356,12 @@ int main(int argc, char** argv) {
         std::fprintf(stderr,
                      "usage: %s in.pgm|in.ppm out_prefix [--max-size N|fraction] [--refine] [--threads N]\n"
                      "          [--h-strategy rotate_h|rotate_v|rectify|keep] [--v-strategy ...] [--warp] [--device-prepare]\n"
-                     "          [--lines] [--jpeg Q] [--jpeg-in]\n",
+                     "          [--lines] [--jpeg Q] [--jpeg-in] [--orient]\n",
                      argv[0]);
         return 2;
     }
     float max_size = 1200.f;  // the demo's default
-    bool refine = false, warp = false, device_prepare = false, lines_pictures = false, jpeg_in = false;
+    bool refine = false, warp = false, device_prepare = false, lines_pictures = false, jpeg_in = false, orient = false;
     int threads = -1, jpeg = 0;
     RectificationConfig cfg;
     cfg.horizontal_vp_min_distance = 2;  // autorectify.cpp:347
@@ -370,6 +373,7 @@ int main(int argc, char** argv) {
         else if (a == "--device-prepare") device_prepare = true;
         else if (a == "--lines") lines_pictures = true;
         else if (a == "--jpeg-in") jpeg_in = device_prepare = true;
+        else if (a == "--orient") orient = true;
         else if (a == "--max-size" && has_val) max_size = (float)std::atof(argv[++i]);
         else if (a == "--threads" && has_val) threads = std::atoi(argv[++i]);
         else if (a == "--jpeg" && has_val && std::atoi(argv[i + 1]) >= 1 && std::atoi(argv[i + 1]) <= 100) {
@@ -383,9 +387,13 @@ int main(int argc, char** argv) {
             return 2;
         }
     }
+    if (orient && !jpeg_in) {
+        std::fprintf(stderr, "--orient goes with --jpeg-in: a PGM or PPM file carries no EXIF orientation\n");
+        return 2;
+    }
     Gray full;
     if (jpeg_in) {
-        if (!load_jpeg(argv[1], full)) return 1;
+        if (!load_jpeg(argv[1], orient, full)) return 1;
     } else if (!load_pnm(argv[1], full)) {
         std::fprintf(stderr, "cannot read %s (binary PGM/PPM, 8 bit, expected)\n", argv[1]);
         return 1;

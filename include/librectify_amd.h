@@ -387,7 +387,7 @@ static inline size_t lr_jpeg_bound(int width, int height, int format, int layout
  * encoder's, because the host needs the statuses.
  * `frames` is a HOST table of 8 doubles per frame: [0] [1] byte offset and length of the stream in the source region (a
  * length below 2^31), [2] [3] byte offset of the picture from d_dst and its row stride in bytes, [4] [5] the width and
- * height the caller allocated for, [6] [7] reserved, 0.  `h_src` is a HOST copy of the source region (same layout as d_src):
+ * height the caller allocated for, [6] reserved, 0, [7] 1 to apply the file's EXIF orientation (below), else 0.  `h_src` is a HOST copy of the source region (same layout as d_src):
  * the host reads the headers up to SOS from it and nothing behind them.  `format` is the OUTPUT's format: LR_PIX_U8 gives the
  * luminance plane (of a colour stream Y alone: its chrominance is entropy-decoded but never transformed), LR_PIX_U8X3 gives
  * RGB with c0 red (a one-component stream replicated).  The table follows LR_WARP_RAGGED's rules: integers (at most 2^53),
@@ -397,7 +397,8 @@ static inline size_t lr_jpeg_bound(int width, int height, int format, int layout
  * lr_last_error names the frame and the entry.
  * `info` (HOST, 8 int32 per frame, written by the call): [0] width, [1] height, [2] components (1 or 3), [3] layout (0 =
  * 4:2:0 or one component, 1 = 4:4:4, 2 = 4:2:2), [4] restart interval in MCUs (0: none), [5] status, [6] the most often
- * any part of the scan had to be entropy-decoded until the chain of parts was consistent (see below; 0 in probe mode), [7] 0.
+ * any part of the scan had to be entropy-decoded until the chain of parts was consistent (see below; 0 in probe mode), [7] 0,
+ * or for a frame whose entry [7] is 1 the orientation that was read, 1..8.
  * Status: 0 decoded; 1 not a JPEG stream, or truncated before SOS; 2 unsupported (progressive, arithmetic, lossless or
  * hierarchical coding, 12-bit precision, 16-bit quantisation tables, component counts other than 1 or 3, another sampling,
  * a non-interleaved or multi-scan file, a missing table: lr_last_error tells which, for the last such frame); 3 the
@@ -406,8 +407,25 @@ static inline size_t lr_jpeg_bound(int width, int height, int format, int layout
  * the call: a frame of status 1 to 3 is skipped on the host and no byte of its extent is written; of one of status 4 the
  * extent's content is unspecified; nothing outside the frames' extents is ever written, and the call returns 0.
  * Accepted: SOF0 or SOF1 with 8-bit samples, Huffman-coded, one interleaved scan, any DHT (table ids 0..3), any DRI or none,
- * APPn and COM of any size, fill bytes in front of markers; the stream ends at EOI or at its length.  EXIF orientation is
- * not applied.
+ * APPn and COM of any size, fill bytes in front of markers; the stream ends at EOI or at its length.
+ * EXIF orientation (the demo's imread applies it; nearly every upright phone photograph is stored sideways, as 6 or 8) is
+ * applied to the frames whose entry [7] is 1, each frame of a batch by its own entry, inside the output pass of the same
+ * chain of launches: the picture is written upright, with no second pass over it.  With S the stored w x h picture that
+ * [7] = 0 gives, the picture O that is written is, bit for bit,
+ *     1: O[y][x] = S[y][x]        2: S[y][w-1-x]      3: S[h-1-y][w-1-x]    4: S[h-1-y][x]        (O is w x h)
+ *     5: O[y][x] = S[x][y]        6: S[h-1-x][y]      7: S[h-1-x][w-1-y]    8: S[x][w-1-y]        (O is h x w)
+ * (what PIL's ImageOps.exif_transpose does).  For such a frame info [0] [1] are the size of O (swapped for 5..8), info [7] is
+ * the orientation, the table's [4] [5] and the stride [3] are held against the size of O (status 3 and its message speak of
+ * that size), and probe mode does the same: probe with [7] = 1, allocate info [0] x info [1], decode with [7] = 1.
+ * With [7] = 0 the call does and reports what it did before entry [7] had a meaning, and info [7] is 0.
+ * The tag: of the segments before SOS the first APP1 whose payload starts with "Exif\0\0" counts and later ones do not
+ * (other APP1 segments, XMP for one, are passed over).  Behind those six bytes lies a TIFF block: "II*\0" (little endian)
+ * or "MM\0*" (big endian), a 32-bit offset of IFD0 from the block's start, there a 16-bit count and 12-byte entries (tag,
+ * type, count, value).  The entry with tag 0x0112 tells the orientation if its type is 3 (SHORT), its count 1 and its
+ * value -- the first two bytes of the value field, in the file's byte order -- 1..8.  Anything else is no orientation and
+ * behaves as 1: no Exif segment, another byte-order mark, an offset or an IFD that reaches beyond the segment, another type
+ * or count, a value of 0 or above 8.  None of it is a failure of the frame or of the call; every read stays inside the
+ * segment; IFD1 and the Exif sub-IFD are not followed.
  * Probe mode: d_dst == NULL fills `info` from the headers alone and launches nothing; it needs no context (ctx may be NULL)
  * and no GPU; [2] .. [5] of the table may then be 0 (no picture, no expected size).  lr_jpeg_info below spells it out.
  * The arithmetic (tests/numpy_jpeg_decode_ref.py restates it) is exact, in integers.
@@ -435,7 +453,8 @@ static inline int lr_decode_jpeg_device(lr_context* ctx, const void* d_src, cons
                                       (const double*)(const void*)&a, d_dst, dst_bytes, 0, 0, 0);
 }
 /* Probe mode of lr_decode_jpeg_device: width, height, components, layout, restart interval and status of every stream, from
- * the headers in host memory.  No context, no GPU. */
+ * the headers in host memory; for a frame whose entry [7] is 1 the upright size and, in info [7], the EXIF orientation.
+ * No context, no GPU. */
 static inline int lr_jpeg_info(const void* h_src, size_t src_bytes, const double* frames, int batch, int32_t* info) {
     return lr_decode_jpeg_device((lr_context*)0, (const void*)0, h_src, src_bytes, LR_PIX_U8X3, frames, batch, (void*)0, 0, info);
 }

@@ -397,12 +397,13 @@ def jpeg_table(sizes, sources, outputs, quality, layout=0):
     return table.astype(np.float64)
 
 
-def jpeg_decode_table(streams, outputs=None, sizes=None):
+def jpeg_decode_table(streams, outputs=None, sizes=None, orient=False):
     """The table of lr_decode_jpeg_device: streams: B pairs (byte_offset, length) of the streams in the source region;
     outputs: B pairs (byte_offset, row_bytes) of the pictures in the destination region; sizes: B pairs (width, height)
-    the caller allocated for.  outputs and sizes None: probe mode's table (zeros).  Returns float64 (B, 8).  Rejects what
-    can be seen without the regions: entries below 0 or above 2^53, a length of 2^31 - 16 or more, sizes outside 1 .. 65535.
-    Needs no GPU."""
+    the caller allocated for.  outputs and sizes None: probe mode's table (zeros).  orient: True, False or B of them:
+    entry [7], the file's EXIF orientation is applied (sizes are then those of the upright picture, as probe mode with
+    the same orient tells them).  Returns float64 (B, 8).  Rejects what can be seen without the regions: entries below 0
+    or above 2^53, a length of 2^31 - 16 or more, sizes outside 1 .. 65535.  Needs no GPU."""
     st = np.asarray(streams)
     if st.ndim != 2 or st.shape[1] != 2 or not np.issubdtype(st.dtype, np.integer) or len(st) < 1:
         raise ValueError("jpeg_decode_table: streams is B pairs of integers (byte_offset, length), B >= 1")
@@ -415,7 +416,11 @@ def jpeg_decode_table(streams, outputs=None, sizes=None):
         if a.shape != (B, 2) or not np.issubdtype(a.dtype, np.integer):
             raise ValueError("jpeg_decode_table: %s is B pairs of integers" % name)
         cols.append(a)
+    flags = np.asarray(orient)
+    if flags.dtype != np.bool_ or flags.shape not in ((), (B,)):
+        raise ValueError("jpeg_decode_table: orient is True, False or B of them")
     table = np.concatenate([c.astype(np.int64) for c in cols] + [np.zeros((B, 2), np.int64)], axis=1)
+    table[:, 7] = flags
     if table.min() < 0 or table.max() > 2 ** 53:
         raise ValueError("jpeg_decode_table: an entry below 0 or above 2^53")
     if int(table[:, 1].max()) > 2 ** 31 - 16:
@@ -449,21 +454,23 @@ def _decode_call(handle, d_src, region, fmt, table, d_dst, dst_bytes):
     return info
 
 
-def jpeg_info(streams):
+def jpeg_info(streams, orient=False):
     """lr_jpeg_info (lr_decode_jpeg_device's probe mode): of every JPEG file in the list (bytes) width, height, components,
     layout (0 = 4:2:0 or one component, 1 = 4:4:4, 2 = 4:2:2), restart interval and status (JPEG_OK, ...), from the headers
-    alone.  Returns int32 (B, 8).  No context, no GPU."""
+    alone.  orient=True: width and height are the upright picture's (swapped for the EXIF orientations 5 .. 8) and the
+    last column is the orientation, 1 .. 8 (1: the file tells none).  Returns int32 (B, 8).  No context, no GPU."""
     region, extents = _stream_region(streams)
-    return _decode_call(None, None, region, PIX_U8X3, jpeg_decode_table(extents), None, 0)
+    return _decode_call(None, None, region, PIX_U8X3, jpeg_decode_table(extents, orient=orient), None, 0)
 
 
-def _all_streams(frames, what):
-    """True if `frames` is a list of JPEG files (bytes), False if it holds none; a mixture is refused"""
-    if not isinstance(frames, (list, tuple)):
-        return False
-    n = sum(isinstance(f, (bytes, bytearray, memoryview)) for f in frames)
-    if n not in (0, len(frames)):
+def _all_streams(frames, what, orient=False):
+    """True if `frames` is a list of JPEG files (bytes), False if it holds none; a mixture is refused, and so is orient
+    with arrays, which carry no EXIF tag"""
+    n = sum(isinstance(f, (bytes, bytearray, memoryview)) for f in frames) if isinstance(frames, (list, tuple)) else 0
+    if n and n != len(frames):
         raise ValueError(what + ": the list is all JPEG files (bytes) or all arrays")
+    if orient and not n:
+        raise ValueError(what + ": orient=True goes with JPEG files (bytes); arrays carry no EXIF orientation")
     return n > 0
 
 
@@ -695,14 +702,16 @@ class Context:
                                                 fmt | WARP_LINES, C.cast(C.byref(args), C.c_void_p), C.c_void_p(d_dst),
                                                 dst_bytes, 0, 0, 0))
 
-    def draw_lines_batch(self, frames, lines_list, Hs=None, jpeg=None):
+    def draw_lines_batch(self, frames, lines_list, Hs=None, jpeg=None, orient=False):
         """The demo's lines picture for a list of 8-bit frames of different shapes (all gray H x W, or all H x W x 3) and
         their segments (one LINE_DTYPE array per frame; Hs: one 3x3 per frame, or None): one upload, one
         lr_draw_lines_device call, one download.  Returns the list of H x W x 3 uint8 pictures: a loop of draw_lines.
         jpeg=Q: the pictures stay in HBM, are encoded there (lr_encode_jpeg_device, quality Q, 4:2:0) and come back as JPEG files
-        (bytes): exactly the encoder's stream of the picture that jpeg=None returns."""
-        if _all_streams(frames, "draw_lines_batch"):
-            return self._draw_lines_streams([bytes(f) for f in frames], lines_list, Hs, jpeg)
+        (bytes): exactly the encoder's stream of the picture that jpeg=None returns.
+        orient=True (JPEG files only): the files' EXIF orientations are applied, the call on decode_jpeg_batch(files,
+        orient=True)'s arrays."""
+        if _all_streams(frames, "draw_lines_batch", orient):
+            return self._draw_lines_streams([bytes(f) for f in frames], lines_list, Hs, jpeg, orient)
         frames = [np.ascontiguousarray(f) for f in frames]
         if not frames or len(lines_list) != len(frames) or (Hs is not None and len(Hs) != len(frames)):
             raise ValueError("draw_lines_batch: as many line arrays (and Hs) as frames, at least one")
@@ -746,11 +755,11 @@ class Context:
                 self.device_free(d_dst.value)
         return [out[off:off + w * h * 3].reshape(h, w, 3).copy() for (w, h), (off, _) in zip(sizes, outputs)]
 
-    def _draw_lines_streams(self, streams, lines_list, Hs, jpeg):
+    def _draw_lines_streams(self, streams, lines_list, Hs, jpeg, orient=False):
         """draw_lines_batch for JPEG files (bytes): decoded in HBM, drawn on where they lie"""
         if len(lines_list) != len(streams) or (Hs is not None and len(Hs) != len(streams)):
             raise ValueError("draw_lines_batch: as many line arrays (and Hs) as frames, at least one")
-        d_src, src_bytes, fmt, frames = self._decode_resident(streams, None, "draw_lines_batch")
+        d_src, src_bytes, fmt, frames = self._decode_resident(streams, None, "draw_lines_batch", orient)
         return self._draw_resident(d_src, src_bytes, fmt, frames, lines_list, Hs, jpeg)
 
     def draw_lines(self, image_u8, lines, H=None):
@@ -843,16 +852,20 @@ class Context:
         the region at d_src (h_src: the same bytes on the host, a uint8 array; only the headers are read from it) become
         8-bit pictures (fmt PIX_U8: luminance, PIX_U8X3: RGB) in the dst_bytes at d_dst.  table: 8 doubles per frame
         (jpeg_decode_table).  Synchronous.  Returns info, int32 (B, 8): width, height, components, layout, restart
-        interval, status, decodes of the most often decoded part, 0.  d_dst None: probe mode."""
+        interval, status, decodes of the most often decoded part, and 0 -- or, for a frame whose entry [7] is 1
+        (jpeg_decode_table's orient), the EXIF orientation applied, 1 .. 8, width and height being the upright picture's.
+        d_dst None: probe mode."""
         return _decode_call(self._h, d_src, h_src, fmt, table, d_dst, dst_bytes)
 
-    def _decode_resident(self, streams, fmt, what):
+    def _decode_resident(self, streams, fmt, what, orient=False):
         """The JPEG files decoded into one fresh device buffer: one upload of the files, one lr_decode_jpeg_device call.
         fmt None: PIX_U8 if every file has one component, else PIX_U8X3.  Returns (d_dst, total_bytes, fmt, frames) with
         frames[b] = (width, height, byte_offset, row_bytes), every picture at a multiple of 4; the caller frees d_dst.
+        orient: the files' EXIF orientations are applied, and the sizes are the upright pictures'.
         Raises LibrectifyError naming the first frame whose status is not 0."""
         region, extents = _stream_region(streams)
-        info = _decode_call(None, None, region, PIX_U8X3, jpeg_decode_table(extents), None, 0)
+        orient = bool(orient)
+        info = _decode_call(None, None, region, PIX_U8X3, jpeg_decode_table(extents, orient=orient), None, 0)
         bad = np.flatnonzero(info[:, 5])
         if len(bad):
             jpeg_info([streams[bad[0]]])  # (once more alone: lr_last_error then tells why)
@@ -865,7 +878,7 @@ class Context:
             start = (end + 3) // 4 * 4
             frames.append((w, h, start, w * bpp))
             end = start + w * h * bpp
-        table = jpeg_decode_table(extents, np.array([f[2:] for f in frames], np.int64), np.array([f[:2] for f in frames], np.int64))
+        table = jpeg_decode_table(extents, np.array([f[2:] for f in frames], np.int64), np.array([f[:2] for f in frames], np.int64), orient)
         d_src = self.device_upload(region)
         d_dst = C.c_void_p()
         try:
@@ -881,14 +894,16 @@ class Context:
             if d_dst.value:
                 self.device_free(d_dst.value)
 
-    def decode_jpeg_batch(self, streams, fmt=PIX_U8X3):
+    def decode_jpeg_batch(self, streams, fmt=PIX_U8X3, orient=False):
         """A list of baseline JPEG files (bytes) of any sizes and samplings decoded on the GPU: one upload of the files, one
         lr_decode_jpeg_device call, one download.  fmt PIX_U8X3: H x W x 3 RGB pictures (a one-component file replicated);
-        PIX_U8: H x W luminance.  Returns a list of uint8 arrays.  Raises LibrectifyError naming the frame on a status
+        PIX_U8: H x W luminance.  orient=True: every file's EXIF orientation (tag 0x0112 of its first Exif segment) is
+        applied in the decoder's output pass and the pictures come out upright, what PIL's ImageOps.exif_transpose makes of
+        them; a file that tells none comes out as stored.  Returns a list of uint8 arrays.  Raises LibrectifyError naming the frame on a status
         other than 0 (jpeg_info tells the statuses beforehand)."""
         if fmt not in (PIX_U8, PIX_U8X3):
             raise ValueError("decode_jpeg_batch: fmt is PIX_U8 or PIX_U8X3")
-        d_dst, total, fmt, frames = self._decode_resident(streams, fmt, "decode_jpeg_batch")
+        d_dst, total, fmt, frames = self._decode_resident(streams, fmt, "decode_jpeg_batch", orient)
         try:
             out = self.device_download(d_dst, (total,), np.uint8)
         finally:
@@ -896,14 +911,15 @@ class Context:
         tail = (3,) if fmt == PIX_U8X3 else ()
         return [out[off:off + h * row].reshape((h, w) + tail).copy() for w, h, off, row in frames]
 
-    def decode_jpeg(self, data, fmt=PIX_U8X3):
-        """One baseline JPEG file (bytes) decoded on the GPU: H x W x 3 RGB (PIX_U8X3) or H x W luminance (PIX_U8)."""
-        return self.decode_jpeg_batch([data], fmt)[0]
+    def decode_jpeg(self, data, fmt=PIX_U8X3, orient=False):
+        """One baseline JPEG file (bytes) decoded on the GPU: H x W x 3 RGB (PIX_U8X3) or H x W luminance (PIX_U8);
+        orient=True: upright, by the file's EXIF orientation."""
+        return self.decode_jpeg_batch([data], fmt, orient)[0]
 
-    def _rectify_streams(self, streams, min_length, refine, cfg, clip, max_size, capacity, jpeg):
+    def _rectify_streams(self, streams, min_length, refine, cfg, clip, max_size, capacity, jpeg, orient=False):
         """rectify_batch for JPEG files: the files go up and are decoded in HBM, the pictures are handed to
         rectify_frames_device where they lie; with jpeg=Q no pixel crosses the link in either direction"""
-        d_src, _, fmt, sources = self._decode_resident(streams, None, "rectify_batch")
+        d_src, _, fmt, sources = self._decode_resident(streams, None, "rectify_batch", orient)
         return self._rectify_resident(d_src, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg)
 
     def prepare_device(self, d_src, src_image_bytes, batch, width, height, src_row_bytes, fmt, d_dst, dst_image_bytes,
@@ -963,7 +979,7 @@ class Context:
                 if p.value:
                     self.device_free(p.value)
 
-    def rectify(self, image_u8, min_length=None, refine=False, cfg=None, clip=3.0, max_size=None, jpeg=None):
+    def rectify(self, image_u8, min_length=None, refine=False, cfg=None, clip=3.0, max_size=None, jpeg=None, orient=False):
         """The reference demo's pipeline (autorectify.cpp) on an 8-bit frame (H x W gray or H x W x 3 RGB): luma
         (4899 R + 9617 G + 1868 B + 8192) >> 14, / 256, find_line_segment_groups with min_length max(w, h) / 100 by
         default, compute_rectification_transform (cfg: the demo's, horizontal_vp_min_distance = 2),
@@ -975,12 +991,16 @@ class Context:
         min_length max(w', h') / 100, the endpoints are divided by the scale, the transform is the full frame's and the
         warp reads the same resident frame.
         jpeg=Q: `warped` is the rectified picture's JPEG file (bytes, quality Q, 4:2:0), encoded in HBM: rectify_batch's
-        path for one frame."""
+        path for one frame.
+        orient=True (a JPEG file only): the file's EXIF orientation is applied as it is decoded, as the demo's imread
+        does: the call on decode_jpeg(file, orient=True)."""
         if isinstance(image_u8, (bytes, bytearray, memoryview)):  # a JPEG file: decoded in HBM, rectify_batch's path for one frame
-            lines, t, out = self.rectify_batch([bytes(image_u8)], min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, jpeg=jpeg)[0]
+            lines, t, out = self.rectify_batch([bytes(image_u8)], min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, jpeg=jpeg, orient=orient)[0]
             if out is None:
                 rectification_homography(t, clip)  # (raises what rectify raises for such a frame)
             return lines, t, out
+        if orient:
+            raise ValueError("rectify: orient=True goes with a JPEG file (bytes); an array carries no EXIF orientation")
         img = np.ascontiguousarray(image_u8)
         if img.dtype != np.uint8 or not (img.ndim == 2 or (img.ndim == 3 and img.shape[2] == 3)):
             raise ValueError("rectify: an H x W or H x W x 3 uint8 frame")
@@ -1267,7 +1287,8 @@ class Context:
             res.append((lines[b], tfs[b], img))
         return res
 
-    def rectify_batch(self, frames_u8, min_length=None, refine=False, cfg=None, clip=3.0, max_size=None, capacity=4096, jpeg=None):
+    def rectify_batch(self, frames_u8, min_length=None, refine=False, cfg=None, clip=3.0, max_size=None, capacity=4096, jpeg=None,
+                      orient=False):
         """Context.rectify for a batch: frames_u8 is a uint8 array [B, H, W] or [B, H, W, 3], or a list of such frames of one
         shape.  One upload, rectify_batch_device (one detector batch, the packed warp), one download.  Returns a
         list of (lines, transform, warped), frame by frame what rectify returns for it; warped is None for a frame whose
@@ -1281,9 +1302,11 @@ class Context:
         A list of JPEG files (bytes; all of them, else ValueError) in place of the frames: the files are uploaded and
         decoded in HBM (lr_decode_jpeg_device; u8x3, or u8 if every file has one component) and handed to
         rectify_frames_device where they lie -- bit for bit the call on decode_jpeg_batch's arrays (decode_jpeg_batch(files,
-        PIX_U8)'s for a list of one-component files); with jpeg=Q no pixel crosses the link in either direction."""
-        if _all_streams(frames_u8, "rectify_batch"):
-            return self._rectify_streams([bytes(f) for f in frames_u8], min_length, refine, cfg, clip, max_size, capacity, jpeg)
+        PIX_U8)'s for a list of one-component files); with jpeg=Q no pixel crosses the link in either direction.
+        orient=True (JPEG files only, else ValueError): the files' EXIF orientations are applied in the decoder's output
+        pass, as the demo's imread applies them -- bit for bit the call on decode_jpeg_batch(files, orient=True)'s arrays."""
+        if _all_streams(frames_u8, "rectify_batch", orient):
+            return self._rectify_streams([bytes(f) for f in frames_u8], min_length, refine, cfg, clip, max_size, capacity, jpeg, orient)
         if not isinstance(frames_u8, np.ndarray):
             frames_u8 = [np.asarray(f) for f in frames_u8]
             if len({f.shape for f in frames_u8}) > 1:

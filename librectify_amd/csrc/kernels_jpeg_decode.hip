@@ -24,7 +24,10 @@
 //                  registers, the transpose through LDS, the second pass; the 64 samples take the place of the block's
 //                  first 64 bytes.
 //   6. output      A thread per pixel: centred triangle upsampling of the chrominance from the blocks' samples, the colour
-//                  rule, the store into the caller's picture.
+//                  rule, the store into the caller's picture -- where the frame's EXIF orientation puts it, if the caller
+//                  asked for that (entry [7]).  Orientations 2..4 keep rows as rows and only move the address; 5..8 turn
+//                  rows into columns, and such a frame's tiles are squares of 32 x 32 stored pixels that go through LDS,
+//                  so that consecutive lanes still store consecutive bytes of one row of the picture.
 //
 // Every loop on the device is bounded by the part's bits, the stream's length or the frame's block count; every read of the
 // stream is clamped to [offset, offset + length), every coefficient store to the frame's blocks, every pixel store to the
@@ -46,6 +49,7 @@ constexpr int kWave = 64;
 constexpr int kPartBytes = 128;   // a part of a scan: one lane's
 constexpr int kSyncBlock = 256;   // parts of a workgroup
 constexpr int kTileW = 32, kTileH = 8;  // pixels of an output tile (a thread each)
+constexpr int kSquare = 32;             // side of a transposing frame's tile: kSquare / kTileH passes of the thread shape
 constexpr int kCoefLimit = 32767;  // |c q| saturates here (legitimate data stays below 2^12)
 constexpr int kMidLimit = 65535;   // the first pass's result here: 21641 * 65535 < 2^31, 21641 the largest column sum of |T|
 constexpr int kMidShift = 7, kEndShift = 19;
@@ -65,7 +69,7 @@ struct JdFrame {
     uint32_t len, scan;  // the stream's length; offset of the scan's first byte in it
     int w, h, comps, layout;
     int ri, bpm, mcus_x, n_mcus;
-    int hs, vs, n_parts, pad;
+    int hs, vs, n_parts, orient;  // orient: 0 or 1 as stored, 2..8 the EXIF orientation the output pass applies
     uint8_t q[3][64];  // divisors per component, natural order
     HuffDec dc[3], ac[3];
 };
@@ -524,35 +528,79 @@ __device__ __forceinline__ int chroma_at(const uint8_t* __restrict__ blocks, con
             sample_at(blocks, f, comp, fx, fy) + 8) >> 4;
 }
 
+// pixel (x, y) of the stored picture: its luminance (kFormat LR_PIX_U8: all that is computed) and its three colour bytes
 template <int kFormat>
+__device__ __forceinline__ void pixel_at(const uint8_t* __restrict__ blocks, const JdFrame* f, int x, int y, int (&c)[3]) {
+    const int yy = sample_at(blocks, f, 0, x, y);
+    c[0] = c[1] = c[2] = yy;
+    if (kFormat == LR_PIX_U8X3 && f->comps == 3) {  // the IJG fixed-point inverse of the encoder's rule
+        const int cb = chroma_at(blocks, f, 1, x, y) - 128, cr = chroma_at(blocks, f, 2, x, y) - 128;
+        c[0] = min(max(yy + ((91881 * cr + 32768) >> 16), 0), 255);
+        c[1] = min(max(yy + ((-22554 * cb - 46802 * cr + 32768) >> 16), 0), 255);
+        c[2] = min(max(yy + ((116130 * cb + 32768) >> 16), 0), 255);
+    }
+}
+
+// The EXIF orientations, S the stored w x h picture and O the one written:
+//   2: O[y][x] = S[y][w-1-x]    3: S[h-1-y][w-1-x]    4: S[h-1-y][x]                 (O is w x h)
+//   5: O[y][x] = S[x][y]        6: S[h-1-x][y]        7: S[h-1-x][w-1-y]    8: S[x][w-1-y]    (O is h x w)
+// kTurn: the batch has a frame of orientation 5..8.  A batch without one -- every call that does not ask for orientations
+// among them -- gets the kernel without the transposing path, its LDS and its registers.
+template <int kFormat, bool kTurn>
 __global__ __launch_bounds__(kTileW * kTileH) void jd_output_kernel(int batch, int n_tiles, const JdFrame* __restrict__ frames,
                                                                     const int* __restrict__ tile_start, const int* __restrict__ grp_start,
                                                                     const int16_t* __restrict__ coef, uint8_t* __restrict__ dst) {
+    constexpr int kBpp = kFormat == LR_PIX_U8 ? 1 : 3;
+    // a square of finished bytes, [stored x][stored y]: the pitch is an odd count of words (9 or 25), so the 32 lanes of a
+    // store group, one stored x each, fall on 32 different banks
+    constexpr int kPitch = kSquare * kBpp + 4;
+    __shared__ uint8_t s_sq[kTurn ? kSquare * kPitch : 4];
     XcdBand band(n_tiles);
     for (int tile; band.next(&tile);) {
         const int b = frame_of_tile(tile_start, batch, tile);
         const JdFrame* f = frames + b;
-        const int local = tile - tile_start[b], tiles_x = (f->w + kTileW - 1) / kTileW;
-        const int x = (local % tiles_x) * kTileW + (int)threadIdx.x % kTileW, y = (local / tiles_x) * kTileH + (int)threadIdx.x / kTileW;
-        if (x >= f->w || y >= f->h) continue;
+        const int local = tile - tile_start[b], o = f->orient;
         const uint8_t* blocks = reinterpret_cast<const uint8_t*>(coef + (size_t)grp_start[b] * 8 * 64);
-        const int yy = sample_at(blocks, f, 0, x, y);
-        uint8_t* out = dst + (size_t)f->dst_off + (size_t)y * (size_t)f->dst_row;
-        if (kFormat == LR_PIX_U8) {
-            out[x] = (uint8_t)yy;
-        } else {
-            int r = yy, g = yy, bl = yy;
-            if (f->comps == 3) {  // the IJG fixed-point inverse of the encoder's rule
-                const int cb = chroma_at(blocks, f, 1, x, y) - 128, cr = chroma_at(blocks, f, 2, x, y) - 128;
-                r = min(max(yy + ((91881 * cr + 32768) >> 16), 0), 255);
-                g = min(max(yy + ((-22554 * cb - 46802 * cr + 32768) >> 16), 0), 255);
-                bl = min(max(yy + ((116130 * cb + 32768) >> 16), 0), 255);
-            }
-            uint8_t* px = out + (size_t)x * 3;
-            px[0] = (uint8_t)r;
-            px[1] = (uint8_t)g;
-            px[2] = (uint8_t)bl;
+        const int tx = (int)threadIdx.x % kTileW, ty = (int)threadIdx.x / kTileW;
+        int c[3];
+        if (!kTurn || o < 5) {  // rows stay rows: a thread per pixel, its place mirrored
+            const int tiles_x = (f->w + kTileW - 1) / kTileW;
+            const int x = (local % tiles_x) * kTileW + tx, y = (local / tiles_x) * kTileH + ty;
+            if (x >= f->w || y >= f->h) continue;
+            pixel_at<kFormat>(blocks, f, x, y, c);
+            const int ox = (o == 2 || o == 3) ? f->w - 1 - x : x, oy = (o == 3 || o == 4) ? f->h - 1 - y : y;
+            uint8_t* px = dst + (size_t)f->dst_off + (size_t)oy * (size_t)f->dst_row + (size_t)ox * kBpp;
+#pragma unroll
+            for (int i = 0; i < kBpp; ++i) px[i] = (uint8_t)c[i];
+            continue;
         }
+        if (!kTurn) continue;  // (not reached: the code below is left out of that kernel)
+        // rows become columns (the branch is the workgroup's: every lane reaches both barriers)
+        const int tiles_x = (f->w + kSquare - 1) / kSquare;
+        const int x0 = (local % tiles_x) * kSquare, y0 = (local / tiles_x) * kSquare;
+#pragma unroll
+        for (int pass = 0; pass < kSquare / kTileH; ++pass) {
+            const int j = ty + pass * kTileH;
+            if (x0 + tx < f->w && y0 + j < f->h) {
+                pixel_at<kFormat>(blocks, f, x0 + tx, y0 + j, c);
+#pragma unroll
+                for (int i = 0; i < kBpp; ++i) s_sq[tx * kPitch + j * kBpp + i] = (uint8_t)c[i];
+            }
+        }
+        __syncthreads();
+        // stored column x0 + i is row oy of the picture, stored row y0 + j its pixel ox; lane order follows ox
+        const bool flip_x = o == 6 || o == 7, flip_y = o == 7 || o == 8;
+#pragma unroll 4  // (all twelve passes of u8x3 unrolled cost the kernel half its occupancy)
+        for (int pass = 0; pass < kSquare * kBpp / kTileH; ++pass) {
+            const int at = (int)threadIdx.x + pass * (kTileW * kTileH);
+            const int i = at / (kSquare * kBpp), k = at % (kSquare * kBpp), ch = k % kBpp;
+            const int j = flip_x ? kSquare - 1 - k / kBpp : k / kBpp;
+            if (x0 + i < f->w && y0 + j < f->h) {
+                const int ox = flip_x ? f->h - 1 - (y0 + j) : y0 + j, oy = flip_y ? f->w - 1 - (x0 + i) : x0 + i;
+                dst[(size_t)f->dst_off + (size_t)oy * (size_t)f->dst_row + (size_t)ox * kBpp + ch] = s_sq[i * kPitch + j * kBpp + ch];
+            }
+        }
+        __syncthreads();
     }
 }
 
@@ -562,6 +610,7 @@ struct Header {
     int status = kNotJpeg;
     std::string message = "no SOI";
     int w = 0, h = 0, comps = 0, layout = 0, ri = 0;
+    int orientation = 0;  // the EXIF tag 0x0112 of the first Exif segment, 1..8; 0: none that counts
     uint32_t scan = 0;
     uint8_t q[3][64];
     HuffDec dc[3], ac[3];
@@ -584,6 +633,30 @@ void make_decoder(const uint8_t* bits, const uint8_t* vals, int count, HuffDec* 
     t->maxcode[0] = t->maxcode[17] = -1;
 }
 
+// The orientation an Exif APP1 payload tells: "Exif\0\0", then a TIFF block -- the byte order ("II*\0" little, "MM\0*" big
+// endian), the offset of IFD0 from the block's start, there a 16-bit count and 12-byte entries (tag, type, count, value).
+// The entry with tag 0x0112 counts if its type is 3 (SHORT), its count 1 and its value, the value field's first two bytes,
+// 1..8.  Everything else is 0, none: a block or an IFD that does not lie within the n bytes, another type, count or value.
+// Only IFD0 is read, and no read goes beyond t[0, n).
+int exif_orientation(const uint8_t* t, size_t n) {
+    if (n < 8) return 0;
+    const bool little = t[0] == 'I' && t[1] == 'I' && t[2] == 0x2A && t[3] == 0;
+    if (!little && !(t[0] == 'M' && t[1] == 'M' && t[2] == 0 && t[3] == 0x2A)) return 0;
+    auto u16 = [&](size_t at) { return little ? (uint32_t)t[at] | ((uint32_t)t[at + 1] << 8) : ((uint32_t)t[at] << 8) | (uint32_t)t[at + 1]; };
+    const size_t ifd = ((size_t)u16(little ? 6 : 4) << 16) | u16(little ? 4 : 6);
+    if (ifd > n - 2) return 0;
+    const size_t count = u16(ifd);
+    if (count * 12 > n - 2 - ifd) return 0;
+    for (size_t i = 0; i < count; ++i) {
+        const size_t at = ifd + 2 + 12 * i;
+        if (u16(at) != 0x0112) continue;
+        const bool one = little ? (t[at + 4] == 1 && !t[at + 5] && !t[at + 6] && !t[at + 7]) : (!t[at + 4] && !t[at + 5] && !t[at + 6] && t[at + 7] == 1);
+        const uint32_t v = u16(at + 8);
+        return u16(at + 2) == 3 && one && v >= 1 && v <= 8 ? (int)v : 0;
+    }
+    return 0;
+}
+
 // the stream d[0, n) up to the first byte of its scan
 void read_header(const uint8_t* d, size_t n, Header& hd) {
     auto fail = [&](int status, const std::string& what) {
@@ -603,6 +676,7 @@ void read_header(const uint8_t* d, size_t n, Header& hd) {
     size_t p = 2;
     const uint8_t* seg = nullptr;
     size_t seg_len = 0;
+    bool have_exif = false;
     for (;;) {
         if (p >= n) return fail(kNotJpeg, "truncated before SOS");
         if (d[p] != 0xFF) return fail(kNotJpeg, "no marker where one is due");
@@ -654,6 +728,11 @@ void read_header(const uint8_t* d, size_t n, Header& hd) {
             }
             if (m == 0xC2) return fail(kUnsupported, "progressive (SOF2)");
             return fail(kUnsupported, "arithmetic, lossless or hierarchical coding (SOF" + std::to_string(m - 0xC0) + ")");
+        } else if (m == 0xE1) {  // the first Exif segment tells the orientation, whatever it holds; XMP and the like are skipped
+            if (!have_exif && seg_len >= 6 && std::memcmp(seg, "Exif\0\0", 6) == 0) {
+                have_exif = true;
+                hd.orientation = exif_orientation(seg + 6, seg_len - 6);
+            }
         } else if (m == 0xDA) {
             break;
         }
@@ -715,6 +794,7 @@ int ctx_decode_jpeg(lr_context* c, const void* d_src, const void* h_src, size_t 
     const uint64_t bpp = format == LR_PIX_U8 ? 1 : 3;
     struct Entry {
         uint64_t off, len, dst_off, dst_row, w, h;
+        bool orient;
     };
     std::vector<Entry> en((size_t)batch);
     std::vector<std::pair<uint64_t, uint64_t>> extent;
@@ -731,7 +811,8 @@ int ctx_decode_jpeg(lr_context* c, const void* d_src, const void* h_src, size_t 
         if (!table_integer(t[3], e.w ? (double)(e.w * bpp) : 0.0, kExact, &e.dst_row))
             return fail_at(b, 3, "(row stride) is not an integer from a row's bytes to 2^53");
         if (!(t[6] == 0.0)) return fail_at(b, 6, "is reserved and must be 0");
-        if (!(t[7] == 0.0)) return fail_at(b, 7, "is reserved and must be 0");
+        if (!(t[7] == 0.0 || t[7] == 1.0)) return fail_at(b, 7, "(EXIF orientation) is 0 (as stored) or 1 (applied)");
+        e.orient = t[7] == 1.0;
         uint64_t end;
         if (__builtin_add_overflow(e.off, e.len, &end) || end > src_bytes)
             return fail_at(b, 0, "(stream offset): the stream reaches beyond src_bytes");
@@ -764,13 +845,17 @@ int ctx_decode_jpeg(lr_context* c, const void* d_src, const void* h_src, size_t 
         const Entry& e = en[(size_t)b];
         hd = Header{};
         read_header(static_cast<const uint8_t*>(h_src) + e.off, (size_t)e.len, hd);
-        if (hd.status == kOk && e.w && ((uint64_t)hd.w != e.w || (uint64_t)hd.h != e.h)) {
+        // the picture as written: with entry [7] the orientation the file tells (1 if none), and its size swapped for 5..8
+        const int orient = e.orient ? std::max(hd.orientation, 1) : 0;
+        const int out_w = orient >= 5 ? hd.h : hd.w, out_h = orient >= 5 ? hd.w : hd.h;
+        if (hd.status == kOk && e.w && ((uint64_t)out_w != e.w || (uint64_t)out_h != e.h)) {
             hd.status = kSizeMismatch;
-            hd.message = "the stream is " + std::to_string(hd.w) + " x " + std::to_string(hd.h);
+            hd.message = "the stream is " + std::to_string(out_w) + " x " + std::to_string(out_h) + (orient >= 5 ? " (turned by its orientation)" : "");
         }
         int32_t* row = rows.data() + (size_t)b * 8;
-        row[0] = hd.w;
-        row[1] = hd.h;
+        row[0] = out_w;
+        row[1] = out_h;
+        row[7] = orient;
         row[2] = hd.comps;
         row[3] = hd.layout;
         row[4] = hd.ri;
@@ -798,6 +883,7 @@ int ctx_decode_jpeg(lr_context* c, const void* d_src, const void* h_src, size_t 
         f.mcus_x = (f.w + 8 * f.hs - 1) / (8 * f.hs);
         f.n_mcus = f.mcus_x * ((f.h + 8 * f.vs - 1) / (8 * f.vs));  // (at most 2^26 of at most 6 blocks)
         f.n_parts = (int)std::max<uint64_t>(1, (e.len - hd.scan + kPartBytes - 1) / kPartBytes);
+        f.orient = orient;
         std::memcpy(f.q, hd.q, sizeof f.q);
         std::memcpy(f.dc, hd.dc, sizeof f.dc);
         std::memcpy(f.ac, hd.ac, sizeof f.ac);
@@ -807,7 +893,8 @@ int ctx_decode_jpeg(lr_context* c, const void* d_src, const void* h_src, size_t 
         tile_start.push_back((int)n_tiles);
         n_groups += ((int64_t)f.n_mcus * f.bpm + 7) / 8;
         n_wg += wgs;
-        n_tiles += (int64_t)((f.w + kTileW - 1) / kTileW) * ((f.h + kTileH - 1) / kTileH);
+        const int tile_w = orient >= 5 ? kSquare : kTileW, tile_h = orient >= 5 ? kSquare : kTileH;
+        n_tiles += (int64_t)((f.w + tile_w - 1) / tile_w) * ((f.h + tile_h - 1) / tile_h);
         most_wg = std::max(most_wg, wgs);
         if (n_groups > 0x0FFFFFF0ll || n_wg > 0x007FFFF0ll || n_tiles > 0x7FFFFFF0ll)
             return fail_at(b, 1, "(stream length): the frames are larger than 2^31 blocks, parts or tiles in total");
@@ -880,12 +967,11 @@ int ctx_decode_jpeg(lr_context* c, const void* d_src, const void* h_src, size_t 
     hipLaunchKernelGGL(jd_transform_kernel, dim3(grid_t), dim3(kWave), 0, c->stream, live, (int)n_groups, format == LR_PIX_U8 ? 1 : 0,
                        d_frames, d_grp, js.coef.get());
     const int grid_o = (int)((std::min<int64_t>(n_tiles, 1 << 18) + 7) / 8 * 8);
-    if (format == LR_PIX_U8)
-        hipLaunchKernelGGL(jd_output_kernel<LR_PIX_U8>, dim3(grid_o), dim3(kTileW * kTileH), 0, c->stream, live, (int)n_tiles, d_frames,
-                           d_tile, d_grp, js.coef.get(), d8);
-    else
-        hipLaunchKernelGGL(jd_output_kernel<LR_PIX_U8X3>, dim3(grid_o), dim3(kTileW * kTileH), 0, c->stream, live, (int)n_tiles, d_frames,
-                           d_tile, d_grp, js.coef.get(), d8);
+    bool turn = false;
+    for (const JdFrame& f : fr) turn = turn || f.orient >= 5;
+    auto output = format == LR_PIX_U8 ? (turn ? jd_output_kernel<LR_PIX_U8, true> : jd_output_kernel<LR_PIX_U8, false>)
+                                      : (turn ? jd_output_kernel<LR_PIX_U8X3, true> : jd_output_kernel<LR_PIX_U8X3, false>);
+    hipLaunchKernelGGL(output, dim3(grid_o), dim3(kTileW * kTileH), 0, c->stream, live, (int)n_tiles, d_frames, d_tile, d_grp, js.coef.get(), d8);
     LR_HIP(hipGetLastError());
     LR_HIP(hipMemcpyAsync(m + o_flags, d + o_flags, need - o_flags, hipMemcpyDeviceToHost, c->stream));
     LR_HIP(hipStreamSynchronize(c->stream));
