@@ -484,6 +484,7 @@ enum lr_buffer_id {
     LR_BUF_SEED_THR = 6,  /* float  n_seeds: (1-TRACE_TOLERANCE)*value at the seed */
     LR_BUF_MAXMAG = 7,    /* float  1 */
     LR_BUF_SEED_SIZE = 8, /* int32  n_seeds: pixels claimed by each seed's flood (0 = skipped) */
+    LR_BUF_SEED_REC = 9,  /* uint32 n_seeds x 4: {SEED_IDX, SEED_BIN, bits of SEED_THR, 0}, the record the flood's walks read */
 };
 int lr_download(lr_context* ctx, int buffer_id, void* dst, size_t bytes);
 

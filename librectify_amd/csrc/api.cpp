@@ -503,6 +503,7 @@ int lr_download(lr_context* ctx, int buffer_id, void* dst, size_t bytes) {
             case LR_BUF_SEED_THR: src = ctx->ws.seed_thr; have = (size_t)ctx->n_seeds * 4; break;
             case LR_BUF_MAXMAG: src = ctx->maxmag; have = 4; break;
             case LR_BUF_SEED_SIZE: src = ctx->ws.seed_size; have = (size_t)ctx->n_seeds * 4; break;
+            case LR_BUF_SEED_REC: src = ctx->ws.seed_rec; have = (size_t)ctx->n_seeds * 16; break;
             default: set_error("lr_download: unknown buffer id"); return 1;
         }
         if (buffer_id == LR_BUF_DMASK && ctx->dmask_consumed) {

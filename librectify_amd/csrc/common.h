@@ -113,7 +113,7 @@ int launch_seed_select(const uint64_t* cand, const uint32_t* cand_count, const u
 // the seed count stays on the device (*n_seeds, clamped to cap); the launches cover `cap` seeds.  keys_alt: a second buffer
 // of cap keys (the merge rounds of large frames go back and forth between the two)
 int launch_seed_order(uint64_t* keys, uint64_t* keys_alt, const uint32_t* n_seeds, uint32_t cap, const float* dx, const float* dy,
-                      BinTrig trig, float trace_tolerance, int32_t* seed_idx, int32_t* seed_bin, float* seed_thr, hipStream_t s);
+                      BinTrig trig, float trace_tolerance, int32_t* seed_idx, int32_t* seed_bin, float* seed_thr, uint4* seed_rec, hipStream_t s);
 
 // kernels_flood.hip
 int launch_label_init(uint32_t* label, size_t n, hipStream_t s);
@@ -212,6 +212,7 @@ struct FloodFrame {
     uint32_t* label;
     int32_t* seed_size;
     int32_t* queue;
+    const uint4* seed_rec;  // per seed: {seed_idx, seed_bin, bits of seed_thr, 0} -- what a walk's set-up reads, in one load (launch_seed_order)
 };
 struct FloodProgress {
     int enqueued = 0;  // rounds enqueued so far

@@ -52,6 +52,7 @@ struct Workspace {
     DeviceBuffer<uint64_t> keys_a, keys_b;
     DeviceBuffer<int32_t> seed_idx, seed_bin;
     DeviceBuffer<float> seed_thr;
+    DeviceBuffer<uint4> seed_rec;  // the three arrays above, a record per seed (FloodFrame::seed_rec)
     DeviceBuffer<int32_t> seed_size;
     // stage 3
     DeviceBuffer<uint32_t> label;

@@ -122,7 +122,7 @@ int ctx_reserve_workspace(lr_context* c, size_t npix, int ntiles) {
     s.cap_tiles = 0;
     if (s.dx.grow(cp) || s.dy.grow(cp) || s.dmask.grow(cp + 16) || s.cand.grow((size_t)ct * fg.cand_cap) || s.cand_count.grow(ct) ||
         s.tile_max.grow(ct) || s.tile_pass.grow(ct) || s.tile_off.grow(tile_off_words) || s.keys_a.grow(cp) || s.keys_b.grow(cp) ||
-        s.seed_idx.grow(cp) || s.seed_bin.grow(cp) || s.seed_thr.grow(cp) || s.seed_size.grow(cp) || s.label.grow(cp) ||
+        s.seed_idx.grow(cp) || s.seed_bin.grow(cp) || s.seed_thr.grow(cp) || s.seed_rec.grow(cp) || s.seed_size.grow(cp) || s.label.grow(cp) ||
         s.queue.grow(cp) || s.comp_rank.grow(cp) || s.comp_seed.grow(cp) || s.comp_off.grow(cp + 1) || s.cursor.grow(cp) ||
         s.px_a.grow(cp) || s.px_b.grow(cp) || s.scratch_w.grow(cp) || s.d_lines.grow(cp / 6 + 16) || s.comp_large.grow(cp / 64 + 16))
         return 1;
@@ -179,7 +179,7 @@ int ensure_flood_buffers(lr_context* c) {
     LR_HIP(hipStreamSynchronize(c->stream));
     const size_t cs = c->ws.cap_pix;
     if (grow_into(o.blocked, f.blocked, cs) || grow_into(o.count, f.count, cs) || grow_into(o.flags, f.flags, cs) ||
-        grow_into(o.state, f.state, cs) || grow_into(o.tier, f.tier, cs) || grow_into(o.blk, f.blk, cs) ||
+        grow_into(o.state, f.state, cs) || grow_into(o.tier, f.tier, cs + 4) /* (read a word at a time) */ || grow_into(o.blk, f.blk, cs) ||
         grow_into(o.act_a, f.act_a, cs) || grow_into(o.act_b, f.act_b, cs) || grow_into(o.ctrl, f.ctrl, kFloodCtrlWords) ||
         grow_into(o.big_list, f.big_list, 8192) || grow_into(o.handover, f.handover, 8192 * kFloodHandWords) ||
         grow_into(o.dirty, f.dirty, cs / 256 + 16) ||

@@ -98,7 +98,7 @@ FloodBuffers flood_buffers_for(lr_context* c) {
 
 FloodFrame flood_frame_for(lr_context* c) {
     return FloodFrame{c->ws.dx, c->ws.dy, c->ws.dmask, c->w, c->h, c->ws.seed_idx, c->ws.seed_bin, c->ws.seed_thr,
-                      c->d_counts + kCntSeeds, c->seed_cap, c->trig, c->ws.label, c->ws.seed_size, c->ws.queue};
+                      c->d_counts + kCntSeeds, c->seed_cap, c->trig, c->ws.label, c->ws.seed_size, c->ws.queue, c->ws.seed_rec};
 }
 
 // everything of a frame's first stage but the launch: workspace, seed-sort capacity, state of the last run
@@ -181,7 +181,7 @@ int enqueue_seeds(lr_context* c) {
                            c->stream))
         return 1;
     if (launch_seed_order(c->ws.keys_a, c->ws.keys_b, c->d_counts + kCntSeeds, c->seed_cap, c->ws.dx, c->ws.dy, c->trig, kTraceTolerance,
-                          c->ws.seed_idx, c->ws.seed_bin, c->ws.seed_thr, c->stream))
+                          c->ws.seed_idx, c->ws.seed_bin, c->ws.seed_thr, c->ws.seed_rec, c->stream))
         return 1;
     if (c->opt.timing_on) LR_HIP(hipEventRecord(c->ev[2], c->stream));
     return 0;

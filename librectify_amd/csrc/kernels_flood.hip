@@ -180,32 +180,54 @@ constexpr uint32_t kHoldMinBig = 4;        // walks in the second tier after whi
 constexpr uint32_t kHoldRelease = 64;      // the hold-back ends when so few seeds below the line are still active
 constexpr uint32_t kPartialSteps = 16;     // partial-commit walks stop after this many tile steps
 constexpr int kPartialRounds = 3;          // rounds that bring the partial commits (enqueue_round)
+// Workgroups of the partial-commit launch (its loop strides over the list): 0 = the exploration's grid, one entry a workgroup.
+// (experiment: -DLR_PARTIAL_GRID=8192, a few workgroups per wave slot; the A/B is in profiles/flood_prologue.txt)
+#ifndef LR_PARTIAL_GRID
+#define LR_PARTIAL_GRID 0
+#endif
+constexpr uint32_t kPartialGrid = LR_PARTIAL_GRID;
 constexpr uint32_t kDenseDiv = 12;         // a frame with a seed in every kDenseDiv pixels starts staged (flood_init_seeds_kernel)
 constexpr uint32_t kLogMinTiles = 16;      // walks of this many tiles leave a log (single calls; the lanes of a batch bring their own) ...
 constexpr uint32_t kLogWalkTiles = 12;     // ... and a seed with a log walks this many before it turns to it
 
+// (The 32 words in front are what a walk reads before its first tile -- explore_body, flood_partial_commit_kernel: a kernel
+// has them in two loads of sixteen, in one round trip; see walk_args.)
 struct FloodArgs {
+    uint32_t* ctrl;     // kCtrl* words
+    uint32_t* act_a;    // the two active lists: a round with work reads the one its index (kCtrlRounds) selects and
+    uint32_t* act_b;    // appends to the other (rounds enqueued behind a request for a giant step do nothing and do not count)
+    const uint4* seed_rec;  // per seed: {seed_idx, seed_bin, bits of seed_thr, 0} (seed_rank_setup_kernel: the three arrays below in one load)
+    uint8_t* tier;      // per seed, kept across rounds: 1 = go to the second storage tier at once
+    uint32_t* log_len;  // per seed: records of its log (0: none; see log_off)
+    uint32_t* label;
+    const uint8_t* dmask;
     const float* dx;
     const float* dy;
-    const uint8_t* dmask;
-    int w, h, tiles_x;
+    int w, h;
+    uint32_t no_rest;         // this round has no `rest` launch: entries past the grid are not walked
+    uint32_t big_cap;         // seeds per round the second tier takes (0: tier switched off)
+    uint32_t giant_hold;      // 1: only the lowest active seed walks on into a slab (see kCtrlLowest)
+    uint32_t log_min_tiles;   // 0xFFFFFFFF: no logs
+    uint32_t log_seeds;       // seeds with per-seed words below (FloodBuffers::log_seeds)
+    uint32_t log_use;         // 0: this round's walks leave logs but none is used yet (the frame's first round)
+    uint32_t log_max_len;     // logs of at most this many records are written and used (what the launched kernels' tables hold)
+    uint32_t log_walk_tiles;  // a seed with a log walks this many tiles before it turns to the log
+    uint32_t quiet;           // this round goes without the second tier's launch on a frame that has one (flood_enqueue: calm hint)
+    uint32_t giant_step;      // 1: a walk of the LOWEST active seed that outgrows the LDS tiers asks for the giant step (kCtrlGiantStep) instead of moving into a slab
+    // ---- everything else
+    int tiles_x;
     const int32_t* seed_idx;
     const int32_t* seed_bin;
     const float* seed_thr;
-    uint32_t* label;
     uint32_t* blocked;  // per seed
     uint32_t* count;    // per seed: pixels walked this round
     uint32_t* flags;    // per seed
-    uint8_t* tier;      // per seed, kept across rounds: 1 = go to the second storage tier at once
-    uint32_t* ctrl;     // kCtrl* words
     uint8_t* dirty;     // per 256 consecutive pixels of the label image: stamped in this round (see the commit pass)
     uint4* slab_ring;   // n_slabs x slab_ring_cap records {tile, -, mask.lo, mask.hi}
     uint4* slab_hash;   // n_slabs x slab_hash_cap x 2 records {generation, tile+1, V.lo, V.hi} {A.lo, A.hi, -, -}
     uint32_t n_slabs, slab_ring_cap, slab_hash_cap;  // caps are powers of two
     uint32_t win_shift;                              // staged start (see kCtrlWindow): growth of the window per round
-    uint32_t no_rest;                                // this round has no `rest` launch: entries past the grid are not walked
     uint32_t next_reach;                             // list entries the NEXT round's exploration reaches (0xFFFFFFFF: all)
-    uint32_t big_cap;                                // seeds per round the second tier takes (0: tier switched off)
     uint32_t* handover;                              // state of the walks handed to the second tier (FloodBuffers::handover)
     uint32_t team_tiles;                             // the team's table counts as full at this many tiles (kTeamTiles, or a test hook's)
     uint32_t* blk;                                   // per seed: the lower seed a long, log-less walk of it was blocked by (0xFFFFFFFF: none; see kCtrlDeferLow)
@@ -217,24 +239,13 @@ struct FloodArgs {
     uint32_t* rewalk_list;                           // this round's seeds whose footprint flood_rewalk_kernel works out from their log, kBigCap entries
     // ---- re-walks from the log (flood_rewalk_kernel): a finished walk of at least log_min_tiles tiles leaves its footprint
     // as (tile, walked pixels) records; the seed's later rounds work on those records instead of walking the image again
-    uint32_t log_min_tiles;                          // 0xFFFFFFFF: no logs
-    uint32_t log_walk_tiles;                         // a seed with a log walks this many tiles before it turns to the log
-    uint32_t log_use;                                // 0: this round's walks leave logs but none is used yet (the frame's first round)
-    uint32_t log_max_len;                            // logs of at most this many records are written and used (what the launched kernels' tables hold)
     uint32_t log_sweep;                              // test hook: every footprint is worked out by sweeps (flood_rewalk_kernel)
     uint32_t* host_progress;                         // FloodBuffers::host_progress (nullptr: nobody is looking)
     uint32_t* host_ctrl;                             // FloodBuffers::host_ctrl (with host_progress only)
-    uint32_t quiet;                                  // this round goes without the second tier's launch on a frame that has one (flood_enqueue: calm hint)
-    uint32_t giant_hold;                             // 1: only the lowest active seed walks on into a slab (see kCtrlLowest)
-    uint32_t log_seeds;                              // seeds with per-seed words below (FloodBuffers::log_seeds)
-    uint32_t* log_off;                               // first record of the seed's log ...
-    uint32_t* log_len;                               // ... and their number (0: none)
+    uint32_t* log_off;                               // first record of the seed's log (log_len of them)
     uint32_t* log_buf;                               // records: tile, walked lo, walked hi
     uint32_t log_cap;                                // records the buffer holds
     // ---- the giant step (see kCtrlGiantStep): the lowest active seed's flood by the whole device
-    uint32_t giant_step;                             // 1: a walk of the LOWEST active seed that outgrows the LDS tiers asks for it instead of moving into a slab
-    uint32_t* act_a;                                 // the two active lists: a round with work reads the one its index (kCtrlRounds) selects and
-    uint32_t* act_b;                                 // appends to the other (rounds enqueued behind a request for a giant step do nothing and do not count)
     unsigned long long* giant_mask;                  // per 8x8 tile: the seed's acceptable pixels, then its flood's (FloodBuffers::giant_mask)
     uint32_t* giant_parent;                          // per pixel: union-find parent of the in-tile components' first pixels (FloodBuffers::giant_parent)
 };
@@ -333,6 +344,32 @@ __device__ __forceinline__ uint64_t m_gt_f(float a, float b) { return __builtin_
 __device__ __forceinline__ bool lane_of(uint64_t mask) { return __builtin_amdgcn_inverse_ballot_w64(mask); }
 __device__ __forceinline__ uint64_t uni64(uint64_t v) { return uni64((uint32_t)v, (uint32_t)(v >> 32)); }
 
+// A walk's set-up is a chain of dependent loads: arguments -> control block -> list entry -> the seed's words -> the words at
+// its pixel.  LR_PIN says "these values are in scalar registers HERE": every load that feeds one of them is issued before
+// this point and a single wait covers them all, instead of one wait per value where the compiler happens to place its use
+// (a short-circuit && between two loaded values is a wait, a branch and a second wait).  The first value named comes out of
+// the statement, and the code behind it goes on with it: that is what keeps the statement in its place.  (Not `volatile`:
+// to the compiler that would be a write to memory, and the loads behind it would leave the scalar unit.)
+#define LR_PIN3(a, b, c) asm("" : "+s"(a) : "s"(b), "s"(c))
+#define LR_PIN4(a, b, c, d) asm("" : "+s"(a) : "s"(b), "s"(c), "s"(d))
+#define LR_PIN5(a, b, c, d, e) asm("" : "+s"(a) : "s"(b), "s"(c), "s"(d), "s"(e))
+#define LR_PIN6(a, b, c, d, e, f) asm("" : "+s"(a) : "s"(b), "s"(c), "s"(d), "s"(e), "s"(f))
+#define LR_PIN7(a, b, c, d, e, f, g) asm("" : "+s"(a) : "s"(b), "s"(c), "s"(d), "s"(e), "s"(f), "s"(g))
+#define LR_PIN10(a, b, c, d, e, f, g, h, i, j) asm("" : "+s"(a) : "s"(b), "s"(c), "s"(d), "s"(e), "s"(f), "s"(g), "s"(h), "s"(i), "s"(j))
+// The arguments a walk reads before its first tile (the front of FloodArgs), in one round trip at the kernel's entry.  Returns
+// a token for the pin of the control block's words, which is what holds this one at the entry.
+__device__ __forceinline__ uint32_t walk_args(const FloodArgs& A) {
+    uint32_t token = 0u;
+    asm("" : "+s"(token) : "s"(A.ctrl), "s"(A.act_a), "s"(A.act_b), "s"(A.seed_rec), "s"(A.tier), "s"(A.log_len), "s"(A.label), "s"(A.dmask),
+        "s"(A.dx), "s"(A.dy), "s"(A.w), "s"(A.h), "s"(A.no_rest), "s"(A.big_cap), "s"(A.giant_hold), "s"(A.log_min_tiles),
+        "s"(A.log_seeds), "s"(A.log_use), "s"(A.log_max_len), "s"(A.log_walk_tiles), "s"(A.quiet), "s"(A.giant_step));
+    return token;
+}
+// byte `i` of a uniform array: the aligned word that holds it, so that the load can go through the scalar unit (which has
+// no byte loads) with the other words of its round trip.  (The arrays read this way are allocated with a word to spare.)
+__device__ __forceinline__ uint32_t ld8_word(const uint8_t* p, uint32_t i) { return reinterpret_cast<const uint32_t*>(p)[i >> 2]; }
+__device__ __forceinline__ uint32_t byte_of(uint32_t word, uint32_t i) { return (word >> ((i & 3u) * 8u)) & 0xFFu; }
+
 // kCtrlStaged: the frame's FIRST round is in progress with a window beyond the strongest quarter, and giant_many walks have been held back
 __device__ __forceinline__ bool giants_many(const uint32_t* ctrl, uint32_t giant_many) {
     const uint32_t n_seeds = uni(ctrl[kCtrlNSeeds]);
@@ -360,6 +397,9 @@ struct WalkState {
     uint32_t steps;  // frontier records popped (diagnostics)
     uint32_t fresh;  // partial-commit walk: pixels it turned from stamps into labels
     uint32_t blocker = 0xFFFFFFFFu;  // lowest seed whose stamp the walk's own stamps met (the second tier's walks: FloodArgs::blk)
+#ifdef LR_WALK_TIMING
+    uint64_t t_first = 0;  // s_memtime when the walk's first tile was requested (g_prologue_timing)
+#endif
 };
 
 // The walk works on 8x8 pixel tiles, one tile per step, one pixel per lane: the acceptance test of the
@@ -529,17 +569,21 @@ struct PushLane {
     bool spread;     // left/right edges: the byte runs down a column
     bool dl;         // lane carries a direction
 };
-__device__ __forceinline__ PushLane push_lane(int lane) {
+constexpr PushLane push_lane_values(int lane) {
     const int d = lane & 7;
     const int dy = (d < 2) ? (d == 0 ? -1 : 1) : (d < 4 ? 0 : (d < 6 ? -1 : 1));
     const int dx = (d < 2) ? 0 : ((d & 1) ? 1 : -1);
-    PushLane c;
+    PushLane c{};
     c.off = (uint32_t)(dy * 0x10000 + dx);
     c.shamt = (d < 4) ? 8u * (uint32_t)d : 32u + (uint32_t)(d - 4);
     c.msk = (d < 4) ? 0xFFu : 1u;
     c.sh = (uint32_t)((0x0007383F00070038ull >> (8 * d)) & 0xFFull);  // 56 0 7 0 63 56 7 0
     c.spread = d == 2 || d == 3;
     c.dl = lane < 8;
+    return c;
+}
+__device__ __forceinline__ PushLane push_lane(int lane) {
+    PushLane c = push_lane_values(lane);
     // keep them in registers: recomputing the selects inside the walk loop costs more than four VGPRs
     asm volatile("" : "+v"(c.off), "+v"(c.shamt), "+v"(c.msk), "+v"(c.sh));
     return c;
@@ -653,15 +697,15 @@ __device__ __forceinline__ void push8(SlabStore& S, Pending& P, WalkState& st, u
 // 16-23 the column to the left (y = 0..7), 24-31 the column to the right, 32-35 the corners (-1,-1) (8,-1)
 // (-1,8) (8,8).  A record is pushed to a neighbour tile only for ring pixels that are themselves acceptable and
 // touch a newly walked pixel, so no step is spent on a tile that nothing can enter.
-__device__ __forceinline__ void ring_xy(int lane, int& rx, int& ry) {
+constexpr void ring_xy(int lane, int& rx, int& ry) {
     const int g = lane >> 3, i = lane & 7;
     rx = (g == 0 || g == 1) ? i : (g == 2 ? -1 : (g == 3 ? 8 : ((i & 1) ? 8 : -1)));
     ry = (g == 0) ? -1 : (g == 1 ? 8 : ((g == 2 || g == 3) ? i : ((i & 2) ? 8 : -1)));
 }
 // in-tile pixels (bit = y*8+x) 8-adjacent to this lane's ring pixel
-__device__ __forceinline__ uint64_t ring_adjacency(int lane) {
+constexpr uint64_t ring_adjacency(int lane) {
     if (lane >= 36) return 0ull;
-    int rx, ry;
+    int rx = 0, ry = 0;
     ring_xy(lane, rx, ry);
     uint64_t m = 0ull;
     for (int dy = -1; dy <= 1; ++dy)
@@ -672,7 +716,7 @@ __device__ __forceinline__ uint64_t ring_adjacency(int lane) {
     return m;
 }
 // pixels of the tile (bit = y*8+x) that are 8-adjacent to this lane's pixel, and the pixel itself
-__device__ __forceinline__ uint64_t tile_neighbours(int lane) {
+constexpr uint64_t tile_neighbours(int lane) {
     const int lr = lane >> 3, lc = lane & 7;
     uint64_t m = 0ull;
     for (int dy = -1; dy <= 1; ++dy)
@@ -682,6 +726,68 @@ __device__ __forceinline__ uint64_t tile_neighbours(int lane) {
         }
     return m;
 }
+// The per-lane constants of a walk (they depend on nothing but the lane number: some 250 instructions of selects and loops when
+// every walk works them out for itself) as a table, built at compile time by the functions above: twelve words a lane, three
+// loads that are on their way while the walk's set-up waits for its seed.
+struct LaneConsts {
+    int rx, ry;       // ring_xy
+    bool ring_lane;   // the lane has a ring pixel
+    uint64_t adj;     // ring_adjacency
+    uint64_t nbr;     // tile_neighbours
+    PushLane pc;
+};
+struct LaneTable {
+    uint32_t w[64][12];  // nbr lo hi, adj lo hi | off, shamt, msk, sh | rx, ry, flags (1 ring lane, 2 spread, 4 direction lane), -
+};
+constexpr LaneTable make_lane_table() {
+    LaneTable t{};
+    for (int lane = 0; lane < 64; ++lane) {
+        const uint64_t nbr = tile_neighbours(lane), adj = ring_adjacency(lane);
+        const PushLane c = push_lane_values(lane);
+        int rx = 0, ry = 0;
+        ring_xy(lane, rx, ry);
+        uint32_t* w = t.w[lane];
+        w[0] = (uint32_t)nbr;
+        w[1] = (uint32_t)(nbr >> 32);
+        w[2] = (uint32_t)adj;
+        w[3] = (uint32_t)(adj >> 32);
+        w[4] = c.off;
+        w[5] = c.shamt;
+        w[6] = c.msk;
+        w[7] = c.sh;
+        w[8] = (uint32_t)rx;
+        w[9] = (uint32_t)ry;
+        w[10] = (lane < 36 ? 1u : 0u) | (c.spread ? 2u : 0u) | (c.dl ? 4u : 0u);
+        w[11] = 0u;
+    }
+    return t;
+}
+__device__ const LaneTable g_lane_table = make_lane_table();
+struct LaneWords {
+    uint4 a, b, c;
+};
+__device__ __forceinline__ LaneWords lane_words(int lane) {
+    const uint4* rec = reinterpret_cast<const uint4*>(g_lane_table.w[lane]);
+    return LaneWords{rec[0], rec[1], rec[2]};
+}
+__device__ __forceinline__ LaneConsts lane_consts(const LaneWords& W) {
+    const uint4 a = W.a, b = W.b, c = W.c;
+    LaneConsts K;
+    K.nbr = ((uint64_t)a.y << 32) | a.x;
+    K.adj = ((uint64_t)a.w << 32) | a.z;
+    K.pc.off = b.x;
+    K.pc.shamt = b.y;
+    K.pc.msk = b.z;
+    K.pc.sh = b.w;
+    K.rx = (int)c.x;
+    K.ry = (int)c.y;
+    K.ring_lane = (c.z & 1u) != 0u;
+    K.pc.spread = (c.z & 2u) != 0u;
+    K.pc.dl = (c.z & 4u) != 0u;
+    return K;
+}
+__device__ __forceinline__ LaneConsts lane_consts(int lane) { return lane_consts(lane_words(lane)); }
+
 // What one lane holds of a frontier record before it is processed.  For a tile the wave already knows, the
 // table answers (V, A, ring) and no memory is touched; otherwise the lane's pixel of the tile and its pixel of
 // the surrounding ring are loaded.
@@ -787,6 +893,18 @@ __device__ __forceinline__ TileFetch fetch_tile(const FloodArgs& A, const Store&
 // cycle; every reading costs some 150 itself) [2] waiting for the tile's pixels, [3] closure, [4] table update,
 // [5] push, [6] pop, lookup and issue of the next loads; [7] steps that found their tile in the table.
 __device__ unsigned long long g_walk_timing[8];
+// What a walk costs around its steps, summed over ALL first-tier walks of a round that reach their stamps: [0] walks, then
+// s_memtime ticks [1] from the kernel's entry (the list entry's turn in the `rest` launch) to the request for the first tile's
+// pixels, [2] from there to the end of the last step, [3] stamps, log and the seed's words; [4] list entries that ended before
+// a first tile (dead at their pixel, finished, outside the window, handed on unwalked) and [5] their ticks; [6] workgroups past
+// the end of the list and [7] their ticks.  (64 copies, one per blockIdx.x & 63: a round's forty thousand walks would
+// queue up on one address.)
+__device__ unsigned long long g_prologue_timing[64][8];
+struct WalkClock {
+    uint64_t entry, first, walked, stamped;
+};
+#define LR_CLOCK_PARAM , WalkClock& clk
+#define LR_CLOCK_ARG , clk
 #define LR_TICK(i)                                        \
     {                                                     \
         const uint64_t t_ = __builtin_amdgcn_s_memtime(); \
@@ -795,6 +913,8 @@ __device__ unsigned long long g_walk_timing[8];
     }
 #else
 #define LR_TICK(i)
+#define LR_CLOCK_PARAM
+#define LR_CLOCK_ARG
 #endif
 
 // kMode 0 explores (acceptance = direction mask and response; a seed that already owns pixels -- `own`, see
@@ -803,20 +923,21 @@ __device__ unsigned long long g_walk_timing[8];
 // stamps it reaches into labels; `dmask_rw` is the direction mask it clears there.
 template <class Store, int kMode = 0>
 __device__ int walk(const FloodArgs& A, uint32_t k, int b, float thr, float sn, float cs, Store& S, Pending& P,
-                    WalkState& st, int lane, bool own = false, uint8_t* dmask_rw = nullptr, uint32_t tile_cap = 0xFFFFFFFFu,
-                    uint32_t wide_tiles = 0xFFFFFFFFu, uint32_t wide_front = 0xFFFFFFFFu) {
+                    WalkState& st, int lane, const LaneConsts& K, bool own = false, uint8_t* dmask_rw = nullptr,
+                    uint32_t tile_cap = 0xFFFFFFFFu, uint32_t wide_tiles = 0xFFFFFFFFu, uint32_t wide_front = 0xFFFFFFFFu) {
     const uint32_t mine = kMarkBit | k;
     const int lr = lane >> 3, lc = lane & 7;
-    int rx, ry;
-    ring_xy(lane, rx, ry);
-    const bool ring_lane = lane < 36;
-    const uint64_t adj = ring_adjacency(lane);
-    uint64_t nbr = tile_neighbours(lane);
+    const int rx = K.rx, ry = K.ry;
+    const bool ring_lane = K.ring_lane;
+    const uint64_t adj = K.adj;
+    uint64_t nbr = K.nbr;
     asm volatile("" : "+v"(nbr));  // a per-lane constant: keep it in registers
     if (st.head == st.tail) return 0;
     const uint32_t tile_limit = min(S.hash_limit(), tile_cap);
     if ((st.tail - st.head) + 8u > S.ring_cap() || st.ntiles + 2u > tile_limit) return 1;
-    const PushLane pc = push_lane(lane);
+    PushLane pc = K.pc;
+    // keep them in registers: recomputing the selects inside the walk loop costs more than four VGPRs
+    asm volatile("" : "+v"(pc.off), "+v"(pc.shamt), "+v"(pc.msk), "+v"(pc.sh));
     const uint32_t bin_bit = 1u << b;
     Forward fw;
     fw.valid = false;
@@ -824,6 +945,9 @@ __device__ int walk(const FloodArgs& A, uint32_t k, int b, float thr, float sn, 
     G.off = (uint32_t)(lr * A.w + lc);
     G.roff = (uint32_t)(ry * A.w + rx);
     asm volatile("" : "+v"(G.off), "+v"(G.roff));
+#ifdef LR_WALK_TIMING
+    if (st.t_first == 0) st.t_first = __builtin_amdgcn_s_memtime();
+#endif
     TileFetch cur = fetch_tile<kMode>(A, S, st.head, lr, lc, rx, ry, ring_lane, fw, G, own);
 #ifdef LR_WALK_TIMING
     uint64_t tacc[5] = {0, 0, 0, 0, 0}, tlast = __builtin_amdgcn_s_memtime();
@@ -996,22 +1120,41 @@ __device__ __forceinline__ void save_log(const FloodArgs& A, uint32_t k, const L
 // One seed's exploration by one wavefront (see walk).  A walk that outgrows the store is handed to the second tier
 // (big_list) when there is one this round, and goes on in a slab otherwise.
 __device__ __forceinline__ void explore_seed(const FloodArgs& A, const BinTrig& trig, uint32_t k, LdsStore& L, Pending& P,
-                                             uint32_t* __restrict__ big_list, int lane, uint32_t t1_tiles) {
-    const int s = (int)uni((uint32_t)A.seed_idx[k]);
-    const int b = (int)uni((uint32_t)A.seed_bin[k]);
-    const float thr = __uint_as_float(uni(__float_as_uint(A.seed_thr[k])));
-    const float sn = trig.st[b], cs = trig.ct[b];
-    // the four values at the seed pixel in one round trip (most seeds of a late round end right here)
-    const uint32_t seed_label = A.label[s];
-    const uint32_t seed_mask = A.dmask[s];
-    const float seed_dx = A.dx[s], seed_dy = A.dy[s];
+                                             uint32_t* __restrict__ big_list, int lane, uint32_t t1_tiles, bool staged LR_CLOCK_PARAM) {
+    // The seed's words in one round trip: its record (index, bin, threshold), its tier marks and the length of its log ...
+    const uint4 rec = A.seed_rec[k];
+    const uint32_t tier_w = ld8_word(A.tier, k);
+    uint32_t log_w = 0u;
+    if (A.log_min_tiles != 0xFFFFFFFFu && k < A.log_seeds) log_w = A.log_len[k];
+    uint32_t s_u = uni(rec.x);
+    const uint32_t b_u = uni(rec.y), thr_u = uni(rec.z), tier_u = uni(tier_w);
+    log_w = uni(log_w);
+    LR_PIN5(s_u, b_u, thr_u, tier_u, log_w);
+    // ... and the per-lane constants of the walk, on their way from here (a vector load: nothing waits for it before the walk)
+    const LaneConsts K = lane_consts(lane);
+    const int s = (int)s_u, b = (int)b_u;
+    const float thr = __uint_as_float(thr_u);
+    const uint32_t tier = byte_of(tier_u, k);
+    // the four values at the seed pixel and the bin's sine and cosine in one round trip (most seeds of a late round end right here)
+    uint32_t seed_label = uni(A.label[s]);
+    const uint32_t mask_u = uni(ld8_word(A.dmask, (uint32_t)s));
+    const uint32_t dx_u = uni(__float_as_uint(A.dx[s])), dy_u = uni(__float_as_uint(A.dy[s]));
+    const uint32_t sn_u = uni(__float_as_uint(trig.st[b])), cs_u = uni(__float_as_uint(trig.ct[b]));
+    LR_PIN6(seed_label, mask_u, dx_u, dy_u, sn_u, cs_u);
+    const float sn = __uint_as_float(sn_u), cs = __uint_as_float(cs_u);
+    const uint32_t seed_mask = byte_of(mask_u, (uint32_t)s);
+    const float seed_dx = __uint_as_float(dx_u), seed_dy = __uint_as_float(dy_u);
     // A seed whose pixel carries its OWN index has committed a part of its flood in an earlier round (partial commit,
     // flood_partial_commit_kernel) and explores on from there: its walk passes through the pixels labelled with its index.
+    // (the tests are on loaded values, all the same in every lane: `&`, not `&&`, so that none of them becomes a branch in
+    // front of another's load)
     const bool own = seed_label == k;
-    if (seed_label < kMarkBit && !own) return;  // claimed by an earlier flood: dead (the survivors pass takes it off the list)
-    // (tier bit 3: finished by a giant step between the rounds -- the survivors pass of this round takes it off the list)
-    if ((uni((uint32_t)A.tier[k]) & 8u) != 0u) return;
-    if (!own && !(((seed_mask >> b) & 1) && directional(seed_dx, seed_dy, sn, cs) > thr)) {
+    const bool dead = (seed_label < kMarkBit) & !own;  // claimed by an earlier flood (the survivors pass takes it off the list)
+    const bool finished = (tier & 8u) != 0u;           // by a giant step between the rounds (the survivors pass of this round takes it off the list)
+    const bool in_mask = ((seed_mask >> b) & 1u) != 0u, above = directional(seed_dx, seed_dy, sn, cs) > thr;
+    const bool accepts = in_mask & above;
+    if (dead | finished) return;
+    if (!own & !accepts) {
         if (lane == 0) A.flags[k] = kFlagSelfFail;  // flood() accepts nothing, not even the seed
         return;
     }
@@ -1021,11 +1164,10 @@ __device__ __forceinline__ void explore_seed(const FloodArgs& A, const BinTrig& 
     // rarely below 190 tiles from above 1500 px)
     // (not on a frame that went on staged after its first round -- kCtrlStaged: what a weak seed reached then says little
     // about what it reaches once the stronger seeds have committed)
-    const bool outgrown = A.big_cap != 0u && (uni((uint32_t)A.tier[k]) & 1u) != 0u && uni(A.ctrl[kCtrlStaged]) == 0u;
+    const bool outgrown = A.big_cap != 0u && (tier & 1u) != 0u && !staged;
     // A seed with a log (save_log) walks a few tiles only: most footprints have shrunk to a handful of tiles by their second
     // round, and a short walk is cheaper than the records of a long one.  If the walk is not over by then, the seed goes
     // on this round's list of flood_rewalk_kernel, which runs behind the exploration (nothing is stamped yet).
-    const uint32_t log_w = (A.log_min_tiles != 0xFFFFFFFFu && k < A.log_seeds) ? uni(A.log_len[k]) : 0u;
     const uint32_t log_n = log_w & ~kLogShrunk;
     const bool has_log = log_n != 0u && log_n <= A.log_max_len && A.log_use != 0u;
     const bool skip_first = outgrown && !has_log;
@@ -1041,7 +1183,7 @@ __device__ __forceinline__ void explore_seed(const FloodArgs& A, const BinTrig& 
             // (a log that the last round has already cut down to the footprint of then, and that is still twice the budget
             // long, goes on the list at once: the walk would only find out the same, 12 steps later)
             const bool direct = (log_w & kLogShrunk) != 0u && log_n >= 2u * A.log_walk_tiles;
-            if (!direct) rc = walk(A, k, b, thr, sn, cs, L, P, st, lane, own, nullptr, A.log_walk_tiles);
+            if (!direct) rc = walk(A, k, b, thr, sn, cs, L, P, st, lane, K, own, nullptr, A.log_walk_tiles);
             if (rc != 0) {
                 uint32_t pos = 0;
                 if (lane == 0) pos = atomicAdd(&A.ctrl[kCtrlNRewalk], 1u);
@@ -1053,7 +1195,7 @@ __device__ __forceinline__ void explore_seed(const FloodArgs& A, const BinTrig& 
             }
         }
         if (rc != 0)  // (from the start, or from where the budgeted walk stands: the list was full)
-            rc = walk(A, k, b, thr, sn, cs, L, P, st, lane, own, nullptr, hand_over ? t1_tiles : 0xFFFFFFFFu,
+            rc = walk(A, k, b, thr, sn, cs, L, P, st, lane, K, own, nullptr, hand_over ? t1_tiles : 0xFFFFFFFFu,
                       hand_over ? A.wide_tiles : 0xFFFFFFFFu, hand_over ? A.wide_front : 0xFFFFFFFFu);
     }
     if (rc != 0 && A.big_cap == 0u && A.quiet != 0u) {
@@ -1106,7 +1248,7 @@ __device__ __forceinline__ void explore_seed(const FloodArgs& A, const BinTrig& 
             P.pt[lane] = 0u;
             const int sr = s / A.w, sc = s - sr * A.w;
             L.put(0u, ((uint32_t)(sr >> 3) << 16) | (uint32_t)(sc >> 3), 1ull << ((sr & 7) * 8 + (sc & 7)));
-            rc = walk(A, k, b, thr, sn, cs, L, P, st, lane, own);
+            rc = walk(A, k, b, thr, sn, cs, L, P, st, lane, K, own);
         }
         // second tier full this round: carry on in a slab from the state reached -- if this is the lowest active seed; any
         // other is held back like a walk that outgrows the second tier's table (see kCtrlLowest): with eight thousand walks in
@@ -1124,7 +1266,14 @@ __device__ __forceinline__ void explore_seed(const FloodArgs& A, const BinTrig& 
             return;
         }
     }
+#ifdef LR_WALK_TIMING
+    clk.first = st.t_first;
+    clk.walked = __builtin_amdgcn_s_memtime();
+#endif
     stamp_footprint(A, k, L, st, lane);
+#ifdef LR_WALK_TIMING
+    clk.stamped = __builtin_amdgcn_s_memtime();
+#endif
     // the footprint's records for the seed's later rounds (flood_rewalk_kernel); one log per seed and frame: the records of
     // ANY finished walk of the seed hold its present footprint
     if (rc == 0 && st.ntiles >= A.log_min_tiles && st.ntiles <= A.log_max_len && k < A.log_seeds && uni(A.log_len[k]) == 0u)
@@ -1156,7 +1305,7 @@ __device__ __forceinline__ void explore_seed(const FloodArgs& A, const BinTrig& 
                     G.update(slot, key - 1u, ((uint64_t)L.hv1[i] << 32) | L.hv0[i]);
                 }
             }
-            rc = walk(A, k, b, thr, sn, cs, G, P, st, lane, own);
+            rc = walk(A, k, b, thr, sn, cs, G, P, st, lane, K, own);
         }
         if (rc != 0 && lane == 0) {
             A.flags[k] = kFlagIncomplete;
@@ -1219,23 +1368,51 @@ __device__ __forceinline__ void explore_body(const FloodArgs& A, const BinTrig& 
     asm volatile("" ::"v"(&s_pad[threadIdx.x]) : "memory");
 #endif
     const int lane = threadIdx.x & 63;
-    if (giant_pending(A)) return;
-    const uint32_t* __restrict__ act = act_now(A);
-    const uint32_t n_act = uni(A.ctrl[kCtrlNAct]), window = uni(A.ctrl[kCtrlWindow]);
+#ifdef LR_WALK_TIMING
+    WalkClock clk{__builtin_amdgcn_s_memtime(), 0, 0, 0};
+    const auto clock_out = [&]() {  // (an entry's sums: see g_prologue_timing)
+        const uint64_t now = __builtin_amdgcn_s_memtime();
+        unsigned long long* t = g_prologue_timing[blockIdx.x & 63u];
+        if (lane == 0) {
+            if (clk.first != 0 && clk.stamped != 0) {
+                atomicAdd(&t[0], 1ull);
+                atomicAdd(&t[1], (unsigned long long)(clk.first - clk.entry));
+                atomicAdd(&t[2], (unsigned long long)(clk.walked - clk.first));
+                atomicAdd(&t[3], (unsigned long long)(clk.stamped - clk.walked));
+            } else {
+                atomicAdd(&t[4], 1ull);
+                atomicAdd(&t[5], (unsigned long long)(now - clk.entry));
+            }
+        }
+        clk = WalkClock{now, 0, 0, 0};
+    };
+#endif
+    // Five round trips to the first tile: the arguments; the control block; the list entry; the seed's words; the words at
+    // its pixel (explore_seed).  A workgroup past the end of the list leaves after the second.
+    const uint32_t args = walk_args(A);
+    const uint32_t* ctrl = A.ctrl;
+    uint32_t c_giant = uni(ctrl[kCtrlGiantStep]);
+    const uint32_t c_rounds = uni(ctrl[kCtrlRounds]), n_act = uni(ctrl[kCtrlNAct]), window = uni(ctrl[kCtrlWindow]),
+                   c_seen = uni(ctrl[kCtrlBigSeen]), c_nbig = uni(ctrl[kCtrlNBig]), lowest = uni(ctrl[kCtrlLowest]),
+                   c_staged = uni(ctrl[kCtrlStaged]);
+    const uint32_t grid = gridDim.x;  // (an argument too, of the launch: behind a branch it is a round trip of its own)
+    LR_PIN10(c_giant, c_rounds, n_act, window, c_seen, c_nbig, lowest, c_staged, args, grid);
+    if (c_giant != 0u) return;  // (giant_pending)
+    const uint32_t* __restrict__ act = (c_rounds & 1u) ? A.act_b : A.act_a;  // (act_now)
+    const bool staged = c_staged != 0u;
     // A frame with many LONG walks (sixteen beyond what the first tier's table holds: natural images, frames of long bars)
     // hands its walks over earlier from the next round on -- at kRegionalTiles = 32 tiles instead of 190: the first tier's rounds last as
     // long as its longest walk, and the second tier has 512 teams to take the walks side by side (with 128 teams the long
     // bars' thousands of thin walks queued up behind each other and the same rule cost that frame 0.5 ms; with 512 it
     // gains 0.3).  The synthetic bench frames never get there (0-7 long walks), and handing THEIR walks over early costs
     // them 0.3-0.9 ms: the tiers' kernels run one after the other, and a thin walk gains nothing from a team.
-    const uint32_t t1_usual = uni(A.ctrl[kCtrlBigSeen]) != 0u ? kRegionalTiles : 0xFFFFFFFFu;
+    const uint32_t t1_usual = c_seen != 0u ? kRegionalTiles : 0xFFFFFFFFu;
     // The second tier's list is full already when this workgroup starts -- eight thousand long walks in this round: a frame of
     // overlapping giants, a noiseless gradient whose every pixel is a seed -- so a walk that outgrows this tier will be held
     // back whatever its length (explore_seed): it is held at kFullTiles tiles instead of walking on to the table's 190 (radial
     // gradient at 1080p, 78 704 seeds: first round 45 -> 11 ms).  Read HERE, with the other words of the control block: the
     // same read in front of every walk cost the bench frames' first round 1.1 ms (0.3 -> 1.4).
-    const bool tier2_full = A.giant_hold != 0u && A.big_cap != 0u && uni(A.ctrl[kCtrlNBig]) >= A.big_cap;
-    const uint32_t lowest = uni(A.ctrl[kCtrlLowest]);
+    const bool tier2_full = A.giant_hold != 0u && A.big_cap != 0u && c_nbig >= A.big_cap;
     LdsStore L{s_ring[0], s_ring[1], s_ring[2], s_hash[0], s_hash[1], s_hash[2], s_ord};
     Pending P{s_pend[0], s_pend[1]};
     // The list is walked from its end: the first round's list is in seed order, strongest first, and the longest
@@ -1243,20 +1420,32 @@ __device__ __forceinline__ void explore_body(const FloodArgs& A, const BinTrig& 
     // alongside the mass of short walks instead of after it.
     if (!kRest) {
         const uint32_t ai = uni(blockIdx.x);
+#ifdef LR_WALK_TIMING
+        if (ai >= n_act && lane == 0) {
+            atomicAdd(&g_prologue_timing[blockIdx.x & 63u][6], 1ull);
+            atomicAdd(&g_prologue_timing[blockIdx.x & 63u][7], (unsigned long long)(__builtin_amdgcn_s_memtime() - clk.entry));
+        }
+#endif
         if (ai >= n_act) return;
         // (a round without a `rest` launch whose list is longer than its grid walks the FIRST entries: the survivors pass
         // that wrote the list has put a barrier at the lowest seed behind them -- enqueue_round)
-        const bool fwd = A.no_rest != 0u && n_act > gridDim.x;
+        const bool fwd = A.no_rest != 0u && n_act > grid;
         const uint32_t k = uni(act[!fwd ? n_act - 1u - ai : ai]);
         if (k >= window) return;  // not yet in the staged window (stays active)
         const uint32_t t1_tiles = (tier2_full && k != lowest) ? min(t1_usual, kFullTiles) : t1_usual;
-        explore_seed(A, trig, k, L, P, big_list, lane, t1_tiles);
+        explore_seed(A, trig, k, L, P, big_list, lane, t1_tiles, staged LR_CLOCK_ARG);
+#ifdef LR_WALK_TIMING
+        clock_out();
+#endif
     } else {
-        for (uint32_t ai = first + uni(blockIdx.x); ai < n_act; ai += gridDim.x) {
+        for (uint32_t ai = first + uni(blockIdx.x); ai < n_act; ai += grid) {
             const uint32_t k = uni(act[n_act - 1u - ai]);
             if (k >= window) continue;
             const uint32_t t1_tiles = (tier2_full && k != lowest) ? min(t1_usual, kFullTiles) : t1_usual;
-            explore_seed(A, trig, k, L, P, big_list, lane, t1_tiles);
+            explore_seed(A, trig, k, L, P, big_list, lane, t1_tiles, staged LR_CLOCK_ARG);
+#ifdef LR_WALK_TIMING
+            clock_out();
+#endif
         }
     }
 }
@@ -1588,8 +1777,13 @@ __global__ __launch_bounds__(64 * kTeamWaves) void flood_explore_team_kernel(Flo
                                                                              const uint32_t* __restrict__ big_list) {
     extern __shared__ uint32_t s_team[];
     const int lane = threadIdx.x & 63, wave = (int)uni(threadIdx.x >> 6);
-    if (uni(A.ctrl[kCtrlNAct]) == 0u || giant_pending(A)) return;  // a round enqueued past the end (or past a stall: the listed seeds are the ordered tail's)
-    const uint32_t n_big_raw = uni(A.ctrl[kCtrlNBig]);
+    // (the round trips of an entry, as in explore_body: arguments and control block once; then the entry, the seed's record
+    // with the head of what the first tier handed over, the words at its pixel)
+    const uint32_t args = walk_args(A);
+    uint32_t c_nact = uni(A.ctrl[kCtrlNAct]);
+    const uint32_t c_giant = uni(A.ctrl[kCtrlGiantStep]), n_big_raw = uni(A.ctrl[kCtrlNBig]);
+    LR_PIN4(c_nact, c_giant, n_big_raw, args);
+    if (c_nact == 0u || c_giant != 0u) return;  // a round enqueued past the end (or past a stall: the listed seeds are the ordered tail's), or behind a request for a giant step
     const uint32_t n_big = n_big_raw < A.big_cap ? n_big_raw : A.big_cap;
     uint32_t* ring = s_team;
     uint32_t* hash = ring + 3 * kRingTeam;
@@ -1599,16 +1793,27 @@ __global__ __launch_bounds__(64 * kTeamWaves) void flood_explore_team_kernel(Flo
     TeamStore S{ring, ring + kRingTeam, ring + 2 * kRingTeam, hash, hash + kHashBig, hash + 2 * kHashBig, ord, sh};
     for (uint32_t ai = uni(blockIdx.x); ai < n_big; ai += gridDim.x) {
         const uint32_t k = uni(big_list[ai]);
-        const int s = (int)uni((uint32_t)A.seed_idx[k]);
-        const int b = (int)uni((uint32_t)A.seed_bin[k]);
-        const float thr = __uint_as_float(uni(__float_as_uint(A.seed_thr[k])));
-        const float sn = trig.st[b], cs = trig.ct[b];
+        // what the first tier handed over with this entry (A.big_cap entries at most, so ai is its position in the list)
+        const uint32_t* hb = A.handover + (size_t)ai * kFloodHandWords;
+        const uint4 rec = A.seed_rec[k];
+        uint32_t s_u = uni(rec.x);
+        const uint32_t b_u = uni(rec.y), thr_u = uni(rec.z), hb_tiles = uni(hb[0]), hb_recs = uni(hb[1]);
+        LR_PIN5(s_u, b_u, thr_u, hb_tiles, hb_recs);
+        const int s = (int)s_u, b = (int)b_u;
+        const float thr = __uint_as_float(thr_u);
         // (the checks of explore_seed again: the first tier passed them in this round, on the same labels)
-        const uint32_t seed_label = uni(A.label[s]);
+        uint32_t seed_label = uni(A.label[s]);
+        const uint32_t mask_u = uni(ld8_word(A.dmask, (uint32_t)s));
+        const uint32_t dx_u = uni(__float_as_uint(A.dx[s])), dy_u = uni(__float_as_uint(A.dy[s]));
+        const uint32_t sn_u = uni(__float_as_uint(trig.st[b])), cs_u = uni(__float_as_uint(trig.ct[b]));
+        LR_PIN6(seed_label, mask_u, dx_u, dy_u, sn_u, cs_u);
+        const float sn = __uint_as_float(sn_u), cs = __uint_as_float(cs_u);
         const bool own = seed_label == k;
-        if (seed_label < kMarkBit && !own) continue;
-        if (!own && !(((uni((uint32_t)A.dmask[s]) >> b) & 1u) &&
-                      directional(__uint_as_float(uni(__float_as_uint(A.dx[s]))), __uint_as_float(uni(__float_as_uint(A.dy[s]))), sn, cs) > thr)) {
+        const bool in_mask = ((byte_of(mask_u, (uint32_t)s) >> b) & 1u) != 0u;
+        const bool above = directional(__uint_as_float(dx_u), __uint_as_float(dy_u), sn, cs) > thr;
+        const bool accepts = in_mask & above;
+        if ((seed_label < kMarkBit) & !own) continue;
+        if (!own & !accepts) {
             if (threadIdx.x == 0) A.flags[k] = kFlagSelfFail;
             continue;
         }
@@ -1626,9 +1831,7 @@ __global__ __launch_bounds__(64 * kTeamWaves) void flood_explore_team_kernel(Flo
             }
             continue;
         }
-        // what the first tier handed over with this entry (A.big_cap entries at most, so ai is its position in the list)
-        const uint32_t* hb = A.handover + (size_t)ai * kFloodHandWords;
-        const uint32_t h_recs = min(uni(hb[1]), kHandRecs);
+        const uint32_t h_recs = min(hb_recs, kHandRecs);
         uint32_t begin = 0u, my_steps = 0u;
         __syncthreads();  // the previous seed's table is no longer read
         for (int i = (int)threadIdx.x; i < kHashBig; i += 64 * kTeamWaves) {
@@ -1636,7 +1839,7 @@ __global__ __launch_bounds__(64 * kTeamWaves) void flood_explore_team_kernel(Flo
             S.hv0[i] = 0u;
             S.hv1[i] = 0u;
         }
-        const uint32_t h_tiles = min(uni(hb[0]), kHandTiles);
+        const uint32_t h_tiles = min(hb_tiles, kHandTiles);
         const uint32_t first_level = h_recs ? h_recs : 1u;
         __syncthreads();  // (table cleared)
         if (h_recs) {
@@ -1907,20 +2110,25 @@ __global__ __launch_bounds__(kThreads) void flood_rewalk_kernel(FloodArgs A, con
     __shared__ uint32_t s_nnodes, s_over, s_blocked, s_cnt, s_seed_node, s_nout, s_nedges;
     const int lane = threadIdx.x & 63, wave = (int)uni(threadIdx.x >> 6);
     const int lr = lane >> 3, lc = lane & 7;
-    if (uni(A.ctrl[kCtrlNAct]) == 0u || giant_pending(A)) return;  // a round enqueued past the end, or past a stall
-    const uint32_t n_list = min(uni(A.ctrl[kCtrlNRewalk]), kBigCap);
-    const uint32_t window = uni(A.ctrl[kCtrlWindow]);
+    // (the control block's words in one round trip, and a list entry's words in one: see explore_body)
+    uint32_t c_nact = uni(A.ctrl[kCtrlNAct]);
+    const uint32_t c_giant = uni(A.ctrl[kCtrlGiantStep]), c_nrewalk = uni(A.ctrl[kCtrlNRewalk]), window = uni(A.ctrl[kCtrlWindow]);
+    LR_PIN4(c_nact, c_giant, c_nrewalk, window);
+    if (c_nact == 0u || c_giant != 0u) return;  // a round enqueued past the end, or past a stall, or behind a request for a giant step
+    const uint32_t n_list = min(c_nrewalk, kBigCap);
     for (uint32_t ai = uni(blockIdx.x); ai < n_list; ai += gridDim.x) {
         const uint32_t k = uni(list[ai]);
         if (k >= window) continue;  // (not walked at all, like every seed above the window)
-        const uint32_t n = uni(A.log_len[k]) & ~kLogShrunk;
+        uint32_t len_w = uni(A.log_len[k]);
+        const uint32_t s = uni(A.seed_rec[k].x), log_off = uni(A.log_off[k]);
+        LR_PIN3(len_w, s, log_off);
+        const uint32_t n = len_w & ~kLogShrunk;
         if (n < min_len || n > (uint32_t)kTiles) continue;  // (another instance of this kernel takes it)
-        const uint32_t s = uni((uint32_t)A.seed_idx[k]);
         const uint32_t seed_label = uni(A.label[s]);
         const bool own = seed_label == k;
         if (seed_label < kMarkBit && !own) continue;  // dead: the survivors pass takes it off the list
         const uint32_t mine = kMarkBit | k;
-        uint32_t* rec = A.log_buf + (size_t)uni(A.log_off[k]) * 3u;
+        uint32_t* rec = A.log_buf + (size_t)log_off * 3u;
         __syncthreads();  // (the previous seed's tables are no longer read)
 #ifdef LR_REWALK_TIMING
         uint64_t tlast = __builtin_amdgcn_s_memtime();
@@ -2244,17 +2452,28 @@ __global__ __launch_bounds__(64) void flood_partial_commit_kernel(FloodArgs A, u
     __shared__ uint32_t s_pend[2][kPend];
     __shared__ uint8_t s_ord[kHashT];
     const int lane = threadIdx.x & 63;
-    if (giant_pending(A)) return;
-    const uint32_t* __restrict__ act = act_now(A);
-    const uint32_t n_act = uni(A.ctrl[kCtrlNAct]), window = uni(A.ctrl[kCtrlWindow]), barrier = uni(A.ctrl[kCtrlBarrier]);
+    // (the round trips of a list entry, as in explore_body: arguments and control block once; then the entry, the seed's
+    // words, the label at its pixel)
+    const uint32_t args = walk_args(A);
+    const uint32_t* ctrl = A.ctrl;
+    uint32_t c_giant = uni(ctrl[kCtrlGiantStep]);
+    const uint32_t c_rounds = uni(ctrl[kCtrlRounds]), n_act = uni(ctrl[kCtrlNAct]), window = uni(ctrl[kCtrlWindow]),
+                   barrier = uni(ctrl[kCtrlBarrier]);
+    const uint32_t grid = gridDim.x;  // (an argument too, of the launch: read in the loop it is a round trip per entry)
+    LR_PIN7(c_giant, c_rounds, n_act, window, barrier, args, grid);
+    if (c_giant != 0u) return;  // (giant_pending)
+    const uint32_t* __restrict__ act = (c_rounds & 1u) ? A.act_b : A.act_a;  // (act_now)
+    LaneWords W = lane_words(lane);  // (on their way while the first entry's words are fetched: looked at in front of the walk)
     LdsStore L{s_ring[0], s_ring[1], s_ring[2], s_hash[0], s_hash[1], s_hash[2], s_ord};
     Pending P{s_pend[0], s_pend[1]};
-    for (uint32_t ai = uni(blockIdx.x); ai < n_act; ai += gridDim.x) {
+    for (uint32_t ai = uni(blockIdx.x); ai < n_act; ai += grid) {
         const uint32_t k = uni(act[ai]);
         if (k >= window || k >= barrier) continue;
-        const uint32_t fl = uni(A.flags[k]);
-        if (uni(A.count[k]) == 0u || uni(A.blocked[k]) == 0u || (fl & (kFlagIncomplete | kFlagSelfFail))) continue;
-        const int s = (int)uni((uint32_t)A.seed_idx[k]);
+        uint32_t fl = uni(A.flags[k]);
+        const uint32_t cnt = uni(A.count[k]), blocked = uni(A.blocked[k]), s_u = uni(A.seed_rec[k].x);
+        LR_PIN4(fl, cnt, blocked, s_u);
+        if ((cnt == 0u) | (blocked == 0u) | ((fl & (kFlagIncomplete | kFlagSelfFail)) != 0u)) continue;
+        const int s = (int)s_u;
         const uint32_t seed_label = uni(A.label[s]);
         if (seed_label != (kMarkBit | k) && seed_label != k) continue;  // its own pixel is contested (or taken)
         for (int i = lane; i < LdsStore::kHashN; i += 64) L.hk[i] = 0u;
@@ -2262,7 +2481,9 @@ __global__ __launch_bounds__(64) void flood_partial_commit_kernel(FloodArgs A, u
         const int sr = s / A.w, sc = s - sr * A.w;
         L.put(0u, ((uint32_t)(sr >> 3) << 16) | (uint32_t)(sc >> 3), 1ull << ((sr & 7) * 8 + (sc & 7)));
         WalkState st{0u, 1u, 0u, 0u, false, 0u, 0u};
-        (void)walk<LdsStore, 1>(A, k, 0, 0.f, 0.f, 0.f, L, P, st, lane, false, dmask_rw);
+        asm volatile("" : "+v"(W.c.z));  // (keeps the first use of the table's words, and with it their wait, here)
+        const LaneConsts K = lane_consts(W);
+        (void)walk<LdsStore, 1>(A, k, 0, 0.f, 0.f, 0.f, L, P, st, lane, K, false, dmask_rw);
     }
 }
 
@@ -3092,6 +3313,17 @@ static void flood_debug_round(const FloodBuffers& B, const FloodFrame& F, uint32
         unsigned long long t[8], z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         (void)hipMemcpyFromSymbol(t, HIP_SYMBOL(g_walk_timing), sizeof(t));
         (void)hipMemcpyToSymbol(HIP_SYMBOL(g_walk_timing), z, sizeof(z));
+        unsigned long long p[64][8], q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        (void)hipMemcpyFromSymbol(p, HIP_SYMBOL(g_prologue_timing), sizeof(p));
+        for (int i = 0; i < 64; ++i)
+            for (int j = 0; j < 8; ++j) q[j] += p[i][j];
+        std::memset(p, 0, sizeof(p));
+        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_prologue_timing), p, sizeof(p));
+        if (q[0] + q[4] + q[6] > 0)
+            std::fprintf(stderr, "  first-tier walks that reached their stamps: %llu; mean s_memtime ticks: prologue %.0f, walk %.0f, epilogue %.0f; "
+                         "entries that ended before a first tile: %llu, mean %.0f ticks; workgroups past the list: %llu, mean %.0f ticks\n",
+                         q[0], q[0] ? (double)q[1] / q[0] : 0., q[0] ? (double)q[2] / q[0] : 0., q[0] ? (double)q[3] / q[0] : 0., q[4],
+                         q[4] ? (double)q[5] / q[4] : 0., q[6], q[6] ? (double)q[7] / q[6] : 0.);
         if (t[1] > 0)
             std::fprintf(stderr, "  walks of more than 100 steps: %llu, %llu steps (%llu of them on a known tile); s_memtime ticks per step: "
                          "wait for pixels %.1f, closure %.1f, table %.1f, push %.1f, pop + issue %.1f\n",
@@ -3209,6 +3441,7 @@ FloodArgs flood_args(const FloodBuffers& B, const FloodFrame& F, bool use_big) {
     A.seed_idx = F.seed_idx;
     A.seed_bin = F.seed_bin;
     A.seed_thr = F.seed_thr;
+    A.seed_rec = F.seed_rec;
     A.label = F.label;
     A.blocked = B.blocked;
     A.count = B.count;
@@ -3342,7 +3575,8 @@ void enqueue_round(const FloodBuffers& B, const FloodFrame& F, const FloodArgs& 
     // there no longer pays their launch -- 0.970 -> 0.935 ms over the four bench frames, same rounds; and the lanes of a batch
     // are better off with a launch less per late round: 9.81 -> 9.99 Gpix/s)
     if (B.partial_commits && index < kPartialRounds)
-        hipLaunchKernelGGL(flood_partial_commit_kernel, dim3(grid), dim3(64), 0, s, A, const_cast<uint8_t*>(F.dmask));
+        hipLaunchKernelGGL(flood_partial_commit_kernel, dim3(kPartialGrid ? std::min(grid, kPartialGrid) : grid), dim3(64), 0, s, A,
+                           const_cast<uint8_t*>(F.dmask));
     hipLaunchKernelGGL(flood_commit_pixels_kernel, dim3(pix_blocks), dim3(256), 0, s, A, F.label, npix,
                        const_cast<uint8_t*>(F.dmask));
     hipLaunchKernelGGL(flood_survivors_kernel, dim3(seed_blocks), dim3(256), 0, s, A, B.state, F.seed_size);

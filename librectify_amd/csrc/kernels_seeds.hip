@@ -357,7 +357,7 @@ __global__ __launch_bounds__(256) void seed_rank_setup_kernel(const uint64_t* __
                                                               uint32_t cap, uint32_t L, const float* __restrict__ dx,
                                                               const float* __restrict__ dy, BinTrig trig, float trace_tolerance,
                                                               int32_t* __restrict__ seed_idx, int32_t* __restrict__ seed_bin,
-                                                              float* __restrict__ seed_thr) {
+                                                              float* __restrict__ seed_thr, uint4* __restrict__ seed_rec) {
     const uint32_t g = blockIdx.x * 256 + threadIdx.x;
     const uint32_t n = min(*n_ptr, cap);
     if (g >= n) return;
@@ -398,14 +398,17 @@ __global__ __launch_bounds__(256) void seed_rank_setup_kernel(const uint64_t* __
     const float v = directional(dx[idx], dy[idx], trig.st[bin], trig.ct[bin]);
     seed_idx[rank] = (int32_t)idx;
     seed_bin[rank] = bin;
-    seed_thr[rank] = (1 - trace_tolerance) * v;
+    const float thr = (1 - trace_tolerance) * v;
+    seed_thr[rank] = thr;
+    // the same three words side by side, for the flood's walks: one load where the arrays are three
+    seed_rec[rank] = make_uint4(idx, (uint32_t)bin, __float_as_uint(thr), 0u);
 }
 
 }  // namespace
 
 // keys / keys_alt: two buffers of at least `cap` keys; the unsorted keys are in `keys`
 int launch_seed_order(uint64_t* keys, uint64_t* keys_alt, const uint32_t* n_seeds, uint32_t cap, const float* dx, const float* dy,
-                      BinTrig trig, float trace_tolerance, int32_t* seed_idx, int32_t* seed_bin, float* seed_thr, hipStream_t s) {
+                      BinTrig trig, float trace_tolerance, int32_t* seed_idx, int32_t* seed_bin, float* seed_thr, uint4* seed_rec, hipStream_t s) {
     if (cap == 0) return 0;
     const uint32_t runs0 = (cap + kRun0 - 1) / kRun0;
     hipLaunchKernelGGL(seed_run_sort_kernel, dim3(runs0), dim3(kRunThreads), 0, s, keys, cap, n_seeds);
@@ -423,7 +426,7 @@ int launch_seed_order(uint64_t* keys, uint64_t* keys_alt, const uint32_t* n_seed
         runs = (runs + 1u) / 2u;
     }
     hipLaunchKernelGGL(seed_rank_setup_kernel, dim3((cap + 255) / 256), dim3(256), 0, s, cur, n_seeds, cap, L, dx, dy, trig,
-                       trace_tolerance, seed_idx, seed_bin, seed_thr);
+                       trace_tolerance, seed_idx, seed_bin, seed_thr, seed_rec);
     LR_HIP(hipGetLastError());
     return 0;
 }
