@@ -114,7 +114,7 @@ int ensure_prosac_buffers(lr_context* c, size_t n_lines, size_t n_pairs, size_t 
 // Stable argsort by weight, descending (reference utils.h:36-44 uses std::stable_sort with a > comparator).  The weights
 // are fourth powers (>= +0), so the order of their bit patterns is their order: three stable 11-bit counting passes over
 // the complemented bits, a fifth of std::stable_sort's time on 24 000 lines.  A NaN weight (a line through the peak
-// itself) has no place in that order: then the comparison sort decides, as before.
+// itself) has no place in that order: then the comparison sort decides, with the NaNs last in their own order.
 void stable_order_descending(const std::vector<float>& w, std::vector<int>& order) {
     const size_t n = w.size();
     order.resize(n);
@@ -122,7 +122,11 @@ void stable_order_descending(const std::vector<float>& w, std::vector<int>& orde
     for (size_t i = 0; i < n; ++i) plain = plain && w[i] >= 0.0f && !std::signbit(w[i]);  // (false for NaN and -0)
     if (!plain || n < 256) {
         for (size_t i = 0; i < n; ++i) order[i] = (int)i;
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return w[a] > w[b]; });
+        std::stable_sort(order.begin(), order.end(), [&](int a, int b) {  // NaN last, stably: a strict weak ordering
+            if (std::isnan(w[a])) return false;
+            if (std::isnan(w[b])) return true;
+            return w[a] > w[b];
+        });
         return;
     }
     std::vector<uint32_t> key(n), key2(n);

@@ -508,7 +508,11 @@ __global__ __launch_bounds__(1024) void ht_votes_kernel(PencilSoA m, const int32
         }
         peak[0] = p0;
         peak[1] = p1;
-        peak[2] = sqrtf(1.f - (p0 * p0 + p1 * p1));
+        // Nobody voted (one line, or copies of one): the "peak" is cell (0, 0), beyond the rim, and the radicand of its
+        // normalised point is 0 give or take an ulp -- taken as 0, the ideal point, not a NaN that every weight inherits.
+        // Where pairs did vote the expression stays as the reference writes it (a rim peak's radicand may fall below 0).
+        const float rad = 1.f - (p0 * p0 + p1 * p1);
+        peak[2] = sqrtf(bv == 0ull ? fmaxf(0.f, rad) : rad);
     }
 }
 

@@ -872,7 +872,10 @@ std::vector<float> get_weights_fixed(const LinePencilModel& M, const std::vector
     V3 p{(max_u - k) / k1, (max_v - k) / k1, 0.f};
     float pn = std::sqrt((p.x * p.x + p.y * p.y) + p.z * p.z);
     if (pn > 1.f) p = {p.x / pn, p.y / pn, p.z / pn};
-    p.z = std::sqrt(1.f - (p.x * p.x + p.y * p.y));
+    // nobody voted (one line, or copies of one): cell (0, 0), beyond the rim, whose radicand is 0 give or take an ulp, is
+    // taken as the ideal point; where pairs voted the expression stays as line_pencil.cpp:83 writes it
+    const float rad = 1.f - (p.x * p.x + p.y * p.y);
+    p.z = std::sqrt(best == 0 ? std::max(0.f, rad) : rad);
     std::vector<float> wts(idx.size());
     for (size_t j = 0; j < idx.size(); ++j) {
         int i = idx[j];
@@ -899,7 +902,13 @@ V3 prosac_solve(const LinePencilModel& model, const std::vector<int>& indices, f
     std::vector<float> weights = get_weights_fixed(model, indices);
     std::vector<int> order(indices.size());
     for (size_t i = 0; i < order.size(); ++i) order[i] = int(i);
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return weights[a] > weights[b]; });  // utils.h:36-44
+    // utils.h:36-44; a NaN weight (a line whose anchor is the Hough peak: 0 / 0) sorts last, stably -- "a > b" alone is no
+    // strict weak ordering once a NaN is among the weights
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
+        if (std::isnan(weights[a])) return false;
+        if (std::isnan(weights[b])) return true;
+        return weights[a] > weights[b];
+    });
     std::vector<int> idx(indices.size());
     for (size_t i = 0; i < order.size(); ++i) idx[i] = indices[order[i]];
     const int N = int(idx.size());

@@ -16,7 +16,8 @@ teeth: an error of u in an end point turns a segment of length 0.03 by 4e-6, the
 an eigenvalue gap of a few percent, and every round has lines inside such a band.)
 
 Model of a line (line_pencil.cpp:25-32), from exact inputs.  h_raw = (y1 - y2, x2 - x1, x1 y2 - y1 x2): the differences
-carry u |.|, the third component u (|x1 y2| + |y1 x2|) + u |h_raw.z| (two products, one difference).  The norm N = |h_raw| is
+carry u |.|, the third component u (|x1 y2| + |y1 x2|) + u |h_raw.z| (two products, one difference; nothing where the two
+products are the same real number, as for a segment whose end points mirror each other in the centre).  The norm N = |h_raw| is
 three squares, two sums and a root (relative 3u / 2 + u) and the quotient adds u: with the error vector r of h_raw,
 dh_k <= r_k / N + |h_k| (|r| / N + 4u).  The anchor (p1 + p2) / 2 carries u |a| per component.  The direction
 (p2 - p1) / |p2 - p1| is off, as a vector, by at most  dd = 2 |r_d| / len + 4u = 6u  (r_d: error of the difference, u |.| per
@@ -103,14 +104,19 @@ def _xy(lines):
     return np.stack([np.asarray(lines[k], np.float64) for k in ("x1", "y1", "x2", "y2")], 1)
 
 
-def normalised_f32(lines):
-    """geometry.cpp:96-112,258-282 in fp32, operation by operation (see the head of the file) -> fp32 records"""
+def normalisation_f32(lines):
+    """geometry.cpp:96-112 in fp32 -> (centre x, centre y, scale) as the fp32 numbers the records are normalised with"""
     f = np.float32
     x = np.concatenate([lines["x1"], lines["x2"]]).astype(f)
     y = np.concatenate([lines["y1"], lines["y2"]]).astype(f)
     sx, sy = f(x.max() - x.min()), f(y.max() - y.min())
-    cx, cy = f(x.min() + f(0.5) * sx), f(y.min() + f(0.5) * sy)
-    scale = max(sx, sy)
+    return f(x.min() + f(0.5) * sx), f(y.min() + f(0.5) * sy), max(sx, sy)
+
+
+def normalised_f32(lines):
+    """geometry.cpp:96-112,258-282 in fp32, operation by operation (see the head of the file) -> fp32 records"""
+    f = np.float32
+    cx, cy, scale = normalisation_f32(lines)
     out = lines.copy()
     out["x1"], out["x2"] = (lines["x1"].astype(f) - cx) / scale, (lines["x2"].astype(f) - cx) / scale
     out["y1"], out["y2"] = (lines["y1"].astype(f) - cy) / scale, (lines["y2"].astype(f) - cy) / scale
@@ -125,6 +131,10 @@ class Model:
         x1, y1, x2, y2 = xy.T
         raw = np.stack([y1 - y2, x2 - x1, x1 * y2 - y1 * x2], 1)
         r = U * np.stack([np.abs(raw[:, 0]), np.abs(raw[:, 1]), np.abs(x1 * y2) + np.abs(y1 * x2) + np.abs(raw[:, 2])], 1)
+        # The same real number rounds to the same float, so the difference is an exact zero.  Two assumptions: the inputs
+        # are fp32 numbers, whose float64 products here are exact (the test compares the real products), and the
+        # implementations round both products before they subtract (built with -ffp-contract=off: no FMA of the difference).
+        r[x1 * y2 == y1 * x2, 2] = 0.0
         nrm = np.linalg.norm(raw, axis=1)
         ok = nrm > 0
         nz = np.where(ok, nrm, 1.0)
@@ -310,17 +320,37 @@ def refit(M, inl):
     return f, np.full(3, 2 * e / (gap - 2 * e) + U)
 
 
-def peel_chain(segments, n_iter, seed, max_models, inlier_deg=2.0, garbage_deg=4.0):
+def ransac_proposal(n_iter, seed):
+    """the hypothesis of a round as estimate_line_pencils takes it: the winner of n_iter scored samples"""
+    def propose(M, obs, k, tol, dtol):
+        if n_iter <= 0:
+            return -1, None, None, ""
+        S = score_intervals(M, obs, tol, n_iter, seed, k, dtol)
+        it, decided = winner(S)
+        if not decided:
+            return it, None, None, "round %d: the winner is open between iteration %d and its rivals" % (k, it)
+        if it < 0:
+            return -1, None, None, ""
+        return it, S["p"][it], S["dp"][it], ""
+    return propose
+
+
+def peel_chain(segments, n_iter, seed, max_models, inlier_deg=2.0, garbage_deg=4.0, propose=None):
     """estimate_line_pencils as far as float64 can say what fp32 does.  -> dict(ids: expected group ids (valid for the lines
     in `settled`), settled: lines whose final id the decided rounds fix, rounds: rounds decided, complete: the chain ran to
-    the end of the peeling, reason, per round: winner, its inliers, lines grouped / garbage / staying)"""
+    the end of the peeling, reason, per round: winner, its inliers, lines grouped / garbage / staying, the refit and its
+    bound).  propose(M, obs, k, tol, dtol) -> (id of the hypothesis or -1 for none, p, dp, reason if it is open): where the
+    round's hypothesis comes from; the default is the RANSAC solve, another estimator's second source passes its own and
+    shares the verdicts."""
     n = len(segments)
     ids = -np.ones(n, np.int64)
     out = dict(ids=ids, settled=np.zeros(n, bool), rounds=0, complete=False, reason="", winners=[], winner_inliers=[], grouped=[],
-               garbage=[], in_band=0)
+               garbage=[], in_band=0, refits=[], removed=[])
     if n < 2 or max_models <= 0:
         out.update(settled=np.ones(n, bool), complete=True, reason="nothing to do")
         return out
+    if propose is None:
+        propose = ransac_proposal(n_iter, seed)
     M = Model(_xy(normalised_f32(segments)))
     tol, dtol = cos_tolerance(inlier_deg)
     gtol, _ = cos_tolerance(garbage_deg)
@@ -329,24 +359,20 @@ def peel_chain(segments, n_iter, seed, max_models, inlier_deg=2.0, garbage_deg=4
         if len(obs) < 2:
             break
         inl = None
-        if n_iter > 0:
-            S = score_intervals(M, obs, tol, n_iter, seed, k, dtol)
-            it, decided = winner(S)
-            if not decided:
-                out["reason"] = "round %d: the winner is open between iteration %d and its rivals" % (k, it)
+        it, p, dp, open_reason = propose(M, obs, k, tol, dtol)
+        if open_reason:
+            out["reason"] = open_reason
+            return out
+        if it >= 0:
+            err, band, _, _ = line_errors(M, obs, p[None, :], dp[None, :], dtol)
+            sure, amb = decide(err[0], band[0], tol)
+            if amb.any():
+                out["in_band"] += int(amb.sum())
+                out["reason"] = "round %d: %d lines within the band of the winner's tolerance" % (k, amb.sum())
                 return out
-            if it >= 0:
-                err, band, _, _ = line_errors(M, obs, S["p"][it:it + 1], S["dp"][it:it + 1], dtol)
-                sure, amb = decide(err[0], band[0], tol)
-                if amb.any():
-                    out["in_band"] += int(amb.sum())
-                    out["reason"] = "round %d: %d lines within the band of the winner's tolerance" % (k, amb.sum())
-                    return out
-                inl = obs[sure]
-                if len(inl) == 0:
-                    inl = None
-        else:
-            it = -1
+            inl = obs[sure]
+            if len(inl) == 0:
+                inl = None
         f, df = refit(M, inl)  # no winner, or a winner without inliers: every line of the model
         if df is None:
             out["reason"] = "round %d: the refit's eigenvector is not separated" % k
@@ -364,6 +390,8 @@ def peel_chain(segments, n_iter, seed, max_models, inlier_deg=2.0, garbage_deg=4
         out["winner_inliers"].append(0 if inl is None else len(inl))
         out["grouped"].append(int(s_in.sum()))
         out["garbage"].append(int((s_gb & ~s_in).sum()))
+        out["refits"].append((f, df))
+        out["removed"].append(obs[s_gb])
         obs = obs[~s_gb]
         out["rounds"] = k + 1
     out["settled"][:] = True

@@ -217,24 +217,24 @@ def refine(lines, cos_gate=0.99, max_offset=0.02, lo=-0.5, hi=1.5):
     for i in range(n_lines - 1):
         js = np.arange(i + 1, n_lines)
         cosv = np.abs(d[js] @ d[i])
-        for j, cv in zip(js[cosv >= cos_gate - 1e-3], cosv[cosv >= cos_gate - 1e-3]):
-            if ln[i] < ln[j]:  # the shorter one's end points in the longer one's frame, in units of its length
-                Wm = (np.stack([P1[i], P2[i]]) - P1[j]) @ np.stack([d[j], nrm[j]], axis=1) / ln[j]
-            else:
-                Wm = (np.stack([P1[j], P2[j]]) - P1[i]) @ np.stack([d[i], nrm[i]], axis=1) / ln[i]
-            off = np.abs(Wm[:, 1]).max()
-            x = Wm[:, 0]
-            g_cos, g_off, g_ovl = cv >= cos_gate, off < max_offset, bool((x > lo).any() and (x < hi).any())
-            if g_off and g_ovl:
-                closest = min(closest, abs(cv - cos_gate))
-            if g_cos and g_ovl:
-                closest = min(closest, abs(off - max_offset))
-            if g_cos and g_off:
-                # (the overlap gate is "any end point above lo and any below hi": it flips where the larger crosses lo or
-                # the smaller crosses hi)
-                closest = min(closest, abs(x.max() - lo), abs(x.min() - hi))
-            if g_cos and g_off and g_ovl:
-                succ[i].append(int(j))
+        near = cosv >= cos_gate - 1e-3
+        if not near.any():
+            continue
+        js, cv = js[near], cosv[near]
+        # the shorter one's end points in the longer one's frame, in units of its length (all candidates j of i at once)
+        sw = (ln[i] < ln[js])[:, None]
+        R1, Rd, Rn, Rl = np.where(sw, P1[js], P1[i]), np.where(sw, d[js], d[i]), np.where(sw, nrm[js], nrm[i]), np.where(sw[:, 0], ln[js], ln[i])
+        A, B = np.where(sw, P1[i], P1[js]) - R1, np.where(sw, P2[i], P2[js]) - R1
+        x = np.stack([(A * Rd).sum(1), (B * Rd).sum(1)], 1) / Rl[:, None]
+        off = np.abs(np.stack([(A * Rn).sum(1), (B * Rn).sum(1)], 1) / Rl[:, None]).max(1)
+        g_cos, g_off, g_ovl = cv >= cos_gate, off < max_offset, (x > lo).any(1) & (x < hi).any(1)
+        # smallest distance of a decisive quantity from its gate (the overlap gate is "any end point above lo and any
+        # below hi": it flips where the larger crosses lo or the smaller crosses hi)
+        for dist, decisive in ((np.abs(cv - cos_gate), g_off & g_ovl), (np.abs(off - max_offset), g_cos & g_ovl),
+                               (np.minimum(np.abs(x.max(1) - lo), np.abs(x.min(1) - hi)), g_cos & g_off)):
+            if decisive.any():
+                closest = min(closest, float(dist[decisive].min()))
+        succ[i] = [int(j) for j in js[g_cos & g_off & g_ovl]]
     # graph_components / dfs (line_detector.cpp:282-329): a breadth-first walk that only follows edges to HIGHER indices
     comp = -np.ones(n_lines, np.int64)
     visited = np.zeros(n_lines, bool)
