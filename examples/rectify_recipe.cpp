@@ -6,7 +6,7 @@
 //
 //   rectify_recipe in.pgm|in.ppm out_prefix [--max-size N|fraction] [--refine] [--threads N]
 //                  [--h-strategy rotate_h|rotate_v|rectify|keep] [--v-strategy ...] [--warp] [--device-prepare] [--lines]
-//                  [--jpeg Q] [--jpeg-in] [--orient]
+//                  [--jpeg Q] [--jpeg-in] [--orient] [--cubic]
 //
 // Input is a binary PGM (P5, 8 bit) or PPM (P6, 8 bit; converted with the usual integer luma weights
 // (4899 R + 9617 G + 1868 B + 8192) >> 14).  Image decoding stays with the caller's imaging library.
@@ -30,6 +30,8 @@
 // --orient (with --jpeg-in alone): the file's EXIF orientation is applied as the demo's imread applies it -- entry [7] of the
 // frame's row is 1 for lr_jpeg_info, which then tells the upright size, and for lr_decode_jpeg_device, whose output pass
 // writes the upright picture; that one goes on to prepare, detect and warp.  Without it the picture is the stored one.
+// --cubic (with --warp or --jpeg alone; it implies neither): the warp samples 4 x 4 bicubic, cv::warpPerspective's INTER_CUBIC
+// (LR_WARP_CUBIC or-ed into the warp's format word), instead of bilinear.  Everything else is as without it.
 // Links against librectify_amd.so exactly like a program written for the reference.
 #include <algorithm>
 #include <cctype>
@@ -263,8 +265,9 @@ bool write_jpeg(lr_context* ctx, const void* d_img, int w, int h, int ch, int qu
 // The demo's homography_from_corners(t, 3.0) + warpPerspective of the frame as read, on the GPU; writes
 // <prefix>_warp.pgm / .ppm.  Returns false with the reason on stderr.
 // `out`, `ow`, `oh` and `H` (source to rectified picture) are kept for --lines.  jpeg > 0: <prefix>_warp.jpg as well.
+// cubic: the bicubic sampling rule.
 bool warp_frame(const Gray& g, const ImageTransform& t, const std::string& prefix, std::vector<uint8_t>& out, int& ow, int& oh,
-                double* H, int jpeg) {
+                double* H, int jpeg, bool cubic) {
     double M[9];
     lr_context* ctx = nullptr;
     void* d_src = nullptr;
@@ -276,8 +279,8 @@ bool warp_frame(const Gray& g, const ImageTransform& t, const std::string& prefi
         ok = lr_device_malloc(ctx, g.raw.size(), &d_src) == 0 && lr_device_malloc(ctx, out.size(), &d_dst) == 0 &&
              lr_memcpy_h2d(ctx, d_src, g.raw.data(), g.raw.size()) == 0 &&
              lr_warp_perspective_device(ctx, d_src, g.raw.size(), 1, g.w, g.h, (size_t)g.w * bpp,
-                                        g.ch == 3 ? LR_PIX_U8X3 : LR_PIX_U8, M, d_dst, out.size(), ow, oh,
-                                        (size_t)ow * bpp) == 0 &&
+                                        (g.ch == 3 ? LR_PIX_U8X3 : LR_PIX_U8) | (cubic ? LR_WARP_CUBIC : 0), M, d_dst, out.size(),
+                                        ow, oh, (size_t)ow * bpp) == 0 &&
              lr_memcpy_d2h(ctx, out.data(), d_dst, out.size()) == 0;
     }
     if (!ok) std::fprintf(stderr, "warp failed: %s\n", lr_last_error());
@@ -356,12 +359,12 @@ int main(int argc, char** argv) {
         std::fprintf(stderr,
                      "usage: %s in.pgm|in.ppm out_prefix [--max-size N|fraction] [--refine] [--threads N]\n"
                      "          [--h-strategy rotate_h|rotate_v|rectify|keep] [--v-strategy ...] [--warp] [--device-prepare]\n"
-                     "          [--lines] [--jpeg Q] [--jpeg-in] [--orient]\n",
+                     "          [--lines] [--jpeg Q] [--jpeg-in] [--orient] [--cubic]\n",
                      argv[0]);
         return 2;
     }
     float max_size = 1200.f;  // the demo's default
-    bool refine = false, warp = false, device_prepare = false, lines_pictures = false, jpeg_in = false, orient = false;
+    bool refine = false, warp = false, device_prepare = false, lines_pictures = false, jpeg_in = false, orient = false, cubic = false;
     int threads = -1, jpeg = 0;
     RectificationConfig cfg;
     cfg.horizontal_vp_min_distance = 2;  // autorectify.cpp:347
@@ -374,6 +377,7 @@ int main(int argc, char** argv) {
         else if (a == "--lines") lines_pictures = true;
         else if (a == "--jpeg-in") jpeg_in = device_prepare = true;
         else if (a == "--orient") orient = true;
+        else if (a == "--cubic") cubic = true;
         else if (a == "--max-size" && has_val) max_size = (float)std::atof(argv[++i]);
         else if (a == "--threads" && has_val) threads = std::atoi(argv[++i]);
         else if (a == "--jpeg" && has_val && std::atoi(argv[i + 1]) >= 1 && std::atoi(argv[i + 1]) <= 100) {
@@ -389,6 +393,10 @@ int main(int argc, char** argv) {
     }
     if (orient && !jpeg_in) {
         std::fprintf(stderr, "--orient goes with --jpeg-in: a PGM or PPM file carries no EXIF orientation\n");
+        return 2;
+    }
+    if (cubic && !warp) {
+        std::fprintf(stderr, "--cubic goes with --warp or --jpeg: it is the warp's sampling rule and implies neither\n");
         return 2;
     }
     Gray full;
@@ -443,7 +451,7 @@ int main(int argc, char** argv) {
     std::vector<uint8_t> warped;
     int ow = 0, oh = 0;
     double H[9];
-    bool ok = !warp || warp_frame(full, t, prefix, warped, ow, oh, H, jpeg);
+    bool ok = !warp || warp_frame(full, t, prefix, warped, ow, oh, H, jpeg, cubic);
     if (ok && lines_pictures) {  // on the gray frame, as the demo draws (autorectify.cpp:364)
         std::vector<uint8_t> gray(full.px.size());
         for (size_t i = 0; i < gray.size(); ++i) gray[i] = (uint8_t)(full.px[i] * 256.0f);

@@ -272,6 +272,25 @@ enum lr_warp_layout { LR_WARP_PACKED = 0x200 }; /* or-ed into `format` like lr_w
  * [17], an entry that is not an integer in its range, a source or output outside its region, overlapping outputs, a
  * non-finite map (the warp only), a non-zero src_row_bytes or dst_row_bytes, more than 2^31 tiles, the alignment rules. */
 enum lr_warp_sources { LR_WARP_RAGGED = 0x800 }; /* or-ed into `format` like lr_warp_option */
+/* LR_WARP_CUBIC is the warp's second sampling rule, cv::warpPerspective's INTER_CUBIC: a 4 x 4 bicubic (the Keys kernel with
+ * a = -0.75, the constant OpenCV uses) in place of the 2 x 2 bilinear, for the rectified picture's magnified far side, where
+ * the bilinear rule softens edges.  It is an option of the three warps and of nothing else:
+ *   fmt | LR_WARP_CUBIC                     the warp above (one output size for all frames);
+ *   fmt | LR_WARP_PACKED | LR_WARP_CUBIC    LR_WARP_PACKED's call;
+ *   fmt | LR_WARP_RAGGED | LR_WARP_CUBIC    LR_WARP_RAGGED's call;
+ * and holds for every frame of the call.  Arguments, tables, checks, failure behaviour and the promise that no other byte of
+ * the destination is written are those of the same call without the bit; without the bit every call gives what it gave.
+ * Arithmetic (tests/numpy_warp_cubic_ref.py restates it): the source coordinates X, Y are the
+ * bilinear warp's, 5 fractional bits per axis; ix = X >> 5, ax = X & 31 (iy, ay likewise); the taps are columns ix - 1 ..
+ * ix + 2 of rows iy - 1 .. iy + 2, a tap outside the source is 0; the four weights of an axis are row ax (ay) of a table of
+ * 32 x 4 integers at scale 2048, whose rows sum to 2048.  u8 and u8x3, per channel, exact and in integers: h_j = sum_i
+ * C[ax][i] v(i, j), s = sum_j C[ay][j] h_j, result (s + 2^21) >> 22 clamped to 0 .. 255 (a bicubic overshoots at edges).  f32:
+ * weights C / 2048.f, each row's four products summed from the first tap to the last, then the rows' likewise, every product
+ * and sum rounded to float on its own; no clamp.  The identity map gives back a u8 source byte for byte (an f32 source of
+ * finite values bit for bit, -0 aside).  Fails cleanly (nothing launched, nothing written, lr_last_error names the
+ * combination) together with LR_WARP_PREPARE (an area average by definition), LR_WARP_LINES, LR_WARP_JPEG or
+ * LR_WARP_JPEG_DECODE. */
+enum lr_warp_sampling { LR_WARP_CUBIC = 0x8000 }; /* or-ed into `format` like lr_warp_option */
 
 /* The demo's lines picture (autorectify.cpp:72-110, draw_lines; <name>_warp_lines.jpg) on frames that stay in HBM: every
  * segment of a frame as a 3-pixel stroke with a disc of radius 5 at each end, in its group's colour, later segments over

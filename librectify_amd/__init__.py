@@ -83,6 +83,7 @@ WARP_PACKED = 0x200  # enum lr_warp_layout, likewise: per-frame output sizes and
 WARP_RAGGED = 0x800  # enum lr_warp_sources, likewise: per-frame source sizes and places as well (ragged_table)
 WARP_LINES = 0x1000  # enum lr_warp_lines, likewise: lr_draw_lines_device, whose own arguments travel behind M (DrawLinesArgs)
 WARP_JPEG = 0x2000  # enum lr_warp_jpeg, likewise: lr_encode_jpeg_device, whose own arguments travel behind M (JpegArgs)
+WARP_CUBIC = 0x8000  # enum lr_warp_sampling, likewise: the warp (plain, WARP_PACKED, WARP_RAGGED) samples 4 x 4 bicubic, not bilinear
 WARP_JPEG_DECODE = 0x4000  # enum lr_warp_jpeg_decode, likewise: lr_decode_jpeg_device, whose own arguments travel behind M (JpegDecodeArgs)
 JPEG_OK, JPEG_NOT_JPEG, JPEG_UNSUPPORTED, JPEG_SIZE_MISMATCH, JPEG_DAMAGED = range(5)  # info[5] of lr_decode_jpeg_device
 FRAMES_U8, FRAMES_U8X3, FRAMES_F32 = 0x100, 0x200, 0x300  # enum lr_frames_option, or-ed into `refine` of the frame entries
@@ -480,6 +481,13 @@ def _source_extent(sources, bpp):
     return max(off + (h - 1) * row + w * bpp for w, h, off, row in sources)
 
 
+def _sampling_bit(interp, what):
+    """the format word's bit for interp= of the calls that end in a warp: WARP_CUBIC for "cubic", 0 for "linear" (anything else: ValueError)"""
+    if isinstance(interp, str) and interp in ("linear", "cubic"):
+        return WARP_CUBIC if interp == "cubic" else 0
+    raise ValueError('%s: interp is "linear" or "cubic", not %r' % (what, interp))
+
+
 def _frame_format(a, what):
     """(format, bytes per pixel) of one 8-bit or f32 frame as the warp and the prepare step take it"""
     if a.dtype == np.uint8 and a.ndim == 2:
@@ -652,7 +660,8 @@ class Context:
     def warp_perspective_device(self, d_src, src_image_bytes, batch, width, height, src_row_bytes, fmt, M, d_dst,
                                 dst_image_bytes, out_width, out_height, dst_row_bytes):
         """lr_warp_perspective_device: one launch for `batch` device frames, enqueued on the context's stream.  M: 9
-        doubles per frame ((batch, 3, 3) or (3, 3)), the destination-to-source map.  fmt: PIX_U8, PIX_U8X3, PIX_F32."""
+        doubles per frame ((batch, 3, 3) or (3, 3)), the destination-to-source map.  fmt: PIX_U8, PIX_U8X3, PIX_F32, with
+        WARP_CUBIC or-ed in for the bicubic sampling rule."""
         M = np.ascontiguousarray(M, np.float64).reshape(-1)
         if M.size < 9 * max(int(batch), 1):
             raise ValueError("warp_perspective_device: M needs 9 values per frame")
@@ -661,16 +670,19 @@ class Context:
     def warp_perspective_packed_device(self, d_src, src_image_bytes, batch, width, height, src_row_bytes, fmt, table, d_dst,
                                        dst_bytes):
         """lr_warp_perspective_device with LR_WARP_PACKED: one launch for `batch` device frames of one size whose outputs
-        have their own sizes and places in the dst_bytes at d_dst.  table: 13 doubles per frame (warp_table)."""
+        have their own sizes and places in the dst_bytes at d_dst.  table: 13 doubles per frame (warp_table).  fmt may carry
+        WARP_CUBIC."""
         table = np.ascontiguousarray(table, np.float64).reshape(-1)
         if table.size != 13 * int(batch) or batch < 1:
             raise ValueError("warp_perspective_packed_device: the table has 13 values per frame")
         out_w, out_h = (int(min(max(v, 1), 2 ** 31 - 1)) for v in np.nan_to_num(table.reshape(-1, 13)[:, 9:11]).max(axis=0))
         _check(lib().lr_warp_perspective_device(self._h, C.c_void_p(d_src), src_image_bytes, batch, width, height, src_row_bytes, fmt | WARP_PACKED, _ptr(table), C.c_void_p(d_dst), dst_bytes, out_w, out_h, 0))
 
-    def warp_perspective(self, array, M, out_size):
+    def warp_perspective(self, array, M, out_size, interp="linear"):
         """Warps one host frame (2-D uint8 or float32, or H x W x 3 uint8) by M (3x3, destination -> source) into an image
-        of out_size = (width, height) on the GPU: upload, one launch, download.  Returns the (height, width[, 3]) array."""
+        of out_size = (width, height) on the GPU: upload, one launch, download.  Returns the (height, width[, 3]) array.
+        interp: "linear" (bilinear) or "cubic" (WARP_CUBIC: 4 x 4 bicubic, cv::warpPerspective's INTER_CUBIC)."""
+        cubic = _sampling_bit(interp, "warp_perspective")
         a = np.ascontiguousarray(array)
         fmt, bpp = _frame_format(a, "warp_perspective")
         h, w = a.shape[:2]
@@ -679,7 +691,7 @@ class Context:
         d_dst = C.c_void_p()
         try:
             _check(lib().lr_device_malloc(self._h, ow * oh * bpp, C.byref(d_dst)))
-            self.warp_perspective_device(d_src, a.nbytes, 1, w, h, w * bpp, fmt, M, d_dst.value, ow * oh * bpp, ow, oh, ow * bpp)
+            self.warp_perspective_device(d_src, a.nbytes, 1, w, h, w * bpp, fmt | cubic, M, d_dst.value, ow * oh * bpp, ow, oh, ow * bpp)
             return self.device_download(d_dst.value, (oh, ow) + a.shape[2:], a.dtype)
         finally:
             self.device_free(d_src)
@@ -919,11 +931,11 @@ class Context:
         orient=True: upright, by the file's EXIF orientation."""
         return self.decode_jpeg_batch([data], fmt, orient)[0]
 
-    def _rectify_streams(self, streams, min_length, refine, cfg, clip, max_size, capacity, jpeg, orient=False):
+    def _rectify_streams(self, streams, min_length, refine, cfg, clip, max_size, capacity, jpeg, orient=False, interp="linear"):
         """rectify_batch for JPEG files: the files go up and are decoded in HBM, the pictures are handed to
         rectify_frames_device where they lie; with jpeg=Q no pixel crosses the link in either direction"""
         d_src, _, fmt, sources = self._decode_resident(streams, None, "rectify_batch", orient)
-        return self._rectify_resident(d_src, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg)
+        return self._rectify_resident(d_src, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp)
 
     def prepare_device(self, d_src, src_image_bytes, batch, width, height, src_row_bytes, fmt, d_dst, dst_image_bytes,
                        out_width, out_height, dst_row_bytes):
@@ -955,7 +967,7 @@ class Context:
                 self.device_free(d_dst.value)
         return out if batched else out[0]
 
-    def _rectify_prepared(self, img, max_size, min_length, refine, cfg, clip):
+    def _rectify_prepared(self, img, max_size, min_length, refine, cfg, clip, cubic=0):
         """rectify with the demo's prescale: the 8-bit frame goes up once; the prepare step, the detector and the warp all
         read it in HBM"""
         fmt, bpp = _frame_format(img, "rectify")
@@ -974,7 +986,7 @@ class Context:
             t = compute_rectification_transform(lines, w, h, cfg)
             _, M, (rw, rh) = rectification_homography(t, clip)
             _check(lib().lr_device_malloc(self._h, rw * rh * bpp, C.byref(d_dst)))
-            self.warp_perspective_device(d_src, img.nbytes, 1, w, h, w * bpp, fmt, M, d_dst.value, rw * rh * bpp, rw, rh, rw * bpp)
+            self.warp_perspective_device(d_src, img.nbytes, 1, w, h, w * bpp, fmt | cubic, M, d_dst.value, rw * rh * bpp, rw, rh, rw * bpp)
             return lines, t, self.device_download(d_dst.value, (rh, rw) + img.shape[2:], np.uint8)
         finally:
             self.device_free(d_src)
@@ -982,7 +994,8 @@ class Context:
                 if p.value:
                     self.device_free(p.value)
 
-    def rectify(self, image_u8, min_length=None, refine=False, cfg=None, clip=3.0, max_size=None, jpeg=None, orient=False):
+    def rectify(self, image_u8, min_length=None, refine=False, cfg=None, clip=3.0, max_size=None, jpeg=None, orient=False,
+                interp="linear"):
         """The reference demo's pipeline (autorectify.cpp) on an 8-bit frame (H x W gray or H x W x 3 RGB): luma
         (4899 R + 9617 G + 1868 B + 8192) >> 14, / 256, find_line_segment_groups with min_length max(w, h) / 100 by
         default, compute_rectification_transform (cfg: the demo's, horizontal_vp_min_distance = 2),
@@ -996,9 +1009,12 @@ class Context:
         jpeg=Q: `warped` is the rectified picture's JPEG file (bytes, quality Q, 4:2:0), encoded in HBM: rectify_batch's
         path for one frame.
         orient=True (a JPEG file only): the file's EXIF orientation is applied as it is decoded, as the demo's imread
-        does: the call on decode_jpeg(file, orient=True)."""
+        does: the call on decode_jpeg(file, orient=True).
+        interp="cubic": the warp samples 4 x 4 bicubic (WARP_CUBIC) instead of bilinear, on every path above; lines,
+        transform, homography and size are those of interp="linear", only the picture (or its JPEG file) differs."""
+        cubic = _sampling_bit(interp, "rectify")
         if isinstance(image_u8, (bytes, bytearray, memoryview)):  # a JPEG file: decoded in HBM, rectify_batch's path for one frame
-            lines, t, out = self.rectify_batch([bytes(image_u8)], min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, jpeg=jpeg, orient=orient)[0]
+            lines, t, out = self.rectify_batch([bytes(image_u8)], min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, jpeg=jpeg, orient=orient, interp=interp)[0]
             if out is None:
                 rectification_homography(t, clip)  # (raises what rectify raises for such a frame)
             return lines, t, out
@@ -1008,12 +1024,12 @@ class Context:
         if img.dtype != np.uint8 or not (img.ndim == 2 or (img.ndim == 3 and img.shape[2] == 3)):
             raise ValueError("rectify: an H x W or H x W x 3 uint8 frame")
         if jpeg is not None:
-            lines, t, stream = self.rectify_batch(img[None], min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, jpeg=jpeg)[0]
+            lines, t, stream = self.rectify_batch(img[None], min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, jpeg=jpeg, interp=interp)[0]
             if stream is None:
                 rectification_homography(t, clip)  # (raises what rectify raises for such a frame)
             return lines, t, stream
         if max_size is not None:
-            return self._rectify_prepared(img, max_size, min_length, refine, cfg or RectificationConfig(hmin=2.0), clip)
+            return self._rectify_prepared(img, max_size, min_length, refine, cfg or RectificationConfig(hmin=2.0), clip, cubic)
         fmt, bpp = _frame_format(img, "rectify")
         h, w = img.shape[:2]
         if min_length is None:
@@ -1027,7 +1043,7 @@ class Context:
             t = compute_rectification_transform(lines, w, h, cfg)
             _, M, (rw, rh) = rectification_homography(t, clip)
             _check(lib().lr_device_malloc(self._h, rw * rh * bpp, C.byref(d_dst)))
-            self.warp_perspective_device(d_src, img.nbytes, 1, w, h, w * bpp, fmt, M, d_dst.value, rw * rh * bpp, rw, rh, rw * bpp)
+            self.warp_perspective_device(d_src, img.nbytes, 1, w, h, w * bpp, fmt | cubic, M, d_dst.value, rw * rh * bpp, rw, rh, rw * bpp)
             return lines, t, self.device_download(d_dst.value, (rh, rw) + img.shape[2:], np.uint8)
         finally:
             self.device_free(d_src)
@@ -1035,7 +1051,7 @@ class Context:
                 self.device_free(d_dst.value)
 
     def rectify_batch_device(self, d_frames, batch, width, height, fmt, src_row_bytes=None, src_image_bytes=None,
-                             min_length=None, refine=False, cfg=None, clip=3.0, max_size=None, capacity=4096):
+                             min_length=None, refine=False, cfg=None, clip=3.0, max_size=None, capacity=4096, interp="linear"):
         """rectify for `batch` 8-bit frames (fmt PIX_U8 or PIX_U8X3) of one width x height that are resident in HBM, frame
         b at d_frames + b * src_image_bytes: with max_size one batched prepare_device, then the batch detector
         (lr_find_line_segment_groups_batch_device on the 8-bit frames, or on the prepared ones; its own transforms are not
@@ -1048,7 +1064,9 @@ class Context:
         has an all-zero row and no bytes in d_out; its lines and transform are returned all the same.
         capacity: lines per frame of the first detector pass.  A frame that has more makes the WHOLE batch's detector pass
         run once more with room for the longest list, so no frame's lines are ever cut, at twice the detector's cost for
-        such a batch; a caller who expects more than 4096 lines in a frame passes a larger capacity."""
+        such a batch; a caller who expects more than 4096 lines in a frame passes a larger capacity.
+        interp: "linear" or "cubic", the packed warp's sampling rule (WARP_CUBIC); nothing else changes."""
+        cubic = _sampling_bit(interp, "rectify_batch_device")
         if fmt not in (PIX_U8, PIX_U8X3):
             raise ValueError("rectify_batch_device: 8-bit frames, PIX_U8 or PIX_U8X3")
         batch, w, h = int(batch), int(width), int(height)
@@ -1109,7 +1127,7 @@ class Context:
             runs = np.split(np.array(good), np.flatnonzero(np.diff(good) != 1) + 1)
             for run in runs:
                 b0 = int(run[0])
-                self.warp_perspective_packed_device(d_frames + b0 * simg, simg, len(run), w, h, srow, fmt, table[run], d_out.value, total)
+                self.warp_perspective_packed_device(d_frames + b0 * simg, simg, len(run), w, h, srow, fmt | cubic, table[run], d_out.value, total)
             res, d_out = d_out.value, C.c_void_p()
             return lines_list, transforms, table, res, total
         finally:
@@ -1127,7 +1145,7 @@ class Context:
     def warp_perspective_ragged_device(self, d_src, src_bytes, fmt, table, d_dst, dst_bytes):
         """lr_warp_perspective_device with LR_WARP_RAGGED: one launch for frames that have their own source size and place
         in the src_bytes at d_src and their own output size and place in the dst_bytes at d_dst.  table: 18 doubles per
-        frame (ragged_table)."""
+        frame (ragged_table).  fmt may carry WARP_CUBIC."""
         self._ragged_call(d_src, src_bytes, fmt | WARP_RAGGED, table, d_dst, dst_bytes, "warp_perspective_ragged_device")
 
     def prepare_ragged_device(self, d_src, src_bytes, fmt, table, d_dst, dst_bytes):
@@ -1160,14 +1178,16 @@ class Context:
         return [out[b][: min(int(n[b]), capacity)].copy() for b in range(len(frames))], tf
 
     def rectify_frames_device(self, d_base, sources, fmt, min_length=None, refine=False, cfg=None, clip=3.0, max_size=None,
-                              capacity=4096):
+                              capacity=4096, interp="linear"):
         """rectify for 8-bit frames (fmt PIX_U8 or PIX_U8X3) that are resident in HBM and have their OWN sizes: frame b is
         sources[b] = (width, height, byte_offset from d_base, row_bytes).  With max_size one ragged prepare
         (prepare_ragged_device) to prepared_size(w_b, h_b, max_size) per frame, one detector call with a frame table (on
         the 8-bit frames, or on the prepared ones; min_length float32(max(pw_b, ph_b) / 100) per frame unless given), on
         the host what rectify does per frame, and the ragged warp into one allocation: one launch per run of consecutive
         frames that have an image.  Returns (lines_list, transforms, table, d_out, total_bytes) like rectify_batch_device;
-        table is ragged_table's (18 columns; an all-zero row for a frame without an image).  capacity: as there."""
+        table is ragged_table's (18 columns; an all-zero row for a frame without an image).  capacity and interp: as
+        there (the ragged warp's sampling rule)."""
+        cubic = _sampling_bit(interp, "rectify_frames_device")
         if fmt not in (PIX_U8, PIX_U8X3):
             raise ValueError("rectify_frames_device: 8-bit frames, PIX_U8 or PIX_U8X3")
         sources = [tuple(int(v) for v in s) for s in sources]
@@ -1229,7 +1249,7 @@ class Context:
             table[good], total = ragged_table(np.stack(Ms), np.array(sizes, np.int64), np.array([sources[b] for b in good], np.int64), bpp, align=4)
             _check(lib().lr_device_malloc(self._h, total, C.byref(d_out)))
             for run in np.split(np.array(good), np.flatnonzero(np.diff(good) != 1) + 1):
-                self.warp_perspective_ragged_device(d_base, src_bytes, fmt, table[run], d_out.value, total)
+                self.warp_perspective_ragged_device(d_base, src_bytes, fmt | cubic, table[run], d_out.value, total)
             res, d_out = d_out.value, C.c_void_p()
             return lines_list, transforms, table, res, total
         finally:
@@ -1246,7 +1266,7 @@ class Context:
             out[b] = s
         return out
 
-    def _rectify_mixed(self, frames, min_length, refine, cfg, clip, max_size, capacity, jpeg=None):
+    def _rectify_mixed(self, frames, min_length, refine, cfg, clip, max_size, capacity, jpeg=None, interp="linear"):
         """rectify_batch for a list of 8-bit frames of different shapes: all frames in one host buffer, one upload,
         rectify_frames_device, one download"""
         frames = [np.ascontiguousarray(f) for f in frames]
@@ -1263,15 +1283,15 @@ class Context:
         host = np.zeros(end, np.uint8)
         for f, (_, _, start, _) in zip(frames, sources):
             host[start: start + f.nbytes] = f.reshape(-1)
-        return self._rectify_resident(self.device_upload(host), sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg)
+        return self._rectify_resident(self.device_upload(host), sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp)
 
-    def _rectify_resident(self, d_src, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg):
+    def _rectify_resident(self, d_src, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp="linear"):
         """rectify_batch for 8-bit frames (width, height, byte_offset, row_bytes) that lie at d_src, which is freed here:
         rectify_frames_device, then one download of the pictures, or with jpeg the encoder and the streams alone"""
         bpp = 3 if fmt == PIX_U8X3 else 1
         d_out = None
         try:
-            lines, tfs, table, d_out, total = self.rectify_frames_device(d_src, sources, fmt, min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, capacity=capacity)
+            lines, tfs, table, d_out, total = self.rectify_frames_device(d_src, sources, fmt, min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, capacity=capacity, interp=interp)
             if jpeg is not None:
                 streams = self._jpeg_results(d_out, total, fmt, table, jpeg) if d_out else [None] * len(sources)
                 return [(lines[b], tfs[b], streams[b]) for b in range(len(sources))]
@@ -1291,7 +1311,7 @@ class Context:
         return res
 
     def rectify_batch(self, frames_u8, min_length=None, refine=False, cfg=None, clip=3.0, max_size=None, capacity=4096, jpeg=None,
-                      orient=False):
+                      orient=False, interp="linear"):
         """Context.rectify for a batch: frames_u8 is a uint8 array [B, H, W] or [B, H, W, 3], or a list of such frames of one
         shape.  One upload, rectify_batch_device (one detector batch, the packed warp), one download.  Returns a
         list of (lines, transform, warped), frame by frame what rectify returns for it; warped is None for a frame whose
@@ -1307,13 +1327,16 @@ class Context:
         rectify_frames_device where they lie -- bit for bit the call on decode_jpeg_batch's arrays (decode_jpeg_batch(files,
         PIX_U8)'s for a list of one-component files); with jpeg=Q no pixel crosses the link in either direction.
         orient=True (JPEG files only, else ValueError): the files' EXIF orientations are applied in the decoder's output
-        pass, as the demo's imread applies them -- bit for bit the call on decode_jpeg_batch(files, orient=True)'s arrays."""
+        pass, as the demo's imread applies them -- bit for bit the call on decode_jpeg_batch(files, orient=True)'s arrays.
+        interp="cubic": the warp launch of whichever path is taken samples 4 x 4 bicubic (WARP_CUBIC); detector, transforms,
+        sizes and the encoder are untouched -- frame by frame what rectify(interp="cubic") returns."""
+        _sampling_bit(interp, "rectify_batch")
         if _all_streams(frames_u8, "rectify_batch", orient):
-            return self._rectify_streams([bytes(f) for f in frames_u8], min_length, refine, cfg, clip, max_size, capacity, jpeg, orient)
+            return self._rectify_streams([bytes(f) for f in frames_u8], min_length, refine, cfg, clip, max_size, capacity, jpeg, orient, interp)
         if not isinstance(frames_u8, np.ndarray):
             frames_u8 = [np.asarray(f) for f in frames_u8]
             if len({f.shape for f in frames_u8}) > 1:
-                return self._rectify_mixed(frames_u8, min_length, refine, cfg, clip, max_size, capacity, jpeg)
+                return self._rectify_mixed(frames_u8, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp)
         a = np.ascontiguousarray(frames_u8 if isinstance(frames_u8, np.ndarray) else np.stack([np.asarray(f) for f in frames_u8]))
         if a.dtype != np.uint8 or a.ndim not in (3, 4) or (a.ndim == 4 and a.shape[3] != 3) or a.shape[0] < 1:
             raise ValueError("rectify_batch: uint8 frames [B, H, W] or [B, H, W, 3]")
@@ -1322,7 +1345,7 @@ class Context:
         d_src = self.device_upload(a)
         d_out = None
         try:
-            lines, tfs, table, d_out, total = self.rectify_batch_device(d_src, batch, w, h, fmt, min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, capacity=capacity)
+            lines, tfs, table, d_out, total = self.rectify_batch_device(d_src, batch, w, h, fmt, min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, capacity=capacity, interp=interp)
             if jpeg is not None:
                 streams = self._jpeg_results(d_out, total, fmt, table, jpeg) if d_out else [None] * batch
                 return [(lines[b], tfs[b], streams[b]) for b in range(batch)]

@@ -1,4 +1,4 @@
-// Rectified images: the bilinear perspective warp of lr_warp_perspective_device for gfx950.
+// Rectified images: the perspective warp of lr_warp_perspective_device for gfx950, bilinear or (LR_WARP_CUBIC) bicubic.
 //
 // A gather: every destination pixel maps back into its source frame through the frame's 3x3 matrix M and reads four
 // source pixels.  The source is read through L2, so what matters is that the pixels a workgroup reads lie close
@@ -15,6 +15,11 @@
 //
 // The arithmetic is the canonical one of DESIGN.md section 3 (mirrored by tests/numpy_warp_ref.py): coordinates in
 // double without contraction (-ffp-contract=off), 5 fractional bits per axis, integer taps and weights.
+//
+// LR_WARP_CUBIC is a second sampling rule, not a second kernel: warp_lane takes the rule as a template parameter and samples a
+// pixel from 4 x 4 taps (cubic_pixel) instead of 2 x 2; tiles, records, the XCD bands and the stores are the same.  The four
+// taps of a source row are consecutive bytes and come in with one load (row_taps), straight through L1 / L2 like the
+// bilinear taps.
 //
 // One lane body, two kernels.  warp_lane is a lane's work inside a tile: its four pixels' taps, blends and stores.  The two
 // kernels differ only in how a workgroup finds its frame and the frame's values, all of which depend on the tile index
@@ -85,12 +90,18 @@ struct Taps {
     int w00, w01, w10, w11;  // weights of (ix, iy), (ix+1, iy), (ix, iy+1), (ix+1, iy+1); they sum to 1024
 };
 
-__device__ __forceinline__ Taps taps_of(const double* __restrict__ m, unsigned x, unsigned y) {
+// the 5-bit fixed-point source coordinates of destination pixel (x, y): both sampling rules start from them
+__device__ __forceinline__ void fixed_xy(const double* __restrict__ m, unsigned x, unsigned y, int& X, int& Y) {
     const double xd = (double)x, yd = (double)y;
     const double W0 = (m[6] * xd + m[7] * yd) + m[8];
     const double Wq = W0 != 0.0 ? 32.0 / W0 : 0.0;
-    const int X = fixed_coord(((m[0] * xd + m[1] * yd) + m[2]) * Wq);
-    const int Y = fixed_coord(((m[3] * xd + m[4] * yd) + m[5]) * Wq);
+    X = fixed_coord(((m[0] * xd + m[1] * yd) + m[2]) * Wq);
+    Y = fixed_coord(((m[3] * xd + m[4] * yd) + m[5]) * Wq);
+}
+
+__device__ __forceinline__ Taps taps_of(const double* __restrict__ m, unsigned x, unsigned y) {
+    int X, Y;
+    fixed_xy(m, x, y, X, Y);
     Taps t;
     t.ix = X >> 5;
     t.iy = Y >> 5;
@@ -147,8 +158,121 @@ __device__ __forceinline__ uint32_t blend_u8(uint32_t a, uint32_t b, uint32_t c,
     return (a * (uint32_t)t.w00 + b * (uint32_t)t.w01 + c * (uint32_t)t.w10 + d * (uint32_t)t.w11 + 512u) >> 10;
 }
 
-// One lane's four consecutive pixels (x0 .. x0 + 3, those below ow) of destination row y, whose first byte is `out`
+// ---- LR_WARP_CUBIC: the 4 x 4 bicubic rule (tests/numpy_warp_cubic_ref.py) ----
+
 template <int kFormat>
+struct PixelBytes {
+    static constexpr int value = kFormat == LR_PIX_U8 ? 1 : (kFormat == LR_PIX_U8X3 ? 3 : 4);
+};
+
+// The four horizontal taps (ix - 1 .. ix + 2) of one source row as the 4, 12 or 16 consecutive bytes they are, in kBpp
+// dwords; a tap outside the source is 0.  Where all four are inside, their bytes and no others come in with one load
+// (dword, dwordx3, dwordx4: global memory asks for no alignment of an 8-bit row's taps and for 4 bytes of f32's);
+// otherwise every tap that is inside is fetched on its own.  So no byte outside the row's own pixels [row, row + w * kBpp)
+// is ever read: not a row's padding, not a neighbouring frame, nothing behind the last row.
+template <int kFormat>
+__device__ __forceinline__ void row_taps(const uint8_t* row, bool row_in, int ix, int w, uint32_t (&d)[PixelBytes<kFormat>::value]) {
+    constexpr int kBpp = PixelBytes<kFormat>::value;
+#pragma unroll
+    for (int i = 0; i < kBpp; ++i) d[i] = 0;
+    if (!row_in) return;
+    const bool cols_in = ix >= 1 && ix + 2 < w;  // (|ix| <= 2^26: no overflow)
+    if constexpr (kFormat == LR_PIX_F32) {
+        const float* r = reinterpret_cast<const float*>(row);
+        if (cols_in) {  // sixteen bytes at a 4-byte aligned address: one dwordx4, which asks for no more than that
+            __builtin_memcpy(d, r + (ix - 1), 16);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (inside(ix - 1 + i, w)) d[i] = __float_as_uint(r[ix - 1 + i]);
+        }
+    } else {
+        if (cols_in) {  // the taps' own 4 or 12 bytes, wherever they start: one load (global memory needs no alignment)
+            __builtin_memcpy(d, row + (size_t)(ix - 1) * kBpp, 4 * kBpp);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int c = ix - 1 + i;
+                const bool in = inside(c, w);
+                if constexpr (kFormat == LR_PIX_U8) {
+                    if (in) d[0] |= (uint32_t)row[c] << (8 * i);
+                } else {
+                    const uint32_t t = tap_u8x3(row + (size_t)(in ? c : 0) * 3, in);
+                    const int bit = 24 * i;  // the tap's three bytes start at byte 3 i of the twelve
+                    d[(bit >> 5)] |= t << (bit & 31);
+                    if ((bit & 31) > 8) d[((bit >> 5) + 1)] |= t >> (32 - (bit & 31));
+                }
+            }
+        }
+    }
+}
+
+// One destination pixel by the bicubic rule: a u8 pixel's byte or a u8x3 pixel's bytes r | g << 8 | b << 16 in `px`, an
+// f32 pixel in `pf`.  8-bit: h_j = sum_i C[ax][i] v(i, j), s = sum_j C[ay][j] h_j, (s + 2^21) >> 22 clamped to 0 .. 255.
+// Everything fits int32: max sum |C[a]| is 2816 and 255 * 2816^2 + 2^21 = 2 024 210 432 < 2^31.  f32: weights C / 2048.f
+// (exact), rows and then the column summed from the first tap to the last, every product and sum rounded on its own.
+template <int kFormat>
+__device__ __forceinline__ void cubic_pixel(const double* m, const uint8_t* src, size_t src_row_bytes, int w, int h, unsigned x,
+                                            unsigned y, uint32_t& px, float& pf) {
+    constexpr int kBpp = PixelBytes<kFormat>::value;
+    constexpr int kChannels = kFormat == LR_PIX_U8X3 ? 3 : 1;
+    int X, Y;
+    fixed_xy(m, x, y, X, Y);
+    const int ix = X >> 5, iy = Y >> 5;
+    const int16_t* cx = kCubicWeights[X & 31];
+    const int16_t* cy = kCubicWeights[Y & 31];
+    const int wx[4] = {cx[0], cx[1], cx[2], cx[3]};
+    const int wy[4] = {cy[0], cy[1], cy[2], cy[3]};
+    int s[kChannels];
+#pragma unroll
+    for (int ch = 0; ch < kChannels; ++ch) s[ch] = 0;
+    float hf[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int ry = iy - 1 + j;
+        const bool row_in = inside(ry, h);
+        const uint8_t* row = src + (size_t)(row_in ? ry : 0) * src_row_bytes;
+        uint32_t d[kBpp];
+        row_taps<kFormat>(row, row_in, ix, w, d);
+        if constexpr (kFormat == LR_PIX_F32) {
+            const float v0 = __uint_as_float(d[0]), v1 = __uint_as_float(d[1]);
+            const float v2 = __uint_as_float(d[2]), v3 = __uint_as_float(d[3]);
+            hf[j] = ((v0 * ((float)wx[0] / 2048.0f) + v1 * ((float)wx[1] / 2048.0f)) + v2 * ((float)wx[2] / 2048.0f)) +
+                    v3 * ((float)wx[3] / 2048.0f);
+        } else {
+#pragma unroll
+            for (int ch = 0; ch < kChannels; ++ch) {
+                int hsum = 0;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int byte = kChannels * i + ch;
+                    hsum += wx[i] * (int)((d[(byte >> 2)] >> (8 * (byte & 3))) & 0xFFu);
+                }
+                s[ch] += wy[j] * hsum;
+            }
+        }
+    }
+    px = 0;
+    pf = 0.f;
+    if constexpr (kFormat == LR_PIX_F32) {
+        pf = ((hf[0] * ((float)wy[0] / 2048.0f) + hf[1] * ((float)wy[1] / 2048.0f)) + hf[2] * ((float)wy[2] / 2048.0f)) +
+             hf[3] * ((float)wy[3] / 2048.0f);
+    } else {
+#pragma unroll
+        for (int ch = 0; ch < kChannels; ++ch) {
+            // clamped BEFORE the shift ((s + 2^21) >> 22 within 0 .. 255 is s + 2^21 within 0 .. 2^30 - 1): the same value, but
+            // written as shift-then-clamp two neighbouring pixels become one v_ashr_pk_u8_i32, whose result the compiler
+            // takes to be zero above bit 15 while the instruction leaves other bits there, which then land in the lane's
+            // third and fourth pixel
+            const int t = min(max(s[ch] + (1 << 21), 0), (1 << 30) - 1);
+            px |= ((uint32_t)t >> 22) << (8 * ch);
+        }
+    }
+}
+
+// One lane's four consecutive pixels (x0 .. x0 + 3, those below ow) of destination row y, whose first byte is `out`;
+// kCubic: sampled by the bicubic rule above instead of the bilinear one
+template <int kFormat, bool kCubic>
 __device__ __forceinline__ void warp_lane(const double* m, const uint8_t* src, size_t src_row_bytes, int w, int h,
                                           uint8_t* out, int ow, unsigned x0, unsigned y) {
     const int n = min(4, ow - (int)x0);  // pixels of this lane inside the row
@@ -158,6 +282,19 @@ __device__ __forceinline__ void warp_lane(const double* m, const uint8_t* src, s
     float res_f[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
+        if (kCubic) {
+            uint32_t px;
+            cubic_pixel<kFormat>(m, src, src_row_bytes, w, h, x0 + (unsigned)k, y, px, res_f[k]);
+            if (kFormat == LR_PIX_U8) res_u8 |= px << (8 * k);
+            if (kFormat == LR_PIX_U8X3) {
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) {
+                    const int byte = 3 * k + ch;  // byte of the lane's twelve
+                    res_rgb[byte >> 2] |= ((px >> (8 * ch)) & 0xFFu) << (8 * (byte & 3));
+                }
+            }
+            continue;
+        }
         const Taps t = taps_of(m, x0 + (unsigned)k, y);
         const bool in0 = inside(t.iy, h), in1 = inside(t.iy + 1, h);
         const uint8_t* row0 = src + (size_t)(in0 ? t.iy : 0) * src_row_bytes;
@@ -216,7 +353,7 @@ __device__ __forceinline__ void warp_lane(const double* m, const uint8_t* src, s
     }
 }
 
-template <int kFormat>
+template <int kFormat, bool kCubic>
 __global__ __launch_bounds__(kBlock) void warp_perspective_kernel(WarpArgs g) {
     const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
     const unsigned lx = (unsigned)lane & 15u, row_in_tile = (unsigned)(wave * 4 + (lane >> 4));
@@ -230,14 +367,14 @@ __global__ __launch_bounds__(kBlock) void warp_perspective_kernel(WarpArgs g) {
         if (y >= (unsigned)g.oh || x0 >= (unsigned)g.ow) continue;
         const uint8_t* src = g.src + (size_t)b * g.src_image_bytes;
         uint8_t* out = g.dst + (size_t)b * g.dst_image_bytes + (size_t)y * g.dst_row_bytes;
-        warp_lane<kFormat>(g.M + (size_t)b * 9, src, g.src_row_bytes, g.w, g.h, out, g.ow, x0, y);
+        warp_lane<kFormat, kCubic>(g.M + (size_t)b * 9, src, g.src_row_bytes, g.w, g.h, out, g.ow, x0, y);
     }
 }
 
 // The same tiles over a ragged list.  frames and start (batch + 1 entries: frame b owns the tiles [start[b], start[b + 1]))
 // are arguments of their own, restrict-qualified: the stores to dst cannot change them, so their uniform reads stay scalar
 // loads.
-template <int kFormat>
+template <int kFormat, bool kCubic>
 __global__ __launch_bounds__(kBlock) void warp_ragged_kernel(RaggedArgs g, const RaggedFrame* __restrict__ frames,
                                                              const int* __restrict__ start, uint8_t* __restrict__ dst) {
     const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
@@ -254,14 +391,14 @@ __global__ __launch_bounds__(kBlock) void warp_ragged_kernel(RaggedArgs g, const
         if (y >= (unsigned)oh || x0 >= (unsigned)ow) continue;
         const uint8_t* src = g.src + (size_t)f->src_offset;
         uint8_t* out = dst + (size_t)f->offset + (size_t)y * (size_t)f->row_bytes;
-        warp_lane<kFormat>(f->m, src, (size_t)f->src_row_bytes, f->w, f->h, out, ow, x0, y);
+        warp_lane<kFormat, kCubic>(f->m, src, (size_t)f->src_row_bytes, f->w, f->h, out, ow, x0, y);
     }
 }
 
 // The table kernel's launch: records, then the tiles' prefix table, go up in the mirror of the maps (in doubles: 18 a
 // frame + the table's ints)
-int launch_ragged(lr_context* c, const void* d_src, int format, const std::vector<RaggedFrame>& rec, const std::vector<int>& start,
-                  void* d_dst) {
+int launch_ragged(lr_context* c, const void* d_src, int format, bool cubic, const std::vector<RaggedFrame>& rec,
+                  const std::vector<int>& start, void* d_dst) {
     const size_t batch = rec.size(), rec_doubles = batch * 18;
     const int64_t n_tiles = start[batch];
     LR_HIP(hipSetDevice(c->device));
@@ -278,8 +415,8 @@ int launch_ragged(lr_context* c, const void* d_src, int format, const std::vecto
     const RaggedFrame* frames = reinterpret_cast<const RaggedFrame*>(c->warp_m.d.get());
     const int* tile_start = reinterpret_cast<const int*>(c->warp_m.d.get() + rec_doubles);
     const int grid = (int)std::min<int64_t>((n_tiles + 7) / 8 * 8, kMaxGrid);
-    launch_by_format(format, [&](auto fmt) {
-        hipLaunchKernelGGL(warp_ragged_kernel<decltype(fmt)::value>, dim3(grid), dim3(kBlock), 0, c->stream, g, frames, tile_start, dst);
+    launch_by_format_and_rule(format, cubic, [&](auto fmt, auto rule) {
+        hipLaunchKernelGGL((warp_ragged_kernel<decltype(fmt)::value, decltype(rule)::value>), dim3(grid), dim3(kBlock), 0, c->stream, g, frames, tile_start, dst);
     });
     LR_HIP(hipGetLastError());
     return 0;
@@ -288,7 +425,8 @@ int launch_ragged(lr_context* c, const void* d_src, int format, const std::vecto
 // lr_warp_perspective_device with LR_WARP_PACKED: M is the table of 13 doubles per frame, out_width x out_height bound the
 // frames' sizes and dst_image_bytes is the size of the whole destination region
 int warp_packed(lr_context* c, const void* d_src, size_t src_image_bytes, int batch, int width, int height, size_t src_row_bytes,
-                int format, const double* T, void* d_dst, size_t dst_bytes, int out_width, int out_height, size_t dst_row_bytes) {
+                int format, bool cubic, const double* T, void* d_dst, size_t dst_bytes, int out_width, int out_height,
+                size_t dst_row_bytes) {
     auto fail = [](const char* what) {
         set_error(std::string("lr_warp_perspective_device: LR_WARP_PACKED: ") + what);
         return 1;
@@ -347,13 +485,14 @@ int warp_packed(lr_context* c, const void* d_src, size_t src_image_bytes, int ba
     }
     start[(size_t)batch] = (int)n_tiles;
     if (extents_overlap(extent)) return fail("two frames' extents overlap");
-    return launch_ragged(c, d_src, format, rec, start, d_dst);
+    return launch_ragged(c, d_src, format, cubic, rec, start, d_dst);
 }
 
 // lr_warp_perspective_device with LR_WARP_RAGGED: M is the table of 18 doubles per frame, width x height and out_width x
 // out_height bound the frames' sizes, src_image_bytes and dst_image_bytes are the sizes of the two regions
 int warp_ragged(lr_context* c, const void* d_src, size_t src_bytes, int batch, int width, int height, size_t src_row_bytes,
-                int format, const double* T, void* d_dst, size_t dst_bytes, int out_width, int out_height, size_t dst_row_bytes) {
+                int format, bool cubic, const double* T, void* d_dst, size_t dst_bytes, int out_width, int out_height,
+                size_t dst_row_bytes) {
     std::vector<RaggedEntry> e;
     int64_t n_tiles = 0;
     if (ragged_parse(d_src, src_bytes, batch, width, height, src_row_bytes, format, false, T, d_dst, dst_bytes, out_width,
@@ -380,7 +519,7 @@ int warp_ragged(lr_context* c, const void* d_src, size_t src_bytes, int batch, i
         tiles += f.tiles_x * (int)((s.oh + kTileH - 1) / kTileH);
     }
     start[(size_t)batch] = tiles;
-    return launch_ragged(c, d_src, format, rec, start, d_dst);
+    return launch_ragged(c, d_src, format, cubic, rec, start, d_dst);
 }
 
 }  // namespace
@@ -450,6 +589,15 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
         set_error(std::string("lr_warp_perspective_device: ") + what);
         return 1;
     };
+    // LR_WARP_CUBIC: the sampling rule of the three warps (one size, LR_WARP_PACKED, LR_WARP_RAGGED) and of nothing else
+    const bool cubic = (format & LR_WARP_CUBIC) != 0;
+    if (cubic) {
+        if (format & LR_WARP_PREPARE) return fail("LR_WARP_CUBIC together with LR_WARP_PREPARE (the prepare step is an area average)");
+        if (format & LR_WARP_LINES) return fail("LR_WARP_CUBIC together with LR_WARP_LINES (the lines picture samples nothing)");
+        if (format & LR_WARP_JPEG) return fail("LR_WARP_CUBIC together with LR_WARP_JPEG (the encoder samples nothing)");
+        if (format & LR_WARP_JPEG_DECODE) return fail("LR_WARP_CUBIC together with LR_WARP_JPEG_DECODE (the decoder samples nothing)");
+        format &= ~LR_WARP_CUBIC;
+    }
     if (format & LR_WARP_JPEG_DECODE) {  // lr_decode_jpeg_device (kernels_jpeg_decode.hip): its own arguments arrive behind M
         if ((format & ~0xFF) != LR_WARP_JPEG_DECODE) return fail("LR_WARP_JPEG_DECODE together with another option bit");
         if (width != 0 || height != 0 || src_row_bytes != 0 || out_width != 0 || out_height != 0 || dst_row_bytes != 0)
@@ -481,7 +629,7 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
         const int opts = format & ~0xFF;
         if (opts & LR_WARP_PACKED) return fail("LR_WARP_RAGGED together with LR_WARP_PACKED (ragged outputs are always packed)");
         if (opts == LR_WARP_RAGGED)
-            return warp_ragged(c, d_src, src_image_bytes, batch, width, height, src_row_bytes, format & 0xFF, M, d_dst,
+            return warp_ragged(c, d_src, src_image_bytes, batch, width, height, src_row_bytes, format & 0xFF, cubic, M, d_dst,
                                dst_image_bytes, out_width, out_height, dst_row_bytes);
         if (opts == (LR_WARP_RAGGED | LR_WARP_PREPARE))
             return ctx_prepare_ragged(c, d_src, src_image_bytes, batch, width, height, src_row_bytes, format & 0xFF, M, d_dst,
@@ -490,7 +638,7 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
     }
     if (format & ~0xFF) {  // option bits above the pixel format
         if ((format & ~0xFF) == LR_WARP_PACKED)
-            return warp_packed(c, d_src, src_image_bytes, batch, width, height, src_row_bytes, format & 0xFF, M, d_dst,
+            return warp_packed(c, d_src, src_image_bytes, batch, width, height, src_row_bytes, format & 0xFF, cubic, M, d_dst,
                                dst_image_bytes, out_width, out_height, dst_row_bytes);
         if ((format & ~0xFF) == (LR_WARP_PACKED | LR_WARP_PREPARE)) return fail("LR_WARP_PACKED together with LR_WARP_PREPARE");
         if ((format & ~0xFF) != LR_WARP_PREPARE) return fail("unknown option bits in format");
@@ -542,8 +690,8 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
     g.tiles_per_frame = (int)(tiles_x * tiles_y);
     g.n_tiles = (int)n_tiles;
     const int grid = (int)std::min<int64_t>((n_tiles + 7) / 8 * 8, kMaxGrid);
-    launch_by_format(format, [&](auto fmt) {
-        hipLaunchKernelGGL(warp_perspective_kernel<decltype(fmt)::value>, dim3(grid), dim3(kBlock), 0, c->stream, g);
+    launch_by_format_and_rule(format, cubic, [&](auto fmt, auto rule) {
+        hipLaunchKernelGGL((warp_perspective_kernel<decltype(fmt)::value, decltype(rule)::value>), dim3(grid), dim3(kBlock), 0, c->stream, g);
     });
     LR_HIP(hipGetLastError());
     return 0;

@@ -3,6 +3,7 @@
 #pragma once
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -50,6 +51,23 @@ int upload_send(lr_context* c, MirroredBuffer<T>& m, Event& ev, size_t bytes) {
     return 0;
 }
 
+// The weights of LR_WARP_CUBIC: row a holds the four taps' weights, at scale 2048, for the
+// fraction a / 32 -- the Keys kernel with A = -0.75, c0 = ((A(t+1) - 5A)(t+1) + 8A)(t+1) - 4A, c1 = ((A+2)t - (A+3))t^2 + 1,
+// c2 = c1 of 1 - t, c3 = 1 - c0 - c1 - c2, each floor(c * 2048 + 0.5), and what a row then lacks to 2048 (at most 1 either way)
+// added to its entry [1] (a <= 16) or [2] (a > 16).  Every row sums to 2048, row 32 - a is row a reversed, the largest sum
+// of magnitudes is 2816 (rows 10 .. 12 and 20 .. 22).  tests/numpy_warp_cubic_ref.py computes the table from the formula and
+// tests/test_warp_cubic_cpu.py holds these literals against it.
+alignas(8) constexpr int16_t kCubicWeights[32][4] = {
+    {   0, 2048,    0,    0}, { -45, 2043,   51,   -1}, { -84, 2031,  107,   -6}, {-118, 2009,  169,  -12},
+    {-147, 1981,  235,  -21}, {-171, 1946,  305,  -32}, {-190, 1903,  379,  -44}, {-205, 1854,  456,  -57},
+    {-216, 1800,  536,  -72}, {-223, 1740,  618,  -87}, {-227, 1676,  702, -103}, {-227, 1607,  787, -119},
+    {-225, 1535,  873, -135}, {-220, 1460,  959, -151}, {-213, 1380, 1046, -165}, {-203, 1299, 1131, -179},
+    {-192, 1216, 1216, -192}, {-179, 1131, 1299, -203}, {-165, 1046, 1380, -213}, {-151,  959, 1460, -220},
+    {-135,  873, 1535, -225}, {-119,  787, 1607, -227}, {-103,  702, 1676, -227}, { -87,  618, 1740, -223},
+    { -72,  536, 1800, -216}, { -57,  456, 1854, -205}, { -44,  379, 1903, -190}, { -32,  305, 1946, -171},
+    { -21,  235, 1981, -147}, { -12,  169, 2009, -118}, {  -6,  107, 2031,  -84}, {  -1,   51, 2043,  -45},
+};
+
 // launch(tag) with tag an std::integral_constant of the pixel format, so that `decltype(tag)::value` names a kernel's
 // instantiation (the caller has checked that `format` is one of the three)
 template <class Launch>
@@ -57,6 +75,16 @@ void launch_by_format(int format, Launch&& launch) {
     if (format == LR_PIX_U8) launch(std::integral_constant<int, LR_PIX_U8>{});
     else if (format == LR_PIX_U8X3) launch(std::integral_constant<int, LR_PIX_U8X3>{});
     else launch(std::integral_constant<int, LR_PIX_F32>{});
+}
+
+// launch(tag, rule) for the warp, whose kernels are instantiated per sampling rule as well: rule is std::true_type for
+// LR_WARP_CUBIC and std::false_type for the bilinear rule
+template <class Launch>
+void launch_by_format_and_rule(int format, bool cubic, Launch&& launch) {
+    launch_by_format(format, [&](auto fmt) {
+        if (cubic) launch(fmt, std::true_type{});
+        else launch(fmt, std::false_type{});
+    });
 }
 
 }  // namespace lramd
