@@ -6,7 +6,7 @@
 //
 //   rectify_recipe in.pgm|in.ppm out_prefix [--max-size N|fraction] [--refine] [--threads N]
 //                  [--h-strategy rotate_h|rotate_v|rectify|keep] [--v-strategy ...] [--warp] [--device-prepare] [--lines]
-//                  [--jpeg Q] [--jpeg-in] [--orient] [--cubic]
+//                  [--jpeg Q] [--optimize] [--jpeg-in] [--orient] [--cubic]
 //
 // Input is a binary PGM (P5, 8 bit) or PPM (P6, 8 bit; converted with the usual integer luma weights
 // (4899 R + 9617 G + 1868 B + 8192) >> 14).  Image decoding stays with the caller's imaging library.
@@ -22,6 +22,8 @@
 // --jpeg Q: the demo's products as it writes them (autorectify.cpp:368-369, imwrite) -- implies --warp; the rectified picture
 // is compressed where the warp left it in HBM (lr_encode_jpeg_device, quality Q, 4:2:0 for colour) and only the stream comes
 // back: <out_prefix>_warp.jpg, and with --lines also <out_prefix>_warp_lines.jpg.
+// --optimize (with --jpeg Q alone): the files are coded with Huffman tables made from their own symbols (LR_JPEG_OPTIMIZE added
+// to entry [7] of the frame's row and to lr_jpeg_bound's layout; cv::IMWRITE_JPEG_OPTIMIZE): the same pixels in fewer bytes.
 // --jpeg-in: the input file is a baseline JPEG file (the demo's imread) -- lr_jpeg_info tells its size from the headers, the
 // file goes up as it is and lr_decode_jpeg_device decodes it in HBM (RGB, or gray for a one-component file).  The example
 // then downloads the picture and goes on exactly as --device-prepare does with a PPM it has read, so here the pixels do
@@ -235,11 +237,13 @@ bool find_groups_device_prepared(const Gray& g, int max_size, bool refine, int t
 }
 
 // A picture that lies in HBM (ch 1: gray, ch 3: RGB, rows packed) as a baseline JPEG file: an extent of lr_jpeg_bound bytes,
-// one lr_encode_jpeg_device call, and the stream alone comes back.  Returns false with the reason on stderr.
-bool write_jpeg(lr_context* ctx, const void* d_img, int w, int h, int ch, int quality, const std::string& path) {
+// one lr_encode_jpeg_device call, and the stream alone comes back.  optimize: with Huffman tables of the picture's own.
+// Returns false with the reason on stderr.
+bool write_jpeg(lr_context* ctx, const void* d_img, int w, int h, int ch, int quality, bool optimize, const std::string& path) {
     const int format = ch == 3 ? LR_PIX_U8X3 : LR_PIX_U8;
-    const size_t cap = lr_jpeg_bound(w, h, format, 0);
-    const double frame[8] = {(double)w, (double)h, 0, (double)w * ch, 0, (double)cap, (double)quality, 0};
+    const int layout = optimize ? LR_JPEG_OPTIMIZE : 0;  // (4:2:0 for colour)
+    const size_t cap = lr_jpeg_bound(w, h, format, layout);
+    const double frame[8] = {(double)w, (double)h, 0, (double)w * ch, 0, (double)cap, (double)quality, (double)layout};
     void* d_jpg = nullptr;
     uint64_t size = 0;
     std::vector<uint8_t> stream;
@@ -258,16 +262,17 @@ bool write_jpeg(lr_context* ctx, const void* d_img, int w, int h, int ch, int qu
         std::fprintf(stderr, "jpeg failed: cannot write %s\n", path.c_str());
         return false;
     }
-    std::printf("wrote %s (%dx%d, quality %d, %zu bytes)\n", path.c_str(), w, h, quality, stream.size());
+    std::printf("wrote %s (%dx%d, quality %d%s, %zu bytes)\n", path.c_str(), w, h, quality, optimize ? ", optimised tables" : "",
+                stream.size());
     return true;
 }
 
 // The demo's homography_from_corners(t, 3.0) + warpPerspective of the frame as read, on the GPU; writes
 // <prefix>_warp.pgm / .ppm.  Returns false with the reason on stderr.
 // `out`, `ow`, `oh` and `H` (source to rectified picture) are kept for --lines.  jpeg > 0: <prefix>_warp.jpg as well.
-// cubic: the bicubic sampling rule.
+// (optimize: with Huffman tables of its own.)  cubic: the bicubic sampling rule.
 bool warp_frame(const Gray& g, const ImageTransform& t, const std::string& prefix, std::vector<uint8_t>& out, int& ow, int& oh,
-                double* H, int jpeg, bool cubic) {
+                double* H, int jpeg, bool optimize, bool cubic) {
     double M[9];
     lr_context* ctx = nullptr;
     void* d_src = nullptr;
@@ -284,7 +289,7 @@ bool warp_frame(const Gray& g, const ImageTransform& t, const std::string& prefi
              lr_memcpy_d2h(ctx, out.data(), d_dst, out.size()) == 0;
     }
     if (!ok) std::fprintf(stderr, "warp failed: %s\n", lr_last_error());
-    const bool jpeg_ok = !ok || jpeg <= 0 || write_jpeg(ctx, d_dst, ow, oh, g.ch, jpeg, prefix + "_warp.jpg");
+    const bool jpeg_ok = !ok || jpeg <= 0 || write_jpeg(ctx, d_dst, ow, oh, g.ch, jpeg, optimize, prefix + "_warp.jpg");
     if (ctx) {
         if (d_src) lr_device_free(ctx, d_src);
         if (d_dst) lr_device_free(ctx, d_dst);
@@ -307,7 +312,7 @@ bool warp_frame(const Gray& g, const ImageTransform& t, const std::string& prefi
 // segments through H if it is not null; writes `path` as a PPM, and with jpeg > 0 `jpg_path` as a JPEG file compressed
 // where the picture was drawn.  Returns false with the reason on stderr.
 bool lines_picture(const uint8_t* img, int w, int h, int ch, const LineSegment* lines, int n, const double* H,
-                   const std::string& path, int jpeg = 0, const std::string& jpg_path = std::string()) {
+                   const std::string& path, int jpeg = 0, bool optimize = false, const std::string& jpg_path = std::string()) {
     lr_context* ctx = nullptr;
     void* d_img = nullptr;
     void* d_rgb = nullptr;
@@ -325,7 +330,7 @@ bool lines_picture(const uint8_t* img, int w, int h, int ch, const LineSegment* 
              lr_draw_lines_device(ctx, d_img, img_bytes, LR_PIX_U8, lines, (size_t)n, from_gray, 1, H, d_rgb, rgb_bytes) == 0 &&
              lr_memcpy_d2h(ctx, out.data(), d_rgb, rgb_bytes) == 0;
     if (!ok) std::fprintf(stderr, "lines picture failed: %s\n", lr_last_error());
-    if (ok && jpeg > 0) ok = write_jpeg(ctx, ch == 3 ? d_img : d_rgb, w, h, 3, jpeg, jpg_path);
+    if (ok && jpeg > 0) ok = write_jpeg(ctx, ch == 3 ? d_img : d_rgb, w, h, 3, jpeg, optimize, jpg_path);
     if (ctx) {
         if (d_img) lr_device_free(ctx, d_img);
         if (d_rgb) lr_device_free(ctx, d_rgb);
@@ -359,12 +364,13 @@ int main(int argc, char** argv) {
         std::fprintf(stderr,
                      "usage: %s in.pgm|in.ppm out_prefix [--max-size N|fraction] [--refine] [--threads N]\n"
                      "          [--h-strategy rotate_h|rotate_v|rectify|keep] [--v-strategy ...] [--warp] [--device-prepare]\n"
-                     "          [--lines] [--jpeg Q] [--jpeg-in] [--orient] [--cubic]\n",
+                     "          [--lines] [--jpeg Q] [--optimize] [--jpeg-in] [--orient] [--cubic]\n",
                      argv[0]);
         return 2;
     }
     float max_size = 1200.f;  // the demo's default
     bool refine = false, warp = false, device_prepare = false, lines_pictures = false, jpeg_in = false, orient = false, cubic = false;
+    bool optimize = false;
     int threads = -1, jpeg = 0;
     RectificationConfig cfg;
     cfg.horizontal_vp_min_distance = 2;  // autorectify.cpp:347
@@ -378,6 +384,7 @@ int main(int argc, char** argv) {
         else if (a == "--jpeg-in") jpeg_in = device_prepare = true;
         else if (a == "--orient") orient = true;
         else if (a == "--cubic") cubic = true;
+        else if (a == "--optimize") optimize = true;
         else if (a == "--max-size" && has_val) max_size = (float)std::atof(argv[++i]);
         else if (a == "--threads" && has_val) threads = std::atoi(argv[++i]);
         else if (a == "--jpeg" && has_val && std::atoi(argv[i + 1]) >= 1 && std::atoi(argv[i + 1]) <= 100) {
@@ -393,6 +400,10 @@ int main(int argc, char** argv) {
     }
     if (orient && !jpeg_in) {
         std::fprintf(stderr, "--orient goes with --jpeg-in: a PGM or PPM file carries no EXIF orientation\n");
+        return 2;
+    }
+    if (optimize && jpeg <= 0) {
+        std::fprintf(stderr, "--optimize goes with --jpeg Q: it is the encoder's choice of Huffman tables\n");
         return 2;
     }
     if (cubic && !warp) {
@@ -451,12 +462,12 @@ int main(int argc, char** argv) {
     std::vector<uint8_t> warped;
     int ow = 0, oh = 0;
     double H[9];
-    bool ok = !warp || warp_frame(full, t, prefix, warped, ow, oh, H, jpeg, cubic);
+    bool ok = !warp || warp_frame(full, t, prefix, warped, ow, oh, H, jpeg, optimize, cubic);
     if (ok && lines_pictures) {  // on the gray frame, as the demo draws (autorectify.cpp:364)
         std::vector<uint8_t> gray(full.px.size());
         for (size_t i = 0; i < gray.size(); ++i) gray[i] = (uint8_t)(full.px[i] * 256.0f);
         ok = lines_picture(gray.data(), full.w, full.h, 1, lines, n, nullptr, prefix + "_lines.ppm") &&
-             (!warp || lines_picture(warped.data(), ow, oh, full.ch, lines, n, H, prefix + "_warp_lines.ppm", jpeg, prefix + "_warp_lines.jpg"));
+             (!warp || lines_picture(warped.data(), ow, oh, full.ch, lines, n, H, prefix + "_warp_lines.ppm", jpeg, optimize, prefix + "_warp_lines.jpg"));
     }
     if (!device_prepare) release_line_segments(&lines);
     if (!ok) return 1;

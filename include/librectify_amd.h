@@ -359,8 +359,18 @@ static inline int lr_draw_lines_device(lr_context* ctx, const void* d_src, size_
  * the forward DCT and the quantisation are exact, in integers.  Frames are padded to whole MCUs by replicating the last
  * column and row; a 4:2:0 luminance block that holds no pixel of the frame is coded as libjpeg codes its dummy blocks (a DC
  * difference of 0 and an end of block).
- * The coefficients (2 bytes per sample of the padded components), the intervals' lengths and places belong to the context's
- * workspace: lr_context_trim frees them.
+ * LR_JPEG_OPTIMIZE added to a frame's [7] (0, 1, 16 or 17 for LR_PIX_U8X3; 0 or 16 for LR_PIX_U8; every frame of a batch its
+ * own value): the frame's stream is coded with Huffman tables made from the frame's own symbols (DESIGN.md section 3, item
+ * 13a; tests/numpy_jpeg_optimize_ref.py produces the same bytes), the two-pass mode of the CPU encoders (libjpeg's
+ * optimize_coding).  The symbols the stream emits are counted per table over all restart intervals; the code lengths are
+ * Annex K.2's as the IJG library finds them (a 257th pseudo-symbol of count 1 keeps the all-ones code free; of equal counts
+ * the larger symbol is merged first), limited to 16 bits by the K.3 adjustment; the DHT segments list the symbols that occur
+ * and nothing else.  Only the DHT payloads and the code bits differ from the stream without the option: a decoder gets
+ * the same pixels from fewer bytes (about 15 % fewer for a photograph at quality 95).  Counting and table making run on the
+ * device in front of the entropy coder, two more launches and the call's one synchronisation at its end; a call in
+ * which no frame has the option launches exactly what it launched before the option existed.
+ * The coefficients (2 bytes per sample of the padded components), the intervals' lengths and places and the symbol counters
+ * belong to the context's workspace: lr_context_trim frees them.
  * The library's table of exported symbols is full, so the call travels through lr_warp_perspective_device like
  * lr_draw_lines_device: LR_WARP_JPEG or-ed into `format`, `M` pointing to an lr_jpeg_args, src_image_bytes and
  * dst_image_bytes the two regions' sizes, and width, height, out_width, out_height and both row strides 0 (any other option
@@ -370,6 +380,7 @@ typedef struct lr_jpeg_args {
     uint64_t* sizes;      /* HOST, one per frame: the streams' lengths */
 } lr_jpeg_args;
 enum lr_warp_jpeg { LR_WARP_JPEG = 0x2000 }; /* or-ed into `format` like lr_warp_option */
+enum lr_jpeg_option { LR_JPEG_OPTIMIZE = 0x10 }; /* added to [7] of a frame's row, and to lr_jpeg_bound's layout */
 static inline int lr_encode_jpeg_device(lr_context* ctx, const void* d_src, size_t src_bytes, int format, const double* frames,
                                         int batch, void* d_dst, size_t dst_bytes, uint64_t* sizes) {
     lr_jpeg_args a;
@@ -383,9 +394,16 @@ static inline int lr_encode_jpeg_device(lr_context* ctx, const void* d_src, size
  * AC coefficients of at most 16 bits of code and 10 of magnitude each, 22 + 63 * 26 = 1660 bits = 207.5 bytes: 208, which
  * also covers an interval's padding to a whole byte (96 blocks leave 48 bytes over).  Every byte can be 0xFF and is then
  * followed by a stuffed zero: 416 per block.  Every interval but the last is followed by a 2-byte RSTm.  The markers and
- * headers in front of the scan are 629 bytes (334 for one component), the EOI 2: 640 covers both. */
+ * headers in front of the scan are 629 bytes (334 for one component), the EOI 2: 640 covers both.
+ * With LR_JPEG_OPTIMIZE added to `layout` (the frame's [7]): a DC code can then have 16 bits, not 11, so a block's longest
+ * code is 27 + 63 * 26 = 1665 bits.  n blocks of an interval are at most ceil(1665 n / 8) <= 208.125 n + 0.875 bytes with
+ * their padding, twice that with every byte stuffed: 416.25 n + 1.75 <= 418 n for every n >= 1 (96 blocks: 39 960 of
+ * 40 128): 418 per block.  The headers are never longer than the standard ones, a table of the frame's own listing at most
+ * the 12 DC and 162 AC symbols that Annex K's lists.  Without the bit the value is what it always was. */
 static inline size_t lr_jpeg_bound(int width, int height, int format, int layout) {
     size_t mcu, bpm, ri, mcus;
+    const size_t block = (layout & LR_JPEG_OPTIMIZE) ? 418 : 416;
+    if (layout >= 0) layout &= ~LR_JPEG_OPTIMIZE;
     if (width < 1 || height < 1 || width > 65535 || height > 65535) return 0;
     if (format == LR_PIX_U8 && layout == 0) {
         mcu = 8; bpm = 1; ri = 96;
@@ -397,7 +415,7 @@ static inline size_t lr_jpeg_bound(int width, int height, int format, int layout
         return 0;
     }
     mcus = (((size_t)width + mcu - 1) / mcu) * (((size_t)height + mcu - 1) / mcu);
-    return 640 + 2 * ((mcus + ri - 1) / ri) + 416 * mcus * bpm;
+    return 640 + 2 * ((mcus + ri - 1) / ri) + block * mcus * bpm;
 }
 
 /* The demo's inputs are JPEG files as well (autorectify.cpp: imread): lr_decode_jpeg_device decodes baseline JPEG streams

@@ -82,6 +82,7 @@ WARP_PREPARE = 0x100  # enum lr_warp_option, or-ed into the format of lr_warp_pe
 WARP_PACKED = 0x200  # enum lr_warp_layout, likewise: per-frame output sizes and places (warp_table)
 WARP_RAGGED = 0x800  # enum lr_warp_sources, likewise: per-frame source sizes and places as well (ragged_table)
 WARP_LINES = 0x1000  # enum lr_warp_lines, likewise: lr_draw_lines_device, whose own arguments travel behind M (DrawLinesArgs)
+JPEG_OPTIMIZE = 0x10  # enum lr_jpeg_option: added to [7] of a row of jpeg_table (its optimize=), and to lr_jpeg_bound's layout
 WARP_JPEG = 0x2000  # enum lr_warp_jpeg, likewise: lr_encode_jpeg_device, whose own arguments travel behind M (JpegArgs)
 WARP_CUBIC = 0x8000  # enum lr_warp_sampling, likewise: the warp (plain, WARP_PACKED, WARP_RAGGED) samples 4 x 4 bicubic, not bilinear
 WARP_JPEG_DECODE = 0x4000  # enum lr_warp_jpeg_decode, likewise: lr_decode_jpeg_device, whose own arguments travel behind M (JpegDecodeArgs)
@@ -344,10 +345,11 @@ def draw_table(sizes, sources, outputs, segments):
     return table.astype(np.float64)
 
 
-def jpeg_bound(width, height, fmt, layout=0):
+def jpeg_bound(width, height, fmt, layout=0, optimize=False):
     """lr_jpeg_bound: the longest stream lr_encode_jpeg_device can produce for a width x height frame of format fmt (PIX_U8,
     PIX_U8X3) and chroma layout (0 = 4:2:0, 1 = 4:4:4; 0 for PIX_U8): 416 bytes a block (1660 bits of code, every byte
-    stuffed), 2 per restart interval, 640 for the headers and the EOI.  0 for a size outside 1 .. 65535 or another format."""
+    stuffed), 2 per restart interval, 640 for the headers and the EOI.  0 for a size outside 1 .. 65535 or another format.
+    optimize=True (LR_JPEG_OPTIMIZE): 418 bytes a block, a DC code of the frame's own tables having up to 16 bits (1665)."""
     width, height = int(width), int(height)
     if not (1 <= width <= 65535 and 1 <= height <= 65535):
         return 0
@@ -360,13 +362,14 @@ def jpeg_bound(width, height, fmt, layout=0):
     else:
         return 0
     mcus = ((width + mcu - 1) // mcu) * ((height + mcu - 1) // mcu)
-    return 640 + 2 * ((mcus + ri - 1) // ri) + 416 * mcus * bpm
+    return 640 + 2 * ((mcus + ri - 1) // ri) + (418 if optimize else 416) * mcus * bpm
 
 
-def jpeg_table(sizes, sources, outputs, quality, layout=0):
+def jpeg_table(sizes, sources, outputs, quality, layout=0, optimize=False):
     """The table of lr_encode_jpeg_device: sizes: B pairs (width, height); sources: B pairs (byte_offset, row_bytes) of the
     frames in the source region; outputs: B pairs (byte_offset, capacity) of the streams' extents in the destination
-    region; quality (1 .. 100) and layout (0 = 4:2:0, 1 = 4:4:4): one value for all frames, or B values.  Returns float64
+    region; quality (1 .. 100) and layout (0 = 4:2:0, 1 = 4:4:4): one value for all frames, or B values; optimize: one bool
+    or B of them, the frames whose streams get Huffman tables of their own (JPEG_OPTIMIZE added to their [7]).  Returns float64
     (B, 8).  Rejects what can be seen without the regions: sizes outside 1 .. 65535, entries below 0 or above 2^53, a
     quality outside 1 .. 100, a layout other than 0 or 1, extents that overlap.  Needs no GPU."""
     sz = np.asarray(sizes)
@@ -396,6 +399,10 @@ def jpeg_table(sizes, sources, outputs, quality, layout=0):
     ext = sorted((int(o), int(o) + int(c)) for o, c in table[:, 4:6].tolist())
     if any(b[0] < a[1] for a, b in zip(ext, ext[1:])):
         raise ValueError("jpeg_table: two frames' extents overlap")
+    opt = np.asarray(optimize)
+    if opt.dtype != np.bool_ or opt.shape not in ((), (B,)):
+        raise ValueError("jpeg_table: optimize is True, False or B of them")
+    table[:, 7] += JPEG_OPTIMIZE * np.broadcast_to(opt, (B,)).astype(np.int64)
     return table.astype(np.float64)
 
 
@@ -463,6 +470,11 @@ def jpeg_info(streams, orient=False):
     last column is the orientation, 1 .. 8 (1: the file tells none).  Returns int32 (B, 8).  No context, no GPU."""
     region, extents = _stream_region(streams)
     return _decode_call(None, None, region, PIX_U8X3, jpeg_decode_table(extents, orient=orient), None, 0)
+
+
+def _check_jpeg_optimize(what, jpeg, jpeg_optimize):
+    if jpeg_optimize and jpeg is None:
+        raise ValueError(what + ": jpeg_optimize=True goes with jpeg=Q; without it nothing is encoded")
 
 
 def _all_streams(frames, what, orient=False):
@@ -717,16 +729,19 @@ class Context:
                                                 fmt | WARP_LINES, C.cast(C.byref(args), C.c_void_p), C.c_void_p(d_dst),
                                                 dst_bytes, 0, 0, 0))
 
-    def draw_lines_batch(self, frames, lines_list, Hs=None, jpeg=None, orient=False):
+    def draw_lines_batch(self, frames, lines_list, Hs=None, jpeg=None, orient=False, jpeg_optimize=False):
         """The demo's lines picture for a list of 8-bit frames of different shapes (all gray H x W, or all H x W x 3) and
         their segments (one LINE_DTYPE array per frame; Hs: one 3x3 per frame, or None): one upload, one
         lr_draw_lines_device call, one download.  Returns the list of H x W x 3 uint8 pictures: a loop of draw_lines.
         jpeg=Q: the pictures stay in HBM, are encoded there (lr_encode_jpeg_device, quality Q, 4:2:0) and come back as JPEG files
         (bytes): exactly the encoder's stream of the picture that jpeg=None returns.
+        jpeg_optimize=True (with jpeg=Q, else ValueError): the files are coded with Huffman tables of their own
+        (LR_JPEG_OPTIMIZE): the same pixels in fewer bytes.
         orient=True (JPEG files only): the files' EXIF orientations are applied, the call on decode_jpeg_batch(files,
         orient=True)'s arrays."""
+        _check_jpeg_optimize("draw_lines_batch", jpeg, jpeg_optimize)
         if _all_streams(frames, "draw_lines_batch", orient):
-            return self._draw_lines_streams([bytes(f) for f in frames], lines_list, Hs, jpeg, orient)
+            return self._draw_lines_streams([bytes(f) for f in frames], lines_list, Hs, jpeg, orient, jpeg_optimize)
         frames = [np.ascontiguousarray(f) for f in frames]
         if not frames or len(lines_list) != len(frames) or (Hs is not None and len(Hs) != len(frames)):
             raise ValueError("draw_lines_batch: as many line arrays (and Hs) as frames, at least one")
@@ -742,9 +757,9 @@ class Context:
         region = np.zeros(src_end, np.uint8)
         for f, (_, _, off, _) in zip(frames, info):
             region[off:off + f.size] = f.reshape(-1)
-        return self._draw_resident(self.device_upload(region), src_end, fmt, info, lines_list, Hs, jpeg)
+        return self._draw_resident(self.device_upload(region), src_end, fmt, info, lines_list, Hs, jpeg, jpeg_optimize)
 
-    def _draw_resident(self, d_src, src_bytes, fmt, frames, lines_list, Hs, jpeg):
+    def _draw_resident(self, d_src, src_bytes, fmt, frames, lines_list, Hs, jpeg, jpeg_optimize=False):
         """draw_lines_batch for frames (width, height, byte_offset, row_bytes) that lie in the src_bytes at d_src, which is
         freed here: one lr_draw_lines_device call into a fresh buffer, then the download, or with jpeg the encoder"""
         d_dst = C.c_void_p()
@@ -762,7 +777,7 @@ class Context:
             _check(lib().lr_device_malloc(self._h, dst_end, C.byref(d_dst)))
             self.draw_lines_device(d_src, src_bytes, fmt, np.concatenate(lines_list), table, d_dst.value, dst_end, H=Hs)
             if jpeg is not None:
-                return self._encode_resident(d_dst.value, dst_end, PIX_U8X3, [(w, h, off, row) for (w, h), (off, row) in zip(sizes, outputs)], jpeg, 0)
+                return self._encode_resident(d_dst.value, dst_end, PIX_U8X3, [(w, h, off, row) for (w, h), (off, row) in zip(sizes, outputs)], jpeg, 0, jpeg_optimize)
             out = self.device_download(d_dst.value, (dst_end,), np.uint8)
         finally:
             self.device_free(d_src)
@@ -770,12 +785,12 @@ class Context:
                 self.device_free(d_dst.value)
         return [out[off:off + w * h * 3].reshape(h, w, 3).copy() for (w, h), (off, _) in zip(sizes, outputs)]
 
-    def _draw_lines_streams(self, streams, lines_list, Hs, jpeg, orient=False):
+    def _draw_lines_streams(self, streams, lines_list, Hs, jpeg, orient=False, jpeg_optimize=False):
         """draw_lines_batch for JPEG files (bytes): decoded in HBM, drawn on where they lie"""
         if len(lines_list) != len(streams) or (Hs is not None and len(Hs) != len(streams)):
             raise ValueError("draw_lines_batch: as many line arrays (and Hs) as frames, at least one")
         d_src, src_bytes, fmt, frames = self._decode_resident(streams, None, "draw_lines_batch", orient)
-        return self._draw_resident(d_src, src_bytes, fmt, frames, lines_list, Hs, jpeg)
+        return self._draw_resident(d_src, src_bytes, fmt, frames, lines_list, Hs, jpeg, jpeg_optimize)
 
     def draw_lines(self, image_u8, lines, H=None):
         """The demo's lines picture of one 8-bit frame (H x W gray or H x W x 3) and the detector's segments, drawn through
@@ -799,10 +814,10 @@ class Context:
                                                 C.cast(C.byref(args), C.c_void_p), C.c_void_p(d_dst), dst_bytes, 0, 0, 0))
         return sizes
 
-    def _encode_resident(self, d_src, src_bytes, fmt, frames, quality, layout):
+    def _encode_resident(self, d_src, src_bytes, fmt, frames, quality, layout, optimize=False):
         """JPEG streams (bytes) of resident frames (width, height, byte_offset, row_bytes): one call with a modest extent per
         frame (half the frame's bytes, or its bound if that is less), a second one with jpeg_bound for the frames whose
-        streams did not fit, and a download of the streams alone."""
+        streams did not fit, and a download of the streams alone.  optimize: LR_JPEG_OPTIMIZE for every frame."""
         bpp = 3 if fmt == PIX_U8X3 else 1
         out = [None] * len(frames)
         todo = list(range(len(frames)))
@@ -810,12 +825,12 @@ class Context:
             caps = []
             for b in todo:
                 w, h = frames[b][:2]
-                bound = jpeg_bound(w, h, fmt, layout)
+                bound = jpeg_bound(w, h, fmt, layout, optimize)
                 first = w * h * bpp // 2 + 1024 if self.jpeg_first_capacity is None else int(self.jpeg_first_capacity)
                 caps.append(bound if attempt else min(bound, first))
             offs = np.concatenate([[0], np.cumsum(caps)]).astype(np.int64)
             table = jpeg_table(np.array([frames[b][:2] for b in todo], np.int64), np.array([frames[b][2:] for b in todo], np.int64),
-                               np.stack([offs[:-1], np.array(caps, np.int64)], axis=1), int(quality), int(layout))
+                               np.stack([offs[:-1], np.array(caps, np.int64)], axis=1), int(quality), int(layout), bool(optimize))
             d_dst = C.c_void_p()
             _check(lib().lr_device_malloc(self._h, int(offs[-1]), C.byref(d_dst)))
             try:
@@ -835,10 +850,12 @@ class Context:
             raise LibrectifyError("encode_jpeg: a stream longer than jpeg_bound")
         return out
 
-    def encode_jpeg_batch(self, frames, quality=95, layout=0):
+    def encode_jpeg_batch(self, frames, quality=95, layout=0, optimize=False):
         """Baseline JPEG files of a list of 8-bit frames of any sizes (all H x W, or all H x W x 3 with c0 red): one upload,
         one lr_encode_jpeg_device call (a second for frames whose streams outgrow half their pixels' bytes), and a download
-        of the streams only.  layout: 0 = 4:2:0, 1 = 4:4:4 (colour frames).  Returns a list of bytes."""
+        of the streams only.  layout: 0 = 4:2:0, 1 = 4:4:4 (colour frames).  optimize=True: every file is coded with Huffman
+        tables made from its own symbols (LR_JPEG_OPTIMIZE; PIL's optimize=True): the same pixels in fewer bytes.  Returns a
+        list of bytes."""
         frames = [np.ascontiguousarray(f) for f in frames]
         if not frames:
             raise ValueError("encode_jpeg_batch: no frames")
@@ -854,13 +871,14 @@ class Context:
         region = np.concatenate([f.reshape(-1) for f in frames])
         d_src = self.device_upload(region)
         try:
-            return self._encode_resident(d_src, end, fmt, info, quality, layout)
+            return self._encode_resident(d_src, end, fmt, info, quality, layout, optimize)
         finally:
             self.device_free(d_src)
 
-    def encode_jpeg(self, image_u8, quality=95, layout=0):
-        """The baseline JPEG file (bytes) of one 8-bit frame, H x W or H x W x 3 (c0 red), encoded on the GPU."""
-        return self.encode_jpeg_batch([image_u8], quality, layout)[0]
+    def encode_jpeg(self, image_u8, quality=95, layout=0, optimize=False):
+        """The baseline JPEG file (bytes) of one 8-bit frame, H x W or H x W x 3 (c0 red), encoded on the GPU; optimize=True:
+        with Huffman tables of its own (LR_JPEG_OPTIMIZE)."""
+        return self.encode_jpeg_batch([image_u8], quality, layout, optimize)[0]
 
     def decode_jpeg_device(self, d_src, h_src, fmt, table, d_dst, dst_bytes):
         """lr_decode_jpeg_device (lr_warp_perspective_device with LR_WARP_JPEG_DECODE): the table's baseline JPEG streams in
@@ -931,11 +949,11 @@ class Context:
         orient=True: upright, by the file's EXIF orientation."""
         return self.decode_jpeg_batch([data], fmt, orient)[0]
 
-    def _rectify_streams(self, streams, min_length, refine, cfg, clip, max_size, capacity, jpeg, orient=False, interp="linear"):
+    def _rectify_streams(self, streams, min_length, refine, cfg, clip, max_size, capacity, jpeg, orient=False, interp="linear", jpeg_optimize=False):
         """rectify_batch for JPEG files: the files go up and are decoded in HBM, the pictures are handed to
         rectify_frames_device where they lie; with jpeg=Q no pixel crosses the link in either direction"""
         d_src, _, fmt, sources = self._decode_resident(streams, None, "rectify_batch", orient)
-        return self._rectify_resident(d_src, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp)
+        return self._rectify_resident(d_src, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp, jpeg_optimize)
 
     def prepare_device(self, d_src, src_image_bytes, batch, width, height, src_row_bytes, fmt, d_dst, dst_image_bytes,
                        out_width, out_height, dst_row_bytes):
@@ -995,7 +1013,7 @@ class Context:
                     self.device_free(p.value)
 
     def rectify(self, image_u8, min_length=None, refine=False, cfg=None, clip=3.0, max_size=None, jpeg=None, orient=False,
-                interp="linear"):
+                interp="linear", jpeg_optimize=False):
         """The reference demo's pipeline (autorectify.cpp) on an 8-bit frame (H x W gray or H x W x 3 RGB): luma
         (4899 R + 9617 G + 1868 B + 8192) >> 14, / 256, find_line_segment_groups with min_length max(w, h) / 100 by
         default, compute_rectification_transform (cfg: the demo's, horizontal_vp_min_distance = 2),
@@ -1007,14 +1025,16 @@ class Context:
         min_length max(w', h') / 100, the endpoints are divided by the scale, the transform is the full frame's and the
         warp reads the same resident frame.
         jpeg=Q: `warped` is the rectified picture's JPEG file (bytes, quality Q, 4:2:0), encoded in HBM: rectify_batch's
-        path for one frame.
+        path for one frame.  jpeg_optimize=True (with jpeg=Q, else ValueError): the file is coded with Huffman tables of its
+        own (LR_JPEG_OPTIMIZE), the same pixels in fewer bytes.
         orient=True (a JPEG file only): the file's EXIF orientation is applied as it is decoded, as the demo's imread
         does: the call on decode_jpeg(file, orient=True).
         interp="cubic": the warp samples 4 x 4 bicubic (WARP_CUBIC) instead of bilinear, on every path above; lines,
         transform, homography and size are those of interp="linear", only the picture (or its JPEG file) differs."""
         cubic = _sampling_bit(interp, "rectify")
+        _check_jpeg_optimize("rectify", jpeg, jpeg_optimize)
         if isinstance(image_u8, (bytes, bytearray, memoryview)):  # a JPEG file: decoded in HBM, rectify_batch's path for one frame
-            lines, t, out = self.rectify_batch([bytes(image_u8)], min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, jpeg=jpeg, orient=orient, interp=interp)[0]
+            lines, t, out = self.rectify_batch([bytes(image_u8)], min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, jpeg=jpeg, orient=orient, interp=interp, jpeg_optimize=jpeg_optimize)[0]
             if out is None:
                 rectification_homography(t, clip)  # (raises what rectify raises for such a frame)
             return lines, t, out
@@ -1024,7 +1044,7 @@ class Context:
         if img.dtype != np.uint8 or not (img.ndim == 2 or (img.ndim == 3 and img.shape[2] == 3)):
             raise ValueError("rectify: an H x W or H x W x 3 uint8 frame")
         if jpeg is not None:
-            lines, t, stream = self.rectify_batch(img[None], min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, jpeg=jpeg, interp=interp)[0]
+            lines, t, stream = self.rectify_batch(img[None], min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, jpeg=jpeg, interp=interp, jpeg_optimize=jpeg_optimize)[0]
             if stream is None:
                 rectification_homography(t, clip)  # (raises what rectify raises for such a frame)
             return lines, t, stream
@@ -1257,16 +1277,16 @@ class Context:
                 if p.value:
                     self.device_free(p.value)
 
-    def _jpeg_results(self, d_out, total, fmt, table, quality):
+    def _jpeg_results(self, d_out, total, fmt, table, quality, optimize=False):
         """the warped pictures at d_out (rows of `table`: columns 9..12 width, height, offset, stride) as JPEG files"""
         good = [b for b in range(len(table)) if table[b, 9]]
-        streams = self._encode_resident(d_out, total, fmt, [tuple(int(v) for v in table[b, 9:13]) for b in good], quality, 0) if good else []
+        streams = self._encode_resident(d_out, total, fmt, [tuple(int(v) for v in table[b, 9:13]) for b in good], quality, 0, optimize) if good else []
         out = [None] * len(table)
         for b, s in zip(good, streams):
             out[b] = s
         return out
 
-    def _rectify_mixed(self, frames, min_length, refine, cfg, clip, max_size, capacity, jpeg=None, interp="linear"):
+    def _rectify_mixed(self, frames, min_length, refine, cfg, clip, max_size, capacity, jpeg=None, interp="linear", jpeg_optimize=False):
         """rectify_batch for a list of 8-bit frames of different shapes: all frames in one host buffer, one upload,
         rectify_frames_device, one download"""
         frames = [np.ascontiguousarray(f) for f in frames]
@@ -1283,9 +1303,9 @@ class Context:
         host = np.zeros(end, np.uint8)
         for f, (_, _, start, _) in zip(frames, sources):
             host[start: start + f.nbytes] = f.reshape(-1)
-        return self._rectify_resident(self.device_upload(host), sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp)
+        return self._rectify_resident(self.device_upload(host), sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp, jpeg_optimize)
 
-    def _rectify_resident(self, d_src, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp="linear"):
+    def _rectify_resident(self, d_src, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp="linear", jpeg_optimize=False):
         """rectify_batch for 8-bit frames (width, height, byte_offset, row_bytes) that lie at d_src, which is freed here:
         rectify_frames_device, then one download of the pictures, or with jpeg the encoder and the streams alone"""
         bpp = 3 if fmt == PIX_U8X3 else 1
@@ -1293,7 +1313,7 @@ class Context:
         try:
             lines, tfs, table, d_out, total = self.rectify_frames_device(d_src, sources, fmt, min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, capacity=capacity, interp=interp)
             if jpeg is not None:
-                streams = self._jpeg_results(d_out, total, fmt, table, jpeg) if d_out else [None] * len(sources)
+                streams = self._jpeg_results(d_out, total, fmt, table, jpeg, jpeg_optimize) if d_out else [None] * len(sources)
                 return [(lines[b], tfs[b], streams[b]) for b in range(len(sources))]
             packed = self.device_download(d_out, (total,), np.uint8) if d_out else None
         finally:
@@ -1311,7 +1331,7 @@ class Context:
         return res
 
     def rectify_batch(self, frames_u8, min_length=None, refine=False, cfg=None, clip=3.0, max_size=None, capacity=4096, jpeg=None,
-                      orient=False, interp="linear"):
+                      orient=False, interp="linear", jpeg_optimize=False):
         """Context.rectify for a batch: frames_u8 is a uint8 array [B, H, W] or [B, H, W, 3], or a list of such frames of one
         shape.  One upload, rectify_batch_device (one detector batch, the packed warp), one download.  Returns a
         list of (lines, transform, warped), frame by frame what rectify returns for it; warped is None for a frame whose
@@ -1322,6 +1342,8 @@ class Context:
         colour frames); `warped` is then the JPEG file as bytes -- exactly the encoder's stream of the picture that jpeg=None
         returns -- and only the streams' lengths and the streams cross the link.  A frame whose stream outgrows a first
         extent of half its pixels' bytes is encoded again with room for jpeg_bound, so nothing is ever cut.
+        jpeg_optimize=True (with jpeg=Q, else ValueError): every file is coded with Huffman tables made from its own symbols
+        (LR_JPEG_OPTIMIZE): the same pixels, about 15 % fewer bytes at quality 95.
         A list of JPEG files (bytes; all of them, else ValueError) in place of the frames: the files are uploaded and
         decoded in HBM (lr_decode_jpeg_device; u8x3, or u8 if every file has one component) and handed to
         rectify_frames_device where they lie -- bit for bit the call on decode_jpeg_batch's arrays (decode_jpeg_batch(files,
@@ -1331,12 +1353,13 @@ class Context:
         interp="cubic": the warp launch of whichever path is taken samples 4 x 4 bicubic (WARP_CUBIC); detector, transforms,
         sizes and the encoder are untouched -- frame by frame what rectify(interp="cubic") returns."""
         _sampling_bit(interp, "rectify_batch")
+        _check_jpeg_optimize("rectify_batch", jpeg, jpeg_optimize)
         if _all_streams(frames_u8, "rectify_batch", orient):
-            return self._rectify_streams([bytes(f) for f in frames_u8], min_length, refine, cfg, clip, max_size, capacity, jpeg, orient, interp)
+            return self._rectify_streams([bytes(f) for f in frames_u8], min_length, refine, cfg, clip, max_size, capacity, jpeg, orient, interp, jpeg_optimize)
         if not isinstance(frames_u8, np.ndarray):
             frames_u8 = [np.asarray(f) for f in frames_u8]
             if len({f.shape for f in frames_u8}) > 1:
-                return self._rectify_mixed(frames_u8, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp)
+                return self._rectify_mixed(frames_u8, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp, jpeg_optimize)
         a = np.ascontiguousarray(frames_u8 if isinstance(frames_u8, np.ndarray) else np.stack([np.asarray(f) for f in frames_u8]))
         if a.dtype != np.uint8 or a.ndim not in (3, 4) or (a.ndim == 4 and a.shape[3] != 3) or a.shape[0] < 1:
             raise ValueError("rectify_batch: uint8 frames [B, H, W] or [B, H, W, 3]")
@@ -1347,7 +1370,7 @@ class Context:
         try:
             lines, tfs, table, d_out, total = self.rectify_batch_device(d_src, batch, w, h, fmt, min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, capacity=capacity, interp=interp)
             if jpeg is not None:
-                streams = self._jpeg_results(d_out, total, fmt, table, jpeg) if d_out else [None] * batch
+                streams = self._jpeg_results(d_out, total, fmt, table, jpeg, jpeg_optimize) if d_out else [None] * batch
                 return [(lines[b], tfs[b], streams[b]) for b in range(batch)]
             packed = self.device_download(d_out, (total,), np.uint8) if d_out else None
         finally:

@@ -127,12 +127,14 @@ struct OverlayStore {
 
 // lr_encode_jpeg_device (kernels_jpeg.hip): a call's frame records, prefix tables and code tables going up and the streams'
 // lengths coming back (block), the quantised coefficients (2 bytes per sample of the padded components), the restart
-// intervals' lengths and places in their streams; all sized by the call
+// intervals' lengths and places in their streams, and for the frames with LR_JPEG_OPTIMIZE the counters of their symbols (544
+// a frame, zeroed on the stream by every call that counts); all sized by the call
 struct JpegStore {
     MirroredBuffer<unsigned char> block;
     DeviceBuffer<int16_t> coef;
     DeviceBuffer<uint32_t> len;
     DeviceBuffer<unsigned long long> place;
+    DeviceBuffer<unsigned long long> counts;
 };
 
 // lr_decode_jpeg_device (kernels_jpeg_decode.hip): a call's frame records (code tables and divisors in them), prefix tables

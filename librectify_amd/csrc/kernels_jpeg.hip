@@ -19,6 +19,21 @@
 // Entropy coding runs twice so that no staging buffer of worst-case size (416 bytes a block) is needed between 2 and 4: the
 // workspace holds the coefficients (2 bytes a sample), 4 bytes and 8 bytes an interval.  Every store into the destination
 // is guarded by the frame's capacity; all device writes are ordinary C++ stores (and LDS atomics).
+//
+// LR_JPEG_OPTIMIZE (tests/numpy_jpeg_optimize_ref.py): a frame that asks is coded with Huffman
+// tables made from its own symbols.  A call with such a frame runs  transform, count, tables, lengths, places, placement:
+//
+//   count          Step 2's walk over the blocks in a third mode of the sink: every table look-up becomes an LDS atomic on
+//                  a histogram laid out like the code table (2 x (256 AC + 16 DC)); a wavefront takes a run of
+//                  neighbouring intervals and adds the non-zero bins to the frame's 64-bit counters when it leaves the frame.
+//   tables         A workgroup per optimised frame, a wavefront per table (DC 0, AC 0, DC 1, AC 1): Annex K.2's merges with
+//                  the 257 entries in registers (a lane holds five) and wave reductions for the two minima, the K.3 limit
+//                  to 16 bits, the canonical codes into the frame's 544-word code table, and the four DHT segments and the
+//                  header's new length into the frame's device record (the segments that follow them move up).
+//
+// Lengths and placement then run in their per-frame-table instantiation (the table is loaded into LDS again whenever the
+// interval's frame changes; table 0 of the array is Annex K's, for frames of the call that did not ask).  A call without
+// such a frame launches the four kernels above in the instantiations it always had.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -36,6 +51,8 @@ constexpr int kWave = 64;
 constexpr int kIntervalBlocks = 96;  // blocks of a restart interval (two per lane, 64 lanes: up to 128)
 constexpr int kBlockWords = 52;      // a block's longest code, 22 + 63 * 26 = 1660 bits, in 32-bit words
 constexpr int kBitWords = kIntervalBlocks * kBlockWords + 2;
+constexpr int kBlockWordsOpt = 53;   // with a frame's own tables a DC code can have 16 bits: 27 + 63 * 26 = 1665 bits
+constexpr int kBitWordsOpt = kIntervalBlocks * kBlockWordsOpt + 2;
 constexpr int kDummyDC = 0x7FFF;     // in a block's DC: a 4:2:0 luminance block wholly outside the frame (coded as diff 0, EOB)
 constexpr int kHeaderMax = 640;
 constexpr int kHuffWords = 2 * 272;  // per table class: 256 AC symbols, then 16 DC categories; entry = code | length << 16
@@ -46,7 +63,9 @@ struct JpegFrame {
     unsigned long long src_off, src_row, dst_off, cap;  // bytes, from d_src and d_dst
     int w, h, mcus_x, n_mcus;
     int bpm, ri, n_intervals, hdr_len;  // blocks per MCU, MCUs per interval
-    int layout, pad[3];
+    int layout;
+    int opt;              // 0: Annex K's tables; else the frame's place in the array of code tables (and, less one, of counters)
+    int dht_at, tail_at;  // in hdr: the first DHT segment, the first segment behind the last
     uint16_t q[2][64];  // divisors in zig-zag order: luminance, chrominance
     uint8_t hdr[kHeaderMax];
 };
@@ -174,16 +193,25 @@ __device__ __forceinline__ int previous_block(int j, int layout) {
     return kb >= 4 ? j - 6 : (kb == 0 ? j - 3 : j - 1);
 }
 
-// Counts (kWrite = false) or writes the code of one block: `c` its 64 coefficients, two to a word.  The writer keeps up to
-// 31 bits in front of the next 32-bit boundary of the bit string and ors whole words into it.
-template <bool kWrite>
+// Counts the bits (kLength), writes the code (kWrite) or counts the symbols (kSymbols) of one block: `c` its 64
+// coefficients, two to a word.  The writer keeps up to 31 bits in front of the next 32-bit boundary of the bit string and
+// ors whole words into it.  The symbol counter takes a histogram in LDS where the others take the code table: a look-up
+// adds one to the symbol's bin and nothing is put.
+enum { kLength = 0, kWrite = 1, kSymbols = 2 };
+template <int kMode>
 struct BitSink {
     unsigned long long acc = 0;
     int n = 0, word = 0;
     uint32_t total = 0;
     uint32_t* out = nullptr;
+    __device__ __forceinline__ uint32_t entry(const uint32_t* table, int symbol) { return table[symbol]; }
+    __device__ __forceinline__ uint32_t entry(uint32_t* histogram, int symbol) {
+        atomicAdd(&histogram[symbol], 1u);
+        return 0;
+    }
     __device__ __forceinline__ void put(uint32_t bits, int len) {
-        if (!kWrite) {
+        if (kMode == kSymbols) return;
+        if (kMode == kLength) {
             total += (uint32_t)len;
             return;
         }
@@ -195,7 +223,7 @@ struct BitSink {
         }
     }
     __device__ __forceinline__ void finish() {
-        if (kWrite && n > 0) atomicOr(&out[word], (uint32_t)(acc << (32 - n)));
+        if (kMode == kWrite && n > 0) atomicOr(&out[word], (uint32_t)(acc << (32 - n)));
     }
 };
 
@@ -205,8 +233,8 @@ __device__ __forceinline__ uint32_t with_magnitude(uint32_t entry, int v, int ca
     return ((entry & 0xFFFFu) << cat) | mag;
 }
 
-template <bool kWrite>
-__device__ __forceinline__ void encode_block(BitSink<kWrite>& sink, const uint4* __restrict__ p, int diff, const uint32_t* huff) {
+template <int kMode, typename Table>
+__device__ __forceinline__ void encode_block(BitSink<kMode>& sink, const uint4* __restrict__ p, int diff, Table* huff) {
     uint32_t c[32];
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -219,7 +247,7 @@ __device__ __forceinline__ void encode_block(BitSink<kWrite>& sink, const uint4*
     int len;
     {
         const int cat = 32 - __clz(diff < 0 ? -diff : diff);
-        const uint32_t bits = with_magnitude(huff[256 + cat], diff, cat, &len);
+        const uint32_t bits = with_magnitude(sink.entry(huff, 256 + cat), diff, cat, &len);
         sink.put(bits, len);
     }
     int run = 0;
@@ -230,26 +258,26 @@ __device__ __forceinline__ void encode_block(BitSink<kWrite>& sink, const uint4*
             ++run;
         } else {
             while (run >= 16) {
-                const uint32_t zrl = huff[0xF0];
+                const uint32_t zrl = sink.entry(huff, 0xF0);
                 sink.put(zrl & 0xFFFFu, (int)(zrl >> 16));
                 run -= 16;
             }
             const int cat = 32 - __clz(v < 0 ? -v : v);
-            const uint32_t bits = with_magnitude(huff[(run << 4) | cat], v, cat, &len);
+            const uint32_t bits = with_magnitude(sink.entry(huff, (run << 4) | cat), v, cat, &len);
             sink.put(bits, len);
             run = 0;
         }
     }
     if (run > 0) {
-        const uint32_t eob = huff[0x00];
+        const uint32_t eob = sink.entry(huff, 0x00);
         sink.put(eob & 0xFFFFu, (int)(eob >> 16));
     }
 }
 
 // both of a lane's blocks (2 lane, 2 lane + 1 of the interval's nb)
-template <bool kWrite>
-__device__ __forceinline__ void encode_lane(BitSink<kWrite>& sink, const int16_t* __restrict__ blocks, int lane, int nb, int layout,
-                                            const uint32_t* s_huff) {
+template <int kMode, typename Table>
+__device__ __forceinline__ void encode_lane(BitSink<kMode>& sink, const int16_t* __restrict__ blocks, int lane, int nb, int layout,
+                                            Table* s_huff) {
 #pragma unroll 1
     for (int s = 0; s < 2; ++s) {
         const int j = 2 * lane + s;
@@ -269,20 +297,23 @@ __device__ __forceinline__ void encode_lane(BitSink<kWrite>& sink, const int16_t
         int kb = 0;
         if (layout == k444) kb = j % 3;
         else if (layout == k420) kb = j % 6 < 4 ? 0 : 1;
-        encode_block<kWrite>(sink, reinterpret_cast<const uint4*>(blocks + (size_t)j * 64), diff, s_huff + (kb != 0 ? 272 : 0));
+        encode_block(sink, reinterpret_cast<const uint4*>(blocks + (size_t)j * 64), diff, s_huff + (kb != 0 ? 272 : 0));
     }
 }
 
-template <bool kPlace>
+// kPerFrame: the frames' own code tables (JpegFrame::opt, table 0 Annex K's), loaded again when the interval's frame changes
+template <bool kPlace, bool kPerFrame>
 __global__ __launch_bounds__(kWave) void jpeg_entropy_kernel(const int16_t* __restrict__ coef, int batch, int n_intervals,
                                                              const JpegFrame* __restrict__ frames, const int* __restrict__ ivl_start,
                                                              const int* __restrict__ grp_start, const uint32_t* __restrict__ huff,
                                                              uint32_t* __restrict__ len, const unsigned long long* __restrict__ place,
                                                              uint8_t* __restrict__ dst) {
-    __shared__ uint32_t s_bits[kBitWords];
+    __shared__ uint32_t s_bits[kPerFrame ? kBitWordsOpt : kBitWords];
     __shared__ uint32_t s_huff[kHuffWords];
     const int lane = (int)threadIdx.x;
-    for (int i = lane; i < kHuffWords; i += kWave) s_huff[i] = huff[i];
+    int loaded = -1;
+    if (!kPerFrame)
+        for (int i = lane; i < kHuffWords; i += kWave) s_huff[i] = huff[i];
     for (int it = (int)blockIdx.x; it < n_intervals; it += (int)gridDim.x) {
         const int b = frame_of_tile(ivl_start, batch, it);
         const JpegFrame* f = frames + b;
@@ -290,10 +321,15 @@ __global__ __launch_bounds__(kWave) void jpeg_entropy_kernel(const int16_t* __re
         const int first_mcu = ii * f->ri;
         const int nb = min(f->ri, f->n_mcus - first_mcu) * f->bpm;
         const int16_t* blocks = coef + ((size_t)grp_start[b] * 8 + (size_t)first_mcu * f->bpm) * 64;
+        if (kPerFrame && f->opt != loaded) {
+            __syncthreads();  // (the previous interval's codes have been looked up)
+            loaded = f->opt;
+            for (int i = lane; i < kHuffWords; i += kWave) s_huff[i] = huff[(size_t)loaded * kHuffWords + i];
+        }
         __syncthreads();  // (the table is there; the previous interval's bytes have been read)
 
-        BitSink<false> counter;
-        encode_lane<false>(counter, blocks, lane, nb, layout, s_huff);
+        BitSink<kLength> counter;
+        encode_lane(counter, blocks, lane, nb, layout, static_cast<const uint32_t*>(s_huff));
         uint32_t incl = counter.total;
 #pragma unroll
         for (int d = 1; d < kWave; d <<= 1) {
@@ -305,11 +341,11 @@ __global__ __launch_bounds__(kWave) void jpeg_entropy_kernel(const int16_t* __re
         for (int i = lane; i < n_words; i += kWave) s_bits[i] = 0;
         __syncthreads();
 
-        BitSink<true> writer;
+        BitSink<kWrite> writer;
         writer.out = s_bits;
         writer.word = (int)(pos0 >> 5);
         writer.n = (int)(pos0 & 31u);
-        encode_lane<true>(writer, blocks, lane, nb, layout, s_huff);
+        encode_lane(writer, blocks, lane, nb, layout, static_cast<const uint32_t*>(s_huff));
         writer.finish();
         if (lane == 0 && (total & 7u)) {  // ones up to the byte boundary (which is never beyond the word's)
             const uint32_t o = total & 31u, padn = 8u - (total & 7u);
@@ -343,6 +379,242 @@ __global__ __launch_bounds__(kWave) void jpeg_entropy_kernel(const int16_t* __re
             if (pos < cap) out[pos] = lane == 0 ? (uint8_t)0xFF : (uint8_t)(0xD0 + (ii & 7));
         }
     }
+}
+
+// LR_JPEG_OPTIMIZE, the statistics: a wavefront takes `chunk` neighbouring intervals, so that it stays with a frame as long
+// as it can; the bins are the code table's places.  Intervals of frames that did not ask are passed over.
+__global__ __launch_bounds__(kWave) void jpeg_count_kernel(const int16_t* __restrict__ coef, int batch, int n_intervals, int chunk,
+                                                           const JpegFrame* __restrict__ frames, const int* __restrict__ ivl_start,
+                                                           const int* __restrict__ grp_start, unsigned long long* __restrict__ counts) {
+    __shared__ uint32_t s_hist[kHuffWords];
+    const int lane = (int)threadIdx.x;
+    for (int i = lane; i < kHuffWords; i += kWave) s_hist[i] = 0;
+    int held = 0;  // the frame (its opt) whose symbols the histogram holds
+    auto flush = [&]() {
+        __syncthreads();
+        if (held > 0)
+            for (int i = lane; i < kHuffWords; i += kWave) {
+                const uint32_t v = s_hist[i];
+                if (v) atomicAdd(&counts[(size_t)(held - 1) * kHuffWords + i], (unsigned long long)v);
+                s_hist[i] = 0;
+            }
+        __syncthreads();
+    };
+    const int first = (int)blockIdx.x * chunk, last = min(first + chunk, n_intervals);
+    for (int it = first; it < last; ++it) {
+        const int b = frame_of_tile(ivl_start, batch, it);
+        const JpegFrame* f = frames + b;
+        if (f->opt != held) {
+            flush();
+            held = f->opt;
+        }
+        if (held == 0) continue;
+        const int first_mcu = (it - ivl_start[b]) * f->ri;
+        const int nb = min(f->ri, f->n_mcus - first_mcu) * f->bpm;
+        const int16_t* blocks = coef + ((size_t)grp_start[b] * 8 + (size_t)first_mcu * f->bpm) * 64;
+        BitSink<kSymbols> sink;
+        encode_lane(sink, blocks, lane, nb, f->layout, s_hist);
+    }
+    flush();
+}
+
+// one step of wave_min: the key of the lane the DPP control names (a lane the control or the row mask leaves out keeps its own)
+template <int kCtrl, int kRowMask>
+__device__ __forceinline__ uint32_t min_with_lane(uint32_t key) {
+    const uint32_t other = (uint32_t)__builtin_amdgcn_update_dpp((int)key, (int)key, kCtrl, kRowMask, 0xF, false);
+    return other < key ? other : key;
+}
+template <int kCtrl, int kRowMask>
+__device__ __forceinline__ unsigned long long min_with_lane(unsigned long long key) {
+    const int lo = (int)(uint32_t)key, hi = (int)(uint32_t)(key >> 32);
+    const uint32_t other_lo = (uint32_t)__builtin_amdgcn_update_dpp(lo, lo, kCtrl, kRowMask, 0xF, false);
+    const uint32_t other_hi = (uint32_t)__builtin_amdgcn_update_dpp(hi, hi, kCtrl, kRowMask, 0xF, false);
+    const unsigned long long other = ((unsigned long long)other_hi << 32) | other_lo;
+    return other < key ? other : key;
+}
+__device__ __forceinline__ uint32_t last_lane(uint32_t key) { return (uint32_t)__builtin_amdgcn_readlane((int)key, kWave - 1); }
+__device__ __forceinline__ unsigned long long last_lane(unsigned long long key) {
+    return ((unsigned long long)last_lane((uint32_t)(key >> 32)) << 32) | last_lane((uint32_t)key);
+}
+// The least of a wavefront's keys (32 or 64 bits), all 64 lanes active: within quads, half rows and rows of 16 lanes by DPP
+// swaps, then row 0 into row 1 and row 2 into row 3 (row_bcast:15), rows 0..1 into rows 2..3 (row_bcast:31); lane 63 has
+// it.  (A 64-bit __shfl_xor per step is two LDS round trips.)
+template <typename Key>
+__device__ __forceinline__ Key wave_min(Key key) {
+    key = min_with_lane<0xB1, 0xF>(key);   // quad_perm:[1,0,3,2]
+    key = min_with_lane<0x4E, 0xF>(key);   // quad_perm:[2,3,0,1]
+    key = min_with_lane<0x141, 0xF>(key);  // row_half_mirror
+    key = min_with_lane<0x140, 0xF>(key);  // row_mirror
+    key = min_with_lane<0x142, 0xA>(key);  // row_bcast:15 into rows 1 and 3
+    key = min_with_lane<0x143, 0xC>(key);  // row_bcast:31 into rows 2 and 3
+    return last_lane(key);
+}
+
+constexpr int kEntries = 257;    // 256 symbols and the pseudo-symbol that keeps the all-ones code free
+constexpr int kOwn = 5;          // entries of a lane: lane, lane + 64, ... (the fifth is lane 0's pseudo-symbol)
+// Annex K.2 over a wavefront's 257 entries: merges the two least frequent entries until one
+// is left and gives every entry its code length.  Of equal counts the larger index goes first, so an entry's key is its count
+// with the index's complement below it (all ones: no count left); Key has room for the sum of all counts above those 9 bits.
+// A lane keeps its two least keys, so the second reduction takes from every lane the least key that is not the first's.
+// An entry remembers the entry its chain was merged into: a merge is a compare per entry, not a walk along a chain.
+template <typename Key>
+__device__ __forceinline__ void code_sizes(const unsigned long long (&freq)[kOwn], int lane, int (&size)[kOwn]) {
+    constexpr Key kNoKey = ~(Key)0;
+    Key key[kOwn];
+    int root[kOwn];
+#pragma unroll
+    for (int k = 0; k < kOwn; ++k) {
+        const int idx = lane + kWave * k;
+        key[k] = freq[k] != 0 ? ((Key)freq[k] << 9) | (Key)(511 - idx) : kNoKey;
+        root[k] = idx;
+        size[k] = 0;
+    }
+    for (;;) {
+        Key l1 = kNoKey, l2 = kNoKey;
+#pragma unroll
+        for (int k = 0; k < kOwn; ++k) {
+            const Key v = key[k];
+            l2 = v < l1 ? l1 : (v < l2 ? v : l2);
+            l1 = v < l1 ? v : l1;
+        }
+        const Key m1 = wave_min(l1);
+        const Key m2 = wave_min(l1 == m1 ? l2 : l1);
+        if (m2 == kNoKey) break;
+        const int c1 = 511 - (int)(m1 & 511u), c2 = 511 - (int)(m2 & 511u);
+#pragma unroll
+        for (int k = 0; k < kOwn; ++k) {
+            if (key[k] == m1) key[k] += m2 & ~(Key)511;  // (the first keeps the sum, under its own index)
+            else if (key[k] == m2) key[k] = kNoKey;
+            if (root[k] == c1 || root[k] == c2) {  // every member of both chains gets one more bit
+                ++size[k];
+                root[k] = c1;
+            }
+        }
+    }
+}
+
+constexpr int kCountWaves = 2048;  // of jpeg_count_kernel: eight to a compute unit; more would only flush more often
+constexpr int kTableWaves = 4;   // DC 0, AC 0, DC 1, AC 1: the order of the DHT segments
+constexpr int kUnused = 0x7FFFFFFF;
+// LR_JPEG_OPTIMIZE, the tables of one frame from its counters: the code table (every word
+// of it: symbols that do not occur get 0), the DHT segments, the header's length.
+__global__ __launch_bounds__(kTableWaves* kWave) void jpeg_tables_kernel(JpegFrame* __restrict__ frames, const int* __restrict__ opt_frame,
+                                                                        const unsigned long long* __restrict__ counts,
+                                                                        uint32_t* __restrict__ huff) {
+    // a symbol's place in HUFFVAL's order: its length before the limit, its value below it (kUnused: it does not occur)
+    __shared__ __attribute__((aligned(16))) int s_order[kTableWaves][256];
+    __shared__ int s_top[kTableWaves];                  // the longest length before the limit
+    __shared__ int s_bits[kTableWaves][kEntries + 1];   // codes of a length (before the limit a length can be 256)
+    __shared__ int s_cum[kTableWaves][17], s_code[kTableWaves][17];  // symbols shorter than or of a length; the length's first code
+    __shared__ uint8_t s_dht[kTableWaves][16 + 256];    // BITS, HUFFVAL
+    const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & (kWave - 1);
+    const int o = (int)blockIdx.x;
+    JpegFrame* f = frames + opt_frame[o];
+    const int n_tables = f->layout == kGray ? 2 : 4;
+    const bool ac = wave & 1;
+    const int n_symbols = wave >= n_tables ? 0 : (ac ? 256 : 16);  // (a wave without a table goes along with no symbols)
+    const int at = (wave >> 1) * 272 + (ac ? 0 : 256);             // the table's place in the code table and the counters
+    const int tail_len = f->hdr_len - f->tail_at;
+    const uint8_t tail = tid < tail_len ? f->hdr[f->tail_at + tid] : (uint8_t)0;
+
+    unsigned long long freq[kOwn], total = 0;
+    int size[kOwn];
+#pragma unroll
+    for (int k = 0; k < kOwn; ++k) {
+        const int idx = lane + kWave * k;
+        freq[k] = idx < n_symbols ? counts[(size_t)o * kHuffWords + at + idx] : (idx == 256 ? 1ull : 0ull);
+        total += freq[k];
+    }
+#pragma unroll
+    for (int d = kWave / 2; d >= 1; d >>= 1) total += __shfl_xor(total, d);
+    // (keys of 32 bits while the sum of the table's counts stays below 2^22 -- a 4K frame's tables do -- cost a third)
+    if (total < (1ull << 22)) code_sizes<uint32_t>(freq, lane, size);
+    else code_sizes<unsigned long long>(freq, lane, size);
+    for (int i = lane; i <= kEntries; i += kWave) s_bits[wave][i] = 0;
+    if (lane == 0) s_top[wave] = 16;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kOwn; ++k) {
+        const int idx = lane + kWave * k;
+        if (idx < 256) s_order[wave][idx] = size[k] > 0 ? (size[k] << 9) | idx : kUnused;
+        if (idx < kEntries && size[k] > 0) {
+            atomicAdd(&s_bits[wave][size[k]], 1);
+            atomicMax(&s_top[wave], size[k]);
+        }
+    }
+    __syncthreads();
+    if (lane == 0) {  // K.3: no code longer than 16 bits; then the pseudo-symbol's code leaves the longest length
+        int* bits = s_bits[wave];
+        for (int i = s_top[wave]; i > 16; --i)
+            while (bits[i] > 0) {
+                int j = i - 2;
+                while (j > 0 && bits[j] == 0) --j;
+                bits[i] -= 2;
+                bits[i - 1] += 1;
+                bits[j + 1] += 2;
+                bits[j] -= 1;
+            }
+        int i = 16;
+        while (i > 0 && bits[i] == 0) --i;
+        if (i > 0) bits[i] -= 1;  // (a wave without a table has no code at all)
+        int code = 0;
+        s_cum[wave][0] = 0;
+        for (int length = 1; length <= 16; ++length) {  // Annex C
+            s_code[wave][length] = code;
+            s_cum[wave][length] = s_cum[wave][length - 1] + bits[length];
+            code = (code + bits[length]) << 1;
+        }
+    }
+    __syncthreads();
+    if (lane < 16) s_dht[wave][lane] = (uint8_t)s_bits[wave][lane + 1];
+    // HUFFVAL: by the length before the limit, within one by the symbol; a symbol's place there -- the number of symbols in
+    // front of it -- gives its length and code
+    int mine[kOwn - 1], place[kOwn - 1];
+#pragma unroll
+    for (int k = 0; k < kOwn - 1; ++k) {
+        mine[k] = size[k] > 0 ? (size[k] << 9) | (lane + kWave * k) : 0;
+        place[k] = 0;
+    }
+    const int4* order = reinterpret_cast<const int4*>(s_order[wave]);
+#pragma unroll 4
+    for (int j = 0; j < n_symbols / 4; ++j) {
+        const int4 v = order[j];
+#pragma unroll
+        for (int k = 0; k < kOwn - 1; ++k) place[k] += (v.x < mine[k]) + (v.y < mine[k]) + (v.z < mine[k]) + (v.w < mine[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < kOwn - 1; ++k) {
+        const int idx = lane + kWave * k;
+        if (idx >= n_symbols) continue;
+        uint32_t word = 0;
+        if (size[k] > 0) {
+            int length = 1;
+            while (s_cum[wave][length] <= place[k]) ++length;
+            word = (uint32_t)(s_code[wave][length] + place[k] - s_cum[wave][length - 1]) | ((uint32_t)length << 16);
+            s_dht[wave][16 + place[k]] = (uint8_t)idx;
+        }
+        huff[(size_t)(o + 1) * kHuffWords + at + idx] = word;
+    }
+    __syncthreads();
+
+    // the DHT segments one behind the other, then what followed them
+    int pos = f->dht_at;
+    for (int t = 0; t < n_tables; ++t) {
+        const int n = s_cum[t][16];
+        for (int i = tid; i < 21 + n; i += kTableWaves * kWave) {
+            uint8_t v;
+            if (i == 0) v = 0xFF;
+            else if (i == 1) v = 0xC4;
+            else if (i == 2) v = (uint8_t)((19 + n) >> 8);
+            else if (i == 3) v = (uint8_t)((19 + n) & 0xFF);
+            else if (i == 4) v = (uint8_t)(((t & 1) << 4) | (t >> 1));
+            else v = s_dht[t][i - 5];
+            if (pos + i < kHeaderMax) f->hdr[pos + i] = v;  // (always: no table has more symbols than Annex K's)
+        }
+        pos += 21 + n;
+    }
+    if (tid < tail_len && pos + tid < kHeaderMax) f->hdr[pos + tid] = tail;
+    if (tid == 0) f->hdr_len = pos + tail_len;
 }
 
 constexpr int kScanBlock = 256;
@@ -456,7 +728,7 @@ struct HeaderWriter {
 };
 
 // everything in front of the scan's first byte
-int write_header(JpegFrame& f, int components) {
+int write_header(JpegFrame& f, int components) {  // (and dht_at, tail_at: where jpeg_tables_kernel puts a frame's own tables)
     HeaderWriter h{f.hdr};
     h.byte(0xFF);
     h.byte(0xD8);
@@ -478,12 +750,14 @@ int write_header(JpegFrame& f, int components) {
         h.byte(c == 0 && f.layout == k420 ? 0x22 : 0x11);
         h.byte(c == 0 ? 0 : 1);
     }
+    f.dht_at = h.n;
     h.dht(0x00, kDcLumaBits, kDcVals, 12);
     h.dht(0x10, kAcLumaBits, kAcLumaVals, 162);
     if (components == 3) {
         h.dht(0x01, kDcChromaBits, kDcVals, 12);
         h.dht(0x11, kAcChromaBits, kAcChromaVals, 162);
     }
+    f.tail_at = h.n;
     h.marker(0xDD, 2);
     h.word(f.ri);
     h.marker(0xDA, 4 + 2 * components);
@@ -524,12 +798,14 @@ int ctx_encode_jpeg(lr_context* c, const void* d_src, size_t src_bytes, int form
     std::vector<JpegFrame> fr((size_t)batch);
     std::vector<int> grp_start((size_t)batch + 1), ivl_start((size_t)batch + 1);
     std::vector<std::pair<uint64_t, uint64_t>> extent((size_t)batch);
+    std::vector<int> opt_frame;  // the frames with LR_JPEG_OPTIMIZE
     int64_t n_groups = 0, n_intervals = 0;
     for (int b = 0; b < batch; ++b) {
         const double* t = T + (size_t)b * 8;
         JpegFrame& f = fr[(size_t)b];
         std::memset(&f, 0, sizeof f);
         uint64_t w, h, src_off, src_row, dst_off, cap, quality, layout;
+        const uint64_t max_layout = components == 3 ? 1 : 0;
         if (!table_integer(t[0], 1, 65535, &w)) return fail_at(b, 0, "(width) is not an integer from 1 to 65535");
         if (!table_integer(t[1], 1, 65535, &h)) return fail_at(b, 1, "(height) is not an integer from 1 to 65535");
         if (!table_integer(t[2], 0, kExact, &src_off)) return fail_at(b, 2, "(source offset) is not an integer from 0 to 2^53");
@@ -538,8 +814,14 @@ int ctx_encode_jpeg(lr_context* c, const void* d_src, size_t src_bytes, int form
         if (!table_integer(t[4], 0, kExact, &dst_off)) return fail_at(b, 4, "(stream offset) is not an integer from 0 to 2^53");
         if (!table_integer(t[5], 0, kExact, &cap)) return fail_at(b, 5, "(capacity) is not an integer from 0 to 2^53");
         if (!table_integer(t[6], 1, 100, &quality)) return fail_at(b, 6, "(quality) is not an integer from 1 to 100");
-        if (!table_integer(t[7], 0, components == 3 ? 1 : 0, &layout))
-            return fail_at(b, 7, components == 3 ? "(layout) is 0 (4:2:0) or 1 (4:4:4)" : "(layout) must be 0 for LR_PIX_U8");
+        if (!table_integer(t[7], 0, (double)(LR_JPEG_OPTIMIZE | max_layout), &layout) || (layout & ~(uint64_t)LR_JPEG_OPTIMIZE) > max_layout)
+            return fail_at(b, 7, components == 3 ? "(layout) is 0 (4:2:0) or 1 (4:4:4), LR_JPEG_OPTIMIZE added or not"
+                                                 : "(layout) must be 0 or LR_JPEG_OPTIMIZE for LR_PIX_U8");
+        if (layout & LR_JPEG_OPTIMIZE) {
+            opt_frame.push_back(b);
+            f.opt = (int)opt_frame.size();
+            layout &= ~(uint64_t)LR_JPEG_OPTIMIZE;
+        }
         uint64_t end;
         if (__builtin_mul_overflow(h - 1, src_row, &end) || __builtin_add_overflow(end, src_off, &end) ||
             __builtin_add_overflow(end, w * bpp, &end) || end > src_bytes)
@@ -582,11 +864,14 @@ int ctx_encode_jpeg(lr_context* c, const void* d_src, size_t src_bytes, int form
         }
     }
 
-    // one block of the mirror: frames | group prefix | interval prefix | code tables | the streams' lengths (coming back)
+    // one block of the mirror: frames | group prefix | interval prefix | the frames with LR_JPEG_OPTIMIZE | code tables: Annex
+    // K's, then one per such frame (the device's alone: made there, never copied) | the streams' lengths (coming back)
     auto up8 = [](size_t v) { return (v + 7) & ~(size_t)7; };
+    const size_t n_opt = opt_frame.size();
     const size_t o_frames = 0, o_grp = o_frames + fr.size() * sizeof(JpegFrame);
-    const size_t o_ivl = up8(o_grp + grp_start.size() * sizeof(int)), o_huff = up8(o_ivl + ivl_start.size() * sizeof(int));
-    const size_t o_sizes = up8(o_huff + kHuffWords * sizeof(uint32_t)), need = o_sizes + (size_t)batch * sizeof(unsigned long long);
+    const size_t o_ivl = up8(o_grp + grp_start.size() * sizeof(int)), o_opt = up8(o_ivl + ivl_start.size() * sizeof(int));
+    const size_t o_huff = up8(o_opt + n_opt * sizeof(int)), o_own = up8(o_huff + kHuffWords * sizeof(uint32_t));
+    const size_t o_sizes = o_own + n_opt * kHuffWords * sizeof(uint32_t), need = o_sizes + (size_t)batch * sizeof(unsigned long long);
     LR_HIP(hipSetDevice(c->device));
     JpegStore& js = c->jpeg;
     // (the call is synchronous: nothing of an earlier one is in flight when these are replaced, so the block needs neither
@@ -597,35 +882,54 @@ int ctx_encode_jpeg(lr_context* c, const void* d_src, size_t src_bytes, int form
     if (n_coef > js.coef.cap() && js.coef.grow(n_coef)) return 1;
     if ((size_t)n_intervals > js.len.cap() && js.len.grow((size_t)n_intervals)) return 1;
     if ((size_t)n_intervals > js.place.cap() && js.place.grow((size_t)n_intervals)) return 1;
+    if (n_opt * kHuffWords > js.counts.cap() && js.counts.grow(n_opt * kHuffWords)) return 1;
     unsigned char* m = js.block.h;
     std::memcpy(m + o_frames, fr.data(), fr.size() * sizeof(JpegFrame));
     std::memcpy(m + o_grp, grp_start.data(), grp_start.size() * sizeof(int));
     std::memcpy(m + o_ivl, ivl_start.data(), ivl_start.size() * sizeof(int));
+    if (n_opt) std::memcpy(m + o_opt, opt_frame.data(), n_opt * sizeof(int));
     uint32_t* codes = reinterpret_cast<uint32_t*>(m + o_huff);
     std::memset(codes, 0, kHuffWords * sizeof(uint32_t));
     huffman_codes(kAcLumaBits, kAcLumaVals, codes);
     huffman_codes(kDcLumaBits, kDcVals, codes + 256);
     huffman_codes(kAcChromaBits, kAcChromaVals, codes + 272);
     huffman_codes(kDcChromaBits, kDcVals, codes + 272 + 256);
-    LR_HIP(hipMemcpyAsync(js.block.d, m, o_sizes, hipMemcpyHostToDevice, c->stream));
+    LR_HIP(hipMemcpyAsync(js.block.d, m, o_own, hipMemcpyHostToDevice, c->stream));
 
     unsigned char* d = js.block.d.get();
-    const JpegFrame* d_frames = reinterpret_cast<const JpegFrame*>(d + o_frames);
+    JpegFrame* d_frames = reinterpret_cast<JpegFrame*>(d + o_frames);
     const int* d_grp = reinterpret_cast<const int*>(d + o_grp);
     const int* d_ivl = reinterpret_cast<const int*>(d + o_ivl);
-    const uint32_t* d_huff = reinterpret_cast<const uint32_t*>(d + o_huff);
+    uint32_t* d_huff = reinterpret_cast<uint32_t*>(d + o_huff);
     unsigned long long* d_sizes = reinterpret_cast<unsigned long long*>(d + o_sizes);
     const uint8_t* s8 = static_cast<const uint8_t*>(d_src);
     uint8_t* d8 = static_cast<uint8_t*>(d_dst);
     const int grid_t = (int)std::min<int64_t>(n_groups, 1 << 18), grid_e = (int)std::min<int64_t>(n_intervals, 1 << 16);
     hipLaunchKernelGGL(jpeg_transform_kernel, dim3(grid_t), dim3(kWave), 0, c->stream, s8, batch, (int)n_groups, d_frames, d_grp,
                        js.coef.get());
-    hipLaunchKernelGGL(jpeg_entropy_kernel<false>, dim3(grid_e), dim3(kWave), 0, c->stream, js.coef.get(), batch, (int)n_intervals,
-                       d_frames, d_ivl, d_grp, d_huff, js.len.get(), js.place.get(), d8);
-    hipLaunchKernelGGL(jpeg_place_kernel, dim3(batch), dim3(kScanBlock), 0, c->stream, d_frames, d_ivl, js.len.get(), js.place.get(),
-                       d_sizes, d8);
-    hipLaunchKernelGGL(jpeg_entropy_kernel<true>, dim3(grid_e), dim3(kWave), 0, c->stream, js.coef.get(), batch, (int)n_intervals,
-                       d_frames, d_ivl, d_grp, d_huff, js.len.get(), js.place.get(), d8);
+    if (n_opt == 0) {
+        hipLaunchKernelGGL((jpeg_entropy_kernel<false, false>), dim3(grid_e), dim3(kWave), 0, c->stream, js.coef.get(), batch,
+                           (int)n_intervals, d_frames, d_ivl, d_grp, d_huff, js.len.get(), js.place.get(), d8);
+        hipLaunchKernelGGL(jpeg_place_kernel, dim3(batch), dim3(kScanBlock), 0, c->stream, d_frames, d_ivl, js.len.get(), js.place.get(),
+                           d_sizes, d8);
+        hipLaunchKernelGGL((jpeg_entropy_kernel<true, false>), dim3(grid_e), dim3(kWave), 0, c->stream, js.coef.get(), batch,
+                           (int)n_intervals, d_frames, d_ivl, d_grp, d_huff, js.len.get(), js.place.get(), d8);
+    } else {  // LR_JPEG_OPTIMIZE: the symbols' counts and the tables made of them first, then the same with a table per frame
+        const int* d_opt = reinterpret_cast<const int*>(d + o_opt);
+        const int grid_c = (int)std::min<int64_t>(n_intervals, kCountWaves);
+        const int chunk = (int)((n_intervals + grid_c - 1) / grid_c);
+        LR_HIP(hipMemsetAsync(js.counts.get(), 0, n_opt * kHuffWords * sizeof(unsigned long long), c->stream));
+        hipLaunchKernelGGL(jpeg_count_kernel, dim3((unsigned)((n_intervals + chunk - 1) / chunk)), dim3(kWave), 0, c->stream,
+                           js.coef.get(), batch, (int)n_intervals, chunk, d_frames, d_ivl, d_grp, js.counts.get());
+        hipLaunchKernelGGL(jpeg_tables_kernel, dim3((unsigned)n_opt), dim3(kTableWaves * kWave), 0, c->stream, d_frames, d_opt,
+                           js.counts.get(), d_huff);
+        hipLaunchKernelGGL((jpeg_entropy_kernel<false, true>), dim3(grid_e), dim3(kWave), 0, c->stream, js.coef.get(), batch,
+                           (int)n_intervals, d_frames, d_ivl, d_grp, d_huff, js.len.get(), js.place.get(), d8);
+        hipLaunchKernelGGL(jpeg_place_kernel, dim3(batch), dim3(kScanBlock), 0, c->stream, d_frames, d_ivl, js.len.get(), js.place.get(),
+                           d_sizes, d8);
+        hipLaunchKernelGGL((jpeg_entropy_kernel<true, true>), dim3(grid_e), dim3(kWave), 0, c->stream, js.coef.get(), batch,
+                           (int)n_intervals, d_frames, d_ivl, d_grp, d_huff, js.len.get(), js.place.get(), d8);
+    }
     LR_HIP(hipGetLastError());
     LR_HIP(hipMemcpyAsync(m + o_sizes, d_sizes, (size_t)batch * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     LR_HIP(hipStreamSynchronize(c->stream));
