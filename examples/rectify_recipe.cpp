@@ -6,7 +6,7 @@
 //
 //   rectify_recipe in.pgm|in.ppm out_prefix [--max-size N|fraction] [--refine] [--threads N]
 //                  [--h-strategy rotate_h|rotate_v|rectify|keep] [--v-strategy ...] [--warp] [--device-prepare] [--lines]
-//                  [--jpeg Q] [--optimize] [--jpeg-in] [--orient] [--cubic]
+//                  [--jpeg Q] [--optimize] [--jpeg-in] [--orient] [--any-sampling] [--cubic]
 //
 // Input is a binary PGM (P5, 8 bit) or PPM (P6, 8 bit; converted with the usual integer luma weights
 // (4899 R + 9617 G + 1868 B + 8192) >> 14).  Image decoding stays with the caller's imaging library.
@@ -32,6 +32,9 @@
 // --orient (with --jpeg-in alone): the file's EXIF orientation is applied as the demo's imread applies it -- entry [7] of the
 // frame's row is 1 for lr_jpeg_info, which then tells the upright size, and for lr_decode_jpeg_device, whose output pass
 // writes the upright picture; that one goes on to prepare, detect and warp.  Without it the picture is the stored one.
+// --any-sampling (with --jpeg-in alone): LR_JPEG_ANY_SAMPLING is or-ed into the format of lr_decode_jpeg_device (lr_jpeg_info
+// is that call in probe mode, so the same word goes to both): a file of 4:4:0 (a losslessly rotated 4:2:2 photograph), 4:1:1 or
+// any other sampling with factors 1, 2 or 4 is decoded, which without the option is refused with status 2.
 // --cubic (with --warp or --jpeg alone; it implies neither): the warp samples 4 x 4 bicubic, cv::warpPerspective's INTER_CUBIC
 // (LR_WARP_CUBIC or-ed into the warp's format word), instead of bilinear.  Everything else is as without it.
 // Links against librectify_amd.so exactly like a program written for the reference.
@@ -105,7 +108,7 @@ bool load_pnm(const std::string& path, Gray& g) {
 }
 
 // --jpeg-in: the file decoded on the GPU into g.raw (and g.px, for --lines).  Returns false with the reason on stderr.
-bool load_jpeg(const std::string& path, bool orient, Gray& g) {
+bool load_jpeg(const std::string& path, bool orient, bool any_sampling, Gray& g) {
     std::ifstream f(path, std::ios::binary);
     std::vector<uint8_t> file((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
     if (!f || file.empty()) {
@@ -114,7 +117,9 @@ bool load_jpeg(const std::string& path, bool orient, Gray& g) {
     }
     double frame[8] = {0, (double)file.size(), 0, 0, 0, 0, 0, orient ? 1.0 : 0.0};
     int32_t info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (lr_jpeg_info(file.data(), file.size(), frame, 1, info) != 0 || info[5] != 0) {
+    const int option = any_sampling ? LR_JPEG_ANY_SAMPLING : 0;
+    // (lr_jpeg_info spelled out, for the option: the decoder call without a destination and without a context)
+    if (lr_decode_jpeg_device(nullptr, nullptr, file.data(), file.size(), LR_PIX_U8X3 | option, frame, 1, nullptr, 0, info) != 0 || info[5] != 0) {
         std::fprintf(stderr, "jpeg input failed: %s\n", lr_last_error());
         return false;
     }
@@ -130,7 +135,7 @@ bool load_jpeg(const std::string& path, bool orient, Gray& g) {
     void* d_img = nullptr;
     const bool ok = lr_context_create(0, &ctx) == 0 && lr_device_malloc(ctx, file.size(), &d_file) == 0 &&
                     lr_device_malloc(ctx, g.raw.size(), &d_img) == 0 && lr_memcpy_h2d(ctx, d_file, file.data(), file.size()) == 0 &&
-                    lr_decode_jpeg_device(ctx, d_file, file.data(), file.size(), g.ch == 3 ? LR_PIX_U8X3 : LR_PIX_U8, frame, 1, d_img,
+                    lr_decode_jpeg_device(ctx, d_file, file.data(), file.size(), (g.ch == 3 ? LR_PIX_U8X3 : LR_PIX_U8) | option, frame, 1, d_img,
                                           g.raw.size(), info) == 0 &&
                     info[5] == 0 && lr_memcpy_d2h(ctx, g.raw.data(), d_img, g.raw.size()) == 0;
     if (!ok) std::fprintf(stderr, "jpeg input failed: %s\n", lr_last_error());
@@ -364,12 +369,12 @@ int main(int argc, char** argv) {
         std::fprintf(stderr,
                      "usage: %s in.pgm|in.ppm out_prefix [--max-size N|fraction] [--refine] [--threads N]\n"
                      "          [--h-strategy rotate_h|rotate_v|rectify|keep] [--v-strategy ...] [--warp] [--device-prepare]\n"
-                     "          [--lines] [--jpeg Q] [--optimize] [--jpeg-in] [--orient] [--cubic]\n",
+                     "          [--lines] [--jpeg Q] [--optimize] [--jpeg-in] [--orient] [--any-sampling] [--cubic]\n",
                      argv[0]);
         return 2;
     }
     float max_size = 1200.f;  // the demo's default
-    bool refine = false, warp = false, device_prepare = false, lines_pictures = false, jpeg_in = false, orient = false, cubic = false;
+    bool refine = false, warp = false, device_prepare = false, lines_pictures = false, jpeg_in = false, orient = false, any_sampling = false, cubic = false;
     bool optimize = false;
     int threads = -1, jpeg = 0;
     RectificationConfig cfg;
@@ -383,6 +388,7 @@ int main(int argc, char** argv) {
         else if (a == "--lines") lines_pictures = true;
         else if (a == "--jpeg-in") jpeg_in = device_prepare = true;
         else if (a == "--orient") orient = true;
+        else if (a == "--any-sampling") any_sampling = true;
         else if (a == "--cubic") cubic = true;
         else if (a == "--optimize") optimize = true;
         else if (a == "--max-size" && has_val) max_size = (float)std::atof(argv[++i]);
@@ -402,6 +408,10 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--orient goes with --jpeg-in: a PGM or PPM file carries no EXIF orientation\n");
         return 2;
     }
+    if (any_sampling && !jpeg_in) {
+        std::fprintf(stderr, "--any-sampling goes with --jpeg-in: a PGM or PPM file has no chroma sampling\n");
+        return 2;
+    }
     if (optimize && jpeg <= 0) {
         std::fprintf(stderr, "--optimize goes with --jpeg Q: it is the encoder's choice of Huffman tables\n");
         return 2;
@@ -412,7 +422,7 @@ int main(int argc, char** argv) {
     }
     Gray full;
     if (jpeg_in) {
-        if (!load_jpeg(argv[1], orient, full)) return 1;
+        if (!load_jpeg(argv[1], orient, any_sampling, full)) return 1;
     } else if (!load_pnm(argv[1], full)) {
         std::fprintf(stderr, "cannot read %s (binary PGM/PPM, 8 bit, expected)\n", argv[1]);
         return 1;

@@ -433,7 +433,8 @@ static inline size_t lr_jpeg_bound(int width, int height, int format, int layout
  * table error (also a null pointer, batch < 1, another format) nothing is launched or written, `info` is untouched and
  * lr_last_error names the frame and the entry.
  * `info` (HOST, 8 int32 per frame, written by the call): [0] width, [1] height, [2] components (1 or 3), [3] layout (0 =
- * 4:2:0 or one component, 1 = 4:4:4, 2 = 4:2:2), [4] restart interval in MCUs (0: none), [5] status, [6] the most often
+ * 4:2:0 or one component, 1 = 4:4:4, 2 = 4:2:2; with LR_JPEG_ANY_SAMPLING, below, any other accepted sampling: component 0's
+ * sampling byte), [4] restart interval in MCUs (0: none), [5] status, [6] the most often
  * any part of the scan had to be entropy-decoded until the chain of parts was consistent (see below; 0 in probe mode), [7] 0,
  * or for a frame whose entry [7] is 1 the orientation that was read, 1..8.
  * Status: 0 decoded; 1 not a JPEG stream, or truncated before SOS; 2 unsupported (progressive, arithmetic, lossless or
@@ -455,6 +456,24 @@ static inline size_t lr_jpeg_bound(int width, int height, int format, int layout
  * the orientation, the table's [4] [5] and the stride [3] are held against the size of O (status 3 and its message speak of
  * that size), and probe mode does the same: probe with [7] = 1, allocate info [0] x info [1], decode with [7] = 1.
  * With [7] = 0 the call does and reports what it did before entry [7] had a meaning, and info [7] is 0.
+ * Any sampling: LR_JPEG_ANY_SAMPLING (0x20000) or-ed into `format` beside the pixel format applies to the whole call, probe
+ * mode included (lr_jpeg_info passes LR_PIX_U8X3 alone; with the option call lr_decode_jpeg_device with d_dst == NULL).
+ * Without it a three-component stream is 4:4:4, 4:2:2 (Y 2x1) or 4:2:0 (Y 2x2) with Cb = Cr = 1x1, or its status is 2.
+ * With it a three-component stream that passes every other check is accepted if every h_i, v_i is 1, 2 or 4, component 0
+ * has the largest factors (h_0 = Hmax, v_0 = Vmax, so Hmax / h_i and Vmax / v_i are 1, 2 or 4; Cb and Cr may differ) and
+ * the sum of h_i * v_i is at most 10 (T.81 B.2.3): 4:4:0 (Y 1x2, what a lossless rotation makes of 4:2:2), 4:1:1 (Y 4x1),
+ * equal non-unit factors, and the like.  Status 2 stays: luminance sampled below chrominance, a factor of 3, four
+ * components, non-interleaved, multi-scan and progressive files.  A one-component stream is one block to the MCU whatever
+ * its header's factors say, with the option and without.  An MCU is 8 Hmax x 8 Vmax pixels, its blocks component by
+ * component, each as v_i rows of h_i blocks; component i's own grid is ceil(w h_i / Hmax) x ceil(h v_i / Vmax) samples, and
+ * coordinates are clamped to it.  Upsampling, exact and in integers, per axis by the ratio r of the largest factor to the
+ * component's: r = 1 the sample; r = 2 the centred triangle, (3 near + far + 2) >> 2 on one axis and (9, 3, 3, 1) + 8 >> 4 on
+ * both, near = x >> 1, far its neighbour on the side of x's parity, clamped; r = 4 the sample x >> 2 (replication, as the
+ * IJG library does where it has no triangle); r = 4 on one axis and 2 on the other: the triangle along the ratio-2 axis over
+ * the replicated samples.  The IDCT and the colour rule are the same.  The three layouts are special cases: with the
+ * option they come out byte for byte as without it, and info [3] keeps 0, 1, 2 for them; for every other accepted sampling
+ * info [3] is component 0's sampling byte of SOF (h << 4 | v: 0x12 = 18 for 4:4:0, 0x41 = 65 for 4:1:1), which cannot
+ * collide with 0..2.  Without the option every call does, reports and launches exactly what it did before there was one.
  * The tag: of the segments before SOS the first APP1 whose payload starts with "Exif\0\0" counts and later ones do not
  * (other APP1 segments, XMP for one, are passed over).  Behind those six bytes lies a TIFF block: "II*\0" (little endian)
  * or "MM\0*" (big endian), a 32-bit offset of IFD0 from the block's start, there a 16-bit count and 12-byte entries (tag,
@@ -473,13 +492,15 @@ static inline size_t lr_jpeg_bound(int width, int height, int format, int layout
  * the context's workspace: lr_context_trim frees them.
  * The call travels through lr_warp_perspective_device like lr_encode_jpeg_device: LR_WARP_JPEG_DECODE or-ed into `format`,
  * `M` pointing to an lr_jpeg_decode_args, src_image_bytes and dst_image_bytes the two regions' sizes, and width, height,
- * out_width, out_height and both row strides 0 (any other option bit or a non-zero one of these fails cleanly). */
+ * out_width, out_height and both row strides 0 (any option bit but LR_JPEG_ANY_SAMPLING, or a non-zero one of these,
+ * fails cleanly). */
 typedef struct lr_jpeg_decode_args {
     const void* h_src;    /* HOST copy of the stream region (same layout as d_src); only the headers are read from it */
     const double* frames; /* HOST, 8 doubles per frame */
     int32_t* info;        /* HOST, 8 int32 per frame, written by the call */
 } lr_jpeg_decode_args;
 enum lr_warp_jpeg_decode { LR_WARP_JPEG_DECODE = 0x4000 }; /* or-ed into `format` like lr_warp_option */
+enum lr_jpeg_decode_option { LR_JPEG_ANY_SAMPLING = 0x20000 }; /* or-ed into lr_decode_jpeg_device's `format` (see above) */
 static inline int lr_decode_jpeg_device(lr_context* ctx, const void* d_src, const void* h_src, size_t src_bytes, int format,
                                         const double* frames, int batch, void* d_dst, size_t dst_bytes, int32_t* info) {
     lr_jpeg_decode_args a;

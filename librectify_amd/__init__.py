@@ -85,6 +85,7 @@ WARP_LINES = 0x1000  # enum lr_warp_lines, likewise: lr_draw_lines_device, whose
 JPEG_OPTIMIZE = 0x10  # enum lr_jpeg_option: added to [7] of a row of jpeg_table (its optimize=), and to lr_jpeg_bound's layout
 WARP_JPEG = 0x2000  # enum lr_warp_jpeg, likewise: lr_encode_jpeg_device, whose own arguments travel behind M (JpegArgs)
 WARP_CUBIC = 0x8000  # enum lr_warp_sampling, likewise: the warp (plain, WARP_PACKED, WARP_RAGGED) samples 4 x 4 bicubic, not bilinear
+JPEG_ANY_SAMPLING = 0x20000  # enum lr_jpeg_decode_option: or-ed into lr_decode_jpeg_device's format, it admits every sampling with factors 1, 2, 4
 WARP_JPEG_DECODE = 0x4000  # enum lr_warp_jpeg_decode, likewise: lr_decode_jpeg_device, whose own arguments travel behind M (JpegDecodeArgs)
 JPEG_OK, JPEG_NOT_JPEG, JPEG_UNSUPPORTED, JPEG_SIZE_MISMATCH, JPEG_DAMAGED = range(5)  # info[5] of lr_decode_jpeg_device
 FRAMES_U8, FRAMES_U8X3, FRAMES_F32 = 0x100, 0x200, 0x300  # enum lr_frames_option, or-ed into `refine` of the frame entries
@@ -463,13 +464,20 @@ def _decode_call(handle, d_src, region, fmt, table, d_dst, dst_bytes):
     return info
 
 
-def jpeg_info(streams, orient=False):
+def jpeg_info(streams, orient=False, any_sampling=False):
     """lr_jpeg_info (lr_decode_jpeg_device's probe mode): of every JPEG file in the list (bytes) width, height, components,
     layout (0 = 4:2:0 or one component, 1 = 4:4:4, 2 = 4:2:2), restart interval and status (JPEG_OK, ...), from the headers
     alone.  orient=True: width and height are the upright picture's (swapped for the EXIF orientations 5 .. 8) and the
-    last column is the orientation, 1 .. 8 (1: the file tells none).  Returns int32 (B, 8).  No context, no GPU."""
+    last column is the orientation, 1 .. 8 (1: the file tells none).  any_sampling=True (LR_JPEG_ANY_SAMPLING): a
+    three-component file of any sampling with factors 1, 2 or 4, the luminance's the largest and at most 10 blocks to the
+    MCU, is status 0 as well, its layout column being the luminance's sampling byte (0x12 = 18 for 4:4:0, 0x41 = 65 for
+    4:1:1).  Returns int32 (B, 8).  No context, no GPU."""
     region, extents = _stream_region(streams)
-    return _decode_call(None, None, region, PIX_U8X3, jpeg_decode_table(extents, orient=orient), None, 0)
+    return _decode_call(None, None, region, PIX_U8X3 | _any_sampling_bit(any_sampling), jpeg_decode_table(extents, orient=orient), None, 0)
+
+
+def _any_sampling_bit(any_sampling):
+    return JPEG_ANY_SAMPLING if any_sampling else 0
 
 
 def _check_jpeg_optimize(what, jpeg, jpeg_optimize):
@@ -477,14 +485,16 @@ def _check_jpeg_optimize(what, jpeg, jpeg_optimize):
         raise ValueError(what + ": jpeg_optimize=True goes with jpeg=Q; without it nothing is encoded")
 
 
-def _all_streams(frames, what, orient=False):
-    """True if `frames` is a list of JPEG files (bytes), False if it holds none; a mixture is refused, and so is orient
-    with arrays, which carry no EXIF tag"""
+def _all_streams(frames, what, orient=False, any_sampling=False):
+    """True if `frames` is a list of JPEG files (bytes), False if it holds none; a mixture is refused, and so are orient
+    with arrays, which carry no EXIF tag, and any_sampling with arrays, which have no sampling"""
     n = sum(isinstance(f, (bytes, bytearray, memoryview)) for f in frames) if isinstance(frames, (list, tuple)) else 0
     if n and n != len(frames):
         raise ValueError(what + ": the list is all JPEG files (bytes) or all arrays")
     if orient and not n:
         raise ValueError(what + ": orient=True goes with JPEG files (bytes); arrays carry no EXIF orientation")
+    if any_sampling and not n:
+        raise ValueError(what + ": any_sampling=True goes with JPEG files (bytes); arrays have no chroma sampling")
     return n > 0
 
 
@@ -729,7 +739,7 @@ class Context:
                                                 fmt | WARP_LINES, C.cast(C.byref(args), C.c_void_p), C.c_void_p(d_dst),
                                                 dst_bytes, 0, 0, 0))
 
-    def draw_lines_batch(self, frames, lines_list, Hs=None, jpeg=None, orient=False, jpeg_optimize=False):
+    def draw_lines_batch(self, frames, lines_list, Hs=None, jpeg=None, orient=False, jpeg_optimize=False, any_sampling=False):
         """The demo's lines picture for a list of 8-bit frames of different shapes (all gray H x W, or all H x W x 3) and
         their segments (one LINE_DTYPE array per frame; Hs: one 3x3 per frame, or None): one upload, one
         lr_draw_lines_device call, one download.  Returns the list of H x W x 3 uint8 pictures: a loop of draw_lines.
@@ -738,10 +748,11 @@ class Context:
         jpeg_optimize=True (with jpeg=Q, else ValueError): the files are coded with Huffman tables of their own
         (LR_JPEG_OPTIMIZE): the same pixels in fewer bytes.
         orient=True (JPEG files only): the files' EXIF orientations are applied, the call on decode_jpeg_batch(files,
-        orient=True)'s arrays."""
+        orient=True)'s arrays.
+        any_sampling=True (JPEG files only, else ValueError): files of any sampling are decoded (decode_jpeg_batch)."""
         _check_jpeg_optimize("draw_lines_batch", jpeg, jpeg_optimize)
-        if _all_streams(frames, "draw_lines_batch", orient):
-            return self._draw_lines_streams([bytes(f) for f in frames], lines_list, Hs, jpeg, orient, jpeg_optimize)
+        if _all_streams(frames, "draw_lines_batch", orient, any_sampling):
+            return self._draw_lines_streams([bytes(f) for f in frames], lines_list, Hs, jpeg, orient, jpeg_optimize, any_sampling)
         frames = [np.ascontiguousarray(f) for f in frames]
         if not frames or len(lines_list) != len(frames) or (Hs is not None and len(Hs) != len(frames)):
             raise ValueError("draw_lines_batch: as many line arrays (and Hs) as frames, at least one")
@@ -785,11 +796,11 @@ class Context:
                 self.device_free(d_dst.value)
         return [out[off:off + w * h * 3].reshape(h, w, 3).copy() for (w, h), (off, _) in zip(sizes, outputs)]
 
-    def _draw_lines_streams(self, streams, lines_list, Hs, jpeg, orient=False, jpeg_optimize=False):
+    def _draw_lines_streams(self, streams, lines_list, Hs, jpeg, orient=False, jpeg_optimize=False, any_sampling=False):
         """draw_lines_batch for JPEG files (bytes): decoded in HBM, drawn on where they lie"""
         if len(lines_list) != len(streams) or (Hs is not None and len(Hs) != len(streams)):
             raise ValueError("draw_lines_batch: as many line arrays (and Hs) as frames, at least one")
-        d_src, src_bytes, fmt, frames = self._decode_resident(streams, None, "draw_lines_batch", orient)
+        d_src, src_bytes, fmt, frames = self._decode_resident(streams, None, "draw_lines_batch", orient, any_sampling)
         return self._draw_resident(d_src, src_bytes, fmt, frames, lines_list, Hs, jpeg, jpeg_optimize)
 
     def draw_lines(self, image_u8, lines, H=None):
@@ -887,21 +898,23 @@ class Context:
         (jpeg_decode_table).  Synchronous.  Returns info, int32 (B, 8): width, height, components, layout, restart
         interval, status, decodes of the most often decoded part, and 0 -- or, for a frame whose entry [7] is 1
         (jpeg_decode_table's orient), the EXIF orientation applied, 1 .. 8, width and height being the upright picture's.
-        d_dst None: probe mode."""
+        JPEG_ANY_SAMPLING or-ed into fmt admits every sampling with factors 1, 2 or 4 (jpeg_info); the layout column of
+        such a frame is its luminance's sampling byte.  d_dst None: probe mode."""
         return _decode_call(self._h, d_src, h_src, fmt, table, d_dst, dst_bytes)
 
-    def _decode_resident(self, streams, fmt, what, orient=False):
+    def _decode_resident(self, streams, fmt, what, orient=False, any_sampling=False):
         """The JPEG files decoded into one fresh device buffer: one upload of the files, one lr_decode_jpeg_device call.
         fmt None: PIX_U8 if every file has one component, else PIX_U8X3.  Returns (d_dst, total_bytes, fmt, frames) with
         frames[b] = (width, height, byte_offset, row_bytes), every picture at a multiple of 4; the caller frees d_dst.
         orient: the files' EXIF orientations are applied, and the sizes are the upright pictures'.
+        any_sampling: both calls carry JPEG_ANY_SAMPLING.
         Raises LibrectifyError naming the first frame whose status is not 0."""
         region, extents = _stream_region(streams)
-        orient = bool(orient)
-        info = _decode_call(None, None, region, PIX_U8X3, jpeg_decode_table(extents, orient=orient), None, 0)
+        orient, bit = bool(orient), _any_sampling_bit(any_sampling)
+        info = _decode_call(None, None, region, PIX_U8X3 | bit, jpeg_decode_table(extents, orient=orient), None, 0)
         bad = np.flatnonzero(info[:, 5])
         if len(bad):
-            jpeg_info([streams[bad[0]]])  # (once more alone: lr_last_error then tells why)
+            jpeg_info([streams[bad[0]]], any_sampling=any_sampling)  # (once more alone: lr_last_error then tells why)
             raise LibrectifyError("%s: frame %d: status %d: %s" % (what, bad[0], info[bad[0], 5], lib().lr_last_error().decode().split(": ", 2)[-1]))
         if fmt is None:
             fmt = PIX_U8 if int(info[:, 2].max()) == 1 else PIX_U8X3
@@ -916,7 +929,7 @@ class Context:
         d_dst = C.c_void_p()
         try:
             _check(lib().lr_device_malloc(self._h, end, C.byref(d_dst)))
-            info = self.decode_jpeg_device(d_src, region, fmt, table, d_dst.value, end)
+            info = self.decode_jpeg_device(d_src, region, fmt | bit, table, d_dst.value, end)
             bad = np.flatnonzero(info[:, 5])
             if len(bad):
                 raise LibrectifyError("%s: frame %d: status %d: %s" % (what, bad[0], info[bad[0], 5], lib().lr_last_error().decode()))
@@ -927,16 +940,17 @@ class Context:
             if d_dst.value:
                 self.device_free(d_dst.value)
 
-    def decode_jpeg_batch(self, streams, fmt=PIX_U8X3, orient=False):
+    def decode_jpeg_batch(self, streams, fmt=PIX_U8X3, orient=False, any_sampling=False):
         """A list of baseline JPEG files (bytes) of any sizes and samplings decoded on the GPU: one upload of the files, one
         lr_decode_jpeg_device call, one download.  fmt PIX_U8X3: H x W x 3 RGB pictures (a one-component file replicated);
         PIX_U8: H x W luminance.  orient=True: every file's EXIF orientation (tag 0x0112 of its first Exif segment) is
         applied in the decoder's output pass and the pictures come out upright, what PIL's ImageOps.exif_transpose makes of
-        them; a file that tells none comes out as stored.  Returns a list of uint8 arrays.  Raises LibrectifyError naming the frame on a status
+        them; a file that tells none comes out as stored.  any_sampling=True (LR_JPEG_ANY_SAMPLING): files of 4:4:0, 4:1:1 and
+        every other sampling with factors 1, 2 or 4 (jpeg_info) are decoded too, not refused with status 2.  Returns a list of uint8 arrays.  Raises LibrectifyError naming the frame on a status
         other than 0 (jpeg_info tells the statuses beforehand)."""
         if fmt not in (PIX_U8, PIX_U8X3):
             raise ValueError("decode_jpeg_batch: fmt is PIX_U8 or PIX_U8X3")
-        d_dst, total, fmt, frames = self._decode_resident(streams, fmt, "decode_jpeg_batch", orient)
+        d_dst, total, fmt, frames = self._decode_resident(streams, fmt, "decode_jpeg_batch", orient, any_sampling)
         try:
             out = self.device_download(d_dst, (total,), np.uint8)
         finally:
@@ -944,15 +958,16 @@ class Context:
         tail = (3,) if fmt == PIX_U8X3 else ()
         return [out[off:off + h * row].reshape((h, w) + tail).copy() for w, h, off, row in frames]
 
-    def decode_jpeg(self, data, fmt=PIX_U8X3, orient=False):
+    def decode_jpeg(self, data, fmt=PIX_U8X3, orient=False, any_sampling=False):
         """One baseline JPEG file (bytes) decoded on the GPU: H x W x 3 RGB (PIX_U8X3) or H x W luminance (PIX_U8);
-        orient=True: upright, by the file's EXIF orientation."""
-        return self.decode_jpeg_batch([data], fmt, orient)[0]
+        orient=True: upright, by the file's EXIF orientation; any_sampling=True: of any sampling (decode_jpeg_batch)."""
+        return self.decode_jpeg_batch([data], fmt, orient, any_sampling)[0]
 
-    def _rectify_streams(self, streams, min_length, refine, cfg, clip, max_size, capacity, jpeg, orient=False, interp="linear", jpeg_optimize=False):
+    def _rectify_streams(self, streams, min_length, refine, cfg, clip, max_size, capacity, jpeg, orient=False, interp="linear", jpeg_optimize=False,
+                         any_sampling=False):
         """rectify_batch for JPEG files: the files go up and are decoded in HBM, the pictures are handed to
         rectify_frames_device where they lie; with jpeg=Q no pixel crosses the link in either direction"""
-        d_src, _, fmt, sources = self._decode_resident(streams, None, "rectify_batch", orient)
+        d_src, _, fmt, sources = self._decode_resident(streams, None, "rectify_batch", orient, any_sampling)
         return self._rectify_resident(d_src, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp, jpeg_optimize)
 
     def prepare_device(self, d_src, src_image_bytes, batch, width, height, src_row_bytes, fmt, d_dst, dst_image_bytes,
@@ -1013,7 +1028,7 @@ class Context:
                     self.device_free(p.value)
 
     def rectify(self, image_u8, min_length=None, refine=False, cfg=None, clip=3.0, max_size=None, jpeg=None, orient=False,
-                interp="linear", jpeg_optimize=False):
+                interp="linear", jpeg_optimize=False, any_sampling=False):
         """The reference demo's pipeline (autorectify.cpp) on an 8-bit frame (H x W gray or H x W x 3 RGB): luma
         (4899 R + 9617 G + 1868 B + 8192) >> 14, / 256, find_line_segment_groups with min_length max(w, h) / 100 by
         default, compute_rectification_transform (cfg: the demo's, horizontal_vp_min_distance = 2),
@@ -1029,17 +1044,21 @@ class Context:
         own (LR_JPEG_OPTIMIZE), the same pixels in fewer bytes.
         orient=True (a JPEG file only): the file's EXIF orientation is applied as it is decoded, as the demo's imread
         does: the call on decode_jpeg(file, orient=True).
+        any_sampling=True (a JPEG file only): a file of any sampling is decoded (LR_JPEG_ANY_SAMPLING): the call on
+        decode_jpeg(file, any_sampling=True).
         interp="cubic": the warp samples 4 x 4 bicubic (WARP_CUBIC) instead of bilinear, on every path above; lines,
         transform, homography and size are those of interp="linear", only the picture (or its JPEG file) differs."""
         cubic = _sampling_bit(interp, "rectify")
         _check_jpeg_optimize("rectify", jpeg, jpeg_optimize)
         if isinstance(image_u8, (bytes, bytearray, memoryview)):  # a JPEG file: decoded in HBM, rectify_batch's path for one frame
-            lines, t, out = self.rectify_batch([bytes(image_u8)], min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, jpeg=jpeg, orient=orient, interp=interp, jpeg_optimize=jpeg_optimize)[0]
+            lines, t, out = self.rectify_batch([bytes(image_u8)], min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, jpeg=jpeg, orient=orient, interp=interp, jpeg_optimize=jpeg_optimize, any_sampling=any_sampling)[0]
             if out is None:
                 rectification_homography(t, clip)  # (raises what rectify raises for such a frame)
             return lines, t, out
         if orient:
             raise ValueError("rectify: orient=True goes with a JPEG file (bytes); an array carries no EXIF orientation")
+        if any_sampling:
+            raise ValueError("rectify: any_sampling=True goes with a JPEG file (bytes); an array has no chroma sampling")
         img = np.ascontiguousarray(image_u8)
         if img.dtype != np.uint8 or not (img.ndim == 2 or (img.ndim == 3 and img.shape[2] == 3)):
             raise ValueError("rectify: an H x W or H x W x 3 uint8 frame")
@@ -1331,7 +1350,7 @@ class Context:
         return res
 
     def rectify_batch(self, frames_u8, min_length=None, refine=False, cfg=None, clip=3.0, max_size=None, capacity=4096, jpeg=None,
-                      orient=False, interp="linear", jpeg_optimize=False):
+                      orient=False, interp="linear", jpeg_optimize=False, any_sampling=False):
         """Context.rectify for a batch: frames_u8 is a uint8 array [B, H, W] or [B, H, W, 3], or a list of such frames of one
         shape.  One upload, rectify_batch_device (one detector batch, the packed warp), one download.  Returns a
         list of (lines, transform, warped), frame by frame what rectify returns for it; warped is None for a frame whose
@@ -1350,12 +1369,17 @@ class Context:
         PIX_U8)'s for a list of one-component files); with jpeg=Q no pixel crosses the link in either direction.
         orient=True (JPEG files only, else ValueError): the files' EXIF orientations are applied in the decoder's output
         pass, as the demo's imread applies them -- bit for bit the call on decode_jpeg_batch(files, orient=True)'s arrays.
+        any_sampling=True (JPEG files only, else ValueError): the decoder call carries LR_JPEG_ANY_SAMPLING, so that files of
+        4:4:0 (a losslessly rotated 4:2:2 photograph), 4:1:1 and every other sampling with factors 1, 2 or 4 are decoded --
+        bit for bit the call on decode_jpeg_batch(files, any_sampling=True)'s arrays.  Without it the first such file raises
+        LibrectifyError (status 2) for the whole batch.
         interp="cubic": the warp launch of whichever path is taken samples 4 x 4 bicubic (WARP_CUBIC); detector, transforms,
         sizes and the encoder are untouched -- frame by frame what rectify(interp="cubic") returns."""
         _sampling_bit(interp, "rectify_batch")
         _check_jpeg_optimize("rectify_batch", jpeg, jpeg_optimize)
-        if _all_streams(frames_u8, "rectify_batch", orient):
-            return self._rectify_streams([bytes(f) for f in frames_u8], min_length, refine, cfg, clip, max_size, capacity, jpeg, orient, interp, jpeg_optimize)
+        if _all_streams(frames_u8, "rectify_batch", orient, any_sampling):
+            return self._rectify_streams([bytes(f) for f in frames_u8], min_length, refine, cfg, clip, max_size, capacity, jpeg, orient, interp, jpeg_optimize,
+                                         any_sampling)
         if not isinstance(frames_u8, np.ndarray):
             frames_u8 = [np.asarray(f) for f in frames_u8]
             if len({f.shape for f in frames_u8}) > 1:

@@ -29,6 +29,13 @@
 //                  rows into columns, and such a frame's tiles are squares of 32 x 32 stored pixels that go through LDS,
 //                  so that consecutive lanes still store consecutive bytes of one row of the picture.
 //
+// LR_JPEG_ANY_SAMPLING (or-ed into the call's format): three-component streams of any sampling whose factors are 1, 2 or 4,
+// the luminance's the largest, at most 10 blocks to the MCU (4:4:0, 4:1:1, ...; tests/numpy_jpeg_sampling_ref.py restates it).
+// The stages only need to know which component a block of the MCU belongs to (a table in the frame record) and where a
+// component's sample lies (shifts by the factors); the upsampling is per axis by the ratio: the sample, the triangle, or
+// replication for 4.  Those are the kAny instantiations of the kernels, which a call gets only if it has the bit and one of
+// its frames needs them: every other call launches the kernels it always did (docs/jpeg_decode_bounds.md has the stores).
+//
 // Every loop on the device is bounded by the part's bits, the stream's length or the frame's block count; every read of the
 // stream is clamped to [offset, offset + length), every coefficient store to the frame's blocks, every pixel store to the
 // frame's size.  All device writes are ordinary C++ stores (and LDS).
@@ -72,6 +79,14 @@ struct JdFrame {
     int hs, vs, n_parts, orient;  // orient: 0 or 1 as stored, 2..8 the EXIF orientation the output pass applies
     uint8_t q[3][64];  // divisors per component, natural order
     HuffDec dc[3], ac[3];
+    // The general geometry (LR_JPEG_ANY_SAMPLING), filled for every frame and read by the kAny instantiations alone.  Every
+    // factor is 1, 2 or 4, so the device shifts and masks and never divides.  Component i of the MCU is v_i rows of h_i
+    // blocks from block first[i] on; its own grid is cw[i] x ch[i] samples.
+    uint32_t comp_word;              // the table block of the MCU -> component: bits [2 kb, 2 kb + 2), kb < bpm <= 10
+    uint8_t first[4];                // first block of the MCU of component i
+    uint8_t hsh[4], vsh[4];          // log2 h_i, log2 v_i
+    uint8_t rxs[4], rys[4];          // log2 (Hmax / h_i), log2 (Vmax / v_i): 0 the sample, 1 the triangle, 2 replication
+    int cw[4], ch[4];
 };
 static_assert(sizeof(JdFrame) % 8 == 0, "rows of the mirror block stay 8-byte aligned");
 
@@ -94,7 +109,10 @@ __device__ __forceinline__ State unpack(unsigned long long v) {
     return State{(uint32_t)v, (int)((v >> 32) & 7u), (int)((v >> 35) & 15u), (int)((v >> 39) & 63u)};
 }
 
-__device__ __forceinline__ int component_of(int bpm, int kb) {
+// the component of block kb of the MCU.  kAny: from the frame's table (word); else the three layouts' rule
+template <bool kAny>
+__device__ __forceinline__ int component_of(int bpm, uint32_t word, int kb) {
+    if (kAny) return (int)((word >> (2 * kb)) & 3u);
     const int ny = bpm - 2;
     return (bpm == 1 || kb < ny) ? 0 : kb - ny + 1;
 }
@@ -170,7 +188,7 @@ __device__ __forceinline__ int extend(uint32_t v, int s) { return v < (1u << (s 
 // Decodes from `st` until a symbol ends at or behind byte `limit` (or the stream ends): `st` becomes that state, `blocks`
 // the blocks completed, `markers` the RSTm passed.  kWrite: the coefficients of block first + (blocks so far) are stored
 // and the markers' numbers checked; `err` is then what damages the scan.
-template <bool kWrite>
+template <bool kWrite, bool kAny>
 __device__ void decode_part(const JdFrame* f, const HuffDec* s_huff, const uint8_t* __restrict__ stream, State& st, uint32_t limit,
                             uint32_t* blocks_out, uint32_t* markers_out, int16_t* __restrict__ coef, uint32_t first, uint32_t total,
                             bool* err_out) {
@@ -180,11 +198,12 @@ __device__ void decode_part(const JdFrame* f, const HuffDec* s_huff, const uint8
     else r.cur = stream[r.k];
     int c = st.c, z = st.z;
     const int bpm = f->bpm;
+    const uint32_t word = kAny ? f->comp_word : 0u;
     uint32_t blocks = 0, markers = 0;
     bool err = false;
     // (a symbol is at least one bit, so a part's bits bound the turns; a lane never enters in front of its part)
     for (int turn = 0; turn < kPartBytes * 8 + 16 && r.k < limit && !r.ended(); ++turn) {
-        const int comp = component_of(bpm, c);
+        const int comp = component_of<kAny>(bpm, word, c);
         bool done = false, wrong = false;
         if (z == 0) {
             int s = huff_symbol(r, s_huff + comp);
@@ -259,6 +278,9 @@ __device__ __forceinline__ void load_tables(const JdFrame* f, uint32_t* s_words,
 __device__ __forceinline__ unsigned long long true_start(const JdFrame* f) { return pack(State{f->scan, 0, 0, 0}); }
 
 // state: entry[n] | exit[n] | carry[2][n_wg], n = n_wg * kSyncBlock; part: counts[n] | tries[n] | first[n]
+// kAny (here and below): the call has LR_JPEG_ANY_SAMPLING and a frame whose sampling is none of the three layouts; every
+// other call gets the kernels without the general geometry.
+template <bool kAny>
 __global__ __launch_bounds__(kSyncBlock) void jd_sync_kernel(const uint8_t* __restrict__ src, int batch, int n_wg, int round,
                                                              const JdFrame* __restrict__ frames, const int* __restrict__ wg_start,
                                                              unsigned long long* __restrict__ state, uint32_t* __restrict__ part,
@@ -302,7 +324,7 @@ __global__ __launch_bounds__(kSyncBlock) void jd_sync_kernel(const uint8_t* __re
             last = s_entry[t];
             State st = unpack(last);
             uint32_t blocks, markers;
-            decode_part<false>(f, reinterpret_cast<const HuffDec*>(s_huff), stream, st, limit, &blocks, &markers, nullptr, 0, 0, nullptr);
+            decode_part<false, kAny>(f, reinterpret_cast<const HuffDec*>(s_huff), stream, st, limit, &blocks, &markers, nullptr, 0, 0, nullptr);
             mine = pack(st);
             counts = blocks | (markers << 16);
             ++tries;
@@ -368,6 +390,7 @@ __global__ __launch_bounds__(kScanBlock) void jd_place_kernel(int n_wg, const Jd
     if (tid == 0) result[b] = JdResult{carry, s_mark[0], s_tries[0], 0u};
 }
 
+template <bool kAny>
 __global__ __launch_bounds__(kSyncBlock) void jd_write_kernel(const uint8_t* __restrict__ src, int batch, int n_wg,
                                                               const JdFrame* __restrict__ frames, const int* __restrict__ wg_start,
                                                               const int* __restrict__ grp_start,
@@ -387,7 +410,7 @@ __global__ __launch_bounds__(kSyncBlock) void jd_write_kernel(const uint8_t* __r
     const uint32_t limit = (uint32_t)min((unsigned long long)f->len, (unsigned long long)f->scan + ((unsigned long long)i + 1) * kPartBytes);
     uint32_t blocks, markers;
     bool err = false;
-    decode_part<true>(f, reinterpret_cast<const HuffDec*>(s_huff), src + (size_t)f->src_off, st, limit, &blocks, &markers,
+    decode_part<true, kAny>(f, reinterpret_cast<const HuffDec*>(s_huff), src + (size_t)f->src_off, st, limit, &blocks, &markers,
                       coef + (size_t)grp_start[b] * 8 * 64, part[2 * n + g], (uint32_t)f->n_mcus * (uint32_t)f->bpm, &err);
     if (err) damaged[b] = 1u;
 }
@@ -396,17 +419,18 @@ __global__ __launch_bounds__(kSyncBlock) void jd_write_kernel(const uint8_t* __r
 
 // the MCUs [m0, m0 + count) in order: kStore = false sums their differences per component into acc, kStore = true stores
 // the running values (32-bit sums that wrap, saturated to int16 where stored; legitimate values stay below 2^11)
-template <bool kStore>
-__device__ __forceinline__ void dc_run(int16_t* __restrict__ coef, int bpm, int m0, int count, uint32_t (&acc)[3]) {
+template <bool kStore, bool kAny>
+__device__ __forceinline__ void dc_run(int16_t* __restrict__ coef, int bpm, uint32_t word, int m0, int count, uint32_t (&acc)[3]) {
     for (int m = m0; m < m0 + count; ++m)
         for (int kb = 0; kb < bpm; ++kb) {
             int16_t* at = coef + ((size_t)m * bpm + kb) * 64;
-            const int comp = component_of(bpm, kb);
+            const int comp = component_of<kAny>(bpm, word, kb);
             acc[comp] += (uint32_t)(int)*at;
             if (kStore) *at = (int16_t)min(max((int)acc[comp], -32768), 32767);
         }
 }
 
+template <bool kAny>
 __global__ __launch_bounds__(kScanBlock) void jd_dc_kernel(const JdFrame* __restrict__ frames, const int* __restrict__ grp_start,
                                                            int16_t* __restrict__ coef_all) {
     __shared__ uint32_t s_sum[3][kScanBlock];
@@ -414,11 +438,12 @@ __global__ __launch_bounds__(kScanBlock) void jd_dc_kernel(const JdFrame* __rest
     const JdFrame* f = frames + b;
     int16_t* coef = coef_all + (size_t)grp_start[b] * 8 * 64;
     const int bpm = f->bpm, n_mcus = f->n_mcus;
+    const uint32_t word = kAny ? f->comp_word : 0u;
     const int seg = f->ri > 0 ? min(f->ri, n_mcus) : n_mcus, n_seg = (n_mcus + seg - 1) / seg;
     if (n_seg >= kScanBlock / 4) {  // many intervals: a thread takes whole ones
         for (int s = tid; s < n_seg; s += kScanBlock) {
             uint32_t acc[3] = {0u, 0u, 0u};
-            dc_run<true>(coef, bpm, s * seg, min(seg, n_mcus - s * seg), acc);
+            dc_run<true, kAny>(coef, bpm, word, s * seg, min(seg, n_mcus - s * seg), acc);
         }
         return;
     }
@@ -426,7 +451,7 @@ __global__ __launch_bounds__(kScanBlock) void jd_dc_kernel(const JdFrame* __rest
         const int m0 = s * seg, nm = min(seg, n_mcus - m0), per = (nm + kScanBlock - 1) / kScanBlock;
         const int mine0 = min(tid * per, nm), mine_n = min(per, nm - mine0);
         uint32_t acc[3] = {0u, 0u, 0u};
-        dc_run<false>(coef, bpm, m0 + mine0, mine_n, acc);
+        dc_run<false, kAny>(coef, bpm, word, m0 + mine0, mine_n, acc);
         for (int c = 0; c < 3; ++c) s_sum[c][tid] = acc[c];
         __syncthreads();
         for (int d = 1; d < kScanBlock; d <<= 1) {
@@ -437,7 +462,7 @@ __global__ __launch_bounds__(kScanBlock) void jd_dc_kernel(const JdFrame* __rest
             __syncthreads();
         }
         for (int c = 0; c < 3; ++c) acc[c] = s_sum[c][tid] - acc[c];  // what lies in front of this thread's run
-        dc_run<true>(coef, bpm, m0 + mine0, mine_n, acc);
+        dc_run<true, kAny>(coef, bpm, word, m0 + mine0, mine_n, acc);
         __syncthreads();
     }
 }
@@ -459,6 +484,7 @@ __device__ __forceinline__ void idct8(const int (&s)[8], int (&out)[8]) {
     }
 }
 
+template <bool kAny>
 __global__ __launch_bounds__(kWave) void jd_transform_kernel(int batch, int n_groups, int luma_only, const JdFrame* __restrict__ frames,
                                                              const int* __restrict__ grp_start, int16_t* __restrict__ coef) {
     __shared__ int s_t[8][65];
@@ -467,7 +493,7 @@ __global__ __launch_bounds__(kWave) void jd_transform_kernel(int batch, int n_gr
         const int b = frame_of_tile(grp_start, batch, grp);
         const JdFrame* f = frames + b;
         const int blk = (grp - grp_start[b]) * 8 + k;
-        const int comp = component_of(f->bpm, blk % f->bpm);
+        const int comp = component_of<kAny>(f->bpm, kAny ? f->comp_word : 0u, blk % f->bpm);
         const bool valid = blk < f->n_mcus * f->bpm && !(luma_only && comp != 0);
         int16_t* slot = coef + ((size_t)grp * 8 + k) * 64;
         int s[8] = {0, 0, 0, 0, 0, 0, 0, 0}, a[8];
@@ -507,34 +533,52 @@ __global__ __launch_bounds__(kWave) void jd_transform_kernel(int batch, int n_gr
 
 // ---- upsampling, colour, the picture ----
 
-// sample (x, y) of component comp, in its own grid
+// sample (x, y) of component comp, in its own grid.  kAny: the MCU is the block's column and row shifted by the component's
+// factors, the block in it row (by mod v) and column (bx mod h) of the component's v x h blocks
+template <bool kAny>
 __device__ __forceinline__ int sample_at(const uint8_t* __restrict__ blocks, const JdFrame* f, int comp, int x, int y) {
     const int bx = x >> 3, by = y >> 3;
     size_t blk;
-    if (comp == 0) blk = ((size_t)(by / f->vs) * f->mcus_x + bx / f->hs) * f->bpm + (by % f->vs) * f->hs + bx % f->hs;
+    if (kAny) {
+        const int hsh = f->hsh[comp], vsh = f->vsh[comp];
+        blk = ((size_t)(by >> vsh) * f->mcus_x + (bx >> hsh)) * f->bpm + f->first[comp] + ((by & ((1 << vsh) - 1)) << hsh) + (bx & ((1 << hsh) - 1));
+    } else if (comp == 0) blk = ((size_t)(by / f->vs) * f->mcus_x + bx / f->hs) * f->bpm + (by % f->vs) * f->hs + bx % f->hs;
     else blk = ((size_t)by * f->mcus_x + bx) * f->bpm + f->hs * f->vs + comp - 1;
     return (int)blocks[blk * 128 + (y & 7) * 8 + (x & 7)];
 }
 
 // the chrominance at pixel (x, y): centred triangle filters, the edges replicated at the component's own size
+// kAny, per axis by the ratio of the largest factor to the component's: 1 the sample, 2 the triangle, 4 the sample x >> 2
+// (near and far are then one sample, and the triangle over the other axis is taken over the replicated samples)
+template <bool kAny>
 __device__ __forceinline__ int chroma_at(const uint8_t* __restrict__ blocks, const JdFrame* f, int comp, int x, int y) {
-    if (f->hs == 1) return sample_at(blocks, f, comp, x, y);
+    if (kAny) {
+        const int rxs = f->rxs[comp], rys = f->rys[comp];
+        const int nx = x >> rxs, ny = y >> rys;
+        if (rxs != 1 && rys != 1) return sample_at<true>(blocks, f, comp, nx, ny);
+        const int fx = min(max(nx + ((x & 1) ? 1 : -1), 0), f->cw[comp] - 1), fy = min(max(ny + ((y & 1) ? 1 : -1), 0), f->ch[comp] - 1);
+        if (rys != 1) return (3 * sample_at<true>(blocks, f, comp, nx, ny) + sample_at<true>(blocks, f, comp, fx, ny) + 2) >> 2;
+        if (rxs != 1) return (3 * sample_at<true>(blocks, f, comp, nx, ny) + sample_at<true>(blocks, f, comp, nx, fy) + 2) >> 2;
+        return (9 * sample_at<true>(blocks, f, comp, nx, ny) + 3 * sample_at<true>(blocks, f, comp, fx, ny) +
+                3 * sample_at<true>(blocks, f, comp, nx, fy) + sample_at<true>(blocks, f, comp, fx, fy) + 8) >> 4;
+    }
+    if (f->hs == 1) return sample_at<false>(blocks, f, comp, x, y);
     const int cw = (f->w + 1) >> 1;
     const int nx = x >> 1, fx = min(max(nx + ((x & 1) ? 1 : -1), 0), cw - 1);
-    if (f->vs == 1) return (3 * sample_at(blocks, f, comp, nx, y) + sample_at(blocks, f, comp, fx, y) + 2) >> 2;
+    if (f->vs == 1) return (3 * sample_at<false>(blocks, f, comp, nx, y) + sample_at<false>(blocks, f, comp, fx, y) + 2) >> 2;
     const int ch = (f->h + 1) >> 1;
     const int ny = y >> 1, fy = min(max(ny + ((y & 1) ? 1 : -1), 0), ch - 1);
-    return (9 * sample_at(blocks, f, comp, nx, ny) + 3 * sample_at(blocks, f, comp, fx, ny) + 3 * sample_at(blocks, f, comp, nx, fy) +
-            sample_at(blocks, f, comp, fx, fy) + 8) >> 4;
+    return (9 * sample_at<false>(blocks, f, comp, nx, ny) + 3 * sample_at<false>(blocks, f, comp, fx, ny) + 3 * sample_at<false>(blocks, f, comp, nx, fy) +
+            sample_at<false>(blocks, f, comp, fx, fy) + 8) >> 4;
 }
 
 // pixel (x, y) of the stored picture: its luminance (kFormat LR_PIX_U8: all that is computed) and its three colour bytes
-template <int kFormat>
+template <int kFormat, bool kAny>
 __device__ __forceinline__ void pixel_at(const uint8_t* __restrict__ blocks, const JdFrame* f, int x, int y, int (&c)[3]) {
-    const int yy = sample_at(blocks, f, 0, x, y);
+    const int yy = sample_at<kAny>(blocks, f, 0, x, y);
     c[0] = c[1] = c[2] = yy;
     if (kFormat == LR_PIX_U8X3 && f->comps == 3) {  // the IJG fixed-point inverse of the encoder's rule
-        const int cb = chroma_at(blocks, f, 1, x, y) - 128, cr = chroma_at(blocks, f, 2, x, y) - 128;
+        const int cb = chroma_at<kAny>(blocks, f, 1, x, y) - 128, cr = chroma_at<kAny>(blocks, f, 2, x, y) - 128;
         c[0] = min(max(yy + ((91881 * cr + 32768) >> 16), 0), 255);
         c[1] = min(max(yy + ((-22554 * cb - 46802 * cr + 32768) >> 16), 0), 255);
         c[2] = min(max(yy + ((116130 * cb + 32768) >> 16), 0), 255);
@@ -546,7 +590,7 @@ __device__ __forceinline__ void pixel_at(const uint8_t* __restrict__ blocks, con
 //   5: O[y][x] = S[x][y]        6: S[h-1-x][y]        7: S[h-1-x][w-1-y]    8: S[x][w-1-y]    (O is h x w)
 // kTurn: the batch has a frame of orientation 5..8.  A batch without one -- every call that does not ask for orientations
 // among them -- gets the kernel without the transposing path, its LDS and its registers.
-template <int kFormat, bool kTurn>
+template <int kFormat, bool kTurn, bool kAny>
 __global__ __launch_bounds__(kTileW * kTileH) void jd_output_kernel(int batch, int n_tiles, const JdFrame* __restrict__ frames,
                                                                     const int* __restrict__ tile_start, const int* __restrict__ grp_start,
                                                                     const int16_t* __restrict__ coef, uint8_t* __restrict__ dst) {
@@ -567,7 +611,7 @@ __global__ __launch_bounds__(kTileW * kTileH) void jd_output_kernel(int batch, i
             const int tiles_x = (f->w + kTileW - 1) / kTileW;
             const int x = (local % tiles_x) * kTileW + tx, y = (local / tiles_x) * kTileH + ty;
             if (x >= f->w || y >= f->h) continue;
-            pixel_at<kFormat>(blocks, f, x, y, c);
+            pixel_at<kFormat, kAny>(blocks, f, x, y, c);
             const int ox = (o == 2 || o == 3) ? f->w - 1 - x : x, oy = (o == 3 || o == 4) ? f->h - 1 - y : y;
             uint8_t* px = dst + (size_t)f->dst_off + (size_t)oy * (size_t)f->dst_row + (size_t)ox * kBpp;
 #pragma unroll
@@ -582,7 +626,7 @@ __global__ __launch_bounds__(kTileW * kTileH) void jd_output_kernel(int batch, i
         for (int pass = 0; pass < kSquare / kTileH; ++pass) {
             const int j = ty + pass * kTileH;
             if (x0 + tx < f->w && y0 + j < f->h) {
-                pixel_at<kFormat>(blocks, f, x0 + tx, y0 + j, c);
+                pixel_at<kFormat, kAny>(blocks, f, x0 + tx, y0 + j, c);
 #pragma unroll
                 for (int i = 0; i < kBpp; ++i) s_sq[tx * kPitch + j * kBpp + i] = (uint8_t)c[i];
             }
@@ -610,6 +654,8 @@ struct Header {
     int status = kNotJpeg;
     std::string message = "no SOI";
     int w = 0, h = 0, comps = 0, layout = 0, ri = 0;
+    int hf[3] = {1, 1, 1}, vf[3] = {1, 1, 1};  // the sampling factors the decoder works with (1 x 1 for one component)
+    bool general = false;                      // a sampling that only LR_JPEG_ANY_SAMPLING admits
     int orientation = 0;  // the EXIF tag 0x0112 of the first Exif segment, 1..8; 0: none that counts
     uint32_t scan = 0;
     uint8_t q[3][64];
@@ -657,8 +703,8 @@ int exif_orientation(const uint8_t* t, size_t n) {
     return 0;
 }
 
-// the stream d[0, n) up to the first byte of its scan
-void read_header(const uint8_t* d, size_t n, Header& hd) {
+// the stream d[0, n) up to the first byte of its scan; any: LR_JPEG_ANY_SAMPLING
+void read_header(const uint8_t* d, size_t n, bool any, Header& hd) {
     auto fail = [&](int status, const std::string& what) {
         hd.status = status;
         hd.message = what;
@@ -747,9 +793,22 @@ void read_header(const uint8_t* d, size_t n, Header& hd) {
     if (nc != 1 && nc != 3) return fail(kUnsupported, std::to_string(nc) + " components");
     if (nc == 3) {
         const int y = sof[7], cb = sof[10], cr = sof[13];
-        if (cb != 0x11 || cr != 0x11 || (y != 0x22 && y != 0x11 && y != 0x21))
-            return fail(kUnsupported, "sampling other than 4:2:0, 4:4:4, 4:2:2");
-        hd.layout = y == 0x22 ? kL420 : (y == 0x11 ? kL444 : kL422);
+        const bool known = cb == 0x11 && cr == 0x11 && (y == 0x22 || y == 0x11 || y == 0x21);
+        if (!known && !any) return fail(kUnsupported, "sampling other than 4:2:0, 4:4:4, 4:2:2");
+        if (!known) {  // every factor 1, 2 or 4; component 0 the largest; at most 10 blocks to the MCU (T.81 B.2.3)
+            int sum = 0;
+            for (int i = 0; i < 3; ++i) {
+                const int hi = sof[7 + 3 * i] >> 4, vi = sof[7 + 3 * i] & 15;
+                if ((hi != 1 && hi != 2 && hi != 4) || (vi != 1 && vi != 2 && vi != 4))
+                    return fail(kUnsupported, "a sampling factor other than 1, 2 or 4");
+                if (hi > (y >> 4) || vi > (y & 15)) return fail(kUnsupported, "luminance sampled below chrominance");
+                sum += hi * vi;
+            }
+            if (sum > 10) return fail(kUnsupported, "more than 10 blocks to the MCU");
+        }
+        for (int i = 0; i < 3; ++i) hd.hf[i] = sof[7 + 3 * i] >> 4, hd.vf[i] = sof[7 + 3 * i] & 15;
+        hd.general = !known;
+        hd.layout = !known ? y : (y == 0x22 ? kL420 : (y == 0x11 ? kL444 : kL422));  // (a sampling byte is never 0, 1 or 2)
     }
     if (seg_len < 1 || seg_len != 4 + 2 * (size_t)seg[0]) return fail(kNotJpeg, "bad SOS");
     if (seg[0] != nc) return fail(kUnsupported, "a non-interleaved or multi-scan file");
@@ -773,6 +832,8 @@ void read_header(const uint8_t* d, size_t n, Header& hd) {
 
 int ctx_decode_jpeg(lr_context* c, const void* d_src, const void* h_src, size_t src_bytes, int format, const double* T, int batch,
                     void* d_dst, size_t dst_bytes, int32_t* info) {
+    const bool any_sampling = (format & LR_JPEG_ANY_SAMPLING) != 0;
+    format &= ~LR_JPEG_ANY_SAMPLING;
     auto fail = [](const std::string& what) {
         set_error("lr_decode_jpeg_device: " + what);
         return 1;
@@ -840,11 +901,12 @@ int ctx_decode_jpeg(lr_context* c, const void* d_src, const void* h_src, size_t 
     std::vector<int32_t> rows((size_t)batch * 8, 0);
     int64_t n_groups = 0, n_wg = 0, n_tiles = 0;
     int most_wg = 0;
+    bool general = false;  // a frame that needs the kAny instantiations
     Header hd;
     for (int b = 0; b < batch; ++b) {
         const Entry& e = en[(size_t)b];
         hd = Header{};
-        read_header(static_cast<const uint8_t*>(h_src) + e.off, (size_t)e.len, hd);
+        read_header(static_cast<const uint8_t*>(h_src) + e.off, (size_t)e.len, any_sampling, hd);
         // the picture as written: with entry [7] the orientation the file tells (1 if none), and its size swapped for 5..8
         const int orient = e.orient ? std::max(hd.orientation, 1) : 0;
         const int out_w = orient >= 5 ? hd.h : hd.w, out_h = orient >= 5 ? hd.w : hd.h;
@@ -877,11 +939,25 @@ int ctx_decode_jpeg(lr_context* c, const void* d_src, const void* h_src, size_t 
         f.comps = hd.comps;
         f.layout = hd.layout;
         f.ri = hd.ri;
-        f.hs = hd.comps == 3 && hd.layout != kL444 ? 2 : 1;
-        f.vs = hd.comps == 3 && hd.layout == kL420 ? 2 : 1;
-        f.bpm = hd.comps == 1 ? 1 : f.hs * f.vs + 2;
+        // an MCU is 8 Hmax x 8 Vmax pixels, component 0 having the largest factors; its blocks come component by component,
+        // each as v_i rows of h_i blocks (T.81 A.2.3).  (For the three layouts this is what it was: hs x vs + 2 blocks.)
+        f.hs = hd.hf[0];
+        f.vs = hd.vf[0];
+        auto log2_of = [](int v) { return v == 4 ? 2 : (v == 2 ? 1 : 0); };
+        for (int i = 0; i < hd.comps; ++i) {
+            f.first[i] = (uint8_t)f.bpm;
+            for (int k = 0; k < hd.hf[i] * hd.vf[i]; ++k) f.comp_word |= (uint32_t)i << (2 * (f.bpm + k));
+            f.bpm += hd.hf[i] * hd.vf[i];
+            f.hsh[i] = (uint8_t)log2_of(hd.hf[i]);
+            f.vsh[i] = (uint8_t)log2_of(hd.vf[i]);
+            f.rxs[i] = (uint8_t)log2_of(f.hs / hd.hf[i]);
+            f.rys[i] = (uint8_t)log2_of(f.vs / hd.vf[i]);
+            f.cw[i] = (f.w * hd.hf[i] + f.hs - 1) / f.hs;  // ceil(w h_i / Hmax)
+            f.ch[i] = (f.h * hd.vf[i] + f.vs - 1) / f.vs;
+        }
         f.mcus_x = (f.w + 8 * f.hs - 1) / (8 * f.hs);
-        f.n_mcus = f.mcus_x * ((f.h + 8 * f.vs - 1) / (8 * f.vs));  // (at most 2^26 of at most 6 blocks)
+        f.n_mcus = f.mcus_x * ((f.h + 8 * f.vs - 1) / (8 * f.vs));  // (at most 2^26 of at most 10 blocks)
+        general = general || hd.general;
         f.n_parts = (int)std::max<uint64_t>(1, (e.len - hd.scan + kPartBytes - 1) / kPartBytes);
         f.orient = orient;
         std::memcpy(f.q, hd.q, sizeof f.q);
@@ -949,8 +1025,8 @@ int ctx_decode_jpeg(lr_context* c, const void* d_src, const void* h_src, size_t 
     bool settled = false;
     for (int round = 0; round < most_wg + 2 && !settled; ++round) {
         if (round >= 2) LR_HIP(hipMemsetAsync(d_active + (round & 1), 0, sizeof(uint32_t), c->stream));
-        hipLaunchKernelGGL(jd_sync_kernel, dim3((unsigned)n_wg), dim3(kSyncBlock), 0, c->stream, s8, live, (int)n_wg, round, d_frames, d_wg,
-                           js.state.get(), js.part.get(), d_active);
+        hipLaunchKernelGGL(general ? jd_sync_kernel<true> : jd_sync_kernel<false>, dim3((unsigned)n_wg), dim3(kSyncBlock), 0, c->stream, s8, live,
+                           (int)n_wg, round, d_frames, d_wg, js.state.get(), js.part.get(), d_active);
         LR_HIP(hipGetLastError());
         LR_HIP(hipMemcpyAsync(const_cast<uint32_t*>(h_active) + (round & 1), d_active + (round & 1), sizeof(uint32_t), hipMemcpyDeviceToHost,
                               c->stream));
@@ -960,17 +1036,20 @@ int ctx_decode_jpeg(lr_context* c, const void* d_src, const void* h_src, size_t 
     if (!settled) return fail("the entropy decoder's rounds did not settle (this cannot happen)");
 
     hipLaunchKernelGGL(jd_place_kernel, dim3(live), dim3(kScanBlock), 0, c->stream, (int)n_wg, d_frames, d_wg, js.part.get(), d_result);
-    hipLaunchKernelGGL(jd_write_kernel, dim3((unsigned)n_wg), dim3(kSyncBlock), 0, c->stream, s8, live, (int)n_wg, d_frames, d_wg, d_grp,
-                       js.state.get(), js.part.get(), js.coef.get(), d_damaged);
-    hipLaunchKernelGGL(jd_dc_kernel, dim3(live), dim3(kScanBlock), 0, c->stream, d_frames, d_grp, js.coef.get());
+    hipLaunchKernelGGL(general ? jd_write_kernel<true> : jd_write_kernel<false>, dim3((unsigned)n_wg), dim3(kSyncBlock), 0, c->stream, s8, live,
+                       (int)n_wg, d_frames, d_wg, d_grp, js.state.get(), js.part.get(), js.coef.get(), d_damaged);
+    hipLaunchKernelGGL(general ? jd_dc_kernel<true> : jd_dc_kernel<false>, dim3(live), dim3(kScanBlock), 0, c->stream, d_frames, d_grp, js.coef.get());
     const int grid_t = (int)std::min<int64_t>(n_groups, 1 << 18);
-    hipLaunchKernelGGL(jd_transform_kernel, dim3(grid_t), dim3(kWave), 0, c->stream, live, (int)n_groups, format == LR_PIX_U8 ? 1 : 0,
-                       d_frames, d_grp, js.coef.get());
+    hipLaunchKernelGGL(general ? jd_transform_kernel<true> : jd_transform_kernel<false>, dim3(grid_t), dim3(kWave), 0, c->stream, live,
+                       (int)n_groups, format == LR_PIX_U8 ? 1 : 0, d_frames, d_grp, js.coef.get());
     const int grid_o = (int)((std::min<int64_t>(n_tiles, 1 << 18) + 7) / 8 * 8);
     bool turn = false;
     for (const JdFrame& f : fr) turn = turn || f.orient >= 5;
-    auto output = format == LR_PIX_U8 ? (turn ? jd_output_kernel<LR_PIX_U8, true> : jd_output_kernel<LR_PIX_U8, false>)
-                                      : (turn ? jd_output_kernel<LR_PIX_U8X3, true> : jd_output_kernel<LR_PIX_U8X3, false>);
+    auto output = format == LR_PIX_U8 ? (turn ? jd_output_kernel<LR_PIX_U8, true, false> : jd_output_kernel<LR_PIX_U8, false, false>)
+                                      : (turn ? jd_output_kernel<LR_PIX_U8X3, true, false> : jd_output_kernel<LR_PIX_U8X3, false, false>);
+    if (general)
+        output = format == LR_PIX_U8 ? (turn ? jd_output_kernel<LR_PIX_U8, true, true> : jd_output_kernel<LR_PIX_U8, false, true>)
+                                     : (turn ? jd_output_kernel<LR_PIX_U8X3, true, true> : jd_output_kernel<LR_PIX_U8X3, false, true>);
     hipLaunchKernelGGL(output, dim3(grid_o), dim3(kTileW * kTileH), 0, c->stream, live, (int)n_tiles, d_frames, d_tile, d_grp, js.coef.get(), d8);
     LR_HIP(hipGetLastError());
     LR_HIP(hipMemcpyAsync(m + o_flags, d + o_flags, need - o_flags, hipMemcpyDeviceToHost, c->stream));
