@@ -6,7 +6,7 @@
 //
 //   rectify_recipe in.pgm|in.ppm out_prefix [--max-size N|fraction] [--refine] [--threads N]
 //                  [--h-strategy rotate_h|rotate_v|rectify|keep] [--v-strategy ...] [--warp] [--device-prepare] [--lines]
-//                  [--jpeg Q] [--optimize] [--jpeg-in] [--orient] [--any-sampling] [--cubic]
+//                  [--jpeg Q] [--optimize] [--jpeg-in] [--orient] [--any-sampling] [--cubic] [--border MODE[:VALUE]] [--crop]
 //
 // Input is a binary PGM (P5, 8 bit) or PPM (P6, 8 bit; converted with the usual integer luma weights
 // (4899 R + 9617 G + 1868 B + 8192) >> 14).  Image decoding stays with the caller's imaging library.
@@ -35,6 +35,10 @@
 // --any-sampling (with --jpeg-in alone): LR_JPEG_ANY_SAMPLING is or-ed into the format of lr_decode_jpeg_device (lr_jpeg_info
 // is that call in probe mode, so the same word goes to both): a file of 4:4:0 (a losslessly rotated 4:2:2 photograph), 4:1:1 or
 // any other sampling with factors 1, 2 or 4 is decoded, which without the option is refused with status 2.
+// --border MODE[:VALUE] (with --warp or --jpeg alone): what lies outside the source in the rectified picture, LR_WARP_BORDER --
+// MODE constant, replicate, reflect or reflect101; VALUE (constant only) a gray level 0 .. 255 or R,G,B, default 0.
+// --crop (likewise): the rectified picture is its constrained crop (lr_crop_homography: the largest upright rectangle of the
+// source's aspect that holds no border; the margin follows --cubic); the segments of --lines are drawn through the crop's H.
 // --cubic (with --warp or --jpeg alone; it implies neither): the warp samples 4 x 4 bicubic, cv::warpPerspective's INTER_CUBIC
 // (LR_WARP_CUBIC or-ed into the warp's format word), instead of bilinear.  Everything else is as without it.
 // Links against librectify_amd.so exactly like a program written for the reference.
@@ -275,21 +279,45 @@ bool write_jpeg(lr_context* ctx, const void* d_img, int w, int h, int ch, int qu
 // The demo's homography_from_corners(t, 3.0) + warpPerspective of the frame as read, on the GPU; writes
 // <prefix>_warp.pgm / .ppm.  Returns false with the reason on stderr.
 // `out`, `ow`, `oh` and `H` (source to rectified picture) are kept for --lines.  jpeg > 0: <prefix>_warp.jpg as well.
-// (optimize: with Huffman tables of its own.)  cubic: the bicubic sampling rule.
+// (optimize: with Huffman tables of its own.)  cubic: the bicubic sampling rule.  border: --border's rule, or null.  crop: the
+// picture is the constrained crop, and H, ow, oh are the crop's.
+struct Border {
+    int mode = LR_BORDER_CONSTANT;
+    unsigned v[3] = {0, 0, 0};
+};
+
 bool warp_frame(const Gray& g, const ImageTransform& t, const std::string& prefix, std::vector<uint8_t>& out, int& ow, int& oh,
-                double* H, int jpeg, bool optimize, bool cubic) {
-    double M[9];
+                double* H, int jpeg, bool optimize, bool cubic, const Border* border, bool crop) {
+    double M[10];  // (the tenth: the border word of LR_WARP_BORDER)
     lr_context* ctx = nullptr;
     void* d_src = nullptr;
     void* d_dst = nullptr;
     const size_t bpp = (size_t)g.ch;
-    bool ok = lr_rectification_homography(&t, 3.0f, H, M, &ow, &oh) == 0 && lr_context_create(0, &ctx) == 0;
+    bool ok = lr_rectification_homography(&t, 3.0f, H, M, &ow, &oh) == 0;
+    if (ok && crop) {
+        int x0 = 0, y0 = 0, cw = 0, ch = 0;
+        const int rc = lr_crop_homography(H, M, g.w, g.h, ow, oh, cubic ? 1 : 0, 0.0, H, M, &x0, &y0, &cw, &ch);
+        if (rc != 0) {
+            std::fprintf(stderr, "warp failed: no constrained crop (lr_crop_homography: %d)\n", rc);
+            return false;
+        }
+        std::printf("crop %dx%d at (%d, %d) of %dx%d\n", cw, ch, x0, y0, ow, oh);
+        ow = cw;
+        oh = ch;
+    }
+    int options = cubic ? LR_WARP_CUBIC : 0;
+    if (border) {
+        const unsigned value = g.ch == 3 ? (border->v[0] | border->v[1] << 8 | border->v[2] << 16) : border->v[0];
+        M[9] = (double)border->mode + 8.0 * (double)(border->mode == LR_BORDER_CONSTANT ? value : 0u);
+        options |= LR_WARP_BORDER;
+    }
+    ok = ok && lr_context_create(0, &ctx) == 0;
     if (ok) {
         out.resize((size_t)ow * oh * bpp);
         ok = lr_device_malloc(ctx, g.raw.size(), &d_src) == 0 && lr_device_malloc(ctx, out.size(), &d_dst) == 0 &&
              lr_memcpy_h2d(ctx, d_src, g.raw.data(), g.raw.size()) == 0 &&
              lr_warp_perspective_device(ctx, d_src, g.raw.size(), 1, g.w, g.h, (size_t)g.w * bpp,
-                                        (g.ch == 3 ? LR_PIX_U8X3 : LR_PIX_U8) | (cubic ? LR_WARP_CUBIC : 0), M, d_dst, out.size(),
+                                        (g.ch == 3 ? LR_PIX_U8X3 : LR_PIX_U8) | options, M, d_dst, out.size(),
                                         ow, oh, (size_t)ow * bpp) == 0 &&
              lr_memcpy_d2h(ctx, out.data(), d_dst, out.size()) == 0;
     }
@@ -310,6 +338,34 @@ bool warp_frame(const Gray& g, const ImageTransform& t, const std::string& prefi
         return false;
     }
     std::printf("wrote %s (%dx%d)\n", path.c_str(), ow, oh);
+    return true;
+}
+
+// --border's argument: MODE[:VALUE], VALUE a gray level or R,G,B (a gray level serves all three channels)
+bool parse_border(const char* text, Border& b) {
+    const std::string s = text;
+    const size_t colon = s.find(':');
+    const std::string mode = s.substr(0, colon);
+    if (mode == "constant") b.mode = LR_BORDER_CONSTANT;
+    else if (mode == "replicate") b.mode = LR_BORDER_REPLICATE;
+    else if (mode == "reflect") b.mode = LR_BORDER_REFLECT;
+    else if (mode == "reflect101") b.mode = LR_BORDER_REFLECT_101;
+    else return false;
+    if (colon == std::string::npos) return true;
+    if (b.mode != LR_BORDER_CONSTANT) return false;
+    int v[3] = {0, 0, 0}, used = 0;
+    const int n = std::sscanf(s.c_str() + colon + 1, "%d,%d,%d%n", &v[0], &v[1], &v[2], &used);
+    if (n == 1) {
+        if (std::sscanf(s.c_str() + colon + 1, "%d%n", &v[0], &used) != 1) return false;
+        v[1] = v[2] = v[0];
+    } else if (n != 3) {
+        return false;
+    }
+    if (s.c_str()[colon + 1 + (size_t)used] != 0) return false;
+    for (int i = 0; i < 3; ++i) {
+        if (v[i] < 0 || v[i] > 255) return false;
+        b.v[i] = (unsigned)v[i];
+    }
     return true;
 }
 
@@ -369,13 +425,15 @@ int main(int argc, char** argv) {
         std::fprintf(stderr,
                      "usage: %s in.pgm|in.ppm out_prefix [--max-size N|fraction] [--refine] [--threads N]\n"
                      "          [--h-strategy rotate_h|rotate_v|rectify|keep] [--v-strategy ...] [--warp] [--device-prepare]\n"
-                     "          [--lines] [--jpeg Q] [--optimize] [--jpeg-in] [--orient] [--any-sampling] [--cubic]\n",
+                     "          [--lines] [--jpeg Q] [--optimize] [--jpeg-in] [--orient] [--any-sampling] [--cubic]\n"
+                     "          [--border constant|replicate|reflect|reflect101[:VALUE]] [--crop]\n",
                      argv[0]);
         return 2;
     }
     float max_size = 1200.f;  // the demo's default
     bool refine = false, warp = false, device_prepare = false, lines_pictures = false, jpeg_in = false, orient = false, any_sampling = false, cubic = false;
-    bool optimize = false;
+    bool optimize = false, bordered = false, crop = false;
+    Border border;
     int threads = -1, jpeg = 0;
     RectificationConfig cfg;
     cfg.horizontal_vp_min_distance = 2;  // autorectify.cpp:347
@@ -391,6 +449,11 @@ int main(int argc, char** argv) {
         else if (a == "--any-sampling") any_sampling = true;
         else if (a == "--cubic") cubic = true;
         else if (a == "--optimize") optimize = true;
+        else if (a == "--crop") crop = true;
+        else if (a == "--border" && has_val && parse_border(argv[i + 1], border)) {
+            bordered = true;
+            ++i;
+        }
         else if (a == "--max-size" && has_val) max_size = (float)std::atof(argv[++i]);
         else if (a == "--threads" && has_val) threads = std::atoi(argv[++i]);
         else if (a == "--jpeg" && has_val && std::atoi(argv[i + 1]) >= 1 && std::atoi(argv[i + 1]) <= 100) {
@@ -418,6 +481,10 @@ int main(int argc, char** argv) {
     }
     if (cubic && !warp) {
         std::fprintf(stderr, "--cubic goes with --warp or --jpeg: it is the warp's sampling rule and implies neither\n");
+        return 2;
+    }
+    if ((bordered || crop) && !warp) {
+        std::fprintf(stderr, "--border and --crop go with --warp or --jpeg: they shape the rectified picture and imply neither\n");
         return 2;
     }
     Gray full;
@@ -472,7 +539,7 @@ int main(int argc, char** argv) {
     std::vector<uint8_t> warped;
     int ow = 0, oh = 0;
     double H[9];
-    bool ok = !warp || warp_frame(full, t, prefix, warped, ow, oh, H, jpeg, optimize, cubic);
+    bool ok = !warp || warp_frame(full, t, prefix, warped, ow, oh, H, jpeg, optimize, cubic, bordered ? &border : nullptr, crop);
     if (ok && lines_pictures) {  // on the gray frame, as the demo draws (autorectify.cpp:364)
         std::vector<uint8_t> gray(full.px.size());
         for (size_t i = 0; i < gray.size(); ++i) gray[i] = (uint8_t)(full.px[i] * 256.0f);

@@ -16,6 +16,7 @@
  * No function falls back to a CPU path: if no GPU is present they fail.
  */
 #pragma once
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -219,7 +220,7 @@ int lr_rectification_homography(const ImageTransform* t, float clip, double* H, 
  * d_src + b*src_image_bytes (rows src_row_bytes apart), its output at d_dst + b*dst_image_bytes (rows dst_row_bytes
  * apart); M: 9 doubles per frame (HOST), the destination-to-source map of that frame; one output size for all.
  * Arithmetic: OpenCV's 8-bit bilinear warp, 5 fractional bits per axis, pixel centres on integer
- * coordinates, a constant zero border.  Formats: u8 gray, u8 interleaved 3-channel, f32 gray (4-byte aligned pointers
+ * coordinates, a constant zero border (LR_WARP_BORDER below: a border rule per frame).  Formats: u8 gray, u8 interleaved 3-channel, f32 gray (4-byte aligned pointers
  * and strides).  Byte offsets are 64-bit.  Fails cleanly on null pointers, batch < 1, sizes below 1, strides shorter
  * than a row (or, for batch > 1, than a frame), misaligned f32 pointers or strides, an unknown format, a non-finite M. */
 int lr_warp_perspective_device(lr_context* ctx, const void* d_src, size_t src_image_bytes, int batch, int width,
@@ -291,6 +292,124 @@ enum lr_warp_sources { LR_WARP_RAGGED = 0x800 }; /* or-ed into `format` like lr_
  * combination) together with LR_WARP_PREPARE (an area average by definition), LR_WARP_LINES, LR_WARP_JPEG or
  * LR_WARP_JPEG_DECODE. */
 enum lr_warp_sampling { LR_WARP_CUBIC = 0x8000 }; /* or-ed into `format` like lr_warp_option */
+/* LR_WARP_BORDER gives every frame a border rule, cv::warpPerspective's borderMode and borderValue, in place of the constant
+ * zero border: what a tap OUTSIDE the source contributes.  It is an option of the three warps and of nothing else, alone or
+ * with LR_WARP_CUBIC.  With the bit every frame's row of the host table M carries one border word:
+ *   fmt | LR_WARP_BORDER                    10 doubles per frame instead of 9, the word is entry [9];
+ *   fmt | LR_WARP_PACKED | LR_WARP_BORDER   14 doubles per frame instead of 13, the word is entry [13];
+ *   fmt | LR_WARP_RAGGED | LR_WARP_BORDER   18 doubles per frame as ever, the word is entry [17].
+ * The word is the integer mode + 8 * value.  mode, in OpenCV's numbers: 0 constant, 1 replicate (aaaa|abcd|dddd), 2 reflect
+ * (cba|abc|cba), 4 reflect-101 (dcb|abcd|cba); 3 (wrap), 5 (transparent), 6 and 7 are refused.  value belongs to mode 0 and
+ * is 0 with the others: u8 0 .. 255; u8x3 c0 | c1 << 8 | c2 << 16; f32 the IEEE bit pattern of a finite float.
+ * Coordinates, the taps' positions, the weights, the u8 rounding and clamping and the f32 order of summation are exactly those
+ * of the same call without the bit (tests/numpy_warp_border_ref.py restates it).  A
+ * tap at (cx, cy) outside the source has, mode 0, the value `value` (per channel) or, modes 1, 2 and 4, the value of source
+ * pixel (b(cx, width), b(cy, height)), b being OpenCV's borderInterpolate: replicate clamp(p, 0, n - 1); reflect q = p mod 2n
+ * (non-negative), q < n ? q : 2n - 1 - q; reflect-101 0 for n == 1, else q = p mod (2n - 2), q < n ? q : 2n - 2 - q.  Zero
+ * weights multiply their taps like any other.  A frame whose word is 0 is byte for byte the frame of the call without the bit.
+ * Fails cleanly (nothing launched, nothing written, lr_last_error names the frame and the reason) on what the call without
+ * the bit rejects, on a word that is not an integer from 0 to 2^35 - 1, a refused mode, a value out of the format's range, a
+ * non-zero value with modes 1, 2 or 4, f32 bits that are no finite float, and together with LR_WARP_PREPARE, LR_WARP_LINES,
+ * LR_WARP_JPEG or LR_WARP_JPEG_DECODE.  Without the bit nothing changes: rows keep their lengths, a non-zero [17] fails. */
+enum lr_warp_border { LR_WARP_BORDER = 0x40000 }; /* or-ed into `format` like lr_warp_option */
+enum lr_border_mode { LR_BORDER_CONSTANT = 0, LR_BORDER_REPLICATE = 1, LR_BORDER_REFLECT = 2, LR_BORDER_REFLECT_101 = 4 };
+
+/* The constrained crop: the largest upright rectangle of the rectified picture, of the given aspect and centred on the image
+ * of the source's centre, that contains no border at all.  Host arithmetic only, in double; a static inline because the export
+ * table is full.  H, M, out_width, out_height: what lr_rectification_homography returned for a source of width x height.
+ * margin: source pixels kept clear at each side so that every tap of non-zero weight is inside: 0 for the bilinear rule, 1
+ * for LR_WARP_CUBIC.  aspect: the rectangle's width / height; <= 0 means the source's width / height.
+ * Rule: Q is the image under H of (m, m), (w-1-m, m), (w-1-m, h-1-m), (m, h-1-m) and c that of ((w-1)/2, (h-1)/2); the
+ * rectangle is centred on c with half-extents (s a, s), s the minimum of eight bounds: the window's c.x / a, (out_width - 1 -
+ * c.x) / a, c.y, out_height - 1 - c.y, and for each edge P -> R of Q with inward normal n, n.(c - P) / (|n.x| a + |n.y|).
+ * x0 = ceil(c.x - s a), x1 = floor(c.x + s a), y0 and y1 likewise; crop_width = x1 - x0 + 1, crop_height = y1 - y0 + 1;
+ * H_out = T(-x0, -y0) H (H_out[8] stays 1), M_out = M T(x0, y0): the warp with M_out into crop_width x crop_height gives the
+ * crop.  Any output pointer may be NULL; H_out may be H and M_out may be M.  Compiled without floating-point contraction
+ * (-ffp-contract=off) it is, operation for operation, the Python package's crop_homography.  Returns 0, or with nothing written:
+ *   1  a non-finite input (H, M, aspect), a null H or M, or a size, output size or margin below its minimum (1, 1, 0);
+ *   2  width - 1 - 2 margin < 1 or height - 1 - 2 margin < 1;
+ *   3  a zero denominator, or denominators of mixed sign, at the five points;
+ *   4  a quadrilateral Q that is not strictly convex;
+ *   5  a crop below 1 x 1. */
+static inline int lr_crop_homography(const double* H, const double* M, int width, int height, int out_width, int out_height,
+                                     int margin, double aspect, double* H_out, double* M_out, int* x0, int* y0,
+                                     int* crop_width, int* crop_height) {
+    double px[5], py[5], qx[5], qy[5], a, s, area2, cx, cy, lo_x, hi_x, lo_y, hi_y;
+    int i, pos = 0, neg = 0, w1, h1;
+    if (!H || !M || width < 1 || height < 1 || out_width < 1 || out_height < 1 || margin < 0) return 1;
+    for (i = 0; i < 9; ++i)
+        if (!(H[i] - H[i] == 0.0) || !(M[i] - M[i] == 0.0)) return 1; /* (x - x is 0 for finite x alone) */
+    if (!(aspect - aspect == 0.0)) return 1;
+    if (width > 1073741824 || height > 1073741824 || margin > 1073741824) return 1;
+    w1 = width - 1 - 2 * margin;
+    h1 = height - 1 - 2 * margin;
+    if (w1 < 1 || h1 < 1) return 2;
+    a = aspect > 0.0 ? aspect : (double)width / (double)height;
+    px[0] = margin;              py[0] = margin;
+    px[1] = width - 1 - margin;  py[1] = margin;
+    px[2] = width - 1 - margin;  py[2] = height - 1 - margin;
+    px[3] = margin;              py[3] = height - 1 - margin;
+    px[4] = (width - 1) / 2.0;   py[4] = (height - 1) / 2.0;
+    for (i = 0; i < 5; ++i) {
+        const double d = (H[6] * px[i] + H[7] * py[i]) + H[8];
+        if (d > 0.0) ++pos;
+        else if (d < 0.0) ++neg;
+        else return 3;
+        qx[i] = ((H[0] * px[i] + H[1] * py[i]) + H[2]) / d;
+        qy[i] = ((H[3] * px[i] + H[4] * py[i]) + H[5]) / d;
+    }
+    if (pos && neg) return 3;
+    cx = qx[4];
+    cy = qy[4];
+    /* twice the signed area gives the orientation; every corner must turn the same way, strictly */
+    area2 = 0.0;
+    for (i = 0; i < 4; ++i) area2 += qx[i] * qy[(i + 1) & 3] - qx[(i + 1) & 3] * qy[i];
+    if (!(area2 - area2 == 0.0) || area2 == 0.0) return 4;
+    for (i = 0; i < 4; ++i) {
+        const int j = (i + 1) & 3, k = (i + 2) & 3;
+        const double turn = (qx[j] - qx[i]) * (qy[k] - qy[j]) - (qy[j] - qy[i]) * (qx[k] - qx[j]);
+        if (!(area2 > 0.0 ? turn > 0.0 : turn < 0.0)) return 4;
+    }
+    s = cx / a;
+    if ((out_width - 1 - cx) / a < s) s = (out_width - 1 - cx) / a;
+    if (cy < s) s = cy;
+    if (out_height - 1 - cy < s) s = out_height - 1 - cy;
+    for (i = 0; i < 4; ++i) {
+        const int j = (i + 1) & 3;
+        const double ex = qx[j] - qx[i], ey = qy[j] - qy[i];
+        /* the inward normal of edge P -> R: the edge turned a quarter towards the inside */
+        const double nx = area2 > 0.0 ? -ey : ey, ny = area2 > 0.0 ? ex : -ex;
+        const double den = (nx < 0.0 ? -nx : nx) * a + (ny < 0.0 ? -ny : ny);
+        const double bound = (nx * (cx - qx[i]) + ny * (cy - qy[i])) / den; /* (den > 0: the edge has a length) */
+        if (!(bound >= s)) s = bound; /* (a NaN bound ends below as a crop below 1 x 1) */
+    }
+    if (!(s >= 0.0)) return 5;
+    lo_x = ceil(cx - s * a);
+    hi_x = floor(cx + s * a);
+    lo_y = ceil(cy - s);
+    hi_y = floor(cy + s);
+    if (!(hi_x >= lo_x && hi_y >= lo_y) || lo_x < 0.0 || lo_y < 0.0 || hi_x > (double)(out_width - 1) || hi_y > (double)(out_height - 1))
+        return 5;
+    if (H_out) {
+        for (i = 0; i < 3; ++i) {
+            H_out[i] = H[i] - lo_x * H[6 + i];
+            H_out[3 + i] = H[3 + i] - lo_y * H[6 + i];
+            H_out[6 + i] = H[6 + i];
+        }
+    }
+    if (M_out) {
+        for (i = 0; i < 3; ++i) {
+            M_out[3 * i] = M[3 * i];
+            M_out[3 * i + 1] = M[3 * i + 1];
+            M_out[3 * i + 2] = (M[3 * i] * lo_x + M[3 * i + 1] * lo_y) + M[3 * i + 2];
+        }
+    }
+    if (x0) *x0 = (int)lo_x;
+    if (y0) *y0 = (int)lo_y;
+    if (crop_width) *crop_width = (int)(hi_x - lo_x) + 1;
+    if (crop_height) *crop_height = (int)(hi_y - lo_y) + 1;
+    return 0;
+}
 
 /* The demo's lines picture (autorectify.cpp:72-110, draw_lines; <name>_warp_lines.jpg) on frames that stay in HBM: every
  * segment of a frame as a 3-pixel stroke with a disc of radius 5 at each end, in its group's colour, later segments over

@@ -87,6 +87,8 @@ WARP_JPEG = 0x2000  # enum lr_warp_jpeg, likewise: lr_encode_jpeg_device, whose 
 WARP_CUBIC = 0x8000  # enum lr_warp_sampling, likewise: the warp (plain, WARP_PACKED, WARP_RAGGED) samples 4 x 4 bicubic, not bilinear
 JPEG_ANY_SAMPLING = 0x20000  # enum lr_jpeg_decode_option: or-ed into lr_decode_jpeg_device's format, it admits every sampling with factors 1, 2, 4
 WARP_JPEG_DECODE = 0x4000  # enum lr_warp_jpeg_decode, likewise: lr_decode_jpeg_device, whose own arguments travel behind M (JpegDecodeArgs)
+WARP_BORDER = 0x40000  # enum lr_warp_border, likewise: a border word per frame in the warp's table (border_word, border= of the tables)
+BORDER_CONSTANT, BORDER_REPLICATE, BORDER_REFLECT, BORDER_REFLECT_101 = 0, 1, 2, 4  # enum lr_border_mode: OpenCV's numbers
 JPEG_OK, JPEG_NOT_JPEG, JPEG_UNSUPPORTED, JPEG_SIZE_MISMATCH, JPEG_DAMAGED = range(5)  # info[5] of lr_decode_jpeg_device
 FRAMES_U8, FRAMES_U8X3, FRAMES_F32 = 0x100, 0x200, 0x300  # enum lr_frames_option, or-ed into `refine` of the frame entries
 
@@ -247,12 +249,166 @@ def prepared_size(width, height, max_size):
     return size(int(width)), size(int(height)), scale
 
 
-def warp_table(Ms, sizes, bpp, align=4):
+def border_word(border, fmt):
+    """A frame's border word of LR_WARP_BORDER, mode + 8 * value, as an int.  border: None (the zero border: word 0), a mode name
+    -- "constant", "replicate", "reflect", "reflect101" -- or ("constant", value); value is an integer 0 .. 255 for PIX_U8, a
+    triple of them for PIX_U8X3 and a finite number (taken as float32) for PIX_F32.  ValueError for anything the library
+    would refuse."""
+    if fmt not in (PIX_U8, PIX_U8X3, PIX_F32):
+        raise ValueError("border_word: fmt is PIX_U8, PIX_U8X3 or PIX_F32")
+    if border is None:
+        return 0
+    modes = {"constant": BORDER_CONSTANT, "replicate": BORDER_REPLICATE, "reflect": BORDER_REFLECT, "reflect101": BORDER_REFLECT_101,
+             "reflect_101": BORDER_REFLECT_101}
+    if isinstance(border, str):
+        if border not in modes:
+            raise ValueError('border_word: a mode is "constant", "replicate", "reflect" or "reflect101", not %r' % (border,))
+        return modes[border]
+    if not (isinstance(border, (tuple, list)) and len(border) == 2 and isinstance(border[0], str) and border[0] == "constant"):
+        raise ValueError('border_word: a border is None, a mode name or ("constant", value), not %r' % (border,))
+    value = border[1]
+    byte = lambda v: not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, np.integer)) and 0 <= int(v) <= 255  # noqa: E731
+    if fmt == PIX_U8:
+        if not byte(value):
+            raise ValueError("border_word: a u8 border value is an integer from 0 to 255")
+        bits = int(value)
+    elif fmt == PIX_U8X3:
+        if not (isinstance(value, (tuple, list, np.ndarray)) and len(value) == 3 and all(byte(v) for v in value)):
+            raise ValueError("border_word: a u8x3 border value is three integers from 0 to 255")
+        bits = int(value[0]) | int(value[1]) << 8 | int(value[2]) << 16
+    else:
+        if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)):
+            raise ValueError("border_word: an f32 border value is a finite number")
+        with np.errstate(all="ignore"):
+            f = np.float32(value)
+        if not np.isfinite(f):
+            raise ValueError("border_word: an f32 border value is a finite float32")
+        bits = int(f.view(np.uint32))
+    return BORDER_CONSTANT + 8 * bits
+
+
+def _is_border_spec(border):
+    return border is None or isinstance(border, str) or (isinstance(border, tuple) and len(border) == 2 and isinstance(border[0], str))
+
+
+def _border_words(border, count, fmt, what):
+    """the border words of `count` frames from border=: one spec for all, or a list of one spec per frame"""
+    try:
+        if _is_border_spec(border):
+            return [border_word(border, fmt)] * count
+        specs = list(border)
+        if len(specs) != count:
+            raise ValueError("border_word: as many borders as frames (%d), not %d" % (count, len(specs)))
+        return [border_word(b, fmt) for b in specs]
+    except ValueError as e:
+        raise ValueError(str(e).replace("border_word", what)) from None
+    except TypeError:
+        raise ValueError('%s: border is None, a mode name, ("constant", value) or a list of those' % what) from None
+
+
+_FMT_OF_BPP = {1: PIX_U8, 3: PIX_U8X3, 4: PIX_F32}
+
+
+def crop_homography(H, M, width, height, out_size, margin=0, aspect=None):
+    """The constrained crop of a rectified picture (lr_crop_homography of include/librectify_amd.h, restated operation for
+    operation in float64; host only): the largest upright rectangle of the given aspect (width / height; None: the source's),
+    centred on the image of the source's centre, that contains no border.  H, M, out_size: what rectification_homography
+    returned for a source of width x height; margin: 0 for interp="linear", 1 for "cubic".  Returns (H_out, M_out, (x0, y0,
+    crop_width, crop_height)): the warp with M_out into crop_width x crop_height is the crop.  Raises LibrectifyError whose
+    `code` is the header's: 1 non-finite or absent input, 2 a source too small for the margin, 3 a denominator that is zero or
+    changes sign, 4 a quadrilateral that is not strictly convex, 5 a crop below 1 x 1."""
+    def fail(code, why):
+        e = LibrectifyError("crop_homography: " + why)
+        e.code = code
+        raise e
+
+    f8 = np.float64
+    try:
+        H = np.asarray(H, f8).reshape(9)
+        M = np.asarray(M, f8).reshape(9)
+        width, height, margin = int(width), int(height), int(margin)
+        out_width, out_height = int(out_size[0]), int(out_size[1])
+        aspect = f8(0.0 if aspect is None else aspect)
+    except (TypeError, ValueError):
+        fail(1, "H and M are 3 x 3, sizes and margin integers")
+    if width < 1 or height < 1 or out_width < 1 or out_height < 1 or margin < 0:
+        fail(1, "a size below 1 or a margin below 0")
+    if not (np.isfinite(H).all() and np.isfinite(M).all() and np.isfinite(aspect)):
+        fail(1, "a non-finite input")
+    if width > 2 ** 30 or height > 2 ** 30 or margin > 2 ** 30:
+        fail(1, "a size or margin above 2^30")
+    if width - 1 - 2 * margin < 1 or height - 1 - 2 * margin < 1:
+        fail(2, "the source is too small for the margin")
+    a = aspect if aspect > 0.0 else f8(width) / f8(height)
+    m = margin
+    px = [f8(m), f8(width - 1 - m), f8(width - 1 - m), f8(m), f8(width - 1) / f8(2.0)]
+    py = [f8(m), f8(m), f8(height - 1 - m), f8(height - 1 - m), f8(height - 1) / f8(2.0)]
+    qx, qy, pos, neg = [], [], 0, 0
+    with np.errstate(all="ignore"):
+        for x, y in zip(px, py):
+            d = (H[6] * x + H[7] * y) + H[8]
+            if d > 0.0:
+                pos += 1
+            elif d < 0.0:
+                neg += 1
+            else:
+                fail(3, "a zero denominator")
+            qx.append(((H[0] * x + H[1] * y) + H[2]) / d)
+            qy.append(((H[3] * x + H[4] * y) + H[5]) / d)
+        if pos and neg:
+            fail(3, "denominators of mixed sign")
+        cx, cy = qx[4], qy[4]
+        area2 = f8(0.0)
+        for i in range(4):
+            j = (i + 1) & 3
+            area2 = area2 + (qx[i] * qy[j] - qx[j] * qy[i])
+        if not np.isfinite(area2) or area2 == 0.0:
+            fail(4, "the quadrilateral has no area")
+        for i in range(4):
+            j, k = (i + 1) & 3, (i + 2) & 3
+            turn = (qx[j] - qx[i]) * (qy[k] - qy[j]) - (qy[j] - qy[i]) * (qx[k] - qx[j])
+            if not (turn > 0.0 if area2 > 0.0 else turn < 0.0):
+                fail(4, "the quadrilateral is not strictly convex")
+        s = cx / a
+        if (f8(out_width - 1) - cx) / a < s:
+            s = (f8(out_width - 1) - cx) / a
+        if cy < s:
+            s = cy
+        if f8(out_height - 1) - cy < s:
+            s = f8(out_height - 1) - cy
+        for i in range(4):
+            j = (i + 1) & 3
+            ex, ey = qx[j] - qx[i], qy[j] - qy[i]
+            nx, ny = (-ey, ex) if area2 > 0.0 else (ey, -ex)
+            den = abs(nx) * a + abs(ny)
+            bound = (nx * (cx - qx[i]) + ny * (cy - qy[i])) / den
+            if not bound >= s:
+                s = bound
+        if not s >= 0.0:
+            fail(5, "the crop is below 1 x 1")
+        lo_x, hi_x = np.ceil(cx - s * a), np.floor(cx + s * a)
+        lo_y, hi_y = np.ceil(cy - s), np.floor(cy + s)
+        if not (hi_x >= lo_x and hi_y >= lo_y) or lo_x < 0.0 or lo_y < 0.0 or hi_x > f8(out_width - 1) or hi_y > f8(out_height - 1):
+            fail(5, "the crop is below 1 x 1")
+        H_out, M_out = np.zeros(9, f8), np.zeros(9, f8)
+        for i in range(3):
+            H_out[i] = H[i] - lo_x * H[6 + i]
+            H_out[3 + i] = H[3 + i] - lo_y * H[6 + i]
+            H_out[6 + i] = H[6 + i]
+            M_out[3 * i] = M[3 * i]
+            M_out[3 * i + 1] = M[3 * i + 1]
+            M_out[3 * i + 2] = (M[3 * i] * lo_x + M[3 * i + 1] * lo_y) + M[3 * i + 2]
+    return H_out.reshape(3, 3), M_out.reshape(3, 3), (int(lo_x), int(lo_y), int(hi_x - lo_x) + 1, int(hi_y - lo_y) + 1)
+
+
+def warp_table(Ms, sizes, bpp, align=4, border=None):
     """The table of a packed warp (lr_warp_perspective_device with LR_WARP_PACKED) for frames laid out one after the
     other in frame order.  Ms: (B, 3, 3) destination-to-source maps; sizes: B pairs (out_width, out_height); bpp: bytes
     per pixel (1 u8, 3 u8x3, 4 f32); every row stride and every frame's start is rounded up to `align` bytes (for f32 a
     multiple of 4).  Returns (table, total_bytes): table float64 (B, 13) -- the map, width, height, byte offset, row
-    stride -- and the bytes of the destination, which end with the last frame's last pixel.  Needs no GPU."""
+    stride -- and the bytes of the destination, which end with the last frame's last pixel.  Needs no GPU.
+    border (not None): the table of LR_WARP_PACKED | LR_WARP_BORDER, (B, 14), whose column 13 is every frame's border word:
+    one spec for all frames (border_word's) or a list of one per frame."""
     Ms = np.asarray(Ms, np.float64)
     if Ms.ndim == 2 and Ms.shape == (3, 3):
         Ms = Ms[None]
@@ -280,17 +436,22 @@ def warp_table(Ms, sizes, bpp, align=4):
         table[b, 9:] = (ow, oh, start, row)
     if end > 2 ** 53:
         raise ValueError("warp_table: the destination is larger than 2^53 bytes")
+    if border is not None:
+        words = _border_words(border, len(Ms), _FMT_OF_BPP[bpp], "warp_table")
+        table = np.concatenate([table, np.array(words, np.float64).reshape(-1, 1)], axis=1)
     return table, end
 
 
-def ragged_table(Ms, out_sizes, sources, bpp, out_bpp=None, align=4):
+def ragged_table(Ms, out_sizes, sources, bpp, out_bpp=None, align=4, border=None):
     """The table of a ragged call (lr_warp_perspective_device with LR_WARP_RAGGED): warp_table's layout for the outputs plus
     the four source columns.  Ms: (B, 3, 3) destination-to-source maps, or None (identity: the prepare step ignores them);
     out_sizes: B pairs (out_width, out_height); sources: B rows (width, height, byte_offset, row_bytes) of the frames in
     the source region; bpp: bytes per source pixel (1 u8, 3 u8x3, 4 f32); out_bpp: bytes per output pixel (default bpp;
     4 for the prepare step, whose output is f32 gray).  Outputs lie one after the other in frame order, every row stride
     and start rounded up to `align` bytes (a multiple of 4 for 4-byte outputs).  Returns (table, dst_bytes): table
-    float64 (B, 18).  Needs no GPU."""
+    float64 (B, 18).  Needs no GPU.
+    border (not None): the table of LR_WARP_RAGGED | LR_WARP_BORDER, whose column 17 is every frame's border word: one spec
+    for all frames (border_word's) or a list of one per frame."""
     if bpp not in (1, 3, 4):
         raise ValueError("ragged_table: bpp is 1, 3 or 4")
     out_bpp = bpp if out_bpp is None else out_bpp
@@ -320,6 +481,8 @@ def ragged_table(Ms, out_sizes, sources, bpp, out_bpp=None, align=4):
     table = np.zeros((B, 18), np.float64)
     table[:, :13] = packed
     table[:, 13:17] = src
+    if border is not None:
+        table[:, 17] = _border_words(border, B, _FMT_OF_BPP[bpp], "ragged_table")
     return table, total
 
 
@@ -535,6 +698,24 @@ def _host_frame(a, what):
     return a, fmt, bpp, a.strides[0] // bpp
 
 
+def _rectified_map(t, clip, crop, cubic):
+    """(M, (out_width, out_height), crop rectangle or None) of a frame's transform: rectification_homography, and with crop
+    the constrained crop's map and size (crop_homography; margin 1 for the bicubic rule)"""
+    H, M, size = rectification_homography(t, clip)
+    if not crop:
+        return M, size, None
+    _, M, rect = crop_homography(H, M, int(t.width), int(t.height), size, 1 if cubic else 0)
+    return M, rect[2:], rect
+
+
+def _border_bit_and_map(border, fmt, M, what):
+    """(WARP_BORDER or 0, M or M's nine values and the border word behind them) for a single-frame warp with border="""
+    if border is None:
+        return 0, M
+    word = _border_words(border, 1, fmt, what)[0]
+    return WARP_BORDER, np.concatenate([np.asarray(M, np.float64).reshape(9), [float(word)]])
+
+
 class Context:
     """One device, one stream, one workspace (include/librectify_amd.h)."""
 
@@ -683,37 +864,43 @@ class Context:
                                 dst_image_bytes, out_width, out_height, dst_row_bytes):
         """lr_warp_perspective_device: one launch for `batch` device frames, enqueued on the context's stream.  M: 9
         doubles per frame ((batch, 3, 3) or (3, 3)), the destination-to-source map.  fmt: PIX_U8, PIX_U8X3, PIX_F32, with
-        WARP_CUBIC or-ed in for the bicubic sampling rule."""
+        WARP_CUBIC or-ed in for the bicubic sampling rule and WARP_BORDER for a border rule per frame (M then has 10 doubles
+        per frame, the tenth the frame's border_word)."""
         M = np.ascontiguousarray(M, np.float64).reshape(-1)
-        if M.size < 9 * max(int(batch), 1):
-            raise ValueError("warp_perspective_device: M needs 9 values per frame")
+        per_frame = 10 if fmt & WARP_BORDER else 9
+        if M.size < per_frame * max(int(batch), 1):
+            raise ValueError("warp_perspective_device: M needs %d values per frame" % per_frame)
         _check(lib().lr_warp_perspective_device(self._h, C.c_void_p(d_src), src_image_bytes, batch, width, height, src_row_bytes, fmt, _ptr(M), C.c_void_p(d_dst), dst_image_bytes, out_width, out_height, dst_row_bytes))
 
     def warp_perspective_packed_device(self, d_src, src_image_bytes, batch, width, height, src_row_bytes, fmt, table, d_dst,
                                        dst_bytes):
         """lr_warp_perspective_device with LR_WARP_PACKED: one launch for `batch` device frames of one size whose outputs
         have their own sizes and places in the dst_bytes at d_dst.  table: 13 doubles per frame (warp_table).  fmt may carry
-        WARP_CUBIC."""
+        WARP_CUBIC, and WARP_BORDER with a table of 14 doubles per frame (warp_table's border=)."""
         table = np.ascontiguousarray(table, np.float64).reshape(-1)
-        if table.size != 13 * int(batch) or batch < 1:
-            raise ValueError("warp_perspective_packed_device: the table has 13 values per frame")
-        out_w, out_h = (int(min(max(v, 1), 2 ** 31 - 1)) for v in np.nan_to_num(table.reshape(-1, 13)[:, 9:11]).max(axis=0))
+        cols = 14 if fmt & WARP_BORDER else 13
+        if table.size != cols * int(batch) or batch < 1:
+            raise ValueError("warp_perspective_packed_device: the table has %d values per frame" % cols)
+        out_w, out_h = (int(min(max(v, 1), 2 ** 31 - 1)) for v in np.nan_to_num(table.reshape(-1, cols)[:, 9:11]).max(axis=0))
         _check(lib().lr_warp_perspective_device(self._h, C.c_void_p(d_src), src_image_bytes, batch, width, height, src_row_bytes, fmt | WARP_PACKED, _ptr(table), C.c_void_p(d_dst), dst_bytes, out_w, out_h, 0))
 
-    def warp_perspective(self, array, M, out_size, interp="linear"):
+    def warp_perspective(self, array, M, out_size, interp="linear", border=None):
         """Warps one host frame (2-D uint8 or float32, or H x W x 3 uint8) by M (3x3, destination -> source) into an image
         of out_size = (width, height) on the GPU: upload, one launch, download.  Returns the (height, width[, 3]) array.
-        interp: "linear" (bilinear) or "cubic" (WARP_CUBIC: 4 x 4 bicubic, cv::warpPerspective's INTER_CUBIC)."""
+        interp: "linear" (bilinear) or "cubic" (WARP_CUBIC: 4 x 4 bicubic, cv::warpPerspective's INTER_CUBIC).
+        border: None (the zero border) or border_word's spec -- "replicate", "reflect", "reflect101", ("constant", value):
+        cv::warpPerspective's borderMode and borderValue (WARP_BORDER)."""
         cubic = _sampling_bit(interp, "warp_perspective")
         a = np.ascontiguousarray(array)
         fmt, bpp = _frame_format(a, "warp_perspective")
+        bbit, M = _border_bit_and_map(border, fmt, M, "warp_perspective")
         h, w = a.shape[:2]
         ow, oh = int(out_size[0]), int(out_size[1])
         d_src = self.device_upload(a)
         d_dst = C.c_void_p()
         try:
             _check(lib().lr_device_malloc(self._h, ow * oh * bpp, C.byref(d_dst)))
-            self.warp_perspective_device(d_src, a.nbytes, 1, w, h, w * bpp, fmt | cubic, M, d_dst.value, ow * oh * bpp, ow, oh, ow * bpp)
+            self.warp_perspective_device(d_src, a.nbytes, 1, w, h, w * bpp, fmt | cubic | bbit, M, d_dst.value, ow * oh * bpp, ow, oh, ow * bpp)
             return self.device_download(d_dst.value, (oh, ow) + a.shape[2:], a.dtype)
         finally:
             self.device_free(d_src)
@@ -964,11 +1151,11 @@ class Context:
         return self.decode_jpeg_batch([data], fmt, orient, any_sampling)[0]
 
     def _rectify_streams(self, streams, min_length, refine, cfg, clip, max_size, capacity, jpeg, orient=False, interp="linear", jpeg_optimize=False,
-                         any_sampling=False):
+                         any_sampling=False, border=None, crop=False):
         """rectify_batch for JPEG files: the files go up and are decoded in HBM, the pictures are handed to
         rectify_frames_device where they lie; with jpeg=Q no pixel crosses the link in either direction"""
         d_src, _, fmt, sources = self._decode_resident(streams, None, "rectify_batch", orient, any_sampling)
-        return self._rectify_resident(d_src, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp, jpeg_optimize)
+        return self._rectify_resident(d_src, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp, jpeg_optimize, border, crop)
 
     def prepare_device(self, d_src, src_image_bytes, batch, width, height, src_row_bytes, fmt, d_dst, dst_image_bytes,
                        out_width, out_height, dst_row_bytes):
@@ -1000,7 +1187,7 @@ class Context:
                 self.device_free(d_dst.value)
         return out if batched else out[0]
 
-    def _rectify_prepared(self, img, max_size, min_length, refine, cfg, clip, cubic=0):
+    def _rectify_prepared(self, img, max_size, min_length, refine, cfg, clip, cubic=0, border=None, crop=False):
         """rectify with the demo's prescale: the 8-bit frame goes up once; the prepare step, the detector and the warp all
         read it in HBM"""
         fmt, bpp = _frame_format(img, "rectify")
@@ -1017,10 +1204,11 @@ class Context:
             for k in ("x1", "y1", "x2", "y2"):  # back to the coordinates of the full frame, in float32 as the demo
                 lines[k] = lines[k] / scale
             t = compute_rectification_transform(lines, w, h, cfg)
-            _, M, (rw, rh) = rectification_homography(t, clip)
+            M, (rw, rh), rect = _rectified_map(t, clip, crop, cubic)
+            bbit, M = _border_bit_and_map(border, fmt, M, "rectify")
             _check(lib().lr_device_malloc(self._h, rw * rh * bpp, C.byref(d_dst)))
-            self.warp_perspective_device(d_src, img.nbytes, 1, w, h, w * bpp, fmt | cubic, M, d_dst.value, rw * rh * bpp, rw, rh, rw * bpp)
-            return lines, t, self.device_download(d_dst.value, (rh, rw) + img.shape[2:], np.uint8)
+            self.warp_perspective_device(d_src, img.nbytes, 1, w, h, w * bpp, fmt | cubic | bbit, M, d_dst.value, rw * rh * bpp, rw, rh, rw * bpp)
+            return (lines, t, self.device_download(d_dst.value, (rh, rw) + img.shape[2:], np.uint8)) + ((rect,) if crop else ())
         finally:
             self.device_free(d_src)
             for p in (d_small, d_dst):
@@ -1028,7 +1216,7 @@ class Context:
                     self.device_free(p.value)
 
     def rectify(self, image_u8, min_length=None, refine=False, cfg=None, clip=3.0, max_size=None, jpeg=None, orient=False,
-                interp="linear", jpeg_optimize=False, any_sampling=False):
+                interp="linear", jpeg_optimize=False, any_sampling=False, border=None, crop=False):
         """The reference demo's pipeline (autorectify.cpp) on an 8-bit frame (H x W gray or H x W x 3 RGB): luma
         (4899 R + 9617 G + 1868 B + 8192) >> 14, / 256, find_line_segment_groups with min_length max(w, h) / 100 by
         default, compute_rectification_transform (cfg: the demo's, horizontal_vp_min_distance = 2),
@@ -1047,14 +1235,19 @@ class Context:
         any_sampling=True (a JPEG file only): a file of any sampling is decoded (LR_JPEG_ANY_SAMPLING): the call on
         decode_jpeg(file, any_sampling=True).
         interp="cubic": the warp samples 4 x 4 bicubic (WARP_CUBIC) instead of bilinear, on every path above; lines,
-        transform, homography and size are those of interp="linear", only the picture (or its JPEG file) differs."""
+        transform, homography and size are those of interp="linear", only the picture (or its JPEG file) differs.
+        border: None (the zero border: the demo's black wedges) or border_word's spec -- "replicate", "reflect", "reflect101",
+        ("constant", value) -- for what lies outside the source (WARP_BORDER); only the picture differs.
+        crop=True: the picture (or its JPEG file) is the constrained crop, the largest upright rectangle of the source's aspect
+        around the image of the source's centre that contains no border (crop_homography; the margin follows interp), and the
+        call returns (lines, transform, warped, (x0, y0, width, height)), the rectangle in the uncropped picture."""
         cubic = _sampling_bit(interp, "rectify")
         _check_jpeg_optimize("rectify", jpeg, jpeg_optimize)
         if isinstance(image_u8, (bytes, bytearray, memoryview)):  # a JPEG file: decoded in HBM, rectify_batch's path for one frame
-            lines, t, out = self.rectify_batch([bytes(image_u8)], min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, jpeg=jpeg, orient=orient, interp=interp, jpeg_optimize=jpeg_optimize, any_sampling=any_sampling)[0]
-            if out is None:
-                rectification_homography(t, clip)  # (raises what rectify raises for such a frame)
-            return lines, t, out
+            res = self.rectify_batch([bytes(image_u8)], min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, jpeg=jpeg, orient=orient, interp=interp, jpeg_optimize=jpeg_optimize, any_sampling=any_sampling, border=border, crop=crop)[0]
+            if res[2] is None:
+                _rectified_map(res[1], clip, crop, cubic)  # (raises what rectify raises for such a frame)
+            return res
         if orient:
             raise ValueError("rectify: orient=True goes with a JPEG file (bytes); an array carries no EXIF orientation")
         if any_sampling:
@@ -1063,13 +1256,14 @@ class Context:
         if img.dtype != np.uint8 or not (img.ndim == 2 or (img.ndim == 3 and img.shape[2] == 3)):
             raise ValueError("rectify: an H x W or H x W x 3 uint8 frame")
         if jpeg is not None:
-            lines, t, stream = self.rectify_batch(img[None], min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, jpeg=jpeg, interp=interp, jpeg_optimize=jpeg_optimize)[0]
-            if stream is None:
-                rectification_homography(t, clip)  # (raises what rectify raises for such a frame)
-            return lines, t, stream
-        if max_size is not None:
-            return self._rectify_prepared(img, max_size, min_length, refine, cfg or RectificationConfig(hmin=2.0), clip, cubic)
+            res = self.rectify_batch(img[None], min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, jpeg=jpeg, interp=interp, jpeg_optimize=jpeg_optimize, border=border, crop=crop)[0]
+            if res[2] is None:
+                _rectified_map(res[1], clip, crop, cubic)  # (raises what rectify raises for such a frame)
+            return res
         fmt, bpp = _frame_format(img, "rectify")
+        _border_words(border, 1, fmt, "rectify")  # (a bad spec: ValueError before anything is launched)
+        if max_size is not None:
+            return self._rectify_prepared(img, max_size, min_length, refine, cfg or RectificationConfig(hmin=2.0), clip, cubic, border, crop)
         h, w = img.shape[:2]
         if min_length is None:
             min_length = max(w, h) / 100.0
@@ -1080,17 +1274,19 @@ class Context:
         try:
             lines = self.find_line_segment_groups_device(d_src, w, h, min_length, refine=refine, fmt=fmt).copy()
             t = compute_rectification_transform(lines, w, h, cfg)
-            _, M, (rw, rh) = rectification_homography(t, clip)
+            M, (rw, rh), rect = _rectified_map(t, clip, crop, cubic)
+            bbit, M = _border_bit_and_map(border, fmt, M, "rectify")
             _check(lib().lr_device_malloc(self._h, rw * rh * bpp, C.byref(d_dst)))
-            self.warp_perspective_device(d_src, img.nbytes, 1, w, h, w * bpp, fmt | cubic, M, d_dst.value, rw * rh * bpp, rw, rh, rw * bpp)
-            return lines, t, self.device_download(d_dst.value, (rh, rw) + img.shape[2:], np.uint8)
+            self.warp_perspective_device(d_src, img.nbytes, 1, w, h, w * bpp, fmt | cubic | bbit, M, d_dst.value, rw * rh * bpp, rw, rh, rw * bpp)
+            return (lines, t, self.device_download(d_dst.value, (rh, rw) + img.shape[2:], np.uint8)) + ((rect,) if crop else ())
         finally:
             self.device_free(d_src)
             if d_dst.value:
                 self.device_free(d_dst.value)
 
     def rectify_batch_device(self, d_frames, batch, width, height, fmt, src_row_bytes=None, src_image_bytes=None,
-                             min_length=None, refine=False, cfg=None, clip=3.0, max_size=None, capacity=4096, interp="linear"):
+                             min_length=None, refine=False, cfg=None, clip=3.0, max_size=None, capacity=4096, interp="linear",
+                             border=None, crop=False):
         """rectify for `batch` 8-bit frames (fmt PIX_U8 or PIX_U8X3) of one width x height that are resident in HBM, frame
         b at d_frames + b * src_image_bytes: with max_size one batched prepare_device, then the batch detector
         (lr_find_line_segment_groups_batch_device on the 8-bit frames, or on the prepared ones; its own transforms are not
@@ -1104,13 +1300,18 @@ class Context:
         capacity: lines per frame of the first detector pass.  A frame that has more makes the WHOLE batch's detector pass
         run once more with room for the longest list, so no frame's lines are ever cut, at twice the detector's cost for
         such a batch; a caller who expects more than 4096 lines in a frame passes a larger capacity.
-        interp: "linear" or "cubic", the packed warp's sampling rule (WARP_CUBIC); nothing else changes."""
+        interp: "linear" or "cubic", the packed warp's sampling rule (WARP_CUBIC); nothing else changes.
+        border: None, one border_word spec for all frames or a list of one per frame (WARP_BORDER: the table then has 14
+        columns).  crop=True: every picture is its constrained crop (rectify's crop=; a frame whose crop cannot be formed
+        has no image) and a sixth value is returned: the list of the frames' rectangles (x0, y0, width, height), None for a
+        frame without an image."""
         cubic = _sampling_bit(interp, "rectify_batch_device")
         if fmt not in (PIX_U8, PIX_U8X3):
             raise ValueError("rectify_batch_device: 8-bit frames, PIX_U8 or PIX_U8X3")
         batch, w, h = int(batch), int(width), int(height)
         if batch < 1:
             raise ValueError("rectify_batch_device: batch < 1")
+        words = None if border is None else _border_words(border, batch, fmt, "rectify_batch_device")
         bpp = 3 if fmt == PIX_U8X3 else 1
         srow = w * bpp if src_row_bytes is None else int(src_row_bytes)
         simg = h * srow if src_image_bytes is None else int(src_image_bytes)
@@ -1141,7 +1342,7 @@ class Context:
                 if int(n.max()) <= capacity:
                     break
                 capacity = int(n.max())  # (a frame's lines were cut: once more, with room for the longest list)
-            lines_list, transforms, good, Ms, sizes = [], [], [], [], []
+            lines_list, transforms, good, Ms, sizes, rects = [], [], [], [], [], [None] * batch
             for b in range(batch):
                 lines = out[b][: n[b]].copy()
                 if scale is not None:
@@ -1151,24 +1352,27 @@ class Context:
                 lines_list.append(lines)
                 transforms.append(t)
                 try:
-                    _, M, size = rectification_homography(t, clip)
+                    M, size, rects[b] = _rectified_map(t, clip, crop, cubic)
                 except LibrectifyError:
                     continue  # (collinear corners, a size below 1, ...: this frame has no image)
                 good.append(b)
                 Ms.append(M)
                 sizes.append(size)
-            table = np.zeros((batch, 13), np.float64)
+            table = np.zeros((batch, 13 if words is None else 14), np.float64)
+            more = (rects,) if crop else ()
             if not good:
-                return lines_list, transforms, table, None, 0
-            table[good], total = warp_table(np.stack(Ms), np.array(sizes, np.int64), bpp, 4)
+                return (lines_list, transforms, table, None, 0) + more
+            table[good, :13], total = warp_table(np.stack(Ms), np.array(sizes, np.int64), bpp, 4)
+            if words is not None:
+                table[good, 13] = [words[b] for b in good]
             _check(lib().lr_device_malloc(self._h, total, C.byref(d_out)))
             # one launch; a frame without an image splits it, as a launch's frames are consecutive in the source
             runs = np.split(np.array(good), np.flatnonzero(np.diff(good) != 1) + 1)
             for run in runs:
                 b0 = int(run[0])
-                self.warp_perspective_packed_device(d_frames + b0 * simg, simg, len(run), w, h, srow, fmt | cubic, table[run], d_out.value, total)
+                self.warp_perspective_packed_device(d_frames + b0 * simg, simg, len(run), w, h, srow, fmt | cubic | (0 if words is None else WARP_BORDER), table[run], d_out.value, total)
             res, d_out = d_out.value, C.c_void_p()
-            return lines_list, transforms, table, res, total
+            return (lines_list, transforms, table, res, total) + more
         finally:
             for p in (d_small, d_out):
                 if p.value:
@@ -1217,7 +1421,7 @@ class Context:
         return [out[b][: min(int(n[b]), capacity)].copy() for b in range(len(frames))], tf
 
     def rectify_frames_device(self, d_base, sources, fmt, min_length=None, refine=False, cfg=None, clip=3.0, max_size=None,
-                              capacity=4096, interp="linear"):
+                              capacity=4096, interp="linear", border=None, crop=False):
         """rectify for 8-bit frames (fmt PIX_U8 or PIX_U8X3) that are resident in HBM and have their OWN sizes: frame b is
         sources[b] = (width, height, byte_offset from d_base, row_bytes).  With max_size one ragged prepare
         (prepare_ragged_device) to prepared_size(w_b, h_b, max_size) per frame, one detector call with a frame table (on
@@ -1225,7 +1429,8 @@ class Context:
         the host what rectify does per frame, and the ragged warp into one allocation: one launch per run of consecutive
         frames that have an image.  Returns (lines_list, transforms, table, d_out, total_bytes) like rectify_batch_device;
         table is ragged_table's (18 columns; an all-zero row for a frame without an image).  capacity and interp: as
-        there (the ragged warp's sampling rule)."""
+        there (the ragged warp's sampling rule); border and crop likewise (the border words are the table's column 17; with
+        crop=True the frames' rectangles are a sixth value)."""
         cubic = _sampling_bit(interp, "rectify_frames_device")
         if fmt not in (PIX_U8, PIX_U8X3):
             raise ValueError("rectify_frames_device: 8-bit frames, PIX_U8 or PIX_U8X3")
@@ -1233,6 +1438,7 @@ class Context:
         batch = len(sources)
         if batch < 1 or any(len(s) != 4 for s in sources):
             raise ValueError("rectify_frames_device: sources is B rows (width, height, byte_offset, row_bytes)")
+        words = None if border is None else _border_words(border, batch, fmt, "rectify_frames_device")
         bpp = 3 if fmt == PIX_U8X3 else 1
         src_bytes = _source_extent(sources, bpp)
         if cfg is None:
@@ -1266,7 +1472,7 @@ class Context:
                 if int(n.max()) <= capacity:
                     break
                 capacity = int(n.max())  # (a frame's lines were cut: once more, with room for the longest list)
-            lines_list, transforms, good, Ms, sizes = [], [], [], [], []
+            lines_list, transforms, good, Ms, sizes, rects = [], [], [], [], [], [None] * batch
             for b, (w, h, _, _) in enumerate(sources):
                 lines = out[b][: n[b]].copy()
                 if scales[b] is not None:
@@ -1276,21 +1482,24 @@ class Context:
                 lines_list.append(lines)
                 transforms.append(t)
                 try:
-                    _, M, size = rectification_homography(t, clip)
+                    M, size, rects[b] = _rectified_map(t, clip, crop, cubic)
                 except LibrectifyError:
                     continue  # (collinear corners, a size below 1, ...: this frame has no image)
                 good.append(b)
                 Ms.append(M)
                 sizes.append(size)
             table = np.zeros((batch, 18), np.float64)
+            more = (rects,) if crop else ()
             if not good:
-                return lines_list, transforms, table, None, 0
+                return (lines_list, transforms, table, None, 0) + more
             table[good], total = ragged_table(np.stack(Ms), np.array(sizes, np.int64), np.array([sources[b] for b in good], np.int64), bpp, align=4)
+            if words is not None:
+                table[good, 17] = [words[b] for b in good]
             _check(lib().lr_device_malloc(self._h, total, C.byref(d_out)))
             for run in np.split(np.array(good), np.flatnonzero(np.diff(good) != 1) + 1):
-                self.warp_perspective_ragged_device(d_base, src_bytes, fmt | cubic, table[run], d_out.value, total)
+                self.warp_perspective_ragged_device(d_base, src_bytes, fmt | cubic | (0 if words is None else WARP_BORDER), table[run], d_out.value, total)
             res, d_out = d_out.value, C.c_void_p()
-            return lines_list, transforms, table, res, total
+            return (lines_list, transforms, table, res, total) + more
         finally:
             for p in (d_small, d_out):
                 if p.value:
@@ -1305,7 +1514,7 @@ class Context:
             out[b] = s
         return out
 
-    def _rectify_mixed(self, frames, min_length, refine, cfg, clip, max_size, capacity, jpeg=None, interp="linear", jpeg_optimize=False):
+    def _rectify_mixed(self, frames, min_length, refine, cfg, clip, max_size, capacity, jpeg=None, interp="linear", jpeg_optimize=False, border=None, crop=False):
         """rectify_batch for a list of 8-bit frames of different shapes: all frames in one host buffer, one upload,
         rectify_frames_device, one download"""
         frames = [np.ascontiguousarray(f) for f in frames]
@@ -1322,18 +1531,20 @@ class Context:
         host = np.zeros(end, np.uint8)
         for f, (_, _, start, _) in zip(frames, sources):
             host[start: start + f.nbytes] = f.reshape(-1)
-        return self._rectify_resident(self.device_upload(host), sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp, jpeg_optimize)
+        _border_words(border, len(frames), fmt, "rectify_batch")  # (a bad spec: ValueError before anything goes up)
+        return self._rectify_resident(self.device_upload(host), sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp, jpeg_optimize, border, crop)
 
-    def _rectify_resident(self, d_src, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp="linear", jpeg_optimize=False):
+    def _rectify_resident(self, d_src, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp="linear", jpeg_optimize=False, border=None, crop=False):
         """rectify_batch for 8-bit frames (width, height, byte_offset, row_bytes) that lie at d_src, which is freed here:
         rectify_frames_device, then one download of the pictures, or with jpeg the encoder and the streams alone"""
         bpp = 3 if fmt == PIX_U8X3 else 1
         d_out = None
         try:
-            lines, tfs, table, d_out, total = self.rectify_frames_device(d_src, sources, fmt, min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, capacity=capacity, interp=interp)
+            lines, tfs, table, d_out, total, *more = self.rectify_frames_device(d_src, sources, fmt, min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, capacity=capacity, interp=interp, border=border, crop=crop)
+            rect = (lambda b: (more[0][b],)) if crop else (lambda b: ())
             if jpeg is not None:
                 streams = self._jpeg_results(d_out, total, fmt, table, jpeg, jpeg_optimize) if d_out else [None] * len(sources)
-                return [(lines[b], tfs[b], streams[b]) for b in range(len(sources))]
+                return [(lines[b], tfs[b], streams[b]) + rect(b) for b in range(len(sources))]
             packed = self.device_download(d_out, (total,), np.uint8) if d_out else None
         finally:
             self.device_free(d_src)
@@ -1346,11 +1557,11 @@ class Context:
             if ow:
                 rows = np.lib.stride_tricks.as_strided(packed[off:], (oh, ow * bpp), (row, 1))
                 img = np.ascontiguousarray(rows).reshape((oh, ow) + ((3,) if bpp == 3 else ()))
-            res.append((lines[b], tfs[b], img))
+            res.append((lines[b], tfs[b], img) + rect(b))
         return res
 
     def rectify_batch(self, frames_u8, min_length=None, refine=False, cfg=None, clip=3.0, max_size=None, capacity=4096, jpeg=None,
-                      orient=False, interp="linear", jpeg_optimize=False, any_sampling=False):
+                      orient=False, interp="linear", jpeg_optimize=False, any_sampling=False, border=None, crop=False):
         """Context.rectify for a batch: frames_u8 is a uint8 array [B, H, W] or [B, H, W, 3], or a list of such frames of one
         shape.  One upload, rectify_batch_device (one detector batch, the packed warp), one download.  Returns a
         list of (lines, transform, warped), frame by frame what rectify returns for it; warped is None for a frame whose
@@ -1374,28 +1585,37 @@ class Context:
         bit for bit the call on decode_jpeg_batch(files, any_sampling=True)'s arrays.  Without it the first such file raises
         LibrectifyError (status 2) for the whole batch.
         interp="cubic": the warp launch of whichever path is taken samples 4 x 4 bicubic (WARP_CUBIC); detector, transforms,
-        sizes and the encoder are untouched -- frame by frame what rectify(interp="cubic") returns."""
+        sizes and the encoder are untouched -- frame by frame what rectify(interp="cubic") returns.
+        border: None, one border_word spec for all frames or a list of one per frame (WARP_BORDER on the warp launch of
+        whichever path is taken); crop=True: every picture, or JPEG file, is its constrained crop and every result has a fourth
+        entry, the rectangle (x0, y0, width, height) -- frame by frame what rectify(border=, crop=) returns."""
         _sampling_bit(interp, "rectify_batch")
         _check_jpeg_optimize("rectify_batch", jpeg, jpeg_optimize)
         if _all_streams(frames_u8, "rectify_batch", orient, any_sampling):
+            try:  # (the files' format is known once they are decoded: a spec that suits neither 8-bit format fails here)
+                _border_words(border, len(frames_u8), PIX_U8X3, "rectify_batch")
+            except ValueError:
+                _border_words(border, len(frames_u8), PIX_U8, "rectify_batch")
             return self._rectify_streams([bytes(f) for f in frames_u8], min_length, refine, cfg, clip, max_size, capacity, jpeg, orient, interp, jpeg_optimize,
-                                         any_sampling)
+                                         any_sampling, border, crop)
         if not isinstance(frames_u8, np.ndarray):
             frames_u8 = [np.asarray(f) for f in frames_u8]
             if len({f.shape for f in frames_u8}) > 1:
-                return self._rectify_mixed(frames_u8, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp, jpeg_optimize)
+                return self._rectify_mixed(frames_u8, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp, jpeg_optimize, border, crop)
         a = np.ascontiguousarray(frames_u8 if isinstance(frames_u8, np.ndarray) else np.stack([np.asarray(f) for f in frames_u8]))
         if a.dtype != np.uint8 or a.ndim not in (3, 4) or (a.ndim == 4 and a.shape[3] != 3) or a.shape[0] < 1:
             raise ValueError("rectify_batch: uint8 frames [B, H, W] or [B, H, W, 3]")
         fmt, bpp = _frame_format(a[0], "rectify_batch")
         batch, h, w = a.shape[:3]
+        _border_words(border, batch, fmt, "rectify_batch")  # (a bad spec: ValueError before anything goes up)
         d_src = self.device_upload(a)
         d_out = None
         try:
-            lines, tfs, table, d_out, total = self.rectify_batch_device(d_src, batch, w, h, fmt, min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, capacity=capacity, interp=interp)
+            lines, tfs, table, d_out, total, *more = self.rectify_batch_device(d_src, batch, w, h, fmt, min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, capacity=capacity, interp=interp, border=border, crop=crop)
+            rect = (lambda b: (more[0][b],)) if crop else (lambda b: ())
             if jpeg is not None:
                 streams = self._jpeg_results(d_out, total, fmt, table, jpeg, jpeg_optimize) if d_out else [None] * batch
-                return [(lines[b], tfs[b], streams[b]) for b in range(batch)]
+                return [(lines[b], tfs[b], streams[b]) + rect(b) for b in range(batch)]
             packed = self.device_download(d_out, (total,), np.uint8) if d_out else None
         finally:
             self.device_free(d_src)
@@ -1403,12 +1623,12 @@ class Context:
                 self.device_free(d_out)
         res = []
         for b in range(batch):
-            ow, oh, off, row = (int(v) for v in table[b, 9:])
+            ow, oh, off, row = (int(v) for v in table[b, 9:13])
             img = None
             if ow:
                 rows = np.lib.stride_tricks.as_strided(packed[off:], (oh, ow * bpp), (row, 1))
                 img = np.ascontiguousarray(rows).reshape((oh, ow) + a.shape[3:])
-            res.append((lines[b], tfs[b], img))
+            res.append((lines[b], tfs[b], img) + rect(b))
         return res
 
     def set_seed_capacity(self, cap):

@@ -18,6 +18,7 @@ SOURCES = [
     "kernels_ransac.hip",
     "kernels_groups.hip",
     "kernels_warp.hip",
+    "kernels_warp_border.hip",
     "kernels_prepare.hip",
     "kernels_overlay.hip",
     "kernels_jpeg.hip",

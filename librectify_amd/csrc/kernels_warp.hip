@@ -21,6 +21,11 @@
 // taps of a source row are consecutive bytes and come in with one load (row_taps), straight through L1 / L2 like the
 // bilinear taps.
 //
+// LR_WARP_BORDER is a third template parameter of warp_lane: what a tap outside the source contributes is the frame's border
+// rule (a constant, or the pixel that replicate, reflect or reflect-101 names) instead of 0.  Pixels and rows of taps that lie
+// inside keep the loads above; only the others map their indices.  Its launches all go through warp_ragged_border_kernel, which
+// is kernels_warp_border.hip's; the lane body is in warp_lane.h for the two files.
+//
 // One lane body, two kernels.  warp_lane is a lane's work inside a tile: its four pixels' taps, blends and stores.  The two
 // kernels differ only in how a workgroup finds its frame and the frame's values, all of which depend on the tile index
 // alone and are uniform across the workgroup:
@@ -42,316 +47,10 @@
 #include <utility>
 #include <vector>
 
-#include "tables.h"
-#include "tiles.h"
+#include "warp_lane.h"
 
 namespace lramd {
 namespace {
-
-constexpr int kTileW = 64;  // destination pixels per tile row (16 lanes x 4 pixels)
-constexpr int kTileH = 16;  // destination rows per tile (4 wavefronts x 4 rows)
-constexpr int kBlock = 256;
-constexpr int kMaxGrid = 8 * 8192;  // beyond that the workgroups of an XCD loop over its run of tiles
-
-struct WarpArgs {
-    const uint8_t* src;
-    size_t src_image_bytes, src_row_bytes;
-    int w, h;
-    uint8_t* dst;
-    size_t dst_image_bytes, dst_row_bytes;
-    int ow, oh;
-    const double* M;  // 9 doubles per frame
-    int tiles_x, tiles_per_frame, n_tiles;
-};
-
-// a frame's record of the table kernel, 18 doubles long like the row of LR_WARP_RAGGED's table it is made from
-struct RaggedFrame {
-    double m[9];
-    unsigned long long offset, row_bytes;          // of its output, from the destination pointer
-    unsigned long long src_offset, src_row_bytes;  // of its source, from the source pointer
-    int ow, oh, tiles_x, w, h, pad[5];
-};
-static_assert(sizeof(RaggedFrame) == 18 * sizeof(double), "a record per 18 doubles of the mirror");
-
-struct RaggedArgs {
-    const uint8_t* src;
-    int batch, n_tiles;
-};
-
-// ((M0 x + M1 y) + M2) * Wq clamped to [INT_MIN, INT_MAX] and rounded half to even; a NaN fails both comparisons and
-// becomes INT_MIN, whose taps lie outside every source
-__device__ __forceinline__ int fixed_coord(double v) {
-    const double c = v >= 2147483647.0 ? 2147483647.0 : (v >= -2147483648.0 ? v : -2147483648.0);
-    return (int)rint(c);
-}
-
-struct Taps {
-    int ix, iy;        // the top-left tap
-    int w00, w01, w10, w11;  // weights of (ix, iy), (ix+1, iy), (ix, iy+1), (ix+1, iy+1); they sum to 1024
-};
-
-// the 5-bit fixed-point source coordinates of destination pixel (x, y): both sampling rules start from them
-__device__ __forceinline__ void fixed_xy(const double* __restrict__ m, unsigned x, unsigned y, int& X, int& Y) {
-    const double xd = (double)x, yd = (double)y;
-    const double W0 = (m[6] * xd + m[7] * yd) + m[8];
-    const double Wq = W0 != 0.0 ? 32.0 / W0 : 0.0;
-    X = fixed_coord(((m[0] * xd + m[1] * yd) + m[2]) * Wq);
-    Y = fixed_coord(((m[3] * xd + m[4] * yd) + m[5]) * Wq);
-}
-
-__device__ __forceinline__ Taps taps_of(const double* __restrict__ m, unsigned x, unsigned y) {
-    int X, Y;
-    fixed_xy(m, x, y, X, Y);
-    Taps t;
-    t.ix = X >> 5;
-    t.iy = Y >> 5;
-    const int ax = X & 31, ay = Y & 31;
-    t.w00 = (32 - ax) * (32 - ay);
-    t.w01 = ax * (32 - ay);
-    t.w10 = (32 - ax) * ay;
-    t.w11 = ax * ay;
-    return t;
-}
-
-__device__ __forceinline__ bool inside(int i, int n) { return (unsigned)i < (unsigned)n; }
-
-// the two horizontal taps (ix, ix+1) of one source row; 0 outside
-__device__ __forceinline__ void pair_u8(const uint8_t* row, bool row_in, int ix, int w, uint32_t& a, uint32_t& b) {
-    const bool in_a = row_in && inside(ix, w), in_b = row_in && inside(ix + 1, w);
-    a = 0;
-    b = 0;
-    if (in_a && in_b && ((reinterpret_cast<uintptr_t>(row) + (unsigned)ix) & 1u) == 0) {
-        const uint32_t v = *reinterpret_cast<const uint16_t*>(row + ix);
-        a = v & 0xFFu;
-        b = v >> 8;
-    } else {
-        if (in_a) a = row[ix];
-        if (in_b) b = row[ix + 1];
-    }
-}
-
-__device__ __forceinline__ void pair_f32(const uint8_t* row, bool row_in, int ix, int w, float& a, float& b) {
-    const bool in_a = row_in && inside(ix, w), in_b = row_in && inside(ix + 1, w);
-    a = 0.f;
-    b = 0.f;
-    const float* r = reinterpret_cast<const float*>(row);
-    if (in_a && in_b && ((reinterpret_cast<uintptr_t>(r + ix)) & 7u) == 0) {
-        const float2 v = *reinterpret_cast<const float2*>(r + ix);
-        a = v.x;
-        b = v.y;
-    } else {
-        if (in_a) a = r[ix];
-        if (in_b) b = r[ix + 1];
-    }
-}
-
-// one interleaved 3-byte tap at p: an aligned u16 and the byte beside it (two loads, no branch)
-__device__ __forceinline__ uint32_t tap_u8x3(const uint8_t* p, bool in) {
-    if (!in) return 0;
-    const uint32_t odd = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 1u);
-    const uint32_t v = *reinterpret_cast<const uint16_t*>(p + odd);
-    const uint32_t s = p[odd ? 0 : 2];
-    return odd ? (s | (v << 8)) : (v | (s << 16));  // bytes r | g << 8 | b << 16
-}
-
-__device__ __forceinline__ uint32_t blend_u8(uint32_t a, uint32_t b, uint32_t c, uint32_t d, const Taps& t) {
-    return (a * (uint32_t)t.w00 + b * (uint32_t)t.w01 + c * (uint32_t)t.w10 + d * (uint32_t)t.w11 + 512u) >> 10;
-}
-
-// ---- LR_WARP_CUBIC: the 4 x 4 bicubic rule (tests/numpy_warp_cubic_ref.py) ----
-
-template <int kFormat>
-struct PixelBytes {
-    static constexpr int value = kFormat == LR_PIX_U8 ? 1 : (kFormat == LR_PIX_U8X3 ? 3 : 4);
-};
-
-// The four horizontal taps (ix - 1 .. ix + 2) of one source row as the 4, 12 or 16 consecutive bytes they are, in kBpp
-// dwords; a tap outside the source is 0.  Where all four are inside, their bytes and no others come in with one load
-// (dword, dwordx3, dwordx4: global memory asks for no alignment of an 8-bit row's taps and for 4 bytes of f32's);
-// otherwise every tap that is inside is fetched on its own.  So no byte outside the row's own pixels [row, row + w * kBpp)
-// is ever read: not a row's padding, not a neighbouring frame, nothing behind the last row.
-template <int kFormat>
-__device__ __forceinline__ void row_taps(const uint8_t* row, bool row_in, int ix, int w, uint32_t (&d)[PixelBytes<kFormat>::value]) {
-    constexpr int kBpp = PixelBytes<kFormat>::value;
-#pragma unroll
-    for (int i = 0; i < kBpp; ++i) d[i] = 0;
-    if (!row_in) return;
-    const bool cols_in = ix >= 1 && ix + 2 < w;  // (|ix| <= 2^26: no overflow)
-    if constexpr (kFormat == LR_PIX_F32) {
-        const float* r = reinterpret_cast<const float*>(row);
-        if (cols_in) {  // sixteen bytes at a 4-byte aligned address: one dwordx4, which asks for no more than that
-            __builtin_memcpy(d, r + (ix - 1), 16);
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (inside(ix - 1 + i, w)) d[i] = __float_as_uint(r[ix - 1 + i]);
-        }
-    } else {
-        if (cols_in) {  // the taps' own 4 or 12 bytes, wherever they start: one load (global memory needs no alignment)
-            __builtin_memcpy(d, row + (size_t)(ix - 1) * kBpp, 4 * kBpp);
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int c = ix - 1 + i;
-                const bool in = inside(c, w);
-                if constexpr (kFormat == LR_PIX_U8) {
-                    if (in) d[0] |= (uint32_t)row[c] << (8 * i);
-                } else {
-                    const uint32_t t = tap_u8x3(row + (size_t)(in ? c : 0) * 3, in);
-                    const int bit = 24 * i;  // the tap's three bytes start at byte 3 i of the twelve
-                    d[(bit >> 5)] |= t << (bit & 31);
-                    if ((bit & 31) > 8) d[((bit >> 5) + 1)] |= t >> (32 - (bit & 31));
-                }
-            }
-        }
-    }
-}
-
-// One destination pixel by the bicubic rule: a u8 pixel's byte or a u8x3 pixel's bytes r | g << 8 | b << 16 in `px`, an
-// f32 pixel in `pf`.  8-bit: h_j = sum_i C[ax][i] v(i, j), s = sum_j C[ay][j] h_j, (s + 2^21) >> 22 clamped to 0 .. 255.
-// Everything fits int32: max sum |C[a]| is 2816 and 255 * 2816^2 + 2^21 = 2 024 210 432 < 2^31.  f32: weights C / 2048.f
-// (exact), rows and then the column summed from the first tap to the last, every product and sum rounded on its own.
-template <int kFormat>
-__device__ __forceinline__ void cubic_pixel(const double* m, const uint8_t* src, size_t src_row_bytes, int w, int h, unsigned x,
-                                            unsigned y, uint32_t& px, float& pf) {
-    constexpr int kBpp = PixelBytes<kFormat>::value;
-    constexpr int kChannels = kFormat == LR_PIX_U8X3 ? 3 : 1;
-    int X, Y;
-    fixed_xy(m, x, y, X, Y);
-    const int ix = X >> 5, iy = Y >> 5;
-    const int16_t* cx = kCubicWeights[X & 31];
-    const int16_t* cy = kCubicWeights[Y & 31];
-    const int wx[4] = {cx[0], cx[1], cx[2], cx[3]};
-    const int wy[4] = {cy[0], cy[1], cy[2], cy[3]};
-    int s[kChannels];
-#pragma unroll
-    for (int ch = 0; ch < kChannels; ++ch) s[ch] = 0;
-    float hf[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int ry = iy - 1 + j;
-        const bool row_in = inside(ry, h);
-        const uint8_t* row = src + (size_t)(row_in ? ry : 0) * src_row_bytes;
-        uint32_t d[kBpp];
-        row_taps<kFormat>(row, row_in, ix, w, d);
-        if constexpr (kFormat == LR_PIX_F32) {
-            const float v0 = __uint_as_float(d[0]), v1 = __uint_as_float(d[1]);
-            const float v2 = __uint_as_float(d[2]), v3 = __uint_as_float(d[3]);
-            hf[j] = ((v0 * ((float)wx[0] / 2048.0f) + v1 * ((float)wx[1] / 2048.0f)) + v2 * ((float)wx[2] / 2048.0f)) +
-                    v3 * ((float)wx[3] / 2048.0f);
-        } else {
-#pragma unroll
-            for (int ch = 0; ch < kChannels; ++ch) {
-                int hsum = 0;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int byte = kChannels * i + ch;
-                    hsum += wx[i] * (int)((d[(byte >> 2)] >> (8 * (byte & 3))) & 0xFFu);
-                }
-                s[ch] += wy[j] * hsum;
-            }
-        }
-    }
-    px = 0;
-    pf = 0.f;
-    if constexpr (kFormat == LR_PIX_F32) {
-        pf = ((hf[0] * ((float)wy[0] / 2048.0f) + hf[1] * ((float)wy[1] / 2048.0f)) + hf[2] * ((float)wy[2] / 2048.0f)) +
-             hf[3] * ((float)wy[3] / 2048.0f);
-    } else {
-#pragma unroll
-        for (int ch = 0; ch < kChannels; ++ch) {
-            // clamped BEFORE the shift ((s + 2^21) >> 22 within 0 .. 255 is s + 2^21 within 0 .. 2^30 - 1): the same value, but
-            // written as shift-then-clamp two neighbouring pixels become one v_ashr_pk_u8_i32, whose result the compiler
-            // takes to be zero above bit 15 while the instruction leaves other bits there, which then land in the lane's
-            // third and fourth pixel
-            const int t = min(max(s[ch] + (1 << 21), 0), (1 << 30) - 1);
-            px |= ((uint32_t)t >> 22) << (8 * ch);
-        }
-    }
-}
-
-// One lane's four consecutive pixels (x0 .. x0 + 3, those below ow) of destination row y, whose first byte is `out`;
-// kCubic: sampled by the bicubic rule above instead of the bilinear one
-template <int kFormat, bool kCubic>
-__device__ __forceinline__ void warp_lane(const double* m, const uint8_t* src, size_t src_row_bytes, int w, int h,
-                                          uint8_t* out, int ow, unsigned x0, unsigned y) {
-    const int n = min(4, ow - (int)x0);  // pixels of this lane inside the row
-
-    uint32_t res_u8 = 0;          // LR_PIX_U8: four bytes
-    uint32_t res_rgb[3] = {0, 0, 0};  // LR_PIX_U8X3: twelve bytes
-    float res_f[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (kCubic) {
-            uint32_t px;
-            cubic_pixel<kFormat>(m, src, src_row_bytes, w, h, x0 + (unsigned)k, y, px, res_f[k]);
-            if (kFormat == LR_PIX_U8) res_u8 |= px << (8 * k);
-            if (kFormat == LR_PIX_U8X3) {
-#pragma unroll
-                for (int ch = 0; ch < 3; ++ch) {
-                    const int byte = 3 * k + ch;  // byte of the lane's twelve
-                    res_rgb[byte >> 2] |= ((px >> (8 * ch)) & 0xFFu) << (8 * (byte & 3));
-                }
-            }
-            continue;
-        }
-        const Taps t = taps_of(m, x0 + (unsigned)k, y);
-        const bool in0 = inside(t.iy, h), in1 = inside(t.iy + 1, h);
-        const uint8_t* row0 = src + (size_t)(in0 ? t.iy : 0) * src_row_bytes;
-        const uint8_t* row1 = src + (size_t)(in1 ? t.iy + 1 : 0) * src_row_bytes;
-        if (kFormat == LR_PIX_U8) {
-            uint32_t a, bb, c, d;
-            pair_u8(row0, in0, t.ix, w, a, bb);
-            pair_u8(row1, in1, t.ix, w, c, d);
-            res_u8 |= blend_u8(a, bb, c, d, t) << (8 * k);
-        } else if (kFormat == LR_PIX_U8X3) {
-            const bool ia = inside(t.ix, w), ib = inside(t.ix + 1, w);
-            const size_t oa = (size_t)(ia ? t.ix : 0) * 3, ob = (size_t)(ib ? t.ix + 1 : 0) * 3;
-            const uint32_t p00 = tap_u8x3(row0 + oa, in0 && ia), p01 = tap_u8x3(row0 + ob, in0 && ib);
-            const uint32_t p10 = tap_u8x3(row1 + oa, in1 && ia), p11 = tap_u8x3(row1 + ob, in1 && ib);
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) {
-                const int s = 8 * ch;
-                const uint32_t v = blend_u8((p00 >> s) & 0xFFu, (p01 >> s) & 0xFFu, (p10 >> s) & 0xFFu, (p11 >> s) & 0xFFu, t);
-                const int byte = 3 * k + ch;  // byte of the lane's twelve
-                res_rgb[byte >> 2] |= v << (8 * (byte & 3));
-            }
-        } else {
-            float a, bb, c, d;
-            pair_f32(row0, in0, t.ix, w, a, bb);
-            pair_f32(row1, in1, t.ix, w, c, d);
-            const float f00 = (float)t.w00 / 1024.0f, f01 = (float)t.w01 / 1024.0f;
-            const float f10 = (float)t.w10 / 1024.0f, f11 = (float)t.w11 / 1024.0f;
-            res_f[k] = ((a * f00 + bb * f01) + c * f10) + d * f11;
-        }
-    }
-
-    if (kFormat == LR_PIX_U8) {
-        uint8_t* p = out + x0;
-        if (n == 4 && (reinterpret_cast<uintptr_t>(p) & 3u) == 0) {
-            *reinterpret_cast<uint32_t*>(p) = res_u8;
-        } else {
-            for (int k = 0; k < n; ++k) p[k] = (uint8_t)(res_u8 >> (8 * k));
-        }
-    } else if (kFormat == LR_PIX_U8X3) {
-        uint8_t* p = out + (size_t)x0 * 3;
-        if (n == 4 && (reinterpret_cast<uintptr_t>(p) & 3u) == 0) {
-            uint32_t* q = reinterpret_cast<uint32_t*>(p);
-            q[0] = res_rgb[0];
-            q[1] = res_rgb[1];
-            q[2] = res_rgb[2];
-        } else {
-            for (int k = 0; k < 3 * n; ++k) p[k] = (uint8_t)(res_rgb[k >> 2] >> (8 * (k & 3)));
-        }
-    } else {
-        float* p = reinterpret_cast<float*>(out) + x0;
-        if (n == 4 && (reinterpret_cast<uintptr_t>(p) & 15u) == 0) {
-            *reinterpret_cast<float4*>(p) = make_float4(res_f[0], res_f[1], res_f[2], res_f[3]);
-        } else {
-            for (int k = 0; k < n; ++k) p[k] = res_f[k];
-        }
-    }
-}
 
 template <int kFormat, bool kCubic>
 __global__ __launch_bounds__(kBlock) void warp_perspective_kernel(WarpArgs g) {
@@ -367,7 +66,7 @@ __global__ __launch_bounds__(kBlock) void warp_perspective_kernel(WarpArgs g) {
         if (y >= (unsigned)g.oh || x0 >= (unsigned)g.ow) continue;
         const uint8_t* src = g.src + (size_t)b * g.src_image_bytes;
         uint8_t* out = g.dst + (size_t)b * g.dst_image_bytes + (size_t)y * g.dst_row_bytes;
-        warp_lane<kFormat, kCubic>(g.M + (size_t)b * 9, src, g.src_row_bytes, g.w, g.h, out, g.ow, x0, y);
+        warp_lane<kFormat, kCubic, false>(g.M + (size_t)b * 9, src, g.src_row_bytes, g.w, g.h, out, g.ow, x0, y);
     }
 }
 
@@ -391,13 +90,36 @@ __global__ __launch_bounds__(kBlock) void warp_ragged_kernel(RaggedArgs g, const
         if (y >= (unsigned)oh || x0 >= (unsigned)ow) continue;
         const uint8_t* src = g.src + (size_t)f->src_offset;
         uint8_t* out = dst + (size_t)f->offset + (size_t)y * (size_t)f->row_bytes;
-        warp_lane<kFormat, kCubic>(f->m, src, (size_t)f->src_row_bytes, f->w, f->h, out, ow, x0, y);
+        warp_lane<kFormat, kCubic, false>(f->m, src, (size_t)f->src_row_bytes, f->w, f->h, out, ow, x0, y);
     }
+}
+
+// A frame's border word (LR_WARP_BORDER): mode + 8 * value, an integer.  Fills the record's two fields; on a fault returns
+// the reason (NULL: none).
+const char* parse_border_word(double word, int format, RaggedFrame* f) {
+    uint64_t v;
+    if (!table_integer(word, 0, 34359738367.0, &v)) return "is not an integer from 0 to 2^35 - 1";
+    const int mode = (int)(v & 7u);
+    const uint64_t value = v >> 3;
+    if (mode != kBorderConstant && mode != kBorderReplicate && mode != kBorderReflect && mode != kBorderReflect101)
+        return "names a mode that is not 0 (constant), 1 (replicate), 2 (reflect) or 4 (reflect-101)";
+    if (mode != kBorderConstant && value != 0) return "carries a value with a mode other than 0 (constant)";
+    if (format == LR_PIX_U8 && value > 0xFFu) return "carries a value above 255 for u8";
+    if (format == LR_PIX_U8X3 && value > 0xFFFFFFu) return "carries a value above 2^24 - 1 for u8x3";
+    if (format == LR_PIX_F32 && (value & 0x7F800000u) == 0x7F800000u) return "carries f32 bits that are not a finite float";
+    f->border_mode = mode;
+    f->border_value = (unsigned)value;
+    return nullptr;
+}
+
+int fail_border(const char* layout, int b, const char* why) {
+    set_error(std::string("lr_warp_perspective_device: ") + layout + "LR_WARP_BORDER: frame " + std::to_string(b) + ": the border word " + why);
+    return 1;
 }
 
 // The table kernel's launch: records, then the tiles' prefix table, go up in the mirror of the maps (in doubles: 18 a
 // frame + the table's ints)
-int launch_ragged(lr_context* c, const void* d_src, int format, bool cubic, const std::vector<RaggedFrame>& rec,
+int launch_ragged(lr_context* c, const void* d_src, int format, bool cubic, bool border, const std::vector<RaggedFrame>& rec,
                   const std::vector<int>& start, void* d_dst) {
     const size_t batch = rec.size(), rec_doubles = batch * 18;
     const int64_t n_tiles = start[batch];
@@ -415,6 +137,11 @@ int launch_ragged(lr_context* c, const void* d_src, int format, bool cubic, cons
     const RaggedFrame* frames = reinterpret_cast<const RaggedFrame*>(c->warp_m.d.get());
     const int* tile_start = reinterpret_cast<const int*>(c->warp_m.d.get() + rec_doubles);
     const int grid = (int)std::min<int64_t>((n_tiles + 7) / 8 * 8, kMaxGrid);
+    if (border) {  // (some frame's word is not 0: the kernels of kernels_warp_border.hip)
+        launch_warp_ragged_border(format, cubic, grid, c->stream, g.src, g.batch, g.n_tiles, frames, tile_start, dst);
+        LR_HIP(hipGetLastError());
+        return 0;
+    }
     launch_by_format_and_rule(format, cubic, [&](auto fmt, auto rule) {
         hipLaunchKernelGGL((warp_ragged_kernel<decltype(fmt)::value, decltype(rule)::value>), dim3(grid), dim3(kBlock), 0, c->stream, g, frames, tile_start, dst);
     });
@@ -425,7 +152,7 @@ int launch_ragged(lr_context* c, const void* d_src, int format, bool cubic, cons
 // lr_warp_perspective_device with LR_WARP_PACKED: M is the table of 13 doubles per frame, out_width x out_height bound the
 // frames' sizes and dst_image_bytes is the size of the whole destination region
 int warp_packed(lr_context* c, const void* d_src, size_t src_image_bytes, int batch, int width, int height, size_t src_row_bytes,
-                int format, bool cubic, const double* T, void* d_dst, size_t dst_bytes, int out_width, int out_height,
+                int format, bool cubic, bool border, const double* T, void* d_dst, size_t dst_bytes, int out_width, int out_height,
                 size_t dst_row_bytes) {
     auto fail = [](const char* what) {
         set_error(std::string("lr_warp_perspective_device: LR_WARP_PACKED: ") + what);
@@ -451,8 +178,10 @@ int warp_packed(lr_context* c, const void* d_src, size_t src_image_bytes, int ba
     std::vector<int> start((size_t)batch + 1);
     std::vector<std::pair<uint64_t, uint64_t>> extent((size_t)batch);  // [first byte, end)
     int64_t n_tiles = 0;
+    const size_t row_doubles = border ? 14 : 13;  // (LR_WARP_BORDER: the border word behind the row)
+    bool bordered = false;                        // some frame's word is not 0
     for (int b = 0; b < batch; ++b) {
-        const double* t = T + (size_t)b * 13;
+        const double* t = T + (size_t)b * row_doubles;
         for (int i = 0; i < 9; ++i)
             if (!std::isfinite(t[i])) return fail("M is not finite");
         uint64_t ow, oh, off, row;
@@ -479,22 +208,35 @@ int warp_packed(lr_context* c, const void* d_src, size_t src_image_bytes, int ba
         f.tiles_x = (int)((ow + kTileW - 1) / kTileW);
         f.w = width;
         f.h = height;
+        if (border) {
+            if (const char* why = parse_border_word(t[13], format, &f)) return fail_border("LR_WARP_PACKED: ", b, why);
+            bordered = bordered || t[13] != 0.0;
+        }
         start[(size_t)b] = (int)n_tiles;
         n_tiles += (int64_t)f.tiles_x * (int64_t)((oh + kTileH - 1) / kTileH);
         if (n_tiles > 0x7FFFFFF0ll) return fail("output larger than 2^31 tiles of 64 x 16 pixels");
     }
     start[(size_t)batch] = (int)n_tiles;
     if (extents_overlap(extent)) return fail("two frames' extents overlap");
-    return launch_ragged(c, d_src, format, cubic, rec, start, d_dst);
+    return launch_ragged(c, d_src, format, cubic, bordered, rec, start, d_dst);
 }
 
 // lr_warp_perspective_device with LR_WARP_RAGGED: M is the table of 18 doubles per frame, width x height and out_width x
 // out_height bound the frames' sizes, src_image_bytes and dst_image_bytes are the sizes of the two regions
 int warp_ragged(lr_context* c, const void* d_src, size_t src_bytes, int batch, int width, int height, size_t src_row_bytes,
-                int format, bool cubic, const double* T, void* d_dst, size_t dst_bytes, int out_width, int out_height,
+                int format, bool cubic, bool border, const double* T, void* d_dst, size_t dst_bytes, int out_width, int out_height,
                 size_t dst_row_bytes) {
     std::vector<RaggedEntry> e;
     int64_t n_tiles = 0;
+    // LR_WARP_BORDER: entry [17] is the frame's border word; the table's other checks see it as the 0 they ask for
+    std::vector<double> plain;
+    const double* words = T;
+    if (border && T && batch >= 1) {
+        plain.assign(T, T + (size_t)batch * 18);
+        for (int b = 0; b < batch; ++b) plain[(size_t)b * 18 + 17] = 0.0;
+        T = plain.data();
+    }
+    bool bordered = false;  // some frame's word is not 0
     if (ragged_parse(d_src, src_bytes, batch, width, height, src_row_bytes, format, false, T, d_dst, dst_bytes, out_width,
                      out_height, dst_row_bytes, kTileW, kTileH, e, &n_tiles))
         return 1;
@@ -515,11 +257,16 @@ int warp_ragged(lr_context* c, const void* d_src, size_t src_bytes, int batch, i
         f.tiles_x = (int)((s.ow + kTileW - 1) / kTileW);
         f.w = (int)s.w;
         f.h = (int)s.h;
+        if (border) {
+            const double word = words[(size_t)b * 18 + 17];
+            if (const char* why = parse_border_word(word, format, &f)) return fail_border("LR_WARP_RAGGED: ", b, why);
+            bordered = bordered || word != 0.0;
+        }
         start[(size_t)b] = tiles;
         tiles += f.tiles_x * (int)((s.oh + kTileH - 1) / kTileH);
     }
     start[(size_t)batch] = tiles;
-    return launch_ragged(c, d_src, format, cubic, rec, start, d_dst);
+    return launch_ragged(c, d_src, format, cubic, bordered, rec, start, d_dst);
 }
 
 }  // namespace
@@ -598,6 +345,15 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
         if (format & LR_WARP_JPEG_DECODE) return fail("LR_WARP_CUBIC together with LR_WARP_JPEG_DECODE (the decoder samples nothing)");
         format &= ~LR_WARP_CUBIC;
     }
+    // LR_WARP_BORDER: a border word per frame behind (LR_WARP_RAGGED: in) its row of M; likewise of the three warps alone
+    const bool border = (format & LR_WARP_BORDER) != 0;
+    if (border) {
+        if (format & LR_WARP_PREPARE) return fail("LR_WARP_BORDER together with LR_WARP_PREPARE (the prepare step reads no pixel outside its source)");
+        if (format & LR_WARP_LINES) return fail("LR_WARP_BORDER together with LR_WARP_LINES (the lines picture samples nothing)");
+        if (format & LR_WARP_JPEG) return fail("LR_WARP_BORDER together with LR_WARP_JPEG (the encoder samples nothing)");
+        if (format & LR_WARP_JPEG_DECODE) return fail("LR_WARP_BORDER together with LR_WARP_JPEG_DECODE (the decoder samples nothing)");
+        format &= ~LR_WARP_BORDER;
+    }
     if (format & LR_WARP_JPEG_DECODE) {  // lr_decode_jpeg_device (kernels_jpeg_decode.hip): its own arguments arrive behind M
         // (LR_JPEG_ANY_SAMPLING is the decoder's own option and travels on with the format)
         if ((format & ~(0xFF | LR_JPEG_ANY_SAMPLING)) != LR_WARP_JPEG_DECODE) return fail("LR_WARP_JPEG_DECODE together with another option bit");
@@ -630,7 +386,7 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
         const int opts = format & ~0xFF;
         if (opts & LR_WARP_PACKED) return fail("LR_WARP_RAGGED together with LR_WARP_PACKED (ragged outputs are always packed)");
         if (opts == LR_WARP_RAGGED)
-            return warp_ragged(c, d_src, src_image_bytes, batch, width, height, src_row_bytes, format & 0xFF, cubic, M, d_dst,
+            return warp_ragged(c, d_src, src_image_bytes, batch, width, height, src_row_bytes, format & 0xFF, cubic, border, M, d_dst,
                                dst_image_bytes, out_width, out_height, dst_row_bytes);
         if (opts == (LR_WARP_RAGGED | LR_WARP_PREPARE))
             return ctx_prepare_ragged(c, d_src, src_image_bytes, batch, width, height, src_row_bytes, format & 0xFF, M, d_dst,
@@ -639,7 +395,7 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
     }
     if (format & ~0xFF) {  // option bits above the pixel format
         if ((format & ~0xFF) == LR_WARP_PACKED)
-            return warp_packed(c, d_src, src_image_bytes, batch, width, height, src_row_bytes, format & 0xFF, cubic, M, d_dst,
+            return warp_packed(c, d_src, src_image_bytes, batch, width, height, src_row_bytes, format & 0xFF, cubic, border, M, d_dst,
                                dst_image_bytes, out_width, out_height, dst_row_bytes);
         if ((format & ~0xFF) == (LR_WARP_PACKED | LR_WARP_PREPARE)) return fail("LR_WARP_PACKED together with LR_WARP_PREPARE");
         if ((format & ~0xFF) != LR_WARP_PREPARE) return fail("unknown option bits in format");
@@ -664,15 +420,42 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
                                dst_row_bytes | (batch > 1 ? (src_image_bytes | dst_image_bytes) : 0);
         if (bits & 3u) return fail("f32 pointer or stride not 4-byte aligned");
     }
-    for (size_t i = 0; i < (size_t)batch * 9; ++i)
-        if (!std::isfinite(M[i])) return fail("M is not finite");
+    const size_t row_doubles = border ? 10 : 9;  // (LR_WARP_BORDER: the border word behind the map)
+    for (size_t b = 0; b < (size_t)batch; ++b)
+        for (size_t i = 0; i < 9; ++i)
+            if (!std::isfinite(M[b * row_doubles + i])) return fail("M is not finite");
     const int64_t tiles_x = ((int64_t)out_width + kTileW - 1) / kTileW, tiles_y = ((int64_t)out_height + kTileH - 1) / kTileH;
     const int64_t n_tiles = tiles_x * tiles_y * (int64_t)batch;
     if (n_tiles > 0x7FFFFFF0ll) return fail("output larger than 2^31 tiles of 64 x 16 pixels");
+    if (border) {  // the frames as records of the table kernel; where every word is 0, the launch below as without the bit
+        std::vector<RaggedFrame> rec((size_t)batch);
+        std::vector<int> start((size_t)batch + 1);
+        bool bordered = false;
+        for (int b = 0; b < batch; ++b) {
+            const double* t = M + (size_t)b * 10;
+            RaggedFrame& f = rec[(size_t)b];
+            std::memset(&f, 0, sizeof f);
+            std::memcpy(f.m, t, sizeof f.m);
+            f.offset = (uint64_t)b * dst_image_bytes;
+            f.row_bytes = dst_row_bytes;
+            f.src_offset = (uint64_t)b * src_image_bytes;
+            f.src_row_bytes = src_row_bytes;
+            f.ow = out_width;
+            f.oh = out_height;
+            f.tiles_x = (int)tiles_x;
+            f.w = width;
+            f.h = height;
+            if (const char* why = parse_border_word(t[9], format, &f)) return fail_border("", b, why);
+            bordered = bordered || t[9] != 0.0;
+            start[(size_t)b] = (int)(tiles_x * tiles_y * b);
+        }
+        start[(size_t)batch] = (int)n_tiles;
+        if (bordered) return launch_ragged(c, d_src, format, cubic, true, rec, start, d_dst);
+    }
 
     LR_HIP(hipSetDevice(c->device));
     if (upload_reserve(c, c->warp_m, c->ev_warp_m, (size_t)batch * 9)) return 1;
-    std::memcpy(c->warp_m.h, M, (size_t)batch * 9 * sizeof(double));
+    for (size_t b = 0; b < (size_t)batch; ++b) std::memcpy(c->warp_m.h + b * 9, M + b * row_doubles, 9 * sizeof(double));
     if (upload_send(c, c->warp_m, c->ev_warp_m, (size_t)batch * 9 * sizeof(double))) return 1;
 
     WarpArgs g;

@@ -1,0 +1,46 @@
+// LR_WARP_BORDER: the perspective warp's kernels with a border rule per frame (kernels_warp.hip has the layout of tiles and
+// records, warp_lane.h the lane body).  A translation unit and so a code object of their own: a process that never sets the bit
+// loads the warp's code as it was.
+#include "warp_lane.h"
+
+namespace lramd {
+namespace {
+
+// LR_WARP_BORDER: warp_ragged_kernel with a border rule per frame (the record's border_mode and border_value, uniform across
+// the workgroup like the rest of the record).  A kernel of its own name, so that the unbordered kernels are the parent's.
+template <int kFormat, bool kCubic>
+__global__ __launch_bounds__(kBlock) void warp_ragged_border_kernel(RaggedArgs g, const RaggedFrame* __restrict__ frames,
+                                                                    const int* __restrict__ start, uint8_t* __restrict__ dst) {
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    const unsigned lx = (unsigned)lane & 15u, row_in_tile = (unsigned)(wave * 4 + (lane >> 4));
+    XcdBand band(g.n_tiles);
+    for (int tile; band.next(&tile);) {
+        const int b = frame_of_tile(start, g.batch, tile);
+        const RaggedFrame* f = frames + b;
+        const int ow = f->ow, oh = f->oh, tiles_x = f->tiles_x;
+        const int r = tile - start[b];
+        const int ty = r / tiles_x, tx = r - ty * tiles_x;
+        const unsigned y = (unsigned)ty * kTileH + row_in_tile;
+        const unsigned x0 = (unsigned)tx * kTileW + lx * 4u;
+        if (y >= (unsigned)oh || x0 >= (unsigned)ow) continue;
+        const uint8_t* src = g.src + (size_t)f->src_offset;
+        uint8_t* out = dst + (size_t)f->offset + (size_t)y * (size_t)f->row_bytes;
+        warp_lane<kFormat, kCubic, true>(f->m, src, (size_t)f->src_row_bytes, f->w, f->h, out, ow, x0, y, f->border_mode, f->border_value);
+    }
+}
+
+}  // namespace
+
+void launch_warp_ragged_border(int format, bool cubic, int grid, hipStream_t stream, const uint8_t* src, int batch, int n_tiles,
+                               const void* frames, const int* start, uint8_t* dst) {
+    RaggedArgs g;
+    g.src = src;
+    g.batch = batch;
+    g.n_tiles = n_tiles;
+    launch_by_format_and_rule(format, cubic, [&](auto fmt, auto rule) {
+        hipLaunchKernelGGL((warp_ragged_border_kernel<decltype(fmt)::value, decltype(rule)::value>), dim3(grid), dim3(kBlock), 0, stream, g,
+                           static_cast<const RaggedFrame*>(frames), start, dst);
+    });
+}
+
+}  // namespace lramd
