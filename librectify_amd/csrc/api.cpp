@@ -9,6 +9,7 @@
 #include <string>
 
 #include "context.h"
+#include "host.h"
 
 using namespace lramd;
 
@@ -41,6 +42,9 @@ lr_context* thread_context() {
 int upload_host_image(lr_context* c, const float* buffer, int width, int height, int stride, int num_threads) {
     if (ctx_upload_frame(c, 0, buffer, width, height, stride, num_threads)) return 1;
     LR_HIP(hipStreamWaitEvent(c->stream, c->ev_up[0], 0));
+    // A pageable frame has been copied into the staging buffer by now; a page-locked one is read where it lies, by a
+    // transfer that may not have started: the caller may change its buffer as soon as the call returns, so wait for it.
+    if (lramd::is_page_locked(buffer)) LR_HIP(hipEventSynchronize(c->ev_up[0]));
     return 0;
 }
 
@@ -95,7 +99,7 @@ int nothing_found(int batch, int width, int height, int* n_lines, const Rectific
 int copy_out(const std::vector<LineSegment>& v, LineSegment* out, int capacity, int* n_lines) {
     const int n = (int)v.size();
     if (n_lines) *n_lines = n;
-    if (out && capacity > 0) std::memcpy(out, v.data(), sizeof(LineSegment) * (size_t)std::min(n, capacity));
+    if (out && capacity > 0 && n > 0) std::memcpy(out, v.data(), sizeof(LineSegment) * (size_t)std::min(n, capacity));  // (an empty vector's data() may be null)
     return 0;
 }
 

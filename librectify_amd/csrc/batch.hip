@@ -86,7 +86,7 @@ struct BatchOut {
     void write(int b, const std::vector<LineSegment>& res, int w, int h) const {
         const int n = (int)res.size();
         if (n_lines) n_lines[b] = n;
-        if (out && capacity > 0) std::memcpy(out + (size_t)b * capacity, res.data(), sizeof(LineSegment) * (size_t)std::min(n, capacity));
+        if (out && capacity > 0 && n > 0) std::memcpy(out + (size_t)b * capacity, res.data(), sizeof(LineSegment) * (size_t)std::min(n, capacity));
         if (transforms) {
             const RectificationConfig def;
             transforms[b] = rectification_transform(res.data(), std::min(n, capacity > 0 ? capacity : n), w, h, cfg ? *cfg : def);
