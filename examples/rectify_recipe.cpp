@@ -6,7 +6,7 @@
 //
 //   rectify_recipe in.pgm|in.ppm out_prefix [--max-size N|fraction] [--refine] [--threads N]
 //                  [--h-strategy rotate_h|rotate_v|rectify|keep] [--v-strategy ...] [--warp] [--device-prepare] [--lines]
-//                  [--jpeg Q] [--optimize] [--jpeg-in] [--orient] [--any-sampling] [--cubic] [--border MODE[:VALUE]] [--crop]
+//                  [--jpeg Q] [--optimize] [--jpeg-in] [--orient] [--any-sampling] [--scale N] [--cubic] [--border MODE[:VALUE]] [--crop]
 //
 // Input is a binary PGM (P5, 8 bit) or PPM (P6, 8 bit; converted with the usual integer luma weights
 // (4899 R + 9617 G + 1868 B + 8192) >> 14).  Image decoding stays with the caller's imaging library.
@@ -35,6 +35,10 @@
 // --any-sampling (with --jpeg-in alone): LR_JPEG_ANY_SAMPLING is or-ed into the format of lr_decode_jpeg_device (lr_jpeg_info
 // is that call in probe mode, so the same word goes to both): a file of 4:4:0 (a losslessly rotated 4:2:2 photograph), 4:1:1 or
 // any other sampling with factors 1, 2 or 4 is decoded, which without the option is refused with status 2.
+// --scale N (with --jpeg-in alone; N = 1, 2, 4 or 8): the file is decoded at 1/N of its size -- LR_JPEG_SCALED is or-ed into the
+// format and entry [6] of the frame's row is N, for lr_jpeg_info's probe call, which then tells the reduced size ceil(w / N) x
+// ceil(h / N), and for lr_decode_jpeg_device, which averages the blocks' samples in its transform.  Everything behind the
+// decoder works on the reduced picture, so the segments and the homography are in its coordinates (the file's, divided by N).
 // --border MODE[:VALUE] (with --warp or --jpeg alone): what lies outside the source in the rectified picture, LR_WARP_BORDER --
 // MODE constant, replicate, reflect or reflect101; VALUE (constant only) a gray level 0 .. 255 or R,G,B, default 0.
 // --crop (likewise): the rectified picture is its constrained crop (lr_crop_homography: the largest upright rectangle of the
@@ -112,16 +116,16 @@ bool load_pnm(const std::string& path, Gray& g) {
 }
 
 // --jpeg-in: the file decoded on the GPU into g.raw (and g.px, for --lines).  Returns false with the reason on stderr.
-bool load_jpeg(const std::string& path, bool orient, bool any_sampling, Gray& g) {
+bool load_jpeg(const std::string& path, bool orient, bool any_sampling, int scale, Gray& g) {
     std::ifstream f(path, std::ios::binary);
     std::vector<uint8_t> file((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
     if (!f || file.empty()) {
         std::fprintf(stderr, "cannot read %s\n", path.c_str());
         return false;
     }
-    double frame[8] = {0, (double)file.size(), 0, 0, 0, 0, 0, orient ? 1.0 : 0.0};
+    double frame[8] = {0, (double)file.size(), 0, 0, 0, 0, (double)scale, orient ? 1.0 : 0.0};
     int32_t info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const int option = any_sampling ? LR_JPEG_ANY_SAMPLING : 0;
+    const int option = (any_sampling ? LR_JPEG_ANY_SAMPLING : 0) | (scale ? LR_JPEG_SCALED : 0);
     // (lr_jpeg_info spelled out, for the option: the decoder call without a destination and without a context)
     if (lr_decode_jpeg_device(nullptr, nullptr, file.data(), file.size(), LR_PIX_U8X3 | option, frame, 1, nullptr, 0, info) != 0 || info[5] != 0) {
         std::fprintf(stderr, "jpeg input failed: %s\n", lr_last_error());
@@ -425,8 +429,8 @@ int main(int argc, char** argv) {
         std::fprintf(stderr,
                      "usage: %s in.pgm|in.ppm out_prefix [--max-size N|fraction] [--refine] [--threads N]\n"
                      "          [--h-strategy rotate_h|rotate_v|rectify|keep] [--v-strategy ...] [--warp] [--device-prepare]\n"
-                     "          [--lines] [--jpeg Q] [--optimize] [--jpeg-in] [--orient] [--any-sampling] [--cubic]\n"
-                     "          [--border constant|replicate|reflect|reflect101[:VALUE]] [--crop]\n",
+                     "          [--lines] [--jpeg Q] [--optimize] [--jpeg-in] [--orient] [--any-sampling] [--scale 1|2|4|8]\n"
+                     "          [--cubic] [--border constant|replicate|reflect|reflect101[:VALUE]] [--crop]\n",
                      argv[0]);
         return 2;
     }
@@ -434,7 +438,7 @@ int main(int argc, char** argv) {
     bool refine = false, warp = false, device_prepare = false, lines_pictures = false, jpeg_in = false, orient = false, any_sampling = false, cubic = false;
     bool optimize = false, bordered = false, crop = false;
     Border border;
-    int threads = -1, jpeg = 0;
+    int threads = -1, jpeg = 0, decode_scale = 0;
     RectificationConfig cfg;
     cfg.horizontal_vp_min_distance = 2;  // autorectify.cpp:347
     for (int i = 3; i < argc; ++i) {
@@ -447,6 +451,8 @@ int main(int argc, char** argv) {
         else if (a == "--jpeg-in") jpeg_in = device_prepare = true;
         else if (a == "--orient") orient = true;
         else if (a == "--any-sampling") any_sampling = true;
+        else if (a == "--scale" && has_val && lr_jpeg_scaled_size(1, std::atoi(argv[i + 1])) == 1 && std::atoi(argv[i + 1]) != 0)
+            decode_scale = std::atoi(argv[++i]);
         else if (a == "--cubic") cubic = true;
         else if (a == "--optimize") optimize = true;
         else if (a == "--crop") crop = true;
@@ -475,6 +481,10 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--any-sampling goes with --jpeg-in: a PGM or PPM file has no chroma sampling\n");
         return 2;
     }
+    if (decode_scale && !jpeg_in) {
+        std::fprintf(stderr, "--scale goes with --jpeg-in: it is the decoder's reduction, and a PGM or PPM file is not decoded\n");
+        return 2;
+    }
     if (optimize && jpeg <= 0) {
         std::fprintf(stderr, "--optimize goes with --jpeg Q: it is the encoder's choice of Huffman tables\n");
         return 2;
@@ -489,7 +499,7 @@ int main(int argc, char** argv) {
     }
     Gray full;
     if (jpeg_in) {
-        if (!load_jpeg(argv[1], orient, any_sampling, full)) return 1;
+        if (!load_jpeg(argv[1], orient, any_sampling, decode_scale, full)) return 1;
     } else if (!load_pnm(argv[1], full)) {
         std::fprintf(stderr, "cannot read %s (binary PGM/PPM, 8 bit, expected)\n", argv[1]);
         return 1;

@@ -543,7 +543,7 @@ static inline size_t lr_jpeg_bound(int width, int height, int format, int layout
  * encoder's, because the host needs the statuses.
  * `frames` is a HOST table of 8 doubles per frame: [0] [1] byte offset and length of the stream in the source region (a
  * length below 2^31), [2] [3] byte offset of the picture from d_dst and its row stride in bytes, [4] [5] the width and
- * height the caller allocated for, [6] reserved, 0, [7] 1 to apply the file's EXIF orientation (below), else 0.  `h_src` is a HOST copy of the source region (same layout as d_src):
+ * height the caller allocated for, [6] reserved, 0 (with LR_JPEG_SCALED, below: the scale denominator), [7] 1 to apply the file's EXIF orientation (below), else 0.  `h_src` is a HOST copy of the source region (same layout as d_src):
  * the host reads the headers up to SOS from it and nothing behind them.  `format` is the OUTPUT's format: LR_PIX_U8 gives the
  * luminance plane (of a colour stream Y alone: its chrominance is entropy-decoded but never transformed), LR_PIX_U8X3 gives
  * RGB with c0 red (a one-component stream replicated).  The table follows LR_WARP_RAGGED's rules: integers (at most 2^53),
@@ -593,6 +593,24 @@ static inline size_t lr_jpeg_bound(int width, int height, int format, int layout
  * option they come out byte for byte as without it, and info [3] keeps 0, 1, 2 for them; for every other accepted sampling
  * info [3] is component 0's sampling byte of SOF (h << 4 | v: 0x12 = 18 for 4:4:0, 0x41 = 65 for 4:1:1), which cannot
  * collide with 0..2.  Without the option every call does, reports and launches exactly what it did before there was one.
+ * Reduced size: LR_JPEG_SCALED (0x80000) or-ed into `format` (beside LR_JPEG_ANY_SAMPLING or without it; probe mode
+ * included) gives entry [6] of every frame's row a meaning: that frame's scale denominator N.  0 or 1: as stored; 2, 4 or
+ * 8: the picture at 1/N of its size, ceil(w / N) x ceil(h / N) (lr_jpeg_scaled_size); anything else is a table error that
+ * names the frame and [6].  Frames of different N mix in one call.  The reduced size takes the stored size's place
+ * everywhere: info [0] [1] (with [7] = 1 swapped for 5..8 after the reduction), the table's [4] [5] and status 3 with its
+ * message, the stride [3], probe mode.  So: probe with the bit and [6], allocate info [0] x info [1], decode with the same
+ * row.  Without the bit a non-zero [6] is the table error it always was.  The rule, exact and in integers: for component i
+ * and each axis on its own let rho be the ratio of the largest sampling factor to the component's (1, 2 or 4), d = min(N,
+ * rho), r = N / d (the reduction of the component's blocks on that axis, 1..8) and rho' = rho / d (the upsampling that is
+ * left).  The reduced samples are S'[Y][X] = (sum over j < ry, i < rx of S[Y ry + j][X rx + i] + rx ry / 2) >> log2(rx ry),
+ * S being the component's samples as the inverse transform leaves them (clamped to 0..255, the blocks' padding beyond the
+ * component's size included; r divides 8, so a cell lies in one block); the reduced grid is ceil(cw_i / rx) x ceil(ch_i /
+ * ry); it is upsampled per axis by rho' with the rule above (the sample, the triangle, replication), clamped at the reduced
+ * grid's size; the colour rule is the same.  LR_PIX_U8 reduces the luminance alone.  A 4:2:0 file at N = 2 thus has its
+ * luminance averaged 2 x 2 and its chrominance taken as it is, with no upsampling at all.  N = 1 is byte for byte the
+ * unscaled decode, and the orientation is applied to the reduced picture as to a full one.  The reduced picture is within
+ * a few levels of the N x N box average of the full decode (DESIGN.md section 3, item 14 has the figures); coordinates
+ * found in it are the file's divided by N.
  * The tag: of the segments before SOS the first APP1 whose payload starts with "Exif\0\0" counts and later ones do not
  * (other APP1 segments, XMP for one, are passed over).  Behind those six bytes lies a TIFF block: "II*\0" (little endian)
  * or "MM\0*" (big endian), a 32-bit offset of IFD0 from the block's start, there a 16-bit count and 12-byte entries (tag,
@@ -611,7 +629,7 @@ static inline size_t lr_jpeg_bound(int width, int height, int format, int layout
  * the context's workspace: lr_context_trim frees them.
  * The call travels through lr_warp_perspective_device like lr_encode_jpeg_device: LR_WARP_JPEG_DECODE or-ed into `format`,
  * `M` pointing to an lr_jpeg_decode_args, src_image_bytes and dst_image_bytes the two regions' sizes, and width, height,
- * out_width, out_height and both row strides 0 (any option bit but LR_JPEG_ANY_SAMPLING, or a non-zero one of these,
+ * out_width, out_height and both row strides 0 (any option bit but LR_JPEG_ANY_SAMPLING and LR_JPEG_SCALED, or a non-zero one of these,
  * fails cleanly). */
 typedef struct lr_jpeg_decode_args {
     const void* h_src;    /* HOST copy of the stream region (same layout as d_src); only the headers are read from it */
@@ -619,7 +637,14 @@ typedef struct lr_jpeg_decode_args {
     int32_t* info;        /* HOST, 8 int32 per frame, written by the call */
 } lr_jpeg_decode_args;
 enum lr_warp_jpeg_decode { LR_WARP_JPEG_DECODE = 0x4000 }; /* or-ed into `format` like lr_warp_option */
-enum lr_jpeg_decode_option { LR_JPEG_ANY_SAMPLING = 0x20000 }; /* or-ed into lr_decode_jpeg_device's `format` (see above) */
+enum lr_jpeg_decode_option { LR_JPEG_ANY_SAMPLING = 0x20000, LR_JPEG_SCALED = 0x80000 }; /* or-ed into lr_decode_jpeg_device's `format` (see above) */
+/* One side of the picture that a frame of n samples gives at scale denominator N (LR_JPEG_SCALED, entry [6]: 0 or 1 as
+ * stored, 2, 4, 8): ceil(n / N).  0 for anything else. */
+static inline int lr_jpeg_scaled_size(int n, int N) {
+    if (N == 0) N = 1;
+    if (n < 1 || (N != 1 && N != 2 && N != 4 && N != 8)) return 0;
+    return (n + N - 1) / N;
+}
 static inline int lr_decode_jpeg_device(lr_context* ctx, const void* d_src, const void* h_src, size_t src_bytes, int format,
                                         const double* frames, int batch, void* d_dst, size_t dst_bytes, int32_t* info) {
     lr_jpeg_decode_args a;

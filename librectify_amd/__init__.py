@@ -85,6 +85,7 @@ WARP_LINES = 0x1000  # enum lr_warp_lines, likewise: lr_draw_lines_device, whose
 JPEG_OPTIMIZE = 0x10  # enum lr_jpeg_option: added to [7] of a row of jpeg_table (its optimize=), and to lr_jpeg_bound's layout
 WARP_JPEG = 0x2000  # enum lr_warp_jpeg, likewise: lr_encode_jpeg_device, whose own arguments travel behind M (JpegArgs)
 WARP_CUBIC = 0x8000  # enum lr_warp_sampling, likewise: the warp (plain, WARP_PACKED, WARP_RAGGED) samples 4 x 4 bicubic, not bilinear
+JPEG_SCALED = 0x80000  # enum lr_jpeg_decode_option: or-ed into lr_decode_jpeg_device's format, entry [6] of a frame's row is its scale denominator (1, 2, 4, 8)
 JPEG_ANY_SAMPLING = 0x20000  # enum lr_jpeg_decode_option: or-ed into lr_decode_jpeg_device's format, it admits every sampling with factors 1, 2, 4
 WARP_JPEG_DECODE = 0x4000  # enum lr_warp_jpeg_decode, likewise: lr_decode_jpeg_device, whose own arguments travel behind M (JpegDecodeArgs)
 WARP_BORDER = 0x40000  # enum lr_warp_border, likewise: a border word per frame in the warp's table (border_word, border= of the tables)
@@ -570,12 +571,14 @@ def jpeg_table(sizes, sources, outputs, quality, layout=0, optimize=False):
     return table.astype(np.float64)
 
 
-def jpeg_decode_table(streams, outputs=None, sizes=None, orient=False):
+def jpeg_decode_table(streams, outputs=None, sizes=None, orient=False, scale=None):
     """The table of lr_decode_jpeg_device: streams: B pairs (byte_offset, length) of the streams in the source region;
     outputs: B pairs (byte_offset, row_bytes) of the pictures in the destination region; sizes: B pairs (width, height)
     the caller allocated for.  outputs and sizes None: probe mode's table (zeros).  orient: True, False or B of them:
     entry [7], the file's EXIF orientation is applied (sizes are then those of the upright picture, as probe mode with
-    the same orient tells them).  Returns float64 (B, 8).  Rejects what can be seen without the regions: entries below 0
+    the same orient tells them).  scale: None, or an int or B ints out of 1, 2, 4, 8: entry [6], the frame's scale
+    denominator for a call that carries JPEG_SCALED (sizes are then those of the reduced picture, ceil(w / N) x ceil(h / N),
+    as probe mode with the same scale tells them); None leaves [6] 0.  Returns float64 (B, 8).  Rejects what can be seen without the regions: entries below 0
     or above 2^53, a length of 2^31 - 16 or more, sizes outside 1 .. 65535.  Needs no GPU."""
     st = np.asarray(streams)
     if st.ndim != 2 or st.shape[1] != 2 or not np.issubdtype(st.dtype, np.integer) or len(st) < 1:
@@ -594,6 +597,8 @@ def jpeg_decode_table(streams, outputs=None, sizes=None, orient=False):
         raise ValueError("jpeg_decode_table: orient is True, False or B of them")
     table = np.concatenate([c.astype(np.int64) for c in cols] + [np.zeros((B, 2), np.int64)], axis=1)
     table[:, 7] = flags
+    if scale is not None:
+        table[:, 6] = _scales(scale, B, "jpeg_decode_table")
     if table.min() < 0 or table.max() > 2 ** 53:
         raise ValueError("jpeg_decode_table: an entry below 0 or above 2^53")
     if int(table[:, 1].max()) > 2 ** 31 - 16:
@@ -627,16 +632,39 @@ def _decode_call(handle, d_src, region, fmt, table, d_dst, dst_bytes):
     return info
 
 
-def jpeg_info(streams, orient=False, any_sampling=False):
+def _scales(scale, B, what):
+    """scale= as B scale denominators"""
+    n = np.asarray(scale)
+    if not np.issubdtype(n.dtype, np.integer) or n.shape not in ((), (B,)) or not np.isin(n, (1, 2, 4, 8)).all():
+        raise ValueError(what + ": scale is None, or one or B of 1, 2, 4, 8")
+    return np.broadcast_to(n, (B,)).astype(np.int64)
+
+
+def _scaled_bit(scale):
+    return 0 if scale is None else JPEG_SCALED
+
+
+def jpeg_scale_for(sizes, max_size):
+    """decode_max_size's choice (PIL's Image.draft rule): per (width, height) the largest N of 1, 2, 4, 8 whose reduced
+    picture's longer side, ceil(max(w, h) / N), is still at least max_size; 1 if none is"""
+    if int(max_size) != max_size or max_size < 1:
+        raise ValueError("decode_max_size is an integer of at least 1")
+    return [max([1] + [n for n in (2, 4, 8) if -(-max(int(w), int(h)) // n) >= max_size]) for w, h in sizes]
+
+
+def jpeg_info(streams, orient=False, any_sampling=False, scale=None):
     """lr_jpeg_info (lr_decode_jpeg_device's probe mode): of every JPEG file in the list (bytes) width, height, components,
     layout (0 = 4:2:0 or one component, 1 = 4:4:4, 2 = 4:2:2), restart interval and status (JPEG_OK, ...), from the headers
     alone.  orient=True: width and height are the upright picture's (swapped for the EXIF orientations 5 .. 8) and the
     last column is the orientation, 1 .. 8 (1: the file tells none).  any_sampling=True (LR_JPEG_ANY_SAMPLING): a
     three-component file of any sampling with factors 1, 2 or 4, the luminance's the largest and at most 10 blocks to the
     MCU, is status 0 as well, its layout column being the luminance's sampling byte (0x12 = 18 for 4:4:0, 0x41 = 65 for
-    4:1:1).  Returns int32 (B, 8).  No context, no GPU."""
+    4:1:1).  scale (None, an int or B ints out of 1, 2, 4, 8; LR_JPEG_SCALED): width and height are those of the picture
+    reduced to 1/N, ceil(w / N) x ceil(h / N), what a decode with the same scale writes.  Returns int32 (B, 8).  No
+    context, no GPU."""
     region, extents = _stream_region(streams)
-    return _decode_call(None, None, region, PIX_U8X3 | _any_sampling_bit(any_sampling), jpeg_decode_table(extents, orient=orient), None, 0)
+    return _decode_call(None, None, region, PIX_U8X3 | _any_sampling_bit(any_sampling) | _scaled_bit(scale),
+                        jpeg_decode_table(extents, orient=orient, scale=scale), None, 0)
 
 
 def _any_sampling_bit(any_sampling):
@@ -648,9 +676,10 @@ def _check_jpeg_optimize(what, jpeg, jpeg_optimize):
         raise ValueError(what + ": jpeg_optimize=True goes with jpeg=Q; without it nothing is encoded")
 
 
-def _all_streams(frames, what, orient=False, any_sampling=False):
+def _all_streams(frames, what, orient=False, any_sampling=False, decode_scale=None, decode_max_size=None):
     """True if `frames` is a list of JPEG files (bytes), False if it holds none; a mixture is refused, and so are orient
-    with arrays, which carry no EXIF tag, and any_sampling with arrays, which have no sampling"""
+    with arrays, which carry no EXIF tag, any_sampling with arrays, which have no sampling, and decode_scale or
+    decode_max_size with arrays, which are not decoded (and the two together)"""
     n = sum(isinstance(f, (bytes, bytearray, memoryview)) for f in frames) if isinstance(frames, (list, tuple)) else 0
     if n and n != len(frames):
         raise ValueError(what + ": the list is all JPEG files (bytes) or all arrays")
@@ -658,6 +687,10 @@ def _all_streams(frames, what, orient=False, any_sampling=False):
         raise ValueError(what + ": orient=True goes with JPEG files (bytes); arrays carry no EXIF orientation")
     if any_sampling and not n:
         raise ValueError(what + ": any_sampling=True goes with JPEG files (bytes); arrays have no chroma sampling")
+    if decode_scale is not None and decode_max_size is not None:
+        raise ValueError(what + ": decode_scale and decode_max_size are two ways to say one thing; give one")
+    if (decode_scale is not None or decode_max_size is not None) and not n:
+        raise ValueError(what + ": decode_scale and decode_max_size go with JPEG files (bytes); arrays are not decoded")
     return n > 0
 
 
@@ -926,7 +959,8 @@ class Context:
                                                 fmt | WARP_LINES, C.cast(C.byref(args), C.c_void_p), C.c_void_p(d_dst),
                                                 dst_bytes, 0, 0, 0))
 
-    def draw_lines_batch(self, frames, lines_list, Hs=None, jpeg=None, orient=False, jpeg_optimize=False, any_sampling=False):
+    def draw_lines_batch(self, frames, lines_list, Hs=None, jpeg=None, orient=False, jpeg_optimize=False, any_sampling=False,
+                         decode_scale=None, decode_max_size=None):
         """The demo's lines picture for a list of 8-bit frames of different shapes (all gray H x W, or all H x W x 3) and
         their segments (one LINE_DTYPE array per frame; Hs: one 3x3 per frame, or None): one upload, one
         lr_draw_lines_device call, one download.  Returns the list of H x W x 3 uint8 pictures: a loop of draw_lines.
@@ -936,10 +970,17 @@ class Context:
         (LR_JPEG_OPTIMIZE): the same pixels in fewer bytes.
         orient=True (JPEG files only): the files' EXIF orientations are applied, the call on decode_jpeg_batch(files,
         orient=True)'s arrays.
-        any_sampling=True (JPEG files only, else ValueError): files of any sampling are decoded (decode_jpeg_batch)."""
+        any_sampling=True (JPEG files only, else ValueError): files of any sampling are decoded (decode_jpeg_batch).
+        decode_scale=N (JPEG files only, else ValueError; None, an int or one per file out of 1, 2, 4, 8): the files are
+        decoded at 1/N of their size (LR_JPEG_SCALED): the call on decode_jpeg_batch(files, scale=N)'s arrays, every later
+        stage working on 1/N^2 of the pixels.  decode_max_size=M instead (both: ValueError): per file the largest N whose
+        longer side ceil(max(w, h) / N) is still at least M (jpeg_scale_for, PIL's Image.draft rule).  Segments, transforms
+        and homographies that come back are in the DECODED picture's coordinates: multiply by N for the file's.  The segments
+        given here are drawn as they are, so they are in the decoded picture's coordinates too."""
         _check_jpeg_optimize("draw_lines_batch", jpeg, jpeg_optimize)
-        if _all_streams(frames, "draw_lines_batch", orient, any_sampling):
-            return self._draw_lines_streams([bytes(f) for f in frames], lines_list, Hs, jpeg, orient, jpeg_optimize, any_sampling)
+        if _all_streams(frames, "draw_lines_batch", orient, any_sampling, decode_scale, decode_max_size):
+            return self._draw_lines_streams([bytes(f) for f in frames], lines_list, Hs, jpeg, orient, jpeg_optimize, any_sampling, decode_scale,
+                                            decode_max_size)
         frames = [np.ascontiguousarray(f) for f in frames]
         if not frames or len(lines_list) != len(frames) or (Hs is not None and len(Hs) != len(frames)):
             raise ValueError("draw_lines_batch: as many line arrays (and Hs) as frames, at least one")
@@ -983,11 +1024,12 @@ class Context:
                 self.device_free(d_dst.value)
         return [out[off:off + w * h * 3].reshape(h, w, 3).copy() for (w, h), (off, _) in zip(sizes, outputs)]
 
-    def _draw_lines_streams(self, streams, lines_list, Hs, jpeg, orient=False, jpeg_optimize=False, any_sampling=False):
+    def _draw_lines_streams(self, streams, lines_list, Hs, jpeg, orient=False, jpeg_optimize=False, any_sampling=False, decode_scale=None,
+                            decode_max_size=None):
         """draw_lines_batch for JPEG files (bytes): decoded in HBM, drawn on where they lie"""
         if len(lines_list) != len(streams) or (Hs is not None and len(Hs) != len(streams)):
             raise ValueError("draw_lines_batch: as many line arrays (and Hs) as frames, at least one")
-        d_src, src_bytes, fmt, frames = self._decode_resident(streams, None, "draw_lines_batch", orient, any_sampling)
+        d_src, src_bytes, fmt, frames = self._decode_resident(streams, None, "draw_lines_batch", orient, any_sampling, decode_scale, decode_max_size)
         return self._draw_resident(d_src, src_bytes, fmt, frames, lines_list, Hs, jpeg, jpeg_optimize)
 
     def draw_lines(self, image_u8, lines, H=None):
@@ -1086,19 +1128,26 @@ class Context:
         interval, status, decodes of the most often decoded part, and 0 -- or, for a frame whose entry [7] is 1
         (jpeg_decode_table's orient), the EXIF orientation applied, 1 .. 8, width and height being the upright picture's.
         JPEG_ANY_SAMPLING or-ed into fmt admits every sampling with factors 1, 2 or 4 (jpeg_info); the layout column of
-        such a frame is its luminance's sampling byte.  d_dst None: probe mode."""
+        such a frame is its luminance's sampling byte.  JPEG_SCALED or-ed into fmt makes entry [6] of a frame's row its
+        scale denominator (jpeg_decode_table's scale): the picture is written at 1/2, 1/4 or 1/8 of its size, and width and
+        height are the reduced picture's.  d_dst None: probe mode."""
         return _decode_call(self._h, d_src, h_src, fmt, table, d_dst, dst_bytes)
 
-    def _decode_resident(self, streams, fmt, what, orient=False, any_sampling=False):
+    def _decode_resident(self, streams, fmt, what, orient=False, any_sampling=False, scale=None, max_size=None):
         """The JPEG files decoded into one fresh device buffer: one upload of the files, one lr_decode_jpeg_device call.
         fmt None: PIX_U8 if every file has one component, else PIX_U8X3.  Returns (d_dst, total_bytes, fmt, frames) with
         frames[b] = (width, height, byte_offset, row_bytes), every picture at a multiple of 4; the caller frees d_dst.
         orient: the files' EXIF orientations are applied, and the sizes are the upright pictures'.
         any_sampling: both calls carry JPEG_ANY_SAMPLING.
+        scale (None, an int or B ints out of 1, 2, 4, 8): both calls carry JPEG_SCALED, and the sizes are the reduced
+        pictures'.  max_size (instead of scale): the scales are jpeg_scale_for's choice from one more probe.
         Raises LibrectifyError naming the first frame whose status is not 0."""
         region, extents = _stream_region(streams)
-        orient, bit = bool(orient), _any_sampling_bit(any_sampling)
-        info = _decode_call(None, None, region, PIX_U8X3 | bit, jpeg_decode_table(extents, orient=orient), None, 0)
+        if max_size is not None:  # (a file that the probe refuses keeps scale 1 and is named below)
+            scale = jpeg_scale_for(_decode_call(None, None, region, PIX_U8X3 | _any_sampling_bit(any_sampling), jpeg_decode_table(extents), None, 0)[:, :2].tolist(),
+                                   max_size)
+        orient, bit = bool(orient), _any_sampling_bit(any_sampling) | _scaled_bit(scale)
+        info = _decode_call(None, None, region, PIX_U8X3 | bit, jpeg_decode_table(extents, orient=orient, scale=scale), None, 0)
         bad = np.flatnonzero(info[:, 5])
         if len(bad):
             jpeg_info([streams[bad[0]]], any_sampling=any_sampling)  # (once more alone: lr_last_error then tells why)
@@ -1111,7 +1160,7 @@ class Context:
             start = (end + 3) // 4 * 4
             frames.append((w, h, start, w * bpp))
             end = start + w * h * bpp
-        table = jpeg_decode_table(extents, np.array([f[2:] for f in frames], np.int64), np.array([f[:2] for f in frames], np.int64), orient)
+        table = jpeg_decode_table(extents, np.array([f[2:] for f in frames], np.int64), np.array([f[:2] for f in frames], np.int64), orient, scale)
         d_src = self.device_upload(region)
         d_dst = C.c_void_p()
         try:
@@ -1127,17 +1176,20 @@ class Context:
             if d_dst.value:
                 self.device_free(d_dst.value)
 
-    def decode_jpeg_batch(self, streams, fmt=PIX_U8X3, orient=False, any_sampling=False):
+    def decode_jpeg_batch(self, streams, fmt=PIX_U8X3, orient=False, any_sampling=False, scale=None):
         """A list of baseline JPEG files (bytes) of any sizes and samplings decoded on the GPU: one upload of the files, one
         lr_decode_jpeg_device call, one download.  fmt PIX_U8X3: H x W x 3 RGB pictures (a one-component file replicated);
         PIX_U8: H x W luminance.  orient=True: every file's EXIF orientation (tag 0x0112 of its first Exif segment) is
         applied in the decoder's output pass and the pictures come out upright, what PIL's ImageOps.exif_transpose makes of
         them; a file that tells none comes out as stored.  any_sampling=True (LR_JPEG_ANY_SAMPLING): files of 4:4:0, 4:1:1 and
-        every other sampling with factors 1, 2 or 4 (jpeg_info) are decoded too, not refused with status 2.  Returns a list of uint8 arrays.  Raises LibrectifyError naming the frame on a status
+        every other sampling with factors 1, 2 or 4 (jpeg_info) are decoded too, not refused with status 2.
+        scale (None, an int or B ints out of 1, 2, 4, 8; LR_JPEG_SCALED): file b comes out at 1/N of its size, ceil(w / N) x
+        ceil(h / N), averaged from the blocks' samples inside the decoder (within a few levels of the N x N box average of the
+        full decode); coordinates in it are the file's divided by N.  Returns a list of uint8 arrays.  Raises LibrectifyError naming the frame on a status
         other than 0 (jpeg_info tells the statuses beforehand)."""
         if fmt not in (PIX_U8, PIX_U8X3):
             raise ValueError("decode_jpeg_batch: fmt is PIX_U8 or PIX_U8X3")
-        d_dst, total, fmt, frames = self._decode_resident(streams, fmt, "decode_jpeg_batch", orient, any_sampling)
+        d_dst, total, fmt, frames = self._decode_resident(streams, fmt, "decode_jpeg_batch", orient, any_sampling, scale)
         try:
             out = self.device_download(d_dst, (total,), np.uint8)
         finally:
@@ -1145,16 +1197,17 @@ class Context:
         tail = (3,) if fmt == PIX_U8X3 else ()
         return [out[off:off + h * row].reshape((h, w) + tail).copy() for w, h, off, row in frames]
 
-    def decode_jpeg(self, data, fmt=PIX_U8X3, orient=False, any_sampling=False):
+    def decode_jpeg(self, data, fmt=PIX_U8X3, orient=False, any_sampling=False, scale=None):
         """One baseline JPEG file (bytes) decoded on the GPU: H x W x 3 RGB (PIX_U8X3) or H x W luminance (PIX_U8);
-        orient=True: upright, by the file's EXIF orientation; any_sampling=True: of any sampling (decode_jpeg_batch)."""
-        return self.decode_jpeg_batch([data], fmt, orient, any_sampling)[0]
+        orient=True: upright, by the file's EXIF orientation; any_sampling=True: of any sampling; scale=2, 4 or 8: at 1/N of
+        its size (decode_jpeg_batch)."""
+        return self.decode_jpeg_batch([data], fmt, orient, any_sampling, scale)[0]
 
     def _rectify_streams(self, streams, min_length, refine, cfg, clip, max_size, capacity, jpeg, orient=False, interp="linear", jpeg_optimize=False,
-                         any_sampling=False, border=None, crop=False):
+                         any_sampling=False, border=None, crop=False, decode_scale=None, decode_max_size=None):
         """rectify_batch for JPEG files: the files go up and are decoded in HBM, the pictures are handed to
         rectify_frames_device where they lie; with jpeg=Q no pixel crosses the link in either direction"""
-        d_src, _, fmt, sources = self._decode_resident(streams, None, "rectify_batch", orient, any_sampling)
+        d_src, _, fmt, sources = self._decode_resident(streams, None, "rectify_batch", orient, any_sampling, decode_scale, decode_max_size)
         return self._rectify_resident(d_src, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp, jpeg_optimize, border, crop)
 
     def prepare_device(self, d_src, src_image_bytes, batch, width, height, src_row_bytes, fmt, d_dst, dst_image_bytes,
@@ -1216,7 +1269,7 @@ class Context:
                     self.device_free(p.value)
 
     def rectify(self, image_u8, min_length=None, refine=False, cfg=None, clip=3.0, max_size=None, jpeg=None, orient=False,
-                interp="linear", jpeg_optimize=False, any_sampling=False, border=None, crop=False):
+                interp="linear", jpeg_optimize=False, any_sampling=False, border=None, crop=False, decode_scale=None, decode_max_size=None):
         """The reference demo's pipeline (autorectify.cpp) on an 8-bit frame (H x W gray or H x W x 3 RGB): luma
         (4899 R + 9617 G + 1868 B + 8192) >> 14, / 256, find_line_segment_groups with min_length max(w, h) / 100 by
         default, compute_rectification_transform (cfg: the demo's, horizontal_vp_min_distance = 2),
@@ -1234,6 +1287,11 @@ class Context:
         does: the call on decode_jpeg(file, orient=True).
         any_sampling=True (a JPEG file only): a file of any sampling is decoded (LR_JPEG_ANY_SAMPLING): the call on
         decode_jpeg(file, any_sampling=True).
+        decode_scale=N (a JPEG file only, else ValueError; None, an int or one per file out of 1, 2, 4, 8): the files are
+        decoded at 1/N of their size (LR_JPEG_SCALED): the call on decode_jpeg_batch(files, scale=N)'s arrays, every later
+        stage working on 1/N^2 of the pixels.  decode_max_size=M instead (both: ValueError): per file the largest N whose
+        longer side ceil(max(w, h) / N) is still at least M (jpeg_scale_for, PIL's Image.draft rule).  Segments, transforms
+        and homographies that come back are in the DECODED picture's coordinates: multiply by N for the file's.
         interp="cubic": the warp samples 4 x 4 bicubic (WARP_CUBIC) instead of bilinear, on every path above; lines,
         transform, homography and size are those of interp="linear", only the picture (or its JPEG file) differs.
         border: None (the zero border: the demo's black wedges) or border_word's spec -- "replicate", "reflect", "reflect101",
@@ -1244,7 +1302,8 @@ class Context:
         cubic = _sampling_bit(interp, "rectify")
         _check_jpeg_optimize("rectify", jpeg, jpeg_optimize)
         if isinstance(image_u8, (bytes, bytearray, memoryview)):  # a JPEG file: decoded in HBM, rectify_batch's path for one frame
-            res = self.rectify_batch([bytes(image_u8)], min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, jpeg=jpeg, orient=orient, interp=interp, jpeg_optimize=jpeg_optimize, any_sampling=any_sampling, border=border, crop=crop)[0]
+            res = self.rectify_batch([bytes(image_u8)], min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, jpeg=jpeg, orient=orient, interp=interp, jpeg_optimize=jpeg_optimize, any_sampling=any_sampling, border=border, crop=crop,
+                                     decode_scale=decode_scale, decode_max_size=decode_max_size)[0]
             if res[2] is None:
                 _rectified_map(res[1], clip, crop, cubic)  # (raises what rectify raises for such a frame)
             return res
@@ -1252,6 +1311,8 @@ class Context:
             raise ValueError("rectify: orient=True goes with a JPEG file (bytes); an array carries no EXIF orientation")
         if any_sampling:
             raise ValueError("rectify: any_sampling=True goes with a JPEG file (bytes); an array has no chroma sampling")
+        if decode_scale is not None or decode_max_size is not None:
+            raise ValueError("rectify: decode_scale and decode_max_size go with a JPEG file (bytes); an array is not decoded")
         img = np.ascontiguousarray(image_u8)
         if img.dtype != np.uint8 or not (img.ndim == 2 or (img.ndim == 3 and img.shape[2] == 3)):
             raise ValueError("rectify: an H x W or H x W x 3 uint8 frame")
@@ -1561,7 +1622,8 @@ class Context:
         return res
 
     def rectify_batch(self, frames_u8, min_length=None, refine=False, cfg=None, clip=3.0, max_size=None, capacity=4096, jpeg=None,
-                      orient=False, interp="linear", jpeg_optimize=False, any_sampling=False, border=None, crop=False):
+                      orient=False, interp="linear", jpeg_optimize=False, any_sampling=False, border=None, crop=False, decode_scale=None,
+                      decode_max_size=None):
         """Context.rectify for a batch: frames_u8 is a uint8 array [B, H, W] or [B, H, W, 3], or a list of such frames of one
         shape.  One upload, rectify_batch_device (one detector batch, the packed warp), one download.  Returns a
         list of (lines, transform, warped), frame by frame what rectify returns for it; warped is None for a frame whose
@@ -1584,6 +1646,11 @@ class Context:
         4:4:0 (a losslessly rotated 4:2:2 photograph), 4:1:1 and every other sampling with factors 1, 2 or 4 are decoded --
         bit for bit the call on decode_jpeg_batch(files, any_sampling=True)'s arrays.  Without it the first such file raises
         LibrectifyError (status 2) for the whole batch.
+        decode_scale=N (JPEG files only, else ValueError; None, an int or one per file out of 1, 2, 4, 8): the files are
+        decoded at 1/N of their size (LR_JPEG_SCALED): the call on decode_jpeg_batch(files, scale=N)'s arrays, every later
+        stage working on 1/N^2 of the pixels.  decode_max_size=M instead (both: ValueError): per file the largest N whose
+        longer side ceil(max(w, h) / N) is still at least M (jpeg_scale_for, PIL's Image.draft rule).  Segments, transforms
+        and homographies that come back are in the DECODED picture's coordinates: multiply by N for the file's.
         interp="cubic": the warp launch of whichever path is taken samples 4 x 4 bicubic (WARP_CUBIC); detector, transforms,
         sizes and the encoder are untouched -- frame by frame what rectify(interp="cubic") returns.
         border: None, one border_word spec for all frames or a list of one per frame (WARP_BORDER on the warp launch of
@@ -1591,13 +1658,13 @@ class Context:
         entry, the rectangle (x0, y0, width, height) -- frame by frame what rectify(border=, crop=) returns."""
         _sampling_bit(interp, "rectify_batch")
         _check_jpeg_optimize("rectify_batch", jpeg, jpeg_optimize)
-        if _all_streams(frames_u8, "rectify_batch", orient, any_sampling):
+        if _all_streams(frames_u8, "rectify_batch", orient, any_sampling, decode_scale, decode_max_size):
             try:  # (the files' format is known once they are decoded: a spec that suits neither 8-bit format fails here)
                 _border_words(border, len(frames_u8), PIX_U8X3, "rectify_batch")
             except ValueError:
                 _border_words(border, len(frames_u8), PIX_U8, "rectify_batch")
             return self._rectify_streams([bytes(f) for f in frames_u8], min_length, refine, cfg, clip, max_size, capacity, jpeg, orient, interp, jpeg_optimize,
-                                         any_sampling, border, crop)
+                                         any_sampling, border, crop, decode_scale, decode_max_size)
         if not isinstance(frames_u8, np.ndarray):
             frames_u8 = [np.asarray(f) for f in frames_u8]
             if len({f.shape for f in frames_u8}) > 1:

@@ -36,6 +36,15 @@
 // replication for 4.  Those are the kAny instantiations of the kernels, which a call gets only if it has the bit and one of
 // its frames needs them: every other call launches the kernels it always did (docs/jpeg_decode_bounds.md has the stores).
 //
+// LR_JPEG_SCALED (or-ed into the call's format): entry [6] of a frame's row is its scale denominator N, 1, 2, 4 or 8, and the
+// picture is written at ceil(w / N) x ceil(h / N) (tests/numpy_jpeg_scale_ref.py restates it).  Steps 1 to 4 are the same at
+// every scale.  Per component and axis, with rho the ratio of the largest factor to the component's, d = min(N, rho) of the
+// scale is taken from the upsampling and r = N / d from the blocks: step 5 averages the block's 64 samples over cells of
+// rx x ry (the rounded mean) and stores the (8 / rx) x (8 / ry) reduced samples densely in the slot's first bytes; step 6 runs
+// over the reduced picture, a reduced block's sides being shifts, the upsampling that is left rho / d, the clamps the reduced
+// grid's.  Those are the kScaled instantiations of the two kernels (on the general geometry, of which the three layouts are
+// special cases), which a call gets only if it has the bit and a live frame with N > 1.
+//
 // Every loop on the device is bounded by the part's bits, the stream's length or the frame's block count; every read of the
 // stream is clamped to [offset, offset + length), every coefficient store to the frame's blocks, every pixel store to the
 // frame's size.  All device writes are ordinary C++ stores (and LDS).
@@ -87,6 +96,13 @@ struct JdFrame {
     uint8_t hsh[4], vsh[4];          // log2 h_i, log2 v_i
     uint8_t rxs[4], rys[4];          // log2 (Hmax / h_i), log2 (Vmax / v_i): 0 the sample, 1 the triangle, 2 replication
     int cw[4], ch[4];
+    // The reduced geometry (LR_JPEG_SCALED, scale denominator N), filled for every frame and read by the kScaled
+    // instantiations alone.  Per component and axis, with rho the ratio above: d = min(N, rho), the blocks are reduced by
+    // r = N / d and the upsampling that is left is rho / d.  N = 1 gives sides of 8, the ratios and the sizes above.
+    int sw, sh;                      // the reduced picture: ceil(w / N) x ceil(h / N)
+    uint8_t sbx[4], sby[4];          // log2 of a reduced block's sides, 3 - log2 r: 0..3
+    uint8_t srx[4], sry[4];          // log2 (rho / d): 0 the sample, 1 the triangle, 2 replication
+    int scw[4], sch[4];              // the component's reduced grid: ceil(cw / rx) x ceil(ch / ry)
 };
 static_assert(sizeof(JdFrame) % 8 == 0, "rows of the mirror block stay 8-byte aligned");
 
@@ -484,7 +500,24 @@ __device__ __forceinline__ void idct8(const int (&s)[8], int (&out)[8]) {
     }
 }
 
-template <bool kAny>
+// v[i] becomes the sum of cell i of 1 << l neighbours (l = 0..3); the entries from 8 >> l on are left over
+__device__ __forceinline__ void sum_cells(int (&v)[8], int l) {
+    if (l >= 1) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = v[2 * i] + v[2 * i + 1];
+    }
+    if (l >= 2) {
+        v[0] = v[0] + v[1];
+        v[1] = v[2] + v[3];
+    }
+    if (l >= 3) v[0] = v[0] + v[1];
+}
+
+// kScaled (with kAny: the general geometry throughout): the call has LR_JPEG_SCALED and a frame of scale 2, 4 or 8.  The
+// block's 64 samples are then averaged over cells of rx x ry, the reductions of the block's component -- down a column in
+// the registers of the lane that holds it, across a row behind the transpose -- and the (8 / rx) x (8 / ry) reduced samples
+// stored densely, row by row, in the slot's first bytes (a frame of scale 1: all 64, as ever).
+template <bool kAny, bool kScaled>
 __global__ __launch_bounds__(kWave) void jd_transform_kernel(int batch, int n_groups, int luma_only, const JdFrame* __restrict__ frames,
                                                              const int* __restrict__ grp_start, int16_t* __restrict__ coef) {
     __shared__ int s_t[8][65];
@@ -515,10 +548,40 @@ __global__ __launch_bounds__(kWave) void jd_transform_kernel(int batch, int n_gr
         for (int v = 0; v < 8; ++v) s[v] = s_t[k][v * 8 + r];  // column r
         idct8(s, a);
         __syncthreads();
+        const int lx = kScaled ? 3 - f->sbx[comp] : 0, ly = kScaled ? 3 - f->sby[comp] : 0;  // log2 of the component's cells
+        if (kScaled) {  // column r is in registers: its cells' sums, ry samples each, go to LDS in the samples' place
+            int v[8];
 #pragma unroll
-        for (int y = 0; y < 8; ++y) s_t[k][y * 8 + r] = min(max(((a[y] + (1 << (kEndShift - 1))) >> kEndShift) + 128, 0), 255);
+            for (int y = 0; y < 8; ++y) v[y] = min(max(((a[y] + (1 << (kEndShift - 1))) >> kEndShift) + 128, 0), 255);
+            sum_cells(v, ly);
+#pragma unroll
+            for (int y = 0; y < 8; ++y) s_t[k][y * 8 + r] = v[y];  // (rows from 8 >> ly on are not read)
+        } else {
+#pragma unroll
+            for (int y = 0; y < 8; ++y) s_t[k][y * 8 + r] = min(max(((a[y] + (1 << (kEndShift - 1))) >> kEndShift) + 128, 0), 255);
+        }
         __syncthreads();
-        if (valid) {  // row r of the samples, into the block's first 64 bytes (all of which were read above)
+        if (kScaled) {
+            if (valid && r < (8 >> ly)) {  // row r of the reduced samples: the cells' sums across, the rounded means, 8 >> lx bytes
+                int w[8];
+#pragma unroll
+                for (int x = 0; x < 8; ++x) w[x] = s_t[k][r * 8 + x];
+                sum_cells(w, lx);
+                const int shift = lx + ly, half = (1 << shift) >> 1;
+                uint32_t lo = 0, hi = 0;
+#pragma unroll
+                for (int x = 0; x < 4; ++x) {  // (entries from 8 >> lx on are no means; they lie above the bytes that are stored)
+                    lo |= (uint32_t)(((w[x] + half) >> shift) & 255) << (8 * x);
+                    hi |= (uint32_t)(((w[4 + x] + half) >> shift) & 255) << (8 * x);
+                }
+                // rows are dense, (8 >> lx) bytes each: row r < 8 >> ly ends at or below byte 64 of the slot, all of which was read above
+                uint8_t* out = reinterpret_cast<uint8_t*>(slot) + (r << (3 - lx));
+                if (lx == 0) *reinterpret_cast<uint2*>(out) = make_uint2(lo, hi);
+                else if (lx == 1) *reinterpret_cast<uint32_t*>(out) = lo;
+                else if (lx == 2) *reinterpret_cast<uint16_t*>(out) = (uint16_t)lo;
+                else *out = (uint8_t)lo;
+            }
+        } else if (valid) {  // row r of the samples, into the block's first 64 bytes (all of which were read above)
             uint32_t lo = 0, hi = 0;
 #pragma unroll
             for (int x = 0; x < 4; ++x) {
@@ -535,32 +598,36 @@ __global__ __launch_bounds__(kWave) void jd_transform_kernel(int batch, int n_gr
 
 // sample (x, y) of component comp, in its own grid.  kAny: the MCU is the block's column and row shifted by the component's
 // factors, the block in it row (by mod v) and column (bx mod h) of the component's v x h blocks
-template <bool kAny>
+// kScaled: (x, y) in the component's reduced grid, a block's reduced samples being (1 << sby) rows of (1 << sbx)
+template <bool kAny, bool kScaled = false>
 __device__ __forceinline__ int sample_at(const uint8_t* __restrict__ blocks, const JdFrame* f, int comp, int x, int y) {
-    const int bx = x >> 3, by = y >> 3;
+    const int sx = kScaled ? f->sbx[comp] : 3, sy = kScaled ? f->sby[comp] : 3;
+    const int bx = x >> sx, by = y >> sy;
     size_t blk;
     if (kAny) {
         const int hsh = f->hsh[comp], vsh = f->vsh[comp];
         blk = ((size_t)(by >> vsh) * f->mcus_x + (bx >> hsh)) * f->bpm + f->first[comp] + ((by & ((1 << vsh) - 1)) << hsh) + (bx & ((1 << hsh) - 1));
     } else if (comp == 0) blk = ((size_t)(by / f->vs) * f->mcus_x + bx / f->hs) * f->bpm + (by % f->vs) * f->hs + bx % f->hs;
     else blk = ((size_t)by * f->mcus_x + bx) * f->bpm + f->hs * f->vs + comp - 1;
-    return (int)blocks[blk * 128 + (y & 7) * 8 + (x & 7)];
+    return (int)blocks[blk * 128 + ((y & ((1 << sy) - 1)) << sx) + (x & ((1 << sx) - 1))];
 }
 
 // the chrominance at pixel (x, y): centred triangle filters, the edges replicated at the component's own size
 // kAny, per axis by the ratio of the largest factor to the component's: 1 the sample, 2 the triangle, 4 the sample x >> 2
 // (near and far are then one sample, and the triangle over the other axis is taken over the replicated samples)
-template <bool kAny>
+// kScaled: (x, y) a pixel of the reduced picture, the ratios those that the reduction leaves, the clamps the reduced grid's
+template <bool kAny, bool kScaled = false>
 __device__ __forceinline__ int chroma_at(const uint8_t* __restrict__ blocks, const JdFrame* f, int comp, int x, int y) {
     if (kAny) {
-        const int rxs = f->rxs[comp], rys = f->rys[comp];
+        const int rxs = kScaled ? f->srx[comp] : f->rxs[comp], rys = kScaled ? f->sry[comp] : f->rys[comp];
+        const int cw = kScaled ? f->scw[comp] : f->cw[comp], ch = kScaled ? f->sch[comp] : f->ch[comp];
         const int nx = x >> rxs, ny = y >> rys;
-        if (rxs != 1 && rys != 1) return sample_at<true>(blocks, f, comp, nx, ny);
-        const int fx = min(max(nx + ((x & 1) ? 1 : -1), 0), f->cw[comp] - 1), fy = min(max(ny + ((y & 1) ? 1 : -1), 0), f->ch[comp] - 1);
-        if (rys != 1) return (3 * sample_at<true>(blocks, f, comp, nx, ny) + sample_at<true>(blocks, f, comp, fx, ny) + 2) >> 2;
-        if (rxs != 1) return (3 * sample_at<true>(blocks, f, comp, nx, ny) + sample_at<true>(blocks, f, comp, nx, fy) + 2) >> 2;
-        return (9 * sample_at<true>(blocks, f, comp, nx, ny) + 3 * sample_at<true>(blocks, f, comp, fx, ny) +
-                3 * sample_at<true>(blocks, f, comp, nx, fy) + sample_at<true>(blocks, f, comp, fx, fy) + 8) >> 4;
+        if (rxs != 1 && rys != 1) return sample_at<true, kScaled>(blocks, f, comp, nx, ny);
+        const int fx = min(max(nx + ((x & 1) ? 1 : -1), 0), cw - 1), fy = min(max(ny + ((y & 1) ? 1 : -1), 0), ch - 1);
+        if (rys != 1) return (3 * sample_at<true, kScaled>(blocks, f, comp, nx, ny) + sample_at<true, kScaled>(blocks, f, comp, fx, ny) + 2) >> 2;
+        if (rxs != 1) return (3 * sample_at<true, kScaled>(blocks, f, comp, nx, ny) + sample_at<true, kScaled>(blocks, f, comp, nx, fy) + 2) >> 2;
+        return (9 * sample_at<true, kScaled>(blocks, f, comp, nx, ny) + 3 * sample_at<true, kScaled>(blocks, f, comp, fx, ny) +
+                3 * sample_at<true, kScaled>(blocks, f, comp, nx, fy) + sample_at<true, kScaled>(blocks, f, comp, fx, fy) + 8) >> 4;
     }
     if (f->hs == 1) return sample_at<false>(blocks, f, comp, x, y);
     const int cw = (f->w + 1) >> 1;
@@ -573,24 +640,31 @@ __device__ __forceinline__ int chroma_at(const uint8_t* __restrict__ blocks, con
 }
 
 // pixel (x, y) of the stored picture: its luminance (kFormat LR_PIX_U8: all that is computed) and its three colour bytes
-template <int kFormat, bool kAny>
+template <int kFormat, bool kAny, bool kScaled>
 __device__ __forceinline__ void pixel_at(const uint8_t* __restrict__ blocks, const JdFrame* f, int x, int y, int (&c)[3]) {
-    const int yy = sample_at<kAny>(blocks, f, 0, x, y);
+    const int yy = sample_at<kAny, kScaled>(blocks, f, 0, x, y);
     c[0] = c[1] = c[2] = yy;
     if (kFormat == LR_PIX_U8X3 && f->comps == 3) {  // the IJG fixed-point inverse of the encoder's rule
-        const int cb = chroma_at<kAny>(blocks, f, 1, x, y) - 128, cr = chroma_at<kAny>(blocks, f, 2, x, y) - 128;
+        const int cb = chroma_at<kAny, kScaled>(blocks, f, 1, x, y) - 128, cr = chroma_at<kAny, kScaled>(blocks, f, 2, x, y) - 128;
         c[0] = min(max(yy + ((91881 * cr + 32768) >> 16), 0), 255);
         c[1] = min(max(yy + ((-22554 * cb - 46802 * cr + 32768) >> 16), 0), 255);
         c[2] = min(max(yy + ((116130 * cb + 32768) >> 16), 0), 255);
     }
 }
 
+// the stored picture's size: kScaled the reduced one
+template <bool kScaled>
+__device__ __forceinline__ int pic_w(const JdFrame* f) { return kScaled ? f->sw : f->w; }
+template <bool kScaled>
+__device__ __forceinline__ int pic_h(const JdFrame* f) { return kScaled ? f->sh : f->h; }
+
 // The EXIF orientations, S the stored w x h picture and O the one written:
 //   2: O[y][x] = S[y][w-1-x]    3: S[h-1-y][w-1-x]    4: S[h-1-y][x]                 (O is w x h)
 //   5: O[y][x] = S[x][y]        6: S[h-1-x][y]        7: S[h-1-x][w-1-y]    8: S[x][w-1-y]    (O is h x w)
 // kTurn: the batch has a frame of orientation 5..8.  A batch without one -- every call that does not ask for orientations
 // among them -- gets the kernel without the transposing path, its LDS and its registers.
-template <int kFormat, bool kTurn, bool kAny>
+// kScaled (with kAny): the stored picture is the reduced one, sw x sh, and its tiles are counted over that.
+template <int kFormat, bool kTurn, bool kAny, bool kScaled>
 __global__ __launch_bounds__(kTileW * kTileH) void jd_output_kernel(int batch, int n_tiles, const JdFrame* __restrict__ frames,
                                                                     const int* __restrict__ tile_start, const int* __restrict__ grp_start,
                                                                     const int16_t* __restrict__ coef, uint8_t* __restrict__ dst) {
@@ -608,11 +682,11 @@ __global__ __launch_bounds__(kTileW * kTileH) void jd_output_kernel(int batch, i
         const int tx = (int)threadIdx.x % kTileW, ty = (int)threadIdx.x / kTileW;
         int c[3];
         if (!kTurn || o < 5) {  // rows stay rows: a thread per pixel, its place mirrored
-            const int tiles_x = (f->w + kTileW - 1) / kTileW;
+            const int tiles_x = (pic_w<kScaled>(f) + kTileW - 1) / kTileW;
             const int x = (local % tiles_x) * kTileW + tx, y = (local / tiles_x) * kTileH + ty;
-            if (x >= f->w || y >= f->h) continue;
-            pixel_at<kFormat, kAny>(blocks, f, x, y, c);
-            const int ox = (o == 2 || o == 3) ? f->w - 1 - x : x, oy = (o == 3 || o == 4) ? f->h - 1 - y : y;
+            if (x >= pic_w<kScaled>(f) || y >= pic_h<kScaled>(f)) continue;
+            pixel_at<kFormat, kAny, kScaled>(blocks, f, x, y, c);
+            const int ox = (o == 2 || o == 3) ? pic_w<kScaled>(f) - 1 - x : x, oy = (o == 3 || o == 4) ? pic_h<kScaled>(f) - 1 - y : y;
             uint8_t* px = dst + (size_t)f->dst_off + (size_t)oy * (size_t)f->dst_row + (size_t)ox * kBpp;
 #pragma unroll
             for (int i = 0; i < kBpp; ++i) px[i] = (uint8_t)c[i];
@@ -620,13 +694,13 @@ __global__ __launch_bounds__(kTileW * kTileH) void jd_output_kernel(int batch, i
         }
         if (!kTurn) continue;  // (not reached: the code below is left out of that kernel)
         // rows become columns (the branch is the workgroup's: every lane reaches both barriers)
-        const int tiles_x = (f->w + kSquare - 1) / kSquare;
+        const int tiles_x = (pic_w<kScaled>(f) + kSquare - 1) / kSquare;
         const int x0 = (local % tiles_x) * kSquare, y0 = (local / tiles_x) * kSquare;
 #pragma unroll
         for (int pass = 0; pass < kSquare / kTileH; ++pass) {
             const int j = ty + pass * kTileH;
-            if (x0 + tx < f->w && y0 + j < f->h) {
-                pixel_at<kFormat, kAny>(blocks, f, x0 + tx, y0 + j, c);
+            if (x0 + tx < pic_w<kScaled>(f) && y0 + j < pic_h<kScaled>(f)) {
+                pixel_at<kFormat, kAny, kScaled>(blocks, f, x0 + tx, y0 + j, c);
 #pragma unroll
                 for (int i = 0; i < kBpp; ++i) s_sq[tx * kPitch + j * kBpp + i] = (uint8_t)c[i];
             }
@@ -639,8 +713,8 @@ __global__ __launch_bounds__(kTileW * kTileH) void jd_output_kernel(int batch, i
             const int at = (int)threadIdx.x + pass * (kTileW * kTileH);
             const int i = at / (kSquare * kBpp), k = at % (kSquare * kBpp), ch = k % kBpp;
             const int j = flip_x ? kSquare - 1 - k / kBpp : k / kBpp;
-            if (x0 + i < f->w && y0 + j < f->h) {
-                const int ox = flip_x ? f->h - 1 - (y0 + j) : y0 + j, oy = flip_y ? f->w - 1 - (x0 + i) : x0 + i;
+            if (x0 + i < pic_w<kScaled>(f) && y0 + j < pic_h<kScaled>(f)) {
+                const int ox = flip_x ? pic_h<kScaled>(f) - 1 - (y0 + j) : y0 + j, oy = flip_y ? pic_w<kScaled>(f) - 1 - (x0 + i) : x0 + i;
                 dst[(size_t)f->dst_off + (size_t)oy * (size_t)f->dst_row + (size_t)ox * kBpp + ch] = s_sq[i * kPitch + j * kBpp + ch];
             }
         }
@@ -833,7 +907,8 @@ void read_header(const uint8_t* d, size_t n, bool any, Header& hd) {
 int ctx_decode_jpeg(lr_context* c, const void* d_src, const void* h_src, size_t src_bytes, int format, const double* T, int batch,
                     void* d_dst, size_t dst_bytes, int32_t* info) {
     const bool any_sampling = (format & LR_JPEG_ANY_SAMPLING) != 0;
-    format &= ~LR_JPEG_ANY_SAMPLING;
+    const bool scaled = (format & LR_JPEG_SCALED) != 0;
+    format &= ~(LR_JPEG_ANY_SAMPLING | LR_JPEG_SCALED);
     auto fail = [](const std::string& what) {
         set_error("lr_decode_jpeg_device: " + what);
         return 1;
@@ -856,6 +931,7 @@ int ctx_decode_jpeg(lr_context* c, const void* d_src, const void* h_src, size_t 
     struct Entry {
         uint64_t off, len, dst_off, dst_row, w, h;
         bool orient;
+        int scale;  // the scale denominator: 1, 2, 4 or 8
     };
     std::vector<Entry> en((size_t)batch);
     std::vector<std::pair<uint64_t, uint64_t>> extent;
@@ -871,7 +947,10 @@ int ctx_decode_jpeg(lr_context* c, const void* d_src, const void* h_src, size_t 
         if ((e.w == 0) != (e.h == 0)) return fail_at(b, 4, "(width) and [5] (height): one is 0 and the other is not");
         if (!table_integer(t[3], e.w ? (double)(e.w * bpp) : 0.0, kExact, &e.dst_row))
             return fail_at(b, 3, "(row stride) is not an integer from a row's bytes to 2^53");
-        if (!(t[6] == 0.0)) return fail_at(b, 6, "is reserved and must be 0");
+        if (!scaled && !(t[6] == 0.0)) return fail_at(b, 6, "is reserved and must be 0");
+        if (!(t[6] == 0.0 || t[6] == 1.0 || t[6] == 2.0 || t[6] == 4.0 || t[6] == 8.0))
+            return fail_at(b, 6, "(scale denominator) is 0 or 1 (as stored), 2, 4 or 8");
+        e.scale = t[6] == 0.0 ? 1 : (int)t[6];
         if (!(t[7] == 0.0 || t[7] == 1.0)) return fail_at(b, 7, "(EXIF orientation) is 0 (as stored) or 1 (applied)");
         e.orient = t[7] == 1.0;
         uint64_t end;
@@ -902,6 +981,7 @@ int ctx_decode_jpeg(lr_context* c, const void* d_src, const void* h_src, size_t 
     int64_t n_groups = 0, n_wg = 0, n_tiles = 0;
     int most_wg = 0;
     bool general = false;  // a frame that needs the kAny instantiations
+    bool reduced = false;  // a frame of scale 2, 4 or 8: the kScaled instantiations
     Header hd;
     for (int b = 0; b < batch; ++b) {
         const Entry& e = en[(size_t)b];
@@ -909,10 +989,12 @@ int ctx_decode_jpeg(lr_context* c, const void* d_src, const void* h_src, size_t 
         read_header(static_cast<const uint8_t*>(h_src) + e.off, (size_t)e.len, any_sampling, hd);
         // the picture as written: with entry [7] the orientation the file tells (1 if none), and its size swapped for 5..8
         const int orient = e.orient ? std::max(hd.orientation, 1) : 0;
-        const int out_w = orient >= 5 ? hd.h : hd.w, out_h = orient >= 5 ? hd.w : hd.h;
+        // (and with LR_JPEG_SCALED the reduced one, reduced before it is turned)
+        const int sw = lr_jpeg_scaled_size(hd.w, e.scale), sh = lr_jpeg_scaled_size(hd.h, e.scale);
+        const int out_w = orient >= 5 ? sh : sw, out_h = orient >= 5 ? sw : sh;
         if (hd.status == kOk && e.w && ((uint64_t)out_w != e.w || (uint64_t)out_h != e.h)) {
             hd.status = kSizeMismatch;
-            hd.message = "the stream is " + std::to_string(out_w) + " x " + std::to_string(out_h) + (orient >= 5 ? " (turned by its orientation)" : "");
+            hd.message = "the stream is " + std::to_string(out_w) + " x " + std::to_string(out_h) + (e.scale > 1 ? " at 1/" + std::to_string(e.scale) : std::string()) + (orient >= 5 ? " (turned by its orientation)" : "");
         }
         int32_t* row = rows.data() + (size_t)b * 8;
         row[0] = out_w;
@@ -954,7 +1036,19 @@ int ctx_decode_jpeg(lr_context* c, const void* d_src, const void* h_src, size_t 
             f.rys[i] = (uint8_t)log2_of(f.vs / hd.vf[i]);
             f.cw[i] = (f.w * hd.hf[i] + f.hs - 1) / f.hs;  // ceil(w h_i / Hmax)
             f.ch[i] = (f.h * hd.vf[i] + f.vs - 1) / f.vs;
+            // of the scale's log2 an axis' ratio takes what it can (the chrominance is then simply upsampled less); the
+            // rest, log2 r, is the reduction of the component's blocks
+            const int n = e.scale == 8 ? 3 : log2_of(e.scale), rx = n - std::min(n, (int)f.rxs[i]), ry = n - std::min(n, (int)f.rys[i]);
+            f.sbx[i] = (uint8_t)(3 - rx);
+            f.sby[i] = (uint8_t)(3 - ry);
+            f.srx[i] = (uint8_t)(f.rxs[i] - (n - rx));
+            f.sry[i] = (uint8_t)(f.rys[i] - (n - ry));
+            f.scw[i] = (f.cw[i] + (1 << rx) - 1) >> rx;
+            f.sch[i] = (f.ch[i] + (1 << ry) - 1) >> ry;
         }
+        f.sw = sw;
+        f.sh = sh;
+        reduced = reduced || e.scale > 1;
         f.mcus_x = (f.w + 8 * f.hs - 1) / (8 * f.hs);
         f.n_mcus = f.mcus_x * ((f.h + 8 * f.vs - 1) / (8 * f.vs));  // (at most 2^26 of at most 10 blocks)
         general = general || hd.general;
@@ -970,7 +1064,7 @@ int ctx_decode_jpeg(lr_context* c, const void* d_src, const void* h_src, size_t 
         n_groups += ((int64_t)f.n_mcus * f.bpm + 7) / 8;
         n_wg += wgs;
         const int tile_w = orient >= 5 ? kSquare : kTileW, tile_h = orient >= 5 ? kSquare : kTileH;
-        n_tiles += (int64_t)((f.w + tile_w - 1) / tile_w) * ((f.h + tile_h - 1) / tile_h);
+        n_tiles += (int64_t)((f.sw + tile_w - 1) / tile_w) * ((f.sh + tile_h - 1) / tile_h);  // (sw x sh is w x h at scale 1)
         most_wg = std::max(most_wg, wgs);
         if (n_groups > 0x0FFFFFF0ll || n_wg > 0x007FFFF0ll || n_tiles > 0x7FFFFFF0ll)
             return fail_at(b, 1, "(stream length): the frames are larger than 2^31 blocks, parts or tiles in total");
@@ -1040,16 +1134,21 @@ int ctx_decode_jpeg(lr_context* c, const void* d_src, const void* h_src, size_t 
                        (int)n_wg, d_frames, d_wg, d_grp, js.state.get(), js.part.get(), js.coef.get(), d_damaged);
     hipLaunchKernelGGL(general ? jd_dc_kernel<true> : jd_dc_kernel<false>, dim3(live), dim3(kScanBlock), 0, c->stream, d_frames, d_grp, js.coef.get());
     const int grid_t = (int)std::min<int64_t>(n_groups, 1 << 18);
-    hipLaunchKernelGGL(general ? jd_transform_kernel<true> : jd_transform_kernel<false>, dim3(grid_t), dim3(kWave), 0, c->stream, live,
+    auto transform = general ? jd_transform_kernel<true, false> : jd_transform_kernel<false, false>;
+    if (reduced) transform = jd_transform_kernel<true, true>;
+    hipLaunchKernelGGL(transform, dim3(grid_t), dim3(kWave), 0, c->stream, live,
                        (int)n_groups, format == LR_PIX_U8 ? 1 : 0, d_frames, d_grp, js.coef.get());
     const int grid_o = (int)((std::min<int64_t>(n_tiles, 1 << 18) + 7) / 8 * 8);
     bool turn = false;
     for (const JdFrame& f : fr) turn = turn || f.orient >= 5;
-    auto output = format == LR_PIX_U8 ? (turn ? jd_output_kernel<LR_PIX_U8, true, false> : jd_output_kernel<LR_PIX_U8, false, false>)
-                                      : (turn ? jd_output_kernel<LR_PIX_U8X3, true, false> : jd_output_kernel<LR_PIX_U8X3, false, false>);
+    auto output = format == LR_PIX_U8 ? (turn ? jd_output_kernel<LR_PIX_U8, true, false, false> : jd_output_kernel<LR_PIX_U8, false, false, false>)
+                                      : (turn ? jd_output_kernel<LR_PIX_U8X3, true, false, false> : jd_output_kernel<LR_PIX_U8X3, false, false, false>);
     if (general)
-        output = format == LR_PIX_U8 ? (turn ? jd_output_kernel<LR_PIX_U8, true, true> : jd_output_kernel<LR_PIX_U8, false, true>)
-                                     : (turn ? jd_output_kernel<LR_PIX_U8X3, true, true> : jd_output_kernel<LR_PIX_U8X3, false, true>);
+        output = format == LR_PIX_U8 ? (turn ? jd_output_kernel<LR_PIX_U8, true, true, false> : jd_output_kernel<LR_PIX_U8, false, true, false>)
+                                     : (turn ? jd_output_kernel<LR_PIX_U8X3, true, true, false> : jd_output_kernel<LR_PIX_U8X3, false, true, false>);
+    if (reduced)  // (the general geometry throughout: the three layouts are special cases of it)
+        output = format == LR_PIX_U8 ? (turn ? jd_output_kernel<LR_PIX_U8, true, true, true> : jd_output_kernel<LR_PIX_U8, false, true, true>)
+                                     : (turn ? jd_output_kernel<LR_PIX_U8X3, true, true, true> : jd_output_kernel<LR_PIX_U8X3, false, true, true>);
     hipLaunchKernelGGL(output, dim3(grid_o), dim3(kTileW * kTileH), 0, c->stream, live, (int)n_tiles, d_frames, d_tile, d_grp, js.coef.get(), d8);
     LR_HIP(hipGetLastError());
     LR_HIP(hipMemcpyAsync(m + o_flags, d + o_flags, need - o_flags, hipMemcpyDeviceToHost, c->stream));

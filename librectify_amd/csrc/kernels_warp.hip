@@ -355,14 +355,15 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
         format &= ~LR_WARP_BORDER;
     }
     if (format & LR_WARP_JPEG_DECODE) {  // lr_decode_jpeg_device (kernels_jpeg_decode.hip): its own arguments arrive behind M
-        // (LR_JPEG_ANY_SAMPLING is the decoder's own option and travels on with the format)
-        if ((format & ~(0xFF | LR_JPEG_ANY_SAMPLING)) != LR_WARP_JPEG_DECODE) return fail("LR_WARP_JPEG_DECODE together with another option bit");
+        // (LR_JPEG_ANY_SAMPLING and LR_JPEG_SCALED are the decoder's own options and travel on with the format)
+        constexpr int kDecoderOptions = LR_JPEG_ANY_SAMPLING | LR_JPEG_SCALED;
+        if ((format & ~(0xFF | kDecoderOptions)) != LR_WARP_JPEG_DECODE) return fail("LR_WARP_JPEG_DECODE together with another option bit");
         if (width != 0 || height != 0 || src_row_bytes != 0 || out_width != 0 || out_height != 0 || dst_row_bytes != 0)
             return fail("LR_WARP_JPEG_DECODE: width, height, out_width, out_height and the row strides must be 0 (they are in the frame table)");
         if (!M) return fail("LR_WARP_JPEG_DECODE: null pointer (lr_jpeg_decode_args)");
         const lr_jpeg_decode_args* a = reinterpret_cast<const lr_jpeg_decode_args*>(M);
         // (probe mode, d_dst == NULL, needs no context)
-        return ctx_decode_jpeg(c, d_src, a->h_src, src_image_bytes, format & (0xFF | LR_JPEG_ANY_SAMPLING), a->frames, batch, d_dst, dst_image_bytes, a->info);
+        return ctx_decode_jpeg(c, d_src, a->h_src, src_image_bytes, format & (0xFF | kDecoderOptions), a->frames, batch, d_dst, dst_image_bytes, a->info);
     }
     if (!c) return fail("no context");
     if (format & LR_WARP_JPEG) {  // lr_encode_jpeg_device (kernels_jpeg.hip): its own arguments arrive behind M

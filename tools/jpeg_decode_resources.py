@@ -1,14 +1,14 @@
 #!/usr/bin/env python3
 """The registers of the JPEG decoder's kernels in two checkouts, from the code objects' metadata (a tool, not a test; no GPU).
 
-    python tools/jpeg_decode_resources.py PARENT_TREE [--out profiles/jpeg_decode_sampling.txt]
+    python tools/jpeg_decode_resources.py PARENT_TREE [--out profiles/jpeg_decode_scale.txt]
 
 Compiles librectify_amd/csrc/kernels_jpeg_decode.hip of PARENT_TREE (a checkout of the parent commit) and of this tree for
 gfx950 with the build's flags, keeps the assembly, and reads .vgpr_count, .sgpr_count, .group_segment_fixed_size (LDS) and
 .private_segment_fixed_size (scratch) of every kernel from its amdhsa.kernels metadata.  A kernel of this tree stands beside
-the parent's kernel of the same name once the template argument kAny = false, which the parent does not have, is taken off:
-those are the kernels a call without LR_JPEG_ANY_SAMPLING launches, and their four numbers must be the parent's.  Exits 1
-if they are not.
+the parent's kernel of the same name, or, where this tree's templates have one argument more than the parent's (kScaled
+of the transform and the output pass), of that name with the new argument false: those are the kernels a call without the new
+option launches, and their four numbers must be the parent's.  Exits 1 if they are not.
 """
 import argparse
 import os
@@ -45,16 +45,17 @@ def resources(tree):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("parent_tree")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "jpeg_decode_sampling.txt"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "jpeg_decode_scale.txt"))
     a = ap.parse_args()
     old, new = resources(a.parent_tree), resources(ROOT)
     lines = ["", "== registers of the decoder's kernels, gfx950, from the code objects' metadata: VGPRs / SGPRs / LDS bytes / scratch bytes ==",
-             "   (left: the parent commit; right: this commit, the instantiation a call without LR_JPEG_ANY_SAMPLING launches, and",
-             "    further right the general one that a call with the bit and a frame that needs it launches)"]
+             "   (left: the parent commit; right: this commit, the same instantiation, which a call without the new option launches;",
+             "    further right the instantiation that a call with LR_JPEG_SCALED and a frame of scale 2, 4 or 8 launches in its place)"]
     same = True
     for name, was in sorted(old.items()):
-        special = name.replace(">", ", false>") if "<" in name else (name if name in new else name + "<false>")
-        general = special.replace("false>", "true>") if special != name else None
+        special = name if name in new else (name.replace(">", ", false>") if "<" in name else name + "<false>")
+        # (the scaled instantiations take the general geometry: kAny and kScaled both true)
+        general = re.sub(r"(true|false), false>$", "true, true>", special) if special != name else None
         now = new.get(special)
         same = same and now == was
         fmt = lambda r: "%3d / %3d / %5d / %d" % r if r else "(none)"  # noqa: E731
