@@ -7,6 +7,7 @@
 //   rectify_recipe in.pgm|in.ppm out_prefix [--max-size N|fraction] [--refine] [--threads N]
 //                  [--h-strategy rotate_h|rotate_v|rectify|keep] [--v-strategy ...] [--warp] [--device-prepare] [--lines]
 //                  [--jpeg Q] [--optimize] [--jpeg-in] [--orient] [--any-sampling] [--scale N] [--cubic] [--border MODE[:VALUE]] [--crop]
+//                  [--lens fx,fy,cx,cy,k1,k2,p1,p2,k3]
 //
 // Input is a binary PGM (P5, 8 bit) or PPM (P6, 8 bit; converted with the usual integer luma weights
 // (4899 R + 9617 G + 1868 B + 8192) >> 14).  Image decoding stays with the caller's imaging library.
@@ -45,6 +46,11 @@
 // source's aspect that holds no border; the margin follows --cubic); the segments of --lines are drawn through the crop's H.
 // --cubic (with --warp or --jpeg alone; it implies neither): the warp samples 4 x 4 bicubic, cv::warpPerspective's INTER_CUBIC
 // (LR_WARP_CUBIC or-ed into the warp's format word), instead of bilinear.  Everything else is as without it.
+// --lens fx,fy,cx,cy,k1,k2,p1,p2,k3 (with --warp or --jpeg alone; not with --crop): the frame's camera matrix and distortion
+// vector, OpenCV's, in the pixel units of the frame as read (LR_WARP_LENS).  One warp with the identity map and the lens writes
+// the frame without its distortion; prescale, detector and the CSV files work on that one, so segments and transform are in
+// ideal coordinates (lr_lens_distort takes a point back onto the photograph); the rectified picture is then warped from the
+// frame AS READ with the lens and the homography: one resampling.
 // Links against librectify_amd.so exactly like a program written for the reference.
 #include <algorithm>
 #include <cctype>
@@ -290,9 +296,10 @@ struct Border {
     unsigned v[3] = {0, 0, 0};
 };
 
+// lens: --lens's nine entries, or null; they travel behind the border word (LR_WARP_LENS).
 bool warp_frame(const Gray& g, const ImageTransform& t, const std::string& prefix, std::vector<uint8_t>& out, int& ow, int& oh,
-                double* H, int jpeg, bool optimize, bool cubic, const Border* border, bool crop) {
-    double M[10];  // (the tenth: the border word of LR_WARP_BORDER)
+                double* H, int jpeg, bool optimize, bool cubic, const Border* border, bool crop, const double* lens) {
+    double M[19];  // (the tenth: the border word of LR_WARP_BORDER; the last nine: the lens of LR_WARP_LENS)
     lr_context* ctx = nullptr;
     void* d_src = nullptr;
     void* d_dst = nullptr;
@@ -314,6 +321,10 @@ bool warp_frame(const Gray& g, const ImageTransform& t, const std::string& prefi
         const unsigned value = g.ch == 3 ? (border->v[0] | border->v[1] << 8 | border->v[2] << 16) : border->v[0];
         M[9] = (double)border->mode + 8.0 * (double)(border->mode == LR_BORDER_CONSTANT ? value : 0u);
         options |= LR_WARP_BORDER;
+    }
+    if (lens) {
+        std::memcpy(M + (border ? 10 : 9), lens, 9 * sizeof(double));
+        options |= LR_WARP_LENS;
     }
     ok = ok && lr_context_create(0, &ctx) == 0;
     if (ok) {
@@ -343,6 +354,53 @@ bool warp_frame(const Gray& g, const ImageTransform& t, const std::string& prefi
     }
     std::printf("wrote %s (%dx%d)\n", path.c_str(), ow, oh);
     return true;
+}
+
+// --lens: the frame without its distortion (the identity map, bilinear, zero border: LR_WARP_LENS), for prescale and detector.
+// Returns false with the reason on stderr.
+bool undistort_frame(const Gray& g, const double* lens, Gray& out) {
+    double M[18] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    std::memcpy(M + 9, lens, 9 * sizeof(double));
+    lr_context* ctx = nullptr;
+    void* d_src = nullptr;
+    void* d_dst = nullptr;
+    const size_t bpp = (size_t)g.ch;
+    out.w = g.w;
+    out.h = g.h;
+    out.ch = g.ch;
+    out.raw.resize(g.raw.size());
+    const bool ok = lr_context_create(0, &ctx) == 0 && lr_device_malloc(ctx, g.raw.size(), &d_src) == 0 &&
+                    lr_device_malloc(ctx, g.raw.size(), &d_dst) == 0 && lr_memcpy_h2d(ctx, d_src, g.raw.data(), g.raw.size()) == 0 &&
+                    lr_warp_perspective_device(ctx, d_src, g.raw.size(), 1, g.w, g.h, (size_t)g.w * bpp,
+                                               (g.ch == 3 ? LR_PIX_U8X3 : LR_PIX_U8) | LR_WARP_LENS, M, d_dst, g.raw.size(), g.w, g.h,
+                                               (size_t)g.w * bpp) == 0 &&
+                    lr_memcpy_d2h(ctx, out.raw.data(), d_dst, out.raw.size()) == 0;
+    if (!ok) std::fprintf(stderr, "undistorting failed: %s\n", lr_last_error());
+    if (ctx) {
+        if (d_src) lr_device_free(ctx, d_src);
+        if (d_dst) lr_device_free(ctx, d_dst);
+        lr_context_destroy(ctx);
+    }
+    if (!ok) return false;
+    out.px.resize((size_t)out.w * out.h);
+    for (size_t i = 0; i < out.px.size(); ++i) {
+        int v = out.raw[i * out.ch];
+        if (out.ch == 3) v = (4899 * out.raw[i * 3] + 9617 * out.raw[i * 3 + 1] + 1868 * out.raw[i * 3 + 2] + 8192) >> 14;
+        out.px[i] = (float)v * (1.0f / 256.0f);
+    }
+    return true;
+}
+
+// --lens's argument: nine numbers separated by commas, all finite, fx and fy above 0
+bool parse_lens(const char* text, double* lens) {
+    const char* p = text;
+    for (int i = 0; i < 9; ++i) {
+        char* end = nullptr;
+        lens[i] = std::strtod(p, &end);
+        if (end == p || !std::isfinite(lens[i]) || *end != (i < 8 ? ',' : '\0')) return false;
+        p = end + 1;
+    }
+    return lens[0] > 0.0 && lens[1] > 0.0;
 }
 
 // --border's argument: MODE[:VALUE], VALUE a gray level or R,G,B (a gray level serves all three channels)
@@ -430,14 +488,16 @@ int main(int argc, char** argv) {
                      "usage: %s in.pgm|in.ppm out_prefix [--max-size N|fraction] [--refine] [--threads N]\n"
                      "          [--h-strategy rotate_h|rotate_v|rectify|keep] [--v-strategy ...] [--warp] [--device-prepare]\n"
                      "          [--lines] [--jpeg Q] [--optimize] [--jpeg-in] [--orient] [--any-sampling] [--scale 1|2|4|8]\n"
-                     "          [--cubic] [--border constant|replicate|reflect|reflect101[:VALUE]] [--crop]\n",
+                     "          [--cubic] [--border constant|replicate|reflect|reflect101[:VALUE]] [--crop]\n"
+                     "          [--lens fx,fy,cx,cy,k1,k2,p1,p2,k3]\n",
                      argv[0]);
         return 2;
     }
     float max_size = 1200.f;  // the demo's default
     bool refine = false, warp = false, device_prepare = false, lines_pictures = false, jpeg_in = false, orient = false, any_sampling = false, cubic = false;
-    bool optimize = false, bordered = false, crop = false;
+    bool optimize = false, bordered = false, crop = false, lensed = false;
     Border border;
+    double lens[9];
     int threads = -1, jpeg = 0, decode_scale = 0;
     RectificationConfig cfg;
     cfg.horizontal_vp_min_distance = 2;  // autorectify.cpp:347
@@ -458,6 +518,10 @@ int main(int argc, char** argv) {
         else if (a == "--crop") crop = true;
         else if (a == "--border" && has_val && parse_border(argv[i + 1], border)) {
             bordered = true;
+            ++i;
+        }
+        else if (a == "--lens" && has_val && parse_lens(argv[i + 1], lens)) {
+            lensed = true;
             ++i;
         }
         else if (a == "--max-size" && has_val) max_size = (float)std::atof(argv[++i]);
@@ -497,6 +561,10 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--border and --crop go with --warp or --jpeg: they shape the rectified picture and imply neither\n");
         return 2;
     }
+    if (lensed && (!warp || crop)) {
+        std::fprintf(stderr, "--lens goes with --warp or --jpeg and not with --crop: the crop's rectangle assumes straight source edges\n");
+        return 2;
+    }
     Gray full;
     if (jpeg_in) {
         if (!load_jpeg(argv[1], orient, any_sampling, decode_scale, full)) return 1;
@@ -504,6 +572,10 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "cannot read %s (binary PGM/PPM, 8 bit, expected)\n", argv[1]);
         return 1;
     }
+    // --lens: prescale, detector and the lines picture see the frame without its distortion; the warp reads it as read
+    Gray ideal;
+    if (lensed && !undistort_frame(full, lens, ideal)) return 1;
+    const Gray& seen = lensed ? ideal : full;
     // a value below 1 is a fraction of the long side (autorectify.cpp:121-125)
     const int max_px = max_size < 1.f ? (int)(std::max(full.w, full.h) * max_size) : (int)max_size;
     float scale = 1.f;
@@ -511,12 +583,12 @@ int main(int argc, char** argv) {
     LineSegment* lines = nullptr;
     std::vector<LineSegment> found;  // --device-prepare: the caller's array
     if (device_prepare) {
-        if (!find_groups_device_prepared(full, std::max(1, max_px), refine, threads, found, small_w, small_h, scale))
+        if (!find_groups_device_prepared(seen, std::max(1, max_px), refine, threads, found, small_w, small_h, scale))
             return 1;
         n = (int)found.size();
         lines = found.data();
     } else {
-        Gray img = prescale(full, std::max(1, max_px), scale);
+        Gray img = prescale(seen, std::max(1, max_px), scale);
         small_w = img.w;
         small_h = img.h;
         lines = find_line_segment_groups(img.px.data(), img.w, img.h, img.w, (float)std::max(img.w, img.h) / 100.0f,
@@ -549,10 +621,10 @@ int main(int argc, char** argv) {
     std::vector<uint8_t> warped;
     int ow = 0, oh = 0;
     double H[9];
-    bool ok = !warp || warp_frame(full, t, prefix, warped, ow, oh, H, jpeg, optimize, cubic, bordered ? &border : nullptr, crop);
+    bool ok = !warp || warp_frame(full, t, prefix, warped, ow, oh, H, jpeg, optimize, cubic, bordered ? &border : nullptr, crop, lensed ? lens : nullptr);
     if (ok && lines_pictures) {  // on the gray frame, as the demo draws (autorectify.cpp:364)
-        std::vector<uint8_t> gray(full.px.size());
-        for (size_t i = 0; i < gray.size(); ++i) gray[i] = (uint8_t)(full.px[i] * 256.0f);
+        std::vector<uint8_t> gray(seen.px.size());
+        for (size_t i = 0; i < gray.size(); ++i) gray[i] = (uint8_t)(seen.px[i] * 256.0f);
         ok = lines_picture(gray.data(), full.w, full.h, 1, lines, n, nullptr, prefix + "_lines.ppm") &&
              (!warp || lines_picture(warped.data(), ow, oh, full.ch, lines, n, H, prefix + "_warp_lines.ppm", jpeg, optimize, prefix + "_warp_lines.jpg"));
     }

@@ -313,6 +313,51 @@ enum lr_warp_sampling { LR_WARP_CUBIC = 0x8000 }; /* or-ed into `format` like lr
  * LR_WARP_JPEG or LR_WARP_JPEG_DECODE.  Without the bit nothing changes: rows keep their lengths, a non-zero [17] fails. */
 enum lr_warp_border { LR_WARP_BORDER = 0x40000 }; /* or-ed into `format` like lr_warp_option */
 enum lr_border_mode { LR_BORDER_CONSTANT = 0, LR_BORDER_REPLICATE = 1, LR_BORDER_REFLECT = 2, LR_BORDER_REFLECT_101 = 4 };
+/* LR_WARP_LENS gives every frame a lens model, OpenCV's camera matrix and five distortion coefficients, so that the warp reads
+ * a photograph that is no pinhole picture: it undistorts and warps in ONE resampling.  It is an option of the three warps and
+ * of nothing else, with or without LR_WARP_CUBIC and LR_WARP_BORDER, for u8, u8x3 and f32.  With the bit every frame's row of
+ * the host table M carries nine more doubles at its end, behind the border word where there is one:
+ *   fmt | LR_WARP_LENS                    18 doubles per frame, 19 with LR_WARP_BORDER;
+ *   fmt | LR_WARP_PACKED | LR_WARP_LENS   22 doubles per frame, 23 with LR_WARP_BORDER;
+ *   fmt | LR_WARP_RAGGED | LR_WARP_LENS   27 doubles per frame (the border word stays entry [17]).
+ * The nine are fx, fy, cx, cy, k1, k2, p1, p2, k3 in the source frame's pixel units.  M keeps its meaning, destination pixel
+ * to source; with the bit "source" is the IDEAL (undistorted) picture, which has the source's size and camera matrix, and the
+ * lens model takes that point to the pixel of the stored frame that is sampled.  Arithmetic (DESIGN.md section 3, item 17;
+ * tests/numpy_warp_lens_ref.py restates it), in double, every operation rounded on its own; N0, N1, W0 are the three dot
+ * products of the warp's rule:
+ *   Wq = W0 != 0 ? 32 / W0 : 0;   U = N0 * Wq;   V = N1 * Wq
+ *   a  = (U * 0.03125 - cx) / fx;                b = (V * 0.03125 - cy) / fy
+ *   r2 = a*a + b*b;    rad = r2 * (k1 + r2 * (k2 + r2 * k3))
+ *   ta = (2*p1) * (a*b) + p2 * (r2 + 2*(a*a));   tb = p1 * (r2 + 2*(b*b)) + (2*p2) * (a*b)
+ *   du = fx * (a*rad + ta);                      dv = fy * (b*rad + tb)
+ *   X  = fixed(U + 32*du);                       Y  = fixed(V + 32*dv)
+ * fixed being the warp's clamp to [INT_MIN, INT_MAX] (a NaN becomes INT_MIN) and rounding half to even.  Taps, weights, both
+ * sampling rules and every border mode behind X, Y are what they are without the bit.  A frame whose five coefficients are all
+ * zero (of either sign) is by definition warped by the plain rule: byte for byte the frame of the call without the bit.
+ * Infinities and NaN go the way they go in the plain rule; there is no guard against a model that folds over at a large radius
+ * (the caller's model, as with cv::undistort).  Fails cleanly (nothing launched, nothing written, lr_last_error names the frame)
+ * on what the call without the bit rejects, a non-finite entry among the nine, fx <= 0 or fy <= 0, and together with
+ * LR_WARP_PREPARE, LR_WARP_LINES, LR_WARP_JPEG or LR_WARP_JPEG_DECODE.  Without the bit nothing changes. */
+enum lr_warp_lens { LR_WARP_LENS = 0x100000 }; /* or-ed into `format` like lr_warp_option */
+
+/* The lens model on the host: the pixel (*ud, *vd) of the stored photograph that shows the ideal point (u, v); lens: the nine
+ * entries above.  The same operations in the same order as LR_WARP_LENS's rule with U = 32 u and V = 32 v, returning
+ * (U + 32 du) / 32 and (V + 32 dv) / 32: it takes detected lines, which are in ideal coordinates, back onto the photograph.
+ * Host arithmetic only; a static inline because the export table is full.  Compiled without floating-point contraction
+ * (-ffp-contract=off) it is, operation for operation, the Python package's lens_distort. */
+static inline void lr_lens_distort(const double lens[9], double u, double v, double* ud, double* vd) {
+    const double fx = lens[0], fy = lens[1], cx = lens[2], cy = lens[3];
+    const double k1 = lens[4], k2 = lens[5], p1 = lens[6], p2 = lens[7], k3 = lens[8];
+    const double U = 32.0 * u, V = 32.0 * v;
+    const double a = (U * 0.03125 - cx) / fx, b = (V * 0.03125 - cy) / fy;
+    const double r2 = a * a + b * b;
+    const double rad = r2 * (k1 + r2 * (k2 + r2 * k3));
+    const double ta = (2.0 * p1) * (a * b) + p2 * (r2 + 2.0 * (a * a));
+    const double tb = p1 * (r2 + 2.0 * (b * b)) + (2.0 * p2) * (a * b);
+    const double du = fx * (a * rad + ta), dv = fy * (b * rad + tb);
+    if (ud) *ud = (U + 32.0 * du) / 32.0;
+    if (vd) *vd = (V + 32.0 * dv) / 32.0;
+}
 
 /* The constrained crop: the largest upright rectangle of the rectified picture, of the given aspect and centred on the image
  * of the source's centre, that contains no border at all.  Host arithmetic only, in double; a static inline because the export

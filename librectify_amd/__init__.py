@@ -5,6 +5,7 @@ shared library librectify_amd.so (HIP kernels for gfx950).  This module is plumb
 declarations, numpy views of the POD structs, and a thin Context class.  There is NO CPU
 fallback: if the library or a GPU is missing, calls raise.
 """
+import collections
 import ctypes as C
 import os
 
@@ -90,6 +91,7 @@ JPEG_ANY_SAMPLING = 0x20000  # enum lr_jpeg_decode_option: or-ed into lr_decode_
 WARP_JPEG_DECODE = 0x4000  # enum lr_warp_jpeg_decode, likewise: lr_decode_jpeg_device, whose own arguments travel behind M (JpegDecodeArgs)
 WARP_BORDER = 0x40000  # enum lr_warp_border, likewise: a border word per frame in the warp's table (border_word, border= of the tables)
 BORDER_CONSTANT, BORDER_REPLICATE, BORDER_REFLECT, BORDER_REFLECT_101 = 0, 1, 2, 4  # enum lr_border_mode: OpenCV's numbers
+WARP_LENS = 0x100000  # enum lr_warp_lens, likewise: nine lens entries per frame at the end of its row of the warp's table (Lens, lens= of the tables)
 JPEG_OK, JPEG_NOT_JPEG, JPEG_UNSUPPORTED, JPEG_SIZE_MISMATCH, JPEG_DAMAGED = range(5)  # info[5] of lr_decode_jpeg_device
 FRAMES_U8, FRAMES_U8X3, FRAMES_F32 = 0x100, 0x200, 0x300  # enum lr_frames_option, or-ed into `refine` of the frame entries
 
@@ -288,6 +290,55 @@ def border_word(border, fmt):
     return BORDER_CONSTANT + 8 * bits
 
 
+Lens = collections.namedtuple("Lens", "fx fy cx cy k1 k2 p1 p2 k3", defaults=(0.0, 0.0, 0.0, 0.0, 0.0))
+Lens.__doc__ = """A frame's lens of LR_WARP_LENS: OpenCV's camera matrix (fx, fy, cx, cy) and distortion vector (k1, k2, p1, p2, k3), in the
+source frame's pixel units.  All five coefficients zero: no lens, the plain rule."""
+
+
+def _lens_row(lens, what):
+    """the nine doubles of one frame's lens (None: zeros, with fx = fy = 1), checked as the library checks them"""
+    if lens is None:
+        return [1.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0]
+    try:
+        row = [float(v) for v in Lens(*lens)]
+    except (TypeError, ValueError):
+        raise ValueError("%s: a lens is a Lens(fx, fy, cx, cy, k1, k2, p1, p2, k3) or None, not %r" % (what, lens)) from None
+    if not all(np.isfinite(row)):
+        raise ValueError("%s: a lens entry is not finite" % what)
+    if row[0] <= 0.0 or row[1] <= 0.0:
+        raise ValueError("%s: a lens has fx <= 0 or fy <= 0" % what)
+    return row
+
+
+def _lens_rows(lens, count, what):
+    """float64 (count, 9): the lens entries of `count` frames from lens=: one Lens for all, or a list of one per frame (None: zeros)"""
+    if lens is None or isinstance(lens, Lens):
+        return np.array([_lens_row(lens, what)] * count, np.float64).reshape(count, 9)
+    specs = list(lens)
+    if len(specs) != count:
+        raise ValueError("%s: as many lenses as frames (%d), not %d" % (what, count, len(specs)))
+    return np.array([_lens_row(v, what) for v in specs], np.float64).reshape(count, 9)
+
+
+def lens_distort(lens, points):
+    """lr_lens_distort of include/librectify_amd.h restated operation for operation in float64: the pixels of the stored
+    photograph that show the ideal points.  lens: a Lens; points: (..., 2) array of (u, v).  Returns float64 of the same
+    shape.  It takes detected lines, which are in ideal coordinates, back onto the photograph.  Needs no GPU."""
+    fx, fy, cx, cy, k1, k2, p1, p2, k3 = (np.float64(v) for v in Lens(*lens))
+    pts = np.asarray(points, np.float64)
+    if pts.shape[-1:] != (2,):
+        raise ValueError("lens_distort: points is (..., 2)")
+    with np.errstate(all="ignore"):
+        U, V = 32.0 * pts[..., 0], 32.0 * pts[..., 1]
+        a, b = (U * 0.03125 - cx) / fx, (V * 0.03125 - cy) / fy
+        r2 = a * a + b * b
+        rad = r2 * (k1 + r2 * (k2 + r2 * k3))
+        ta = (2.0 * p1) * (a * b) + p2 * (r2 + 2.0 * (a * a))
+        tb = p1 * (r2 + 2.0 * (b * b)) + (2.0 * p2) * (a * b)
+        du, dv = fx * (a * rad + ta), fy * (b * rad + tb)
+        return np.stack([(U + 32.0 * du) / 32.0, (V + 32.0 * dv) / 32.0], axis=-1)
+
+
 def _is_border_spec(border):
     return border is None or isinstance(border, str) or (isinstance(border, tuple) and len(border) == 2 and isinstance(border[0], str))
 
@@ -402,14 +453,16 @@ def crop_homography(H, M, width, height, out_size, margin=0, aspect=None):
     return H_out.reshape(3, 3), M_out.reshape(3, 3), (int(lo_x), int(lo_y), int(hi_x - lo_x) + 1, int(hi_y - lo_y) + 1)
 
 
-def warp_table(Ms, sizes, bpp, align=4, border=None):
+def warp_table(Ms, sizes, bpp, align=4, border=None, lens=None):
     """The table of a packed warp (lr_warp_perspective_device with LR_WARP_PACKED) for frames laid out one after the
     other in frame order.  Ms: (B, 3, 3) destination-to-source maps; sizes: B pairs (out_width, out_height); bpp: bytes
     per pixel (1 u8, 3 u8x3, 4 f32); every row stride and every frame's start is rounded up to `align` bytes (for f32 a
     multiple of 4).  Returns (table, total_bytes): table float64 (B, 13) -- the map, width, height, byte offset, row
     stride -- and the bytes of the destination, which end with the last frame's last pixel.  Needs no GPU.
     border (not None): the table of LR_WARP_PACKED | LR_WARP_BORDER, (B, 14), whose column 13 is every frame's border word:
-    one spec for all frames (border_word's) or a list of one per frame."""
+    one spec for all frames (border_word's) or a list of one per frame.
+    lens (not None): the table of LR_WARP_PACKED | LR_WARP_LENS, (B, 22) or with border (B, 23), whose last nine columns are
+    every frame's lens: one Lens for all frames or a list of one per frame, in which None means zeros."""
     Ms = np.asarray(Ms, np.float64)
     if Ms.ndim == 2 and Ms.shape == (3, 3):
         Ms = Ms[None]
@@ -440,10 +493,12 @@ def warp_table(Ms, sizes, bpp, align=4, border=None):
     if border is not None:
         words = _border_words(border, len(Ms), _FMT_OF_BPP[bpp], "warp_table")
         table = np.concatenate([table, np.array(words, np.float64).reshape(-1, 1)], axis=1)
+    if lens is not None:
+        table = np.concatenate([table, _lens_rows(lens, len(Ms), "warp_table")], axis=1)
     return table, end
 
 
-def ragged_table(Ms, out_sizes, sources, bpp, out_bpp=None, align=4, border=None):
+def ragged_table(Ms, out_sizes, sources, bpp, out_bpp=None, align=4, border=None, lens=None):
     """The table of a ragged call (lr_warp_perspective_device with LR_WARP_RAGGED): warp_table's layout for the outputs plus
     the four source columns.  Ms: (B, 3, 3) destination-to-source maps, or None (identity: the prepare step ignores them);
     out_sizes: B pairs (out_width, out_height); sources: B rows (width, height, byte_offset, row_bytes) of the frames in
@@ -452,7 +507,9 @@ def ragged_table(Ms, out_sizes, sources, bpp, out_bpp=None, align=4, border=None
     and start rounded up to `align` bytes (a multiple of 4 for 4-byte outputs).  Returns (table, dst_bytes): table
     float64 (B, 18).  Needs no GPU.
     border (not None): the table of LR_WARP_RAGGED | LR_WARP_BORDER, whose column 17 is every frame's border word: one spec
-    for all frames (border_word's) or a list of one per frame."""
+    for all frames (border_word's) or a list of one per frame.
+    lens (not None): the table of LR_WARP_RAGGED | LR_WARP_LENS, (B, 27), whose last nine columns are every frame's lens: one
+    Lens for all frames or a list of one per frame, in which None means zeros."""
     if bpp not in (1, 3, 4):
         raise ValueError("ragged_table: bpp is 1, 3 or 4")
     out_bpp = bpp if out_bpp is None else out_bpp
@@ -484,6 +541,8 @@ def ragged_table(Ms, out_sizes, sources, bpp, out_bpp=None, align=4, border=None
     table[:, 13:17] = src
     if border is not None:
         table[:, 17] = _border_words(border, B, _FMT_OF_BPP[bpp], "ragged_table")
+    if lens is not None:
+        table = np.concatenate([table, _lens_rows(lens, B, "ragged_table")], axis=1)
     return table, total
 
 
@@ -741,12 +800,19 @@ def _rectified_map(t, clip, crop, cubic):
     return M, rect[2:], rect
 
 
-def _border_bit_and_map(border, fmt, M, what):
-    """(WARP_BORDER or 0, M or M's nine values and the border word behind them) for a single-frame warp with border="""
-    if border is None:
+def _border_bit_and_map(border, fmt, M, what, lens=None):
+    """(WARP_BORDER, WARP_LENS or 0, M or M's nine values with the border word and the nine lens entries behind them) for a
+    single-frame warp with border= and lens="""
+    if border is None and lens is None:
         return 0, M
-    word = _border_words(border, 1, fmt, what)[0]
-    return WARP_BORDER, np.concatenate([np.asarray(M, np.float64).reshape(9), [float(word)]])
+    row, bits = [np.asarray(M, np.float64).reshape(9)], 0
+    if border is not None:
+        row.append([float(_border_words(border, 1, fmt, what)[0])])
+        bits |= WARP_BORDER
+    if lens is not None:
+        row.append(_lens_rows(lens, 1, what)[0])
+        bits |= WARP_LENS
+    return bits, np.concatenate(row)
 
 
 class Context:
@@ -898,9 +964,10 @@ class Context:
         """lr_warp_perspective_device: one launch for `batch` device frames, enqueued on the context's stream.  M: 9
         doubles per frame ((batch, 3, 3) or (3, 3)), the destination-to-source map.  fmt: PIX_U8, PIX_U8X3, PIX_F32, with
         WARP_CUBIC or-ed in for the bicubic sampling rule and WARP_BORDER for a border rule per frame (M then has 10 doubles
-        per frame, the tenth the frame's border_word)."""
+        per frame, the tenth the frame's border_word), and WARP_LENS for a lens per frame (nine more doubles per frame at the
+        end: a Lens)."""
         M = np.ascontiguousarray(M, np.float64).reshape(-1)
-        per_frame = 10 if fmt & WARP_BORDER else 9
+        per_frame = (10 if fmt & WARP_BORDER else 9) + (9 if fmt & WARP_LENS else 0)
         if M.size < per_frame * max(int(batch), 1):
             raise ValueError("warp_perspective_device: M needs %d values per frame" % per_frame)
         _check(lib().lr_warp_perspective_device(self._h, C.c_void_p(d_src), src_image_bytes, batch, width, height, src_row_bytes, fmt, _ptr(M), C.c_void_p(d_dst), dst_image_bytes, out_width, out_height, dst_row_bytes))
@@ -909,24 +976,27 @@ class Context:
                                        dst_bytes):
         """lr_warp_perspective_device with LR_WARP_PACKED: one launch for `batch` device frames of one size whose outputs
         have their own sizes and places in the dst_bytes at d_dst.  table: 13 doubles per frame (warp_table).  fmt may carry
-        WARP_CUBIC, and WARP_BORDER with a table of 14 doubles per frame (warp_table's border=)."""
+        WARP_CUBIC, WARP_BORDER with a table of 14 doubles per frame (warp_table's border=), and WARP_LENS with nine more
+        (warp_table's lens=)."""
         table = np.ascontiguousarray(table, np.float64).reshape(-1)
-        cols = 14 if fmt & WARP_BORDER else 13
+        cols = (14 if fmt & WARP_BORDER else 13) + (9 if fmt & WARP_LENS else 0)
         if table.size != cols * int(batch) or batch < 1:
             raise ValueError("warp_perspective_packed_device: the table has %d values per frame" % cols)
         out_w, out_h = (int(min(max(v, 1), 2 ** 31 - 1)) for v in np.nan_to_num(table.reshape(-1, cols)[:, 9:11]).max(axis=0))
         _check(lib().lr_warp_perspective_device(self._h, C.c_void_p(d_src), src_image_bytes, batch, width, height, src_row_bytes, fmt | WARP_PACKED, _ptr(table), C.c_void_p(d_dst), dst_bytes, out_w, out_h, 0))
 
-    def warp_perspective(self, array, M, out_size, interp="linear", border=None):
+    def warp_perspective(self, array, M, out_size, interp="linear", border=None, lens=None):
         """Warps one host frame (2-D uint8 or float32, or H x W x 3 uint8) by M (3x3, destination -> source) into an image
         of out_size = (width, height) on the GPU: upload, one launch, download.  Returns the (height, width[, 3]) array.
         interp: "linear" (bilinear) or "cubic" (WARP_CUBIC: 4 x 4 bicubic, cv::warpPerspective's INTER_CUBIC).
         border: None (the zero border) or border_word's spec -- "replicate", "reflect", "reflect101", ("constant", value):
-        cv::warpPerspective's borderMode and borderValue (WARP_BORDER)."""
+        cv::warpPerspective's borderMode and borderValue (WARP_BORDER).
+        lens: None or the frame's Lens (WARP_LENS): M then maps into the ideal picture, and the lens model takes the point to the
+        pixel of `array` that is sampled -- undistortion and warp in one resampling."""
         cubic = _sampling_bit(interp, "warp_perspective")
         a = np.ascontiguousarray(array)
         fmt, bpp = _frame_format(a, "warp_perspective")
-        bbit, M = _border_bit_and_map(border, fmt, M, "warp_perspective")
+        bbit, M = _border_bit_and_map(border, fmt, M, "warp_perspective", lens)
         h, w = a.shape[:2]
         ow, oh = int(out_size[0]), int(out_size[1])
         d_src = self.device_upload(a)
@@ -939,6 +1009,14 @@ class Context:
             self.device_free(d_src)
             if d_dst.value:
                 self.device_free(d_dst.value)
+
+    def undistort(self, image, lens, interp="linear", border=None):
+        """The frame without its lens distortion (cv::undistort with the frame's own camera matrix): warp_perspective with the
+        identity map, the lens and the source's size."""
+        a = np.asarray(image)
+        if a.ndim < 2:
+            raise ValueError("undistort: a 2-D uint8 or float32 frame, or an H x W x 3 uint8 frame")
+        return self.warp_perspective(a, np.eye(3), (a.shape[1], a.shape[0]), interp=interp, border=border, lens=lens)
 
     # ---- the lines picture ----
     def draw_lines_device(self, d_src, src_bytes, fmt, lines, table, d_dst, dst_bytes, H=None):
@@ -1204,11 +1282,11 @@ class Context:
         return self.decode_jpeg_batch([data], fmt, orient, any_sampling, scale)[0]
 
     def _rectify_streams(self, streams, min_length, refine, cfg, clip, max_size, capacity, jpeg, orient=False, interp="linear", jpeg_optimize=False,
-                         any_sampling=False, border=None, crop=False, decode_scale=None, decode_max_size=None):
+                         any_sampling=False, border=None, crop=False, decode_scale=None, decode_max_size=None, lens=None):
         """rectify_batch for JPEG files: the files go up and are decoded in HBM, the pictures are handed to
         rectify_frames_device where they lie; with jpeg=Q no pixel crosses the link in either direction"""
         d_src, _, fmt, sources = self._decode_resident(streams, None, "rectify_batch", orient, any_sampling, decode_scale, decode_max_size)
-        return self._rectify_resident(d_src, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp, jpeg_optimize, border, crop)
+        return self._rectify_resident(d_src, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp, jpeg_optimize, border, crop, lens)
 
     def prepare_device(self, d_src, src_image_bytes, batch, width, height, src_row_bytes, fmt, d_dst, dst_image_bytes,
                        out_width, out_height, dst_row_bytes):
@@ -1269,7 +1347,8 @@ class Context:
                     self.device_free(p.value)
 
     def rectify(self, image_u8, min_length=None, refine=False, cfg=None, clip=3.0, max_size=None, jpeg=None, orient=False,
-                interp="linear", jpeg_optimize=False, any_sampling=False, border=None, crop=False, decode_scale=None, decode_max_size=None):
+                interp="linear", jpeg_optimize=False, any_sampling=False, border=None, crop=False, decode_scale=None, decode_max_size=None,
+                lens=None):
         """The reference demo's pipeline (autorectify.cpp) on an 8-bit frame (H x W gray or H x W x 3 RGB): luma
         (4899 R + 9617 G + 1868 B + 8192) >> 14, / 256, find_line_segment_groups with min_length max(w, h) / 100 by
         default, compute_rectification_transform (cfg: the demo's, horizontal_vp_min_distance = 2),
@@ -1298,12 +1377,23 @@ class Context:
         ("constant", value) -- for what lies outside the source (WARP_BORDER); only the picture differs.
         crop=True: the picture (or its JPEG file) is the constrained crop, the largest upright rectangle of the source's aspect
         around the image of the source's centre that contains no border (crop_homography; the margin follows interp), and the
-        call returns (lines, transform, warped, (x0, y0, width, height)), the rectangle in the uncropped picture."""
+        call returns (lines, transform, warped, (x0, y0, width, height)), the rectangle in the uncropped picture.
+        lens: the frame's Lens (WARP_LENS), for a photograph that is no pinhole picture; it refers to the frame as uploaded or
+        decoded.  The frame goes up (or is decoded) once; one WARP_LENS launch with the identity map, bilinear, zero border,
+        writes it without its distortion in HBM; luma, the prepare step and the detector run on that, so lines, transform
+        and homography are in IDEAL coordinates (lens_distort takes them back onto the photograph); the final warp reads
+        the ORIGINAL frame with WARP_LENS, the homography and the call's interp and border: one resampling.  The lines and the
+        transform are those of rectify(undistort(image, lens)), the picture is warp_perspective(image, M, lens=lens).
+        With crop=True: ValueError (the crop's rectangle assumes straight source edges)."""
         cubic = _sampling_bit(interp, "rectify")
         _check_jpeg_optimize("rectify", jpeg, jpeg_optimize)
+        if lens is not None:
+            if crop:
+                raise ValueError("rectify: crop=True together with lens= (the crop's rectangle assumes straight source edges)")
+            lens = Lens(*_lens_row(lens, "rectify"))
         if isinstance(image_u8, (bytes, bytearray, memoryview)):  # a JPEG file: decoded in HBM, rectify_batch's path for one frame
             res = self.rectify_batch([bytes(image_u8)], min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, jpeg=jpeg, orient=orient, interp=interp, jpeg_optimize=jpeg_optimize, any_sampling=any_sampling, border=border, crop=crop,
-                                     decode_scale=decode_scale, decode_max_size=decode_max_size)[0]
+                                     decode_scale=decode_scale, decode_max_size=decode_max_size, lens=lens)[0]
             if res[2] is None:
                 _rectified_map(res[1], clip, crop, cubic)  # (raises what rectify raises for such a frame)
             return res
@@ -1316,8 +1406,8 @@ class Context:
         img = np.ascontiguousarray(image_u8)
         if img.dtype != np.uint8 or not (img.ndim == 2 or (img.ndim == 3 and img.shape[2] == 3)):
             raise ValueError("rectify: an H x W or H x W x 3 uint8 frame")
-        if jpeg is not None:
-            res = self.rectify_batch(img[None], min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, jpeg=jpeg, interp=interp, jpeg_optimize=jpeg_optimize, border=border, crop=crop)[0]
+        if jpeg is not None or lens is not None:  # (with a lens: the mixed-size pipeline for one frame, which has the undistorting launch)
+            res = self.rectify_batch(img[None], min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, jpeg=jpeg, interp=interp, jpeg_optimize=jpeg_optimize, border=border, crop=crop, lens=lens)[0]
             if res[2] is None:
                 _rectified_map(res[1], clip, crop, cubic)  # (raises what rectify raises for such a frame)
             return res
@@ -1441,15 +1531,17 @@ class Context:
 
     def _ragged_call(self, d_src, src_bytes, fmt_word, table, d_dst, dst_bytes, what):
         table = np.ascontiguousarray(table, np.float64)
-        if table.ndim != 2 or table.shape[1] != 18 or len(table) < 1:
-            raise ValueError(what + ": the table has 18 values per frame")
+        cols = 27 if fmt_word & WARP_LENS else 18
+        if table.ndim != 2 or table.shape[1] != cols or len(table) < 1:
+            raise ValueError(what + ": the table has %d values per frame" % cols)
         bound = lambda col: int(min(max(np.nan_to_num(table[:, col]).max(), 1), 2 ** 31 - 1))  # noqa: E731
         _check(lib().lr_warp_perspective_device(self._h, C.c_void_p(d_src), src_bytes, len(table), bound(13), bound(14), 0, fmt_word, _ptr(table), C.c_void_p(d_dst), dst_bytes, bound(9), bound(10), 0))
 
     def warp_perspective_ragged_device(self, d_src, src_bytes, fmt, table, d_dst, dst_bytes):
         """lr_warp_perspective_device with LR_WARP_RAGGED: one launch for frames that have their own source size and place
         in the src_bytes at d_src and their own output size and place in the dst_bytes at d_dst.  table: 18 doubles per
-        frame (ragged_table).  fmt may carry WARP_CUBIC."""
+        frame (ragged_table).  fmt may carry WARP_CUBIC, WARP_BORDER, and WARP_LENS with a table of 27 doubles per frame
+        (ragged_table's lens=)."""
         self._ragged_call(d_src, src_bytes, fmt | WARP_RAGGED, table, d_dst, dst_bytes, "warp_perspective_ragged_device")
 
     def prepare_ragged_device(self, d_src, src_bytes, fmt, table, d_dst, dst_bytes):
@@ -1492,6 +1584,13 @@ class Context:
         table is ragged_table's (18 columns; an all-zero row for a frame without an image).  capacity and interp: as
         there (the ragged warp's sampling rule); border and crop likewise (the border words are the table's column 17; with
         crop=True the frames' rectangles are a sixth value)."""
+        return self._rectify_frames(d_base, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, interp, border, crop)
+
+    def _rectify_frames(self, d_base, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, interp, border, crop, lens_rows=None):
+        """rectify_frames_device; lens_rows (float64 (B, 9), rectify_batch's lens=): one WARP_LENS launch with the identity map,
+        bilinear, zero border, writes every frame without its distortion into a second region of the sources' layout; the
+        prepare step and the detector read that one, so lines and transforms are in ideal coordinates; the warp reads the
+        ORIGINAL frames with WARP_LENS: one resampling"""
         cubic = _sampling_bit(interp, "rectify_frames_device")
         if fmt not in (PIX_U8, PIX_U8X3):
             raise ValueError("rectify_frames_device: 8-bit frames, PIX_U8 or PIX_U8X3")
@@ -1504,14 +1603,24 @@ class Context:
         src_bytes = _source_extent(sources, bpp)
         if cfg is None:
             cfg = RectificationConfig(hmin=2.0)
-        d_small, d_out = C.c_void_p(), C.c_void_p()
+        d_small, d_out, d_ideal = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        d_seen = d_base  # what the prepare step and the detector read
         try:
             frames = (Frame * batch)()
+            if lens_rows is not None:
+                itable = np.zeros((batch, 27), np.float64)
+                itable[:, :9] = np.eye(3).reshape(9)
+                itable[:, 9:13] = itable[:, 13:17] = np.array(sources, np.float64)
+                itable[:, 18:] = lens_rows
+                _check(lib().lr_device_malloc(self._h, src_bytes, C.byref(d_ideal)))
+                self.warp_perspective_ragged_device(d_base, src_bytes, fmt | WARP_LENS, itable, d_ideal.value, src_bytes)
+                self.synchronize()  # (the batch detector reads the frames on its lanes' streams, not after this one's work)
+                d_seen = d_ideal.value
             if max_size is not None:
                 prepared = [prepared_size(w, h, max_size) for w, h, _, _ in sources]
                 ptable, small_bytes = ragged_table(None, np.array([p[:2] for p in prepared], np.int64), np.array(sources, np.int64), bpp, out_bpp=4)
                 _check(lib().lr_device_malloc(self._h, small_bytes, C.byref(d_small)))
-                self.prepare_ragged_device(d_base, src_bytes, fmt, ptable, d_small.value, small_bytes)
+                self.prepare_ragged_device(d_seen, src_bytes, fmt, ptable, d_small.value, small_bytes)
                 self.synchronize()  # (the batch detector reads the frames on its lanes' streams, not after this one's work)
                 det_fmt = PIX_F32
                 for b, (pw, ph, _) in enumerate(prepared):
@@ -1522,7 +1631,7 @@ class Context:
                     raise ValueError("rectify_frames_device: the detector takes strides in whole pixels")
                 det_fmt = fmt
                 for b, (w, h, off, row) in enumerate(sources):
-                    frames[b] = Frame(d_base + off, w, h, row // bpp, -1.0)
+                    frames[b] = Frame(d_seen + off, w, h, row // bpp, -1.0)
                 scales = [None] * batch
             for f in frames:
                 f.min_length = float(np.float32(max(f.width, f.height) / 100.0)) if min_length is None else float(min_length)
@@ -1557,12 +1666,14 @@ class Context:
             if words is not None:
                 table[good, 17] = [words[b] for b in good]
             _check(lib().lr_device_malloc(self._h, total, C.byref(d_out)))
+            bits = cubic | (0 if words is None else WARP_BORDER) | (0 if lens_rows is None else WARP_LENS)
             for run in np.split(np.array(good), np.flatnonzero(np.diff(good) != 1) + 1):
-                self.warp_perspective_ragged_device(d_base, src_bytes, fmt | cubic | (0 if words is None else WARP_BORDER), table[run], d_out.value, total)
+                rows = table[run] if lens_rows is None else np.concatenate([table[run], lens_rows[run]], axis=1)
+                self.warp_perspective_ragged_device(d_base, src_bytes, fmt | bits, rows, d_out.value, total)
             res, d_out = d_out.value, C.c_void_p()
             return (lines_list, transforms, table, res, total) + more
         finally:
-            for p in (d_small, d_out):
+            for p in (d_small, d_out, d_ideal):
                 if p.value:
                     self.device_free(p.value)
 
@@ -1575,7 +1686,8 @@ class Context:
             out[b] = s
         return out
 
-    def _rectify_mixed(self, frames, min_length, refine, cfg, clip, max_size, capacity, jpeg=None, interp="linear", jpeg_optimize=False, border=None, crop=False):
+    def _rectify_mixed(self, frames, min_length, refine, cfg, clip, max_size, capacity, jpeg=None, interp="linear", jpeg_optimize=False, border=None, crop=False,
+                       lens=None):
         """rectify_batch for a list of 8-bit frames of different shapes: all frames in one host buffer, one upload,
         rectify_frames_device, one download"""
         frames = [np.ascontiguousarray(f) for f in frames]
@@ -1593,15 +1705,16 @@ class Context:
         for f, (_, _, start, _) in zip(frames, sources):
             host[start: start + f.nbytes] = f.reshape(-1)
         _border_words(border, len(frames), fmt, "rectify_batch")  # (a bad spec: ValueError before anything goes up)
-        return self._rectify_resident(self.device_upload(host), sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp, jpeg_optimize, border, crop)
+        return self._rectify_resident(self.device_upload(host), sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp, jpeg_optimize, border, crop, lens)
 
-    def _rectify_resident(self, d_src, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp="linear", jpeg_optimize=False, border=None, crop=False):
+    def _rectify_resident(self, d_src, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp="linear", jpeg_optimize=False, border=None, crop=False,
+                          lens=None):
         """rectify_batch for 8-bit frames (width, height, byte_offset, row_bytes) that lie at d_src, which is freed here:
         rectify_frames_device, then one download of the pictures, or with jpeg the encoder and the streams alone"""
         bpp = 3 if fmt == PIX_U8X3 else 1
         d_out = None
         try:
-            lines, tfs, table, d_out, total, *more = self.rectify_frames_device(d_src, sources, fmt, min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, capacity=capacity, interp=interp, border=border, crop=crop)
+            lines, tfs, table, d_out, total, *more = self._rectify_frames(d_src, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, interp, border, crop, lens)
             rect = (lambda b: (more[0][b],)) if crop else (lambda b: ())
             if jpeg is not None:
                 streams = self._jpeg_results(d_out, total, fmt, table, jpeg, jpeg_optimize) if d_out else [None] * len(sources)
@@ -1623,7 +1736,7 @@ class Context:
 
     def rectify_batch(self, frames_u8, min_length=None, refine=False, cfg=None, clip=3.0, max_size=None, capacity=4096, jpeg=None,
                       orient=False, interp="linear", jpeg_optimize=False, any_sampling=False, border=None, crop=False, decode_scale=None,
-                      decode_max_size=None):
+                      decode_max_size=None, lens=None):
         """Context.rectify for a batch: frames_u8 is a uint8 array [B, H, W] or [B, H, W, 3], or a list of such frames of one
         shape.  One upload, rectify_batch_device (one detector batch, the packed warp), one download.  Returns a
         list of (lines, transform, warped), frame by frame what rectify returns for it; warped is None for a frame whose
@@ -1655,16 +1768,26 @@ class Context:
         sizes and the encoder are untouched -- frame by frame what rectify(interp="cubic") returns.
         border: None, one border_word spec for all frames or a list of one per frame (WARP_BORDER on the warp launch of
         whichever path is taken); crop=True: every picture, or JPEG file, is its constrained crop and every result has a fourth
-        entry, the rectangle (x0, y0, width, height) -- frame by frame what rectify(border=, crop=) returns."""
+        entry, the rectangle (x0, y0, width, height) -- frame by frame what rectify(border=, crop=) returns.
+        lens: None, one Lens for all frames or a list of one per frame, in which None means no lens (WARP_LENS): frame by frame
+        what rectify(lens=) returns.  Arrays and files alike then take the mixed-size pipeline, with one WARP_LENS launch in
+        front of it that writes the frames without their distortion for the detector, and the final warp reading the frames
+        as they were uploaded or decoded.  With crop=True: ValueError."""
         _sampling_bit(interp, "rectify_batch")
         _check_jpeg_optimize("rectify_batch", jpeg, jpeg_optimize)
+        if lens is not None:
+            if crop:
+                raise ValueError("rectify_batch: crop=True together with lens= (the crop's rectangle assumes straight source edges)")
+            lens = _lens_rows(lens, len(frames_u8), "rectify_batch")
         if _all_streams(frames_u8, "rectify_batch", orient, any_sampling, decode_scale, decode_max_size):
             try:  # (the files' format is known once they are decoded: a spec that suits neither 8-bit format fails here)
                 _border_words(border, len(frames_u8), PIX_U8X3, "rectify_batch")
             except ValueError:
                 _border_words(border, len(frames_u8), PIX_U8, "rectify_batch")
             return self._rectify_streams([bytes(f) for f in frames_u8], min_length, refine, cfg, clip, max_size, capacity, jpeg, orient, interp, jpeg_optimize,
-                                         any_sampling, border, crop, decode_scale, decode_max_size)
+                                         any_sampling, border, crop, decode_scale, decode_max_size, lens)
+        if lens is not None:
+            return self._rectify_mixed(list(frames_u8), min_length, refine, cfg, clip, max_size, capacity, jpeg, interp, jpeg_optimize, border, crop, lens)
         if not isinstance(frames_u8, np.ndarray):
             frames_u8 = [np.asarray(f) for f in frames_u8]
             if len({f.shape for f in frames_u8}) > 1:

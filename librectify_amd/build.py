@@ -19,6 +19,7 @@ SOURCES = [
     "kernels_groups.hip",
     "kernels_warp.hip",
     "kernels_warp_border.hip",
+    "kernels_warp_lens.hip",
     "kernels_prepare.hip",
     "kernels_overlay.hip",
     "kernels_jpeg.hip",

@@ -26,6 +26,10 @@
 // inside keep the loads above; only the others map their indices.  Its launches all go through warp_ragged_border_kernel, which
 // is kernels_warp_border.hip's; the lane body is in warp_lane.h for the two files.
 //
+// LR_WARP_LENS is a fourth: between the perspective divide and the rounding to 5-bit coordinates the point goes through the
+// frame's lens model (OpenCV's five coefficients; fixed_xy and lens_displace of warp_lane.h).  Its launches all go through
+// warp_ragged_lens_kernel, which is kernels_warp_lens.hip's, with a second array of records, one LensRecord per frame.
+//
 // One lane body, two kernels.  warp_lane is a lane's work inside a tile: its four pixels' taps, blends and stores.  The two
 // kernels differ only in how a workgroup finds its frame and the frame's values, all of which depend on the tile index
 // alone and are uniform across the workgroup:
@@ -117,15 +121,46 @@ int fail_border(const char* layout, int b, const char* why) {
     return 1;
 }
 
-// The table kernel's launch: records, then the tiles' prefix table, go up in the mirror of the maps (in doubles: 18 a
-// frame + the table's ints)
+// A frame's nine lens entries (LR_WARP_LENS): fx, fy, cx, cy, k1, k2, p1, p2, k3.  Fills the record; on a fault returns the
+// reason (NULL: none).  A frame whose five coefficients are all zero, of either sign, has no lens: the plain rule.
+const char* parse_lens(const double* t, LensRecord* l) {
+    for (int i = 0; i < 9; ++i)
+        if (!std::isfinite(t[i])) return "are not all finite";
+    if (!(t[0] > 0.0)) return "have fx <= 0";
+    if (!(t[1] > 0.0)) return "have fy <= 0";
+    std::memset(l, 0, sizeof *l);
+    l->fx = t[0];
+    l->fy = t[1];
+    l->cx = t[2];
+    l->cy = t[3];
+    l->k1 = t[4];
+    l->k2 = t[5];
+    l->p1 = t[6];
+    l->p2 = t[7];
+    l->k3 = t[8];
+    l->has_lens = t[4] != 0.0 || t[5] != 0.0 || t[6] != 0.0 || t[7] != 0.0 || t[8] != 0.0;
+    return nullptr;
+}
+
+int fail_lens(const char* layout, int b, const char* why) {
+    set_error(std::string("lr_warp_perspective_device: ") + layout + "LR_WARP_LENS: frame " + std::to_string(b) + ": the nine lens entries " + why);
+    return 1;
+}
+
+bool any_lens(const std::vector<LensRecord>& lens) {
+    return std::any_of(lens.begin(), lens.end(), [](const LensRecord& l) { return l.has_lens != 0; });
+}
+
+// The table kernel's launch: records, then (LR_WARP_LENS, `lens` not NULL) the lens records, then the tiles' prefix table, go
+// up in the mirror of the maps (in doubles: 18 a frame, 10 a lens + the table's ints)
 int launch_ragged(lr_context* c, const void* d_src, int format, bool cubic, bool border, const std::vector<RaggedFrame>& rec,
-                  const std::vector<int>& start, void* d_dst) {
-    const size_t batch = rec.size(), rec_doubles = batch * 18;
+                  const std::vector<int>& start, void* d_dst, const std::vector<LensRecord>* lens = nullptr) {
+    const size_t batch = rec.size(), lens_doubles = lens ? batch * 10 : 0, rec_doubles = batch * 18 + lens_doubles;
     const int64_t n_tiles = start[batch];
     LR_HIP(hipSetDevice(c->device));
     if (upload_reserve(c, c->warp_m, c->ev_warp_m, rec_doubles + (batch + 2) / 2)) return 1;
-    std::memcpy(c->warp_m.h, rec.data(), rec_doubles * sizeof(double));
+    std::memcpy(c->warp_m.h, rec.data(), batch * 18 * sizeof(double));
+    if (lens) std::memcpy(c->warp_m.h + batch * 18, lens->data(), lens_doubles * sizeof(double));
     std::memcpy(c->warp_m.h + rec_doubles, start.data(), start.size() * sizeof(int));
     if (upload_send(c, c->warp_m, c->ev_warp_m, rec_doubles * sizeof(double) + start.size() * sizeof(int))) return 1;
 
@@ -137,6 +172,11 @@ int launch_ragged(lr_context* c, const void* d_src, int format, bool cubic, bool
     const RaggedFrame* frames = reinterpret_cast<const RaggedFrame*>(c->warp_m.d.get());
     const int* tile_start = reinterpret_cast<const int*>(c->warp_m.d.get() + rec_doubles);
     const int grid = (int)std::min<int64_t>((n_tiles + 7) / 8 * 8, kMaxGrid);
+    if (lens) {  // (some frame has a lens: the kernels of kernels_warp_lens.hip)
+        launch_warp_ragged_lens(format, cubic, border, grid, c->stream, g.src, g.batch, g.n_tiles, frames, c->warp_m.d.get() + batch * 18, tile_start, dst);
+        LR_HIP(hipGetLastError());
+        return 0;
+    }
     if (border) {  // (some frame's word is not 0: the kernels of kernels_warp_border.hip)
         launch_warp_ragged_border(format, cubic, grid, c->stream, g.src, g.batch, g.n_tiles, frames, tile_start, dst);
         LR_HIP(hipGetLastError());
@@ -152,8 +192,8 @@ int launch_ragged(lr_context* c, const void* d_src, int format, bool cubic, bool
 // lr_warp_perspective_device with LR_WARP_PACKED: M is the table of 13 doubles per frame, out_width x out_height bound the
 // frames' sizes and dst_image_bytes is the size of the whole destination region
 int warp_packed(lr_context* c, const void* d_src, size_t src_image_bytes, int batch, int width, int height, size_t src_row_bytes,
-                int format, bool cubic, bool border, const double* T, void* d_dst, size_t dst_bytes, int out_width, int out_height,
-                size_t dst_row_bytes) {
+                int format, bool cubic, bool border, bool lens, const double* T, void* d_dst, size_t dst_bytes, int out_width,
+                int out_height, size_t dst_row_bytes) {
     auto fail = [](const char* what) {
         set_error(std::string("lr_warp_perspective_device: LR_WARP_PACKED: ") + what);
         return 1;
@@ -178,8 +218,10 @@ int warp_packed(lr_context* c, const void* d_src, size_t src_image_bytes, int ba
     std::vector<int> start((size_t)batch + 1);
     std::vector<std::pair<uint64_t, uint64_t>> extent((size_t)batch);  // [first byte, end)
     int64_t n_tiles = 0;
-    const size_t row_doubles = border ? 14 : 13;  // (LR_WARP_BORDER: the border word behind the row)
-    bool bordered = false;                        // some frame's word is not 0
+    const size_t lens_at = border ? 14 : 13;                // (LR_WARP_BORDER: the border word behind the row)
+    const size_t row_doubles = lens_at + (lens ? 9 : 0);    // (LR_WARP_LENS: the nine lens entries behind that)
+    bool bordered = false;                                  // some frame's word is not 0
+    std::vector<LensRecord> lenses(lens ? (size_t)batch : 0);
     for (int b = 0; b < batch; ++b) {
         const double* t = T + (size_t)b * row_doubles;
         for (int i = 0; i < 9; ++i)
@@ -212,30 +254,38 @@ int warp_packed(lr_context* c, const void* d_src, size_t src_image_bytes, int ba
             if (const char* why = parse_border_word(t[13], format, &f)) return fail_border("LR_WARP_PACKED: ", b, why);
             bordered = bordered || t[13] != 0.0;
         }
+        if (lens)
+            if (const char* why = parse_lens(t + lens_at, &lenses[(size_t)b])) return fail_lens("LR_WARP_PACKED: ", b, why);
         start[(size_t)b] = (int)n_tiles;
         n_tiles += (int64_t)f.tiles_x * (int64_t)((oh + kTileH - 1) / kTileH);
         if (n_tiles > 0x7FFFFFF0ll) return fail("output larger than 2^31 tiles of 64 x 16 pixels");
     }
     start[(size_t)batch] = (int)n_tiles;
     if (extents_overlap(extent)) return fail("two frames' extents overlap");
-    return launch_ragged(c, d_src, format, cubic, bordered, rec, start, d_dst);
+    return launch_ragged(c, d_src, format, cubic, bordered, rec, start, d_dst, any_lens(lenses) ? &lenses : nullptr);
 }
 
 // lr_warp_perspective_device with LR_WARP_RAGGED: M is the table of 18 doubles per frame, width x height and out_width x
 // out_height bound the frames' sizes, src_image_bytes and dst_image_bytes are the sizes of the two regions
 int warp_ragged(lr_context* c, const void* d_src, size_t src_bytes, int batch, int width, int height, size_t src_row_bytes,
-                int format, bool cubic, bool border, const double* T, void* d_dst, size_t dst_bytes, int out_width, int out_height,
-                size_t dst_row_bytes) {
+                int format, bool cubic, bool border, bool lens, const double* T, void* d_dst, size_t dst_bytes, int out_width,
+                int out_height, size_t dst_row_bytes) {
     std::vector<RaggedEntry> e;
     int64_t n_tiles = 0;
     // LR_WARP_BORDER: entry [17] is the frame's border word; the table's other checks see it as the 0 they ask for
+    // LR_WARP_LENS: rows of 27, the nine lens entries behind [17]; the table's checks see rows of 18
     std::vector<double> plain;
     const double* words = T;
-    if (border && T && batch >= 1) {
-        plain.assign(T, T + (size_t)batch * 18);
-        for (int b = 0; b < batch; ++b) plain[(size_t)b * 18 + 17] = 0.0;
+    const size_t row_doubles = lens ? 27 : 18;
+    if ((border || lens) && T && batch >= 1) {
+        plain.resize((size_t)batch * 18);
+        for (int b = 0; b < batch; ++b) {
+            std::memcpy(&plain[(size_t)b * 18], words + (size_t)b * row_doubles, 18 * sizeof(double));
+            if (border) plain[(size_t)b * 18 + 17] = 0.0;
+        }
         T = plain.data();
     }
+    std::vector<LensRecord> lenses(lens && batch >= 1 ? (size_t)batch : 0);
     bool bordered = false;  // some frame's word is not 0
     if (ragged_parse(d_src, src_bytes, batch, width, height, src_row_bytes, format, false, T, d_dst, dst_bytes, out_width,
                      out_height, dst_row_bytes, kTileW, kTileH, e, &n_tiles))
@@ -258,15 +308,17 @@ int warp_ragged(lr_context* c, const void* d_src, size_t src_bytes, int batch, i
         f.w = (int)s.w;
         f.h = (int)s.h;
         if (border) {
-            const double word = words[(size_t)b * 18 + 17];
+            const double word = words[(size_t)b * row_doubles + 17];
             if (const char* why = parse_border_word(word, format, &f)) return fail_border("LR_WARP_RAGGED: ", b, why);
             bordered = bordered || word != 0.0;
         }
+        if (lens)
+            if (const char* why = parse_lens(words + (size_t)b * row_doubles + 18, &lenses[(size_t)b])) return fail_lens("LR_WARP_RAGGED: ", b, why);
         start[(size_t)b] = tiles;
         tiles += f.tiles_x * (int)((s.oh + kTileH - 1) / kTileH);
     }
     start[(size_t)batch] = tiles;
-    return launch_ragged(c, d_src, format, cubic, bordered, rec, start, d_dst);
+    return launch_ragged(c, d_src, format, cubic, bordered, rec, start, d_dst, any_lens(lenses) ? &lenses : nullptr);
 }
 
 }  // namespace
@@ -354,6 +406,15 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
         if (format & LR_WARP_JPEG_DECODE) return fail("LR_WARP_BORDER together with LR_WARP_JPEG_DECODE (the decoder samples nothing)");
         format &= ~LR_WARP_BORDER;
     }
+    // LR_WARP_LENS: nine lens entries per frame at the end of its row of M; likewise of the three warps alone
+    const bool lens = (format & LR_WARP_LENS) != 0;
+    if (lens) {
+        if (format & LR_WARP_PREPARE) return fail("LR_WARP_LENS together with LR_WARP_PREPARE (the prepare step is an area average of the stored frame)");
+        if (format & LR_WARP_LINES) return fail("LR_WARP_LENS together with LR_WARP_LINES (the lines picture samples nothing)");
+        if (format & LR_WARP_JPEG) return fail("LR_WARP_LENS together with LR_WARP_JPEG (the encoder samples nothing)");
+        if (format & LR_WARP_JPEG_DECODE) return fail("LR_WARP_LENS together with LR_WARP_JPEG_DECODE (the decoder samples nothing)");
+        format &= ~LR_WARP_LENS;
+    }
     if (format & LR_WARP_JPEG_DECODE) {  // lr_decode_jpeg_device (kernels_jpeg_decode.hip): its own arguments arrive behind M
         // (LR_JPEG_ANY_SAMPLING and LR_JPEG_SCALED are the decoder's own options and travel on with the format)
         constexpr int kDecoderOptions = LR_JPEG_ANY_SAMPLING | LR_JPEG_SCALED;
@@ -387,7 +448,7 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
         const int opts = format & ~0xFF;
         if (opts & LR_WARP_PACKED) return fail("LR_WARP_RAGGED together with LR_WARP_PACKED (ragged outputs are always packed)");
         if (opts == LR_WARP_RAGGED)
-            return warp_ragged(c, d_src, src_image_bytes, batch, width, height, src_row_bytes, format & 0xFF, cubic, border, M, d_dst,
+            return warp_ragged(c, d_src, src_image_bytes, batch, width, height, src_row_bytes, format & 0xFF, cubic, border, lens, M, d_dst,
                                dst_image_bytes, out_width, out_height, dst_row_bytes);
         if (opts == (LR_WARP_RAGGED | LR_WARP_PREPARE))
             return ctx_prepare_ragged(c, d_src, src_image_bytes, batch, width, height, src_row_bytes, format & 0xFF, M, d_dst,
@@ -396,7 +457,7 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
     }
     if (format & ~0xFF) {  // option bits above the pixel format
         if ((format & ~0xFF) == LR_WARP_PACKED)
-            return warp_packed(c, d_src, src_image_bytes, batch, width, height, src_row_bytes, format & 0xFF, cubic, border, M, d_dst,
+            return warp_packed(c, d_src, src_image_bytes, batch, width, height, src_row_bytes, format & 0xFF, cubic, border, lens, M, d_dst,
                                dst_image_bytes, out_width, out_height, dst_row_bytes);
         if ((format & ~0xFF) == (LR_WARP_PACKED | LR_WARP_PREPARE)) return fail("LR_WARP_PACKED together with LR_WARP_PREPARE");
         if ((format & ~0xFF) != LR_WARP_PREPARE) return fail("unknown option bits in format");
@@ -421,19 +482,21 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
                                dst_row_bytes | (batch > 1 ? (src_image_bytes | dst_image_bytes) : 0);
         if (bits & 3u) return fail("f32 pointer or stride not 4-byte aligned");
     }
-    const size_t row_doubles = border ? 10 : 9;  // (LR_WARP_BORDER: the border word behind the map)
+    const size_t lens_at = border ? 10 : 9;               // (LR_WARP_BORDER: the border word behind the map)
+    const size_t row_doubles = lens_at + (lens ? 9 : 0);  // (LR_WARP_LENS: the nine lens entries behind that)
     for (size_t b = 0; b < (size_t)batch; ++b)
         for (size_t i = 0; i < 9; ++i)
             if (!std::isfinite(M[b * row_doubles + i])) return fail("M is not finite");
     const int64_t tiles_x = ((int64_t)out_width + kTileW - 1) / kTileW, tiles_y = ((int64_t)out_height + kTileH - 1) / kTileH;
     const int64_t n_tiles = tiles_x * tiles_y * (int64_t)batch;
     if (n_tiles > 0x7FFFFFF0ll) return fail("output larger than 2^31 tiles of 64 x 16 pixels");
-    if (border) {  // the frames as records of the table kernel; where every word is 0, the launch below as without the bit
+    if (border || lens) {  // the frames as records of the table kernel; where every word is 0 and no frame has a lens, the launch below as without the bits
         std::vector<RaggedFrame> rec((size_t)batch);
+        std::vector<LensRecord> lenses(lens ? (size_t)batch : 0);
         std::vector<int> start((size_t)batch + 1);
         bool bordered = false;
         for (int b = 0; b < batch; ++b) {
-            const double* t = M + (size_t)b * 10;
+            const double* t = M + (size_t)b * row_doubles;
             RaggedFrame& f = rec[(size_t)b];
             std::memset(&f, 0, sizeof f);
             std::memcpy(f.m, t, sizeof f.m);
@@ -446,12 +509,17 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
             f.tiles_x = (int)tiles_x;
             f.w = width;
             f.h = height;
-            if (const char* why = parse_border_word(t[9], format, &f)) return fail_border("", b, why);
-            bordered = bordered || t[9] != 0.0;
+            if (border) {
+                if (const char* why = parse_border_word(t[9], format, &f)) return fail_border("", b, why);
+                bordered = bordered || t[9] != 0.0;
+            }
+            if (lens)
+                if (const char* why = parse_lens(t + lens_at, &lenses[(size_t)b])) return fail_lens("", b, why);
             start[(size_t)b] = (int)(tiles_x * tiles_y * b);
         }
         start[(size_t)batch] = (int)n_tiles;
-        if (bordered) return launch_ragged(c, d_src, format, cubic, true, rec, start, d_dst);
+        const bool lensed = any_lens(lenses);
+        if (bordered || lensed) return launch_ragged(c, d_src, format, cubic, bordered, rec, start, d_dst, lensed ? &lenses : nullptr);
     }
 
     LR_HIP(hipSetDevice(c->device));

@@ -1,7 +1,8 @@
 // The lane body of the perspective warp, shared by its two translation units: kernels_warp.hip (the kernels of a call without
 // LR_WARP_BORDER and all host code) and kernels_warp_border.hip (the kernels with a border rule per frame).  The bordered
 // kernels are a code object of their own, so that the one kernels_warp.hip makes holds exactly the kernels it held before them.
-// Everything here has internal linkage; what kernels_warp.hip says about tiles, records and loads holds for both.
+// kernels_warp_lens.hip (the kernels with a lens model per frame, LR_WARP_LENS) is a third of the same kind.
+// Everything here has internal linkage; what kernels_warp.hip says about tiles, records and loads holds for all of them.
 #pragma once
 #include <cstdint>
 
@@ -16,6 +17,11 @@ namespace lramd {
 // array of RaggedFrame records
 void launch_warp_ragged_border(int format, bool cubic, int grid, hipStream_t stream, const uint8_t* src, int batch, int n_tiles,
                                const void* frames, const int* start, uint8_t* dst);
+
+// warp_ragged_lens_kernel's launch (kernels_warp_lens.hip): the same arguments, `lenses` the device array of LensRecord
+// records, one per frame; `border`: with the records' border rules
+void launch_warp_ragged_lens(int format, bool cubic, bool border, int grid, hipStream_t stream, const uint8_t* src, int batch,
+                             int n_tiles, const void* frames, const void* lenses, const int* start, uint8_t* dst);
 
 namespace {
 
@@ -47,6 +53,15 @@ struct RaggedFrame {
 };
 static_assert(sizeof(RaggedFrame) == 18 * sizeof(double), "a record per 18 doubles of the mirror");
 
+// LR_WARP_LENS: a frame's lens, the nine doubles of its table row (fx, fy, cx, cy, k1, k2, p1, p2, k3), and whether any of
+// the five coefficients is not zero; a frame without one is warped by the plain rule
+struct LensRecord {
+    double fx, fy, cx, cy, k1, k2, p1, p2, k3;
+    int has_lens;
+    int pad;
+};
+static_assert(sizeof(LensRecord) == 10 * sizeof(double), "a record per 10 doubles of the mirror");
+
 struct RaggedArgs {
     const uint8_t* src;
     int batch, n_tiles;
@@ -64,18 +79,44 @@ struct Taps {
     int w00, w01, w10, w11;  // weights of (ix, iy), (ix+1, iy), (ix, iy+1), (ix+1, iy+1); they sum to 1024
 };
 
-// the 5-bit fixed-point source coordinates of destination pixel (x, y): both sampling rules start from them
-__device__ __forceinline__ void fixed_xy(const double* __restrict__ m, unsigned x, unsigned y, int& X, int& Y) {
+// LR_WARP_LENS (tests/numpy_warp_lens_ref.py): the displacement, in 1/32 pixels, that the
+// frame's lens adds to the ideal point (U, V) (1/32 pixels as well), every operation rounded on its own.  The two divisions
+// stay divisions: the rule says so, and a reciprocal would round differently.
+__device__ __forceinline__ void lens_displace(const LensRecord* __restrict__ l, double& U, double& V) {
+    const double a = (U * 0.03125 - l->cx) / l->fx, b = (V * 0.03125 - l->cy) / l->fy;
+    const double aa = a * a, bb = b * b, ab = a * b;
+    const double r2 = aa + bb;
+    const double rad = r2 * (l->k1 + r2 * (l->k2 + r2 * l->k3));
+    const double ta = (2.0 * l->p1) * ab + l->p2 * (r2 + 2.0 * aa);
+    const double tb = l->p1 * (r2 + 2.0 * bb) + (2.0 * l->p2) * ab;
+    const double du = l->fx * (a * rad + ta), dv = l->fy * (b * rad + tb);
+    U = U + 32.0 * du;
+    V = V + 32.0 * dv;
+}
+
+// the 5-bit fixed-point source coordinates of destination pixel (x, y): both sampling rules start from them; kLens: through the
+// frame's lens (`lens`, uniform across the workgroup like m) where it has one
+template <bool kLens = false>
+__device__ __forceinline__ void fixed_xy(const double* __restrict__ m, unsigned x, unsigned y, int& X, int& Y,
+                                         const LensRecord* __restrict__ lens = nullptr) {
     const double xd = (double)x, yd = (double)y;
     const double W0 = (m[6] * xd + m[7] * yd) + m[8];
     const double Wq = W0 != 0.0 ? 32.0 / W0 : 0.0;
-    X = fixed_coord(((m[0] * xd + m[1] * yd) + m[2]) * Wq);
-    Y = fixed_coord(((m[3] * xd + m[4] * yd) + m[5]) * Wq);
+    if constexpr (kLens) {
+        double U = ((m[0] * xd + m[1] * yd) + m[2]) * Wq, V = ((m[3] * xd + m[4] * yd) + m[5]) * Wq;
+        if (lens->has_lens) lens_displace(lens, U, V);
+        X = fixed_coord(U);
+        Y = fixed_coord(V);
+    } else {
+        X = fixed_coord(((m[0] * xd + m[1] * yd) + m[2]) * Wq);
+        Y = fixed_coord(((m[3] * xd + m[4] * yd) + m[5]) * Wq);
+    }
 }
 
-__device__ __forceinline__ Taps taps_of(const double* __restrict__ m, unsigned x, unsigned y) {
+template <bool kLens = false>
+__device__ __forceinline__ Taps taps_of(const double* __restrict__ m, unsigned x, unsigned y, const LensRecord* __restrict__ lens = nullptr) {
     int X, Y;
-    fixed_xy(m, x, y, X, Y);
+    fixed_xy<kLens>(m, x, y, X, Y, lens);
     Taps t;
     t.ix = X >> 5;
     t.iy = Y >> 5;
@@ -217,10 +258,11 @@ __device__ __forceinline__ uint32_t load_tap(const uint8_t* row, int cx) {
 // they come in as in the unbordered rule (paired loads); otherwise the constant border gives `value` for a tap outside and
 // the other modes map the two columns and the two rows once (border_index) and read the four pixels they name.  `mode` is the
 // frame's and uniform across the workgroup.  Result as cubic_pixel's.
-template <int kFormat>
+template <int kFormat, bool kLens = false>
 __device__ __forceinline__ void border_linear_pixel(const double* m, const uint8_t* src, size_t src_row_bytes, int w, int h,
-                                                    unsigned x, unsigned y, int mode, uint32_t value, uint32_t& px, float& pf) {
-    const Taps t = taps_of(m, x, y);
+                                                    unsigned x, unsigned y, int mode, uint32_t value, uint32_t& px, float& pf,
+                                                    const LensRecord* lens = nullptr) {
+    const Taps t = taps_of<kLens>(m, x, y, lens);
     uint32_t v[4];  // (ix, iy), (ix + 1, iy), (ix, iy + 1), (ix + 1, iy + 1), in border_tap's form
     if (t.ix >= 0 && t.ix + 1 < w && t.iy >= 0 && t.iy + 1 < h) {  // (|ix|, |iy| <= 2^26: no overflow)
         const uint8_t* row0 = src + (size_t)t.iy * src_row_bytes;
@@ -313,13 +355,13 @@ __device__ __forceinline__ void border_row_taps(const uint8_t* row, bool row_in,
 // Everything fits int32: max sum |C[a]| is 2816 and 255 * 2816^2 + 2^21 = 2 024 210 432 < 2^31.  f32: weights C / 2048.f
 // (exact), rows and then the column summed from the first tap to the last, every product and sum rounded on its own.
 // kBorder: a row's taps come through border_row_taps (the frame's `mode` and `value`); without it the two arguments are unused.
-template <int kFormat, bool kBorder>
+template <int kFormat, bool kBorder, bool kLens = false>
 __device__ __forceinline__ void cubic_pixel(const double* m, const uint8_t* src, size_t src_row_bytes, int w, int h, unsigned x,
-                                            unsigned y, int mode, uint32_t value, uint32_t& px, float& pf) {
+                                            unsigned y, int mode, uint32_t value, uint32_t& px, float& pf, const LensRecord* lens = nullptr) {
     constexpr int kBpp = PixelBytes<kFormat>::value;
     constexpr int kChannels = kFormat == LR_PIX_U8X3 ? 3 : 1;
     int X, Y;
-    fixed_xy(m, x, y, X, Y);
+    fixed_xy<kLens>(m, x, y, X, Y, lens);
     const int ix = X >> 5, iy = Y >> 5;
     const int16_t* cx = kCubicWeights[X & 31];
     const int16_t* cy = kCubicWeights[Y & 31];
@@ -388,10 +430,12 @@ __device__ __forceinline__ void cubic_pixel(const double* m, const uint8_t* src,
 
 // One lane's four consecutive pixels (x0 .. x0 + 3, those below ow) of destination row y, whose first byte is `out`;
 // kCubic: sampled by the bicubic rule above instead of the bilinear one; kBorder: with the frame's border rule (`mode`,
-// `value`: LR_WARP_BORDER) instead of the constant zero one, which with kBorder false is the parent's code and ignores both
-template <int kFormat, bool kCubic, bool kBorder>
+// `value`: LR_WARP_BORDER) instead of the constant zero one, which with kBorder false is the parent's code and ignores both;
+// kLens: the coordinates go through the frame's lens (`lens`: LR_WARP_LENS), which with kLens false is never looked at
+template <int kFormat, bool kCubic, bool kBorder, bool kLens = false>
 __device__ __forceinline__ void warp_lane(const double* m, const uint8_t* src, size_t src_row_bytes, int w, int h,
-                                          uint8_t* out, int ow, unsigned x0, unsigned y, int mode = 0, uint32_t value = 0) {
+                                          uint8_t* out, int ow, unsigned x0, unsigned y, int mode = 0, uint32_t value = 0,
+                                          const LensRecord* lens = nullptr) {
     const int n = min(4, ow - (int)x0);  // pixels of this lane inside the row
 
     uint32_t res_u8 = 0;          // LR_PIX_U8: four bytes
@@ -401,8 +445,8 @@ __device__ __forceinline__ void warp_lane(const double* m, const uint8_t* src, s
     for (int k = 0; k < 4; ++k) {
         if (kCubic || kBorder) {
             uint32_t px;
-            if constexpr (kCubic) cubic_pixel<kFormat, kBorder>(m, src, src_row_bytes, w, h, x0 + (unsigned)k, y, mode, value, px, res_f[k]);
-            else border_linear_pixel<kFormat>(m, src, src_row_bytes, w, h, x0 + (unsigned)k, y, mode, value, px, res_f[k]);
+            if constexpr (kCubic) cubic_pixel<kFormat, kBorder, kLens>(m, src, src_row_bytes, w, h, x0 + (unsigned)k, y, mode, value, px, res_f[k], lens);
+            else border_linear_pixel<kFormat, kLens>(m, src, src_row_bytes, w, h, x0 + (unsigned)k, y, mode, value, px, res_f[k], lens);
             if (kFormat == LR_PIX_U8) res_u8 |= px << (8 * k);
             if (kFormat == LR_PIX_U8X3) {
 #pragma unroll
@@ -413,7 +457,7 @@ __device__ __forceinline__ void warp_lane(const double* m, const uint8_t* src, s
             }
             continue;
         }
-        const Taps t = taps_of(m, x0 + (unsigned)k, y);
+        const Taps t = taps_of<kLens>(m, x0 + (unsigned)k, y, lens);
         const bool in0 = inside(t.iy, h), in1 = inside(t.iy + 1, h);
         const uint8_t* row0 = src + (size_t)(in0 ? t.iy : 0) * src_row_bytes;
         const uint8_t* row1 = src + (size_t)(in1 ? t.iy + 1 : 0) * src_row_bytes;
