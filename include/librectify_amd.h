@@ -603,9 +603,12 @@ static inline size_t lr_jpeg_bound(int width, int height, int format, int layout
  * or for a frame whose entry [7] is 1 the orientation that was read, 1..8.
  * Status: 0 decoded; 1 not a JPEG stream, or truncated before SOS; 2 unsupported (progressive, arithmetic, lossless or
  * hierarchical coding, 12-bit precision, 16-bit quantisation tables, component counts other than 1 or 3, another sampling,
- * a non-interleaved or multi-scan file, a missing table: lr_last_error tells which, for the last such frame); 3 the
+ * a non-interleaved or multi-scan file, a missing table, a file that is RGB and not YCbCr by libjpeg's rule -- no JFIF segment,
+ * and an Adobe APP14 segment with transform 0 or, without an Adobe segment, the component ids 'R', 'G', 'B': lr_last_error tells which, for
+ * the last such frame); 3 the
  * table's [4] [5] differ from the stream's size; 4 the scan is damaged (an invalid code, a coefficient index beyond 63,
- * fewer or more MCUs than the frame has, a missing or misnumbered RSTm).  Per-frame failures are statuses, not failures of
+ * fewer or more MCUs than the frame has, a missing or misnumbered RSTm, padding in front of an RSTm that is not 1-bits
+ * (T.81 F.1.2.3); in front of EOI any padding is taken).  Per-frame failures are statuses, not failures of
  * the call: a frame of status 1 to 3 is skipped on the host and no byte of its extent is written; of one of status 4 the
  * extent's content is unspecified; nothing outside the frames' extents is ever written, and the call returns 0.
  * Accepted: SOF0 or SOF1 with 8-bit samples, Huffman-coded, one interleaved scan, any DHT (table ids 0..3), any DRI or none,

@@ -13,7 +13,11 @@
 //                  host launches rounds until one in which no lane decoded: then every part's entry state is its
 //                  predecessor's exit state -- a verified fixed point, and with the first part true the decode is the
 //                  sequential one by induction, whatever the guesses were.  Huffman codes synchronise by themselves within
-//                  a few symbols, so three launches are the rule.  An RSTm met by the bit reader byte-aligns and resets.
+//                  a few symbols, so three launches are the rule.  (For a scan that never does, such as
+//                  tests/jpeg_stream_cases.py's no_resync, the text above gives one launch per workgroup of its parts and
+//                  one more that finds nothing to do; the call does not report its launches, so this is derived, not
+//                  measured.)  An RSTm met by the bit reader
+//                  byte-aligns and resets.
 //   2. place       A workgroup per frame: the prefix sum of the parts' block counts gives every part its first block; the
 //                  totals (blocks, markers) and the most decodes of any part go back to the host.
 //   3. write       Step 1's decode once more from the final entry states, the coefficients now stored (int16, natural
@@ -180,7 +184,10 @@ struct Reader {
         for (int i = 0; i < n; ++i) v = (v << 1) | bit();
         return v;
     }
-    // at an MCU's end: what is left of the byte is padding if it is all ones and a marker or the end follows
+    // at an MCU's end: what is left of the byte is padding if it is all ones and a marker or the end follows.  Any other
+    // padding is read as the start of a symbol: in front of EOI that symbol runs over the end and is none (any padding is
+    // taken there), in front of an RSTm it runs into the marker: damage (T.81 F.1.2.3 asks for 1-bits, and only 1-bits are
+    // never a code, which is what a lane that enters on a guess needs; docs/jpeg_decode_bounds.md, "Padding").
     __device__ __forceinline__ void skip_padding() {
         if (off == 0 || k >= len) return;
         const uint32_t mask = (1u << (8 - off)) - 1u;
@@ -797,6 +804,8 @@ void read_header(const uint8_t* d, size_t n, bool any, Header& hd) {
     const uint8_t* seg = nullptr;
     size_t seg_len = 0;
     bool have_exif = false;
+    bool have_jfif = false;
+    int adobe = -1;  // the transform byte of the last Adobe APP14, -1: none
     for (;;) {
         if (p >= n) return fail(kNotJpeg, "truncated before SOS");
         if (d[p] != 0xFF) return fail(kNotJpeg, "no marker where one is due");
@@ -853,6 +862,10 @@ void read_header(const uint8_t* d, size_t n, bool any, Header& hd) {
                 have_exif = true;
                 hd.orientation = exif_orientation(seg + 6, seg_len - 6);
             }
+        } else if (m == 0xE0) {
+            if (seg_len >= 5 && std::memcmp(seg, "JFIF\0", 5) == 0) have_jfif = true;
+        } else if (m == 0xEE) {
+            if (seg_len >= 12 && std::memcmp(seg, "Adobe", 5) == 0) adobe = seg[11];
         } else if (m == 0xDA) {
             break;
         }
@@ -865,6 +878,12 @@ void read_header(const uint8_t* d, size_t n, bool any, Header& hd) {
     if (hd.w < 1 || hd.h < 1) return fail(kUnsupported, "a size of 0 (DNL)");
     hd.comps = nc;
     if (nc != 1 && nc != 3) return fail(kUnsupported, std::to_string(nc) + " components");
+    // libjpeg's rule for three components (default_decompress_parms): a JFIF segment says YCbCr; else an Adobe segment
+    // decides (transform 0: RGB); else the ids 'R', 'G', 'B' say RGB.  The output pass knows YCbCr's colour rule alone: an
+    // RGB file is refused.
+    if (nc == 3 && !have_jfif && adobe == 0) return fail(kUnsupported, "an RGB file (Adobe segment with transform 0 and no JFIF segment)");
+    if (nc == 3 && !have_jfif && adobe < 0 && sof[6] == 'R' && sof[9] == 'G' && sof[12] == 'B')
+        return fail(kUnsupported, "an RGB file (component ids 'R', 'G', 'B' and neither a JFIF nor an Adobe segment)");
     if (nc == 3) {
         const int y = sof[7], cb = sof[10], cr = sof[13];
         const bool known = cb == 0x11 && cr == 0x11 && (y == 0x22 || y == 0x11 || y == 0x21);

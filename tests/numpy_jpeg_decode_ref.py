@@ -50,6 +50,7 @@ def probe(data, expect=None):
     if n < 4 or d[0] != 0xFF or d[1] != 0xD8:
         return fail(NOT_JPEG, "no SOI")
     qt, ht, sof, p = {}, {}, None, 2
+    jfif, adobe = False, None  # a JFIF APP0 was seen; the transform byte of the last Adobe APP14
     while True:
         if p >= n:
             return fail(NOT_JPEG, "truncated before SOS")
@@ -112,6 +113,10 @@ def probe(data, expect=None):
             if m == 0xC2:
                 return fail(UNSUPPORTED, "progressive (SOF2)")
             return fail(UNSUPPORTED, "arithmetic, lossless or hierarchical coding (SOF%d)" % (m - 0xC0))
+        elif m == 0xE0 and seg[:5] == b"JFIF\0":
+            jfif = True
+        elif m == 0xEE and len(seg) >= 12 and seg[:5] == b"Adobe":
+            adobe = seg[11]
         elif m == 0xDA:
             break
     if sof is None:
@@ -125,6 +130,13 @@ def probe(data, expect=None):
         info.components = nc
         return fail(UNSUPPORTED, "%d components" % nc)
     info.components = nc
+    # libjpeg's rule for three components (default_decompress_parms): a JFIF segment says YCbCr; else an Adobe segment
+    # decides (transform 0: RGB); else the ids 'R', 'G', 'B' say RGB.  The colour rule here is YCbCr's alone, so an RGB file
+    # is refused, not decoded into wrong colours.
+    if nc == 3 and not jfif and adobe == 0:
+        return fail(UNSUPPORTED, "an RGB file (Adobe segment with transform 0 and no JFIF segment)")
+    if nc == 3 and not jfif and adobe is None and [sof[6], sof[9], sof[12]] == [0x52, 0x47, 0x42]:
+        return fail(UNSUPPORTED, "an RGB file (component ids 'R', 'G', 'B' and neither a JFIF nor an Adobe segment)")
     comps = [(sof[6 + 3 * i], sof[7 + 3 * i] >> 4, sof[7 + 3 * i] & 15, sof[8 + 3 * i]) for i in range(nc)]
     if nc == 1:
         info.layout = 0
@@ -302,6 +314,11 @@ def coefficients(info, data):
                 pos, pred[comp] = got
         if not last and n - pos >= 8:
             return DAMAGED, out  # whole bytes of data where the interval's end is due
+        if not last and n > pos and win[pos] >> (16 - (n - pos)) != (1 << (n - pos)) - 1:
+            # In front of an RSTm the padding is 1-bits (T.81 F.1.2.3).  Only 1-bits are never a code, so only they tell a
+            # decoder that starts in the middle of the scan that the interval has ended: any other padding is damage.  In
+            # front of EOI any padding is taken (the symbol it begins runs over the end).
+            return DAMAGED, out
         if last and block(win, n, pos, comp_of[0], scratch, 0) is not SHORT:
             return DAMAGED, out  # behind the last MCU one more whole block (more MCUs than the frame has), or no code
     return OK, out
