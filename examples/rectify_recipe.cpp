@@ -7,7 +7,7 @@
 //   rectify_recipe in.pgm|in.ppm out_prefix [--max-size N|fraction] [--refine] [--threads N]
 //                  [--h-strategy rotate_h|rotate_v|rectify|keep] [--v-strategy ...] [--warp] [--device-prepare] [--lines]
 //                  [--jpeg Q] [--optimize] [--jpeg-in] [--orient] [--any-sampling] [--scale N] [--cubic] [--border MODE[:VALUE]] [--crop]
-//                  [--lens fx,fy,cx,cy,k1,k2,p1,p2,k3]
+//                  [--lens fx,fy,cx,cy,k1,k2,p1,p2,k3] [--out-max N]
 //
 // Input is a binary PGM (P5, 8 bit) or PPM (P6, 8 bit; converted with the usual integer luma weights
 // (4899 R + 9617 G + 1868 B + 8192) >> 14).  Image decoding stays with the caller's imaging library.
@@ -46,6 +46,9 @@
 // source's aspect that holds no border; the margin follows --cubic); the segments of --lines are drawn through the crop's H.
 // --cubic (with --warp or --jpeg alone; it implies neither): the warp samples 4 x 4 bicubic, cv::warpPerspective's INTER_CUBIC
 // (LR_WARP_CUBIC or-ed into the warp's format word), instead of bilinear.  Everything else is as without it.
+// --out-max N (with --warp or --jpeg alone): the rectified picture is at most N pixels on its longer side -- lr_shrink_homography
+// gives the map, the size and the sampling factor S, and the warp averages S x S samples per pixel (LR_WARP_AREA): shrunk without
+// aliasing in the one resampling there is; applied after --crop, and the segments of --lines are drawn through the small picture's H.
 // --lens fx,fy,cx,cy,k1,k2,p1,p2,k3 (with --warp or --jpeg alone; not with --crop): the frame's camera matrix and distortion
 // vector, OpenCV's, in the pixel units of the frame as read (LR_WARP_LENS).  One warp with the identity map and the lens writes
 // the frame without its distortion; prescale, detector and the CSV files work on that one, so segments and transform are in
@@ -296,10 +299,11 @@ struct Border {
     unsigned v[3] = {0, 0, 0};
 };
 
-// lens: --lens's nine entries, or null; they travel behind the border word (LR_WARP_LENS).
+// lens: --lens's nine entries, or null; they travel behind the border word (LR_WARP_LENS).  out_max: --out-max's bound, or 0;
+// the sampling factor travels at the very end (LR_WARP_AREA), and H, ow, oh are the small picture's.
 bool warp_frame(const Gray& g, const ImageTransform& t, const std::string& prefix, std::vector<uint8_t>& out, int& ow, int& oh,
-                double* H, int jpeg, bool optimize, bool cubic, const Border* border, bool crop, const double* lens) {
-    double M[19];  // (the tenth: the border word of LR_WARP_BORDER; the last nine: the lens of LR_WARP_LENS)
+                double* H, int jpeg, bool optimize, bool cubic, const Border* border, bool crop, const double* lens, int out_max) {
+    double M[20];  // (the tenth: the border word of LR_WARP_BORDER; then nine: the lens of LR_WARP_LENS; the last: LR_WARP_AREA's S)
     lr_context* ctx = nullptr;
     void* d_src = nullptr;
     void* d_dst = nullptr;
@@ -325,6 +329,17 @@ bool warp_frame(const Gray& g, const ImageTransform& t, const std::string& prefi
     if (lens) {
         std::memcpy(M + (border ? 10 : 9), lens, 9 * sizeof(double));
         options |= LR_WARP_LENS;
+    }
+    if (ok && out_max > 0) {
+        int S = 1;
+        const int full_w = ow, full_h = oh;
+        if (lr_shrink_homography(H, M, ow, oh, out_max, H, M, &ow, &oh, &S) != 0) {
+            std::fprintf(stderr, "warp failed: lr_shrink_homography refused the picture\n");
+            return false;
+        }
+        std::printf("out-max %d: %dx%d written as %dx%d, %d x %d samples per pixel\n", out_max, full_w, full_h, ow, oh, S, S);
+        M[9 + (border ? 1 : 0) + (lens ? 9 : 0)] = (double)S;
+        options |= LR_WARP_AREA;
     }
     ok = ok && lr_context_create(0, &ctx) == 0;
     if (ok) {
@@ -489,7 +504,7 @@ int main(int argc, char** argv) {
                      "          [--h-strategy rotate_h|rotate_v|rectify|keep] [--v-strategy ...] [--warp] [--device-prepare]\n"
                      "          [--lines] [--jpeg Q] [--optimize] [--jpeg-in] [--orient] [--any-sampling] [--scale 1|2|4|8]\n"
                      "          [--cubic] [--border constant|replicate|reflect|reflect101[:VALUE]] [--crop]\n"
-                     "          [--lens fx,fy,cx,cy,k1,k2,p1,p2,k3]\n",
+                     "          [--lens fx,fy,cx,cy,k1,k2,p1,p2,k3] [--out-max N]\n",
                      argv[0]);
         return 2;
     }
@@ -498,7 +513,7 @@ int main(int argc, char** argv) {
     bool optimize = false, bordered = false, crop = false, lensed = false;
     Border border;
     double lens[9];
-    int threads = -1, jpeg = 0, decode_scale = 0;
+    int threads = -1, jpeg = 0, decode_scale = 0, out_max = 0;
     RectificationConfig cfg;
     cfg.horizontal_vp_min_distance = 2;  // autorectify.cpp:347
     for (int i = 3; i < argc; ++i) {
@@ -524,6 +539,7 @@ int main(int argc, char** argv) {
             lensed = true;
             ++i;
         }
+        else if (a == "--out-max" && has_val && std::atoi(argv[i + 1]) >= 1) out_max = std::atoi(argv[++i]);
         else if (a == "--max-size" && has_val) max_size = (float)std::atof(argv[++i]);
         else if (a == "--threads" && has_val) threads = std::atoi(argv[++i]);
         else if (a == "--jpeg" && has_val && std::atoi(argv[i + 1]) >= 1 && std::atoi(argv[i + 1]) <= 100) {
@@ -563,6 +579,10 @@ int main(int argc, char** argv) {
     }
     if (lensed && (!warp || crop)) {
         std::fprintf(stderr, "--lens goes with --warp or --jpeg and not with --crop: the crop's rectangle assumes straight source edges\n");
+        return 2;
+    }
+    if (out_max && !warp) {
+        std::fprintf(stderr, "--out-max goes with --warp or --jpeg: it bounds the rectified picture's size and implies neither\n");
         return 2;
     }
     Gray full;
@@ -621,7 +641,7 @@ int main(int argc, char** argv) {
     std::vector<uint8_t> warped;
     int ow = 0, oh = 0;
     double H[9];
-    bool ok = !warp || warp_frame(full, t, prefix, warped, ow, oh, H, jpeg, optimize, cubic, bordered ? &border : nullptr, crop, lensed ? lens : nullptr);
+    bool ok = !warp || warp_frame(full, t, prefix, warped, ow, oh, H, jpeg, optimize, cubic, bordered ? &border : nullptr, crop, lensed ? lens : nullptr, out_max);
     if (ok && lines_pictures) {  // on the gray frame, as the demo draws (autorectify.cpp:364)
         std::vector<uint8_t> gray(seen.px.size());
         for (size_t i = 0; i < gray.size(); ++i) gray[i] = (uint8_t)(seen.px[i] * 256.0f);

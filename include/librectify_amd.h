@@ -339,6 +339,104 @@ enum lr_border_mode { LR_BORDER_CONSTANT = 0, LR_BORDER_REPLICATE = 1, LR_BORDER
  * on what the call without the bit rejects, a non-finite entry among the nine, fx <= 0 or fy <= 0, and together with
  * LR_WARP_PREPARE, LR_WARP_LINES, LR_WARP_JPEG or LR_WARP_JPEG_DECODE.  Without the bit nothing changes. */
 enum lr_warp_lens { LR_WARP_LENS = 0x100000 }; /* or-ed into `format` like lr_warp_option */
+/* LR_WARP_AREA makes the warp an area-sampled one: every destination pixel is the mean of S x S samples spread over its own
+ * footprint, so that a warp which SHRINKS (a bounded-size rectified picture: lr_shrink_homography below) does not alias.  One
+ * resampling: the stored frame is read once and only the small picture is written.  It is an option of the three warps and of
+ * nothing else, with or without LR_WARP_CUBIC, LR_WARP_BORDER and LR_WARP_LENS, for u8, u8x3 and f32.  With the bit every
+ * frame's row of the host table M carries ONE more double at its very end, behind the border word and the nine lens entries
+ * where they exist: the frame's sampling factor S, an integer from 1 to 8.  Rows are then
+ *   fmt | LR_WARP_AREA                    10 / 11 / 19 / 20 doubles per frame (alone / BORDER / LENS / both);
+ *   fmt | LR_WARP_PACKED | LR_WARP_AREA   14 / 15 / 23 / 24;
+ *   fmt | LR_WARP_RAGGED | LR_WARP_AREA   19 / 28 (without / with LENS; the border word stays entry [17]).
+ * Frames with different S mix in one launch.  Arithmetic (tests/numpy_warp_area_ref.py restates it):
+ *   1. the fine map F = lr_area_fine_map(M, S), on the host in double: the destination-to-source map of a picture S times as
+ *      large, whose pixel (S x + i, S y + j) is sub-sample (i, j) of destination pixel (x, y), at ((i + 0.5) / S - 0.5,
+ *      (j + 0.5) / S - 0.5) from the pixel's centre;
+ *   2. sub-sample v(i, j), i, j = 0 .. S - 1, is exactly what the call without the bit gives for pixel (S x + i, S y + j)
+ *      under the map F: the frame's lens, the 5-bit coordinates, the bilinear or bicubic taps and weights, the frame's border
+ *      rule and the per-sample rounding to a byte (u8, u8x3) or a float (f32);
+ *   3. u8 and u8x3, per channel: s = the sum of the S^2 bytes, out = (2 s + S^2) / (2 S^2) in integers (round half up);
+ *      f32: acc = 0.0f; for j from 0, for i from 0: acc = acc + v(i, j), every sum rounded to float; out = acc / (float)(S * S);
+ *   4. a frame with S = 1 is by definition warped by the plain rule: byte for byte (f32: bit for bit) the frame of the call
+ *      without the bit.
+ * So a frame's picture is the S x S box mean of the warp without the bit, map F, into S out_width x S out_height; for the pure
+ * shrink M = [[S, 0, (S - 1) / 2], [0, S, (S - 1) / 2], [0, 0, 1]] F is the identity and the picture the rounded S x S box mean
+ * of the source (cv::resize's INTER_AREA for an integer factor).  Fails cleanly (nothing launched, nothing written,
+ * lr_last_error names the frame and the reason) on what the call without the bit rejects, an S that is not an integer from 1 to
+ * 8, S * out_width_b or S * out_height_b above 2^31 - 1, and together with LR_WARP_PREPARE, LR_WARP_LINES, LR_WARP_JPEG or
+ * LR_WARP_JPEG_DECODE.  Without the bit nothing changes: rows keep their lengths and every call gives what it gave. */
+enum lr_warp_area { LR_WARP_AREA = 0x400000 }; /* or-ed into `format` like lr_warp_option */
+
+/* LR_WARP_AREA's fine map F (9 doubles; F may be M) of the map M and the sampling factor S, for k = 0, 1, 2:
+ *   F[k][0] = M[k][0] / S;   F[k][1] = M[k][1] / S;   F[k][2] = M[k][2] - ((M[k][0] + M[k][1]) * (double)(S - 1)) / (double)(2 S)
+ * Host arithmetic only, every operation rounded on its own (-ffp-contract=off); operation for operation the Python package's
+ * area_fine_map and what the library computes per frame. */
+static inline void lr_area_fine_map(const double* M, int S, double* F) {
+    int k;
+    for (k = 0; k < 3; ++k) {
+        const double m0 = M[3 * k], m1 = M[3 * k + 1], m2 = M[3 * k + 2];
+        F[3 * k] = m0 / (double)S;
+        F[3 * k + 1] = m1 / (double)S;
+        F[3 * k + 2] = m2 - ((m0 + m1) * (double)(S - 1)) / (double)(2 * S);
+    }
+}
+
+/* A rectified picture of bounded size: the map, the size and the sampling factor with which LR_WARP_AREA writes the picture of
+ * (H, M, out_width x out_height) -- what lr_rectification_homography or lr_crop_homography returned -- at no more than
+ * max_size pixels on its longer side.  Host arithmetic only, in double; a static inline because the export table is full.
+ * With L = max(out_width, out_height): if L <= max_size nothing changes and S = 1.  Otherwise
+ *   w' = max(1, (out_width * max_size) / L) in 64-bit integers, h' likewise;  sx = out_width / (double)w', sy likewise;
+ *   tx = (sx - 1) / 2, ty = (sy - 1) / 2;
+ *   M_out[k][0] = M[k][0] * sx;  M_out[k][1] = M[k][1] * sy;  M_out[k][2] = M[k][2] + (M[k][0] * tx + M[k][1] * ty);
+ *   H_out = diag(1 / sx, 1 / sy, 1) T(-tx, -ty) H:  H_out[0][i] = (H[0][i] - tx * H[2][i]) / sx,  H_out[1][i] = (H[1][i] - ty *
+ *   H[2][i]) / sy,  H_out[2][i] = H[2][i] (H_out[8] stays 1);   S = min(8, ceil(max(sx, sy))).
+ * Destination pixel (x, y) of the small picture covers the pixels [sx x, sx (x + 1)) x [sy y, sy (y + 1)) of the large one.
+ * H or M may be NULL (not both), and so may any output pointer; H_out may be H and M_out may be M.  Compiled without
+ * floating-point contraction it is, operation for operation, the Python package's shrink_homography.  Returns 0, or 1 with
+ * nothing written: a non-finite entry of H or M, H and M both NULL, or a size or max_size below 1. */
+static inline int lr_shrink_homography(const double* H, const double* M, int out_width, int out_height, int max_size, double* H_out,
+                                       double* M_out, int* new_width, int* new_height, int* S) {
+    int i, k, longer, nw = out_width, nh = out_height, s = 1;
+    double sx = 1.0, sy = 1.0, tx, ty, top, h[9], m[9];
+    if ((!H && !M) || out_width < 1 || out_height < 1 || max_size < 1) return 1;
+    for (i = 0; i < 9; ++i)
+        if ((H && !(H[i] - H[i] == 0.0)) || (M && !(M[i] - M[i] == 0.0))) return 1; /* (x - x is 0 for finite x alone) */
+    for (i = 0; i < 9; ++i) {
+        h[i] = H ? H[i] : 0.0;
+        m[i] = M ? M[i] : 0.0;
+    }
+    longer = out_width > out_height ? out_width : out_height;
+    if (longer > max_size) {
+        nw = (int)(((long long)out_width * (long long)max_size) / (long long)longer);
+        nh = (int)(((long long)out_height * (long long)max_size) / (long long)longer);
+        if (nw < 1) nw = 1;
+        if (nh < 1) nh = 1;
+        sx = (double)out_width / (double)nw;
+        sy = (double)out_height / (double)nh;
+        tx = (sx - 1.0) / 2.0;
+        ty = (sy - 1.0) / 2.0;
+        for (i = 0; i < 3; ++i) {
+            h[i] = (h[i] - tx * h[6 + i]) / sx;
+            h[3 + i] = (h[3 + i] - ty * h[6 + i]) / sy;
+        }
+        for (k = 0; k < 3; ++k) {
+            const double m0 = m[3 * k], m1 = m[3 * k + 1];
+            m[3 * k] = m0 * sx;
+            m[3 * k + 1] = m1 * sy;
+            m[3 * k + 2] = m[3 * k + 2] + (m0 * tx + m1 * ty);
+        }
+        top = ceil(sx > sy ? sx : sy);
+        s = top < 8.0 ? (int)top : 8;
+    }
+    if (H && H_out)
+        for (i = 0; i < 9; ++i) H_out[i] = h[i];
+    if (M && M_out)
+        for (i = 0; i < 9; ++i) M_out[i] = m[i];
+    if (new_width) *new_width = nw;
+    if (new_height) *new_height = nh;
+    if (S) *S = s;
+    return 0;
+}
 
 /* The lens model on the host: the pixel (*ud, *vd) of the stored photograph that shows the ideal point (u, v); lens: the nine
  * entries above.  The same operations in the same order as LR_WARP_LENS's rule with U = 32 u and V = 32 v, returning

@@ -92,6 +92,7 @@ WARP_JPEG_DECODE = 0x4000  # enum lr_warp_jpeg_decode, likewise: lr_decode_jpeg_
 WARP_BORDER = 0x40000  # enum lr_warp_border, likewise: a border word per frame in the warp's table (border_word, border= of the tables)
 BORDER_CONSTANT, BORDER_REPLICATE, BORDER_REFLECT, BORDER_REFLECT_101 = 0, 1, 2, 4  # enum lr_border_mode: OpenCV's numbers
 WARP_LENS = 0x100000  # enum lr_warp_lens, likewise: nine lens entries per frame at the end of its row of the warp's table (Lens, lens= of the tables)
+WARP_AREA = 0x400000  # enum lr_warp_area, likewise: a sampling factor S (1 .. 8) per frame at the very end of its row of the warp's table (area= of the tables)
 JPEG_OK, JPEG_NOT_JPEG, JPEG_UNSUPPORTED, JPEG_SIZE_MISMATCH, JPEG_DAMAGED = range(5)  # info[5] of lr_decode_jpeg_device
 FRAMES_U8, FRAMES_U8X3, FRAMES_F32 = 0x100, 0x200, 0x300  # enum lr_frames_option, or-ed into `refine` of the frame entries
 
@@ -339,6 +340,80 @@ def lens_distort(lens, points):
         return np.stack([(U + 32.0 * du) / 32.0, (V + 32.0 * dv) / 32.0], axis=-1)
 
 
+def _area_col(area, count, what):
+    """float64 (count, 1): the sampling factors of `count` frames from area=: one integer from 1 to 8 for all, or a list of one per frame"""
+    one = lambda v: not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, np.integer)) and 1 <= int(v) <= 8  # noqa: E731
+    if isinstance(area, (int, np.integer, bool, np.bool_, float, np.floating, str)):
+        factors = [area] * count
+    else:
+        try:
+            factors = list(area)
+        except TypeError:
+            raise ValueError("%s: area is an integer from 1 to 8 or a list of one per frame" % what) from None
+        if len(factors) != count:
+            raise ValueError("%s: as many sampling factors as frames (%d), not %d" % (what, count, len(factors)))
+    if not all(one(v) for v in factors):
+        raise ValueError("%s: a sampling factor (area=) is an integer from 1 to 8" % what)
+    return np.array(factors, np.float64).reshape(count, 1)
+
+
+def area_fine_map(M, S):
+    """lr_area_fine_map of include/librectify_amd.h restated operation for operation in float64: LR_WARP_AREA's fine map F of
+    the map M (3 x 3, destination to source) and the sampling factor S, the map of a picture S times as large whose pixel
+    (S x + i, S y + j) is sub-sample (i, j) of destination pixel (x, y).  Returns float64 (3, 3).  Needs no GPU."""
+    M = np.asarray(M, np.float64).reshape(3, 3)
+    S = int(S)
+    if not 1 <= S <= 8:
+        raise ValueError("area_fine_map: S is an integer from 1 to 8")
+    F = np.zeros((3, 3), np.float64)
+    with np.errstate(all="ignore"):
+        for k in range(3):
+            F[k, 0] = M[k, 0] / np.float64(S)
+            F[k, 1] = M[k, 1] / np.float64(S)
+            F[k, 2] = M[k, 2] - ((M[k, 0] + M[k, 1]) * np.float64(S - 1)) / np.float64(2 * S)
+    return F
+
+
+def shrink_homography(H, M, out_size, max_size):
+    """A rectified picture of bounded size (lr_shrink_homography of include/librectify_amd.h, restated operation for operation
+    in float64; host only): H, M, out_size = (width, height) are what rectification_homography or crop_homography returned;
+    either of H and M may be None.  Returns (H_out, M_out, (new_width, new_height), S): the warp with M_out into the new
+    size, which is at most max_size on its longer side, with WARP_AREA and the sampling factor S (area=S) is the picture
+    shrunk without aliasing.  A picture that fits already comes back as it is, with S = 1.  ValueError for what the header
+    refuses."""
+    f8 = np.float64
+    try:
+        h = None if H is None else np.array(H, f8).reshape(9)
+        m = None if M is None else np.array(M, f8).reshape(9)
+        ow, oh, max_size = int(out_size[0]), int(out_size[1]), int(max_size)
+    except (TypeError, ValueError):
+        raise ValueError("shrink_homography: H and M are 3 x 3 or None, out_size two integers and max_size one") from None
+    if h is None and m is None:
+        raise ValueError("shrink_homography: H and M are both None")
+    if ow < 1 or oh < 1 or max_size < 1:
+        raise ValueError("shrink_homography: a size or max_size below 1")
+    if not all(v is None or np.isfinite(v).all() for v in (h, m)):
+        raise ValueError("shrink_homography: a non-finite input")
+    longer, nw, nh, S = max(ow, oh), ow, oh, 1
+    if longer > max_size:
+        nw, nh = max(1, ow * max_size // longer), max(1, oh * max_size // longer)
+        sx, sy = f8(ow) / f8(nw), f8(oh) / f8(nh)
+        tx, ty = (sx - f8(1.0)) / f8(2.0), (sy - f8(1.0)) / f8(2.0)
+        with np.errstate(all="ignore"):
+            if h is not None:
+                for i in range(3):
+                    h[i] = (h[i] - tx * h[6 + i]) / sx
+                    h[3 + i] = (h[3 + i] - ty * h[6 + i]) / sy
+            if m is not None:
+                for k in range(3):
+                    m0, m1 = m[3 * k], m[3 * k + 1]
+                    m[3 * k] = m0 * sx
+                    m[3 * k + 1] = m1 * sy
+                    m[3 * k + 2] = m[3 * k + 2] + (m0 * tx + m1 * ty)
+        S = min(8, int(np.ceil(max(sx, sy))))
+    return (None if h is None else h.reshape(3, 3)), (None if m is None else m.reshape(3, 3)), (nw, nh), S
+
+
 def _is_border_spec(border):
     return border is None or isinstance(border, str) or (isinstance(border, tuple) and len(border) == 2 and isinstance(border[0], str))
 
@@ -453,7 +528,7 @@ def crop_homography(H, M, width, height, out_size, margin=0, aspect=None):
     return H_out.reshape(3, 3), M_out.reshape(3, 3), (int(lo_x), int(lo_y), int(hi_x - lo_x) + 1, int(hi_y - lo_y) + 1)
 
 
-def warp_table(Ms, sizes, bpp, align=4, border=None, lens=None):
+def warp_table(Ms, sizes, bpp, align=4, border=None, lens=None, area=None):
     """The table of a packed warp (lr_warp_perspective_device with LR_WARP_PACKED) for frames laid out one after the
     other in frame order.  Ms: (B, 3, 3) destination-to-source maps; sizes: B pairs (out_width, out_height); bpp: bytes
     per pixel (1 u8, 3 u8x3, 4 f32); every row stride and every frame's start is rounded up to `align` bytes (for f32 a
@@ -462,7 +537,9 @@ def warp_table(Ms, sizes, bpp, align=4, border=None, lens=None):
     border (not None): the table of LR_WARP_PACKED | LR_WARP_BORDER, (B, 14), whose column 13 is every frame's border word:
     one spec for all frames (border_word's) or a list of one per frame.
     lens (not None): the table of LR_WARP_PACKED | LR_WARP_LENS, (B, 22) or with border (B, 23), whose last nine columns are
-    every frame's lens: one Lens for all frames or a list of one per frame, in which None means zeros."""
+    every frame's lens: one Lens for all frames or a list of one per frame, in which None means zeros.
+    area (not None): the table of LR_WARP_PACKED | LR_WARP_AREA, one more column at the very end, every frame's sampling
+    factor S: one integer from 1 to 8 for all frames or a list of one per frame."""
     Ms = np.asarray(Ms, np.float64)
     if Ms.ndim == 2 and Ms.shape == (3, 3):
         Ms = Ms[None]
@@ -495,10 +572,12 @@ def warp_table(Ms, sizes, bpp, align=4, border=None, lens=None):
         table = np.concatenate([table, np.array(words, np.float64).reshape(-1, 1)], axis=1)
     if lens is not None:
         table = np.concatenate([table, _lens_rows(lens, len(Ms), "warp_table")], axis=1)
+    if area is not None:
+        table = np.concatenate([table, _area_col(area, len(Ms), "warp_table")], axis=1)
     return table, end
 
 
-def ragged_table(Ms, out_sizes, sources, bpp, out_bpp=None, align=4, border=None, lens=None):
+def ragged_table(Ms, out_sizes, sources, bpp, out_bpp=None, align=4, border=None, lens=None, area=None):
     """The table of a ragged call (lr_warp_perspective_device with LR_WARP_RAGGED): warp_table's layout for the outputs plus
     the four source columns.  Ms: (B, 3, 3) destination-to-source maps, or None (identity: the prepare step ignores them);
     out_sizes: B pairs (out_width, out_height); sources: B rows (width, height, byte_offset, row_bytes) of the frames in
@@ -509,7 +588,9 @@ def ragged_table(Ms, out_sizes, sources, bpp, out_bpp=None, align=4, border=None
     border (not None): the table of LR_WARP_RAGGED | LR_WARP_BORDER, whose column 17 is every frame's border word: one spec
     for all frames (border_word's) or a list of one per frame.
     lens (not None): the table of LR_WARP_RAGGED | LR_WARP_LENS, (B, 27), whose last nine columns are every frame's lens: one
-    Lens for all frames or a list of one per frame, in which None means zeros."""
+    Lens for all frames or a list of one per frame, in which None means zeros.
+    area (not None): the table of LR_WARP_RAGGED | LR_WARP_AREA, (B, 19) or with lens (B, 28), whose last column is every
+    frame's sampling factor S: one integer from 1 to 8 for all frames or a list of one per frame."""
     if bpp not in (1, 3, 4):
         raise ValueError("ragged_table: bpp is 1, 3 or 4")
     out_bpp = bpp if out_bpp is None else out_bpp
@@ -543,6 +624,8 @@ def ragged_table(Ms, out_sizes, sources, bpp, out_bpp=None, align=4, border=None
         table[:, 17] = _border_words(border, B, _FMT_OF_BPP[bpp], "ragged_table")
     if lens is not None:
         table = np.concatenate([table, _lens_rows(lens, B, "ragged_table")], axis=1)
+    if area is not None:
+        table = np.concatenate([table, _area_col(area, B, "ragged_table")], axis=1)
     return table, total
 
 
@@ -800,10 +883,24 @@ def _rectified_map(t, clip, crop, cubic):
     return M, rect[2:], rect
 
 
-def _border_bit_and_map(border, fmt, M, what, lens=None):
-    """(WARP_BORDER, WARP_LENS or 0, M or M's nine values with the border word and the nine lens entries behind them) for a
-    single-frame warp with border= and lens="""
-    if border is None and lens is None:
+def _bounded_map(M, size, out_max_size):
+    """(M, size, S) of a rectified picture with out_max_size= of the rectify calls: shrink_homography's map, size and sampling
+    factor (None: the picture as it is, S None)"""
+    if out_max_size is None:
+        return M, size, None
+    _, M, size, S = shrink_homography(None, M, size, out_max_size)
+    return M, size, S
+
+
+def _check_out_max_size(what, out_max_size):
+    if out_max_size is not None and (isinstance(out_max_size, (bool, np.bool_)) or not isinstance(out_max_size, (int, np.integer)) or out_max_size < 1):
+        raise ValueError("%s: out_max_size is None or an integer >= 1" % what)
+
+
+def _border_bit_and_map(border, fmt, M, what, lens=None, area=None):
+    """(WARP_BORDER, WARP_LENS, WARP_AREA or 0, M or M's nine values with the border word, the nine lens entries and the
+    sampling factor behind them) for a single-frame warp with border=, lens= and area="""
+    if border is None and lens is None and area is None:
         return 0, M
     row, bits = [np.asarray(M, np.float64).reshape(9)], 0
     if border is not None:
@@ -812,6 +909,9 @@ def _border_bit_and_map(border, fmt, M, what, lens=None):
     if lens is not None:
         row.append(_lens_rows(lens, 1, what)[0])
         bits |= WARP_LENS
+    if area is not None:
+        row.append(_area_col(area, 1, what)[0])
+        bits |= WARP_AREA
     return bits, np.concatenate(row)
 
 
@@ -965,9 +1065,10 @@ class Context:
         doubles per frame ((batch, 3, 3) or (3, 3)), the destination-to-source map.  fmt: PIX_U8, PIX_U8X3, PIX_F32, with
         WARP_CUBIC or-ed in for the bicubic sampling rule and WARP_BORDER for a border rule per frame (M then has 10 doubles
         per frame, the tenth the frame's border_word), and WARP_LENS for a lens per frame (nine more doubles per frame at the
-        end: a Lens)."""
+        end: a Lens), and WARP_AREA for S x S samples per destination pixel (one more double at the very end of every frame's
+        row: its sampling factor S, 1 .. 8)."""
         M = np.ascontiguousarray(M, np.float64).reshape(-1)
-        per_frame = (10 if fmt & WARP_BORDER else 9) + (9 if fmt & WARP_LENS else 0)
+        per_frame = (10 if fmt & WARP_BORDER else 9) + (9 if fmt & WARP_LENS else 0) + (1 if fmt & WARP_AREA else 0)
         if M.size < per_frame * max(int(batch), 1):
             raise ValueError("warp_perspective_device: M needs %d values per frame" % per_frame)
         _check(lib().lr_warp_perspective_device(self._h, C.c_void_p(d_src), src_image_bytes, batch, width, height, src_row_bytes, fmt, _ptr(M), C.c_void_p(d_dst), dst_image_bytes, out_width, out_height, dst_row_bytes))
@@ -977,26 +1078,28 @@ class Context:
         """lr_warp_perspective_device with LR_WARP_PACKED: one launch for `batch` device frames of one size whose outputs
         have their own sizes and places in the dst_bytes at d_dst.  table: 13 doubles per frame (warp_table).  fmt may carry
         WARP_CUBIC, WARP_BORDER with a table of 14 doubles per frame (warp_table's border=), and WARP_LENS with nine more
-        (warp_table's lens=)."""
+        (warp_table's lens=), and WARP_AREA with one more (warp_table's area=)."""
         table = np.ascontiguousarray(table, np.float64).reshape(-1)
-        cols = (14 if fmt & WARP_BORDER else 13) + (9 if fmt & WARP_LENS else 0)
+        cols = (14 if fmt & WARP_BORDER else 13) + (9 if fmt & WARP_LENS else 0) + (1 if fmt & WARP_AREA else 0)
         if table.size != cols * int(batch) or batch < 1:
             raise ValueError("warp_perspective_packed_device: the table has %d values per frame" % cols)
         out_w, out_h = (int(min(max(v, 1), 2 ** 31 - 1)) for v in np.nan_to_num(table.reshape(-1, cols)[:, 9:11]).max(axis=0))
         _check(lib().lr_warp_perspective_device(self._h, C.c_void_p(d_src), src_image_bytes, batch, width, height, src_row_bytes, fmt | WARP_PACKED, _ptr(table), C.c_void_p(d_dst), dst_bytes, out_w, out_h, 0))
 
-    def warp_perspective(self, array, M, out_size, interp="linear", border=None, lens=None):
+    def warp_perspective(self, array, M, out_size, interp="linear", border=None, lens=None, area=None):
         """Warps one host frame (2-D uint8 or float32, or H x W x 3 uint8) by M (3x3, destination -> source) into an image
         of out_size = (width, height) on the GPU: upload, one launch, download.  Returns the (height, width[, 3]) array.
         interp: "linear" (bilinear) or "cubic" (WARP_CUBIC: 4 x 4 bicubic, cv::warpPerspective's INTER_CUBIC).
         border: None (the zero border) or border_word's spec -- "replicate", "reflect", "reflect101", ("constant", value):
         cv::warpPerspective's borderMode and borderValue (WARP_BORDER).
         lens: None or the frame's Lens (WARP_LENS): M then maps into the ideal picture, and the lens model takes the point to the
-        pixel of `array` that is sampled -- undistortion and warp in one resampling."""
+        pixel of `array` that is sampled -- undistortion and warp in one resampling.
+        area: None or the sampling factor S, an integer from 1 to 8 (WARP_AREA): every pixel is the mean of S x S samples spread
+        over its footprint, for a map that shrinks (shrink_homography gives map, size and S for a bound on the size)."""
         cubic = _sampling_bit(interp, "warp_perspective")
         a = np.ascontiguousarray(array)
         fmt, bpp = _frame_format(a, "warp_perspective")
-        bbit, M = _border_bit_and_map(border, fmt, M, "warp_perspective", lens)
+        bbit, M = _border_bit_and_map(border, fmt, M, "warp_perspective", lens, area)
         h, w = a.shape[:2]
         ow, oh = int(out_size[0]), int(out_size[1])
         d_src = self.device_upload(a)
@@ -1282,11 +1385,11 @@ class Context:
         return self.decode_jpeg_batch([data], fmt, orient, any_sampling, scale)[0]
 
     def _rectify_streams(self, streams, min_length, refine, cfg, clip, max_size, capacity, jpeg, orient=False, interp="linear", jpeg_optimize=False,
-                         any_sampling=False, border=None, crop=False, decode_scale=None, decode_max_size=None, lens=None):
+                         any_sampling=False, border=None, crop=False, decode_scale=None, decode_max_size=None, lens=None, out_max_size=None):
         """rectify_batch for JPEG files: the files go up and are decoded in HBM, the pictures are handed to
         rectify_frames_device where they lie; with jpeg=Q no pixel crosses the link in either direction"""
         d_src, _, fmt, sources = self._decode_resident(streams, None, "rectify_batch", orient, any_sampling, decode_scale, decode_max_size)
-        return self._rectify_resident(d_src, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp, jpeg_optimize, border, crop, lens)
+        return self._rectify_resident(d_src, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp, jpeg_optimize, border, crop, lens, out_max_size)
 
     def prepare_device(self, d_src, src_image_bytes, batch, width, height, src_row_bytes, fmt, d_dst, dst_image_bytes,
                        out_width, out_height, dst_row_bytes):
@@ -1318,7 +1421,7 @@ class Context:
                 self.device_free(d_dst.value)
         return out if batched else out[0]
 
-    def _rectify_prepared(self, img, max_size, min_length, refine, cfg, clip, cubic=0, border=None, crop=False):
+    def _rectify_prepared(self, img, max_size, min_length, refine, cfg, clip, cubic=0, border=None, crop=False, out_max_size=None):
         """rectify with the demo's prescale: the 8-bit frame goes up once; the prepare step, the detector and the warp all
         read it in HBM"""
         fmt, bpp = _frame_format(img, "rectify")
@@ -1336,7 +1439,8 @@ class Context:
                 lines[k] = lines[k] / scale
             t = compute_rectification_transform(lines, w, h, cfg)
             M, (rw, rh), rect = _rectified_map(t, clip, crop, cubic)
-            bbit, M = _border_bit_and_map(border, fmt, M, "rectify")
+            M, (rw, rh), S = _bounded_map(M, (rw, rh), out_max_size)
+            bbit, M = _border_bit_and_map(border, fmt, M, "rectify", None, S)
             _check(lib().lr_device_malloc(self._h, rw * rh * bpp, C.byref(d_dst)))
             self.warp_perspective_device(d_src, img.nbytes, 1, w, h, w * bpp, fmt | cubic | bbit, M, d_dst.value, rw * rh * bpp, rw, rh, rw * bpp)
             return (lines, t, self.device_download(d_dst.value, (rh, rw) + img.shape[2:], np.uint8)) + ((rect,) if crop else ())
@@ -1348,7 +1452,7 @@ class Context:
 
     def rectify(self, image_u8, min_length=None, refine=False, cfg=None, clip=3.0, max_size=None, jpeg=None, orient=False,
                 interp="linear", jpeg_optimize=False, any_sampling=False, border=None, crop=False, decode_scale=None, decode_max_size=None,
-                lens=None):
+                lens=None, out_max_size=None):
         """The reference demo's pipeline (autorectify.cpp) on an 8-bit frame (H x W gray or H x W x 3 RGB): luma
         (4899 R + 9617 G + 1868 B + 8192) >> 14, / 256, find_line_segment_groups with min_length max(w, h) / 100 by
         default, compute_rectification_transform (cfg: the demo's, horizontal_vp_min_distance = 2),
@@ -1384,16 +1488,22 @@ class Context:
         and homography are in IDEAL coordinates (lens_distort takes them back onto the photograph); the final warp reads
         the ORIGINAL frame with WARP_LENS, the homography and the call's interp and border: one resampling.  The lines and the
         transform are those of rectify(undistort(image, lens)), the picture is warp_perspective(image, M, lens=lens).
-        With crop=True: ValueError (the crop's rectangle assumes straight source edges)."""
+        With crop=True: ValueError (the crop's rectangle assumes straight source edges).
+        out_max_size=N: the picture (or its JPEG file) is at most N pixels on its longer side.  The final warp carries
+        WARP_AREA with shrink_homography's map, size and sampling factor S (applied after the crop where crop=True, whose
+        rectangle stays in the uncropped full-size picture): every pixel is the mean of S x S samples over its footprint, taken
+        from the stored frame in the one resampling there is, with the call's lens, interp and border; no full-size picture
+        exists in HBM.  Lines and transform do not change.  None: the call as it was."""
         cubic = _sampling_bit(interp, "rectify")
         _check_jpeg_optimize("rectify", jpeg, jpeg_optimize)
+        _check_out_max_size("rectify", out_max_size)
         if lens is not None:
             if crop:
                 raise ValueError("rectify: crop=True together with lens= (the crop's rectangle assumes straight source edges)")
             lens = Lens(*_lens_row(lens, "rectify"))
         if isinstance(image_u8, (bytes, bytearray, memoryview)):  # a JPEG file: decoded in HBM, rectify_batch's path for one frame
             res = self.rectify_batch([bytes(image_u8)], min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, jpeg=jpeg, orient=orient, interp=interp, jpeg_optimize=jpeg_optimize, any_sampling=any_sampling, border=border, crop=crop,
-                                     decode_scale=decode_scale, decode_max_size=decode_max_size, lens=lens)[0]
+                                     decode_scale=decode_scale, decode_max_size=decode_max_size, lens=lens, out_max_size=out_max_size)[0]
             if res[2] is None:
                 _rectified_map(res[1], clip, crop, cubic)  # (raises what rectify raises for such a frame)
             return res
@@ -1407,14 +1517,14 @@ class Context:
         if img.dtype != np.uint8 or not (img.ndim == 2 or (img.ndim == 3 and img.shape[2] == 3)):
             raise ValueError("rectify: an H x W or H x W x 3 uint8 frame")
         if jpeg is not None or lens is not None:  # (with a lens: the mixed-size pipeline for one frame, which has the undistorting launch)
-            res = self.rectify_batch(img[None], min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, jpeg=jpeg, interp=interp, jpeg_optimize=jpeg_optimize, border=border, crop=crop, lens=lens)[0]
+            res = self.rectify_batch(img[None], min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, jpeg=jpeg, interp=interp, jpeg_optimize=jpeg_optimize, border=border, crop=crop, lens=lens, out_max_size=out_max_size)[0]
             if res[2] is None:
                 _rectified_map(res[1], clip, crop, cubic)  # (raises what rectify raises for such a frame)
             return res
         fmt, bpp = _frame_format(img, "rectify")
         _border_words(border, 1, fmt, "rectify")  # (a bad spec: ValueError before anything is launched)
         if max_size is not None:
-            return self._rectify_prepared(img, max_size, min_length, refine, cfg or RectificationConfig(hmin=2.0), clip, cubic, border, crop)
+            return self._rectify_prepared(img, max_size, min_length, refine, cfg or RectificationConfig(hmin=2.0), clip, cubic, border, crop, out_max_size)
         h, w = img.shape[:2]
         if min_length is None:
             min_length = max(w, h) / 100.0
@@ -1426,7 +1536,8 @@ class Context:
             lines = self.find_line_segment_groups_device(d_src, w, h, min_length, refine=refine, fmt=fmt).copy()
             t = compute_rectification_transform(lines, w, h, cfg)
             M, (rw, rh), rect = _rectified_map(t, clip, crop, cubic)
-            bbit, M = _border_bit_and_map(border, fmt, M, "rectify")
+            M, (rw, rh), S = _bounded_map(M, (rw, rh), out_max_size)
+            bbit, M = _border_bit_and_map(border, fmt, M, "rectify", None, S)
             _check(lib().lr_device_malloc(self._h, rw * rh * bpp, C.byref(d_dst)))
             self.warp_perspective_device(d_src, img.nbytes, 1, w, h, w * bpp, fmt | cubic | bbit, M, d_dst.value, rw * rh * bpp, rw, rh, rw * bpp)
             return (lines, t, self.device_download(d_dst.value, (rh, rw) + img.shape[2:], np.uint8)) + ((rect,) if crop else ())
@@ -1437,7 +1548,7 @@ class Context:
 
     def rectify_batch_device(self, d_frames, batch, width, height, fmt, src_row_bytes=None, src_image_bytes=None,
                              min_length=None, refine=False, cfg=None, clip=3.0, max_size=None, capacity=4096, interp="linear",
-                             border=None, crop=False):
+                             border=None, crop=False, out_max_size=None):
         """rectify for `batch` 8-bit frames (fmt PIX_U8 or PIX_U8X3) of one width x height that are resident in HBM, frame
         b at d_frames + b * src_image_bytes: with max_size one batched prepare_device, then the batch detector
         (lr_find_line_segment_groups_batch_device on the 8-bit frames, or on the prepared ones; its own transforms are not
@@ -1455,8 +1566,10 @@ class Context:
         border: None, one border_word spec for all frames or a list of one per frame (WARP_BORDER: the table then has 14
         columns).  crop=True: every picture is its constrained crop (rectify's crop=; a frame whose crop cannot be formed
         has no image) and a sixth value is returned: the list of the frames' rectangles (x0, y0, width, height), None for a
-        frame without an image."""
+        frame without an image.  out_max_size=N: every picture is at most N pixels on its longer side (rectify's out_max_size=:
+        WARP_AREA on the packed warp; the table then has one more column at its end, the frames' sampling factors)."""
         cubic = _sampling_bit(interp, "rectify_batch_device")
+        _check_out_max_size("rectify_batch_device", out_max_size)
         if fmt not in (PIX_U8, PIX_U8X3):
             raise ValueError("rectify_batch_device: 8-bit frames, PIX_U8 or PIX_U8X3")
         batch, w, h = int(batch), int(width), int(height)
@@ -1493,7 +1606,7 @@ class Context:
                 if int(n.max()) <= capacity:
                     break
                 capacity = int(n.max())  # (a frame's lines were cut: once more, with room for the longest list)
-            lines_list, transforms, good, Ms, sizes, rects = [], [], [], [], [], [None] * batch
+            lines_list, transforms, good, Ms, sizes, rects, factors = [], [], [], [], [], [None] * batch, []
             for b in range(batch):
                 lines = out[b][: n[b]].copy()
                 if scale is not None:
@@ -1506,22 +1619,26 @@ class Context:
                     M, size, rects[b] = _rectified_map(t, clip, crop, cubic)
                 except LibrectifyError:
                     continue  # (collinear corners, a size below 1, ...: this frame has no image)
+                M, size, S = _bounded_map(M, size, out_max_size)
                 good.append(b)
                 Ms.append(M)
                 sizes.append(size)
-            table = np.zeros((batch, 13 if words is None else 14), np.float64)
+                factors.append(S)
+            table = np.zeros((batch, (13 if words is None else 14) + (0 if out_max_size is None else 1)), np.float64)
             more = (rects,) if crop else ()
             if not good:
                 return (lines_list, transforms, table, None, 0) + more
             table[good, :13], total = warp_table(np.stack(Ms), np.array(sizes, np.int64), bpp, 4)
             if words is not None:
                 table[good, 13] = [words[b] for b in good]
+            if out_max_size is not None:
+                table[good, -1] = factors
             _check(lib().lr_device_malloc(self._h, total, C.byref(d_out)))
             # one launch; a frame without an image splits it, as a launch's frames are consecutive in the source
             runs = np.split(np.array(good), np.flatnonzero(np.diff(good) != 1) + 1)
             for run in runs:
                 b0 = int(run[0])
-                self.warp_perspective_packed_device(d_frames + b0 * simg, simg, len(run), w, h, srow, fmt | cubic | (0 if words is None else WARP_BORDER), table[run], d_out.value, total)
+                self.warp_perspective_packed_device(d_frames + b0 * simg, simg, len(run), w, h, srow, fmt | cubic | (0 if words is None else WARP_BORDER) | (0 if out_max_size is None else WARP_AREA), table[run], d_out.value, total)
             res, d_out = d_out.value, C.c_void_p()
             return (lines_list, transforms, table, res, total) + more
         finally:
@@ -1531,7 +1648,7 @@ class Context:
 
     def _ragged_call(self, d_src, src_bytes, fmt_word, table, d_dst, dst_bytes, what):
         table = np.ascontiguousarray(table, np.float64)
-        cols = 27 if fmt_word & WARP_LENS else 18
+        cols = (27 if fmt_word & WARP_LENS else 18) + (1 if fmt_word & WARP_AREA else 0)
         if table.ndim != 2 or table.shape[1] != cols or len(table) < 1:
             raise ValueError(what + ": the table has %d values per frame" % cols)
         bound = lambda col: int(min(max(np.nan_to_num(table[:, col]).max(), 1), 2 ** 31 - 1))  # noqa: E731
@@ -1541,7 +1658,7 @@ class Context:
         """lr_warp_perspective_device with LR_WARP_RAGGED: one launch for frames that have their own source size and place
         in the src_bytes at d_src and their own output size and place in the dst_bytes at d_dst.  table: 18 doubles per
         frame (ragged_table).  fmt may carry WARP_CUBIC, WARP_BORDER, and WARP_LENS with a table of 27 doubles per frame
-        (ragged_table's lens=)."""
+        (ragged_table's lens=), and WARP_AREA with one more (ragged_table's area=)."""
         self._ragged_call(d_src, src_bytes, fmt | WARP_RAGGED, table, d_dst, dst_bytes, "warp_perspective_ragged_device")
 
     def prepare_ragged_device(self, d_src, src_bytes, fmt, table, d_dst, dst_bytes):
@@ -1574,7 +1691,7 @@ class Context:
         return [out[b][: min(int(n[b]), capacity)].copy() for b in range(len(frames))], tf
 
     def rectify_frames_device(self, d_base, sources, fmt, min_length=None, refine=False, cfg=None, clip=3.0, max_size=None,
-                              capacity=4096, interp="linear", border=None, crop=False):
+                              capacity=4096, interp="linear", border=None, crop=False, out_max_size=None):
         """rectify for 8-bit frames (fmt PIX_U8 or PIX_U8X3) that are resident in HBM and have their OWN sizes: frame b is
         sources[b] = (width, height, byte_offset from d_base, row_bytes).  With max_size one ragged prepare
         (prepare_ragged_device) to prepared_size(w_b, h_b, max_size) per frame, one detector call with a frame table (on
@@ -1583,15 +1700,18 @@ class Context:
         frames that have an image.  Returns (lines_list, transforms, table, d_out, total_bytes) like rectify_batch_device;
         table is ragged_table's (18 columns; an all-zero row for a frame without an image).  capacity and interp: as
         there (the ragged warp's sampling rule); border and crop likewise (the border words are the table's column 17; with
-        crop=True the frames' rectangles are a sixth value)."""
-        return self._rectify_frames(d_base, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, interp, border, crop)
+        crop=True the frames' rectangles are a sixth value).  out_max_size=N: every picture is at most N pixels on its longer
+        side (rectify's out_max_size=: WARP_AREA on the ragged warp, the sampling factors behind the launch's rows; the table
+        that comes back keeps its 18 columns, with the shrunk maps and sizes)."""
+        return self._rectify_frames(d_base, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, interp, border, crop, None, out_max_size)
 
-    def _rectify_frames(self, d_base, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, interp, border, crop, lens_rows=None):
+    def _rectify_frames(self, d_base, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, interp, border, crop, lens_rows=None, out_max_size=None):
         """rectify_frames_device; lens_rows (float64 (B, 9), rectify_batch's lens=): one WARP_LENS launch with the identity map,
         bilinear, zero border, writes every frame without its distortion into a second region of the sources' layout; the
         prepare step and the detector read that one, so lines and transforms are in ideal coordinates; the warp reads the
         ORIGINAL frames with WARP_LENS: one resampling"""
         cubic = _sampling_bit(interp, "rectify_frames_device")
+        _check_out_max_size("rectify_frames_device", out_max_size)
         if fmt not in (PIX_U8, PIX_U8X3):
             raise ValueError("rectify_frames_device: 8-bit frames, PIX_U8 or PIX_U8X3")
         sources = [tuple(int(v) for v in s) for s in sources]
@@ -1642,7 +1762,7 @@ class Context:
                 if int(n.max()) <= capacity:
                     break
                 capacity = int(n.max())  # (a frame's lines were cut: once more, with room for the longest list)
-            lines_list, transforms, good, Ms, sizes, rects = [], [], [], [], [], [None] * batch
+            lines_list, transforms, good, Ms, sizes, rects, factors = [], [], [], [], [], [None] * batch, np.zeros((batch, 1), np.float64)
             for b, (w, h, _, _) in enumerate(sources):
                 lines = out[b][: n[b]].copy()
                 if scales[b] is not None:
@@ -1655,9 +1775,11 @@ class Context:
                     M, size, rects[b] = _rectified_map(t, clip, crop, cubic)
                 except LibrectifyError:
                     continue  # (collinear corners, a size below 1, ...: this frame has no image)
+                M, size, S = _bounded_map(M, size, out_max_size)
                 good.append(b)
                 Ms.append(M)
                 sizes.append(size)
+                factors[b] = S or 0
             table = np.zeros((batch, 18), np.float64)
             more = (rects,) if crop else ()
             if not good:
@@ -1666,9 +1788,11 @@ class Context:
             if words is not None:
                 table[good, 17] = [words[b] for b in good]
             _check(lib().lr_device_malloc(self._h, total, C.byref(d_out)))
-            bits = cubic | (0 if words is None else WARP_BORDER) | (0 if lens_rows is None else WARP_LENS)
+            bits = cubic | (0 if words is None else WARP_BORDER) | (0 if lens_rows is None else WARP_LENS) | (0 if out_max_size is None else WARP_AREA)
             for run in np.split(np.array(good), np.flatnonzero(np.diff(good) != 1) + 1):
                 rows = table[run] if lens_rows is None else np.concatenate([table[run], lens_rows[run]], axis=1)
+                if out_max_size is not None:
+                    rows = np.concatenate([rows, factors[run]], axis=1)
                 self.warp_perspective_ragged_device(d_base, src_bytes, fmt | bits, rows, d_out.value, total)
             res, d_out = d_out.value, C.c_void_p()
             return (lines_list, transforms, table, res, total) + more
@@ -1687,7 +1811,7 @@ class Context:
         return out
 
     def _rectify_mixed(self, frames, min_length, refine, cfg, clip, max_size, capacity, jpeg=None, interp="linear", jpeg_optimize=False, border=None, crop=False,
-                       lens=None):
+                       lens=None, out_max_size=None):
         """rectify_batch for a list of 8-bit frames of different shapes: all frames in one host buffer, one upload,
         rectify_frames_device, one download"""
         frames = [np.ascontiguousarray(f) for f in frames]
@@ -1705,16 +1829,16 @@ class Context:
         for f, (_, _, start, _) in zip(frames, sources):
             host[start: start + f.nbytes] = f.reshape(-1)
         _border_words(border, len(frames), fmt, "rectify_batch")  # (a bad spec: ValueError before anything goes up)
-        return self._rectify_resident(self.device_upload(host), sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp, jpeg_optimize, border, crop, lens)
+        return self._rectify_resident(self.device_upload(host), sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp, jpeg_optimize, border, crop, lens, out_max_size)
 
     def _rectify_resident(self, d_src, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp="linear", jpeg_optimize=False, border=None, crop=False,
-                          lens=None):
+                          lens=None, out_max_size=None):
         """rectify_batch for 8-bit frames (width, height, byte_offset, row_bytes) that lie at d_src, which is freed here:
         rectify_frames_device, then one download of the pictures, or with jpeg the encoder and the streams alone"""
         bpp = 3 if fmt == PIX_U8X3 else 1
         d_out = None
         try:
-            lines, tfs, table, d_out, total, *more = self._rectify_frames(d_src, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, interp, border, crop, lens)
+            lines, tfs, table, d_out, total, *more = self._rectify_frames(d_src, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, interp, border, crop, lens, out_max_size)
             rect = (lambda b: (more[0][b],)) if crop else (lambda b: ())
             if jpeg is not None:
                 streams = self._jpeg_results(d_out, total, fmt, table, jpeg, jpeg_optimize) if d_out else [None] * len(sources)
@@ -1736,7 +1860,7 @@ class Context:
 
     def rectify_batch(self, frames_u8, min_length=None, refine=False, cfg=None, clip=3.0, max_size=None, capacity=4096, jpeg=None,
                       orient=False, interp="linear", jpeg_optimize=False, any_sampling=False, border=None, crop=False, decode_scale=None,
-                      decode_max_size=None, lens=None):
+                      decode_max_size=None, lens=None, out_max_size=None):
         """Context.rectify for a batch: frames_u8 is a uint8 array [B, H, W] or [B, H, W, 3], or a list of such frames of one
         shape.  One upload, rectify_batch_device (one detector batch, the packed warp), one download.  Returns a
         list of (lines, transform, warped), frame by frame what rectify returns for it; warped is None for a frame whose
@@ -1772,8 +1896,12 @@ class Context:
         lens: None, one Lens for all frames or a list of one per frame, in which None means no lens (WARP_LENS): frame by frame
         what rectify(lens=) returns.  Arrays and files alike then take the mixed-size pipeline, with one WARP_LENS launch in
         front of it that writes the frames without their distortion for the detector, and the final warp reading the frames
-        as they were uploaded or decoded.  With crop=True: ValueError."""
+        as they were uploaded or decoded.  With crop=True: ValueError.
+        out_max_size=N: every picture, or JPEG file, is at most N pixels on its longer side (WARP_AREA on the warp launch of
+        whichever path is taken, after the crop and in front of the encoder) -- frame by frame what rectify(out_max_size=N)
+        returns.  The full-size pictures never exist: HBM holds, the link carries and the encoder reads the small ones."""
         _sampling_bit(interp, "rectify_batch")
+        _check_out_max_size("rectify_batch", out_max_size)
         _check_jpeg_optimize("rectify_batch", jpeg, jpeg_optimize)
         if lens is not None:
             if crop:
@@ -1785,13 +1913,13 @@ class Context:
             except ValueError:
                 _border_words(border, len(frames_u8), PIX_U8, "rectify_batch")
             return self._rectify_streams([bytes(f) for f in frames_u8], min_length, refine, cfg, clip, max_size, capacity, jpeg, orient, interp, jpeg_optimize,
-                                         any_sampling, border, crop, decode_scale, decode_max_size, lens)
+                                         any_sampling, border, crop, decode_scale, decode_max_size, lens, out_max_size)
         if lens is not None:
-            return self._rectify_mixed(list(frames_u8), min_length, refine, cfg, clip, max_size, capacity, jpeg, interp, jpeg_optimize, border, crop, lens)
+            return self._rectify_mixed(list(frames_u8), min_length, refine, cfg, clip, max_size, capacity, jpeg, interp, jpeg_optimize, border, crop, lens, out_max_size)
         if not isinstance(frames_u8, np.ndarray):
             frames_u8 = [np.asarray(f) for f in frames_u8]
             if len({f.shape for f in frames_u8}) > 1:
-                return self._rectify_mixed(frames_u8, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp, jpeg_optimize, border, crop)
+                return self._rectify_mixed(frames_u8, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp, jpeg_optimize, border, crop, None, out_max_size)
         a = np.ascontiguousarray(frames_u8 if isinstance(frames_u8, np.ndarray) else np.stack([np.asarray(f) for f in frames_u8]))
         if a.dtype != np.uint8 or a.ndim not in (3, 4) or (a.ndim == 4 and a.shape[3] != 3) or a.shape[0] < 1:
             raise ValueError("rectify_batch: uint8 frames [B, H, W] or [B, H, W, 3]")
@@ -1801,7 +1929,7 @@ class Context:
         d_src = self.device_upload(a)
         d_out = None
         try:
-            lines, tfs, table, d_out, total, *more = self.rectify_batch_device(d_src, batch, w, h, fmt, min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, capacity=capacity, interp=interp, border=border, crop=crop)
+            lines, tfs, table, d_out, total, *more = self.rectify_batch_device(d_src, batch, w, h, fmt, min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, capacity=capacity, interp=interp, border=border, crop=crop, out_max_size=out_max_size)
             rect = (lambda b: (more[0][b],)) if crop else (lambda b: ())
             if jpeg is not None:
                 streams = self._jpeg_results(d_out, total, fmt, table, jpeg, jpeg_optimize) if d_out else [None] * batch

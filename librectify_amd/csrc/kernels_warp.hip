@@ -30,6 +30,10 @@
 // frame's lens model (OpenCV's five coefficients; fixed_xy and lens_displace of warp_lane.h).  Its launches all go through
 // warp_ragged_lens_kernel, which is kernels_warp_lens.hip's, with a second array of records, one LensRecord per frame.
 //
+// LR_WARP_AREA is no parameter of warp_lane but a loop around its per-pixel rules: S x S sub-samples per destination pixel under
+// the frame's fine map, averaged.  Its launches all go through warp_ragged_area_kernel, which is
+// kernels_warp_area.hip's, with a third array of records, one AreaRecord per frame; the fine maps are made here, on the host.
+//
 // One lane body, two kernels.  warp_lane is a lane's work inside a tile: its four pixels' taps, blends and stores.  The two
 // kernels differ only in how a workgroup finds its frame and the frame's values, all of which depend on the tile index
 // alone and are uniform across the workgroup:
@@ -151,16 +155,65 @@ bool any_lens(const std::vector<LensRecord>& lens) {
     return std::any_of(lens.begin(), lens.end(), [](const LensRecord& l) { return l.has_lens != 0; });
 }
 
-// The table kernel's launch: records, then (LR_WARP_LENS, `lens` not NULL) the lens records, then the tiles' prefix table, go
-// up in the mirror of the maps (in doubles: 18 a frame, 10 a lens + the table's ints)
-int launch_ragged(lr_context* c, const void* d_src, int format, bool cubic, bool border, const std::vector<RaggedFrame>& rec,
-                  const std::vector<int>& start, void* d_dst, const std::vector<LensRecord>* lens = nullptr) {
-    const size_t batch = rec.size(), lens_doubles = lens ? batch * 10 : 0, rec_doubles = batch * 18 + lens_doubles;
+// A frame's sampling factor (LR_WARP_AREA): the last double of its row, an integer from 1 to 8.  Fills the record with S and
+// the fine map of the frame's map m (S = 1: m itself, the plain rule); on a fault returns the reason (NULL: none).
+const char* parse_area(double entry, const double* m, uint64_t ow, uint64_t oh, AreaRecord* a) {
+    uint64_t v;
+    if (!table_integer(entry, 1, 8, &v)) return "is not an integer from 1 to 8";
+    if (v * ow > 2147483647ull) return "times the frame's output width is above 2^31 - 1";
+    if (v * oh > 2147483647ull) return "times the frame's output height is above 2^31 - 1";
+    std::memset(a, 0, sizeof *a);
+    a->s = (int)v;
+    if (v == 1) std::memcpy(a->f, m, sizeof a->f);
+    else lr_area_fine_map(m, (int)v, a->f);
+    return nullptr;
+}
+
+int fail_area(const char* layout, int b, const char* why) {
+    set_error(std::string("lr_warp_perspective_device: ") + layout + "LR_WARP_AREA: frame " + std::to_string(b) + ": the sampling factor S " + why);
+    return 1;
+}
+
+bool any_area(const std::vector<AreaRecord>& area) {
+    return std::any_of(area.begin(), area.end(), [](const AreaRecord& a) { return a.s > 1; });
+}
+
+// The table kernel's launch: records, then (LR_WARP_LENS, `lens` not NULL) the lens records, then (LR_WARP_AREA, `area` not
+// NULL) the area records, then the tiles' prefix table, go up in the mirror of the maps (in doubles: 18 a frame, 10 a lens,
+// 10 an area record + the table's ints).  The area kernel cuts a frame with S > 1 into tiles of (64 / S) x (16 / S) destination
+// pixels (kernels_warp_area.hip: a tile is 64 x 16 samples), so with `area` the frames' tiles are counted again by that size.
+int launch_ragged(lr_context* c, const void* d_src, int format, bool cubic, bool border, const std::vector<RaggedFrame>& frame_rec,
+                  const std::vector<int>& frame_start, void* d_dst, const std::vector<LensRecord>* lens = nullptr,
+                  const std::vector<AreaRecord>* area = nullptr) {
+    const size_t batch = frame_rec.size(), lens_doubles = lens ? batch * 10 : 0, area_doubles = area ? batch * 10 : 0;
+    const size_t rec_doubles = batch * 18 + lens_doubles + area_doubles;
+    std::vector<RaggedFrame> area_rec;
+    std::vector<int> area_start;
+    if (area) {
+        area_rec = frame_rec;
+        area_start.resize(batch + 1);
+        int64_t tiles = 0;
+        for (size_t b = 0; b < batch; ++b) {
+            RaggedFrame& f = area_rec[b];
+            const int tile_w = kTileW / (*area)[b].s, tile_h = kTileH / (*area)[b].s;  // (S = 1: the plain tile)
+            f.tiles_x = (int)(((int64_t)f.ow + tile_w - 1) / tile_w);
+            area_start[b] = (int)tiles;
+            tiles += (int64_t)f.tiles_x * (((int64_t)f.oh + tile_h - 1) / tile_h);
+            if (tiles > 0x7FFFFFF0ll) {
+                set_error("lr_warp_perspective_device: LR_WARP_AREA: frame " + std::to_string(b) + ": output larger than 2^31 tiles of 64 x 16 samples");
+                return 1;
+            }
+        }
+        area_start[batch] = (int)tiles;
+    }
+    const std::vector<RaggedFrame>& rec = area ? area_rec : frame_rec;
+    const std::vector<int>& start = area ? area_start : frame_start;
     const int64_t n_tiles = start[batch];
     LR_HIP(hipSetDevice(c->device));
     if (upload_reserve(c, c->warp_m, c->ev_warp_m, rec_doubles + (batch + 2) / 2)) return 1;
     std::memcpy(c->warp_m.h, rec.data(), batch * 18 * sizeof(double));
     if (lens) std::memcpy(c->warp_m.h + batch * 18, lens->data(), lens_doubles * sizeof(double));
+    if (area) std::memcpy(c->warp_m.h + batch * 18 + lens_doubles, area->data(), area_doubles * sizeof(double));
     std::memcpy(c->warp_m.h + rec_doubles, start.data(), start.size() * sizeof(int));
     if (upload_send(c, c->warp_m, c->ev_warp_m, rec_doubles * sizeof(double) + start.size() * sizeof(int))) return 1;
 
@@ -172,6 +225,12 @@ int launch_ragged(lr_context* c, const void* d_src, int format, bool cubic, bool
     const RaggedFrame* frames = reinterpret_cast<const RaggedFrame*>(c->warp_m.d.get());
     const int* tile_start = reinterpret_cast<const int*>(c->warp_m.d.get() + rec_doubles);
     const int grid = (int)std::min<int64_t>((n_tiles + 7) / 8 * 8, kMaxGrid);
+    if (area) {  // (some frame's S is above 1: the kernels of kernels_warp_area.hip, which take the border rules as they are)
+        launch_warp_ragged_area(format, cubic, grid, c->stream, g.src, g.batch, g.n_tiles, frames, lens ? c->warp_m.d.get() + batch * 18 : nullptr,
+                                c->warp_m.d.get() + batch * 18 + lens_doubles, tile_start, dst);
+        LR_HIP(hipGetLastError());
+        return 0;
+    }
     if (lens) {  // (some frame has a lens: the kernels of kernels_warp_lens.hip)
         launch_warp_ragged_lens(format, cubic, border, grid, c->stream, g.src, g.batch, g.n_tiles, frames, c->warp_m.d.get() + batch * 18, tile_start, dst);
         LR_HIP(hipGetLastError());
@@ -192,7 +251,7 @@ int launch_ragged(lr_context* c, const void* d_src, int format, bool cubic, bool
 // lr_warp_perspective_device with LR_WARP_PACKED: M is the table of 13 doubles per frame, out_width x out_height bound the
 // frames' sizes and dst_image_bytes is the size of the whole destination region
 int warp_packed(lr_context* c, const void* d_src, size_t src_image_bytes, int batch, int width, int height, size_t src_row_bytes,
-                int format, bool cubic, bool border, bool lens, const double* T, void* d_dst, size_t dst_bytes, int out_width,
+                int format, bool cubic, bool border, bool lens, bool area, const double* T, void* d_dst, size_t dst_bytes, int out_width,
                 int out_height, size_t dst_row_bytes) {
     auto fail = [](const char* what) {
         set_error(std::string("lr_warp_perspective_device: LR_WARP_PACKED: ") + what);
@@ -219,9 +278,11 @@ int warp_packed(lr_context* c, const void* d_src, size_t src_image_bytes, int ba
     std::vector<std::pair<uint64_t, uint64_t>> extent((size_t)batch);  // [first byte, end)
     int64_t n_tiles = 0;
     const size_t lens_at = border ? 14 : 13;                // (LR_WARP_BORDER: the border word behind the row)
-    const size_t row_doubles = lens_at + (lens ? 9 : 0);    // (LR_WARP_LENS: the nine lens entries behind that)
+    const size_t area_at = lens_at + (lens ? 9 : 0);        // (LR_WARP_LENS: the nine lens entries behind that)
+    const size_t row_doubles = area_at + (area ? 1 : 0);    // (LR_WARP_AREA: the sampling factor at the very end)
     bool bordered = false;                                  // some frame's word is not 0
     std::vector<LensRecord> lenses(lens ? (size_t)batch : 0);
+    std::vector<AreaRecord> areas(area ? (size_t)batch : 0);
     for (int b = 0; b < batch; ++b) {
         const double* t = T + (size_t)b * row_doubles;
         for (int i = 0; i < 9; ++i)
@@ -256,28 +317,32 @@ int warp_packed(lr_context* c, const void* d_src, size_t src_image_bytes, int ba
         }
         if (lens)
             if (const char* why = parse_lens(t + lens_at, &lenses[(size_t)b])) return fail_lens("LR_WARP_PACKED: ", b, why);
+        if (area)
+            if (const char* why = parse_area(t[area_at], f.m, ow, oh, &areas[(size_t)b])) return fail_area("LR_WARP_PACKED: ", b, why);
         start[(size_t)b] = (int)n_tiles;
         n_tiles += (int64_t)f.tiles_x * (int64_t)((oh + kTileH - 1) / kTileH);
         if (n_tiles > 0x7FFFFFF0ll) return fail("output larger than 2^31 tiles of 64 x 16 pixels");
     }
     start[(size_t)batch] = (int)n_tiles;
     if (extents_overlap(extent)) return fail("two frames' extents overlap");
-    return launch_ragged(c, d_src, format, cubic, bordered, rec, start, d_dst, any_lens(lenses) ? &lenses : nullptr);
+    return launch_ragged(c, d_src, format, cubic, bordered, rec, start, d_dst, any_lens(lenses) ? &lenses : nullptr,
+                         any_area(areas) ? &areas : nullptr);
 }
 
 // lr_warp_perspective_device with LR_WARP_RAGGED: M is the table of 18 doubles per frame, width x height and out_width x
 // out_height bound the frames' sizes, src_image_bytes and dst_image_bytes are the sizes of the two regions
 int warp_ragged(lr_context* c, const void* d_src, size_t src_bytes, int batch, int width, int height, size_t src_row_bytes,
-                int format, bool cubic, bool border, bool lens, const double* T, void* d_dst, size_t dst_bytes, int out_width,
+                int format, bool cubic, bool border, bool lens, bool area, const double* T, void* d_dst, size_t dst_bytes, int out_width,
                 int out_height, size_t dst_row_bytes) {
     std::vector<RaggedEntry> e;
     int64_t n_tiles = 0;
     // LR_WARP_BORDER: entry [17] is the frame's border word; the table's other checks see it as the 0 they ask for
     // LR_WARP_LENS: rows of 27, the nine lens entries behind [17]; the table's checks see rows of 18
+    // LR_WARP_AREA: one more, the sampling factor at the very end
     std::vector<double> plain;
     const double* words = T;
-    const size_t row_doubles = lens ? 27 : 18;
-    if ((border || lens) && T && batch >= 1) {
+    const size_t area_at = lens ? 27 : 18, row_doubles = area_at + (area ? 1 : 0);
+    if ((border || lens || area) && T && batch >= 1) {
         plain.resize((size_t)batch * 18);
         for (int b = 0; b < batch; ++b) {
             std::memcpy(&plain[(size_t)b * 18], words + (size_t)b * row_doubles, 18 * sizeof(double));
@@ -286,6 +351,7 @@ int warp_ragged(lr_context* c, const void* d_src, size_t src_bytes, int batch, i
         T = plain.data();
     }
     std::vector<LensRecord> lenses(lens && batch >= 1 ? (size_t)batch : 0);
+    std::vector<AreaRecord> areas(area && batch >= 1 ? (size_t)batch : 0);
     bool bordered = false;  // some frame's word is not 0
     if (ragged_parse(d_src, src_bytes, batch, width, height, src_row_bytes, format, false, T, d_dst, dst_bytes, out_width,
                      out_height, dst_row_bytes, kTileW, kTileH, e, &n_tiles))
@@ -314,11 +380,14 @@ int warp_ragged(lr_context* c, const void* d_src, size_t src_bytes, int batch, i
         }
         if (lens)
             if (const char* why = parse_lens(words + (size_t)b * row_doubles + 18, &lenses[(size_t)b])) return fail_lens("LR_WARP_RAGGED: ", b, why);
+        if (area)
+            if (const char* why = parse_area(words[(size_t)b * row_doubles + area_at], f.m, s.ow, s.oh, &areas[(size_t)b])) return fail_area("LR_WARP_RAGGED: ", b, why);
         start[(size_t)b] = tiles;
         tiles += f.tiles_x * (int)((s.oh + kTileH - 1) / kTileH);
     }
     start[(size_t)batch] = tiles;
-    return launch_ragged(c, d_src, format, cubic, bordered, rec, start, d_dst, any_lens(lenses) ? &lenses : nullptr);
+    return launch_ragged(c, d_src, format, cubic, bordered, rec, start, d_dst, any_lens(lenses) ? &lenses : nullptr,
+                         any_area(areas) ? &areas : nullptr);
 }
 
 }  // namespace
@@ -415,6 +484,15 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
         if (format & LR_WARP_JPEG_DECODE) return fail("LR_WARP_LENS together with LR_WARP_JPEG_DECODE (the decoder samples nothing)");
         format &= ~LR_WARP_LENS;
     }
+    // LR_WARP_AREA: a sampling factor per frame at the very end of its row of M; likewise of the three warps alone
+    const bool area = (format & LR_WARP_AREA) != 0;
+    if (area) {
+        if (format & LR_WARP_PREPARE) return fail("LR_WARP_AREA together with LR_WARP_PREPARE (the prepare step is an area average of its own)");
+        if (format & LR_WARP_LINES) return fail("LR_WARP_AREA together with LR_WARP_LINES (the lines picture samples nothing)");
+        if (format & LR_WARP_JPEG) return fail("LR_WARP_AREA together with LR_WARP_JPEG (the encoder samples nothing)");
+        if (format & LR_WARP_JPEG_DECODE) return fail("LR_WARP_AREA together with LR_WARP_JPEG_DECODE (the decoder samples nothing)");
+        format &= ~LR_WARP_AREA;
+    }
     if (format & LR_WARP_JPEG_DECODE) {  // lr_decode_jpeg_device (kernels_jpeg_decode.hip): its own arguments arrive behind M
         // (LR_JPEG_ANY_SAMPLING and LR_JPEG_SCALED are the decoder's own options and travel on with the format)
         constexpr int kDecoderOptions = LR_JPEG_ANY_SAMPLING | LR_JPEG_SCALED;
@@ -448,7 +526,7 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
         const int opts = format & ~0xFF;
         if (opts & LR_WARP_PACKED) return fail("LR_WARP_RAGGED together with LR_WARP_PACKED (ragged outputs are always packed)");
         if (opts == LR_WARP_RAGGED)
-            return warp_ragged(c, d_src, src_image_bytes, batch, width, height, src_row_bytes, format & 0xFF, cubic, border, lens, M, d_dst,
+            return warp_ragged(c, d_src, src_image_bytes, batch, width, height, src_row_bytes, format & 0xFF, cubic, border, lens, area, M, d_dst,
                                dst_image_bytes, out_width, out_height, dst_row_bytes);
         if (opts == (LR_WARP_RAGGED | LR_WARP_PREPARE))
             return ctx_prepare_ragged(c, d_src, src_image_bytes, batch, width, height, src_row_bytes, format & 0xFF, M, d_dst,
@@ -457,7 +535,7 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
     }
     if (format & ~0xFF) {  // option bits above the pixel format
         if ((format & ~0xFF) == LR_WARP_PACKED)
-            return warp_packed(c, d_src, src_image_bytes, batch, width, height, src_row_bytes, format & 0xFF, cubic, border, lens, M, d_dst,
+            return warp_packed(c, d_src, src_image_bytes, batch, width, height, src_row_bytes, format & 0xFF, cubic, border, lens, area, M, d_dst,
                                dst_image_bytes, out_width, out_height, dst_row_bytes);
         if ((format & ~0xFF) == (LR_WARP_PACKED | LR_WARP_PREPARE)) return fail("LR_WARP_PACKED together with LR_WARP_PREPARE");
         if ((format & ~0xFF) != LR_WARP_PREPARE) return fail("unknown option bits in format");
@@ -483,16 +561,18 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
         if (bits & 3u) return fail("f32 pointer or stride not 4-byte aligned");
     }
     const size_t lens_at = border ? 10 : 9;               // (LR_WARP_BORDER: the border word behind the map)
-    const size_t row_doubles = lens_at + (lens ? 9 : 0);  // (LR_WARP_LENS: the nine lens entries behind that)
+    const size_t area_at = lens_at + (lens ? 9 : 0);      // (LR_WARP_LENS: the nine lens entries behind that)
+    const size_t row_doubles = area_at + (area ? 1 : 0);  // (LR_WARP_AREA: the sampling factor at the very end)
     for (size_t b = 0; b < (size_t)batch; ++b)
         for (size_t i = 0; i < 9; ++i)
             if (!std::isfinite(M[b * row_doubles + i])) return fail("M is not finite");
     const int64_t tiles_x = ((int64_t)out_width + kTileW - 1) / kTileW, tiles_y = ((int64_t)out_height + kTileH - 1) / kTileH;
     const int64_t n_tiles = tiles_x * tiles_y * (int64_t)batch;
     if (n_tiles > 0x7FFFFFF0ll) return fail("output larger than 2^31 tiles of 64 x 16 pixels");
-    if (border || lens) {  // the frames as records of the table kernel; where every word is 0 and no frame has a lens, the launch below as without the bits
+    if (border || lens || area) {  // the frames as records of the table kernel; where every word is 0, no frame has a lens and every S is 1, the launch below as without the bits
         std::vector<RaggedFrame> rec((size_t)batch);
         std::vector<LensRecord> lenses(lens ? (size_t)batch : 0);
+        std::vector<AreaRecord> areas(area ? (size_t)batch : 0);
         std::vector<int> start((size_t)batch + 1);
         bool bordered = false;
         for (int b = 0; b < batch; ++b) {
@@ -515,11 +595,14 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
             }
             if (lens)
                 if (const char* why = parse_lens(t + lens_at, &lenses[(size_t)b])) return fail_lens("", b, why);
+            if (area)
+                if (const char* why = parse_area(t[area_at], f.m, (uint64_t)out_width, (uint64_t)out_height, &areas[(size_t)b])) return fail_area("", b, why);
             start[(size_t)b] = (int)(tiles_x * tiles_y * b);
         }
         start[(size_t)batch] = (int)n_tiles;
-        const bool lensed = any_lens(lenses);
-        if (bordered || lensed) return launch_ragged(c, d_src, format, cubic, bordered, rec, start, d_dst, lensed ? &lenses : nullptr);
+        const bool lensed = any_lens(lenses), sampled = any_area(areas);
+        if (bordered || lensed || sampled)
+            return launch_ragged(c, d_src, format, cubic, bordered, rec, start, d_dst, lensed ? &lenses : nullptr, sampled ? &areas : nullptr);
     }
 
     LR_HIP(hipSetDevice(c->device));

@@ -2,6 +2,7 @@
 // LR_WARP_BORDER and all host code) and kernels_warp_border.hip (the kernels with a border rule per frame).  The bordered
 // kernels are a code object of their own, so that the one kernels_warp.hip makes holds exactly the kernels it held before them.
 // kernels_warp_lens.hip (the kernels with a lens model per frame, LR_WARP_LENS) is a third of the same kind.
+// kernels_warp_area.hip (the kernels that average S x S samples per destination pixel, LR_WARP_AREA) is a fourth.
 // Everything here has internal linkage; what kernels_warp.hip says about tiles, records and loads holds for all of them.
 #pragma once
 #include <cstdint>
@@ -22,6 +23,11 @@ void launch_warp_ragged_border(int format, bool cubic, int grid, hipStream_t str
 // records, one per frame; `border`: with the records' border rules
 void launch_warp_ragged_lens(int format, bool cubic, bool border, int grid, hipStream_t stream, const uint8_t* src, int batch,
                              int n_tiles, const void* frames, const void* lenses, const int* start, uint8_t* dst);
+
+// warp_ragged_area_kernel's launch (kernels_warp_area.hip): the same arguments, `areas` the device array of AreaRecord records,
+// one per frame; `lenses` NULL: no frame has a lens; the records' border rules always hold (a zero word is the zero border)
+void launch_warp_ragged_area(int format, bool cubic, int grid, hipStream_t stream, const uint8_t* src, int batch, int n_tiles,
+                             const void* frames, const void* lenses, const void* areas, const int* start, uint8_t* dst);
 
 namespace {
 
@@ -61,6 +67,14 @@ struct LensRecord {
     int pad;
 };
 static_assert(sizeof(LensRecord) == 10 * sizeof(double), "a record per 10 doubles of the mirror");
+
+// LR_WARP_AREA: a frame's sampling factor S (1 .. 8) and its fine map F (lr_area_fine_map of the frame's M and S; S = 1: M)
+struct AreaRecord {
+    double f[9];
+    int s;
+    int pad;
+};
+static_assert(sizeof(AreaRecord) == 10 * sizeof(double), "a record per 10 doubles of the mirror");
 
 struct RaggedArgs {
     const uint8_t* src;
