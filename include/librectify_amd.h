@@ -205,6 +205,25 @@ void lr_set_flood_just_in_time(lr_context* ctx, int on);
  * instead of one team of wavefronts walking it tile after tile through a global slab.  Same labels.  On by default;
  * 0 = the slab walk (comparison), LIBRECTIFY_FLOOD_GIANT_STEP=0 likewise; lr_stage_counters [14] counts the steps. */
 void lr_set_flood_giant_step(lr_context* ctx, int on);
+/* Test hook: the schedule of the flood's rounds.  The parallel flood is exact because a round's result depends neither on the
+ * order nor on the concurrency in which its walks run (DESIGN.md section 7 has the argument, and the table of everything that
+ * reads a list by position); this hook makes both a variable, so that a test can choose them instead of taking what the
+ * hardware gives.
+ *   order: the round's active list as its exploration reads it -- 0 as is, 1 reversed (the exploration reads from the end,
+ *          so this walks the strongest seed first), 2 a permutation that depends only on (seed, the round's index, the list's
+ *          length): position i takes the entry at (a i + b) mod n, a coprime to n (csrc/common.h: flood_schedule_perm;
+ *          librectify_amd.flood_schedule_perm in Python).  A small kernel pair of its own in front of the exploration
+ *          rewrites the list; behind a pending giant step it does nothing, like the round.
+ *   width: workgroups of every launch of a round that walks a list -- the exploration (`width` workgroups for the last
+ *          `width` entries, `width` more that stride over the rest), the second tier's teams, both re-walk launches and the
+ *          partial commits.  0 = each launch's own grid; 1 = a serial round, its walks one after the other in list order.
+ *          The commit pass and the survivors pass keep their grids (they walk no list of seeds in an order that matters).
+ * With the hook set every round brings its `rest` launch, never takes the list's known length for its grid and sets no
+ * barrier for entries "the next round will not reach": that path walks the FIRST entries of a list and counts on the order
+ * the survivors pass left.  (0, 0, 0) -- the default -- enqueues the rounds as ever; the kernels of the rounds are the same
+ * either way.  It applies to single calls and stage calls; the lanes of a batch call ignore it.  lr_stage_counters [10] counts
+ * the rounds enqueued under it.  Same labels whatever the schedule. */
+void lr_set_flood_schedule(lr_context* ctx, int order, uint32_t seed, int width);
 
 /* ---- rectified images ------------------------------------------------------------------ */
 /* The reference demo's last step (autorectify.cpp: homography_from_corners with clip 3.0, then warpPerspective).
@@ -860,8 +879,9 @@ int lr_filter_kernel_ms(lr_context* ctx, float* ms);
 /* Extra counters of the last call: [0] seeds, [1] components, [2] flood rounds, [3] labelled pixels, and how the
  * flood's walks were stored: [4] seeds that moved to the second LDS tier, [5] global slabs used, [6] seeds finished by
  * the ordered single-wave tail (storage exhausted); [7] laps of the frame through the pipeline (1 normally); [8] pixels
- * the flood's explorations walked in all rounds together (over [3]: the re-walk factor), [9] their 8x8-tile steps, [10] retired (always 0:
- * it counted the re-walks from way-points, a path the logs replaced), [11] footprints worked out from a log instead of
+ * the flood's explorations walked in all rounds together (over [3]: the re-walk factor), [9] their 8x8-tile steps, [10] rounds enqueued under
+ * the schedule hook (lr_set_flood_schedule; counted on the host, 0 without the hook; the slot counted re-walks from
+ * way-points once), [11] footprints worked out from a log instead of
  * walked (lr_set_flood_logs), [12] those of them that took the fall-back path (sweeps), [13] walks that outgrew the second
  * tier's table and were held back until their seed was the lowest active one (instead of moving into a global slab),
  * [14] giant steps: floods of the lowest active seed labelled by the whole device (lr_set_flood_giant_step), [15] walks that

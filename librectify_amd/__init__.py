@@ -113,6 +113,36 @@ def split_frames_word(word):
         return (word >> 8) - 1, (word & 0xFF) != 0
     return PIX_F32, word != 0
 
+def _schedule_mix(x):
+    x &= 0xFFFFFFFF
+    x ^= x >> 16
+    x = (x * 0x7FEB352D) & 0xFFFFFFFF
+    x ^= x >> 15
+    x = (x * 0x846CA68B) & 0xFFFFFFFF
+    x ^= x >> 16
+    return x
+
+
+def flood_schedule_perm(n, seed, rnd):
+    """The permutation of Context.set_flood_schedule(2, seed): a list of n positions, p[i] the position of the OLD list whose
+    entry position i of the new list takes in round `rnd` (0-based: the device's count of rounds with work).  The statement of
+    csrc/common.h (flood_schedule_coeffs, flood_schedule_perm) again: i -> (a i + b) mod n, a coprime to n and, from n = 8 on,
+    neither 1 nor n - 1; a and b from a hash of (seed, rnd, n)."""
+    import math
+
+    n, seed, rnd = int(n), int(seed) & 0xFFFFFFFF, int(rnd) & 0xFFFFFFFF
+    if n <= 0:
+        return []
+    h = _schedule_mix(seed ^ _schedule_mix((rnd * 0x9E3779B9 + n) & 0xFFFFFFFF))
+    a = 1
+    if n >= 5 and n != 6:
+        a = 2 + h % (n - 3)
+        while math.gcd(a, n) != 1:
+            a = 2 if a + 1 > n - 2 else a + 1
+    b = _schedule_mix((h + 1) & 0xFFFFFFFF) % n
+    return [(a * i + b) % n for i in range(n)]
+
+
 EXPORTS = [
     "find_line_segment_groups", "release_line_segments", "compute_rectification_transform",
     "compute_rectification_transform_from_vp", "fit_vanishing_point", "assign_to_group",
@@ -123,7 +153,7 @@ EXPORTS = [
     "lr_stage_counters", "lr_filter_kernel_ms", "lr_ransac_best", "lr_estimate_line_pencils",
     "lr_find_line_segment_groups_batch_host", "lr_find_line_segment_groups_batch_host_ptrs", "lr_host_alloc", "lr_host_free",
     "lr_set_seed_capacity", "lr_set_flood_blind_rounds", "lr_set_flood_staged", "lr_set_batch_streams", "lr_device_malloc", "lr_device_free", "lr_memcpy_h2d", "lr_cht_vanishing_point", "lr_refine_lines", "lr_set_estimator", "lr_ht_weights", "lr_prosac_solve", "lr_estimate_line_pencils_prosac", "lr_direct_solve", "lr_estimate_line_pencils_direct",
-    "lr_estimate_line_pencils_cht", "lr_set_stage_timing", "lr_release_thread_context", "lr_set_flood_partial_commits", "lr_set_flood_logs", "lr_set_flood_just_in_time", "lr_set_flood_giant_step", "lr_context_trim", "lr_trim_thread_context",
+    "lr_estimate_line_pencils_cht", "lr_set_stage_timing", "lr_release_thread_context", "lr_set_flood_partial_commits", "lr_set_flood_logs", "lr_set_flood_just_in_time", "lr_set_flood_giant_step", "lr_set_flood_schedule", "lr_context_trim", "lr_trim_thread_context",
     "lr_find_line_segment_groups_batch_host_multi", "lr_memcpy_d2h", "lr_rectification_homography", "lr_warp_perspective_device",
 ]
 
@@ -208,6 +238,8 @@ def lib():
         L.lr_set_flood_logs.restype = None
         L.lr_set_flood_giant_step.argtypes = [C.c_void_p, C.c_int]
         L.lr_set_flood_giant_step.restype = None
+        L.lr_set_flood_schedule.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_int]
+        L.lr_set_flood_schedule.restype = None
         L.lr_set_flood_just_in_time.argtypes = [C.c_void_p, C.c_int]
         L.lr_set_flood_just_in_time.restype = None
         L.lr_release_thread_context.argtypes = []
@@ -1014,7 +1046,7 @@ class Context:
         _check(lib().lr_stage_counters(self._h, _ptr(c), 16))
         return dict(seeds=int(c[0]), components=int(c[1]), flood_rounds=int(c[2]), labelled_px=int(c[3]),
                     second_tier_seeds=int(c[4]), slabs=int(c[5]), ordered_tail_seeds=int(c[6]), frame_laps=int(c[7]),
-                    walked_px=int(c[8]), walk_steps=int(c[9]), log_rewalks=int(c[11]), log_give_ups=int(c[12]), giants_held=int(c[13]), giant_steps=int(c[14]),
+                    walked_px=int(c[8]), walk_steps=int(c[9]), scheduled_rounds=int(c[10]), log_rewalks=int(c[11]), log_give_ups=int(c[12]), giants_held=int(c[13]), giant_steps=int(c[14]),
                     quiet_round_misses=int(c[15]))
 
     # ---- full path ----
@@ -2077,6 +2109,12 @@ class Context:
     def set_flood_logs(self, on=1):
         """0 = off, 1 = on (default for single calls), 2 = on with every log through the fall-back path (test hook)."""
         lib().lr_set_flood_logs(self._h, int(on))
+
+    def set_flood_schedule(self, order=0, seed=0, width=0):
+        """Test hook: the order of a flood round's active list (0 as is, 1 reversed, 2 flood_schedule_perm of (seed, round,
+        length)) and the workgroups of every launch that walks it (0: its own grid, 1: a serial round).  Single calls and stage
+        calls; stage_counters()["scheduled_rounds"] counts the rounds enqueued under it."""
+        lib().lr_set_flood_schedule(self._h, int(order), int(seed) & 0xFFFFFFFF, int(width))
 
     def set_stage_timing(self, on=True):
         """stage timers of the frame calls (off by default: each event record idles the GPU for a few microseconds)"""

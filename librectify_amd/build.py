@@ -14,6 +14,7 @@ SOURCES = [
     "kernels_filter.hip",
     "kernels_seeds.hip",
     "kernels_flood.hip",
+    "kernels_flood_order.hip",
     "kernels_fit.hip",
     "kernels_ransac.hip",
     "kernels_groups.hip",

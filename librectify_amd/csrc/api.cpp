@@ -1,5 +1,6 @@
 // C ABI of librectify_amd.so: the reference's six functions (include/librectify.h) and the
 // lr_* extensions (include/librectify_amd.h).
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -443,6 +444,11 @@ void lr_set_flood_logs(lr_context* ctx, int on) {
     ctx->opt.flood_logs = on != 0;
     ctx->opt.flood_log_sweep = on == 2;
 }
+void lr_set_flood_schedule(lr_context* ctx, int order, uint32_t seed, int width) {
+    ctx->flood_sched_order = (order == 1 || order == 2) ? order : 0;
+    ctx->flood_sched_seed = seed;
+    ctx->flood_sched_width = (uint32_t)std::min(std::max(width, 0), 1 << 20);
+}
 
 int lr_stage_filter(lr_context* ctx, const float* d_image, int width, int height, int stride) {
     try {
@@ -553,7 +559,7 @@ int lr_stage_counters(lr_context* ctx, int64_t* out, int count) {
                                (int64_t)ctx->flood_tiers[2], (int64_t)ctx->frame_laps,
                                (int64_t)(((uint64_t)ctx->flood_tiers[5] << 32) | ctx->flood_tiers[4]),
                                (int64_t)(((uint64_t)ctx->flood_tiers[7] << 32) | ctx->flood_tiers[6]),
-                               0 /* [10]: retired */, (int64_t)ctx->flood_tiers[10], (int64_t)ctx->flood_tiers[11], (int64_t)ctx->flood_tiers[12],
+                               (int64_t)ctx->flood_tiers[9] /* [10]: rounds under the schedule hook */, (int64_t)ctx->flood_tiers[10], (int64_t)ctx->flood_tiers[11], (int64_t)ctx->flood_tiers[12],
                                (int64_t)ctx->flood_tiers[13], (int64_t)ctx->flood_tiers[15]};
         for (int i = 0; i < count && i < 16; ++i) out[i] = v[i];
         return 0;

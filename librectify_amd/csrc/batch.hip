@@ -49,6 +49,7 @@ public:
             // Measured (profiles/r04_flood_logs.txt, section 9): 9.93 -> 10.29 Gpix/s from pageable frames, 11.7 -> 12.1 from
             // resident ones -- a frame of a lane no longer drags 3-4 rounds of empty launches through its stream.
             l->flood_jit_sleep_us = S == 1 ? 0 : 20;
+            l->flood_sched_off = true;  // (the schedule hook is for single calls and stage calls: the caller's own is lane 0)
             // LIBRECTIFY_LANES_SLEEP: the lanes sleep on an event instead of spinning in hipStreamSynchronize, for hosts
             // short of cores (on the 16-core share of a one-GPU box: pageable frames equal, page-locked ones 5 % slower)
             static const bool sleep_env = std::getenv("LIBRECTIFY_LANES_SLEEP") != nullptr;
@@ -62,6 +63,7 @@ public:
         for (lr_context* l : lanes) {
             l->sleep_in_wait = false;
             l->keep_workspace = false;
+            l->flood_sched_off = false;
         }
         c->flood_logbig_off = false;
         c->flood_log_min = c->flood_log_walk = 0;

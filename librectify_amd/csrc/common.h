@@ -195,7 +195,55 @@ struct FloodBuffers {
     int jit_sleep_us = 0;               // the polling thread sleeps this long between looks (0: it spins -- single calls)
     uint32_t big_cap_override = 0;  // test hook: seeds per round the second tier takes (0 = the default, 8192)
     uint32_t team_tile_cap = 0;     // test hook: tiles after which the second tier's team hands a walk to a slab (0 = its table)
+    // Test hook (lr_set_flood_schedule; kernels_flood.hip: enqueue_round, kernels_flood_order.hip): the order of a round's
+    // active list as its exploration reads it (0 as is, 1 reversed, 2 a permutation of (sched_seed, round, length)) and the
+    // workgroups every list-walking launch of a round gets (0: its own grid; 1: the round's walks one after the other).
+    // All zero: the rounds are enqueued as ever.  The lanes of a batch call never see it.
+    int sched_order = 0;
+    uint32_t sched_seed = 0;
+    uint32_t sched_width = 0;
 };
+inline bool flood_scheduled(const FloodBuffers& B) { return B.sched_order != 0 || B.sched_width != 0u; }
+// kernels_flood_order.hip: puts the list that the control block's round counter selects into the hook's order, through the
+// other list and back (nothing reads that one between a round's start and its survivors pass).  Two launches on s; each
+// leaves at once behind a pending giant step or an empty list.  cap: entries either list holds.
+void launch_flood_order(const FloodBuffers& B, uint32_t cap, hipStream_t s);
+// the words of the control block that launch reads (kernels_flood.hip holds the whole layout and checks these against it)
+constexpr int kFloodCtrlNAct = 2, kFloodCtrlRounds = 7, kFloodCtrlGiantStep = 38;
+// The hook's permutation: position i of the new list takes the entry at flood_schedule_perm(i, ...) of the old one.  A bijection
+// of [0, n) for every n: i -> (a i + b) mod n with a coprime to n, a and b from a hash of (seed, round, n); for n >= 8 a is
+// neither 1 nor n - 1, so the map is neither the identity nor the reversal whatever b is.  (n = 1 .. 4 and 6 have no such
+// multiplier: a = 1, a rotation.)  The Python statement is librectify_amd.flood_schedule_perm.
+__host__ __device__ inline uint32_t flood_schedule_mix(uint32_t x) {
+    x ^= x >> 16;
+    x *= 0x7FEB352Du;
+    x ^= x >> 15;
+    x *= 0x846CA68Bu;
+    x ^= x >> 16;
+    return x;
+}
+__host__ __device__ inline void flood_schedule_coeffs(uint32_t seed, uint32_t round, uint32_t n, uint32_t* a_out, uint32_t* b_out) {
+    const uint32_t h = flood_schedule_mix(seed ^ flood_schedule_mix(round * 0x9E3779B9u + n));
+    uint32_t a = 1u;
+    if (n >= 5u && n != 6u) {
+        a = 2u + h % (n - 3u);  // 2 .. n - 2
+        for (;;) {
+            uint32_t x = a, y = n;
+            while (y != 0u) {
+                const uint32_t t = x % y;
+                x = y;
+                y = t;
+            }
+            if (x == 1u) break;
+            a = a + 1u > n - 2u ? 2u : a + 1u;
+        }
+    }
+    *a_out = a;
+    *b_out = n ? flood_schedule_mix(h + 1u) % n : 0u;
+}
+__host__ __device__ inline uint32_t flood_schedule_perm(uint32_t i, uint32_t a, uint32_t b, uint32_t n) {
+    return (uint32_t)(((unsigned long long)a * i + b) % n);
+}
 // What a frame hands to the flood.  The seed count stays on the device (*d_n_seeds, clamped to seed_cap, the
 // capacity the seed sort ran with): launches are sized by seed_cap.
 struct FloodFrame {
@@ -222,6 +270,7 @@ struct FloodProgress {
     // (sizes_known = false: blind rounds, or a flood that flood_finish had to complete; max_flood: 0 or "more than 2^14 pixels")
     bool sizes_known = false;
     uint32_t max_flood = 0;
+    uint32_t scheduled = 0;  // rounds enqueued under the schedule hook (FloodBuffers::sched_order): lr_stage_counters [10]
 };
 constexpr int kFloodCtrlWords = 56;
 // Enqueues the initialisation and a first batch of rounds, then an asynchronous copy of the control block into
@@ -232,7 +281,7 @@ int flood_enqueue(const FloodBuffers& B, const FloodFrame& F, FloodProgress* P, 
 int flood_finish(const FloodBuffers& B, const FloodFrame& F, FloodProgress* P, uint32_t* h_ctrl, int* rounds_out,
                  uint32_t* tiers_out /* [14]: seeds moved to the second tier, slabs used, seeds left to the ordered tail,
                                         hold-back engaged, pixels walked (lo, hi), tile steps (lo, hi), ... giant steps;
-                                        [9] is retired and always 0 */,
+                                        [9] rounds enqueued under the schedule hook (counted on the host) */,
                  bool* extra, hipStream_t s);
 
 // kernels_fit.hip (all counts stay on the device: launches cover seed_cap / comp_cap)

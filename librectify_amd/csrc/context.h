@@ -248,7 +248,7 @@ struct lr_context {
     int flood_staged_streak = 0;     // frames in a row that started staged (every sixteenth starts without the hint)
     bool flood_staged_hint = false;  // was the last frame one of overlapping giants (kernels_flood.hip: kCtrlStaged)?  Then this one starts on its strongest quarter
     bool flood_calm_hint = false;      // the last frame's walks all stayed in the first storage tier (FloodBuffers::calm_hint)
-    uint32_t flood_tiers[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // last flood: seeds in the second tier, slabs used, seeds of the ordered tail, hold-back, walked px (lo, hi), steps (lo, hi), walks beyond the first tier's table, 0 (retired), re-walks from logs, logs given up, giants held back
+    uint32_t flood_tiers[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // last flood: seeds in the second tier, slabs used, seeds of the ordered tail, hold-back, walked px (lo, hi), steps (lo, hi), walks beyond the first tier's table, rounds enqueued under the schedule hook, re-walks from logs, logs given up, giants held back
     lramd::Event ev[16];  // stage timers (Settings::timing_on)
     float stage_ms[LR_T_COUNT] = {};
     double host_ms[3] = {0, 0, 0};  // last frame: enqueue, next-frame staging + upload, wait (LIBRECTIFY_LANE_DEBUG)
@@ -256,6 +256,11 @@ struct lr_context {
     bool dmask_consumed = false;  // the parallel flood clears the mask of labelled pixels: LR_BUF_DMASK is then stale
     // (last: the members above keep the places they had before it came)
     lramd::JpegDecodeStore jpeg_decode;
+    // test hook (lr_set_flood_schedule; FloodBuffers::sched_order): the caller's single calls and stage calls only -- not part
+    // of Settings, so no lane or peer gets it, and a batch call switches its caller's off while it runs (batch.hip: LaneSet)
+    int flood_sched_order = 0;
+    uint32_t flood_sched_seed = 0, flood_sched_width = 0;
+    bool flood_sched_off = false;
 };
 
 namespace lramd {

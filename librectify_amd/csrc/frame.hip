@@ -69,6 +69,11 @@ FloodBuffers flood_buffers_for(lr_context* c) {
     fbuf.partial_commits = !partial_off && c->opt.flood_partial;
     fbuf.rewalk_logs = c->opt.flood_logs;
     fbuf.log_sweep = c->opt.flood_log_sweep;
+    if (!c->flood_sched_off) {  // (test hook lr_set_flood_schedule: single calls and stage calls)
+        fbuf.sched_order = c->flood_sched_order;
+        fbuf.sched_seed = c->flood_sched_seed;
+        fbuf.sched_width = c->flood_sched_width;
+    }
     fbuf.log_min_tiles = c->flood_log_min;
     fbuf.log_walk_tiles = c->flood_log_walk;
     fbuf.giant_hold = c->opt.flood_mode == 1;  // (the storage test hooks -- modes 2-7 -- keep their slabs)

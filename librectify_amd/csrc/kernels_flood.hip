@@ -326,6 +326,8 @@ enum {
     kCtrlWords = 56,
 };
 static_assert(kCtrlWords == kFloodCtrlWords, "control block size");
+static_assert(kCtrlNAct == kFloodCtrlNAct && kCtrlRounds == kFloodCtrlRounds && kCtrlGiantStep == kFloodCtrlGiantStep,
+              "the words kernels_flood_order.hip reads");
 
 // Frontier records, table entries and ballots are the same in all 64 lanes.  Saying so (readfirstlane) lets the
 // compiler keep them in SGPRs and run the bit-board logic on the scalar unit instead of the vector ALU.
@@ -3503,8 +3505,18 @@ FloodArgs flood_args(const FloodBuffers& B, const FloodFrame& F, bool use_big) {
 // unordered list could leave the lowest active seed unwalked, move nothing, and send the frame to the ordered tail.)
 constexpr uint32_t kFullGridCap = 1u << 18;
 constexpr int kRestRounds = 4;  // rounds 0 .. kRestRounds - 1 always bring their `rest` launch: the rounds a frame may enqueue blindly (frame.hip: flood_buffers_for, kJitFirstMax)
+//
+// The schedule hook (FloodBuffers::sched_order, sched_width; lr_set_flood_schedule) chooses what the hardware otherwise does: the
+// list's order (a launch pair of kernels_flood_order.hip in front of the exploration) and the number of workgroups of every
+// launch that walks a list.  The main exploration takes ONE entry per workgroup, so `width` workgroups walk the last `width`
+// entries and the `rest` launch -- `width` workgroups, first = width -- strides over the others; the team, both re-walk
+// instances and the partial commits stride over their lists whatever their grid.  The commit pass and the survivors pass keep
+// their grids: the first walks marked runs of pixels, not a list, and the second reads every entry once and appends in the
+// order of arrival (DESIGN.md section 7 has the table of readers).  Under the hook every round brings its `rest` launch, its
+// grid is never the list's known length, and no barrier stands for entries "the next round will not reach": the path that
+// walks the FIRST entries of a list (explore_body: fwd, next_reach) counts on the order the survivors pass left.
 void enqueue_round(const FloodBuffers& B, const FloodFrame& F, const FloodArgs& A0, bool use_big, int index, hipStream_t s,
-                   uint32_t known_len = 0xFFFFFFFFu, bool next_known = false) {
+                   FloodProgress* P, uint32_t known_len = 0xFFFFFFFFu, bool next_known = false) {
     // (which of the two active lists a round reads is the device's business -- kCtrlRounds, act_now: rounds enqueued behind a
     // request for a giant step do nothing and do not count; `index` only sizes grids and picks the launches of a round)
     const size_t npix = (size_t)F.w * F.h;
@@ -3538,26 +3550,32 @@ void enqueue_round(const FloodBuffers& B, const FloodFrame& F, const FloodArgs& 
     // (a round enqueued with its list's length known takes a grid of exactly that many workgroups: the guess is cap / 4 in the
     // late rounds, some 14 000 workgroups that leave at once for a list of a few hundred, and the dispatcher's time is the
     // one thing all the frames in flight share)
-    const bool exact = known_len < 0xFFFFFFFEu && known_len <= F.seed_cap && !(test_grid > 0 && index >= kRestRounds);
-    const uint32_t grid = exact ? std::max<uint32_t>(known_len, 1u) : grid_of(index);
-    const bool rest_now = !exact && (has_rest(index) || (known_len != 0xFFFFFFFFu && known_len > grid));
+    const bool sched = flood_scheduled(B);
+    const uint32_t width = B.sched_width;  // (0: every launch keeps its grid)
+    const bool exact = !sched && known_len < 0xFFFFFFFEu && known_len <= F.seed_cap && !(test_grid > 0 && index >= kRestRounds);
+    const uint32_t grid = width ? width : exact ? std::max<uint32_t>(known_len, 1u) : grid_of(index);
+    const bool rest_now = sched || (!exact && (has_rest(index) || (known_len != 0xFFFFFFFFu && known_len > grid)));
     FloodArgs A = A0;
     A.no_rest = (grid < F.seed_cap && !rest_now && !exact) ? 1u : 0u;
-    A.next_reach = (grid_of(index + 1) < F.seed_cap && !has_rest(index + 1) && !next_known) ? grid_of(index + 1) : 0xFFFFFFFFu;
+    A.next_reach = (grid_of(index + 1) < F.seed_cap && !has_rest(index + 1) && !next_known && !sched) ? grid_of(index + 1) : 0xFFFFFFFFu;
     // (walks leave logs from the first round on, the rounds after it use them)
     const bool logs = A.log_min_tiles != 0xFFFFFFFFu;
     A.log_use = (logs && index >= 1) ? 1u : 0u;
+    if (sched) {
+        P->scheduled += 1u;
+        launch_flood_order(B, F.seed_cap, s);
+    }
     hipLaunchKernelGGL(flood_explore_kernel, dim3(grid), dim3(64), 0, s, A, F.trig, B.big_list);
     if (rest_now)  // entries past the guess, if any
-        hipLaunchKernelGGL(flood_explore_rest_kernel, dim3(1024), dim3(64), 0, s, A, F.trig, B.big_list, grid);
+        hipLaunchKernelGGL(flood_explore_rest_kernel, dim3(width ? width : 1024u), dim3(64), 0, s, A, F.trig, B.big_list, grid);
     if (use_big)
-        hipLaunchKernelGGL(flood_explore_team_kernel, dim3(std::min<uint32_t>(F.seed_cap, kTeamGrid)), dim3(64 * kTeamWaves),
+        hipLaunchKernelGGL(flood_explore_team_kernel, dim3(width ? width : std::min<uint32_t>(F.seed_cap, kTeamGrid)), dim3(64 * kTeamWaves),
                            kTeamLdsBytes, s, A, F.trig, B.big_list);
     if (logs && index >= 1)
-        hipLaunchKernelGGL((flood_rewalk_kernel<kRewalkThreads, kRewalkTiles>), dim3(std::min<uint32_t>(F.seed_cap, kRewalkGrid)), dim3(kRewalkThreads),
+        hipLaunchKernelGGL((flood_rewalk_kernel<kRewalkThreads, kRewalkTiles>), dim3(width ? width : std::min<uint32_t>(F.seed_cap, kRewalkGrid)), dim3(kRewalkThreads),
                            rewalk_lds_bytes<kRewalkTiles>(), s, A, B.rewalk_list, 1u);
     if (logs && index >= 1 && A.log_max_len > (uint32_t)kRewalkTiles)
-        hipLaunchKernelGGL((flood_rewalk_kernel<kRewalkThreadsBig, kRewalkTilesBig>), dim3(std::min<uint32_t>(F.seed_cap, 1024u)),
+        hipLaunchKernelGGL((flood_rewalk_kernel<kRewalkThreadsBig, kRewalkTilesBig>), dim3(width ? width : std::min<uint32_t>(F.seed_cap, 1024u)),
                            dim3(kRewalkThreadsBig), rewalk_lds_bytes<kRewalkTilesBig>(), s, A, B.rewalk_list, (uint32_t)kRewalkTiles + 1u);
     if (g_flood_debug) (void)hipEventRecord(dbg1, s);
     if (g_flood_debug) {
@@ -3617,6 +3635,7 @@ void enqueue_giant_step(const FloodBuffers& B, const FloodFrame& F, const FloodA
 // its own: the caller goes on enqueuing the later stages and looks at the control block when the frame is done.
 int flood_enqueue(const FloodBuffers& B, const FloodFrame& F, FloodProgress* P, uint32_t* h_ctrl, hipStream_t s) {
     P->enqueued = 0;
+    P->scheduled = 0;
     P->sizes_known = false;
     P->max_flood = 0;
     P->use_big = B.second_tier && B.second_tier_from_start;
@@ -3694,7 +3713,7 @@ int flood_enqueue(const FloodBuffers& B, const FloodFrame& F, FloodProgress* P, 
         }
         for (int r = 0; r < first; ++r, ++P->enqueued) {
             const bool q = quiet && r >= 1;
-            enqueue_round(B, F, q ? A_quiet : A, q ? false : P->use_big, P->enqueued, s, 0xFFFFFFFFu, r == first - 1);
+            enqueue_round(B, F, q ? A_quiet : A, q ? false : P->use_big, P->enqueued, s, P, 0xFFFFFFFFu, r == first - 1);
         }
         // Rounds that count on the device (kCtrlRounds) against rounds enqueued that can still count: a round enqueued behind a
         // request for a giant step does nothing, so once a request is seen every round enqueued so far is accounted for.
@@ -3773,7 +3792,7 @@ int flood_enqueue(const FloodBuffers& B, const FloodFrame& F, FloodProgress* P, 
             }
             if (timed_out) {
                 // (with the `rest` launch whatever the list's length: the round before them was told its successor would know)
-                for (int k = 0; k < 2; ++k, ++P->enqueued) enqueue_round(B, F, A, P->use_big, P->enqueued, s, 0xFFFFFFFEu, true);
+                for (int k = 0; k < 2; ++k, ++P->enqueued) enqueue_round(B, F, A, P->use_big, P->enqueued, s, P, 0xFFFFFFFEu, true);
                 break;
             }
             if (r.n_left == 0u && !r.stalled) {  // the flood is over, and the report says whether it committed a huge flood
@@ -3791,14 +3810,14 @@ int flood_enqueue(const FloodBuffers& B, const FloodFrame& F, FloodProgress* P, 
                 A_calm = flood_args(B, F, false);
                 A_calm.win_shift = A.win_shift;
             }
-            if (calm) enqueue_round(B, F, A_calm, false, P->enqueued, s, r.n_left, true);
-            else enqueue_round(B, F, A, P->use_big, P->enqueued, s, r.n_left, true);
+            if (calm) enqueue_round(B, F, A_calm, false, P->enqueued, s, P, r.n_left, true);
+            else enqueue_round(B, F, A, P->use_big, P->enqueued, s, P, r.n_left, true);
             ++P->enqueued;
             ++counting;
         }
     } else {
     const int batch = g_flood_debug ? 1 : std::min(std::max(B.blind_rounds, 1), 16);
-    for (int r = 0; r < batch; ++r, ++P->enqueued) enqueue_round(B, F, A, P->use_big, P->enqueued, s);
+    for (int r = 0; r < batch; ++r, ++P->enqueued) enqueue_round(B, F, A, P->use_big, P->enqueued, s, P);
     }
     // (the host saw the flood end: the round that ended it has written the control block to B.host_ctrl itself)
     if (!(ended_in_sight && A.host_ctrl == h_ctrl))
@@ -3836,7 +3855,7 @@ int flood_finish(const FloodBuffers& B, const FloodFrame& F, FloodProgress* P, u
         if (h_ctrl[kCtrlGiantStep] != 0u && A.giant_step != 0u) enqueue_giant_step(B, F, A, s);
         // (these rounds always bring their `rest` launch: the rounds before them may have been told that their successor would
         // know its list's length, and a flood that is still going after its first laps has long lists to walk)
-        for (int r = 0; r < batch; ++r, ++P->enqueued) enqueue_round(B, F, A, P->use_big, P->enqueued, s, 0xFFFFFFFEu, true);
+        for (int r = 0; r < batch; ++r, ++P->enqueued) enqueue_round(B, F, A, P->use_big, P->enqueued, s, P, 0xFFFFFFFEu, true);
         LR_HIP(hipMemcpyAsync(h_ctrl, B.ctrl, kCtrlWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         LR_HIP(hipStreamSynchronize(s));
     }
@@ -3873,7 +3892,7 @@ int flood_finish(const FloodBuffers& B, const FloodFrame& F, FloodProgress* P, u
         tiers_out[6] = h_ctrl[kCtrlSteps];
         tiers_out[7] = h_ctrl[kCtrlSteps + 1];
         tiers_out[8] = h_ctrl[kCtrlBigLong];
-        tiers_out[9] = 0u;  // (retired: re-walks from way-points)
+        tiers_out[9] = P->scheduled;  // (rounds enqueued under the schedule hook, counted by enqueue_round; it counted re-walks from way-points once)
         tiers_out[10] = h_ctrl[kCtrlLogWalks];
         tiers_out[11] = h_ctrl[kCtrlLogGiveUp];
         tiers_out[12] = h_ctrl[kCtrlGiants];

@@ -52,7 +52,7 @@ def test_library_exports_nothing_but_the_declared_symbols(L):
     out = subprocess.run(["nm", "-D", "--defined-only", L.LIB_PATH], capture_output=True, text=True, check=True).stdout
     exported = sorted(line.split()[-1] for line in out.splitlines() if line.strip())
     assert exported == _declared_functions(), sorted(set(exported) ^ set(_declared_functions()))
-    assert len(exported) <= 60
+    assert len(exported) <= 61  # (60 until lr_set_flood_schedule)
 
 
 # The environment variables the library reads: switches a caller or a test may set, and diagnostic printers.  Every other

@@ -844,7 +844,10 @@ def test_lanes_of_a_batch_on_frames_of_every_kind_equal_the_oracle(L, ctx):
             ctx.set_flood_just_in_time(jit)
             out, n, _ = ctx.find_line_segment_groups_batch_host(frames, 10.24, capacity=8192, num_threads=4)
             for k, i in enumerate(order):
-                _assert_lines_equal(out[k][: n[k]], refs[i])
+                try:
+                    _assert_lines_equal(out[k][: n[k]], refs[i])
+                except AssertionError as e:  # (docs/flood_history.md: this test has failed once, and its message did not say where)
+                    raise AssertionError("%d lanes, just in time %s, frame %d of the call (kind %d): %s" % (lanes, jit, k, i, str(e)[:400])) from e
     finally:
         ctx.set_flood_just_in_time(True)
         ctx.set_batch_streams(3)
