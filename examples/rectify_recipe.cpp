@@ -7,7 +7,8 @@
 //   rectify_recipe in.pgm|in.ppm out_prefix [--max-size N|fraction] [--refine] [--threads N]
 //                  [--h-strategy rotate_h|rotate_v|rectify|keep] [--v-strategy ...] [--warp] [--device-prepare] [--lines]
 //                  [--jpeg Q] [--optimize] [--jpeg-in] [--orient] [--any-sampling] [--scale N] [--cubic] [--border MODE[:VALUE]] [--crop]
-//                  [--lens fx,fy,cx,cy,k1,k2,p1,p2,k3] [--out-max N]
+//                  [--lens fx,fy,cx,cy,k1,k2,p1,p2,k3[,k4,k5,k6,s1,s2,s3,s4,model]] [--fisheye fx,fy,cx,cy,k1,k2,k3,k4]
+//                  [--lens-scale S] [--out-max N]
 //
 // Input is a binary PGM (P5, 8 bit) or PPM (P6, 8 bit; converted with the usual integer luma weights
 // (4899 R + 9617 G + 1868 B + 8192) >> 14).  Image decoding stays with the caller's imaging library.
@@ -53,7 +54,12 @@
 // vector, OpenCV's, in the pixel units of the frame as read (LR_WARP_LENS).  One warp with the identity map and the lens writes
 // the frame without its distortion; prescale, detector and the CSV files work on that one, so segments and transform are in
 // ideal coordinates (lr_lens_distort takes a point back onto the photograph); the rectified picture is then warped from the
-// frame AS READ with the lens and the homography: one resampling.
+// frame AS READ with the lens and the homography: one resampling.  Seventeen values instead of nine (k4, k5, k6, s1, s2, s3,
+// s4 and the model behind k3) are OpenCV's rational and thin-prism model, or with model 1 cv::fisheye's (LR_WARP_LENS_MODEL).
+// --fisheye fx,fy,cx,cy,k1,k2,k3,k4: cv::fisheye's camera matrix and D, the same as --lens with model 1.
+// --lens-scale S (with --lens or --fisheye; S > 0): prescale and detector see the ideal picture scaled by S about (cx, cy) --
+// below 1 brings more of a fisheye's view into the frame -- and the rectified picture's map goes through the same scaling.
+// Segments and transform are then in the scaled ideal picture's coordinates.
 // Links against librectify_amd.so exactly like a program written for the reference.
 #include <algorithm>
 #include <cctype>
@@ -299,11 +305,30 @@ struct Border {
     unsigned v[3] = {0, 0, 0};
 };
 
-// lens: --lens's nine entries, or null; they travel behind the border word (LR_WARP_LENS).  out_max: --out-max's bound, or 0;
+// --lens, --fisheye and --lens-scale: the frame's lens entries, nine (LR_WARP_LENS) or seventeen (with LR_WARP_LENS_MODEL), and
+// the scale s of the ideal picture about (cx, cy) that the detector sees
+struct LensArg {
+    double v[17];
+    int n = 0;  // 0: no lens
+    double scale = 1.0;
+    int bits() const { return n == 17 ? LR_WARP_LENS | LR_WARP_LENS_MODEL : LR_WARP_LENS; }
+    // the map from the scaled ideal picture to the ideal picture, [[1/s, 0, cx (1 - 1/s)], [0, 1/s, cy (1 - 1/s)], [0, 0, 1]],
+    // in front of M: every product and sum rounded on its own, as the Python package composes them
+    void scaled(double* M) const {
+        if (scale == 1.0) return;
+        const double q = 1.0 / scale, tx = v[2] * (1.0 - q), ty = v[3] * (1.0 - q);
+        for (int j = 0; j < 3; ++j) {
+            M[j] = q * M[j] + tx * M[6 + j];
+            M[3 + j] = q * M[3 + j] + ty * M[6 + j];
+        }
+    }
+};
+
+// lens: the frame's lens, or null; its entries travel behind the border word.  out_max: --out-max's bound, or 0;
 // the sampling factor travels at the very end (LR_WARP_AREA), and H, ow, oh are the small picture's.
 bool warp_frame(const Gray& g, const ImageTransform& t, const std::string& prefix, std::vector<uint8_t>& out, int& ow, int& oh,
-                double* H, int jpeg, bool optimize, bool cubic, const Border* border, bool crop, const double* lens, int out_max) {
-    double M[20];  // (the tenth: the border word of LR_WARP_BORDER; then nine: the lens of LR_WARP_LENS; the last: LR_WARP_AREA's S)
+                double* H, int jpeg, bool optimize, bool cubic, const Border* border, bool crop, const LensArg* lens, int out_max) {
+    double M[28];  // (the tenth: the border word of LR_WARP_BORDER; then nine or seventeen: the lens; the last: LR_WARP_AREA's S)
     lr_context* ctx = nullptr;
     void* d_src = nullptr;
     void* d_dst = nullptr;
@@ -327,8 +352,8 @@ bool warp_frame(const Gray& g, const ImageTransform& t, const std::string& prefi
         options |= LR_WARP_BORDER;
     }
     if (lens) {
-        std::memcpy(M + (border ? 10 : 9), lens, 9 * sizeof(double));
-        options |= LR_WARP_LENS;
+        std::memcpy(M + (border ? 10 : 9), lens->v, (size_t)lens->n * sizeof(double));
+        options |= lens->bits();
     }
     if (ok && out_max > 0) {
         int S = 1;
@@ -338,9 +363,10 @@ bool warp_frame(const Gray& g, const ImageTransform& t, const std::string& prefi
             return false;
         }
         std::printf("out-max %d: %dx%d written as %dx%d, %d x %d samples per pixel\n", out_max, full_w, full_h, ow, oh, S, S);
-        M[9 + (border ? 1 : 0) + (lens ? 9 : 0)] = (double)S;
+        M[9 + (border ? 1 : 0) + (lens ? lens->n : 0)] = (double)S;
         options |= LR_WARP_AREA;
     }
+    if (ok && lens) lens->scaled(M);  // (H, the lines and the transform stay in the scaled ideal picture's coordinates)
     ok = ok && lr_context_create(0, &ctx) == 0;
     if (ok) {
         out.resize((size_t)ow * oh * bpp);
@@ -371,11 +397,12 @@ bool warp_frame(const Gray& g, const ImageTransform& t, const std::string& prefi
     return true;
 }
 
-// --lens: the frame without its distortion (the identity map, bilinear, zero border: LR_WARP_LENS), for prescale and detector.
-// Returns false with the reason on stderr.
-bool undistort_frame(const Gray& g, const double* lens, Gray& out) {
-    double M[18] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    std::memcpy(M + 9, lens, 9 * sizeof(double));
+// --lens: the frame without its distortion (the identity map or --lens-scale's, bilinear, zero border: LR_WARP_LENS), for
+// prescale and detector.  Returns false with the reason on stderr.
+bool undistort_frame(const Gray& g, const LensArg& lens, Gray& out) {
+    double M[26] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    lens.scaled(M);
+    std::memcpy(M + 9, lens.v, (size_t)lens.n * sizeof(double));
     lr_context* ctx = nullptr;
     void* d_src = nullptr;
     void* d_dst = nullptr;
@@ -387,7 +414,7 @@ bool undistort_frame(const Gray& g, const double* lens, Gray& out) {
     const bool ok = lr_context_create(0, &ctx) == 0 && lr_device_malloc(ctx, g.raw.size(), &d_src) == 0 &&
                     lr_device_malloc(ctx, g.raw.size(), &d_dst) == 0 && lr_memcpy_h2d(ctx, d_src, g.raw.data(), g.raw.size()) == 0 &&
                     lr_warp_perspective_device(ctx, d_src, g.raw.size(), 1, g.w, g.h, (size_t)g.w * bpp,
-                                               (g.ch == 3 ? LR_PIX_U8X3 : LR_PIX_U8) | LR_WARP_LENS, M, d_dst, g.raw.size(), g.w, g.h,
+                                               (g.ch == 3 ? LR_PIX_U8X3 : LR_PIX_U8) | lens.bits(), M, d_dst, g.raw.size(), g.w, g.h,
                                                (size_t)g.w * bpp) == 0 &&
                     lr_memcpy_d2h(ctx, out.raw.data(), d_dst, out.raw.size()) == 0;
     if (!ok) std::fprintf(stderr, "undistorting failed: %s\n", lr_last_error());
@@ -406,16 +433,42 @@ bool undistort_frame(const Gray& g, const double* lens, Gray& out) {
     return true;
 }
 
-// --lens's argument: nine numbers separated by commas, all finite, fx and fy above 0
-bool parse_lens(const char* text, double* lens) {
+// `count` numbers separated by commas, all finite; returns how many there were (0: a fault, or more than `most`)
+int parse_numbers(const char* text, double* out, int most) {
     const char* p = text;
-    for (int i = 0; i < 9; ++i) {
+    for (int i = 0; i < most; ++i) {
         char* end = nullptr;
-        lens[i] = std::strtod(p, &end);
-        if (end == p || !std::isfinite(lens[i]) || *end != (i < 8 ? ',' : '\0')) return false;
+        out[i] = std::strtod(p, &end);
+        if (end == p || !std::isfinite(out[i])) return 0;
+        if (*end == '\0') return i + 1;
+        if (*end != ',') return 0;
         p = end + 1;
     }
-    return lens[0] > 0.0 && lens[1] > 0.0;
+    return 0;
+}
+
+// --lens's argument: nine numbers (LR_WARP_LENS) or seventeen (LR_WARP_LENS_MODEL: the last is the model, 0 or 1, and a
+// fisheye's entries [8..15] are zero), fx and fy above 0
+bool parse_lens(const char* text, LensArg& lens) {
+    const int n = parse_numbers(text, lens.v, 17);
+    if ((n != 9 && n != 17) || !(lens.v[0] > 0.0) || !(lens.v[1] > 0.0)) return false;
+    if (n == 17) {
+        if (lens.v[16] != 0.0 && lens.v[16] != 1.0) return false;
+        for (int i = 8; i < 16; ++i)
+            if (lens.v[16] == 1.0 && lens.v[i] != 0.0) return false;
+    }
+    lens.n = n;
+    return true;
+}
+
+// --fisheye's argument: fx,fy,cx,cy,k1,k2,k3,k4 of cv::fisheye, as the seventeen entries of model 1
+bool parse_fisheye(const char* text, LensArg& lens) {
+    double v[8];
+    if (parse_numbers(text, v, 8) != 8 || !(v[0] > 0.0) || !(v[1] > 0.0)) return false;
+    for (int i = 0; i < 17; ++i) lens.v[i] = i < 8 ? v[i] : 0.0;
+    lens.v[16] = (double)LR_LENS_FISHEYE;
+    lens.n = 17;
+    return true;
 }
 
 // --border's argument: MODE[:VALUE], VALUE a gray level or R,G,B (a gray level serves all three channels)
@@ -504,15 +557,16 @@ int main(int argc, char** argv) {
                      "          [--h-strategy rotate_h|rotate_v|rectify|keep] [--v-strategy ...] [--warp] [--device-prepare]\n"
                      "          [--lines] [--jpeg Q] [--optimize] [--jpeg-in] [--orient] [--any-sampling] [--scale 1|2|4|8]\n"
                      "          [--cubic] [--border constant|replicate|reflect|reflect101[:VALUE]] [--crop]\n"
-                     "          [--lens fx,fy,cx,cy,k1,k2,p1,p2,k3] [--out-max N]\n",
+                     "          [--lens fx,fy,cx,cy,k1,k2,p1,p2,k3[,k4,k5,k6,s1,s2,s3,s4,model]] [--fisheye fx,fy,cx,cy,k1,k2,k3,k4]\n"
+                     "          [--lens-scale S] [--out-max N]\n",
                      argv[0]);
         return 2;
     }
     float max_size = 1200.f;  // the demo's default
     bool refine = false, warp = false, device_prepare = false, lines_pictures = false, jpeg_in = false, orient = false, any_sampling = false, cubic = false;
-    bool optimize = false, bordered = false, crop = false, lensed = false;
+    bool optimize = false, bordered = false, crop = false, lensed = false, lens_scaled = false;
     Border border;
-    double lens[9];
+    LensArg lens;
     int threads = -1, jpeg = 0, decode_scale = 0, out_max = 0;
     RectificationConfig cfg;
     cfg.horizontal_vp_min_distance = 2;  // autorectify.cpp:347
@@ -537,6 +591,14 @@ int main(int argc, char** argv) {
         }
         else if (a == "--lens" && has_val && parse_lens(argv[i + 1], lens)) {
             lensed = true;
+            ++i;
+        }
+        else if (a == "--fisheye" && has_val && parse_fisheye(argv[i + 1], lens)) {
+            lensed = true;
+            ++i;
+        }
+        else if (a == "--lens-scale" && has_val && parse_numbers(argv[i + 1], &lens.scale, 1) == 1 && lens.scale > 0.0) {
+            lens_scaled = true;
             ++i;
         }
         else if (a == "--out-max" && has_val && std::atoi(argv[i + 1]) >= 1) out_max = std::atoi(argv[++i]);
@@ -579,6 +641,10 @@ int main(int argc, char** argv) {
     }
     if (lensed && (!warp || crop)) {
         std::fprintf(stderr, "--lens goes with --warp or --jpeg and not with --crop: the crop's rectangle assumes straight source edges\n");
+        return 2;
+    }
+    if (lens_scaled && !lensed) {
+        std::fprintf(stderr, "--lens-scale goes with --lens or --fisheye: it scales the ideal picture about the lens's centre\n");
         return 2;
     }
     if (out_max && !warp) {
@@ -641,7 +707,7 @@ int main(int argc, char** argv) {
     std::vector<uint8_t> warped;
     int ow = 0, oh = 0;
     double H[9];
-    bool ok = !warp || warp_frame(full, t, prefix, warped, ow, oh, H, jpeg, optimize, cubic, bordered ? &border : nullptr, crop, lensed ? lens : nullptr, out_max);
+    bool ok = !warp || warp_frame(full, t, prefix, warped, ow, oh, H, jpeg, optimize, cubic, bordered ? &border : nullptr, crop, lensed ? &lens : nullptr, out_max);
     if (ok && lines_pictures) {  // on the gray frame, as the demo draws (autorectify.cpp:364)
         std::vector<uint8_t> gray(seen.px.size());
         for (size_t i = 0; i < gray.size(); ++i) gray[i] = (uint8_t)(seen.px[i] * 256.0f);

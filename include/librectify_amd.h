@@ -358,6 +358,42 @@ enum lr_border_mode { LR_BORDER_CONSTANT = 0, LR_BORDER_REPLICATE = 1, LR_BORDER
  * on what the call without the bit rejects, a non-finite entry among the nine, fx <= 0 or fy <= 0, and together with
  * LR_WARP_PREPARE, LR_WARP_LINES, LR_WARP_JPEG or LR_WARP_JPEG_DECODE.  Without the bit nothing changes. */
 enum lr_warp_lens { LR_WARP_LENS = 0x100000 }; /* or-ed into `format` like lr_warp_option */
+/* LR_WARP_LENS_MODEL, or-ed in TOGETHER with LR_WARP_LENS, widens every frame's lens from nine entries to seventeen, for the
+ * calibrations the five coefficients cannot hold: cv::calibrateCamera's with CALIB_RATIONAL_MODEL (8 coefficients) and
+ * CALIB_THIN_PRISM_MODEL (12), and cv::fisheye::calibrate's.  It works with everything LR_WARP_LENS works with: the three
+ * layouts, LR_WARP_CUBIC, LR_WARP_BORDER and LR_WARP_AREA, u8, u8x3 and f32.  The seventeen sit where the nine sat, behind the
+ * border word where there is one and in front of LR_WARP_AREA's S:
+ *   fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6, s1, s2, s3, s4, model
+ *   fmt | LR_WARP_LENS | LR_WARP_LENS_MODEL                    26 doubles per frame, 27 with LR_WARP_BORDER;
+ *   fmt | LR_WARP_PACKED | LR_WARP_LENS | LR_WARP_LENS_MODEL   30 doubles per frame, 31 with LR_WARP_BORDER;
+ *   fmt | LR_WARP_RAGGED | LR_WARP_LENS | LR_WARP_LENS_MODEL   35 doubles per frame (the border word stays entry [17]);
+ * each one more with LR_WARP_AREA.  model = 0 (LR_LENS_RATIONAL): entries [4..15] are OpenCV's twelve distCoeffs in OpenCV's
+ * order, so the first nine entries mean what they mean without the bit.  model = 1 (LR_LENS_FISHEYE): entries [4..7] are
+ * cv::fisheye's k1..k4 and entries [8..15] must be zero.  Frames of both models and frames without a lens mix in one launch.
+ * Arithmetic (tests/numpy_warp_lens_model_ref.py restates it), in double, every operation rounded
+ * on its own; U, V, a, b, r2 and fixed are LR_WARP_LENS's.  Model 0, a displacement like LR_WARP_LENS's:
+ *   radn = r2 * (k1 + r2 * (k2 + r2 * k3));      radd = r2 * (k4 + r2 * (k5 + r2 * k6))
+ *   rad  = (radn - radd) / (1 + radd)
+ *   ta   = ((2*p1) * (a*b) + p2 * (r2 + 2*(a*a))) + r2 * (s1 + r2 * s2)
+ *   tb   = (p1 * (r2 + 2*(b*b)) + (2*p2) * (a*b)) + r2 * (s3 + r2 * s4)
+ *   du = fx * (a*rad + ta);   dv = fy * (b*rad + tb);   X = fixed(U + 32*du);   Y = fixed(V + 32*dv)
+ * (OpenCV's x'' = x' (1 + k1 r2 + ..) / (1 + k4 r2 + ..) + tangential + prism terms, with x' subtracted).  A model-0 frame
+ * whose entries [4..15] are all zero (of either sign) is by definition warped by the plain rule; one whose [9..15] are zero has,
+ * for a finite r2, the coordinates of LR_WARP_LENS's rule.  Model 1, which has no displacement form and no "no lens" case (zero
+ * coefficients are the pure equidistant lens):
+ *   r = sqrt(r2);   th = ATAN(r);   t2 = th * th
+ *   thd = th * (1 + t2 * (k1 + t2 * (k2 + t2 * (k3 + t2 * k4))));   sc = r != 0 ? thd / r : 1
+ *   X = fixed(32 * (fx * (a*sc) + cx));   Y = fixed(32 * (fy * (b*sc) + cy))
+ * sqrt is the correctly rounded one and ATAN is lr_lens_atan below, an arctangent made of + - * /, comparisons and one rint,
+ * so that the device, this header and the NumPy reference compute the same bits.  Infinities and NaN go the way they go in the
+ * plain rule; there is no guard against a model that folds over.  A call whose frames all fit the nine entries (model 0,
+ * [9..15] zero) launches what the same call with LR_WARP_LENS alone launches, and gives its bytes.  Fails cleanly (nothing
+ * launched, nothing written, lr_last_error names the frame and the reason) on what the call without the bit rejects, the bit
+ * without LR_WARP_LENS, a non-finite entry among the seventeen, fx <= 0 or fy <= 0, a model other than 0 or 1, a fisheye row
+ * with a non-zero entry in [8..15], and together with LR_WARP_PREPARE, LR_WARP_LINES, LR_WARP_JPEG or LR_WARP_JPEG_DECODE.
+ * Without the bit nothing changes. */
+enum lr_warp_lens_model { LR_WARP_LENS_MODEL = 0x800000 }; /* or-ed into `format` like lr_warp_option, with LR_WARP_LENS */
+enum lr_lens_model { LR_LENS_RATIONAL = 0, LR_LENS_FISHEYE = 1 }; /* entry [16] of a frame's seventeen lens entries */
 /* LR_WARP_AREA makes the warp an area-sampled one: every destination pixel is the mean of S x S samples spread over its own
  * footprint, so that a warp which SHRINKS (a bounded-size rectified picture: lr_shrink_homography below) does not alias.  One
  * resampling: the stored frame is read once and only the small picture is written.  It is an option of the three warps and of
@@ -474,6 +510,76 @@ static inline void lr_lens_distort(const double lens[9], double u, double v, dou
     const double du = fx * (a * rad + ta), dv = fy * (b * rad + tb);
     if (ud) *ud = (U + 32.0 * du) / 32.0;
     if (vd) *vd = (V + 32.0 * dv) / 32.0;
+}
+
+/* LR_WARP_LENS_MODEL's arctangent of r >= 0: out of + - * /, comparisons and one rint (round to nearest, ties to even, the
+ * default rounding mode), so that every side computes the same bits; within 2^-52 of atan.  r > 1 is reflected, pi/2 - ATAN(1 /
+ * r); t in [0, 1] is reduced by the nearest of the nine points c = i / 8, z = (t - c) / (1 + t c) with |z| <= 1/16, and ATAN(t) =
+ * atan(c) + (z + z (z^2 p)), p = -1/3 + z^2 (1/5 + z^2 (-1/7 + ... + z^2 (-1/15))) in Horner's form.  A NaN stays a NaN.  Host
+ * arithmetic only; compiled without floating-point contraction it is, operation for operation, the Python package's lens_atan. */
+static inline double lr_lens_atan(double r) {
+    /* atan(i / 8), i = 0 .. 8, as the shortest decimals that give these doubles (the header is also compiled as C++14, which has
+     * no hexadecimal floating literals); pi/2 below likewise, 0x1.921fb54442d18p+0 */
+    static const double table[9] = {0.0,                  /* 0x0.0p+0 */
+                                    0.12435499454676144,  /* 0x1.fd5ba9aac2f6ep-4 */
+                                    0.24497866312686414,  /* 0x1.f5b75f92c80ddp-3 */
+                                    0.35877067027057225,  /* 0x1.6f61941e4def1p-2 */
+                                    0.4636476090008061,   /* 0x1.dac670561bb4fp-2 */
+                                    0.5585993153435624,   /* 0x1.1e00babdefeb4p-1 */
+                                    0.6435011087932844,   /* 0x1.4978fa3269ee1p-1 */
+                                    0.7188299996216245,   /* 0x1.700a7c5784634p-1 */
+                                    0.7853981633974483};  /* 0x1.921fb54442d18p-1 */
+    const int big = r > 1.0;
+    const double t = big ? 1.0 / r : r;
+    const double n = rint(8.0 * t);
+    const int i = n >= 0.0 && n <= 8.0 ? (int)n : 0; /* (a NaN takes entry 0 and stays a NaN through z) */
+    const double c = (double)i / 8.0;
+    const double z = (t - c) / (1.0 + t * c);
+    const double z2 = z * z;
+    const double p = -1.0 / 3.0 + z2 * (1.0 / 5.0 + z2 * (-1.0 / 7.0 + z2 * (1.0 / 9.0 + z2 * (-1.0 / 11.0 + z2 * (1.0 / 13.0 + z2 * (-1.0 / 15.0))))));
+    const double at = table[i] + (z + z * (z2 * p));
+    return big ? 1.5707963267948966 - at : at;
+}
+
+/* lr_lens_distort for LR_WARP_LENS_MODEL's seventeen entries (fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6, s1, s2, s3, s4,
+ * model): the pixel (*ud, *vd) of the stored photograph that shows the ideal point (u, v).  The same operations in the same
+ * order as the bit's rule with U = 32 u and V = 32 v, returning X / 32 and Y / 32 before `fixed`; a model-0 lens whose entries
+ * [4..15] are all zero returns (U / 32, V / 32), the plain rule.  It does not check the entries: a model other than 1 is taken
+ * for 0.  Host arithmetic only; compiled without floating-point contraction (-ffp-contract=off) it is, operation for
+ * operation, the Python package's lens_distort for a LensModel. */
+static inline void lr_lens_distort_model(const double lens[17], double u, double v, double* ud, double* vd) {
+    const double fx = lens[0], fy = lens[1], cx = lens[2], cy = lens[3];
+    const double U = 32.0 * u, V = 32.0 * v;
+    const double a = (U * 0.03125 - cx) / fx, b = (V * 0.03125 - cy) / fy;
+    const double r2 = a * a + b * b;
+    double X = U, Y = V;
+    int i, any = 0;
+    if (lens[16] == 1.0) {
+        const double k1 = lens[4], k2 = lens[5], k3 = lens[6], k4 = lens[7];
+        const double r = sqrt(r2);
+        const double th = lr_lens_atan(r);
+        const double t2 = th * th;
+        const double thd = th * (1.0 + t2 * (k1 + t2 * (k2 + t2 * (k3 + t2 * k4))));
+        const double sc = r != 0.0 ? thd / r : 1.0;
+        X = 32.0 * (fx * (a * sc) + cx);
+        Y = 32.0 * (fy * (b * sc) + cy);
+    } else {
+        for (i = 4; i < 16; ++i) any = any || lens[i] != 0.0;
+        if (any) {
+            const double k1 = lens[4], k2 = lens[5], p1 = lens[6], p2 = lens[7], k3 = lens[8], k4 = lens[9], k5 = lens[10], k6 = lens[11];
+            const double s1 = lens[12], s2 = lens[13], s3 = lens[14], s4 = lens[15];
+            const double radn = r2 * (k1 + r2 * (k2 + r2 * k3));
+            const double radd = r2 * (k4 + r2 * (k5 + r2 * k6));
+            const double rad = (radn - radd) / (1.0 + radd);
+            const double ta = ((2.0 * p1) * (a * b) + p2 * (r2 + 2.0 * (a * a))) + r2 * (s1 + r2 * s2);
+            const double tb = (p1 * (r2 + 2.0 * (b * b)) + (2.0 * p2) * (a * b)) + r2 * (s3 + r2 * s4);
+            const double du = fx * (a * rad + ta), dv = fy * (b * rad + tb);
+            X = U + 32.0 * du;
+            Y = V + 32.0 * dv;
+        }
+    }
+    if (ud) *ud = X / 32.0;
+    if (vd) *vd = Y / 32.0;
 }
 
 /* The constrained crop: the largest upright rectangle of the rectified picture, of the given aspect and centred on the image

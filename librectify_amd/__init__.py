@@ -92,6 +92,8 @@ WARP_JPEG_DECODE = 0x4000  # enum lr_warp_jpeg_decode, likewise: lr_decode_jpeg_
 WARP_BORDER = 0x40000  # enum lr_warp_border, likewise: a border word per frame in the warp's table (border_word, border= of the tables)
 BORDER_CONSTANT, BORDER_REPLICATE, BORDER_REFLECT, BORDER_REFLECT_101 = 0, 1, 2, 4  # enum lr_border_mode: OpenCV's numbers
 WARP_LENS = 0x100000  # enum lr_warp_lens, likewise: nine lens entries per frame at the end of its row of the warp's table (Lens, lens= of the tables)
+WARP_LENS_MODEL = 0x800000  # enum lr_warp_lens_model, likewise and with WARP_LENS: seventeen lens entries per frame instead of nine (LensModel, lens= of the tables)
+LENS_RATIONAL, LENS_FISHEYE = 0, 1  # enum lr_lens_model: entry [16] of a frame's seventeen lens entries
 WARP_AREA = 0x400000  # enum lr_warp_area, likewise: a sampling factor S (1 .. 8) per frame at the very end of its row of the warp's table (area= of the tables)
 JPEG_OK, JPEG_NOT_JPEG, JPEG_UNSUPPORTED, JPEG_SIZE_MISMATCH, JPEG_DAMAGED = range(5)  # info[5] of lr_decode_jpeg_device
 FRAMES_U8, FRAMES_U8X3, FRAMES_F32 = 0x100, 0x200, 0x300  # enum lr_frames_option, or-ed into `refine` of the frame entries
@@ -328,39 +330,109 @@ Lens.__doc__ = """A frame's lens of LR_WARP_LENS: OpenCV's camera matrix (fx, fy
 source frame's pixel units.  All five coefficients zero: no lens, the plain rule."""
 
 
+class LensModel(collections.namedtuple("LensModel", "fx fy cx cy k1 k2 p1 p2 k3 k4 k5 k6 s1 s2 s3 s4 model", defaults=(0.0,) * 13)):
+    """A frame's lens of LR_WARP_LENS | LR_WARP_LENS_MODEL: the camera matrix (fx, fy, cx, cy) in the source frame's pixel units,
+    twelve coefficients and the model.  model = LENS_RATIONAL (0): OpenCV's distCoeffs of cv::calibrateCamera in OpenCV's order,
+    k1, k2, p1, p2, k3, k4, k5, k6 (CALIB_RATIONAL_MODEL), s1, s2, s3, s4 (CALIB_THIN_PRISM_MODEL); all twelve zero: no lens.
+    model = LENS_FISHEYE (1): the entries named k1, k2, p1, p2 are cv::fisheye's k1, k2, k3, k4 and the other eight are zero
+    (LensModel.fisheye builds it); all four zero: the pure equidistant lens."""
+    __slots__ = ()
+
+    @classmethod
+    def fisheye(cls, fx, fy, cx, cy, k1=0.0, k2=0.0, k3=0.0, k4=0.0):
+        """cv::fisheye's model: camera matrix and D = (k1, k2, k3, k4)"""
+        return cls(fx, fy, cx, cy, k1, k2, k3, k4, model=LENS_FISHEYE)
+
+
+def _is_lens_model(lens):
+    """lens (not None) has seventeen entries: a LensModel, or a plain sequence longer than a Lens"""
+    if isinstance(lens, LensModel):
+        return True
+    try:
+        return not isinstance(lens, Lens) and len(lens) > 9
+    except TypeError:
+        return False
+
+
 def _lens_row(lens, what):
-    """the nine doubles of one frame's lens (None: zeros, with fx = fy = 1), checked as the library checks them"""
+    """the nine doubles of one frame's lens, or the seventeen of a LensModel (None: nine zeros, with fx = fy = 1), checked as
+    the library checks them"""
     if lens is None:
         return [1.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0]
+    model = _is_lens_model(lens)
     try:
-        row = [float(v) for v in Lens(*lens)]
+        row = [float(v) for v in (LensModel(*lens) if model else Lens(*lens))]
     except (TypeError, ValueError):
-        raise ValueError("%s: a lens is a Lens(fx, fy, cx, cy, k1, k2, p1, p2, k3) or None, not %r" % (what, lens)) from None
+        raise ValueError("%s: a lens is a Lens(fx, fy, cx, cy, k1, k2, p1, p2, k3), a LensModel or None, not %r" % (what, lens)) from None
     if not all(np.isfinite(row)):
         raise ValueError("%s: a lens entry is not finite" % what)
     if row[0] <= 0.0 or row[1] <= 0.0:
         raise ValueError("%s: a lens has fx <= 0 or fy <= 0" % what)
+    if model and row[16] not in (LENS_RATIONAL, LENS_FISHEYE):
+        raise ValueError("%s: a lens model is LENS_RATIONAL (0) or LENS_FISHEYE (1)" % what)
+    if model and row[16] == LENS_FISHEYE and any(v != 0.0 for v in row[8:16]):
+        raise ValueError("%s: a fisheye lens has a non-zero entry among k3 .. s4 (its four coefficients are k1, k2, p1, p2)" % what)
     return row
 
 
 def _lens_rows(lens, count, what):
-    """float64 (count, 9): the lens entries of `count` frames from lens=: one Lens for all, or a list of one per frame (None: zeros)"""
-    if lens is None or isinstance(lens, Lens):
-        return np.array([_lens_row(lens, what)] * count, np.float64).reshape(count, 9)
-    specs = list(lens)
-    if len(specs) != count:
-        raise ValueError("%s: as many lenses as frames (%d), not %d" % (what, count, len(specs)))
-    return np.array([_lens_row(v, what) for v in specs], np.float64).reshape(count, 9)
+    """float64 (count, 9): the lens entries of `count` frames from lens=: one Lens for all, or a list of one per frame (None:
+    zeros); (count, 17) where a LensModel is among them: a Lens then fills the first nine entries of a LENS_RATIONAL row"""
+    if lens is None or isinstance(lens, (Lens, LensModel)):
+        specs = [lens] * count
+    else:
+        specs = list(lens)
+        if len(specs) != count:
+            raise ValueError("%s: as many lenses as frames (%d), not %d" % (what, count, len(specs)))
+    rows = []
+    for b, v in enumerate(specs):
+        try:
+            rows.append(_lens_row(v, what))
+        except ValueError as e:
+            raise ValueError("%s (frame %d)" % (e, b)) from None
+    width = 17 if any(len(r) == 17 for r in rows) else 9
+    return np.array([r + [0.0] * (width - len(r)) for r in rows], np.float64).reshape(count, width)
+
+
+def _lens_bits(rows):
+    """WARP_LENS, with WARP_LENS_MODEL for _lens_rows' rows of seventeen"""
+    return WARP_LENS | (WARP_LENS_MODEL if rows.shape[1] == 17 else 0)
+
+
+_ATAN_TABLE = np.array([float.fromhex(v) for v in (
+    "0x0.0p+0", "0x1.fd5ba9aac2f6ep-4", "0x1.f5b75f92c80ddp-3", "0x1.6f61941e4def1p-2", "0x1.dac670561bb4fp-2", "0x1.1e00babdefeb4p-1",
+    "0x1.4978fa3269ee1p-1", "0x1.700a7c5784634p-1", "0x1.921fb54442d18p-1")], np.float64)  # atan(i / 8)
+_PI_2 = float.fromhex("0x1.921fb54442d18p+0")
+
+
+def lens_atan(r):
+    """lr_lens_atan of include/librectify_amd.h restated operation for operation in float64: LR_WARP_LENS_MODEL's arctangent of
+    r >= 0 (an array or a number), within 2^-52 of atan.  Needs no GPU."""
+    r = np.asarray(r, np.float64)
+    with np.errstate(all="ignore"):
+        big = r > 1.0
+        t = np.where(big, 1.0 / np.where(big, r, 1.0), r)
+        n = np.rint(8.0 * t)
+        i = np.where((n >= 0.0) & (n <= 8.0), n, 0.0).astype(np.int64)
+        c = i.astype(np.float64) / 8.0
+        z = (t - c) / (1.0 + t * c)
+        z2 = z * z
+        p = -1.0 / 3.0 + z2 * (1.0 / 5.0 + z2 * (-1.0 / 7.0 + z2 * (1.0 / 9.0 + z2 * (-1.0 / 11.0 + z2 * (1.0 / 13.0 + z2 * (-1.0 / 15.0))))))
+        at = _ATAN_TABLE[i] + (z + z * (z2 * p))
+        return np.where(big, _PI_2 - at, at)
 
 
 def lens_distort(lens, points):
-    """lr_lens_distort of include/librectify_amd.h restated operation for operation in float64: the pixels of the stored
-    photograph that show the ideal points.  lens: a Lens; points: (..., 2) array of (u, v).  Returns float64 of the same
-    shape.  It takes detected lines, which are in ideal coordinates, back onto the photograph.  Needs no GPU."""
-    fx, fy, cx, cy, k1, k2, p1, p2, k3 = (np.float64(v) for v in Lens(*lens))
+    """lr_lens_distort of include/librectify_amd.h (for a LensModel: lr_lens_distort_model) restated operation for operation in
+    float64: the pixels of the stored photograph that show the ideal points.  lens: a Lens or a LensModel; points: (..., 2)
+    array of (u, v).  Returns float64 of the same shape.  It takes detected lines, which are in ideal coordinates, back onto
+    the photograph (after rectify(lens_scale=s): lens_scale_map(lens, s) first).  Needs no GPU."""
     pts = np.asarray(points, np.float64)
     if pts.shape[-1:] != (2,):
         raise ValueError("lens_distort: points is (..., 2)")
+    if _is_lens_model(lens):
+        return _lens_distort_model(LensModel(*lens), pts)
+    fx, fy, cx, cy, k1, k2, p1, p2, k3 = (np.float64(v) for v in Lens(*lens))
     with np.errstate(all="ignore"):
         U, V = 32.0 * pts[..., 0], 32.0 * pts[..., 1]
         a, b = (U * 0.03125 - cx) / fx, (V * 0.03125 - cy) / fy
@@ -370,6 +442,61 @@ def lens_distort(lens, points):
         tb = p1 * (r2 + 2.0 * (b * b)) + (2.0 * p2) * (a * b)
         du, dv = fx * (a * rad + ta), fy * (b * rad + tb)
         return np.stack([(U + 32.0 * du) / 32.0, (V + 32.0 * dv) / 32.0], axis=-1)
+
+
+def _lens_distort_model(lens, pts):
+    fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6, s1, s2, s3, s4, model = (np.float64(v) for v in lens)
+    with np.errstate(all="ignore"):
+        U, V = 32.0 * pts[..., 0], 32.0 * pts[..., 1]
+        a, b = (U * 0.03125 - cx) / fx, (V * 0.03125 - cy) / fy
+        r2 = a * a + b * b
+        if model == 1.0:  # (the fisheye: k1, k2, p1, p2 are its k1 .. k4)
+            r = np.sqrt(r2)
+            th = lens_atan(r)
+            t2 = th * th
+            thd = th * (1.0 + t2 * (k1 + t2 * (k2 + t2 * (p1 + t2 * p2))))
+            sc = np.where(r != 0.0, thd / np.where(r != 0.0, r, 1.0), 1.0)
+            X, Y = 32.0 * (fx * (a * sc) + cx), 32.0 * (fy * (b * sc) + cy)
+        elif any(float(v) != 0.0 for v in lens[4:16]):
+            radn = r2 * (k1 + r2 * (k2 + r2 * k3))
+            radd = r2 * (k4 + r2 * (k5 + r2 * k6))
+            rad = (radn - radd) / (1.0 + radd)
+            ta = ((2.0 * p1) * (a * b) + p2 * (r2 + 2.0 * (a * a))) + r2 * (s1 + r2 * s2)
+            tb = (p1 * (r2 + 2.0 * (b * b)) + (2.0 * p2) * (a * b)) + r2 * (s3 + r2 * s4)
+            du, dv = fx * (a * rad + ta), fy * (b * rad + tb)
+            X, Y = U + 32.0 * du, V + 32.0 * dv
+        else:
+            X, Y = U, V
+        return np.stack([X / 32.0, Y / 32.0], axis=-1)
+
+
+def _check_lens_scale(what, s):
+    if isinstance(s, (bool, np.bool_)) or not isinstance(s, (int, float, np.integer, np.floating)) or not np.isfinite(s) or not s > 0:
+        raise ValueError("%s: lens_scale is a finite number greater than 0" % what)
+    return float(s)
+
+
+def lens_scale_map(lens, s):
+    """The map from the ideal picture scaled by s about the lens's centre (cx, cy) to the ideal picture, float64 (3, 3):
+    [[1/s, 0, cx (1 - 1/s)], [0, 1/s, cy (1 - 1/s)], [0, 0, 1]].  A fisheye's ideal picture at the source's own camera matrix
+    shows only the middle of the view; s < 1 brings more of it into the frame's size.  undistort(lens_scale=s) warps with this
+    map, rectify(lens_scale=s) with lens_scale_map(lens, s) @ M (lens_scale_compose); points of the scaled ideal picture go through it (homogeneous:
+    p' = map @ (x, y, 1)) and then through lens_distort back onto the photograph.  lens: a Lens or a LensModel.  Needs no GPU."""
+    s = _check_lens_scale("lens_scale_map", s)
+    row = _lens_row(lens if lens is not None else Lens(1.0, 1.0, 0.0, 0.0), "lens_scale_map")
+    cx, cy = row[2], row[3]
+    q = 1.0 / s
+    return np.array([[q, 0.0, cx * (1.0 - q)], [0.0, q, cy * (1.0 - q)], [0.0, 0.0, 1.0]], np.float64)
+
+
+def lens_scale_compose(S, M):
+    """lens_scale_map(lens, s) @ M as rectify(lens_scale=s) and the recipe compute it, every product and sum rounded on its
+    own: rows q M[0] + tx M[2], q M[1] + ty M[2] and M[2], with q = S[0][0], tx = S[0][2], ty = S[1][2].  Needs no GPU."""
+    S, M = np.asarray(S, np.float64).reshape(3, 3), np.asarray(M, np.float64).reshape(3, 3)
+    return np.stack([S[0, 0] * M[0] + S[0, 2] * M[2], S[0, 0] * M[1] + S[1, 2] * M[2], M[2]])
+
+
+_LensPlan = collections.namedtuple("_LensPlan", "rows maps")  # rectify_batch's lenses: _lens_rows' rows, and lens_scale_map per frame ((B, 3, 3)) or None for lens_scale 1
 
 
 def _area_col(area, count, what):
@@ -569,7 +696,9 @@ def warp_table(Ms, sizes, bpp, align=4, border=None, lens=None, area=None):
     border (not None): the table of LR_WARP_PACKED | LR_WARP_BORDER, (B, 14), whose column 13 is every frame's border word:
     one spec for all frames (border_word's) or a list of one per frame.
     lens (not None): the table of LR_WARP_PACKED | LR_WARP_LENS, (B, 22) or with border (B, 23), whose last nine columns are
-    every frame's lens: one Lens for all frames or a list of one per frame, in which None means zeros.
+    every frame's lens: one Lens for all frames or a list of one per frame, in which None means zeros.  With a LensModel for
+    all frames or among the list's (Lens, LensModel and None mix) the columns are seventeen, (B, 30) or (B, 31): the table of
+    LR_WARP_PACKED | LR_WARP_LENS | LR_WARP_LENS_MODEL.
     area (not None): the table of LR_WARP_PACKED | LR_WARP_AREA, one more column at the very end, every frame's sampling
     factor S: one integer from 1 to 8 for all frames or a list of one per frame."""
     Ms = np.asarray(Ms, np.float64)
@@ -602,7 +731,7 @@ def warp_table(Ms, sizes, bpp, align=4, border=None, lens=None, area=None):
     if border is not None:
         words = _border_words(border, len(Ms), _FMT_OF_BPP[bpp], "warp_table")
         table = np.concatenate([table, np.array(words, np.float64).reshape(-1, 1)], axis=1)
-    if lens is not None:
+    if lens is not None:  # (nine columns, or seventeen where a LensModel is given: WARP_LENS | WARP_LENS_MODEL)
         table = np.concatenate([table, _lens_rows(lens, len(Ms), "warp_table")], axis=1)
     if area is not None:
         table = np.concatenate([table, _area_col(area, len(Ms), "warp_table")], axis=1)
@@ -620,7 +749,8 @@ def ragged_table(Ms, out_sizes, sources, bpp, out_bpp=None, align=4, border=None
     border (not None): the table of LR_WARP_RAGGED | LR_WARP_BORDER, whose column 17 is every frame's border word: one spec
     for all frames (border_word's) or a list of one per frame.
     lens (not None): the table of LR_WARP_RAGGED | LR_WARP_LENS, (B, 27), whose last nine columns are every frame's lens: one
-    Lens for all frames or a list of one per frame, in which None means zeros.
+    Lens for all frames or a list of one per frame, in which None means zeros.  With a LensModel for all frames or among the
+    list's (Lens, LensModel and None mix) the columns are seventeen, (B, 35): LR_WARP_RAGGED | LR_WARP_LENS | LR_WARP_LENS_MODEL.
     area (not None): the table of LR_WARP_RAGGED | LR_WARP_AREA, (B, 19) or with lens (B, 28), whose last column is every
     frame's sampling factor S: one integer from 1 to 8 for all frames or a list of one per frame."""
     if bpp not in (1, 3, 4):
@@ -654,7 +784,7 @@ def ragged_table(Ms, out_sizes, sources, bpp, out_bpp=None, align=4, border=None
     table[:, 13:17] = src
     if border is not None:
         table[:, 17] = _border_words(border, B, _FMT_OF_BPP[bpp], "ragged_table")
-    if lens is not None:
+    if lens is not None:  # (nine columns, or seventeen where a LensModel is given: WARP_LENS | WARP_LENS_MODEL)
         table = np.concatenate([table, _lens_rows(lens, B, "ragged_table")], axis=1)
     if area is not None:
         table = np.concatenate([table, _area_col(area, B, "ragged_table")], axis=1)
@@ -939,8 +1069,9 @@ def _border_bit_and_map(border, fmt, M, what, lens=None, area=None):
         row.append([float(_border_words(border, 1, fmt, what)[0])])
         bits |= WARP_BORDER
     if lens is not None:
-        row.append(_lens_rows(lens, 1, what)[0])
-        bits |= WARP_LENS
+        rows = _lens_rows(lens, 1, what)
+        row.append(rows[0])
+        bits |= _lens_bits(rows)
     if area is not None:
         row.append(_area_col(area, 1, what)[0])
         bits |= WARP_AREA
@@ -1097,10 +1228,10 @@ class Context:
         doubles per frame ((batch, 3, 3) or (3, 3)), the destination-to-source map.  fmt: PIX_U8, PIX_U8X3, PIX_F32, with
         WARP_CUBIC or-ed in for the bicubic sampling rule and WARP_BORDER for a border rule per frame (M then has 10 doubles
         per frame, the tenth the frame's border_word), and WARP_LENS for a lens per frame (nine more doubles per frame at the
-        end: a Lens), and WARP_AREA for S x S samples per destination pixel (one more double at the very end of every frame's
+        end: a Lens; seventeen with WARP_LENS_MODEL as well: a LensModel), and WARP_AREA for S x S samples per destination pixel (one more double at the very end of every frame's
         row: its sampling factor S, 1 .. 8)."""
         M = np.ascontiguousarray(M, np.float64).reshape(-1)
-        per_frame = (10 if fmt & WARP_BORDER else 9) + (9 if fmt & WARP_LENS else 0) + (1 if fmt & WARP_AREA else 0)
+        per_frame = (10 if fmt & WARP_BORDER else 9) + ((17 if fmt & WARP_LENS_MODEL else 9) if fmt & WARP_LENS else 0) + (1 if fmt & WARP_AREA else 0)
         if M.size < per_frame * max(int(batch), 1):
             raise ValueError("warp_perspective_device: M needs %d values per frame" % per_frame)
         _check(lib().lr_warp_perspective_device(self._h, C.c_void_p(d_src), src_image_bytes, batch, width, height, src_row_bytes, fmt, _ptr(M), C.c_void_p(d_dst), dst_image_bytes, out_width, out_height, dst_row_bytes))
@@ -1109,10 +1240,10 @@ class Context:
                                        dst_bytes):
         """lr_warp_perspective_device with LR_WARP_PACKED: one launch for `batch` device frames of one size whose outputs
         have their own sizes and places in the dst_bytes at d_dst.  table: 13 doubles per frame (warp_table).  fmt may carry
-        WARP_CUBIC, WARP_BORDER with a table of 14 doubles per frame (warp_table's border=), and WARP_LENS with nine more
-        (warp_table's lens=), and WARP_AREA with one more (warp_table's area=)."""
+        WARP_CUBIC, WARP_BORDER with a table of 14 doubles per frame (warp_table's border=), and WARP_LENS with nine more, or
+        with WARP_LENS_MODEL seventeen more (warp_table's lens=), and WARP_AREA with one more (warp_table's area=)."""
         table = np.ascontiguousarray(table, np.float64).reshape(-1)
-        cols = (14 if fmt & WARP_BORDER else 13) + (9 if fmt & WARP_LENS else 0) + (1 if fmt & WARP_AREA else 0)
+        cols = (14 if fmt & WARP_BORDER else 13) + ((17 if fmt & WARP_LENS_MODEL else 9) if fmt & WARP_LENS else 0) + (1 if fmt & WARP_AREA else 0)
         if table.size != cols * int(batch) or batch < 1:
             raise ValueError("warp_perspective_packed_device: the table has %d values per frame" % cols)
         out_w, out_h = (int(min(max(v, 1), 2 ** 31 - 1)) for v in np.nan_to_num(table.reshape(-1, cols)[:, 9:11]).max(axis=0))
@@ -1124,7 +1255,7 @@ class Context:
         interp: "linear" (bilinear) or "cubic" (WARP_CUBIC: 4 x 4 bicubic, cv::warpPerspective's INTER_CUBIC).
         border: None (the zero border) or border_word's spec -- "replicate", "reflect", "reflect101", ("constant", value):
         cv::warpPerspective's borderMode and borderValue (WARP_BORDER).
-        lens: None or the frame's Lens (WARP_LENS): M then maps into the ideal picture, and the lens model takes the point to the
+        lens: None or the frame's Lens (WARP_LENS) or LensModel (WARP_LENS | WARP_LENS_MODEL): M then maps into the ideal picture, and the lens model takes the point to the
         pixel of `array` that is sampled -- undistortion and warp in one resampling.
         area: None or the sampling factor S, an integer from 1 to 8 (WARP_AREA): every pixel is the mean of S x S samples spread
         over its footprint, for a map that shrinks (shrink_homography gives map, size and S for a bound on the size)."""
@@ -1145,13 +1276,16 @@ class Context:
             if d_dst.value:
                 self.device_free(d_dst.value)
 
-    def undistort(self, image, lens, interp="linear", border=None):
+    def undistort(self, image, lens, interp="linear", border=None, lens_scale=1):
         """The frame without its lens distortion (cv::undistort with the frame's own camera matrix): warp_perspective with the
-        identity map, the lens and the source's size."""
+        identity map, the lens (a Lens or a LensModel) and the source's size.  lens_scale=s: with lens_scale_map(lens, s) in
+        place of the identity, the ideal picture scaled by s about (cx, cy): s < 1 shows more of a fisheye's view."""
         a = np.asarray(image)
         if a.ndim < 2:
             raise ValueError("undistort: a 2-D uint8 or float32 frame, or an H x W x 3 uint8 frame")
-        return self.warp_perspective(a, np.eye(3), (a.shape[1], a.shape[0]), interp=interp, border=border, lens=lens)
+        s = _check_lens_scale("undistort", lens_scale)
+        M = np.eye(3) if s == 1.0 else lens_scale_map(lens, s)
+        return self.warp_perspective(a, M, (a.shape[1], a.shape[0]), interp=interp, border=border, lens=lens)
 
     # ---- the lines picture ----
     def draw_lines_device(self, d_src, src_bytes, fmt, lines, table, d_dst, dst_bytes, H=None):
@@ -1484,7 +1618,7 @@ class Context:
 
     def rectify(self, image_u8, min_length=None, refine=False, cfg=None, clip=3.0, max_size=None, jpeg=None, orient=False,
                 interp="linear", jpeg_optimize=False, any_sampling=False, border=None, crop=False, decode_scale=None, decode_max_size=None,
-                lens=None, out_max_size=None):
+                lens=None, out_max_size=None, lens_scale=1):
         """The reference demo's pipeline (autorectify.cpp) on an 8-bit frame (H x W gray or H x W x 3 RGB): luma
         (4899 R + 9617 G + 1868 B + 8192) >> 14, / 256, find_line_segment_groups with min_length max(w, h) / 100 by
         default, compute_rectification_transform (cfg: the demo's, horizontal_vp_min_distance = 2),
@@ -1520,7 +1654,12 @@ class Context:
         and homography are in IDEAL coordinates (lens_distort takes them back onto the photograph); the final warp reads
         the ORIGINAL frame with WARP_LENS, the homography and the call's interp and border: one resampling.  The lines and the
         transform are those of rectify(undistort(image, lens)), the picture is warp_perspective(image, M, lens=lens).
-        With crop=True: ValueError (the crop's rectangle assumes straight source edges).
+        With crop=True: ValueError (the crop's rectangle assumes straight source edges).  A LensModel in place of the Lens
+        (WARP_LENS | WARP_LENS_MODEL on both launches): OpenCV's rational and thin-prism model, or LensModel.fisheye's.
+        lens_scale=s (with lens=, else ValueError; a finite number above 0): the detector sees the ideal picture scaled by s
+        about the lens's (cx, cy) -- s < 1 brings more of a fisheye's view into the frame's size -- and the final map is
+        lens_scale_map(lens, s) @ M.  Lines, transform and homography are then in the SCALED ideal picture's coordinates:
+        lens_scale_map(lens, s) takes a point of it to the ideal picture, lens_distort from there onto the photograph.
         out_max_size=N: the picture (or its JPEG file) is at most N pixels on its longer side.  The final warp carries
         WARP_AREA with shrink_homography's map, size and sampling factor S (applied after the crop where crop=True, whose
         rectangle stays in the uncropped full-size picture): every pixel is the mean of S x S samples over its footprint, taken
@@ -1532,10 +1671,13 @@ class Context:
         if lens is not None:
             if crop:
                 raise ValueError("rectify: crop=True together with lens= (the crop's rectangle assumes straight source edges)")
-            lens = Lens(*_lens_row(lens, "rectify"))
+            row = _lens_row(lens, "rectify")
+            lens = LensModel(*row) if len(row) == 17 else Lens(*row)
+        if _check_lens_scale("rectify", lens_scale) != 1.0 and lens is None:
+            raise ValueError("rectify: lens_scale goes with lens=")
         if isinstance(image_u8, (bytes, bytearray, memoryview)):  # a JPEG file: decoded in HBM, rectify_batch's path for one frame
             res = self.rectify_batch([bytes(image_u8)], min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, jpeg=jpeg, orient=orient, interp=interp, jpeg_optimize=jpeg_optimize, any_sampling=any_sampling, border=border, crop=crop,
-                                     decode_scale=decode_scale, decode_max_size=decode_max_size, lens=lens, out_max_size=out_max_size)[0]
+                                     decode_scale=decode_scale, decode_max_size=decode_max_size, lens=lens, out_max_size=out_max_size, lens_scale=lens_scale)[0]
             if res[2] is None:
                 _rectified_map(res[1], clip, crop, cubic)  # (raises what rectify raises for such a frame)
             return res
@@ -1549,7 +1691,7 @@ class Context:
         if img.dtype != np.uint8 or not (img.ndim == 2 or (img.ndim == 3 and img.shape[2] == 3)):
             raise ValueError("rectify: an H x W or H x W x 3 uint8 frame")
         if jpeg is not None or lens is not None:  # (with a lens: the mixed-size pipeline for one frame, which has the undistorting launch)
-            res = self.rectify_batch(img[None], min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, jpeg=jpeg, interp=interp, jpeg_optimize=jpeg_optimize, border=border, crop=crop, lens=lens, out_max_size=out_max_size)[0]
+            res = self.rectify_batch(img[None], min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, jpeg=jpeg, interp=interp, jpeg_optimize=jpeg_optimize, border=border, crop=crop, lens=lens, out_max_size=out_max_size, lens_scale=lens_scale)[0]
             if res[2] is None:
                 _rectified_map(res[1], clip, crop, cubic)  # (raises what rectify raises for such a frame)
             return res
@@ -1680,7 +1822,7 @@ class Context:
 
     def _ragged_call(self, d_src, src_bytes, fmt_word, table, d_dst, dst_bytes, what):
         table = np.ascontiguousarray(table, np.float64)
-        cols = (27 if fmt_word & WARP_LENS else 18) + (1 if fmt_word & WARP_AREA else 0)
+        cols = 18 + ((17 if fmt_word & WARP_LENS_MODEL else 9) if fmt_word & WARP_LENS else 0) + (1 if fmt_word & WARP_AREA else 0)
         if table.ndim != 2 or table.shape[1] != cols or len(table) < 1:
             raise ValueError(what + ": the table has %d values per frame" % cols)
         bound = lambda col: int(min(max(np.nan_to_num(table[:, col]).max(), 1), 2 ** 31 - 1))  # noqa: E731
@@ -1689,8 +1831,8 @@ class Context:
     def warp_perspective_ragged_device(self, d_src, src_bytes, fmt, table, d_dst, dst_bytes):
         """lr_warp_perspective_device with LR_WARP_RAGGED: one launch for frames that have their own source size and place
         in the src_bytes at d_src and their own output size and place in the dst_bytes at d_dst.  table: 18 doubles per
-        frame (ragged_table).  fmt may carry WARP_CUBIC, WARP_BORDER, and WARP_LENS with a table of 27 doubles per frame
-        (ragged_table's lens=), and WARP_AREA with one more (ragged_table's area=)."""
+        frame (ragged_table).  fmt may carry WARP_CUBIC, WARP_BORDER, and WARP_LENS with a table of 27 doubles per frame, or
+        with WARP_LENS_MODEL 35 (ragged_table's lens=), and WARP_AREA with one more (ragged_table's area=)."""
         self._ragged_call(d_src, src_bytes, fmt | WARP_RAGGED, table, d_dst, dst_bytes, "warp_perspective_ragged_device")
 
     def prepare_ragged_device(self, d_src, src_bytes, fmt, table, d_dst, dst_bytes):
@@ -1738,10 +1880,11 @@ class Context:
         return self._rectify_frames(d_base, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, interp, border, crop, None, out_max_size)
 
     def _rectify_frames(self, d_base, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, interp, border, crop, lens_rows=None, out_max_size=None):
-        """rectify_frames_device; lens_rows (float64 (B, 9), rectify_batch's lens=): one WARP_LENS launch with the identity map,
-        bilinear, zero border, writes every frame without its distortion into a second region of the sources' layout; the
-        prepare step and the detector read that one, so lines and transforms are in ideal coordinates; the warp reads the
-        ORIGINAL frames with WARP_LENS: one resampling"""
+        """rectify_frames_device; lens_rows (a _LensPlan, rectify_batch's lens= and lens_scale=): one WARP_LENS launch with the
+        identity map (the plan's maps: lens_scale_map per frame), bilinear, zero border, writes every frame without its
+        distortion into a second region of the sources' layout; the prepare step and the detector read that one, so lines and
+        transforms are in (scaled) ideal coordinates; the warp reads the ORIGINAL frames with WARP_LENS and the plan's map @ M:
+        one resampling.  Rows of seventeen (a LensModel among the lenses) add WARP_LENS_MODEL to both launches."""
         cubic = _sampling_bit(interp, "rectify_frames_device")
         _check_out_max_size("rectify_frames_device", out_max_size)
         if fmt not in (PIX_U8, PIX_U8X3):
@@ -1760,12 +1903,13 @@ class Context:
         try:
             frames = (Frame * batch)()
             if lens_rows is not None:
-                itable = np.zeros((batch, 27), np.float64)
-                itable[:, :9] = np.eye(3).reshape(9)
+                lens_rows, lens_maps = lens_rows
+                itable = np.zeros((batch, 18 + lens_rows.shape[1]), np.float64)
+                itable[:, :9] = np.eye(3).reshape(9) if lens_maps is None else lens_maps.reshape(batch, 9)
                 itable[:, 9:13] = itable[:, 13:17] = np.array(sources, np.float64)
                 itable[:, 18:] = lens_rows
                 _check(lib().lr_device_malloc(self._h, src_bytes, C.byref(d_ideal)))
-                self.warp_perspective_ragged_device(d_base, src_bytes, fmt | WARP_LENS, itable, d_ideal.value, src_bytes)
+                self.warp_perspective_ragged_device(d_base, src_bytes, fmt | _lens_bits(lens_rows), itable, d_ideal.value, src_bytes)
                 self.synchronize()  # (the batch detector reads the frames on its lanes' streams, not after this one's work)
                 d_seen = d_ideal.value
             if max_size is not None:
@@ -1808,6 +1952,8 @@ class Context:
                 except LibrectifyError:
                     continue  # (collinear corners, a size below 1, ...: this frame has no image)
                 M, size, S = _bounded_map(M, size, out_max_size)
+                if lens_rows is not None and lens_maps is not None:
+                    M = lens_scale_compose(lens_maps[b], M)  # (from the scaled ideal picture, where the detector saw the lines, to the ideal one)
                 good.append(b)
                 Ms.append(M)
                 sizes.append(size)
@@ -1820,7 +1966,7 @@ class Context:
             if words is not None:
                 table[good, 17] = [words[b] for b in good]
             _check(lib().lr_device_malloc(self._h, total, C.byref(d_out)))
-            bits = cubic | (0 if words is None else WARP_BORDER) | (0 if lens_rows is None else WARP_LENS) | (0 if out_max_size is None else WARP_AREA)
+            bits = cubic | (0 if words is None else WARP_BORDER) | (0 if lens_rows is None else _lens_bits(lens_rows)) | (0 if out_max_size is None else WARP_AREA)
             for run in np.split(np.array(good), np.flatnonzero(np.diff(good) != 1) + 1):
                 rows = table[run] if lens_rows is None else np.concatenate([table[run], lens_rows[run]], axis=1)
                 if out_max_size is not None:
@@ -1892,7 +2038,7 @@ class Context:
 
     def rectify_batch(self, frames_u8, min_length=None, refine=False, cfg=None, clip=3.0, max_size=None, capacity=4096, jpeg=None,
                       orient=False, interp="linear", jpeg_optimize=False, any_sampling=False, border=None, crop=False, decode_scale=None,
-                      decode_max_size=None, lens=None, out_max_size=None):
+                      decode_max_size=None, lens=None, out_max_size=None, lens_scale=1):
         """Context.rectify for a batch: frames_u8 is a uint8 array [B, H, W] or [B, H, W, 3], or a list of such frames of one
         shape.  One upload, rectify_batch_device (one detector batch, the packed warp), one download.  Returns a
         list of (lines, transform, warped), frame by frame what rectify returns for it; warped is None for a frame whose
@@ -1928,7 +2074,9 @@ class Context:
         lens: None, one Lens for all frames or a list of one per frame, in which None means no lens (WARP_LENS): frame by frame
         what rectify(lens=) returns.  Arrays and files alike then take the mixed-size pipeline, with one WARP_LENS launch in
         front of it that writes the frames without their distortion for the detector, and the final warp reading the frames
-        as they were uploaded or decoded.  With crop=True: ValueError.
+        as they were uploaded or decoded.  With crop=True: ValueError.  A LensModel for all frames, or Lens, LensModel and
+        None mixed in the list: both launches then carry WARP_LENS_MODEL as well.  lens_scale=s (with lens=, else ValueError):
+        rectify's, for every frame whose lens is not None.
         out_max_size=N: every picture, or JPEG file, is at most N pixels on its longer side (WARP_AREA on the warp launch of
         whichever path is taken, after the crop and in front of the encoder) -- frame by frame what rectify(out_max_size=N)
         returns.  The full-size pictures never exist: HBM holds, the link carries and the encoder reads the small ones."""
@@ -1938,7 +2086,15 @@ class Context:
         if lens is not None:
             if crop:
                 raise ValueError("rectify_batch: crop=True together with lens= (the crop's rectangle assumes straight source edges)")
-            lens = _lens_rows(lens, len(frames_u8), "rectify_batch")
+            s = _check_lens_scale("rectify_batch", lens_scale)
+            rows = _lens_rows(lens, len(frames_u8), "rectify_batch")
+            maps = None
+            if s != 1.0:
+                given = [True] * len(rows) if isinstance(lens, (Lens, LensModel)) else [v is not None for v in lens]
+                maps = np.stack([lens_scale_map(Lens(*r[:9]), s) if g else np.eye(3) for r, g in zip(rows, given)])
+            lens = _LensPlan(rows, maps)
+        elif _check_lens_scale("rectify_batch", lens_scale) != 1.0:
+            raise ValueError("rectify_batch: lens_scale goes with lens=")
         if _all_streams(frames_u8, "rectify_batch", orient, any_sampling, decode_scale, decode_max_size):
             try:  # (the files' format is known once they are decoded: a spec that suits neither 8-bit format fails here)
                 _border_words(border, len(frames_u8), PIX_U8X3, "rectify_batch")

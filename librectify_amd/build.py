@@ -22,6 +22,7 @@ SOURCES = [
     "kernels_warp_border.hip",
     "kernels_warp_lens.hip",
     "kernels_warp_area.hip",
+    "kernels_warp_lens_model.hip",
     "kernels_prepare.hip",
     "kernels_overlay.hip",
     "kernels_jpeg.hip",

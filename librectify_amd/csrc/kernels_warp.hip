@@ -29,6 +29,9 @@
 // LR_WARP_LENS is a fourth: between the perspective divide and the rounding to 5-bit coordinates the point goes through the
 // frame's lens model (OpenCV's five coefficients; fixed_xy and lens_displace of warp_lane.h).  Its launches all go through
 // warp_ragged_lens_kernel, which is kernels_warp_lens.hip's, with a second array of records, one LensRecord per frame.
+// LR_WARP_LENS_MODEL widens the lens to seventeen entries (OpenCV's rational and thin-prism model, or cv::fisheye's); only a
+// call with a frame that needs them (LensSet below) launches kernels_warp_lens_model.hip's kernels, with a LensModelRecord per
+// frame; lenses that all fit the nine entries become LensRecords and take the kernels above.
 //
 // LR_WARP_AREA is no parameter of warp_lane but a loop around its per-pixel rules: S x S sub-samples per destination pixel under
 // the frame's fine map, averaged.  Its launches all go through warp_ragged_area_kernel, which is
@@ -146,14 +149,59 @@ const char* parse_lens(const double* t, LensRecord* l) {
     return nullptr;
 }
 
-int fail_lens(const char* layout, int b, const char* why) {
-    set_error(std::string("lr_warp_perspective_device: ") + layout + "LR_WARP_LENS: frame " + std::to_string(b) + ": the nine lens entries " + why);
+int fail_lens(const char* layout, int b, const char* why, int entries = 9) {
+    set_error(std::string("lr_warp_perspective_device: ") + layout + (entries == 17 ? "LR_WARP_LENS_MODEL: frame " : "LR_WARP_LENS: frame ") +
+              std::to_string(b) + (entries == 17 ? ": the seventeen lens entries " : ": the nine lens entries ") + why);
     return 1;
 }
 
 bool any_lens(const std::vector<LensRecord>& lens) {
     return std::any_of(lens.begin(), lens.end(), [](const LensRecord& l) { return l.has_lens != 0; });
 }
+
+// A frame's seventeen lens entries (LR_WARP_LENS_MODEL): fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6, s1, s2, s3, s4, model.
+// Fills the record; on a fault returns the reason (NULL: none).  A frame of model 0 whose twelve coefficients are all zero, of
+// either sign, has no lens: the plain rule.  A fisheye always has one: zero coefficients are the pure equidistant lens.
+const char* parse_lens_model(const double* t, LensModelRecord* l) {
+    for (int i = 0; i < 17; ++i)
+        if (!std::isfinite(t[i])) return "are not all finite";
+    if (!(t[0] > 0.0)) return "have fx <= 0";
+    if (!(t[1] > 0.0)) return "have fy <= 0";
+    if (t[16] != 0.0 && t[16] != 1.0) return "name a model that is not 0 (LR_LENS_RATIONAL) or 1 (LR_LENS_FISHEYE)";
+    const bool fisheye = t[16] == 1.0;
+    if (fisheye)
+        for (int i = 8; i < 16; ++i)
+            if (t[i] != 0.0) return "are a fisheye's (model 1) with a non-zero entry among [8..15]";
+    std::memset(l, 0, sizeof *l);
+    std::memcpy(&l->fx, t, 17 * sizeof(double));
+    l->kind = fisheye ? kLensFisheye : kLensNone;
+    for (int i = 4; i < 16 && !fisheye; ++i)
+        if (t[i] != 0.0) l->kind = kLensRational;
+    return nullptr;
+}
+
+// The lenses of a call, from rows of nine (LR_WARP_LENS) or seventeen (with LR_WARP_LENS_MODEL) entries.  After the last frame
+// settle() says what is launched: where no frame has a lens, what the call launches without the bits; where every frame fits the
+// nine entries (model 0, [9..15] zero), LR_WARP_LENS's records and kernels; the records of seventeen only where a frame needs them.
+struct LensSet {
+    int entries;  // per frame in the table: 0, 9 or 17
+    std::vector<LensRecord> nine;
+    std::vector<LensModelRecord> model;
+    LensSet(int entries_, size_t batch) : entries(entries_), nine(entries_ == 9 ? batch : 0), model(entries_ == 17 ? batch : 0) {}
+    const char* parse(size_t b, const double* t) { return entries == 17 ? parse_lens_model(t, &model[b]) : parse_lens(t, &nine[b]); }
+    void settle() {
+        if (entries != 17) return;
+        const bool fits = std::all_of(model.begin(), model.end(), [](const LensModelRecord& l) {
+            return l.kind != kLensFisheye && l.k4 == 0.0 && l.k5 == 0.0 && l.k6 == 0.0 && l.s1 == 0.0 && l.s2 == 0.0 && l.s3 == 0.0 && l.s4 == 0.0;
+        });
+        if (!fits) return;
+        nine.resize(model.size());
+        for (size_t b = 0; b < model.size(); ++b) parse_lens(&model[b].fx, &nine[b]);  // (checked already: the first nine entries are the nine)
+        model.clear();
+    }
+    const std::vector<LensRecord>* nine_if_any() const { return model.empty() && any_lens(nine) ? &nine : nullptr; }
+    const std::vector<LensModelRecord>* model_if_any() const { return model.empty() ? nullptr : &model; }
+};
 
 // A frame's sampling factor (LR_WARP_AREA): the last double of its row, an integer from 1 to 8.  Fills the record with S and
 // the fine map of the frame's map m (S = 1: m itself, the plain rule); on a fault returns the reason (NULL: none).
@@ -178,14 +226,15 @@ bool any_area(const std::vector<AreaRecord>& area) {
     return std::any_of(area.begin(), area.end(), [](const AreaRecord& a) { return a.s > 1; });
 }
 
-// The table kernel's launch: records, then (LR_WARP_LENS, `lens` not NULL) the lens records, then (LR_WARP_AREA, `area` not
-// NULL) the area records, then the tiles' prefix table, go up in the mirror of the maps (in doubles: 18 a frame, 10 a lens,
+// The table kernel's launch: records, then (LR_WARP_LENS, `lens` not NULL) the lens records or (LR_WARP_LENS_MODEL, `model` not
+// NULL; never both) the records of seventeen entries, then (LR_WARP_AREA, `area` not NULL) the area records, then the tiles'
+// prefix table, go up in the mirror of the maps (in doubles: 18 a frame, 10 a lens or 18 a lens of seventeen entries,
 // 10 an area record + the table's ints).  The area kernel cuts a frame with S > 1 into tiles of (64 / S) x (16 / S) destination
 // pixels (kernels_warp_area.hip: a tile is 64 x 16 samples), so with `area` the frames' tiles are counted again by that size.
 int launch_ragged(lr_context* c, const void* d_src, int format, bool cubic, bool border, const std::vector<RaggedFrame>& frame_rec,
                   const std::vector<int>& frame_start, void* d_dst, const std::vector<LensRecord>* lens = nullptr,
-                  const std::vector<AreaRecord>* area = nullptr) {
-    const size_t batch = frame_rec.size(), lens_doubles = lens ? batch * 10 : 0, area_doubles = area ? batch * 10 : 0;
+                  const std::vector<AreaRecord>* area = nullptr, const std::vector<LensModelRecord>* model = nullptr) {
+    const size_t batch = frame_rec.size(), lens_doubles = model ? batch * 18 : (lens ? batch * 10 : 0), area_doubles = area ? batch * 10 : 0;
     const size_t rec_doubles = batch * 18 + lens_doubles + area_doubles;
     std::vector<RaggedFrame> area_rec;
     std::vector<int> area_start;
@@ -212,7 +261,8 @@ int launch_ragged(lr_context* c, const void* d_src, int format, bool cubic, bool
     LR_HIP(hipSetDevice(c->device));
     if (upload_reserve(c, c->warp_m, c->ev_warp_m, rec_doubles + (batch + 2) / 2)) return 1;
     std::memcpy(c->warp_m.h, rec.data(), batch * 18 * sizeof(double));
-    if (lens) std::memcpy(c->warp_m.h + batch * 18, lens->data(), lens_doubles * sizeof(double));
+    if (model) std::memcpy(c->warp_m.h + batch * 18, model->data(), lens_doubles * sizeof(double));
+    else if (lens) std::memcpy(c->warp_m.h + batch * 18, lens->data(), lens_doubles * sizeof(double));
     if (area) std::memcpy(c->warp_m.h + batch * 18 + lens_doubles, area->data(), area_doubles * sizeof(double));
     std::memcpy(c->warp_m.h + rec_doubles, start.data(), start.size() * sizeof(int));
     if (upload_send(c, c->warp_m, c->ev_warp_m, rec_doubles * sizeof(double) + start.size() * sizeof(int))) return 1;
@@ -225,6 +275,12 @@ int launch_ragged(lr_context* c, const void* d_src, int format, bool cubic, bool
     const RaggedFrame* frames = reinterpret_cast<const RaggedFrame*>(c->warp_m.d.get());
     const int* tile_start = reinterpret_cast<const int*>(c->warp_m.d.get() + rec_doubles);
     const int grid = (int)std::min<int64_t>((n_tiles + 7) / 8 * 8, kMaxGrid);
+    if (model) {  // (some frame's lens needs the seventeen entries: the kernels of kernels_warp_lens_model.hip)
+        launch_warp_ragged_lens_model(format, cubic, border, grid, c->stream, g.src, g.batch, g.n_tiles, frames, c->warp_m.d.get() + batch * 18,
+                                      area ? c->warp_m.d.get() + batch * 18 + lens_doubles : nullptr, tile_start, dst);
+        LR_HIP(hipGetLastError());
+        return 0;
+    }
     if (area) {  // (some frame's S is above 1: the kernels of kernels_warp_area.hip, which take the border rules as they are)
         launch_warp_ragged_area(format, cubic, grid, c->stream, g.src, g.batch, g.n_tiles, frames, lens ? c->warp_m.d.get() + batch * 18 : nullptr,
                                 c->warp_m.d.get() + batch * 18 + lens_doubles, tile_start, dst);
@@ -251,7 +307,7 @@ int launch_ragged(lr_context* c, const void* d_src, int format, bool cubic, bool
 // lr_warp_perspective_device with LR_WARP_PACKED: M is the table of 13 doubles per frame, out_width x out_height bound the
 // frames' sizes and dst_image_bytes is the size of the whole destination region
 int warp_packed(lr_context* c, const void* d_src, size_t src_image_bytes, int batch, int width, int height, size_t src_row_bytes,
-                int format, bool cubic, bool border, bool lens, bool area, const double* T, void* d_dst, size_t dst_bytes, int out_width,
+                int format, bool cubic, bool border, int lens, bool area, const double* T, void* d_dst, size_t dst_bytes, int out_width,
                 int out_height, size_t dst_row_bytes) {
     auto fail = [](const char* what) {
         set_error(std::string("lr_warp_perspective_device: LR_WARP_PACKED: ") + what);
@@ -278,10 +334,10 @@ int warp_packed(lr_context* c, const void* d_src, size_t src_image_bytes, int ba
     std::vector<std::pair<uint64_t, uint64_t>> extent((size_t)batch);  // [first byte, end)
     int64_t n_tiles = 0;
     const size_t lens_at = border ? 14 : 13;                // (LR_WARP_BORDER: the border word behind the row)
-    const size_t area_at = lens_at + (lens ? 9 : 0);        // (LR_WARP_LENS: the nine lens entries behind that)
+    const size_t area_at = lens_at + (size_t)lens;          // (LR_WARP_LENS: the nine or seventeen lens entries behind that)
     const size_t row_doubles = area_at + (area ? 1 : 0);    // (LR_WARP_AREA: the sampling factor at the very end)
     bool bordered = false;                                  // some frame's word is not 0
-    std::vector<LensRecord> lenses(lens ? (size_t)batch : 0);
+    LensSet lenses(lens, (size_t)batch);
     std::vector<AreaRecord> areas(area ? (size_t)batch : 0);
     for (int b = 0; b < batch; ++b) {
         const double* t = T + (size_t)b * row_doubles;
@@ -316,7 +372,7 @@ int warp_packed(lr_context* c, const void* d_src, size_t src_image_bytes, int ba
             bordered = bordered || t[13] != 0.0;
         }
         if (lens)
-            if (const char* why = parse_lens(t + lens_at, &lenses[(size_t)b])) return fail_lens("LR_WARP_PACKED: ", b, why);
+            if (const char* why = lenses.parse((size_t)b, t + lens_at)) return fail_lens("LR_WARP_PACKED: ", b, why, lens);
         if (area)
             if (const char* why = parse_area(t[area_at], f.m, ow, oh, &areas[(size_t)b])) return fail_area("LR_WARP_PACKED: ", b, why);
         start[(size_t)b] = (int)n_tiles;
@@ -325,23 +381,24 @@ int warp_packed(lr_context* c, const void* d_src, size_t src_image_bytes, int ba
     }
     start[(size_t)batch] = (int)n_tiles;
     if (extents_overlap(extent)) return fail("two frames' extents overlap");
-    return launch_ragged(c, d_src, format, cubic, bordered, rec, start, d_dst, any_lens(lenses) ? &lenses : nullptr,
-                         any_area(areas) ? &areas : nullptr);
+    lenses.settle();
+    return launch_ragged(c, d_src, format, cubic, bordered, rec, start, d_dst, lenses.nine_if_any(), any_area(areas) ? &areas : nullptr,
+                         lenses.model_if_any());
 }
 
 // lr_warp_perspective_device with LR_WARP_RAGGED: M is the table of 18 doubles per frame, width x height and out_width x
 // out_height bound the frames' sizes, src_image_bytes and dst_image_bytes are the sizes of the two regions
 int warp_ragged(lr_context* c, const void* d_src, size_t src_bytes, int batch, int width, int height, size_t src_row_bytes,
-                int format, bool cubic, bool border, bool lens, bool area, const double* T, void* d_dst, size_t dst_bytes, int out_width,
+                int format, bool cubic, bool border, int lens, bool area, const double* T, void* d_dst, size_t dst_bytes, int out_width,
                 int out_height, size_t dst_row_bytes) {
     std::vector<RaggedEntry> e;
     int64_t n_tiles = 0;
     // LR_WARP_BORDER: entry [17] is the frame's border word; the table's other checks see it as the 0 they ask for
-    // LR_WARP_LENS: rows of 27, the nine lens entries behind [17]; the table's checks see rows of 18
+    // LR_WARP_LENS: rows of 27 (LR_WARP_LENS_MODEL: 35), the lens entries behind [17]; the table's checks see rows of 18
     // LR_WARP_AREA: one more, the sampling factor at the very end
     std::vector<double> plain;
     const double* words = T;
-    const size_t area_at = lens ? 27 : 18, row_doubles = area_at + (area ? 1 : 0);
+    const size_t area_at = 18 + (size_t)lens, row_doubles = area_at + (area ? 1 : 0);
     if ((border || lens || area) && T && batch >= 1) {
         plain.resize((size_t)batch * 18);
         for (int b = 0; b < batch; ++b) {
@@ -350,7 +407,7 @@ int warp_ragged(lr_context* c, const void* d_src, size_t src_bytes, int batch, i
         }
         T = plain.data();
     }
-    std::vector<LensRecord> lenses(lens && batch >= 1 ? (size_t)batch : 0);
+    LensSet lenses(lens, batch >= 1 ? (size_t)batch : 0);
     std::vector<AreaRecord> areas(area && batch >= 1 ? (size_t)batch : 0);
     bool bordered = false;  // some frame's word is not 0
     if (ragged_parse(d_src, src_bytes, batch, width, height, src_row_bytes, format, false, T, d_dst, dst_bytes, out_width,
@@ -379,15 +436,16 @@ int warp_ragged(lr_context* c, const void* d_src, size_t src_bytes, int batch, i
             bordered = bordered || word != 0.0;
         }
         if (lens)
-            if (const char* why = parse_lens(words + (size_t)b * row_doubles + 18, &lenses[(size_t)b])) return fail_lens("LR_WARP_RAGGED: ", b, why);
+            if (const char* why = lenses.parse((size_t)b, words + (size_t)b * row_doubles + 18)) return fail_lens("LR_WARP_RAGGED: ", b, why, lens);
         if (area)
             if (const char* why = parse_area(words[(size_t)b * row_doubles + area_at], f.m, s.ow, s.oh, &areas[(size_t)b])) return fail_area("LR_WARP_RAGGED: ", b, why);
         start[(size_t)b] = tiles;
         tiles += f.tiles_x * (int)((s.oh + kTileH - 1) / kTileH);
     }
     start[(size_t)batch] = tiles;
-    return launch_ragged(c, d_src, format, cubic, bordered, rec, start, d_dst, any_lens(lenses) ? &lenses : nullptr,
-                         any_area(areas) ? &areas : nullptr);
+    lenses.settle();
+    return launch_ragged(c, d_src, format, cubic, bordered, rec, start, d_dst, lenses.nine_if_any(), any_area(areas) ? &areas : nullptr,
+                         lenses.model_if_any());
 }
 
 }  // namespace
@@ -476,7 +534,17 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
         format &= ~LR_WARP_BORDER;
     }
     // LR_WARP_LENS: nine lens entries per frame at the end of its row of M; likewise of the three warps alone
-    const bool lens = (format & LR_WARP_LENS) != 0;
+    // LR_WARP_LENS_MODEL: with it the lens entries are seventeen; an option of LR_WARP_LENS and of nothing else
+    const bool lens_model = (format & LR_WARP_LENS_MODEL) != 0;
+    if (lens_model) {
+        if (format & LR_WARP_PREPARE) return fail("LR_WARP_LENS_MODEL together with LR_WARP_PREPARE (the prepare step is an area average of the stored frame)");
+        if (format & LR_WARP_LINES) return fail("LR_WARP_LENS_MODEL together with LR_WARP_LINES (the lines picture samples nothing)");
+        if (format & LR_WARP_JPEG) return fail("LR_WARP_LENS_MODEL together with LR_WARP_JPEG (the encoder samples nothing)");
+        if (format & LR_WARP_JPEG_DECODE) return fail("LR_WARP_LENS_MODEL together with LR_WARP_JPEG_DECODE (the decoder samples nothing)");
+        if (!(format & LR_WARP_LENS)) return fail("LR_WARP_LENS_MODEL without LR_WARP_LENS (it widens that bit's lens entries)");
+        format &= ~LR_WARP_LENS_MODEL;
+    }
+    const int lens = (format & LR_WARP_LENS) != 0 ? (lens_model ? 17 : 9) : 0;
     if (lens) {
         if (format & LR_WARP_PREPARE) return fail("LR_WARP_LENS together with LR_WARP_PREPARE (the prepare step is an area average of the stored frame)");
         if (format & LR_WARP_LINES) return fail("LR_WARP_LENS together with LR_WARP_LINES (the lines picture samples nothing)");
@@ -561,7 +629,7 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
         if (bits & 3u) return fail("f32 pointer or stride not 4-byte aligned");
     }
     const size_t lens_at = border ? 10 : 9;               // (LR_WARP_BORDER: the border word behind the map)
-    const size_t area_at = lens_at + (lens ? 9 : 0);      // (LR_WARP_LENS: the nine lens entries behind that)
+    const size_t area_at = lens_at + (size_t)lens;        // (LR_WARP_LENS: the nine or seventeen lens entries behind that)
     const size_t row_doubles = area_at + (area ? 1 : 0);  // (LR_WARP_AREA: the sampling factor at the very end)
     for (size_t b = 0; b < (size_t)batch; ++b)
         for (size_t i = 0; i < 9; ++i)
@@ -571,7 +639,7 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
     if (n_tiles > 0x7FFFFFF0ll) return fail("output larger than 2^31 tiles of 64 x 16 pixels");
     if (border || lens || area) {  // the frames as records of the table kernel; where every word is 0, no frame has a lens and every S is 1, the launch below as without the bits
         std::vector<RaggedFrame> rec((size_t)batch);
-        std::vector<LensRecord> lenses(lens ? (size_t)batch : 0);
+        LensSet lenses(lens, (size_t)batch);
         std::vector<AreaRecord> areas(area ? (size_t)batch : 0);
         std::vector<int> start((size_t)batch + 1);
         bool bordered = false;
@@ -594,15 +662,16 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
                 bordered = bordered || t[9] != 0.0;
             }
             if (lens)
-                if (const char* why = parse_lens(t + lens_at, &lenses[(size_t)b])) return fail_lens("", b, why);
+                if (const char* why = lenses.parse((size_t)b, t + lens_at)) return fail_lens("", b, why, lens);
             if (area)
                 if (const char* why = parse_area(t[area_at], f.m, (uint64_t)out_width, (uint64_t)out_height, &areas[(size_t)b])) return fail_area("", b, why);
             start[(size_t)b] = (int)(tiles_x * tiles_y * b);
         }
         start[(size_t)batch] = (int)n_tiles;
-        const bool lensed = any_lens(lenses), sampled = any_area(areas);
+        lenses.settle();
+        const bool lensed = lenses.nine_if_any() || lenses.model_if_any(), sampled = any_area(areas);
         if (bordered || lensed || sampled)
-            return launch_ragged(c, d_src, format, cubic, bordered, rec, start, d_dst, lensed ? &lenses : nullptr, sampled ? &areas : nullptr);
+            return launch_ragged(c, d_src, format, cubic, bordered, rec, start, d_dst, lenses.nine_if_any(), sampled ? &areas : nullptr, lenses.model_if_any());
     }
 
     LR_HIP(hipSetDevice(c->device));

@@ -3,6 +3,7 @@
 // kernels are a code object of their own, so that the one kernels_warp.hip makes holds exactly the kernels it held before them.
 // kernels_warp_lens.hip (the kernels with a lens model per frame, LR_WARP_LENS) is a third of the same kind.
 // kernels_warp_area.hip (the kernels that average S x S samples per destination pixel, LR_WARP_AREA) is a fourth.
+// kernels_warp_lens_model.hip (the kernels with a lens of seventeen entries per frame, LR_WARP_LENS_MODEL) is a fifth.
 // Everything here has internal linkage; what kernels_warp.hip says about tiles, records and loads holds for all of them.
 #pragma once
 #include <cstdint>
@@ -28,6 +29,13 @@ void launch_warp_ragged_lens(int format, bool cubic, bool border, int grid, hipS
 // one per frame; `lenses` NULL: no frame has a lens; the records' border rules always hold (a zero word is the zero border)
 void launch_warp_ragged_area(int format, bool cubic, int grid, hipStream_t stream, const uint8_t* src, int batch, int n_tiles,
                              const void* frames, const void* lenses, const void* areas, const int* start, uint8_t* dst);
+
+// the launch of kernels_warp_lens_model.hip's kernels (LR_WARP_LENS_MODEL): `lenses` the device array of LensModelRecord
+// records, one per frame; `areas` NULL: warp_ragged_lens_model_kernel (`border`: with the records' border rules), otherwise
+// warp_ragged_area_lens_model_kernel with the AreaRecord records, for which the border rules always hold
+void launch_warp_ragged_lens_model(int format, bool cubic, bool border, int grid, hipStream_t stream, const uint8_t* src, int batch,
+                                   int n_tiles, const void* frames, const void* lenses, const void* areas, const int* start,
+                                   uint8_t* dst);
 
 namespace {
 
@@ -67,6 +75,27 @@ struct LensRecord {
     int pad;
 };
 static_assert(sizeof(LensRecord) == 10 * sizeof(double), "a record per 10 doubles of the mirror");
+
+// LR_WARP_LENS_MODEL: a frame's lens of seventeen entries, the doubles of its table row (OpenCV's order of distCoeffs behind the
+// camera matrix, then the model), and what the host made of them: kLensNone (model 0 with [4..15] all zero: the plain rule),
+// kLensRational or kLensFisheye
+struct LensModelRecord {
+    double fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6, s1, s2, s3, s4, model;
+    int kind;
+    int pad;
+};
+static_assert(sizeof(LensModelRecord) == 18 * sizeof(double), "a record per 18 doubles of the mirror");
+enum : int { kLensNone = 0, kLensRational = 1, kLensFisheye = 2 };
+
+// the lens argument of the lane body: kLens 0: none (never looked at), 1: a LensRecord, 2: a LensModelRecord
+template <int kLens>
+struct LensOf {
+    using type = LensRecord;
+};
+template <>
+struct LensOf<2> {
+    using type = LensModelRecord;
+};
 
 // LR_WARP_AREA: a frame's sampling factor S (1 .. 8) and its fine map F (lr_area_fine_map of the frame's M and S; S = 1: M)
 struct AreaRecord {
@@ -108,17 +137,77 @@ __device__ __forceinline__ void lens_displace(const LensRecord* __restrict__ l, 
     V = V + 32.0 * dv;
 }
 
+// ---- LR_WARP_LENS_MODEL (tests/numpy_warp_lens_model_ref.py) ----
+
+// The rule's arctangent of r >= 0, out of + - * /, comparisons and one rint, so that the device, the header's lr_lens_atan and
+// the NumPy reference run it operation for operation: r > 1 is reflected (pi/2 - ATAN(1 / r)); t in [0, 1] is reduced by the
+// nearest of the nine points c = i / 8 (z = (t - c) / (1 + t c), |z| <= 1/16), and ATAN(t) = atan(c) + (z + z (z^2 p(z^2))), p the
+// series -1/3 + z^2 / 5 - ... - z^14 / 15.  A NaN takes entry 0 of the table and stays a NaN.  Out of line: one copy a kernel
+// instead of one per pixel of a lane's unrolled four (the frame's model is uniform, so the call does not diverge).
+__device__ __noinline__ double lens_atan(double r) {
+    static constexpr double kAtan[9] = {0x0.0p+0,
+                                        0x1.fd5ba9aac2f6ep-4,
+                                        0x1.f5b75f92c80ddp-3,
+                                        0x1.6f61941e4def1p-2,
+                                        0x1.dac670561bb4fp-2,
+                                        0x1.1e00babdefeb4p-1,
+                                        0x1.4978fa3269ee1p-1,
+                                        0x1.700a7c5784634p-1,
+                                        0x1.921fb54442d18p-1};
+    const bool big = r > 1.0;
+    const double t = big ? 1.0 / r : r;
+    const double n = rint(8.0 * t);
+    const int i = n >= 0.0 && n <= 8.0 ? (int)n : 0;
+    const double c = (double)i / 8.0;
+    const double z = (t - c) / (1.0 + t * c);
+    const double z2 = z * z;
+    const double p = -1.0 / 3.0 + z2 * (1.0 / 5.0 + z2 * (-1.0 / 7.0 + z2 * (1.0 / 9.0 + z2 * (-1.0 / 11.0 + z2 * (1.0 / 13.0 + z2 * (-1.0 / 15.0))))));
+    const double at = kAtan[i] + (z + z * (z2 * p));
+    return big ? 0x1.921fb54442d18p+0 - at : at;
+}
+
+// the point (U, V) of the ideal picture (1/32 pixels) through the frame's lens of seventeen entries: model 0 as a displacement,
+// like lens_displace; model 1 (the fisheye) has no displacement form.  Divisions and the square root stay what they are.
+__device__ __forceinline__ void lens_model_apply(const LensModelRecord* __restrict__ l, double& U, double& V) {
+    const double a = (U * 0.03125 - l->cx) / l->fx, b = (V * 0.03125 - l->cy) / l->fy;
+    const double aa = a * a, bb = b * b;
+    const double r2 = aa + bb;
+    if (l->kind == kLensFisheye) {
+        const double r = __dsqrt_rn(r2);
+        const double th = lens_atan(r);
+        const double t2 = th * th;
+        const double thd = th * (1.0 + t2 * (l->k1 + t2 * (l->k2 + t2 * (l->p1 + t2 * l->p2))));  // (entries [4..7] are the fisheye's k1..k4)
+        const double sc = r != 0.0 ? thd / r : 1.0;
+        U = 32.0 * (l->fx * (a * sc) + l->cx);
+        V = 32.0 * (l->fy * (b * sc) + l->cy);
+        return;
+    }
+    const double ab = a * b;
+    const double radn = r2 * (l->k1 + r2 * (l->k2 + r2 * l->k3));
+    const double radd = r2 * (l->k4 + r2 * (l->k5 + r2 * l->k6));
+    const double rad = (radn - radd) / (1.0 + radd);
+    const double ta = ((2.0 * l->p1) * ab + l->p2 * (r2 + 2.0 * aa)) + r2 * (l->s1 + r2 * l->s2);
+    const double tb = (l->p1 * (r2 + 2.0 * bb) + (2.0 * l->p2) * ab) + r2 * (l->s3 + r2 * l->s4);
+    const double du = l->fx * (a * rad + ta), dv = l->fy * (b * rad + tb);
+    U = U + 32.0 * du;
+    V = V + 32.0 * dv;
+}
+
 // the 5-bit fixed-point source coordinates of destination pixel (x, y): both sampling rules start from them; kLens: through the
-// frame's lens (`lens`, uniform across the workgroup like m) where it has one
-template <bool kLens = false>
+// frame's lens (`lens`, uniform across the workgroup like m) where it has one; kLens 2: the lens is a LensModelRecord
+template <int kLens = 0>
 __device__ __forceinline__ void fixed_xy(const double* __restrict__ m, unsigned x, unsigned y, int& X, int& Y,
-                                         const LensRecord* __restrict__ lens = nullptr) {
+                                         const typename LensOf<kLens>::type* __restrict__ lens = nullptr) {
     const double xd = (double)x, yd = (double)y;
     const double W0 = (m[6] * xd + m[7] * yd) + m[8];
     const double Wq = W0 != 0.0 ? 32.0 / W0 : 0.0;
-    if constexpr (kLens) {
+    if constexpr (kLens != 0) {
         double U = ((m[0] * xd + m[1] * yd) + m[2]) * Wq, V = ((m[3] * xd + m[4] * yd) + m[5]) * Wq;
-        if (lens->has_lens) lens_displace(lens, U, V);
+        if constexpr (kLens == 2) {
+            if (lens->kind != kLensNone) lens_model_apply(lens, U, V);
+        } else {
+            if (lens->has_lens) lens_displace(lens, U, V);
+        }
         X = fixed_coord(U);
         Y = fixed_coord(V);
     } else {
@@ -127,8 +216,8 @@ __device__ __forceinline__ void fixed_xy(const double* __restrict__ m, unsigned 
     }
 }
 
-template <bool kLens = false>
-__device__ __forceinline__ Taps taps_of(const double* __restrict__ m, unsigned x, unsigned y, const LensRecord* __restrict__ lens = nullptr) {
+template <int kLens = 0>
+__device__ __forceinline__ Taps taps_of(const double* __restrict__ m, unsigned x, unsigned y, const typename LensOf<kLens>::type* __restrict__ lens = nullptr) {
     int X, Y;
     fixed_xy<kLens>(m, x, y, X, Y, lens);
     Taps t;
@@ -272,10 +361,10 @@ __device__ __forceinline__ uint32_t load_tap(const uint8_t* row, int cx) {
 // they come in as in the unbordered rule (paired loads); otherwise the constant border gives `value` for a tap outside and
 // the other modes map the two columns and the two rows once (border_index) and read the four pixels they name.  `mode` is the
 // frame's and uniform across the workgroup.  Result as cubic_pixel's.
-template <int kFormat, bool kLens = false>
+template <int kFormat, int kLens = 0>
 __device__ __forceinline__ void border_linear_pixel(const double* m, const uint8_t* src, size_t src_row_bytes, int w, int h,
                                                     unsigned x, unsigned y, int mode, uint32_t value, uint32_t& px, float& pf,
-                                                    const LensRecord* lens = nullptr) {
+                                                    const typename LensOf<kLens>::type* lens = nullptr) {
     const Taps t = taps_of<kLens>(m, x, y, lens);
     uint32_t v[4];  // (ix, iy), (ix + 1, iy), (ix, iy + 1), (ix + 1, iy + 1), in border_tap's form
     if (t.ix >= 0 && t.ix + 1 < w && t.iy >= 0 && t.iy + 1 < h) {  // (|ix|, |iy| <= 2^26: no overflow)
@@ -369,9 +458,10 @@ __device__ __forceinline__ void border_row_taps(const uint8_t* row, bool row_in,
 // Everything fits int32: max sum |C[a]| is 2816 and 255 * 2816^2 + 2^21 = 2 024 210 432 < 2^31.  f32: weights C / 2048.f
 // (exact), rows and then the column summed from the first tap to the last, every product and sum rounded on its own.
 // kBorder: a row's taps come through border_row_taps (the frame's `mode` and `value`); without it the two arguments are unused.
-template <int kFormat, bool kBorder, bool kLens = false>
+template <int kFormat, bool kBorder, int kLens = 0>
 __device__ __forceinline__ void cubic_pixel(const double* m, const uint8_t* src, size_t src_row_bytes, int w, int h, unsigned x,
-                                            unsigned y, int mode, uint32_t value, uint32_t& px, float& pf, const LensRecord* lens = nullptr) {
+                                            unsigned y, int mode, uint32_t value, uint32_t& px, float& pf,
+                                            const typename LensOf<kLens>::type* lens = nullptr) {
     constexpr int kBpp = PixelBytes<kFormat>::value;
     constexpr int kChannels = kFormat == LR_PIX_U8X3 ? 3 : 1;
     int X, Y;
@@ -445,11 +535,12 @@ __device__ __forceinline__ void cubic_pixel(const double* m, const uint8_t* src,
 // One lane's four consecutive pixels (x0 .. x0 + 3, those below ow) of destination row y, whose first byte is `out`;
 // kCubic: sampled by the bicubic rule above instead of the bilinear one; kBorder: with the frame's border rule (`mode`,
 // `value`: LR_WARP_BORDER) instead of the constant zero one, which with kBorder false is the parent's code and ignores both;
-// kLens: the coordinates go through the frame's lens (`lens`: LR_WARP_LENS), which with kLens false is never looked at
-template <int kFormat, bool kCubic, bool kBorder, bool kLens = false>
+// kLens: the coordinates go through the frame's lens (`lens`: 1 LR_WARP_LENS's record, 2 LR_WARP_LENS_MODEL's), which with
+// kLens 0 is never looked at
+template <int kFormat, bool kCubic, bool kBorder, int kLens = 0>
 __device__ __forceinline__ void warp_lane(const double* m, const uint8_t* src, size_t src_row_bytes, int w, int h,
                                           uint8_t* out, int ow, unsigned x0, unsigned y, int mode = 0, uint32_t value = 0,
-                                          const LensRecord* lens = nullptr) {
+                                          const typename LensOf<kLens>::type* lens = nullptr) {
     const int n = min(4, ow - (int)x0);  // pixels of this lane inside the row
 
     uint32_t res_u8 = 0;          // LR_PIX_U8: four bytes
