@@ -958,6 +958,9 @@ enum lr_buffer_id {
     LR_BUF_MAXMAG = 7,    /* float  1 */
     LR_BUF_SEED_SIZE = 8, /* int32  n_seeds: pixels claimed by each seed's flood (0 = skipped) */
     LR_BUF_SEED_REC = 9,  /* uint32 n_seeds x 4: {SEED_IDX, SEED_BIN, bits of SEED_THR, 0}, the record the flood's walks read */
+    LR_BUF_COUNTS = 10,   /* uint32 16: the last frame's count words -- [0] seeds, [1] components, [2] their pixels, [12] components
+                             that were fitted, [13] their pixels ([1] and [2] again unless the frame call left out the fit of components
+                             too small for its min_length: lr_set_estimator); the other words are internal */
 };
 int lr_download(lr_context* ctx, int buffer_id, void* dst, size_t bytes);
 
@@ -1020,7 +1023,10 @@ int lr_refine_lines(lr_context* ctx, const LineSegment* in, int n, LineSegment* 
  * "pure RANSAC is used"), so RANSAC is the default here too.  kind: 0 = RANSAC, 1 = PROSAC with T_N iterations
  * (<= 0: the reference's niter_RANSAC(0.9, 0.5, 2) = 9, prosac.h:116), 2 = DirectEstimator (refit on the lines whose
  * Hough weight exceeds 0.95; the parameter is ignored), 3 = the diamond-space accumulator (cht.h:13-24) with a
- * param x param accumulator (<= 0: 128; 8..128), see lr_estimate_line_pencils_cht. */
+ * param x param accumulator (<= 0: 128; 8..128), see lr_estimate_line_pencils_cht.
+ * kind 0 has one setting: by default a frame call does not fit components of at most floor(max(min_length, 5) / 1.4157)
+ * pixels, whose segments cannot pass its length test (results and counts are the same; LR_BUF_COUNTS [12], [13] say what
+ * was fitted); param == 0 fits every component, any other value (the Python default is -1) leaves them out. */
 void lr_set_estimator(lr_context* ctx, int kind, int param);
 /* estimate_multiple_structures (estimator.h:99-145) around the diamond-space accumulator as cht.h:13-24 describes
  * it: all lines vote once (length-weighted polylines, integer votes in LDS), every round takes the accumulator's

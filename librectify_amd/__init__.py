@@ -77,6 +77,7 @@ class JpegDecodeArgs(C.Structure):  # lr_jpeg_decode_args
 
 BUF_DX, BUF_DY, BUF_DMASK, BUF_LABEL, BUF_SEED_IDX, BUF_SEED_BIN, BUF_SEED_THR, BUF_MAXMAG, BUF_SEED_SIZE = range(9)
 BUF_SEED_REC = 9  # uint32 (n_seeds, 4): index, bin, bits of the threshold, 0
+BUF_COUNTS = 10  # uint32 (16,): [0] seeds, [1] components, [2] their pixels, [12] components that were fitted, [13] their pixels
 T_UPLOAD, T_FILTER, T_SEEDS, T_FLOOD, T_FIT, T_RANSAC, T_TOTAL, T_FILTER_KERNEL, T_COUNT = range(9)
 PIX_U8, PIX_U8X3, PIX_F32 = range(3)  # enum lr_pixel_format
 WARP_PREPARE = 0x100  # enum lr_warp_option, or-ed into the format of lr_warp_perspective_device
@@ -1155,6 +1156,8 @@ class Context:
             a = np.zeros(1, np.float32)
         elif buf == BUF_SEED_REC:
             a = np.zeros((self.n_seeds, 4), np.uint32)
+        elif buf == BUF_COUNTS:
+            a = np.zeros(16, np.uint32)
         else:
             raise ValueError(buf)
         if a.nbytes:

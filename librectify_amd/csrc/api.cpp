@@ -514,6 +514,7 @@ int lr_download(lr_context* ctx, int buffer_id, void* dst, size_t bytes) {
             case LR_BUF_MAXMAG: src = ctx->maxmag; have = 4; break;
             case LR_BUF_SEED_SIZE: src = ctx->ws.seed_size; have = (size_t)ctx->n_seeds * 4; break;
             case LR_BUF_SEED_REC: src = ctx->ws.seed_rec; have = (size_t)ctx->n_seeds * 16; break;
+            case LR_BUF_COUNTS: src = ctx->d_counts; have = 16 * 4; break;
             default: set_error("lr_download: unknown buffer id"); return 1;
         }
         if (buffer_id == LR_BUF_DMASK && ctx->dmask_consumed) {
@@ -627,6 +628,9 @@ int lr_refine_lines(lr_context* ctx, const LineSegment* in, int n, LineSegment* 
 
 void lr_set_estimator(lr_context* ctx, int kind, int param) {
     ctx->opt.estimator = kind;
+    // (the default estimator has one setting: param 0 = every component is fitted before the length test, as until the fit
+    // threshold came -- kernels_fit.hip: component_offsets_kernel; any other value, -1 by default, leaves the small ones out)
+    if (kind == 0) ctx->opt.fit_prune = param != 0;
     if (kind == 3) ctx->opt.cht_d = param > 0 ? param : 128;
     else ctx->opt.prosac_T_N = param;
 }

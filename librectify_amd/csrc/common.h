@@ -297,9 +297,12 @@ struct HugeSort {
 };
 // n_large: seven words (kernels_fit.hip), cleared by the launch; cursor: one word per component, written by it;
 // temp: fit_temp_bytes() bytes, ZERO when allocated (tagged status words); frame_tag: not 0, different from call to call
-int launch_component_offsets(const int32_t* seed_size, const uint32_t* d_n_seeds, uint32_t seed_cap, int min_size,
+// fit_min >= min_size: floods of up to fit_min pixels get no component (they are counted in `totals` all the same);
+// fit_totals: the components and pixels that the scatter, sort and fit launches work on
+int launch_component_offsets(const int32_t* seed_size, const uint32_t* d_n_seeds, uint32_t seed_cap, int min_size, int fit_min,
                              uint32_t* comp_rank, uint32_t* comp_seed, uint32_t* comp_off,
-                             uint32_t* totals /*[0]=n_comp,[1]=n_px*/, uint32_t* large_list, uint32_t large_cap,
+                             uint32_t* totals /*[0]=n_comp,[1]=n_px*/, uint32_t* fit_totals /*the same, fitted*/,
+                             uint32_t* large_list, uint32_t large_cap,
                              uint32_t* n_large, void* temp, size_t temp_bytes, uint32_t frame_tag, uint32_t* cursor, const HugeSort& hs,
                              hipStream_t s);
 // with_huge = false: the caller knows that no flood of the frame has more than 2^14 pixels (the launches for those are left out)
@@ -356,7 +359,9 @@ enum {  // words of the peeling control block
     kGcWords = 8,
 };
 // all / round0 (both or neither): the kept segments' pencil model goes into these tables in the same launch (launch_pencil_model's work)
-int launch_filter_lines(const LineSegment* raw, const uint32_t* d_n_raw, uint32_t raw_cap, float min_length,
+// d_n_fit: segments in `raw`; d_n_raw: the frame's components, of which those are the ones that were fitted (the same word
+// unless the fit was pruned: kernels_fit.hip, component_offsets_kernel)
+int launch_filter_lines(const LineSegment* raw, const uint32_t* d_n_fit, const uint32_t* d_n_raw, uint32_t raw_cap, float min_length,
                         LineSegment* out, uint32_t* gctl, float* gnorm, const PencilTable* all, const PencilTable* round0,
                         hipStream_t s);
 int launch_lines_bbox(LineSegment* lines, uint32_t n, uint32_t* gctl, float* gnorm, hipStream_t s);

@@ -29,6 +29,7 @@ struct Settings {
     bool flood_log_sweep = false;  // test hook (lr_set_flood_logs(ctx, 2)): every footprint worked out from a log goes the fall-back way (sweeps)
     bool flood_logs = true;     // blocked seeds work their next footprint out from the records of their last walk (kernels_flood.hip: flood_rewalk_kernel); lr_set_flood_logs, LIBRECTIFY_FLOOD_LOGS=0
     bool flood_staged = false;  // lr_set_flood_staged: the rounds start on the strongest eighth of the seeds (test / experiment hook)
+    bool fit_prune = true;      // fused frames leave out the fit of floods too small to pass the frame's length test (kernels_fit.hip: component_offsets_kernel); lr_set_estimator(ctx, 0, 0) fits them all
     // Stage timers (HIP events between the stages of a frame): off in the frame calls unless lr_set_stage_timing or
     // LIBRECTIFY_STAGE_TIMES asks -- every event record is a barrier packet in the stream, some 6 us of idle GPU each,
     // seven of them per frame.  The staged API (lr_stage_*) always times its stages.

@@ -2,6 +2,7 @@
 // for device and host images.
 #include "host.h"
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -258,14 +259,25 @@ int finish_flood(lr_context* c, bool* extra) {
     return 0;
 }
 
-int enqueue_fit(lr_context* c) {
+// Floods of up to this many pixels cannot give a segment longer than ml = max(min_length, kLineMinLength), whatever their
+// shape (the proof stands beside component_offsets_kernel, kernels_fit.hip): floor(ml / 1.4157), never below the size
+// threshold itself.  The frame's own min_length: the frames of a table each have theirs.
+int fit_min_for(float min_length) {
+    const double ml = std::fmax((double)min_length, (double)kLineMinLength);  // (a NaN is the floor, as in filter_lines_kernel)
+    const double n = std::floor(ml / 1.4157);
+    return (int)std::min(std::max(n, (double)kComponentMinSize), 1073741824.0);
+}
+
+// fit_min: floods of up to that many pixels get no component (kComponentMinSize: every component is fitted -- the staged API,
+// refine and the opt-in estimators, which need all raw segments)
+int enqueue_fit(lr_context* c, int fit_min = kComponentMinSize) {
     const size_t npix = (size_t)c->w * c->h;
     const uint32_t comp_cap = line_cap_for(c);
     // Floods of more than 2^14 pixels have launches of their own (kernels_fit.hip: huge_count_kernel, huge_sort_kernel), left
     // out when the host KNOWS that the frame has none: the flood's rounds, enqueued just in time, report their largest commit.
     const bool with_huge = !(c->opt.flood_mode != 0 && c->flood_prog.sizes_known && c->flood_prog.max_flood <= (1u << 14));
-    if (launch_component_offsets(c->ws.seed_size, c->d_counts + kCntSeeds, c->seed_cap, kComponentMinSize, c->ws.comp_rank,
-                                 c->ws.comp_seed, c->ws.comp_off, c->d_counts + kCntComp, c->ws.comp_large,
+    if (launch_component_offsets(c->ws.seed_size, c->d_counts + kCntSeeds, c->seed_cap, kComponentMinSize, fit_min, c->ws.comp_rank,
+                                 c->ws.comp_seed, c->ws.comp_off, c->d_counts + kCntComp, c->d_counts + kCntFitComp, c->ws.comp_large,
                                  (uint32_t)(c->ws.cap_pix / 64 + 16), c->d_counts + kCntLarge, c->ws.temp, c->ws.temp.cap(), ++c->fit_tag ? c->fit_tag : ++c->fit_tag, c->ws.cursor,
                                  with_huge ? c->ws.huge : HugeSort{}, c->stream))
         return 1;
@@ -273,7 +285,7 @@ int enqueue_fit(lr_context* c) {
                                  c->stream))
         return 1;
     // (the sorted seed keys are dead once the seeds are set up: their buffer is the large lists' sorting scratch)
-    if (launch_component_sort(c->ws.px_a, c->ws.px_b, c->ws.comp_off, c->d_counts + kCntComp, comp_cap, c->ws.comp_large,
+    if (launch_component_sort(c->ws.px_a, c->ws.px_b, c->ws.comp_off, c->d_counts + kCntFitComp, comp_cap, c->ws.comp_large,
                               (uint32_t)(c->ws.cap_pix / 64 + 16), c->d_counts + kCntLarge, reinterpret_cast<uint32_t*>(c->ws.keys_b.get()),
                               c->ws.cursor, c->ws.huge, with_huge, c->stream))
         return 1;
@@ -282,6 +294,7 @@ int enqueue_fit(lr_context* c) {
         uint32_t cnt[16];
         LR_HIP(hipStreamSynchronize(c->stream));
         LR_HIP(hipMemcpy(cnt, c->d_counts, sizeof(cnt), hipMemcpyDeviceToHost));
+        std::fprintf(stderr, "fit: threshold %d, %u components of %u px fitted\n", fit_min, cnt[kCntFitComp], cnt[kCntFitPx]);
         std::fprintf(stderr, "fit: with_huge %d (sizes known %d, largest flood %u); seeds %u comps %u px %u; lists: %u of 65..1024 px, %u longer, %u huge in %u buckets; counter %u\n",
                      (int)with_huge, (int)c->flood_prog.sizes_known, c->flood_prog.max_flood, cnt[0], cnt[1], cnt[2], cnt[4], cnt[5], cnt[6], cnt[7], cnt[10]);
         const uint32_t nj = std::min<uint32_t>(cnt[7], 6);
@@ -289,7 +302,7 @@ int enqueue_fit(lr_context* c) {
         if (nj) LR_HIP(hipMemcpy(jobs.data(), c->ws.huge.jobs, nj * 16, hipMemcpyDeviceToHost));
         for (uint32_t j = 0; j < nj; ++j) std::fprintf(stderr, "   bucket job %u: start %u, %u px, table word %u\n", j, jobs[4 * j], jobs[4 * j + 1], jobs[4 * j + 2]);
     }
-    if (launch_fit(c->ws.px_b, c->ws.px_a, c->ws.comp_off, c->ws.comp_seed, c->d_counts + kCntComp, comp_cap, c->ws.seed_bin, c->ws.dx, c->ws.dy, c->w,
+    if (launch_fit(c->ws.px_b, c->ws.px_a, c->ws.comp_off, c->ws.comp_seed, c->d_counts + kCntFitComp, comp_cap, c->ws.seed_bin, c->ws.dx, c->ws.dy, c->w,
                    c->trig, c->ws.scratch_w, c->ws.d_lines, c->ws.cursor, c->ws.huge, c->d_counts + kCntLarge, with_huge, c->stream))
         return 1;
     if (c->opt.timing_on) LR_HIP(hipEventRecord(c->ev[4], c->stream));
@@ -347,6 +360,9 @@ void record_stage_times(lr_context* c, bool with_groups) {
         (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[6]);
         c->stage_ms[LR_T_TOTAL] = ms;
     }
+    // (lr_stage_fit behind a frame call that ran untimed: the earlier stages' events were never recorded, and the refusal
+    // must not stay behind as the thread's last error for the next launch to find)
+    (void)hipGetLastError();
 }
 
 // The seed sort's capacity follows the frames: kept between 1.25 and 3 times the last frame's seed count (launches of
@@ -457,6 +473,9 @@ int run_frame(lr_context* c, const void* d_image, int format, int w, int h, int 
     out.clear();
     const double t_begin = now_ms();
     const bool fused = !refine && c->opt.estimator == 0;
+    // The fused path's next launch after the fit is the length test: components that cannot pass it are not fitted at all.
+    // (Everything else reads ALL raw segments -- refine merges short ones before the length test -- and fits them all.)
+    const int fit_min = fused && c->opt.fit_prune ? fit_min_for(min_length) : kComponentMinSize;
     const int n_iter = c->opt.ransac_iters;
     auto groups_after_fit = [&]() -> int {
         const uint32_t lc = line_cap_for(c);
@@ -464,7 +483,7 @@ int run_frame(lr_context* c, const void* d_image, int format, int w, int h, int 
         if (ensure_result_block(c, std::max<size_t>(c->res_lines_cap, 4096))) return 1;
         if (c->opt.timing_on) LR_HIP(hipEventRecord(c->ev[5], c->stream));
         const PencilTable all = table_of(c, 0), round0 = table_of(c, 1);
-        if (launch_filter_lines(c->ws.d_lines, c->d_counts + kCntComp, lc, min_length, c->d_flines, c->d_gctl, c->d_gnorm, &all, &round0,
+        if (launch_filter_lines(c->ws.d_lines, c->d_counts + kCntFitComp, c->d_counts + kCntComp, lc, min_length, c->d_flines, c->d_gctl, c->d_gnorm, &all, &round0,
                                 c->stream))
             return 1;
         static_assert(kMaxModels >= 1 && kGcWords == 8 && kResHeaderBytes == 256, "the last peeling round carries the result block (peel_kernel)");
@@ -486,7 +505,7 @@ int run_frame(lr_context* c, const void* d_image, int format, int w, int h, int 
         if (!(filter_enqueued && attempt == 0) && enqueue_filter(c, d_image, format, w, h, stride)) return 1;
         if (enqueue_seeds(c)) return 1;
         if (enqueue_flood(c)) return 1;
-        if (enqueue_fit(c)) return 1;
+        if (enqueue_fit(c, fit_min)) return 1;
         if (after_fit()) return 1;
         const double t_enq = now_ms();
         const double t_pre = now_ms();
@@ -512,7 +531,7 @@ int run_frame(lr_context* c, const void* d_image, int format, int w, int h, int 
     if (finish_flood(c, &extra)) return 1;
     if (extra) {  // the label image changed after the fit ran: the stages after the flood again
         c->frame_laps += 1;
-        if (enqueue_fit(c)) return 1;
+        if (enqueue_fit(c, fit_min)) return 1;
         if (after_fit()) return 1;
         LR_HIP(hipStreamSynchronize(c->stream));
     }
@@ -521,7 +540,10 @@ int run_frame(lr_context* c, const void* d_image, int format, int w, int h, int 
     c->n_px = cnt[kCntPx];
     adapt_seed_cap(c, c->n_seeds);
     c->stage_valid[0] = c->stage_valid[1] = false;
-    c->stage_valid[2] = c->stage_valid[3] = true;
+    c->stage_valid[2] = true;
+    // (after a pruned fit d_lines holds a part of the raw segments: whoever wants them all runs lr_stage_fit, which fits every
+    // component of the label image that is still there)
+    c->stage_valid[3] = fit_min == kComponentMinSize;
     if (fused) {
         const uint32_t* gctl = reinterpret_cast<const uint32_t*>(c->h_res + 32);
         const size_t n = gctl[kGcLines];

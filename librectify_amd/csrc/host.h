@@ -30,8 +30,9 @@ struct JoinedThreads {
     ~JoinedThreads() { join(); }
 };
 
-// d_counts words
-enum { kCntSeeds = 0, kCntComp = 1, kCntPx = 2, kCntLarge = 4 };
+// d_counts words (kCntLarge: seven words of the component lists, kernels_fit.hip; kCntFitComp, kCntFitPx: the components and
+// pixels that the fit stage worked on -- kCntComp and kCntPx again unless the frame's fit was pruned)
+enum { kCntSeeds = 0, kCntComp = 1, kCntPx = 2, kCntLarge = 4, kCntFitComp = 12, kCntFitPx = 13 };
 
 // context.hip
 int ensure_flood_buffers(lr_context* c);

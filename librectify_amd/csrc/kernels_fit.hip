@@ -39,13 +39,19 @@ constexpr uint32_t kHugeFlag = 0x80000000u;  // cursor[component]: the component
 constexpr int kOffPer = 8;
 constexpr uint32_t kOffChunk = 256 * kOffPer;
 
-__device__ __forceinline__ void chunk_counts(const int32_t* __restrict__ seed_size, uint32_t n_seeds, int min_size,
-                                             uint32_t k0, int (&sz)[kOffPer], uint32_t& c, uint32_t& p) {
-    c = p = 0;
+// (c, p): the floods that get a component -- more than `fit_min` pixels; (rc, rp): all floods of more than `min_size` pixels,
+// what the frame reports as its components (fit_min >= min_size: the same unless the caller prunes, see below)
+__device__ __forceinline__ void chunk_counts(const int32_t* __restrict__ seed_size, uint32_t n_seeds, int min_size, int fit_min,
+                                             uint32_t k0, int (&sz)[kOffPer], uint32_t& c, uint32_t& p, uint32_t& rc, uint32_t& rp) {
+    c = p = rc = rp = 0;
 #pragma unroll
     for (int j = 0; j < kOffPer; ++j) {
         sz[j] = (k0 + j < n_seeds) ? seed_size[k0 + j] : 0;
         if (sz[j] > min_size) {
+            rc += 1u;
+            rp += (uint32_t)sz[j];
+        }
+        if (sz[j] > fit_min) {
             c += 1u;
             p += (uint32_t)sz[j];
         }
@@ -59,24 +65,38 @@ __device__ __forceinline__ void chunk_counts(const int32_t* __restrict__ seed_si
 // order and none waits for a later one; the wait is bounded all the same).  Chunk 0 clears the list counters (n_large) before
 // it publishes -- with release order, the one fence of the launch -- and nobody touches them before having seen its words.
 // `status`: two words per chunk, zero when allocated; tags start at 1 and differ from frame to frame.
+//
+// Pruning (`fit_min` > `min_size`; the fused frame path, frame.hip: enqueue_fit).  The launch after the fit keeps a segment only
+// if it is longer than ml = max(min_length, kLineMinLength).  A segment's ends are the extreme projections of its component's
+// pixel centres on a unit axis (fit_kernel: t0, t1), so its length is at most the largest distance between two pixels of the
+// component, and two pixels of an 8-connected set of n pixels are joined by a chain of at most n - 1 steps of at most sqrt(2):
+// length <= (n - 1) * sqrt(2).  A flood of n <= fit_min = floor(ml / 1.4157) pixels therefore has
+// (n - 1) * sqrt(2) < n * 1.41422 <= ml * (1.41422 / 1.4157) = 0.9990 ml, less sqrt(2): the divisor's 0.1 % over sqrt(2) and the
+// step from n to n - 1 leave more than a pixel between the bound and ml, against float rounding of the axis and the ends of a few
+// 1e-4 of a pixel at these coordinates.  Such a flood cannot survive the length test whatever its shape, and gets no component:
+// comp_rank = kNoComp, no offset, slot, list entry or cursor -- the scatter, sort and fit launches never see it.  The scan and the
+// look-back chain run on the components that are left (`fit_totals`); what the frame REPORTS stays the count of all floods
+// beyond min_size (`totals`: result header, stage counters, the "fewer than two raw segments" exit of the next launch): every
+// workgroup adds its chunk's share to the two words, fire and forget -- chunk 0 clears them with the list counters, and the
+// next launch reads them.
 __global__ __launch_bounds__(256) void component_offsets_kernel(const int32_t* __restrict__ seed_size,
                                                                 const uint32_t* __restrict__ n_ptr, uint32_t cap,
-                                                                int min_size, unsigned long long* __restrict__ status, uint32_t tag,
+                                                                int min_size, int fit_min, unsigned long long* __restrict__ status, uint32_t tag,
                                                                 uint32_t* __restrict__ comp_rank,
                                                                 uint32_t* __restrict__ comp_seed,
                                                                 uint32_t* __restrict__ comp_off,
-                                                                uint32_t* __restrict__ totals,
+                                                                uint32_t* __restrict__ totals, uint32_t* __restrict__ fit_totals,
                                                                 uint32_t* __restrict__ large_list,
                                                                 uint32_t large_cap, uint32_t* __restrict__ n_large,
                                                                 uint32_t* __restrict__ cursor, uint32_t* __restrict__ huge_list,
                                                                 uint32_t huge_max) {
-    __shared__ uint32_t s_c[4], s_p[4], s_cc[4], s_cp[4];
+    __shared__ uint32_t s_c[4], s_p[4], s_cc[4], s_cp[4], s_rc[4], s_rp[4];
     const uint32_t n_seeds = min(*n_ptr, cap);
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const uint32_t k0 = blockIdx.x * kOffChunk + (uint32_t)tid * kOffPer;
     int sz[kOffPer];
-    uint32_t c, p;
-    chunk_counts(seed_size, n_seeds, min_size, k0, sz, c, p);
+    uint32_t c, p, rc, rp;
+    chunk_counts(seed_size, n_seeds, min_size, fit_min, k0, sz, c, p, rc, rp);
     uint32_t ic = c, ip = p;  // inclusive scan inside the wave
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {
@@ -87,9 +107,16 @@ __global__ __launch_bounds__(256) void component_offsets_kernel(const int32_t* _
             ip += tp;
         }
     }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        rc += (uint32_t)__shfl_xor((int)rc, off);
+        rp += (uint32_t)__shfl_xor((int)rp, off);
+    }
     if (lane == 63) {
         s_c[wv] = ic;
         s_p[wv] = ip;
+        s_rc[wv] = rc;
+        s_rp[wv] = rp;
     }
     __syncthreads();
     if (tid == 0) {
@@ -99,6 +126,8 @@ __global__ __launch_bounds__(256) void component_offsets_kernel(const int32_t* _
         if (blockIdx.x == 0) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) __hip_atomic_store(&n_large[i], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&totals[0], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&totals[1], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(&status[0], wc, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(&status[1], wp, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
         } else {
@@ -131,6 +160,13 @@ __global__ __launch_bounds__(256) void component_offsets_kernel(const int32_t* _
         s_cp[wv] = cp;
     }
     __syncthreads();
+    if (tid == 0) {  // (behind chunk 0's clearing of the words, like the atomics on n_large below)
+        const uint32_t wrc = s_rc[0] + s_rc[1] + s_rc[2] + s_rc[3], wrp = s_rp[0] + s_rp[1] + s_rp[2] + s_rp[3];
+        if (wrc != 0u) {
+            __hip_atomic_fetch_add(&totals[0], wrc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_add(&totals[1], wrp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
     uint32_t rank = s_cc[0] + s_cc[1] + s_cc[2] + s_cc[3] + ic - c;
     uint32_t off_px = s_cp[0] + s_cp[1] + s_cp[2] + s_cp[3] + ip - p;
     for (int i = 0; i < wv; ++i) {
@@ -141,7 +177,7 @@ __global__ __launch_bounds__(256) void component_offsets_kernel(const int32_t* _
     for (int j = 0; j < kOffPer; ++j) {
         const uint32_t k = k0 + j;
         if (k < n_seeds) {
-            const bool keep = sz[j] > min_size;
+            const bool keep = sz[j] > fit_min;
             comp_rank[k] = keep ? rank : kNoComp;
             if (keep) {
                 comp_seed[rank] = k;
@@ -167,8 +203,8 @@ __global__ __launch_bounds__(256) void component_offsets_kernel(const int32_t* _
         }
     }
     if (blockIdx.x == gridDim.x - 1 && tid == 255) {  // the last thread of the last chunk ends on the grand totals
-        totals[0] = rank;
-        totals[1] = off_px;
+        fit_totals[0] = rank;
+        fit_totals[1] = off_px;
         comp_off[rank] = off_px;
     }
 }
@@ -883,8 +919,8 @@ size_t fit_temp_bytes(size_t max_pixels, uint32_t max_segments) {
     return (max_pixels / kOffChunk + 2) * 2 * sizeof(unsigned long long) + 256;
 }
 
-int launch_component_offsets(const int32_t* seed_size, const uint32_t* d_n_seeds, uint32_t seed_cap, int min_size,
-                             uint32_t* comp_rank, uint32_t* comp_seed, uint32_t* comp_off, uint32_t* totals,
+int launch_component_offsets(const int32_t* seed_size, const uint32_t* d_n_seeds, uint32_t seed_cap, int min_size, int fit_min,
+                             uint32_t* comp_rank, uint32_t* comp_seed, uint32_t* comp_off, uint32_t* totals, uint32_t* fit_totals,
                              uint32_t* large_list, uint32_t large_cap, uint32_t* n_large, void* temp, size_t temp_bytes,
                              uint32_t frame_tag, uint32_t* cursor, const HugeSort& hs, hipStream_t s) {
     const uint32_t chunks = (seed_cap + kOffChunk - 1) / kOffChunk;
@@ -892,8 +928,12 @@ int launch_component_offsets(const int32_t* seed_size, const uint32_t* d_n_seeds
         set_error("launch_component_offsets: workspace too small");
         return 1;
     }
-    hipLaunchKernelGGL(component_offsets_kernel, dim3(chunks), dim3(256), 0, s, seed_size, d_n_seeds, seed_cap, min_size,
-                       static_cast<unsigned long long*>(temp), frame_tag, comp_rank, comp_seed, comp_off, totals, large_list, large_cap,
+    if (fit_min < min_size) {
+        set_error("launch_component_offsets: fit threshold below the size threshold");
+        return 1;
+    }
+    hipLaunchKernelGGL(component_offsets_kernel, dim3(chunks), dim3(256), 0, s, seed_size, d_n_seeds, seed_cap, min_size, fit_min,
+                       static_cast<unsigned long long*>(temp), frame_tag, comp_rank, comp_seed, comp_off, totals, fit_totals, large_list, large_cap,
                        n_large, cursor, hs.list, hs.tab ? hs.max : 0u);
     LR_HIP(hipGetLastError());
     return 0;

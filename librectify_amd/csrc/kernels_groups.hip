@@ -71,8 +71,11 @@ __device__ __forceinline__ void pencil_model_of(const LineSegment& l, uint32_t i
 // ---- filter_lines + bounding box ----------------------------------------------------------------------------
 // One workgroup: stable compaction of the fitted segments that are long and straight enough, then the bounding box of
 // what is left (min / max are exact whatever the order).  gctl: see GroupCtl in common.h.
+// `raw` holds the n_fit segments that were fitted, in seed order; the frame has *n_all_ptr components (more, when the fit left
+// out those too small to pass the length test here: kernels_fit.hip, component_offsets_kernel), and the exit below is theirs.
 __global__ __launch_bounds__(kWG) void filter_lines_kernel(const LineSegment* __restrict__ raw,
-                                                           const uint32_t* __restrict__ n_raw_ptr, uint32_t raw_cap,
+                                                           const uint32_t* __restrict__ n_fit_ptr,
+                                                           const uint32_t* __restrict__ n_all_ptr, uint32_t raw_cap,
                                                            float min_length, LineSegment* __restrict__ out,
                                                            uint32_t* __restrict__ gctl, float* __restrict__ gnorm,
                                                            PencilTable all, PencilTable round0, uint32_t with_model) {
@@ -82,11 +85,12 @@ __global__ __launch_bounds__(kWG) void filter_lines_kernel(const LineSegment* __
     constexpr int kFlB = 8;
     __shared__ uint32_t s_cnt[kFlB][kWaves];
     __shared__ float s_red[4][kWaves];
-    const uint32_t n_raw = min(*n_raw_ptr, raw_cap);
+    const uint32_t n_raw = min(*n_fit_ptr, raw_cap);
+    const uint32_t n_all = min(*n_all_ptr, raw_cap);
     const float ml = fmaxf(min_length, kLineMinLength);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     uint32_t base = 0;
-    if (n_raw >= 2u) {  // interface.cpp:50-54: fewer than two raw segments -> nothing
+    if (n_all >= 2u) {  // interface.cpp:50-54: fewer than two raw segments -> nothing
         for (uint32_t i0 = 0; i0 < n_raw; i0 += kWG * kFlB) {
             LineSegment l[kFlB];
             uint64_t m[kFlB];
@@ -518,11 +522,11 @@ __global__ __launch_bounds__(kWG) void peel_kernel(PencilTable cur, PencilTable 
 
 }  // namespace
 
-int launch_filter_lines(const LineSegment* raw, const uint32_t* d_n_raw, uint32_t raw_cap, float min_length,
+int launch_filter_lines(const LineSegment* raw, const uint32_t* d_n_fit, const uint32_t* d_n_raw, uint32_t raw_cap, float min_length,
                         LineSegment* out, uint32_t* gctl, float* gnorm, const PencilTable* all, const PencilTable* round0,
                         hipStream_t s) {
     const bool with_model = all != nullptr && round0 != nullptr;
-    hipLaunchKernelGGL(filter_lines_kernel, dim3(1), dim3(kWG), 0, s, raw, d_n_raw, raw_cap, min_length, out, gctl, gnorm,
+    hipLaunchKernelGGL(filter_lines_kernel, dim3(1), dim3(kWG), 0, s, raw, d_n_fit, d_n_raw, raw_cap, min_length, out, gctl, gnorm,
                        with_model ? *all : PencilTable{}, with_model ? *round0 : PencilTable{}, with_model ? 1u : 0u);
     LR_HIP(hipGetLastError());
     return 0;
