@@ -932,6 +932,54 @@ static inline int lr_jpeg_info(const void* h_src, size_t src_bytes, const double
     return lr_decode_jpeg_device((lr_context*)0, (const void*)0, h_src, src_bytes, LR_PIX_U8X3, frames, batch, (void*)0, 0, info);
 }
 
+/* The commonest reader of a rectified picture is a network: lr_pack_tensor_device letterboxes finished 8-bit pictures that
+ * lie in HBM into the slots of one contiguous batch tensor in HBM, converted, normalised and transposed, so that a model
+ * reads its input where it lies.  The pass stands BEHIND the warp as the encoder does (the same pictures can go to both);
+ * one launch for the whole batch; the call is SYNCHRONOUS like the encoder's: it waits for the context's stream, and on
+ * return the tensor may be read from any stream.
+ * format is LR_PIX_U8 (C = 1 channel, or C = 3 with LR_TENSOR_GRAY3) or LR_PIX_U8X3 (C = 3).  The tensor lies at d_dst (4-byte
+ * aligned), contiguous, n x C x height x width (LR_TENSOR_NCHW) or n x height x width x C (LR_TENSOR_NHWC) elements of
+ * `dtype`; dst_bytes is at least its size, and the destination region lies apart from the source region.
+ * `frames` is a HOST table of 8 doubles per frame: [0] [1] the picture's width_b, height_b (1 .. width, 1 .. height), [2] [3]
+ * byte offset of the picture from d_src and its row stride in bytes (at least a row), [4] its slot, 0 .. n - 1 (no two
+ * frames share one), [5] [6] left, top of the picture inside its slot (left + width_b <= width, top + height_b <= height),
+ * [7] reserved, 0.  The table follows LR_WARP_RAGGED's rules: integers (at most 2^53), every picture inside src_bytes.
+ * EVERY element of a slot that a frame names is written: the picture where it lies, the pad level elsewhere.  Slots that no
+ * frame names, and bytes behind the tensor, are not touched.
+ * The rule (tests/numpy_tensor_ref.py produces the same bytes): an element of channel c whose
+ * level is v (an integer 0 .. 255; pad[c] outside the picture) is p = v * scale[c] in double, y = p + bias[c] in double, f =
+ * (float)y rounded to nearest even, and for LR_TENSOR_F16 and LR_TENSOR_BF16 f rounded to nearest even once more (BF16 on
+ * the bits of f).  The host computes the 256 x C elements once per call; the kernel looks them up.  With LR_TENSOR_SWAP
+ * channel c reads source channel 2 - c (scale, bias and pad stay the TENSOR channel's).
+ * The whole call is checked before anything is enqueued: on failure nothing is launched or written and lr_last_error names
+ * the frame and the entry.  Refused: a null pointer, batch < 1 or > n, n, height or width below 1 (or a side above 2^30), a
+ * tensor beyond 2^53 bytes or beyond dst_bytes, an unknown dtype, layout or flag bit, LR_TENSOR_GRAY3 with LR_PIX_U8X3,
+ * LR_TENSOR_SWAP with one channel, another source format, a non-finite scale or bias, a level of a channel whose element is
+ * not finite in the dtype, a pad that is no integer 0 .. 255, a table entry that is no integer in its range, a picture
+ * outside its slot or outside src_bytes, two frames in one slot, overlapping regions, a misaligned d_dst.
+ * The frame records and the element table belong to the context's workspace: lr_context_trim frees them.
+ * The library's table of exported symbols is full, so the call travels through lr_warp_perspective_device like
+ * lr_encode_jpeg_device: LR_WARP_TENSOR or-ed into `format`, `M` pointing to an lr_tensor_args, src_image_bytes and
+ * dst_image_bytes the two regions' sizes, and width, height, out_width, out_height and both row strides 0 (any other option
+ * bit or a non-zero one of these fails cleanly).  lr_pack_tensor_device below is that call, spelled out. */
+enum lr_tensor_dtype { LR_TENSOR_F32 = 0, LR_TENSOR_F16 = 1, LR_TENSOR_BF16 = 2 };
+enum lr_tensor_layout { LR_TENSOR_NCHW = 0, LR_TENSOR_NHWC = 1 };
+enum lr_tensor_flags { LR_TENSOR_SWAP = 1,    /* channel c comes from source channel 2 - c (BGR nets) */
+                       LR_TENSOR_GRAY3 = 2 }; /* LR_PIX_U8 source into THREE channels, each through its own scale/bias */
+typedef struct lr_tensor_args {
+    const double* frames;     /* HOST, 8 doubles per frame */
+    int32_t n, height, width; /* slots N and the slot size H x W */
+    int32_t dtype, layout, flags;
+    double scale[3], bias[3]; /* per channel */
+    double pad[3];            /* per channel: the LEVEL (integer 0..255) of elements outside the picture */
+} lr_tensor_args;
+enum lr_warp_tensor { LR_WARP_TENSOR = 0x10000 }; /* or-ed into `format` like lr_warp_option */
+static inline int lr_pack_tensor_device(lr_context* ctx, const void* d_src, size_t src_bytes, int format, const lr_tensor_args* args,
+                                        int batch, void* d_dst, size_t dst_bytes) {
+    return lr_warp_perspective_device(ctx, d_src, src_bytes, batch, 0, 0, 0, format | LR_WARP_TENSOR, (const double*)(const void*)args,
+                                      d_dst, dst_bytes, 0, 0, 0);
+}
+
 /* ---- stage API (tests, bench) --------------------------------------------------------- */
 /* Stage 1: fused 5x5 derivative filter + magnitude + direction bin + dilated-bin mask +
  * 5x5 non-max candidates (reference line_detector.cpp:41-49,126-182, filter.cpp:29-98,161-168). */

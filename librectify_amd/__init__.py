@@ -75,6 +75,12 @@ class JpegDecodeArgs(C.Structure):  # lr_jpeg_decode_args
     _fields_ = [("h_src", C.c_void_p), ("frames", C.c_void_p), ("info", C.c_void_p)]
 
 
+class TensorArgs(C.Structure):  # lr_tensor_args
+    _fields_ = [("frames", C.c_void_p), ("n", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("dtype", C.c_int32),
+                ("layout", C.c_int32), ("flags", C.c_int32), ("scale", C.c_double * 3), ("bias", C.c_double * 3),
+                ("pad", C.c_double * 3)]
+
+
 BUF_DX, BUF_DY, BUF_DMASK, BUF_LABEL, BUF_SEED_IDX, BUF_SEED_BIN, BUF_SEED_THR, BUF_MAXMAG, BUF_SEED_SIZE = range(9)
 BUF_SEED_REC = 9  # uint32 (n_seeds, 4): index, bin, bits of the threshold, 0
 BUF_COUNTS = 10  # uint32 (16,): [0] seeds, [1] components, [2] their pixels, [12] components that were fitted, [13] their pixels
@@ -96,6 +102,10 @@ WARP_LENS = 0x100000  # enum lr_warp_lens, likewise: nine lens entries per frame
 WARP_LENS_MODEL = 0x800000  # enum lr_warp_lens_model, likewise and with WARP_LENS: seventeen lens entries per frame instead of nine (LensModel, lens= of the tables)
 LENS_RATIONAL, LENS_FISHEYE = 0, 1  # enum lr_lens_model: entry [16] of a frame's seventeen lens entries
 WARP_AREA = 0x400000  # enum lr_warp_area, likewise: a sampling factor S (1 .. 8) per frame at the very end of its row of the warp's table (area= of the tables)
+WARP_TENSOR = 0x10000  # enum lr_warp_tensor, likewise: lr_pack_tensor_device, whose own arguments travel behind M (TensorArgs)
+TENSOR_F32, TENSOR_F16, TENSOR_BF16 = range(3)  # enum lr_tensor_dtype
+TENSOR_NCHW, TENSOR_NHWC = range(2)  # enum lr_tensor_layout
+TENSOR_SWAP, TENSOR_GRAY3 = 1, 2  # enum lr_tensor_flags
 JPEG_OK, JPEG_NOT_JPEG, JPEG_UNSUPPORTED, JPEG_SIZE_MISMATCH, JPEG_DAMAGED = range(5)  # info[5] of lr_decode_jpeg_device
 FRAMES_U8, FRAMES_U8X3, FRAMES_F32 = 0x100, 0x200, 0x300  # enum lr_frames_option, or-ed into `refine` of the frame entries
 
@@ -876,6 +886,132 @@ def jpeg_table(sizes, sources, outputs, quality, layout=0, optimize=False):
     return table.astype(np.float64)
 
 
+def _three(v, what):
+    a = np.asarray(v, np.float64)
+    if a.shape not in ((), (3,)):
+        raise ValueError("TensorSpec: %s is one number or three" % what)
+    return np.broadcast_to(a, (3,)).astype(np.float64)
+
+
+class TensorSpec:
+    """What lr_pack_tensor_device makes of 8-bit pictures (lr_tensor_args without the frame table): size = (H, W) of a slot;
+    dtype "f32", "f16" or "bf16"; layout "nchw" or "nhwc"; mean and std per channel (one number or three) in units of 1,
+    torchvision's ToTensor followed by Normalize as TWO operations: scale_c = 1.0 / (255.0 * std_c) and bias_c = -mean_c /
+    std_c in float64, so that an element is (float)(v * scale_c + bias_c); scale= / bias= give the two directly instead;
+    pad: the LEVEL (integer 0 .. 255, one or three) of elements outside the picture; bgr: channel c comes from source channel
+    2 - c (LR_TENSOR_SWAP); gray3: a gray source into three channels (LR_TENSOR_GRAY3); place: "center" or "topleft", where
+    tensor_table puts a picture in its slot.  Needs no GPU."""
+    _DTYPES = {"f32": (TENSOR_F32, np.float32), "f16": (TENSOR_F16, np.float16), "bf16": (TENSOR_BF16, np.uint16)}
+    _LAYOUTS = {"nchw": TENSOR_NCHW, "nhwc": TENSOR_NHWC}
+
+    def __init__(self, size, dtype="f32", layout="nchw", mean=(0, 0, 0), std=(1, 1, 1), pad=0, bgr=False, gray3=False,
+                 place="center", scale=None, bias=None):
+        try:
+            self.height, self.width = int(size[0]), int(size[1])
+            ok = len(size) == 2 and self.height == size[0] and self.width == size[1]
+        except (TypeError, ValueError, IndexError):
+            ok = False
+        if not ok or self.height < 1 or self.width < 1 or max(self.height, self.width) > 2 ** 30:
+            raise ValueError("TensorSpec: size is (H, W), two integers from 1 to 2^30")
+        if dtype not in self._DTYPES:
+            raise ValueError('TensorSpec: dtype is "f32", "f16" or "bf16"')
+        if layout not in self._LAYOUTS:
+            raise ValueError('TensorSpec: layout is "nchw" or "nhwc"')
+        if place not in ("center", "topleft"):
+            raise ValueError('TensorSpec: place is "center" or "topleft"')
+        self.size, self.dtype, self.layout, self.place = (self.height, self.width), dtype, layout, place
+        self.bgr, self.gray3 = bool(bgr), bool(gray3)
+        mean, std = _three(mean, "mean"), _three(std, "std")
+        if not (np.isfinite(mean).all() and np.isfinite(std).all()) or (std == 0).any():
+            raise ValueError("TensorSpec: mean and std are finite, std not 0")
+        self.scale = np.float64(1.0) / (np.float64(255.0) * std) if scale is None else _three(scale, "scale")
+        self.bias = -mean / std if bias is None else _three(bias, "bias")
+        if not (np.isfinite(self.scale).all() and np.isfinite(self.bias).all()):
+            raise ValueError("TensorSpec: a non-finite scale or bias")
+        pad = _three(pad, "pad")
+        if not (np.isfinite(pad).all() and (pad == np.floor(pad)).all() and pad.min() >= 0 and pad.max() <= 255):
+            raise ValueError("TensorSpec: pad is an integer level from 0 to 255, one or three")
+        self.pad = pad
+
+    @property
+    def np_dtype(self):
+        """The NumPy type of the tensor's elements (uint16 bit patterns for "bf16")"""
+        return self._DTYPES[self.dtype][1]
+
+    def channels(self, fmt):
+        """C for a source of format fmt (PIX_U8, PIX_U8X3); ValueError for what the header refuses"""
+        if fmt not in (PIX_U8, PIX_U8X3):
+            raise ValueError("TensorSpec: the source is PIX_U8 or PIX_U8X3")
+        if self.gray3 and fmt != PIX_U8:
+            raise ValueError("TensorSpec: gray3 takes a gray source (PIX_U8)")
+        C_ = 3 if (fmt == PIX_U8X3 or self.gray3) else 1
+        if self.bgr and C_ == 1:
+            raise ValueError("TensorSpec: bgr needs three channels")
+        return C_
+
+    def shape(self, n, fmt):
+        """The tensor's shape for n slots and a source of format fmt"""
+        C_ = self.channels(fmt)
+        return (n, C_, self.height, self.width) if self.layout == "nchw" else (n, self.height, self.width, C_)
+
+    def args(self, table, n):
+        """lr_tensor_args for a frame table (which must stay alive during the call) and n slots"""
+        return TensorArgs(_ptr(table), n, self.height, self.width, self._DTYPES[self.dtype][0], self._LAYOUTS[self.layout],
+                          (TENSOR_SWAP if self.bgr else 0) | (TENSOR_GRAY3 if self.gray3 else 0),
+                          (C.c_double * 3)(*self.scale.tolist()), (C.c_double * 3)(*self.bias.tolist()), (C.c_double * 3)(*self.pad.tolist()))
+
+
+def fit_box(out_size, box):
+    """The bound N for which shrink_homography makes a picture of out_size = (ow, oh) fit a box = (W, H): the largest integer
+    N <= max(ow, oh) whose size rule (max(1, ow * N // longer), max(1, oh * N // longer)) lies inside W x H.  A picture that
+    fits already gives N = max(ow, oh): pictures are never enlarged.  Integer arithmetic only.
+    (ow * N // longer <= W exactly when N <= ((W + 1) * longer - 1) // ow.)"""
+    ow, oh, W, H = int(out_size[0]), int(out_size[1]), int(box[0]), int(box[1])
+    if ow < 1 or oh < 1 or W < 1 or H < 1:
+        raise ValueError("fit_box: a size below 1")
+    longer = max(ow, oh)
+    return min(longer, ((W + 1) * longer - 1) // ow, ((H + 1) * longer - 1) // oh)
+
+
+def tensor_table(sizes, sources, slots, spec):
+    """The table of lr_pack_tensor_device: sizes: B pairs (width, height) of the pictures; sources: B pairs (byte_offset,
+    row_bytes) of the pictures in the source region; slots: B slot numbers, no two alike; spec: the TensorSpec, whose place
+    puts a picture in its slot ("center": left = (W - w) // 2, top = (H - h) // 2; "topleft": 0, 0).  Returns float64 (B, 8):
+    width, height, source offset and stride, slot, left, top, 0.  Rejects what can be seen without the regions: a picture
+    below 1 or larger than the slot, entries below 0 or above 2^53, a slot named twice.  Needs no GPU."""
+    sz = np.asarray(sizes)
+    if sz.ndim != 2 or sz.shape[1] != 2 or not np.issubdtype(sz.dtype, np.integer) or len(sz) < 1:
+        raise ValueError("tensor_table: sizes is B pairs of integers (width, height), B >= 1")
+    B = len(sz)
+    src, sl = np.asarray(sources), np.asarray(slots)
+    if src.shape != (B, 2) or not np.issubdtype(src.dtype, np.integer):
+        raise ValueError("tensor_table: sources is B pairs of integers")
+    if sl.shape != (B,) or not np.issubdtype(sl.dtype, np.integer):
+        raise ValueError("tensor_table: slots is B integers")
+    sz, src, sl = sz.astype(np.int64), src.astype(np.int64), sl.astype(np.int64)
+    if min(int(src.min()), int(sl.min())) < 0 or max(int(src.max()), int(sl.max())) > 2 ** 53:
+        raise ValueError("tensor_table: an entry below 0 or above 2^53")
+    if int(sz.min()) < 1:
+        raise ValueError("tensor_table: a size below 1")
+    if int(sz[:, 0].max()) > spec.width or int(sz[:, 1].max()) > spec.height:
+        raise ValueError("tensor_table: a picture larger than the slot")
+    if len(set(sl.tolist())) != B:
+        raise ValueError("tensor_table: two frames in one slot")
+    table = np.zeros((B, 8), np.int64)
+    table[:, 0:2], table[:, 2:4], table[:, 4] = sz, src, sl
+    if spec.place == "center":
+        table[:, 5], table[:, 6] = (spec.width - sz[:, 0]) // 2, (spec.height - sz[:, 1]) // 2
+    return table.astype(np.float64)
+
+
+def tensor_map(M, left, top):
+    """The tensor map of a picture that the warp wrote with the destination-to-source map M (3 x 3) and that lies at (left,
+    top) of its slot: the map from a tensor pixel (x, y) of the slot to the coordinates the warp read from, M composed with
+    the translation by (-left, -top).  float64."""
+    T = np.array([[1.0, 0.0, -float(left)], [0.0, 1.0, -float(top)], [0.0, 0.0, 1.0]], np.float64)
+    return np.asarray(M, np.float64).reshape(3, 3) @ T
+
+
 def jpeg_decode_table(streams, outputs=None, sizes=None, orient=False, scale=None):
     """The table of lr_decode_jpeg_device: streams: B pairs (byte_offset, length) of the streams in the source region;
     outputs: B pairs (byte_offset, row_bytes) of the pictures in the destination region; sizes: B pairs (width, height)
@@ -1051,11 +1187,31 @@ def _bounded_map(M, size, out_max_size):
     factor (None: the picture as it is, S None)"""
     if out_max_size is None:
         return M, size, None
+    if isinstance(out_max_size, _FitBox):  # (tensor= of the rectify calls: the bound is the frame's own, fit_box of its size)
+        out_max_size = fit_box(size, out_max_size)
     _, M, size, S = shrink_homography(None, M, size, out_max_size)
     return M, size, S
 
 
+_FitBox = collections.namedtuple("_FitBox", "width height")  # in place of out_max_size inside the rectify calls: a box (W, H) that bounds every frame by fit_box
+
+
+def _check_tensor(what, tensor, tensor_out, out_max_size):
+    """tensor= and tensor_out= of the rectify calls: the bound that stands in for out_max_size (None without tensor=)"""
+    if tensor is None:
+        if tensor_out is not None:
+            raise ValueError("%s: tensor_out goes with tensor=" % what)
+        return out_max_size
+    if not isinstance(tensor, TensorSpec):
+        raise ValueError("%s: tensor is a TensorSpec" % what)
+    if out_max_size is not None:
+        raise ValueError("%s: out_max_size together with tensor= (the tensor's box is the bound)" % what)
+    return _FitBox(tensor.width, tensor.height)
+
+
 def _check_out_max_size(what, out_max_size):
+    if isinstance(out_max_size, _FitBox):
+        return
     if out_max_size is not None and (isinstance(out_max_size, (bool, np.bool_)) or not isinstance(out_max_size, (int, np.integer)) or out_max_size < 1):
         raise ValueError("%s: out_max_size is None or an integer >= 1" % what)
 
@@ -1470,6 +1626,103 @@ class Context:
         with Huffman tables of its own (LR_JPEG_OPTIMIZE)."""
         return self.encode_jpeg_batch([image_u8], quality, layout, optimize)[0]
 
+    # ---- network input tensors ----
+    def pack_tensor_device(self, d_src, src_bytes, fmt, table, spec, n, d_dst, dst_bytes):
+        """lr_pack_tensor_device (lr_warp_perspective_device with LR_WARP_TENSOR): the table's 8-bit pictures (fmt PIX_U8 or
+        PIX_U8X3) in the src_bytes at d_src, each letterboxed into its slot of the n-slot tensor of `spec` in the dst_bytes at
+        d_dst.  table: 8 doubles per frame (tensor_table).  Synchronous: on return the tensor may be read from any stream."""
+        table = np.ascontiguousarray(table, np.float64)
+        if table.ndim != 2 or table.shape[1] != 8 or len(table) < 1:
+            raise ValueError("pack_tensor_device: the table has 8 values per frame")
+        args = spec.args(table, int(n))
+        _check(lib().lr_warp_perspective_device(self._h, C.c_void_p(d_src), src_bytes, len(table), 0, 0, 0, fmt | WARP_TENSOR,
+                                                C.cast(C.byref(args), C.c_void_p), C.c_void_p(d_dst), dst_bytes, 0, 0, 0))
+
+    @staticmethod
+    def _pad_slot(spec, fmt):
+        """A slot of nothing but pad, by the rule restated in NumPy (the slot of a frame that has no picture)"""
+        C_ = spec.channels(fmt)
+        y = (spec.pad[:C_] * spec.scale[:C_] + spec.bias[:C_]).astype(np.float32)
+        if spec.dtype == "f16":
+            y = y.astype(np.float16)
+        elif spec.dtype == "bf16":
+            bits = y.view(np.uint32)
+            y = ((bits + np.uint32(0x7FFF) + ((bits >> np.uint32(16)) & np.uint32(1))) >> np.uint32(16)).astype(np.uint16)
+        shape = spec.shape(1, fmt)[1:]
+        return np.ascontiguousarray(np.broadcast_to(y.reshape((C_, 1, 1) if spec.layout == "nchw" else (1, 1, C_)), shape))
+
+    def _pack_resident(self, d_src, src_bytes, fmt, frames, spec, out=None):
+        """The tensor of resident pictures: frames[b] is (width, height, byte_offset, row_bytes) or None (a slot of pad), frame b
+        goes into slot b.  One lr_pack_tensor_device call; with out=None the tensor is downloaded (NumPy), otherwise `out` (an
+        object with data_ptr(), shape, dtype and is_contiguous(): a torch tensor on the context's device) is written in place
+        and returned."""
+        n = len(frames)
+        shape = spec.shape(n, fmt)
+        elem = np.dtype(spec.np_dtype).itemsize
+        total = int(np.prod(shape, dtype=np.int64)) * elem
+        if out is not None:
+            want = {"f32": "float32", "f16": "float16", "bf16": "bfloat16"}[spec.dtype]
+            if (not all(hasattr(out, a) for a in ("data_ptr", "shape", "dtype", "is_contiguous")) or tuple(out.shape) != shape
+                    or str(out.dtype).split(".")[-1] != want or not out.is_contiguous() or not getattr(out, "is_cuda", True)):
+                raise ValueError("pack_tensor: out is a contiguous device tensor of shape %r and dtype %s" % (shape, want))
+        named = [b for b in range(n) if frames[b] is not None]
+        d_dst = C.c_void_p(out.data_ptr()) if out is not None else C.c_void_p()
+        if out is None:
+            _check(lib().lr_device_malloc(self._h, total, C.byref(d_dst)))
+        try:
+            if named:
+                table = tensor_table(np.array([frames[b][:2] for b in named], np.int64), np.array([frames[b][2:] for b in named], np.int64),
+                                     np.array(named, np.int64), spec)
+                self.pack_tensor_device(d_src, src_bytes, fmt, table, spec, n, d_dst.value, total)
+            if len(named) < n:
+                slot = self._pad_slot(spec, fmt)
+                for b in range(n):
+                    if frames[b] is None:
+                        _check(lib().lr_memcpy_h2d(self._h, C.c_void_p(d_dst.value + b * slot.nbytes), _ptr(slot), slot.nbytes))
+            if out is not None:
+                return out
+            return self.device_download(d_dst.value, shape, spec.np_dtype)
+        finally:
+            if out is None:
+                self.device_free(d_dst.value)
+
+    def pack_tensor(self, pictures, spec, out=None, fmt=None):
+        """The network input tensor of a list of 8-bit pictures (all H x W, or all H x W x 3), each no larger than the slot of
+        `spec` (a TensorSpec): one upload, one lr_pack_tensor_device call, one download.  Picture b goes into slot b, placed as
+        spec.place says; an entry None gives a slot of nothing but pad (fmt= names the format when every entry is None).
+        Returns a NumPy array of the tensor's shape: float32, float16, or uint16 bit patterns for "bf16".  out=: a contiguous
+        torch tensor of that shape and dtype on the context's device (any object with data_ptr(), shape, dtype and
+        is_contiguous()) is written in place and returned, and nothing is downloaded; work that torch has enqueued on `out`
+        must be complete, since the pack runs on the context's stream."""
+        pics = [None if p is None else np.ascontiguousarray(p) for p in pictures]
+        if not pics:
+            raise ValueError("pack_tensor: no pictures")
+        formats = [_frame_format(p, "pack_tensor") for p in pics if p is not None]
+        if formats:
+            if formats[0][0] == PIX_F32 or any(f != formats[0] for f in formats) or (fmt is not None and fmt != formats[0][0]):
+                raise ValueError("pack_tensor: uint8 pictures, all H x W or all H x W x 3")
+            fmt = formats[0][0]
+        elif fmt is None:
+            raise ValueError("pack_tensor: no picture and no fmt=")
+        bpp = 3 if fmt == PIX_U8X3 else 1
+        spec.channels(fmt)
+        info, end = [], 0
+        for p in pics:
+            if p is None:
+                info.append(None)
+                continue
+            h, w = p.shape[:2]
+            if h > spec.height or w > spec.width:
+                raise ValueError("pack_tensor: a picture larger than the slot")
+            info.append((w, h, end, w * bpp))
+            end += p.nbytes
+        region = np.concatenate([p.reshape(-1) for p in pics if p is not None]) if formats else np.zeros(1, np.uint8)
+        d_src = self.device_upload(region)
+        try:
+            return self._pack_resident(d_src, max(end, 1), fmt, info, spec, out)
+        finally:
+            self.device_free(d_src)
+
     def decode_jpeg_device(self, d_src, h_src, fmt, table, d_dst, dst_bytes):
         """lr_decode_jpeg_device (lr_warp_perspective_device with LR_WARP_JPEG_DECODE): the table's baseline JPEG streams in
         the region at d_src (h_src: the same bytes on the host, a uint8 array; only the headers are read from it) become
@@ -1554,11 +1807,11 @@ class Context:
         return self.decode_jpeg_batch([data], fmt, orient, any_sampling, scale)[0]
 
     def _rectify_streams(self, streams, min_length, refine, cfg, clip, max_size, capacity, jpeg, orient=False, interp="linear", jpeg_optimize=False,
-                         any_sampling=False, border=None, crop=False, decode_scale=None, decode_max_size=None, lens=None, out_max_size=None):
+                         any_sampling=False, border=None, crop=False, decode_scale=None, decode_max_size=None, lens=None, out_max_size=None, tensor=None):
         """rectify_batch for JPEG files: the files go up and are decoded in HBM, the pictures are handed to
         rectify_frames_device where they lie; with jpeg=Q no pixel crosses the link in either direction"""
         d_src, _, fmt, sources = self._decode_resident(streams, None, "rectify_batch", orient, any_sampling, decode_scale, decode_max_size)
-        return self._rectify_resident(d_src, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp, jpeg_optimize, border, crop, lens, out_max_size)
+        return self._rectify_resident(d_src, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp, jpeg_optimize, border, crop, lens, out_max_size, tensor)
 
     def prepare_device(self, d_src, src_image_bytes, batch, width, height, src_row_bytes, fmt, d_dst, dst_image_bytes,
                        out_width, out_height, dst_row_bytes):
@@ -1621,7 +1874,7 @@ class Context:
 
     def rectify(self, image_u8, min_length=None, refine=False, cfg=None, clip=3.0, max_size=None, jpeg=None, orient=False,
                 interp="linear", jpeg_optimize=False, any_sampling=False, border=None, crop=False, decode_scale=None, decode_max_size=None,
-                lens=None, out_max_size=None, lens_scale=1):
+                lens=None, out_max_size=None, lens_scale=1, tensor=None, tensor_out=None):
         """The reference demo's pipeline (autorectify.cpp) on an 8-bit frame (H x W gray or H x W x 3 RGB): luma
         (4899 R + 9617 G + 1868 B + 8192) >> 14, / 256, find_line_segment_groups with min_length max(w, h) / 100 by
         default, compute_rectification_transform (cfg: the demo's, horizontal_vp_min_distance = 2),
@@ -1667,7 +1920,18 @@ class Context:
         WARP_AREA with shrink_homography's map, size and sampling factor S (applied after the crop where crop=True, whose
         rectangle stays in the uncropped full-size picture): every pixel is the mean of S x S samples over its footprint, taken
         from the stored frame in the one resampling there is, with the call's lens, interp and border; no full-size picture
-        exists in HBM.  Lines and transform do not change.  None: the call as it was."""
+        exists in HBM.  Lines and transform do not change.  None: the call as it was.
+        tensor=spec (a TensorSpec; with out_max_size=: ValueError): rectify_batch's tensor= for one frame.  The call returns
+        (result, tensor): result is the call's with out_max_size=fit_box(size, (W, H)) and the tensor map at its end, tensor
+        the one-slot tensor (pack_tensor's return; tensor_out= is its out=)."""
+        _check_tensor("rectify", tensor, tensor_out, out_max_size)
+        if tensor is not None:
+            batch = [bytes(image_u8)] if isinstance(image_u8, (bytes, bytearray, memoryview)) else np.asarray(image_u8)[None]
+            res, packed = self.rectify_batch(batch, min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, jpeg=jpeg, orient=orient, interp=interp, jpeg_optimize=jpeg_optimize, any_sampling=any_sampling, border=border, crop=crop,
+                                             decode_scale=decode_scale, decode_max_size=decode_max_size, lens=lens, lens_scale=lens_scale, tensor=tensor, tensor_out=tensor_out)
+            if res[0][2] is None:
+                _rectified_map(res[0][1], clip, crop, _sampling_bit(interp, "rectify"))  # (raises what rectify raises for such a frame)
+            return res[0], packed
         cubic = _sampling_bit(interp, "rectify")
         _check_jpeg_optimize("rectify", jpeg, jpeg_optimize)
         _check_out_max_size("rectify", out_max_size)
@@ -1991,8 +2255,23 @@ class Context:
             out[b] = s
         return out
 
+    def _tensor_of_warped(self, d_out, total, fmt, table, spec, tensor_out):
+        """tensor= of the rectify calls: the warped pictures at d_out (rows of `table`: columns 0..8 the launch's map, 9..12
+        width, height, offset, stride) packed where they lie, frame b into slot b (a frame without a picture: pad).  Returns
+        (tensor, maps): pack_tensor's return and per frame the tensor map (None without a picture)."""
+        frames = [tuple(int(v) for v in table[b, 9:13]) if table[b, 9] else None for b in range(len(table))]
+        packed = self._pack_resident(d_out or 0, total, fmt, frames, spec, tensor_out)
+        maps = []
+        for b, f in enumerate(frames):
+            if f is None:
+                maps.append(None)
+                continue
+            left, top = ((spec.width - f[0]) // 2, (spec.height - f[1]) // 2) if spec.place == "center" else (0, 0)
+            maps.append(tensor_map(table[b, :9], left, top))
+        return packed, maps
+
     def _rectify_mixed(self, frames, min_length, refine, cfg, clip, max_size, capacity, jpeg=None, interp="linear", jpeg_optimize=False, border=None, crop=False,
-                       lens=None, out_max_size=None):
+                       lens=None, out_max_size=None, tensor=None):
         """rectify_batch for a list of 8-bit frames of different shapes: all frames in one host buffer, one upload,
         rectify_frames_device, one download"""
         frames = [np.ascontiguousarray(f) for f in frames]
@@ -2010,20 +2289,27 @@ class Context:
         for f, (_, _, start, _) in zip(frames, sources):
             host[start: start + f.nbytes] = f.reshape(-1)
         _border_words(border, len(frames), fmt, "rectify_batch")  # (a bad spec: ValueError before anything goes up)
-        return self._rectify_resident(self.device_upload(host), sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp, jpeg_optimize, border, crop, lens, out_max_size)
+        return self._rectify_resident(self.device_upload(host), sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp, jpeg_optimize, border, crop, lens, out_max_size, tensor)
 
     def _rectify_resident(self, d_src, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp="linear", jpeg_optimize=False, border=None, crop=False,
-                          lens=None, out_max_size=None):
+                          lens=None, out_max_size=None, tensor=None):
         """rectify_batch for 8-bit frames (width, height, byte_offset, row_bytes) that lie at d_src, which is freed here:
-        rectify_frames_device, then one download of the pictures, or with jpeg the encoder and the streams alone"""
+        rectify_frames_device, then one download of the pictures, or with jpeg the encoder and the streams alone; with tensor
+        (the TensorSpec and tensor_out) the pictures are packed where they lie as well, every result gets its tensor map and
+        the return is (results, tensor)"""
         bpp = 3 if fmt == PIX_U8X3 else 1
         d_out = None
         try:
             lines, tfs, table, d_out, total, *more = self._rectify_frames(d_src, sources, fmt, min_length, refine, cfg, clip, max_size, capacity, interp, border, crop, lens, out_max_size)
             rect = (lambda b: (more[0][b],)) if crop else (lambda b: ())
+            with_tensor = lambda results: results  # noqa: E731
+            if tensor is not None:
+                packed_tensor, maps = self._tensor_of_warped(d_out, total, fmt, table, *tensor)
+                crop_rect, rect = rect, lambda b: crop_rect(b) + (maps[b],)
+                with_tensor = lambda results: (results, packed_tensor)  # noqa: E731
             if jpeg is not None:
                 streams = self._jpeg_results(d_out, total, fmt, table, jpeg, jpeg_optimize) if d_out else [None] * len(sources)
-                return [(lines[b], tfs[b], streams[b]) + rect(b) for b in range(len(sources))]
+                return with_tensor([(lines[b], tfs[b], streams[b]) + rect(b) for b in range(len(sources))])
             packed = self.device_download(d_out, (total,), np.uint8) if d_out else None
         finally:
             self.device_free(d_src)
@@ -2037,11 +2323,11 @@ class Context:
                 rows = np.lib.stride_tricks.as_strided(packed[off:], (oh, ow * bpp), (row, 1))
                 img = np.ascontiguousarray(rows).reshape((oh, ow) + ((3,) if bpp == 3 else ()))
             res.append((lines[b], tfs[b], img) + rect(b))
-        return res
+        return with_tensor(res)
 
     def rectify_batch(self, frames_u8, min_length=None, refine=False, cfg=None, clip=3.0, max_size=None, capacity=4096, jpeg=None,
                       orient=False, interp="linear", jpeg_optimize=False, any_sampling=False, border=None, crop=False, decode_scale=None,
-                      decode_max_size=None, lens=None, out_max_size=None, lens_scale=1):
+                      decode_max_size=None, lens=None, out_max_size=None, lens_scale=1, tensor=None, tensor_out=None):
         """Context.rectify for a batch: frames_u8 is a uint8 array [B, H, W] or [B, H, W, 3], or a list of such frames of one
         shape.  One upload, rectify_batch_device (one detector batch, the packed warp), one download.  Returns a
         list of (lines, transform, warped), frame by frame what rectify returns for it; warped is None for a frame whose
@@ -2082,9 +2368,20 @@ class Context:
         rectify's, for every frame whose lens is not None.
         out_max_size=N: every picture, or JPEG file, is at most N pixels on its longer side (WARP_AREA on the warp launch of
         whichever path is taken, after the crop and in front of the encoder) -- frame by frame what rectify(out_max_size=N)
-        returns.  The full-size pictures never exist: HBM holds, the link carries and the encoder reads the small ones."""
+        returns.  The full-size pictures never exist: HBM holds, the link carries and the encoder reads the small ones.
+        tensor=spec (a TensorSpec; with out_max_size=: ValueError, the tensor's box is the bound): the pictures become a
+        network's input in HBM as well.  After the crop every frame is bounded as out_max_size=fit_box(size_b, (W, H)) bounds
+        it, so that it fits the spec's H x W slot; the pictures stay in HBM, and one lr_pack_tensor_device call packs frame b
+        into slot b of a B-slot tensor (a frame without a picture: a slot of pad); jpeg=Q still encodes the same pictures.
+        The call then returns (results, tensor): results[b] is what rectify(frame_b, ..., out_max_size=fit_box(...)) returns
+        with one more entry at its end, the 3 x 3 float64 TENSOR MAP (None without a picture), which takes a tensor pixel (x,
+        y) of slot b to the coordinates the warp launch read from (that launch's map composed with the translation by
+        (-left, -top): tensor_map), so a network's boxes go back onto the photograph; tensor is pack_tensor's return, with
+        tensor_out= as its out= (a torch tensor on the context's device, written in place; nothing of it is downloaded)."""
+        out_max_size = _check_tensor("rectify_batch", tensor, tensor_out, out_max_size)
         _sampling_bit(interp, "rectify_batch")
         _check_out_max_size("rectify_batch", out_max_size)
+        packing = None if tensor is None else (tensor, tensor_out)
         _check_jpeg_optimize("rectify_batch", jpeg, jpeg_optimize)
         if lens is not None:
             if crop:
@@ -2104,13 +2401,13 @@ class Context:
             except ValueError:
                 _border_words(border, len(frames_u8), PIX_U8, "rectify_batch")
             return self._rectify_streams([bytes(f) for f in frames_u8], min_length, refine, cfg, clip, max_size, capacity, jpeg, orient, interp, jpeg_optimize,
-                                         any_sampling, border, crop, decode_scale, decode_max_size, lens, out_max_size)
+                                         any_sampling, border, crop, decode_scale, decode_max_size, lens, out_max_size, packing)
         if lens is not None:
-            return self._rectify_mixed(list(frames_u8), min_length, refine, cfg, clip, max_size, capacity, jpeg, interp, jpeg_optimize, border, crop, lens, out_max_size)
+            return self._rectify_mixed(list(frames_u8), min_length, refine, cfg, clip, max_size, capacity, jpeg, interp, jpeg_optimize, border, crop, lens, out_max_size, packing)
         if not isinstance(frames_u8, np.ndarray):
             frames_u8 = [np.asarray(f) for f in frames_u8]
             if len({f.shape for f in frames_u8}) > 1:
-                return self._rectify_mixed(frames_u8, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp, jpeg_optimize, border, crop, None, out_max_size)
+                return self._rectify_mixed(frames_u8, min_length, refine, cfg, clip, max_size, capacity, jpeg, interp, jpeg_optimize, border, crop, None, out_max_size, packing)
         a = np.ascontiguousarray(frames_u8 if isinstance(frames_u8, np.ndarray) else np.stack([np.asarray(f) for f in frames_u8]))
         if a.dtype != np.uint8 or a.ndim not in (3, 4) or (a.ndim == 4 and a.shape[3] != 3) or a.shape[0] < 1:
             raise ValueError("rectify_batch: uint8 frames [B, H, W] or [B, H, W, 3]")
@@ -2122,9 +2419,14 @@ class Context:
         try:
             lines, tfs, table, d_out, total, *more = self.rectify_batch_device(d_src, batch, w, h, fmt, min_length=min_length, refine=refine, cfg=cfg, clip=clip, max_size=max_size, capacity=capacity, interp=interp, border=border, crop=crop, out_max_size=out_max_size)
             rect = (lambda b: (more[0][b],)) if crop else (lambda b: ())
+            with_tensor = lambda results: results  # noqa: E731
+            if tensor is not None:
+                packed_tensor, maps = self._tensor_of_warped(d_out, total, fmt, table, tensor, tensor_out)
+                crop_rect, rect = rect, lambda b: crop_rect(b) + (maps[b],)
+                with_tensor = lambda results: (results, packed_tensor)  # noqa: E731
             if jpeg is not None:
                 streams = self._jpeg_results(d_out, total, fmt, table, jpeg, jpeg_optimize) if d_out else [None] * batch
-                return [(lines[b], tfs[b], streams[b]) + rect(b) for b in range(batch)]
+                return with_tensor([(lines[b], tfs[b], streams[b]) + rect(b) for b in range(batch)])
             packed = self.device_download(d_out, (total,), np.uint8) if d_out else None
         finally:
             self.device_free(d_src)
@@ -2138,7 +2440,7 @@ class Context:
                 rows = np.lib.stride_tricks.as_strided(packed[off:], (oh, ow * bpp), (row, 1))
                 img = np.ascontiguousarray(rows).reshape((oh, ow) + a.shape[3:])
             res.append((lines[b], tfs[b], img) + rect(b))
-        return res
+        return with_tensor(res)
 
     def set_seed_capacity(self, cap):
         lib().lr_set_seed_capacity(self._h, int(cap))

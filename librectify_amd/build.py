@@ -27,6 +27,7 @@ SOURCES = [
     "kernels_overlay.hip",
     "kernels_jpeg.hip",
     "kernels_jpeg_decode.hip",
+    "kernels_tensor.hip",
     "context.hip",
     "upload.hip",
     "frame.hip",

@@ -148,6 +148,12 @@ struct JpegDecodeStore {
     DeviceBuffer<unsigned long long> state;  // entry | exit | carry (two of them)
     DeviceBuffer<uint32_t> part;             // counts | tries | first block
 };
+
+// lr_pack_tensor_device (kernels_tensor.hip): a call's frame records, tile prefix table and the 256 x C elements (made per
+// call, sized by the call: cap() = bytes)
+struct TensorStore {
+    MirroredBuffer<unsigned char> block;
+};
 }  // namespace lramd
 
 struct lr_context {
@@ -262,6 +268,7 @@ struct lr_context {
     int flood_sched_order = 0;
     uint32_t flood_sched_seed = 0, flood_sched_width = 0;
     bool flood_sched_off = false;
+    lramd::TensorStore tensor;
 };
 
 namespace lramd {
@@ -364,6 +371,10 @@ int ctx_encode_jpeg(lr_context* c, const void* d_src, size_t src_bytes, int form
 // waits for the statuses); d_dst == NULL: the headers only, and then c may be NULL
 int ctx_decode_jpeg(lr_context* c, const void* d_src, const void* h_src, size_t src_bytes, int format, const double* frames,
                     int batch, void* d_dst, size_t dst_bytes, int32_t* info);
+// kernels_tensor.hip: lr_pack_tensor_device (validates the whole call, computes the elements' table on the host, uploads it with
+// the frame records, enqueues one launch and waits for the stream)
+int ctx_pack_tensor(lr_context* c, const void* d_src, size_t src_bytes, int format, const lr_tensor_args* args, int batch,
+                    void* d_dst, size_t dst_bytes);
 // bytes one frame spans: (rows - 1) * row_bytes + last_row_bytes; false if that does not fit in 64 bits
 inline bool frame_span(int rows, size_t row_bytes, size_t last_row_bytes, size_t* out) {
     size_t s;

@@ -66,6 +66,7 @@ int ctx_trim(lr_context* c, bool frames_too) {
         c->overlay = OverlayStore{};           // (sized by the most segments drawn in a call)
         c->jpeg = JpegStore{};                 // (coefficients and interval tables of the largest batch encoded)
         c->jpeg_decode = JpegDecodeStore{};    // (coefficients and part records of the largest batch decoded)
+        c->tensor = TensorStore{};             // (frame records of the largest batch packed, and the elements' table)
     }
     c->small_frames = 0;
     c->w = c->h = 0;

@@ -522,6 +522,7 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
         if (format & LR_WARP_LINES) return fail("LR_WARP_CUBIC together with LR_WARP_LINES (the lines picture samples nothing)");
         if (format & LR_WARP_JPEG) return fail("LR_WARP_CUBIC together with LR_WARP_JPEG (the encoder samples nothing)");
         if (format & LR_WARP_JPEG_DECODE) return fail("LR_WARP_CUBIC together with LR_WARP_JPEG_DECODE (the decoder samples nothing)");
+        if (format & LR_WARP_TENSOR) return fail("unknown option bits in format: LR_WARP_CUBIC together with LR_WARP_TENSOR (the pack samples nothing)");
         format &= ~LR_WARP_CUBIC;
     }
     // LR_WARP_BORDER: a border word per frame behind (LR_WARP_RAGGED: in) its row of M; likewise of the three warps alone
@@ -531,6 +532,7 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
         if (format & LR_WARP_LINES) return fail("LR_WARP_BORDER together with LR_WARP_LINES (the lines picture samples nothing)");
         if (format & LR_WARP_JPEG) return fail("LR_WARP_BORDER together with LR_WARP_JPEG (the encoder samples nothing)");
         if (format & LR_WARP_JPEG_DECODE) return fail("LR_WARP_BORDER together with LR_WARP_JPEG_DECODE (the decoder samples nothing)");
+        if (format & LR_WARP_TENSOR) return fail("unknown option bits in format: LR_WARP_BORDER together with LR_WARP_TENSOR (the pack samples nothing)");
         format &= ~LR_WARP_BORDER;
     }
     // LR_WARP_LENS: nine lens entries per frame at the end of its row of M; likewise of the three warps alone
@@ -541,6 +543,7 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
         if (format & LR_WARP_LINES) return fail("LR_WARP_LENS_MODEL together with LR_WARP_LINES (the lines picture samples nothing)");
         if (format & LR_WARP_JPEG) return fail("LR_WARP_LENS_MODEL together with LR_WARP_JPEG (the encoder samples nothing)");
         if (format & LR_WARP_JPEG_DECODE) return fail("LR_WARP_LENS_MODEL together with LR_WARP_JPEG_DECODE (the decoder samples nothing)");
+        if (format & LR_WARP_TENSOR) return fail("unknown option bits in format: LR_WARP_LENS_MODEL together with LR_WARP_TENSOR (the pack samples nothing)");
         if (!(format & LR_WARP_LENS)) return fail("LR_WARP_LENS_MODEL without LR_WARP_LENS (it widens that bit's lens entries)");
         format &= ~LR_WARP_LENS_MODEL;
     }
@@ -550,6 +553,7 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
         if (format & LR_WARP_LINES) return fail("LR_WARP_LENS together with LR_WARP_LINES (the lines picture samples nothing)");
         if (format & LR_WARP_JPEG) return fail("LR_WARP_LENS together with LR_WARP_JPEG (the encoder samples nothing)");
         if (format & LR_WARP_JPEG_DECODE) return fail("LR_WARP_LENS together with LR_WARP_JPEG_DECODE (the decoder samples nothing)");
+        if (format & LR_WARP_TENSOR) return fail("unknown option bits in format: LR_WARP_LENS together with LR_WARP_TENSOR (the pack samples nothing)");
         format &= ~LR_WARP_LENS;
     }
     // LR_WARP_AREA: a sampling factor per frame at the very end of its row of M; likewise of the three warps alone
@@ -559,6 +563,7 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
         if (format & LR_WARP_LINES) return fail("LR_WARP_AREA together with LR_WARP_LINES (the lines picture samples nothing)");
         if (format & LR_WARP_JPEG) return fail("LR_WARP_AREA together with LR_WARP_JPEG (the encoder samples nothing)");
         if (format & LR_WARP_JPEG_DECODE) return fail("LR_WARP_AREA together with LR_WARP_JPEG_DECODE (the decoder samples nothing)");
+        if (format & LR_WARP_TENSOR) return fail("unknown option bits in format: LR_WARP_AREA together with LR_WARP_TENSOR (the pack samples nothing)");
         format &= ~LR_WARP_AREA;
     }
     if (format & LR_WARP_JPEG_DECODE) {  // lr_decode_jpeg_device (kernels_jpeg_decode.hip): its own arguments arrive behind M
@@ -589,6 +594,13 @@ int ctx_warp_perspective(lr_context* c, const void* d_src, size_t src_image_byte
         const lr_draw_lines_args* a = reinterpret_cast<const lr_draw_lines_args*>(M);
         return ctx_draw_lines(c, d_src, src_image_bytes, format & 0xFF, a->lines, a->n_lines, a->frames, batch, a->H, d_dst,
                               dst_image_bytes);
+    }
+    if (format & LR_WARP_TENSOR) {  // lr_pack_tensor_device (kernels_tensor.hip): its own arguments arrive behind M
+        if ((format & ~0xFF) != LR_WARP_TENSOR) return fail("unknown option bits in format: LR_WARP_TENSOR together with another option bit");
+        if (width != 0 || height != 0 || src_row_bytes != 0 || out_width != 0 || out_height != 0 || dst_row_bytes != 0)
+            return fail("unknown option bits in format for a warp; as LR_WARP_TENSOR: width, height, out_width, out_height and the row strides must be 0 (they are in the frame table)");
+        if (!M) return fail("LR_WARP_TENSOR: null pointer (lr_tensor_args)");
+        return ctx_pack_tensor(c, d_src, src_image_bytes, format & 0xFF, reinterpret_cast<const lr_tensor_args*>(M), batch, d_dst, dst_image_bytes);
     }
     if (format & LR_WARP_RAGGED) {  // every frame its own source and output: one table for the warp and the prepare step
         const int opts = format & ~0xFF;
